@@ -11,7 +11,7 @@ Workloads (--workload; BASELINE.json configs, reference lines under /root/refere
   c4  final_scene main.rs:635-795, arm :916-936, 800x800, 10 000 spp (the reference's own size; --spp to shorten)
   c5  Cornell box 3840x2160 (16:9), --spp (default 1000; BASELINE names 10 000 = 22 s per step per GPU)
 
-  N = 1  one GPU renders the whole frame into a pinned host frame (rt1w_render, RT1W_OUT_FRAME).  The c3 line also carries
+  N = 1  one GPU renders the whole frame into a pinned host frame (rt1w_render, RT1W_OUT_FRAME).  Under --full the c3 line also carries
          `other_configs`: C2 at full size and C4 at 400 spp measured the same way (D2H-inclusive Mpaths/s, kernel ms,
          segments/path, roofline block), each on three trees: the default build (c2, c4: BVHNode::new with the split axis chosen,
          RT1W_BVH_BEST_AXIS), the axes drawn from build seed 1 (c2_drawn_axes, c4_drawn_axes: rounds 1-3's default) and the opt-in
@@ -24,7 +24,7 @@ Workloads (--workload; BASELINE.json configs, reference lines under /root/refere
          and constant camera -- side = 16N*round(600*sqrt(N)/16N): 600, 864, 1216, 1664, a whole number of 16-row strips per
          GPU -- so every GPU keeps C3's 3.6e8 paths per step within 4 %.  --strong keeps 600x600 for all N.
          c2 / c4 / c5 are one fixed frame each (BASELINE: "tiled across 8 MI355X"): strong scaling.
-         The default N > 1 line (c3, weak) also carries `other_configs` = BASELINE's two multi-GPU configs as strong-scaling jobs of
+         Under --full the default N > 1 line (c3, weak) also carries `other_configs` = BASELINE's two multi-GPU configs as strong-scaling jobs of
          the same N ranks: `c5_strong` (Cornell 3840x2160, 1000 spp per step instead of 10 000) and `c4_strong` (final_scene 800x800,
          400 spp instead of 10 000), each with the D2H-inclusive rate, per-rank kernel ms (min / max: the strips' load balance),
          `n_ranks_seen`, and `gathered_frame_equals_single_gpu_frame` under --check-frame.
@@ -36,6 +36,15 @@ non-zero if any child does.  Under `python -m torch.distributed.run` (WORLD_SIZE
 
 `value` = whole-job paths / s over the timed steps, copy included.  The device-resident rate (framebuffer left in HBM)
 is reported as `value_device_resident`, never as `value`.
+
+A plain run measures the headline only: set-up, --warmup steps, --steps timed steps, the result line (`ms_per_step` = wall ms of
+one timed step).  Everything that takes runs of its own -- `value_device_resident`, `other_configs` (N = 1 and N > 1) and
+`cpu_baseline` -- is measured only under --full.
+
+--dump-outputs DIR writes what the timed path computed in its last step, after the timing: the gathered float64 frame as
+DIR/frame.npy (H x W x 3, the framebuffer Context.render returns), or, for a frame above DUMP_BUDGET_BYTES, DIR/frame_sample.npy:
+the pixels at a fixed seeded sample of positions (dump_sample_index).  The scene (build seed 1) and the sample stream are fixed,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import importlib
@@ -71,6 +80,7 @@ OTHER_CONFIGS = (("c2", "c2", 500, "best_axis", "reference"), ("c4", "c4", 400, 
 # carried by the default N > 1 line: BASELINE's two multi-GPU configs, tiled over the same ranks (entry, workload, spp per step, steps)
 OTHER_CONFIGS_MULTI = (("c5_strong", "c5", 1000, 2), ("c4_strong", "c4", 400, 3))
 DEFAULT_BVH = "best_axis"
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs writes at most this much
 
 
 # --------------------------------------------------------------------------------------------------------- launcher --
@@ -247,6 +257,27 @@ def sample_passes(npix, n_chunks, partial_mib=0):
     budget = (partial_mib << 20) if partial_mib else (8 << 30)
     cpp = max(1, min(n_chunks, budget // max(1, npix * 24)))
     return (n_chunks + cpp - 1) // cpp
+
+
+def dump_sample_index(n_pixels, n):
+    """row-major positions of the pixels --dump-outputs writes for a frame above its budget: n of them, fixed by seed 0"""
+    import numpy as np
+    return np.sort(np.random.default_rng(0).choice(n_pixels, size=n, replace=False))
+
+
+def dump_outputs(out_dir, frame, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the frame of the last timed step as out_dir/frame.npy (float64), or a seeded sample of its pixels as
+    out_dir/frame_sample.npy (n x 3) when the whole frame would exceed `budget` bytes.  Returns the file name written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.asarray(frame, dtype=np.float64)
+    if frame.nbytes <= budget:
+        np.save(os.path.join(out_dir, "frame.npy"), np.ascontiguousarray(frame))
+        return "frame.npy"
+    px = frame.reshape(-1, frame.shape[-1])
+    n = (budget // 2) // px[0].nbytes          # half the budget: far from the limit, header included
+    np.save(os.path.join(out_dir, "frame_sample.npy"), px[dump_sample_index(px.shape[0], n)])
+    return "frame_sample.npy"
 
 
 def git_head():
@@ -596,6 +627,9 @@ def rank_main(a, be=None):
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
             elapsed = float(tm[0])
             seg_total = int(t[1])
+        # every rank has synchronised its copies into `host` before the reduction above returned
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, host)
 
         paths_per_step = W * H * spp
         value = paths_per_step * a.steps / elapsed / 1e6
@@ -608,9 +642,9 @@ def rank_main(a, be=None):
                 frame_check = bool(np.array_equal(solo, host, equal_nan=True))
                 assert frame_check, "gathered frame differs from the single-GPU frame"
 
-        # device-resident rate of this rank's share (framebuffer left in HBM), outside the timed region
+        # device-resident rate of this rank's share (framebuffer left in HBM), outside the timed region: renders of its own, --full only
         dev_ms = None
-        if rows and hasattr(be, "device_resident_ms") and not a.probe_coherent:
+        if a.full and rows and hasattr(be, "device_resident_ms") and not a.probe_coherent:
             dev_ms = be.device_resident_ms(ctx, local_rank, W, H, spp, tile, (srows, period), max(1, min(a.steps, 3)), kw)
 
         if rank == 0:
@@ -640,16 +674,18 @@ def rank_main(a, be=None):
                            "host_frame_pin_error": getattr(frame, "pin_error", None) if frame is not None else None,
                            "backend": be.name, "commit": git_head(), "kernel_sources": kernel_sources_id(),
                            "probe_coherent": bool(a.probe_coherent), "segments_counted": seg_total},
-                "value_device_resident": round(my_pixels * spp / (dev_ms * 1e-3) / 1e6 * (world if world > 1 else 1), 2) if dev_ms else None,
                 "roofline": roofline_block(a.workload if (world == 1 and a.bvh == DEFAULT_BVH and a.walk_order == "reference") else None, st, avg_ms,
                                            my_pixels, spec.get("key") if spec else None, spp),
             }
+            if a.full:
+                line["value_device_resident"] = \
+                    round(my_pixels * spp / (dev_ms * 1e-3) / 1e6 * (world if world > 1 else 1), 2) if dev_ms else None
             if frame_check is not None:
                 line["gathered_frame_equals_single_gpu_frame"] = frame_check
-            if world == 1 and a.workload == "c3" and not a.no_other_configs and not (a.width and a.height):
+            if a.full and world == 1 and a.workload == "c3" and not a.no_other_configs and not (a.width and a.height):
                 line["other_configs"] = {name: measure_single(be, local_rank, k, s, 3, 1, bvh, order)
                                          for name, k, s, bvh, order in OTHER_CONFIGS}
-            if world == 1 and not a.no_cpu_baseline:
+            if a.full and world == 1 and not a.no_cpu_baseline:
                 line["cpu_baseline"] = cpu_baseline(wl, W, H)
     finally:
         ctx.close()
@@ -660,7 +696,7 @@ def rank_main(a, be=None):
             finally:
                 frame.close()
     # N > 1, the default job: BASELINE's two multi-GPU configs on the same ranks (every rank takes part; rank 0 holds the entries)
-    if world > 1 and a.workload == "c3" and not a.no_other_configs and not a.strong and (a.other_size or not (a.width and a.height)):
+    if a.full and world > 1 and a.workload == "c3" and not a.no_other_configs and not a.strong and (a.other_size or not (a.width and a.height)):
         extras = {}
         for name, key, xspp, xsteps in OTHER_CONFIGS_MULTI:
             xw, xh = (a.other_size[0], a.other_size[1]) if a.other_size else (WORKLOADS[key]["W"], WORKLOADS[key]["H"])
@@ -678,10 +714,14 @@ def rank_main(a, be=None):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="N = 1, c3: skip the C2 / C4 entries of the line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: value_device_resident, other_configs, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after timing, write the last timed step's frame to DIR/frame.npy (a seeded sample above 64 MB: DIR/frame_sample.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the other_configs entries of the line")
     ap.add_argument("--generic", action="store_true", help="ablation: the generic kernel instead of the scene-specialised one")
     ap.add_argument("--spp", type=int, default=0, help="default: the workload's own (c3 1000, c2 500, c4 10000, c5 1000)")
     ap.add_argument("--workload", choices=tuple(WORKLOADS), default="c3")
@@ -699,7 +739,10 @@ def parse_args(argv=None):
                     help="measurement runs under rocprofv3 only (tools/bench_pmc.sh): RT1W_PROBE_COHERENT, every wave traces one path 64 times; `value` is then meaningless")
     ap.add_argument("--other-size", type=int, nargs=3, default=None, metavar=("W", "H", "SPP"),
                     help="tests / rehearsals only: frame and spp of the N > 1 line's other_configs (c5_strong, c4_strong)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def main(argv=None, backend_factory=None, script=None):

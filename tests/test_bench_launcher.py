@@ -7,6 +7,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 import orc
 
 ROOT = orc.ROOT
@@ -17,9 +20,9 @@ def _clean_env():
     return env
 
 
-def test_bench_starts_its_own_two_ranks_and_gathers_one_frame(rt):
+def test_bench_starts_its_own_two_ranks_and_gathers_one_frame(rt, tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_cpu_ranks.py"), "--gpus", "2", "--width", "48", "--height", "48",
-           "--spp", "4", "--steps", "1", "--warmup", "0", "--check-frame", "--no-cpu-baseline"]
+           "--spp", "4", "--steps", "1", "--warmup", "0", "--check-frame", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")]
     p = subprocess.run(cmd, env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -32,7 +35,13 @@ def test_bench_starts_its_own_two_ranks_and_gathers_one_frame(rt):
     for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "roofline"):
         assert k in line
+    assert not {"other_configs", "value_device_resident"} & set(line)                  # a plain run: --full only
     assert not [f for f in os.listdir("/dev/shm") if f.startswith("rt1w_bench_")]   # the shared frame was removed
+    # --dump-outputs: rank 0 wrote the gathered frame, the whole image of the CPU build of the core
+    sc = rt.Scene.reference(5, build_seed=1, aspect_ratio=1.0)
+    ref, _ = orc.flat_render(sc, 48, 48, 4, chunk=line["config"]["chunk"])
+    assert os.listdir(tmp_path / "out") == ["frame.npy"]
+    assert np.array_equal(np.load(tmp_path / "out" / "frame.npy"), ref, equal_nan=True)
 
 
 def test_bench_three_ranks_with_a_ragged_last_strip(rt):
@@ -45,12 +54,11 @@ def test_bench_three_ranks_with_a_ragged_last_strip(rt):
 
 
 def test_default_multi_rank_line_carries_baselines_multi_gpu_configs(rt):
-    """`python bench.py --gpus N` with no --workload is the one command the driver runs on an 8-GPU node: besides the c3 weak line it
-    must measure BASELINE's two multi-GPU configs -- C5 (4K Cornell) and C4 (final_scene) tiled over the same ranks, strong scaling --
+    """`python bench.py --gpus N --full` with no --workload: besides the c3 weak line it must measure BASELINE's two multi-GPU configs -- C5 (4K Cornell) and C4 (final_scene) tiled over the same ranks, strong scaling --
     as `other_configs` (here at test size, CPU build of the core injected): D2H-inclusive rate, per-rank kernel ms, ranks seen,
     and the gathered frame equal to the single-rank frame."""
     cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_cpu_ranks.py"), "--gpus", "2", "--width", "48", "--height", "48",
-           "--spp", "2", "--steps", "1", "--warmup", "0", "--check-frame", "--no-cpu-baseline", "--other-size", "40", "40", "2"]
+           "--spp", "2", "--steps", "1", "--warmup", "0", "--check-frame", "--full", "--no-cpu-baseline", "--other-size", "40", "40", "2"]
     p = subprocess.run(cmd, env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -67,6 +75,80 @@ def test_default_multi_rank_line_carries_baselines_multi_gpu_configs(rt):
     # --strong and the explicit workloads are one job each: no extra entries
     p = subprocess.run(cmd[:-4] + ["--workload", "c2"], env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0 and "other_configs" not in json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][0])
+
+
+def test_plain_run_times_exactly_its_steps_and_dumps_the_last_frame(rt, tmp_path, capsys, monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` renders W + N times and nothing else; `ms_per_step` is the wall time of one of
+    the N; --dump-outputs writes the frame of the last timed step, the same bits from run to run"""
+    import bench
+    import bench_cpu_ranks
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        monkeypatch.delenv(k, raising=False)
+    renders = []
+
+    class Counting(bench_cpu_ranks.CpuBackend):
+        def context(self, scene, dev):
+            ctx = super().context(scene, dev)
+            plain = ctx.render
+            ctx.render = lambda *a, **kw: renders.append(kw.get("frame") is not None) or plain(*a, **kw)
+            return ctx
+
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        renders.clear()
+        bench.main(["--gpus", "1", "--width", "32", "--height", "24", "--spp", "2", "--steps", "3", "--warmup", "2",
+                    "--dump-outputs", str(out)], backend_factory=Counting)
+        line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        assert len(renders) == 5 and all(renders)
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert k in line
+        assert not {"other_configs", "cpu_baseline", "value_device_resident"} & set(line)
+        assert os.listdir(out) == ["frame.npy"]
+        dumps.append(np.load(out / "frame.npy"))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (24, 32, 3)
+    assert np.array_equal(dumps[0], dumps[1], equal_nan=True)
+    sc = rt.Scene.reference(5, build_seed=1, aspect_ratio=32 / 24)
+    ref, _ = orc.flat_render(sc, 32, 24, 2, chunk=line["config"]["chunk"])
+    assert np.array_equal(dumps[0], ref, equal_nan=True)
+
+
+def test_dump_of_a_frame_above_the_budget_is_a_fixed_sample(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    frame = np.random.default_rng(5).random((40, 30, 3))
+    assert bench.dump_outputs(str(tmp_path / "a"), frame, budget=frame.nbytes) == "frame.npy"
+    assert bench.dump_outputs(str(tmp_path / "b"), frame, budget=frame.nbytes // 4) == "frame_sample.npy"
+    assert os.listdir(tmp_path / "b") == ["frame_sample.npy"]
+    assert os.path.getsize(tmp_path / "b" / "frame_sample.npy") <= frame.nbytes // 4
+    got = np.load(tmp_path / "b" / "frame_sample.npy")
+    idx = bench.dump_sample_index(40 * 30, got.shape[0])
+    assert got.shape == (150, 3) and len(set(idx.tolist())) == 150
+    assert np.array_equal(got, frame.reshape(-1, 3)[idx])
+    assert np.array_equal(idx, bench.dump_sample_index(40 * 30, 150))
+
+
+def test_bench_rejects_zero_steps():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=_clean_env(),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode == 2 and b"--steps" in p.stderr
+
+
+@pytest.mark.gpu
+def test_product_bench_dumps_the_frame_its_timed_steps_rendered(rt, tmp_path):
+    """the real bench.py, a plain run: the frame --dump-outputs writes is the CPU build of the core's, bit for bit"""
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--width", "64", "--height", "64", "--spp", "8",
+           "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    line = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][0])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["config"]["scene_specialised_kernel"]
+    assert not {"other_configs", "cpu_baseline", "value_device_resident"} & set(line)
+    sc = rt.Scene.reference(5, build_seed=1, aspect_ratio=1.0)
+    ref, _ = orc.flat_render(sc, 64, 64, 8, chunk=line["config"]["chunk"])
+    assert np.array_equal(np.load(out / "frame.npy"), ref, equal_nan=True)
 
 
 def test_a_failing_rank_is_heard_and_ends_the_job(rt):

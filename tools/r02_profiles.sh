@@ -8,7 +8,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 cd $R
 echo "== bench kernel stats"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_stats.json 2> $O/bench_stats.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_stats.json 2> $O/bench_stats.err
 echo "== bench PMC"
 tools/prof_pmc.sh r02 --steps 2 --warmup 0 > $O/bench_pmc.log 2>&1
 cp gpurun_out/pmc_r02/summary.txt $O/bench_pmc_summary.txt
