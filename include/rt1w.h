@@ -296,6 +296,31 @@ typedef int (*rt1w_progress_fn)(void* user, uint32_t rows_done, uint32_t rows_to
 int rt1w_render_rows(rt1w_context* c, const rt1w_render_params* p, uint32_t strip_rows, int format, void* out,
                      rt1w_progress_fn progress, void* user, rt1w_stats* stats);
 
+/* ---- first-hit feature buffers (AOVs): what a denoiser or a learning / compositing host takes next to the frame ----
+ * For every pixel of the tile, samples sample_offset .. sample_offset + spp - 1.  Each sample's camera ray is EXACTLY the camera ray of
+ * that sample in rt1w_render: the same stream, the same u, v jitter, lens draw and time (src/main.rs:964-971, camera.rs:61-73).  Only
+ * that ray is traced, with world.hit(ray, 0.001, inf) (main.rs:62); a ConstantMedium draws its free flight from the same stream, as the
+ * first segment of the beauty path does.  So the first hit of AOV sample k is the first hit of beauty sample k.
+ * Every pixel gets RT1W_AOV_CHANNELS doubles; channels 0-5 and 7 are sums over the samples, in sample order, divided by spp; channel 6
+ * is the sum over the samples that hit divided by their count:
+ *   0-2 albedo   hit: Lambertian / Isotropic the albedo texture's value at (u, v, p) (material.rs:71-80, constant_medium.rs:37-50);
+ *                Metal its `albedo` (material.rs:99-111); Dielectric (1, 1, 1); DiffuseLight emitted(u, v, p) at the hit -- front face:
+ *                the emit texture, else 0 (material.rs:163-178); `()` 0.   miss: the scene's background.
+ *   3-5 normal   hit: HitRecord.normal in world space -- it faces against the ray, FlipFace does not flip it, a medium's is (1, 0, 0)
+ *                (hittable.rs:30-35, :206-270, constant_medium.rs:101); the mean is not renormalised.   miss: (0, 0, 0).
+ *   6 depth      distance from the ray origin to the hit, t * |d|, averaged over the samples that hit; +inf if no sample hits.
+ *   7 coverage   hit 1, miss 0.
+ * Layout double[tile_h][tile_w][8], row 0 = j = y0, as rt1w_render; an interleaved tile (strip_rows / strip_period) maps its rows as
+ * rt1w_render does.  max_depth, chunk and partial_mib are ignored; flags may be 0 or RT1W_FORCE_VARIANT(v) (tests), anything else is
+ * RT1W_ERR_INVALID; precision must be RT1W_PRECISION_F64 (RT1W_ERR_UNSUPPORTED otherwise).  stats: paths = segments = pixels * spp,
+ * kernel_ms (HIP events), total_ms, grid, block, variant.  One lane per pixel runs its samples in order: deterministic sums, bit-identical
+ * to the CPU build of the same code (librt1w_lab.so: rt1w_lab_aov_host).  None of the render kernels is involved. */
+#define RT1W_AOV_CHANNELS 8
+/* into caller host memory: out_aov[tile_h][tile_w][8] (through the context's device framebuffer) */
+int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_aov, rt1w_stats* stats);
+/* same, into device memory on the context's GPU (e.g. a torch tensor); no host copy.  Synchronises the context's stream before returning. */
+int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d_out_aov, rt1w_stats* stats);
+
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory
  * mapping that several single-GPU processes fill with RT1W_OUT_FRAME. */

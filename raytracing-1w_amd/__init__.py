@@ -54,6 +54,7 @@ NO_NODE_CACHE = 0x10000  # big scenes: the stack-walk kernels without the most v
 CLASSIC_WALK = 128  # sphere scenes: the one-entry-per-step walk instead of the pair walk (rt_walk_pair.h)
 WAVEFRONT = 16  # big scenes: path state queued in HBM, trace / shade kernels per bounce
 SPECIALISE_CACHED_ONLY = 1
+AOV_CHANNELS = 8  # rt1w_render_aov: albedo rgb, normal xyz, depth, coverage per pixel
 
 
 class Rt1wError(RuntimeError):
@@ -147,6 +148,8 @@ _sig("rt1w_render_device", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(S
 _sig("rt1w_render_u8", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(Stats))
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, _P, C.c_uint32, C.c_uint32)
 _sig("rt1w_render_rows", C.c_int, _P, C.POINTER(RenderParams), C.c_uint32, C.c_int, _P, PROGRESS_FN, _P, C.POINTER(Stats))
+_sig("rt1w_render_aov", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(Stats))
+_sig("rt1w_render_aov_device", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(Stats))
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -453,6 +456,23 @@ class Context:
         _ck(_lib.rt1w_render_device(self._h, C.byref(p), C.c_void_p(d_ptr), C.byref(st)))
         return {n: getattr(st, n) for n, _ in Stats._fields_}
 
+    def render_aov(self, width, height, spp, tile=None, sample_offset=0, global_seed=0, variant=None, strips=None, with_stats=False):
+        """First-hit feature buffers of the tile (rt1w_render_aov): float64 [tile_h, tile_w, 8] = albedo rgb, normal xyz, depth,
+        coverage, row 0 = reference row j = y0 (include/rt1w.h has the semantics).  with_stats: returns (array, stats dict)."""
+        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
+        out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_aov(self._h, C.byref(p), out.ctypes.data_as(_P), C.byref(st)))
+        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+
+    def render_aov_device(self, d_ptr, width, height, spp, tile=None, sample_offset=0, global_seed=0, variant=None, strips=None):
+        """Same, into device memory `d_ptr` (int address of tile_h * tile_w * 8 float64, e.g. a torch tensor's .data_ptr());
+        returns the stats dict."""
+        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
+        st = Stats()
+        _ck(_lib.rt1w_render_aov_device(self._h, C.byref(p), C.c_void_p(d_ptr), C.byref(st)))
+        return {n: getattr(st, n) for n, _ in Stats._fields_}
+
     def debug_aabb(self, cases):
         """cases[n, 14] = min3, max3, origin3, direction3, t_min, t_max -> (literal[n], fast[n]) from the device."""
         a = np.ascontiguousarray(cases, dtype=np.float64).reshape(-1, 14)
@@ -512,6 +532,21 @@ def host_register(array):
 
 def host_unregister(array):
     _ck(_lib.rt1w_host_unregister(C.c_void_p(array.ctypes.data)))
+
+
+def aov_host(scene, width, height, spp, tile=None, sample_offset=0, global_seed=0, variant=None, strips=None):
+    """CPU twin of Context.render_aov (librt1w_lab.so: rt1w_lab_aov_host, the same rt_aov.h built for the host): the array the GPU
+    must equal bit for bit.  No GPU needed."""
+    lab = load_lab()
+    f = lab.rt1w_lab_aov_host
+    f.restype = C.c_int
+    f.argtypes = [_P, C.POINTER(RenderParams), _P]
+    p = Context._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
+    out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
+    rc = f(scene._h, C.byref(p), out.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_aov_host")
+    return out
 
 
 def resolve(sums, spp):

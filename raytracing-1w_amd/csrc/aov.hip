@@ -1,0 +1,85 @@
+/* aov.hip -- the first-hit feature buffers of rt1w_render_aov (include/rt1w.h): one kernel per scene variant V0..V5 over rt_aov.h.
+ *
+ * Kept out of context.hip, inside its own namespace (the pattern of context_ref.hip), so that none of the render kernels' code objects
+ * and none of the run-time compiler's inputs moves with it.  The host half (validation, buffers, timing) is in context.hip, which
+ * calls the launcher below.
+ *
+ * Work mapping: one lane per pixel, looping over the pixel's samples in order -- the sums have one fixed order, the same as the CPU
+ * twin's (aov_host.cpp), and no partial-sum buffer is needed.  A wave covers an 8 x 8 block of the tile, so its 64 camera rays are
+ * neighbours (the wave-uniform sweep of the small scenes and the stack walk of the big ones see coherent rays).  Lanes outside the
+ * tile leave before any walk; the walks' wave votes (__ballot) count active lanes only, so a partly filled wave is well defined.
+ * Sweep variants walk with scalar node loads (RtGlobalNodes); stack variants keep their stacks in LDS columns as rt_kernel_plain.h
+ * does (RT_STACK_CAP x RT_BLOCK entries).  Built for four waves per SIMD (128 VGPRs); the figures are in DESIGN.md. */
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <string.h>
+#include <type_traits>
+
+namespace rtaov {
+#include "rt1w_num.h"
+#include "rt_flat.h"
+#include "rt_kernel_sorted.h"
+#include "rt_aov.h"
+
+#ifndef RT_AOV_WAVES
+#define RT_AOV_WAVES 4 /* waves per SIMD the kernels are built for */
+#endif
+#ifndef RT_AOV_ROW_MAJOR
+#define RT_AOV_ROW_MAJOR 0 /* 1: consecutive lanes take consecutive pixels of a tile row (the measured alternative) */
+#endif
+
+template <class Cfg>
+__global__ __launch_bounds__(RT_BLOCK, RT_AOV_WAVES) void rt_aov_kernel(RtSceneView sc, RtFrame f, double* __restrict__ out) {
+    __shared__ uint32_t stack_mem[Cfg::sweep ? 1 : RT_STACK_CAP * RT_BLOCK];
+#if RT_AOV_ROW_MAJOR
+    const unsigned long long idx = (unsigned long long)blockIdx.x * RT_BLOCK + threadIdx.x;
+    const uint32_t px = (uint32_t)(idx % f.tile_w), py = (uint32_t)(idx / f.tile_w);
+    if (idx >= (unsigned long long)f.tile_w * f.tile_h) return;
+#else
+    const uint32_t bw = (f.tile_w + 7u) >> 3;
+    const uint32_t wave = blockIdx.x * (RT_BLOCK / 64u) + (threadIdx.x >> 6), in = threadIdx.x & 63u;
+    const uint32_t px = (wave % bw) * 8u + (in & 7u), py = (wave / bw) * 8u + (in >> 3);
+    if (px >= f.tile_w || py >= f.tile_h) return;
+#endif
+    LdsStack stk;
+    stk.base = stack_mem + threadIdx.x;
+    stk.sp = 0;
+    RtGlobalNodes ns;
+    ns.p = sc.nodes;
+    rt_aov_pixel<Cfg>(sc, ns, f, px, py, stk, out + ((unsigned long long)py * f.tile_w + px) * RT_AOV_CHANNELS);
+}
+
+/* workgroups that cover the tile */
+inline unsigned aov_grid(const RtFrame& f) {
+#if RT_AOV_ROW_MAJOR
+    return (unsigned)(((unsigned long long)f.tile_w * f.tile_h + RT_BLOCK - 1u) / RT_BLOCK);
+#else
+    const unsigned long long blocks8 = (unsigned long long)((f.tile_w + 7u) >> 3) * ((f.tile_h + 7u) >> 3);
+    return (unsigned)((blocks8 + RT_BLOCK / 64u - 1u) / (RT_BLOCK / 64u));
+#endif
+}
+} // namespace rtaov
+
+/* called by context.hip; `view` / `frame` are the bytes of its RtSceneView / RtFrame (same headers, same layout: checked through
+ * rt1w_internal_aov_sizeof).  Enqueues one launch on `stream`; grid / block of it in launch[0..1].  0 or -1. */
+extern "C" int rt1w_internal_aov_launch(int variant, const void* view, const void* frame, double* out, hipStream_t stream, unsigned launch[2]) {
+    using namespace rtaov;
+    RtSceneView v;
+    RtFrame f;
+    memcpy(&v, view, sizeof v);
+    memcpy(&f, frame, sizeof f);
+    const unsigned grid = aov_grid(f);
+    launch[0] = grid; launch[1] = RT_BLOCK;
+    switch (variant) {
+        case 0: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV0>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
+        case 1: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV1>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
+        case 2: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV2>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
+        case 3: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV3>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
+        case 4: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV4>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
+        case 5: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV5>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
+        default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" unsigned rt1w_internal_aov_sizeof(int what) { return what == 0 ? (unsigned)sizeof(rtaov::RtSceneView) : (unsigned)sizeof(rtaov::RtFrame); }

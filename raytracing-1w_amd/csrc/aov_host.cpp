@@ -1,0 +1,83 @@
+/* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip): rt_aov.h compiled for the host (g++, -ffp-contract=off like every build
+ * of the core) and run over a committed scene's flat arrays.  Diagnostics library only (librt1w_lab.so): the expected side of the GPU
+ * tests' bit-equality checks and of the CPU tier's checks against the literal oracle.  librt1w.so keeps no CPU render path. */
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "scene.h"
+#include "rt_aov.h"
+#include "walk_lab.h"
+
+namespace {
+struct AovHostStack {
+    uint32_t e[RT_STACK_CAP];
+    int sp = 0;
+    bool overflow = false;
+    void push(uint32_t v) { if (sp >= RT_STACK_CAP) { overflow = true; return; } e[sp++] = v; }
+    void poke(int above, uint32_t v) { if (sp + above >= RT_STACK_CAP) { overflow = true; return; } e[sp + above] = v; }
+    uint32_t pop() { return e[--sp]; }
+};
+
+template <class Cfg>
+bool aov_rows(const RtSceneView& sc, const RtFrame& f, uint32_t row0, uint32_t row_step, double* out) {
+    AovHostStack stk;
+    RtGlobalNodes ns{sc.nodes};
+    for (uint32_t py = row0; py < f.tile_h; py += row_step)
+        for (uint32_t px = 0; px < f.tile_w; ++px) {
+            rt_aov_pixel<Cfg>(sc, ns, f, px, py, stk, out + ((size_t)py * f.tile_w + px) * RT_AOV_CHANNELS);
+            if (stk.overflow) return false;
+        }
+    return true;
+}
+bool aov_rows_variant(int v, const RtSceneView& sc, const RtFrame& f, uint32_t row0, uint32_t row_step, double* out) {
+    switch (v) { /* the variants the kernels are built for */
+        case 0: return aov_rows<RtCfgV0>(sc, f, row0, row_step, out);
+        case 1: return aov_rows<RtCfgV1>(sc, f, row0, row_step, out);
+        case 2: return aov_rows<RtCfgV2>(sc, f, row0, row_step, out);
+        case 4: return aov_rows<RtCfgV4>(sc, f, row0, row_step, out);
+        case 5: return aov_rows<RtCfgV5>(sc, f, row0, row_step, out);
+        default: return aov_rows<RtCfgV3>(sc, f, row0, row_step, out);
+    }
+}
+} // namespace
+
+extern "C" int rt1w_lab_aov_host(const rt1w_scene* s, const rt1w_render_params* p, double* out) {
+    if (!s || !p || !out || !s->committed) return RT1W_ERR_INVALID;
+    if (p->width < 2 || p->height < 2 || p->tile_w == 0 || p->tile_h == 0 || p->spp == 0 ||
+        (uint64_t)p->x0 + p->tile_w > p->width || (uint64_t)p->y0 + p->tile_h > p->height) return RT1W_ERR_INVALID;
+    if ((p->strip_rows == 0) != (p->strip_period == 0) || p->strip_period < p->strip_rows) return RT1W_ERR_INVALID;
+    if ((p->flags & ~(0xFFu << 8)) != 0u) return RT1W_ERR_INVALID;
+    if (p->precision != RT1W_PRECISION_F64) return RT1W_ERR_UNSUPPORTED;
+    const uint32_t n_nodes = (uint32_t)s->flat_nodes.size();
+    int v = rt_pick_variant(n_nodes, s->has_media, s->has_tex, s->has_msphere, s->scope_depth, s->walk_annotated != 0u);
+    if ((p->flags >> 8) & 0xFFu) {
+        v = (int)((p->flags >> 8) & 0xFFu) - 1;
+        if (!rt_variant_valid(v, n_nodes, s->has_media, s->has_tex, s->has_msphere, s->scope_depth)) return RT1W_ERR_INVALID;
+    }
+    std::vector<RtNode> nodes(s->flat_nodes);
+    nodes.push_back(RtNode{}); /* the spare record the context's node array carries */
+    RtSceneView sc;
+    std::memset(&sc, 0, sizeof sc);
+    sc.nodes = nodes.data(); sc.lights = s->flat_lights.data(); sc.materials = s->materials.data(); sc.textures = s->textures.data();
+    sc.perlin = s->perlin.data(); sc.images = s->images.data();
+    sc.root = s->flat_root; sc.n_nodes = n_nodes; sc.n_lights = (uint32_t)s->flat_lights.size();
+    sc.n_materials = (uint32_t)s->materials.size(); sc.n_textures = (uint32_t)s->textures.size();
+    sc.camera = s->camera; sc.background = s->background;
+    RtFrame f;
+    std::memset(&f, 0, sizeof f);
+    f.width = p->width; f.height = p->height; f.x0 = p->x0; f.y0 = p->y0; f.tile_w = p->tile_w; f.tile_h = p->tile_h;
+    f.spp = p->spp; f.sample_offset = p->sample_offset; f.global_seed = p->global_seed; f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u;
+    f.strip_rows = p->strip_rows; f.strip_period = p->strip_period;
+    /* rows dealt round-robin over at most 16 threads: every pixel is computed whole by one thread, so the result does not depend on it */
+    unsigned hw = std::thread::hardware_concurrency();
+    uint32_t n_threads = hw == 0u ? 1u : (hw > 16u ? 16u : hw);
+    if (n_threads > f.tile_h) n_threads = f.tile_h;
+    std::vector<char> ok(n_threads, 1);
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back([&, t]() { ok[t] = aov_rows_variant(v, sc, f, t, n_threads, out) ? 1 : 0; });
+    ok[0] = aov_rows_variant(v, sc, f, 0u, n_threads, out) ? 1 : 0;
+    for (auto& th : pool) th.join();
+    for (char k : ok) if (!k) return RT1W_ERR_STATE; /* a traversal stack overflowed */
+    return RT1W_OK;
+}

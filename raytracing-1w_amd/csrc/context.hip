@@ -38,6 +38,9 @@ extern "C" int rt1w_internal_ref_blocks_per_cu(int stack_walk);
 extern "C" int rt1w_internal_ref_launch(int stack_walk, const void* view, const void* frame, double* partial, unsigned long long* counters,
                                         int grid, hipStream_t stream);
 extern "C" unsigned rt1w_internal_ref_sizeof(int what);
+/* aov.hip: the first-hit feature buffers (rt1w_render_aov); launch[0..1] = grid, block of the launch */
+extern "C" int rt1w_internal_aov_launch(int variant, const void* view, const void* frame, double* out, hipStream_t stream, unsigned launch[2]);
+extern "C" unsigned rt1w_internal_aov_sizeof(int what);
 /* context_f32.hip: the kernels in single precision (RT1W_PRECISION_F32) and the f32 copies of the scene arrays */
 extern "C" int rt1w_internal_f32_create(const void* nodes, uint32_t n_nodes, const void* lights, uint32_t n_lights, const void* materials,
                                         uint32_t n_materials, const void* textures, uint32_t n_textures, const void* perlin, uint32_t n_perlin,
@@ -976,6 +979,102 @@ int rt1w_render(rt1w_context* c, const rt1w_render_params* p, double* out_rgb, r
         }
         if (!hip_ok(hipStreamSynchronize(st), "framebuffer copy")) return RT1W_ERR_DEVICE;
     } else if (!hip_ok(hipMemcpy(out_rgb, c->d_out, bytes, hipMemcpyDeviceToHost), "framebuffer copy")) return RT1W_ERR_DEVICE;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT1W_OK;
+}
+
+/* ---- first-hit feature buffers (include/rt1w.h: rt1w_render_aov) ---- */
+} // extern "C"
+namespace {
+/* the one flag the AOV entries take besides RT1W_FORCE_VARIANT: everything else is named and refused */
+int aov_check_flags(uint32_t flags) {
+    static const struct { uint32_t bit; const char* name; } known[] = {
+        {RT1W_OUT_SUM, "RT1W_OUT_SUM"}, {RT1W_UNSORTED, "RT1W_UNSORTED"}, {RT1W_LDS_NODES, "RT1W_LDS_NODES"}, {RT1W_GENERIC, "RT1W_GENERIC"},
+        {RT1W_WAVEFRONT, "RT1W_WAVEFRONT"}, {RT1W_OUT_FRAME, "RT1W_OUT_FRAME"}, {RT1W_RNG_REFERENCE, "RT1W_RNG_REFERENCE"},
+        {RT1W_CLASSIC_WALK, "RT1W_CLASSIC_WALK"}, {RT1W_NO_NODE_CACHE, "RT1W_NO_NODE_CACHE"}, {RT1W_PROBE_COHERENT, "RT1W_PROBE_COHERENT"}};
+    const uint32_t bad = flags & ~(0xFFu << 8);
+    if (!bad) return RT1W_OK;
+    for (const auto& k : known)
+        if (bad & k.bit) { rt1w::set_error(std::string(k.name) + " does not apply to the AOV entries (flags: 0 or RT1W_FORCE_VARIANT)"); return RT1W_ERR_INVALID; }
+    char buf[96];
+    snprintf(buf, sizeof buf, "unknown flag 0x%x for the AOV entries (flags: 0 or RT1W_FORCE_VARIANT)", bad & (0u - bad));
+    rt1w::set_error(buf);
+    return RT1W_ERR_INVALID;
+}
+
+/* validate, launch the AOV kernel of the context's (or the forced) variant into d_out, wait, fill stats */
+int render_aov_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, rt1w_stats* stats) {
+    int variant = c->variant;
+    if ((p->flags >> 8) & 0xFFu) {
+        variant = (int)((p->flags >> 8) & 0xFFu) - 1;
+        if (!rt_variant_valid(variant, c->n_nodes, c->has_media, c->has_tex, c->has_msphere, c->scope_depth)) {
+            rt1w::set_error("forced kernel variant does not cover this scene's features"); return RT1W_ERR_INVALID;
+        }
+    }
+    RtFrame f;
+    memset(&f, 0, sizeof f);
+    f.width = p->width; f.height = p->height;
+    f.x0 = p->x0; f.y0 = p->y0; f.tile_w = p->tile_w; f.tile_h = p->tile_h;
+    f.spp = p->spp; f.sample_offset = p->sample_offset; f.global_seed = p->global_seed;
+    f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u; /* not read by the AOV kernels */
+    f.strip_rows = p->strip_rows; f.strip_period = p->strip_period;
+    RtLane& l = c->lane[0];
+    if (rt1w_internal_aov_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_aov_sizeof(1) != sizeof(RtFrame)) {
+        rt1w::set_error("AOV kernels built against another scene layout"); return RT1W_ERR_DEVICE;
+    }
+    unsigned launch[2] = {0u, 0u};
+    (void)hipEventRecord(l.ev0, l.stream);
+    if (rt1w_internal_aov_launch(variant, &c->view, &f, d_out, l.stream, launch) != 0) { rt1w::set_error("AOV kernel launch failed"); return RT1W_ERR_DEVICE; }
+    (void)hipEventRecord(l.ev1, l.stream);
+    if (!hip_ok(hipStreamSynchronize(l.stream), "AOV kernel")) return RT1W_ERR_DEVICE;
+    if (stats) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
+        memset(stats, 0, sizeof *stats);
+        stats->paths = (uint64_t)p->tile_w * p->tile_h * p->spp;
+        stats->segments = stats->paths; /* one camera ray per sample */
+        stats->kernel_ms = ms;
+        stats->chunk = p->spp; stats->n_chunks = 1u;
+        stats->grid = launch[0]; stats->block = launch[1];
+        stats->variant = (uint32_t)variant;
+    }
+    return RT1W_OK;
+}
+int aov_validate(const rt1w_context* c, const rt1w_render_params* p, const void* out) {
+    int rc = validate(c, p);
+    if (rc < 0) return rc;
+    if (!out) { rt1w::set_error("null output"); return RT1W_ERR_INVALID; }
+    if ((rc = aov_check_flags(p->flags)) < 0) return rc;
+    if (p->precision != RT1W_PRECISION_F64) { rt1w::set_error("the AOV entries are f64 only (RT1W_PRECISION_F64)"); return RT1W_ERR_UNSUPPORTED; }
+    return RT1W_OK;
+}
+} // namespace
+extern "C" {
+
+int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_aov, rt1w_stats* stats) {
+    int rc = aov_validate(c, p, out_aov);
+    if (rc < 0) return rc;
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t bytes = (size_t)p->tile_w * p->tile_h * RT1W_AOV_CHANNELS * sizeof(double);
+    if (bytes > c->out_bytes) { /* the context's framebuffer, grown as rt1w_render_u8 grows it */
+        if (c->d_out) (void)hipFree(c->d_out);
+        c->d_out = nullptr; c->out_bytes = 0;
+        if (!hip_ok(hipMalloc((void**)&c->d_out, bytes), "hipMalloc(framebuffer)")) return RT1W_ERR_NOMEM;
+        c->out_bytes = bytes;
+    }
+    if ((rc = render_aov_common(c, p, c->d_out, stats)) < 0) return rc;
+    if (!hip_ok(hipMemcpy(out_aov, c->d_out, bytes, hipMemcpyDeviceToHost), "AOV copy")) return RT1W_ERR_DEVICE;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT1W_OK;
+}
+
+int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d_out_aov, rt1w_stats* stats) {
+    int rc = aov_validate(c, p, d_out_aov);
+    if (rc < 0) return rc;
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    auto t0 = std::chrono::steady_clock::now();
+    if ((rc = render_aov_common(c, p, (double*)d_out_aov, stats)) < 0) return rc;
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return RT1W_OK;
 }

@@ -30,6 +30,11 @@ int rt1w_lab_set_rays(rt1w_lab* l, const double* rays, uint64_t n);
 int rt1w_lab_trace(rt1w_lab* l, int mode, const uint32_t params[4], int repeats, double* out_t, uint32_t* out_prim, uint32_t* out_flags,
                    double* ms_best, uint64_t stats_out[8]);
 
+/* CPU twin of rt1w_render_aov (aov_host.cpp: rt_aov.h built for the host): the same double[tile_h][tile_w][8] for a committed scene,
+ * same variant choice (or p->flags' RT1W_FORCE_VARIANT), no GPU.  RT1W_OK, RT1W_ERR_INVALID / _UNSUPPORTED as the device entry,
+ * RT1W_ERR_STATE if a traversal stack overflowed */
+int rt1w_lab_aov_host(const rt1w_scene* s, const rt1w_render_params* p, double* out);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
