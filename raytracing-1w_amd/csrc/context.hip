@@ -34,8 +34,8 @@
 #include "rt1w_internal.h"
 
 /* context_ref.hip: the plain kernels built with the reference's own random stream (RT1W_RNG_REFERENCE) */
-extern "C" int rt1w_internal_ref_blocks_per_cu(int stack_walk);
-extern "C" int rt1w_internal_ref_launch(int stack_walk, const void* view, const void* frame, double* partial, unsigned long long* counters,
+extern "C" int rt1w_internal_ref_blocks_per_cu(int mode); /* mode: RtKernel.mode of the reference-stream kernels */
+extern "C" int rt1w_internal_ref_launch(int mode, const void* view, const void* frame, double* partial, unsigned long long* counters,
                                         int grid, hipStream_t stream);
 extern "C" unsigned rt1w_internal_ref_sizeof(int what);
 /* aov.hip: the first-hit feature buffers (rt1w_render_aov); launch[0..1] = grid, block of the launch */
@@ -46,10 +46,10 @@ extern "C" int rt1w_internal_f32_create(const void* nodes, uint32_t n_nodes, con
                                         uint32_t n_materials, const void* textures, uint32_t n_textures, const void* perlin, uint32_t n_perlin,
                                         const void* view64, void** out);
 extern "C" void rt1w_internal_f32_destroy(void* h);
-extern "C" int rt1w_internal_f32_blocks_per_cu(int variant, int sorted); /* sorted 2: the pair-walk kernel of sphere scenes */
+extern "C" int rt1w_internal_f32_blocks_per_cu(int variant, int mode); /* mode: RtKernel.mode of the f32 kernels (0 plain, 1 reordering, 2 pair walk) */
 extern "C" int rt1w_internal_f32_pw(void* h, unsigned stack_cap); /* 1: the scene has f32 pair-walk records and fits `stack_cap` entries */
 extern "C" unsigned rt1w_internal_f32_view(void* h, void* out, unsigned cap); /* bytes of the f32 RtSceneView (kernel argument) */
-extern "C" int rt1w_internal_f32_launch(void* h, int variant, int sorted, const void* frame, double* partial, unsigned long long* counters, int grid,
+extern "C" int rt1w_internal_f32_launch(void* h, int variant, int mode, const void* frame, double* partial, unsigned long long* counters, int grid,
                                         hipStream_t stream);
 
 #include "rt_kernels.h"
@@ -108,77 +108,113 @@ struct RtLane {
     void* d_strip = nullptr; void* h_strip = nullptr; size_t strip_bytes = 0; /* rt1w_render_rows: device strip + pinned host strip */
 };
 
+/* How a kernel is launched: render_launch switches on it */
+enum RtForm {
+    RT_FORM_F64,     /* a render kernel of this unit: (view, frame, partial, counters) */
+    RT_FORM_PW,      /* a pair-walk kernel of this unit (rt_walk_pair.h): (view, pair-walk view, frame, partial, counters) */
+    RT_FORM_JIT,     /* the scene-specialised kernel (jit.cpp), from its module */
+    RT_FORM_F32,     /* context_f32.hip: rt1w_internal_f32_launch(variant, mode) */
+    RT_FORM_F32_JIT, /* the f32 build of the scene-specialised kernel */
+    RT_FORM_REF,     /* context_ref.hip: rt1w_internal_ref_launch(mode) */
+};
+
+/* the rt1w_stats.sorted bits (include/rt1w.h) a kernel reports; bit 3, the wavefront form, is filled by wavefront.hip */
+enum : uint32_t {
+    RT_BIT_SORTED = 1u, RT_BIT_LDS_NODES = 2u, RT_BIT_JIT = 4u, RT_BIT_REF = 16u, RT_BIT_F32 = 32u, RT_BIT_PW = 128u, RT_BIT_SPHERE_MEDIA = 256u,
+    RT_BIT_SS = 512u, RT_BIT_HC = 1024u
+};
+
+/* one runnable kernel: its launch form, workgroup size, stats bits, what the launch needs, and its persistent grid (0: not built for
+ * this context, or not queried yet) */
+struct RtKernel {
+    RtForm form;
+    int block;
+    uint32_t bits;
+    const void* fn = nullptr;     /* RT_FORM_F64, RT_FORM_PW: the __global__ */
+    int mode = 0;                 /* RT_FORM_REF, RT_FORM_F32: the companion unit's kernel index */
+    hipFunction_t jit = nullptr;  /* RT_FORM_JIT, RT_FORM_F32_JIT */
+    int grid = 0;
+};
+
+/* The f64 render kernels by walk form and variant; nullptr: not built for that variant.  Every walk form is followed by its build for
+ * scenes whose media are all bounded by a bare Sphere (rt_flat.h: RtCfgSphereMedia): form + 1. */
+enum RtWalkForm {
+    RT_WALK_PLAIN, RT_WALK_SPHERE_MEDIA,
+    RT_WALK_SS, RT_WALK_SS_SPHERE_MEDIA,       /* finished paths reordered across the workgroup at the end of every slice (rt_render_ss_body) */
+    RT_WALK_SS_HC, RT_WALK_SS_HC_SPHERE_MEDIA, /* ... and the scene's most visited nodes in LDS (rt_walk_table.h): a context with a walk table */
+    RT_WALK_LDS_NODES,                         /* all nodes in LDS (scenes of <= RT_LDS_NODE_CAP nodes; opt-in: RT1W_LDS_NODES) */
+    RT_WALK_SORTED,                            /* the reordering kernel (rt_kernel_sorted.h) */
+    RT_N_WALKS
+};
+typedef void (*render_kernel_t)(RtSceneView, RtFrame, double*, unsigned long long*);
+static render_kernel_t const g_kernels[RT_N_WALKS][RT_N_VARIANTS] = {
+    {rt_render_kernel<RtCfgV0>, rt_render_kernel<RtCfgV1>, rt_render_kernel<RtCfgV2>, rt_render_kernel<RtCfgV3>, rt_render_kernel<RtCfgV4>,
+     rt_render_kernel<RtCfgV5>},
+    /* the stack variants with media */
+    {nullptr, nullptr, nullptr, rt_render_kernel<RtCfgSphereMedia<RtCfgV3>>, rt_render_kernel<RtCfgSphereMedia<RtCfgV4>>, nullptr},
+    /* the default of the stack-walk scenes they cover */
+    {nullptr, nullptr, rt_render_kernel_ss<RtCfgV2, RT_SS_CAP, 3>, rt_render_kernel_ss<RtCfgV3, RT_SS_CAP, 3>, nullptr, rt_render_kernel_ss<RtCfgV5, RT_SS_CAP, 3>},
+    {nullptr, nullptr, nullptr, rt_render_kernel_ss<RtCfgSphereMedia<RtCfgV3>, RT_SS_CAP, 3>, rt_render_kernel_ss<RtCfgSphereMedia<RtCfgV4>, RT_SS_CAP, 3>, nullptr},
+    {nullptr, nullptr, rt_render_kernel_ss_hc<RtCfgV2>, rt_render_kernel_ss_hc<RtCfgV3>, nullptr, rt_render_kernel_ss_hc<RtCfgV5>},
+    {nullptr, nullptr, nullptr, rt_render_kernel_ss_hc<RtCfgSphereMedia<RtCfgV3>>, rt_render_kernel_ss_hc<RtCfgSphereMedia<RtCfgV4>>, nullptr},
+    /* measured on random_scene: 464 Mpaths/s (80 KB LDS -> 2 waves/SIMD) against 486 for the plain variant at 3 waves/SIMD */
+    {nullptr, nullptr, rt_render_kernel<RtCfgV2, true>, rt_render_kernel<RtCfgV3, true>, nullptr, rt_render_kernel<RtCfgV5, true>},
+    /* where it pays (measured): the sweep variants.  Stack variants: 0.55x (LDS for stack + exchange halves occupancy) */
+    {rt_render_kernel_sorted<RtCfgV0>, rt_render_kernel_sorted<RtCfgV1>, nullptr, nullptr, nullptr, nullptr}};
+static const struct { int block; uint32_t bits; } g_walks[RT_N_WALKS] = {
+    {RT_BLOCK, 0u}, {RT_BLOCK, RT_BIT_SPHERE_MEDIA}, {RT_BLOCK, RT_BIT_SS}, {RT_BLOCK, RT_BIT_SS | RT_BIT_SPHERE_MEDIA},
+    {RT_BLOCK, RT_BIT_SS | RT_BIT_HC}, {RT_BLOCK, RT_BIT_SS | RT_BIT_HC | RT_BIT_SPHERE_MEDIA}, {RT_BLOCK, RT_BIT_LDS_NODES}, {RT_SORT_BLOCK, RT_BIT_SORTED}};
+
+/* a scene-specialised kernel (jit.cpp) of one precision.  The first five members say how loading it differs between the two
+ * (load_specialised) */
+struct RtJitSlot {
+    const char* what;          /* for error texts */
+    RtForm form;               /* RT_FORM_JIT or RT_FORM_F32_JIT */
+    bool recompile_refused;    /* f64: compile once more when the driver refuses a cached object */
+    bool block_from_bounds;    /* f64: the workgroup size is the kernel's launch bound = its sort domain (experiments build it for 512) */
+    bool sticky;               /* f32: honours RT1W_NO_JIT, renders look at the caches once per context, a failure is remembered with
+                                * its reason (rt1w_context_specialise reports it) */
+    std::string src, key;      /* generated source (empty: scene not eligible), cache key */
+    hipModule_t mod = nullptr;
+    RtKernel k{};              /* k.jit != nullptr once loaded */
+    uint32_t vgprs = 0;
+    bool tried = false;
+    bool failed = false;       /* f64: a compile was tried and failed, renders do not try again (render_common); f32: see `sticky` */
+    std::string error;
+};
+
 struct rt1w_context {
     int device = 0;
+    int n_cu = 0; /* compute units: a persistent grid is n_cu x the workgroups resident per CU (kernel_grid) */
     RtLane lane[2];
     hipEvent_t ev_first = nullptr;
     void* d_nodes = nullptr; void* d_lights = nullptr; void* d_materials = nullptr;
     void* d_textures = nullptr; void* d_perlin = nullptr; void* d_images = nullptr;
     RtSceneView view{};
     double* d_out = nullptr; size_t out_bytes = 0;
-    int grid[RT_N_VARIANTS] = {};
-    int grid_sphere_media[RT_N_VARIANTS] = {};
-    int grid_ss[2][RT_N_VARIANTS] = {};
-    int grid_ss_hc[2][RT_N_VARIANTS] = {}; /* the same kernels with the node cache (rt_render_kernel_ss_hc); 0: this context has no walk table */
+    RtKernel k64[RT_N_WALKS][RT_N_VARIANTS] = {}; /* g_kernels, queried at creation; the node-cache walks only with a walk table */
     bool walk_table = false; uint32_t walk_table_first = 0;
-    bool sphere_media = false; /* every medium of the scene is bounded by a bare Sphere: g_kernels_sphere_media serve */
-    int grid_sorted[RT_N_VARIANTS] = {};
-    int grid_cached[RT_N_VARIANTS] = {};
+    bool sphere_media = false; /* every medium of the scene is bounded by a bare Sphere: the sphere-media walks serve */
     int variant = 0;
     bool has_media = false, has_tex = false, has_msphere = false;
     uint32_t n_nodes = 0, scope_depth = 0;
     void* wf_state = nullptr; /* the wavefront form's own state (librt1w_lab.so: wavefront.hip), freed through its destroy hook */
     uint32_t stack_need = 0;
-    int ref_grid[4] = {0, 0, 0, 0}; /* reference-stream kernels: sweep, stack walk, reordering V0, reordering every-feature */
+    RtKernel ref[4] = {}; /* reference-stream kernels by rt1w_internal_ref_* mode: sweep, stack walk, reordering V0, reordering every-feature */
     void* f32_scene = nullptr;   /* context_f32.hip: f32 copies of the scene arrays, built at the first f32 render */
     bool f32_tried = false;
-    /* pair walk (rt_walk_pair.h): records of an eligible scene (sphere-only, variant 5), the kernel's grid */
+    /* pair walk (rt_walk_pair.h): records of an eligible scene (sphere-only, variant 5); its kernels, plain and reordering (grid 0: the
+     * scene is not eligible) */
     void* d_pw_inner = nullptr; void* d_pw_groups = nullptr;
     RtPwView pw{};
-    bool pw_ok = false; std::string pw_why;
-    int pw_grid = 0, pw_ss_grid = 0;
+    std::string pw_why;
+    RtKernel pw_k[2] = {};
     /* host copies of the flat arrays the two opt-in modes convert on first use (a scene may be destroyed before its contexts) */
     std::vector<RtNode> h_nodes, h_lights; std::vector<RtMaterial> h_materials; std::vector<RtTexture> h_textures; std::vector<RtPerlin> h_perlin;
-    int f32_grid[RT_N_VARIANTS][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}; /* [variant][plain, reordering, pair walk] */
-    /* scene-specialised kernel (jit.cpp): generated source (empty: scene not eligible), loaded module */
-    std::string jit_src, jit_key;
-    hipModule_t jit_mod = nullptr;
-    hipFunction_t jit_fn = nullptr;
-    int jit_grid = 0;
-    int jit_block = RT_SORT_BLOCK; /* the specialised kernel's workgroup size = its sort domain (its __launch_bounds__; experiments build it for 512) */
-    uint32_t jit_vgprs = 0;
-    bool jit_failed = false; /* a compile was tried and failed: do not try again on this context */
-    /* the same for RT1W_PRECISION_F32: loaded / compiled at the first f32 render of a specialised context */
-    std::string jit32_src;
-    hipModule_t jit32_mod = nullptr;
-    hipFunction_t jit32_fn = nullptr;
-    int jit32_grid = 0;
-    bool jit32_tried = false, jit32_failed = false;
-    std::string jit32_error;
+    RtKernel k32[RT_N_VARIANTS][3] = {}; /* f32 kernels by variant and rt1w_internal_f32_* mode: plain, reordering, pair walk */
+    RtJitSlot jit{"specialised kernel", RT_FORM_JIT, true, true, false};
+    RtJitSlot jit32{"f32 specialised kernel", RT_FORM_F32_JIT, false, false, true}; /* loaded only where `jit` is */
 };
-
-typedef void (*render_kernel_t)(RtSceneView, RtFrame, double*, unsigned long long*);
-static render_kernel_t const g_kernels[RT_N_VARIANTS] = {rt_render_kernel<RtCfgV0>, rt_render_kernel<RtCfgV1>,
-                                                         rt_render_kernel<RtCfgV2>, rt_render_kernel<RtCfgV3>, rt_render_kernel<RtCfgV4>,
-                                                         rt_render_kernel<RtCfgV5>};
-/* the stack variants with media, for scenes whose media are all bounded by a bare Sphere (rt_flat.h: RtCfgSphereMedia) */
-static render_kernel_t const g_kernels_sphere_media[RT_N_VARIANTS] = {nullptr, nullptr, nullptr, rt_render_kernel<RtCfgSphereMedia<RtCfgV3>>,
-                                                                      rt_render_kernel<RtCfgSphereMedia<RtCfgV4>>, nullptr};
-/* the stack-walk kernels with the finished paths reordered across the workgroup at the end of every slice (rt_render_ss_body): the default
- * for the scenes they cover; [1] = the sphere-media builds */
-static render_kernel_t const g_kernels_ss[2][RT_N_VARIANTS] = {
-    {nullptr, nullptr, rt_render_kernel_ss<RtCfgV2, RT_SS_CAP, 3>, rt_render_kernel_ss<RtCfgV3, RT_SS_CAP, 3>, nullptr, rt_render_kernel_ss<RtCfgV5, RT_SS_CAP, 3>},
-    {nullptr, nullptr, nullptr, rt_render_kernel_ss<RtCfgSphereMedia<RtCfgV3>, RT_SS_CAP, 3>, rt_render_kernel_ss<RtCfgSphereMedia<RtCfgV4>, RT_SS_CAP, 3>, nullptr}};
-/* ... and with the scene's most visited nodes in LDS (rt_walk_table.h): what a context with a walk table runs */
-static render_kernel_t const g_kernels_ss_hc[2][RT_N_VARIANTS] = {
-    {nullptr, nullptr, rt_render_kernel_ss_hc<RtCfgV2>, rt_render_kernel_ss_hc<RtCfgV3>, nullptr, rt_render_kernel_ss_hc<RtCfgV5>},
-    {nullptr, nullptr, nullptr, rt_render_kernel_ss_hc<RtCfgSphereMedia<RtCfgV3>>, rt_render_kernel_ss_hc<RtCfgSphereMedia<RtCfgV4>>, nullptr}};
-/* stack variants with the LDS node cache (scenes of <= RT_LDS_NODE_CAP nodes; opt-in: RT1W_LDS_NODES).  Measured on
- * random_scene: 464 Mpaths/s (80 KB LDS -> 2 waves/SIMD) against 486 for the plain variant at 3 waves/SIMD. */
-static render_kernel_t const g_kernels_cached[RT_N_VARIANTS] = {nullptr, nullptr, rt_render_kernel<RtCfgV2, true>, rt_render_kernel<RtCfgV3, true>, nullptr, rt_render_kernel<RtCfgV5, true>};
-/* the reordering kernel exists for the variants where it pays (measured): the sweep variants */
-static render_kernel_t const g_kernels_sorted[RT_N_VARIANTS] = {rt_render_kernel_sorted<RtCfgV0>, rt_render_kernel_sorted<RtCfgV1>,
-                                                                nullptr, nullptr, nullptr, nullptr}; /* stack variants: measured 0.55x (LDS for stack + exchange halves occupancy) */
 
 namespace {
 
@@ -306,10 +342,49 @@ void lane_destroy(RtLane& l) {
 #ifndef RT_PARTIAL_BUDGET
 #define RT_PARTIAL_BUDGET (8ull << 30)
 #endif
-struct RtLaunch { RtFrame f; unsigned long long npix; unsigned long long partial_budget = RT_PARTIAL_BUDGET; int variant, grid, block; bool sorted, cached, jit, ref, f32, pw = false, sphere_media = false, ss = false, hc = false; };
-int specialise_f32(rt1w_context* c, bool allow_compile);
+struct RtLaunch { RtFrame f; unsigned long long npix; unsigned long long partial_budget = RT_PARTIAL_BUDGET; int variant; RtKernel k; };
 
-/* what the launch will need, without launching: frame, variant, launch shape */
+/* the persistent grid of a kernel: as many workgroups as are resident at once, at least one per CU; 0 if the occupancy query failed */
+int kernel_grid(const rt1w_context* c, const RtKernel& k, int variant) {
+    int per_cu = 0;
+    switch (k.form) {
+        case RT_FORM_F64: case RT_FORM_PW:
+            if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, k.block, 0), "occupancy query")) return 0;
+            break;
+        case RT_FORM_JIT: case RT_FORM_F32_JIT:
+            if (!hip_ok(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.jit, k.block, 0), "occupancy query")) return 0;
+            break;
+        case RT_FORM_REF: per_cu = rt1w_internal_ref_blocks_per_cu(k.mode); break;
+        case RT_FORM_F32: per_cu = rt1w_internal_f32_blocks_per_cu(variant, k.mode); break;
+    }
+    return c->n_cu * (per_cu < 1 ? 1 : per_cu);
+}
+
+/* the kernels whose grid is queried at their first use (reference stream, f32): `slot` becomes `k` with its grid */
+const RtKernel& first_use(const rt1w_context* c, RtKernel& slot, const RtKernel& k, int variant) {
+    if (!slot.grid) { slot = k; slot.grid = kernel_grid(c, slot, variant); }
+    return slot;
+}
+
+/* RT1W_FORCE_VARIANT: `*v` becomes the variant the flags name, if they name one (allow_v4: the order-aware V4, which exists in f64 only) */
+int forced_variant(const rt1w_context* c, uint32_t flags, bool allow_v4, int* v) {
+    if (!((flags >> 8) & 0xFFu)) return RT1W_OK;
+    *v = (int)((flags >> 8) & 0xFFu) - 1;
+    if ((*v == 4 && !allow_v4) || !rt_variant_valid(*v, c->n_nodes, c->has_media, c->has_tex, c->has_msphere, c->scope_depth)) {
+        rt1w::set_error("forced kernel variant does not cover this scene's features"); return RT1W_ERR_INVALID;
+    }
+    return RT1W_OK;
+}
+
+/* the work-item size of a render with chunk 0 (include/rt1w.h: rt1w_scene_default_chunk): one sample per item on the stack-walk scenes,
+ * except for the wavefront form, whose passes are per chunk */
+uint32_t default_chunk(const rt1w_context* c, const rt1w_render_params* p) {
+    return (c->variant >= 2 && !(p->flags & RT1W_WAVEFRONT)) ? 1u : rt1w_default_chunk(p->tile_w, p->tile_h, p->spp);
+}
+
+int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::JitInfo& info);
+
+/* what the launch will need, without launching: frame, variant, kernel */
 int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
     RtFrame& f = L.f;
     f.width = p->width; f.height = p->height;
@@ -318,84 +393,66 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
     f.global_seed = p->global_seed;
     f.strip_rows = p->strip_rows; f.strip_period = p->strip_period;
     f.probe = (p->flags & RT1W_PROBE_COHERENT) ? 1u : 0u;
-    /* stack-walk scenes: one sample per work item (include/rt1w.h: rt1w_scene_default_chunk), except for the wavefront form, whose passes are
-     * per chunk; the reference stream sets its own below */
-    f.chunk = p->chunk ? p->chunk : ((c->variant >= 2 && !(p->flags & RT1W_WAVEFRONT)) ? 1u : rt1w_default_chunk(p->tile_w, p->tile_h, p->spp));
+    f.chunk = p->chunk ? p->chunk : default_chunk(c, p); /* the reference stream sets its own below */
     if (f.chunk > f.spp) f.chunk = f.spp;
     f.n_chunks = (f.spp + f.chunk - 1u) / f.chunk;
     L.npix = (unsigned long long)f.tile_w * f.tile_h;
     L.partial_budget = p->partial_mib ? ((unsigned long long)p->partial_mib << 20) : RT_PARTIAL_BUDGET;
-    L.ref = false; L.f32 = false;
+    const uint32_t fl = p->flags;
+    const bool forced = ((fl >> 8) & 0xFFu) != 0u;
+    rt1w::JitInfo info;
+    int rc;
     if (p->precision == RT1W_PRECISION_F32) {
-        if (p->flags & (RT1W_RNG_REFERENCE | RT1W_WAVEFRONT | RT1W_LDS_NODES)) { rt1w::set_error("RT1W_PRECISION_F32 has the default kernels only"); return RT1W_ERR_INVALID; }
-        { const int rcf = ensure_f32_scene(c); if (rcf < 0) return rcf; }
-        int v = c->variant == 4 ? 3 : c->variant; /* the order-aware variant exists in f64 only */
-        if ((p->flags >> 8) & 0xFFu) {
-            v = (int)((p->flags >> 8) & 0xFFu) - 1;
-            if (v == 4 || !rt_variant_valid(v, c->n_nodes, c->has_media, c->has_tex, c->has_msphere, c->scope_depth)) {
-                rt1w::set_error("forced kernel variant does not cover this scene's features"); return RT1W_ERR_INVALID;
-            }
-        }
+        if (fl & (RT1W_RNG_REFERENCE | RT1W_WAVEFRONT | RT1W_LDS_NODES)) { rt1w::set_error("RT1W_PRECISION_F32 has the default kernels only"); return RT1W_ERR_INVALID; }
+        if ((rc = ensure_f32_scene(c)) < 0) return rc;
+        L.variant = c->variant == 4 ? 3 : c->variant; /* the order-aware variant exists in f64 only */
+        if ((rc = forced_variant(c, fl, false, &L.variant)) < 0) return rc;
         /* a context that runs a scene-specialised kernel in f64 uses the f32 build of that kernel too -- from the kernel
          * caches only: renders never compile (rt1w_context_specialise does, for both precisions) */
-        if (!(p->flags & (RT1W_GENERIC | RT1W_UNSORTED)) && !((p->flags >> 8) & 0xFFu)) (void)specialise_f32(c, false);
-        if (c->jit32_fn && !(p->flags & (RT1W_GENERIC | RT1W_UNSORTED)) && !((p->flags >> 8) & 0xFFu)) {
-            L.f32 = true; L.jit = true; L.sorted = true; L.cached = false; L.variant = v; L.grid = c->jit32_grid; L.block = RT_SORT_BLOCK;
+        if (!(fl & (RT1W_GENERIC | RT1W_UNSORTED)) && !forced && c->jit.k.jit && load_specialised(c, c->jit32, false, info) == RT1W_OK) {
+            L.k = c->jit32.k;
             return RT1W_OK;
         }
-        const bool sorted = !(p->flags & RT1W_UNSORTED); /* v >= 2: the slice-end reordering of the stack walks */
-        L.ss = sorted && v >= 2;
-        /* sphere scenes: the pair walk (rt_walk_pair.h) in this precision too -- in the kernel that reorders the finished paths */
-        L.pw = L.ss && v == 5 && !(p->flags & RT1W_CLASSIC_WALK) && rt1w_internal_f32_pw(c->f32_scene, (unsigned)RT_PW_SS_STACK) == 1;
-        int& g = c->f32_grid[v][L.pw ? 2 : (sorted ? 1 : 0)];
-        if (!g) {
-            hipDeviceProp_t prop;
-            if (!hip_ok(hipGetDeviceProperties(&prop, c->device), "hipGetDeviceProperties")) return RT1W_ERR_DEVICE;
-            g = prop.multiProcessorCount * rt1w_internal_f32_blocks_per_cu(v, L.pw ? 2 : (sorted ? 1 : 0));
-        }
-        L.f32 = true; L.jit = false; L.sorted = sorted; L.cached = false; L.variant = v; L.grid = g; L.block = sorted ? RT_SORT_BLOCK : RT_BLOCK;
+        /* mode 1: the reordering kernel of the sweep variants, the slice-end reordering of the stack walks; 2: sphere scenes' pair walk
+         * (rt_walk_pair.h) in this precision too -- in the kernel that reorders the finished paths */
+        const int v = L.variant;
+        const int mode = (fl & RT1W_UNSORTED) ? 0
+                       : (v == 5 && !(fl & RT1W_CLASSIC_WALK) && rt1w_internal_f32_pw(c->f32_scene, (unsigned)RT_PW_SS_STACK) == 1) ? 2 : 1;
+        const uint32_t bits = RT_BIT_F32 | (mode == 2 ? RT_BIT_PW | RT_BIT_SS : mode == 1 ? (v >= 2 ? RT_BIT_SS : RT_BIT_SORTED) : 0u);
+        L.k = first_use(c, c->k32[v][mode], RtKernel{RT_FORM_F32, mode ? RT_SORT_BLOCK : RT_BLOCK, bits, nullptr, mode}, v);
         return RT1W_OK;
     }
-    if (p->flags & RT1W_RNG_REFERENCE) {
+    if (fl & RT1W_RNG_REFERENCE) {
         /* the reference's own stream: one lane owns a pixel for all its samples (main.rs:964-989) */
         if (p->sample_offset != 0u) { rt1w::set_error("RT1W_RNG_REFERENCE: one stream per pixel, sample_offset must be 0"); return RT1W_ERR_INVALID; }
         f.chunk = f.spp; f.n_chunks = 1u; f.global_seed = 0u;
         const bool stack_walk = c->n_nodes > RT_SWEEP_MAX_NODES;
         /* small scenes: through the workgroup-level path reordering (the stream's state travels with the path) unless RT1W_UNSORTED */
-        const int mode = stack_walk ? 1 : ((p->flags & RT1W_UNSORTED) ? 0 : (c->variant == 0 ? 2 : 3));
-        if (!c->ref_grid[mode]) {
-            hipDeviceProp_t prop;
-            if (!hip_ok(hipGetDeviceProperties(&prop, c->device), "hipGetDeviceProperties")) return RT1W_ERR_DEVICE;
-            c->ref_grid[mode] = prop.multiProcessorCount * rt1w_internal_ref_blocks_per_cu(mode);
-        }
-        L.ref = true; L.jit = false; L.sorted = mode >= 2; L.cached = false;
-        L.variant = stack_walk ? 3 : (mode == 2 ? 0 : 1); L.grid = c->ref_grid[mode]; L.block = mode >= 2 ? RT_SORT_BLOCK : RT_BLOCK;
+        const int mode = stack_walk ? 1 : ((fl & RT1W_UNSORTED) ? 0 : (c->variant == 0 ? 2 : 3));
+        L.variant = stack_walk ? 3 : (mode == 2 ? 0 : 1);
+        L.k = first_use(c, c->ref[mode], RtKernel{RT_FORM_REF, mode >= 2 ? RT_SORT_BLOCK : RT_BLOCK, RT_BIT_REF | (mode >= 2 ? RT_BIT_SORTED : 0u), nullptr, mode}, 0);
         return RT1W_OK;
     }
-    int variant = c->variant;
-    if ((p->flags >> 8) & 0xFFu) {
-        variant = (int)((p->flags >> 8) & 0xFFu) - 1;
-        if (!rt_variant_valid(variant, c->n_nodes, c->has_media, c->has_tex, c->has_msphere, c->scope_depth)) {
-            rt1w::set_error("forced kernel variant does not cover this scene's features"); return RT1W_ERR_INVALID;
-        }
-    }
-    L.variant = variant;
-    L.jit = c->jit_fn != nullptr && !(p->flags & (RT1W_GENERIC | RT1W_UNSORTED | RT1W_LDS_NODES)) && !((p->flags >> 8) & 0xFFu);
-    if (L.jit) { L.sorted = true; L.cached = false; L.grid = c->jit_grid; L.block = c->jit_block; return RT1W_OK; }
+    L.variant = c->variant;
+    if ((rc = forced_variant(c, fl, true, &L.variant)) < 0) return rc;
+    const int v = L.variant;
+    if (c->jit.k.jit && !(fl & (RT1W_GENERIC | RT1W_UNSORTED | RT1W_LDS_NODES)) && !forced) { L.k = c->jit.k; return RT1W_OK; }
     /* sphere scenes: the pair walk (same frames, bit for bit), unless the caller asks for the one-entry-per-step walk */
-    if (c->pw_ok && variant == 5 && !(p->flags & (RT1W_CLASSIC_WALK | RT1W_LDS_NODES | RT1W_WAVEFRONT))) {
-        L.pw = true; L.sorted = false; L.cached = false; L.grid = c->pw_grid; L.block = RT_BLOCK;
-        L.ss = c->pw_ss_grid > 0 && !(p->flags & RT1W_UNSORTED);
-        if (L.ss) L.grid = c->pw_ss_grid;
+    if (c->pw_k[0].grid && v == 5 && !(fl & (RT1W_CLASSIC_WALK | RT1W_LDS_NODES | RT1W_WAVEFRONT))) {
+        L.k = c->pw_k[c->pw_k[1].grid && !(fl & RT1W_UNSORTED) ? 1 : 0];
         return RT1W_OK;
     }
-    L.sorted = g_kernels_sorted[variant] != nullptr && !(p->flags & RT1W_UNSORTED);
-    L.cached = !L.sorted && g_kernels_cached[variant] != nullptr && c->n_nodes <= RT_LDS_NODE_CAP && (p->flags & RT1W_LDS_NODES);
-    L.sphere_media = !L.sorted && !L.cached && c->sphere_media && g_kernels_sphere_media[variant] != nullptr && !(p->flags & RT1W_CLASSIC_WALK);
-    L.ss = !L.sorted && !L.cached && g_kernels_ss[L.sphere_media ? 1 : 0][variant] != nullptr && !(p->flags & RT1W_UNSORTED);
-    L.hc = L.ss && c->walk_table && c->grid_ss_hc[L.sphere_media ? 1 : 0][variant] > 0 && !(p->flags & RT1W_NO_NODE_CACHE);
-    L.grid = L.sorted ? c->grid_sorted[variant] : (L.cached ? c->grid_cached[variant] : (L.hc ? c->grid_ss_hc[L.sphere_media ? 1 : 0][variant] : (L.ss ? c->grid_ss[L.sphere_media ? 1 : 0][variant] : (L.sphere_media ? c->grid_sphere_media[variant] : c->grid[variant]))));
-    L.block = L.sorted ? RT_SORT_BLOCK : RT_BLOCK;
+    auto built = [&](int w) { return c->k64[w][v].grid > 0; };
+    int w;
+    if (built(RT_WALK_SORTED) && !(fl & RT1W_UNSORTED)) w = RT_WALK_SORTED;
+    else if (built(RT_WALK_LDS_NODES) && c->n_nodes <= RT_LDS_NODE_CAP && (fl & RT1W_LDS_NODES)) w = RT_WALK_LDS_NODES;
+    else {
+        const int sm = (c->sphere_media && built(RT_WALK_SPHERE_MEDIA) && !(fl & RT1W_CLASSIC_WALK)) ? 1 : 0;
+        w = RT_WALK_PLAIN + sm;
+        if (built(RT_WALK_SS + sm) && !(fl & RT1W_UNSORTED))
+            w = (built(RT_WALK_SS_HC + sm) && !(fl & RT1W_NO_NODE_CACHE)) ? RT_WALK_SS_HC + sm : RT_WALK_SS + sm;
+    }
+    L.k = c->k64[w][v];
     return RT1W_OK;
 }
 
@@ -421,8 +478,17 @@ int lane_reserve_partial(RtLane& l, const RtLaunch& L) {
     return RT1W_OK;
 }
 
+/* the chunk sums of `n_chunks` chunks into the pixels of `out` (rt_resolve_kernel: carry bit 0 adds to earlier passes, bit 1 keeps raw sums) */
+void launch_resolve(hipStream_t stream, const double* partial, double* out, unsigned long long npix, uint32_t n_chunks, uint32_t spp,
+                    const rt1w_render_params* p, uint32_t carry) {
+    const unsigned int rb = 256;
+    hipLaunchKernelGGL(rt_resolve_kernel, dim3((unsigned int)((npix + rb - 1) / rb)), dim3(rb), 0, stream, partial, out, npix, n_chunks, spp,
+                       (p->flags & RT1W_OUT_SUM) ? 1u : 0u, carry);
+}
+
 /* enqueue on the lane's stream: counters, trace kernel, resolve into d_out, counters back to pinned memory.  No host wait. */
 int render_launch(rt1w_context* c, RtLane& l, const rt1w_render_params* p, const RtLaunch& L, double* d_out) {
+    const RtKernel& k = L.k;
     (void)hipEventRecord(l.ev0, l.stream);
     const uint32_t cpp = chunks_per_pass(L, l.partial_bytes < L.partial_budget ? l.partial_bytes : L.partial_budget); /* what the lane's buffer holds (lane_reserve_partial), within the caller's bound */
     const uint32_t n_pass = (L.f.n_chunks + cpp - 1u) / cpp;
@@ -433,44 +499,39 @@ int render_launch(rt1w_context* c, RtLane& l, const rt1w_render_params* p, const
     PF.n_chunks = L.f.n_chunks - c0 < cpp ? L.f.n_chunks - c0 : cpp;
     PF.sample_offset = L.f.sample_offset + c0 * L.f.chunk;
     PF.spp = (L.f.spp - c0 * L.f.chunk < PF.n_chunks * L.f.chunk) ? L.f.spp - c0 * L.f.chunk : PF.n_chunks * L.f.chunk;
-    hipLaunchKernelGGL(rt_init_counters_kernel, dim3(1), dim3(1), 0, l.stream, l.d_counters, (unsigned long long)L.grid * L.block, pass ? 1u : 0u);
-    if (L.f32 && L.jit) {
-        unsigned char view32[512];
-        if (!c->f32_scene || rt1w_internal_f32_view(c->f32_scene, view32, sizeof view32) == 0u) { rt1w::set_error("single-precision scene missing"); return RT1W_ERR_DEVICE; }
-        RtFrame frame = PF;
-        double* partial = l.d_partial;
-        unsigned long long* counters = l.d_counters;
-        void* args[] = {view32, &frame, &partial, &counters};
-        if (!hip_ok(hipModuleLaunchKernel(c->jit32_fn, (unsigned)L.grid, 1, 1, (unsigned)L.block, 1, 1, 0, l.stream, args, nullptr), "specialised f32 kernel launch")) return RT1W_ERR_DEVICE;
-    } else if (L.f32) {
-        if (!c->f32_scene || rt1w_internal_f32_launch(c->f32_scene, L.variant, L.pw ? 2 : (L.sorted ? 1 : 0), &PF, l.d_partial, l.d_counters, L.grid, l.stream) != 0) {
-            rt1w::set_error("single-precision kernel launch failed"); return RT1W_ERR_DEVICE;
+    hipLaunchKernelGGL(rt_init_counters_kernel, dim3(1), dim3(1), 0, l.stream, l.d_counters, (unsigned long long)k.grid * k.block, pass ? 1u : 0u);
+    RtSceneView view = c->view;
+    RtPwView pw = c->pw;
+    double* partial = l.d_partial;
+    unsigned long long* counters = l.d_counters;
+    void* args[] = {&view, &PF, &partial, &counters};
+    void* pw_args[] = {&view, &pw, &PF, &partial, &counters};
+    switch (k.form) {
+        case RT_FORM_F64: (void)hipLaunchKernel(k.fn, dim3(k.grid), dim3(k.block), args, 0, l.stream); break;
+        case RT_FORM_PW: (void)hipLaunchKernel(k.fn, dim3(k.grid), dim3(k.block), pw_args, 0, l.stream); break;
+        case RT_FORM_JIT:
+            if (!hip_ok(hipModuleLaunchKernel(k.jit, (unsigned)k.grid, 1, 1, (unsigned)k.block, 1, 1, 0, l.stream, args, nullptr), "specialised kernel launch")) return RT1W_ERR_DEVICE;
+            break;
+        case RT_FORM_F32_JIT: {
+            unsigned char view32[512];
+            if (!c->f32_scene || rt1w_internal_f32_view(c->f32_scene, view32, sizeof view32) == 0u) { rt1w::set_error("single-precision scene missing"); return RT1W_ERR_DEVICE; }
+            void* args32[] = {view32, &PF, &partial, &counters};
+            if (!hip_ok(hipModuleLaunchKernel(k.jit, (unsigned)k.grid, 1, 1, (unsigned)k.block, 1, 1, 0, l.stream, args32, nullptr), "specialised f32 kernel launch")) return RT1W_ERR_DEVICE;
+            break;
         }
-    } else if (L.ref) {
-        if (rt1w_internal_ref_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_ref_sizeof(1) != sizeof(RtFrame) ||
-            rt1w_internal_ref_launch(L.variant == 3 ? 1 : (L.sorted ? (L.variant == 0 ? 2 : 3) : 0), &c->view, &PF, l.d_partial, l.d_counters, L.grid, l.stream) != 0) {
-            rt1w::set_error("reference-stream kernel launch failed"); return RT1W_ERR_DEVICE;
-        }
-    } else if (L.jit) {
-        RtSceneView view = c->view;
-        RtFrame frame = PF;
-        double* partial = l.d_partial;
-        unsigned long long* counters = l.d_counters;
-        void* args[] = {&view, &frame, &partial, &counters};
-        if (!hip_ok(hipModuleLaunchKernel(c->jit_fn, (unsigned)L.grid, 1, 1, (unsigned)L.block, 1, 1, 0, l.stream, args, nullptr), "specialised kernel launch")) return RT1W_ERR_DEVICE;
-    } else if (L.pw) {
-        if (L.ss) hipLaunchKernelGGL(rt_render_kernel_pw_ss<RtCfgV5>, dim3(L.grid), dim3(L.block), 0, l.stream, c->view, c->pw, PF, l.d_partial, l.d_counters);
-        else hipLaunchKernelGGL(rt_render_kernel_pw<RtCfgV5>, dim3(L.grid), dim3(L.block), 0, l.stream, c->view, c->pw, PF, l.d_partial, l.d_counters);
-    } else {
-        hipLaunchKernelGGL(L.sorted ? g_kernels_sorted[L.variant] : (L.cached ? g_kernels_cached[L.variant] : (L.hc ? g_kernels_ss_hc[L.sphere_media ? 1 : 0][L.variant] : L.ss ? g_kernels_ss[L.sphere_media ? 1 : 0][L.variant] : (L.sphere_media ? g_kernels_sphere_media[L.variant] : g_kernels[L.variant]))),
-                           dim3(L.grid), dim3(L.block), 0, l.stream, c->view, PF, l.d_partial, l.d_counters);
+        case RT_FORM_F32:
+            if (!c->f32_scene || rt1w_internal_f32_launch(c->f32_scene, L.variant, k.mode, &PF, l.d_partial, l.d_counters, k.grid, l.stream) != 0) {
+                rt1w::set_error("single-precision kernel launch failed"); return RT1W_ERR_DEVICE;
+            }
+            break;
+        case RT_FORM_REF:
+            if (rt1w_internal_ref_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_ref_sizeof(1) != sizeof(RtFrame) ||
+                rt1w_internal_ref_launch(k.mode, &c->view, &PF, l.d_partial, l.d_counters, k.grid, l.stream) != 0) {
+                rt1w::set_error("reference-stream kernel launch failed"); return RT1W_ERR_DEVICE;
+            }
+            break;
     }
-    {
-        unsigned int rb = 256;
-        unsigned int rg = (unsigned int)((L.npix + rb - 1) / rb);
-        hipLaunchKernelGGL(rt_resolve_kernel, dim3(rg), dim3(rb), 0, l.stream, l.d_partial, d_out, L.npix, PF.n_chunks,
-                           L.f.spp, (p->flags & RT1W_OUT_SUM) ? 1u : 0u, (pass ? 1u : 0u) | (pass + 1u < n_pass ? 2u : 0u));
-    }
+    launch_resolve(l.stream, l.d_partial, d_out, L.npix, PF.n_chunks, L.f.spp, p, (pass ? 1u : 0u) | (pass + 1u < n_pass ? 2u : 0u));
     } /* passes */
     (void)hipEventRecord(l.ev1, l.stream);
     if (!hip_ok(hipGetLastError(), "kernel launch")) return RT1W_ERR_DEVICE;
@@ -488,77 +549,57 @@ int render_finish(RtLane& l, const RtLaunch& L, rt1w_stats* stats) {
         stats->segments = l.h_counters[1];
         stats->kernel_ms = ms;
         stats->chunk = L.f.chunk; stats->n_chunks = L.f.n_chunks;
-        stats->grid = (uint32_t)L.grid; stats->block = (uint32_t)L.block;
-        stats->variant = (uint32_t)L.variant; stats->sorted = ((L.sorted && !L.ss) ? 1u : 0u) | (L.cached ? 2u : 0u) | (L.jit ? 4u : 0u) | (L.ref ? 16u : 0u) | (L.f32 ? 32u : 0u) | (L.pw ? 128u : 0u) | (L.sphere_media ? 256u : 0u) | (L.ss ? 512u : 0u) | (L.hc ? 1024u : 0u);
+        stats->grid = (uint32_t)L.k.grid; stats->block = (uint32_t)L.k.block;
+        stats->variant = (uint32_t)L.variant; stats->sorted = L.k.bits;
     }
     return RT1W_OK;
 }
 
-/* load the specialised kernel of this context's scene: from the caches, or (allow_compile) from the compiler */
-int specialise(rt1w_context* c, bool allow_compile, rt1w::JitInfo& info) {
-    if (c->jit_fn) { info = rt1w::JitInfo(); info.key = c->jit_key; info.from_cache = true; return RT1W_OK; }
-    if (c->jit_src.empty()) { rt1w::set_error("scene has more than RT_JIT_MAX_NODES nodes: no specialised kernel"); return RT1W_ERR_UNSUPPORTED; }
+/* load the specialised kernel of this context's scene in the precision of `s`: from the caches, or (allow_compile) from the compiler */
+int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::JitInfo& info) {
+    if (s.k.jit) { info = rt1w::JitInfo(); info.key = s.key; info.from_cache = true; return RT1W_OK; }
+    if (s.src.empty()) { rt1w::set_error("scene has more than RT_JIT_MAX_NODES nodes: no specialised kernel"); return RT1W_ERR_UNSUPPORTED; }
+    const std::string what = s.what;
+    if (s.sticky) {
+        if (s.tried && !allow_compile) return RT1W_ERR_STATE;
+        if (s.failed) { rt1w::set_error(what + ": " + s.error); return RT1W_ERR_DEVICE; }
+        s.tried = true;
+    }
     std::vector<char> code;
-    int rc = rt1w::jit_get_code(c->jit_src, allow_compile, code, info);
-    c->jit_key = info.key;
-    if (rc < 0) { rt1w::set_error("specialised kernel: " + info.message); return rc; }
-    if (!hip_ok(hipModuleLoadData(&c->jit_mod, code.data()), "hipModuleLoadData(specialised kernel)")) {
-        c->jit_mod = nullptr;
-        if (!info.from_cache) return RT1W_ERR_DEVICE;
+    int rc = rt1w::jit_get_code(s.src, allow_compile && !(s.sticky && getenv("RT1W_NO_JIT")), code, info);
+    s.key = info.key;
+    if (rc < 0) {
+        rt1w::set_error(what + ": " + info.message);
+        if (s.sticky && allow_compile) { s.failed = true; s.error = info.message; }
+        return rc;
+    }
+    bool ok = hip_ok(hipModuleLoadData(&s.mod, code.data()), ("hipModuleLoadData(" + what + ")").c_str());
+    if (!ok) s.mod = nullptr;
+    if (!ok && info.from_cache && s.recompile_refused) {
         /* a cached object the driver refuses (truncated, foreign toolchain): forget it and, if allowed, compile afresh */
         rt1w::jit_invalidate(info);
         if (!allow_compile) return RT1W_ERR_DEVICE;
-        rc = rt1w::jit_get_code(c->jit_src, true, code, info, true);
-        if (rc < 0) { rt1w::set_error("specialised kernel: " + info.message); return rc; }
-        if (!hip_ok(hipModuleLoadData(&c->jit_mod, code.data()), "hipModuleLoadData(specialised kernel)")) { c->jit_mod = nullptr; return RT1W_ERR_DEVICE; }
+        if ((rc = rt1w::jit_get_code(s.src, true, code, info, true)) < 0) { rt1w::set_error(what + ": " + info.message); return rc; }
+        if (!(ok = hip_ok(hipModuleLoadData(&s.mod, code.data()), ("hipModuleLoadData(" + what + ")").c_str()))) s.mod = nullptr;
     }
-    hipFunction_t fn = nullptr;
-    if (!hip_ok(hipModuleGetFunction(&fn, c->jit_mod, "rt_jit_sorted"), "hipModuleGetFunction")) {
-        (void)hipModuleUnload(c->jit_mod); c->jit_mod = nullptr; return RT1W_ERR_DEVICE;
-    }
-    int per_cu = 0, max_threads = 0;
-    c->jit_block = RT_SORT_BLOCK;
-    if (hipFuncGetAttribute(&max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, fn) == hipSuccess && (max_threads == 512 || max_threads == 128)) c->jit_block = max_threads;
-    if (!hip_ok(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, c->jit_block, 0), "occupancy query")) per_cu = 1;
-    if (per_cu < 1) per_cu = 1;
-    hipDeviceProp_t prop;
-    if (!hip_ok(hipGetDeviceProperties(&prop, c->device), "hipGetDeviceProperties")) { (void)hipModuleUnload(c->jit_mod); c->jit_mod = nullptr; return RT1W_ERR_DEVICE; }
-    int vg = 0;
-    if (hipFuncGetAttribute(&vg, HIP_FUNC_ATTRIBUTE_NUM_REGS, fn) == hipSuccess) c->jit_vgprs = (uint32_t)vg;
-    c->jit_grid = prop.multiProcessorCount * per_cu;
-    c->jit_fn = fn;
-    return RT1W_OK;
-}
-
-/* the f32 build of the scene-specialised kernel (RT1W_PRECISION_F32): loaded from the kernel caches, compiled only when
- * `allow_compile` (rt1w_context_specialise).  A failure is remembered with its reason (rt1w_last_error at specialise time). */
-int specialise_f32(rt1w_context* c, bool allow_compile) {
-    if (c->jit32_fn) return RT1W_OK;
-    if (!c->jit_fn || c->jit32_src.empty()) return RT1W_ERR_STATE;
-    if (c->jit32_tried && !allow_compile) return RT1W_ERR_STATE;
-    if (c->jit32_failed) { rt1w::set_error("f32 specialised kernel: " + c->jit32_error); return RT1W_ERR_DEVICE; }
-    c->jit32_tried = true;
-    std::vector<char> code;
-    rt1w::JitInfo info;
-    int rc = rt1w::jit_get_code(c->jit32_src, allow_compile && !getenv("RT1W_NO_JIT"), code, info);
-    if (rc < 0) {
-        if (allow_compile) { c->jit32_failed = true; c->jit32_error = info.message; rt1w::set_error("f32 specialised kernel: " + info.message); }
-        return rc;
-    }
-    hipFunction_t fn = nullptr;
-    int per_cu = 0;
-    hipDeviceProp_t prop;
-    if (!hip_ok(hipModuleLoadData(&c->jit32_mod, code.data()), "hipModuleLoadData(f32 specialised kernel)") ||
-        !hip_ok(hipModuleGetFunction(&fn, c->jit32_mod, "rt_jit_sorted"), "hipModuleGetFunction(f32 specialised kernel)") ||
-        !hip_ok(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RT_SORT_BLOCK, 0), "occupancy query") ||
-        !hip_ok(hipGetDeviceProperties(&prop, c->device), "hipGetDeviceProperties")) {
-        if (c->jit32_mod) { (void)hipModuleUnload(c->jit32_mod); c->jit32_mod = nullptr; }
-        if (info.from_cache) rt1w::jit_invalidate(info);
-        c->jit32_failed = true; c->jit32_error = rt1w_last_error();
+    RtKernel k{s.form, RT_SORT_BLOCK, RT_BIT_SORTED | RT_BIT_JIT | (s.form == RT_FORM_F32_JIT ? RT_BIT_F32 : 0u)};
+    int max_threads = 0;
+    ok = ok && hip_ok(hipModuleGetFunction(&k.jit, s.mod, "rt_jit_sorted"), ("hipModuleGetFunction(" + what + ")").c_str());
+    if (ok && s.block_from_bounds && hipFuncGetAttribute(&max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, k.jit) == hipSuccess &&
+        (max_threads == 512 || max_threads == 128)) k.block = max_threads;
+    if (ok) ok = (k.grid = kernel_grid(c, k, 0)) > 0;
+    if (!ok) {
+        if (s.mod) (void)hipModuleUnload(s.mod);
+        s.mod = nullptr;
+        if (s.sticky) {
+            if (info.from_cache) rt1w::jit_invalidate(info);
+            s.failed = true; s.error = rt1w_last_error();
+        }
         return RT1W_ERR_DEVICE;
     }
-    c->jit32_fn = fn;
-    c->jit32_grid = prop.multiProcessorCount * (per_cu < 1 ? 1 : per_cu);
+    int vg = 0;
+    if (hipFuncGetAttribute(&vg, HIP_FUNC_ATTRIBUTE_NUM_REGS, k.jit) == hipSuccess) s.vgprs = (uint32_t)vg;
+    s.k = k;
     return RT1W_OK;
 }
 
@@ -581,12 +622,7 @@ int render_wavefront(rt1w_context* c, const rt1w_render_params* p, const RtLaunc
     (void)hipEventRecord(l.ev0, l.stream);
     const int rc = g_wf_render(&k);                /* enqueues generate / trace / shade / finish / chunk sums on the lane's stream */
     if (rc < 0) return rc;
-    {
-        unsigned int rb = 256;
-        unsigned int rg = (unsigned int)((L.npix + rb - 1) / rb);
-        hipLaunchKernelGGL(rt_resolve_kernel, dim3(rg), dim3(rb), 0, l.stream, l.d_partial, d_out, L.npix, L.f.n_chunks, L.f.spp,
-                           (p->flags & RT1W_OUT_SUM) ? 1u : 0u, 0u);
-    }
+    launch_resolve(l.stream, l.d_partial, d_out, L.npix, L.f.n_chunks, L.f.spp, p, 0u);
     (void)hipEventRecord(l.ev1, l.stream);
     if (!hip_ok(hipGetLastError(), "kernel launch") || !hip_ok(hipStreamSynchronize(l.stream), "wavefront render")) return RT1W_ERR_DEVICE;
     if (stats) {
@@ -602,23 +638,34 @@ int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, r
     /* a render this long repays the 1-8 s of the compiler: 2^35 paths where the gain is ~1.3x (scenes the generic sweep
      * handles), 2^32 where it is 1.5-2.3x (scenes the generic code hands to the stack walk).  RT1W_NO_JIT: never compile
      * behind the caller's back */
-    if (!c->jit_fn && !c->jit_failed && !c->jit_src.empty() && !(p->flags & (RT1W_GENERIC | RT1W_UNSORTED)) &&
+    if (!c->jit.k.jit && !c->jit.failed && !c->jit.src.empty() && !(p->flags & (RT1W_GENERIC | RT1W_UNSORTED)) &&
         (unsigned long long)p->tile_w * p->tile_h * p->spp >= (c->n_nodes <= RT_SWEEP_MAX_NODES ? (1ull << 35) : (1ull << 32)) &&
         !getenv("RT1W_NO_JIT")) {
         rt1w::JitInfo info;
-        if (specialise(c, true, info) < 0) c->jit_failed = true;
+        if (load_specialised(c, c->jit, true, info) < 0) c->jit.failed = true;
     }
     RtLaunch L;
     int rc = render_plan(c, p, L);
     if (rc < 0) return rc;
     RtLane& l = c->lane[0];
     if ((rc = lane_reserve_partial(l, L)) < 0) return rc;
-    if ((p->flags & RT1W_WAVEFRONT) && !L.jit && !L.sorted && !L.ref && !L.f32) {
+    /* the wavefront form stands in for the generic f64 kernels other than the reordering kernel */
+    if ((p->flags & RT1W_WAVEFRONT) && L.k.form == RT_FORM_F64 && !(L.k.bits & RT_BIT_SORTED)) {
         if (chunks_per_pass(L, L.partial_budget) < L.f.n_chunks) { rt1w::set_error("RT1W_WAVEFRONT renders in one pass: its chunk partial sums must fit the budget (rt1w_render_params.partial_mib)"); return RT1W_ERR_UNSUPPORTED; }
         return render_wavefront(c, p, L, d_out, stats);
     }
     if ((rc = render_launch(c, l, p, L, d_out)) < 0) return rc;
     return render_finish(l, L, stats);
+}
+
+/* the context's framebuffer, grown to at least `bytes` */
+int reserve_out(rt1w_context* c, size_t bytes) {
+    if (bytes <= c->out_bytes) return RT1W_OK;
+    if (c->d_out) (void)hipFree(c->d_out);
+    c->d_out = nullptr; c->out_bytes = 0;
+    if (!hip_ok(hipMalloc((void**)&c->d_out, bytes), "hipMalloc(framebuffer)")) return RT1W_ERR_NOMEM;
+    c->out_bytes = bytes;
+    return RT1W_OK;
 }
 
 } // namespace
@@ -659,103 +706,54 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
     v.root = s->flat_root; v.n_nodes = (uint32_t)s->flat_nodes.size(); v.n_lights = (uint32_t)s->flat_lights.size();
     v.n_materials = (uint32_t)s->materials.size(); v.n_textures = (uint32_t)s->textures.size(); v.pad = 0;
     v.camera = s->camera; v.background = s->background;
-    /* persistent grid: as many blocks as are resident at once */
     hipDeviceProp_t prop;
     if (!hip_ok(hipGetDeviceProperties(&prop, device_id), "hipGetDeviceProperties")) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
-    for (int v = 0; v < RT_N_VARIANTS; ++v) {
-        int per_cu = 0;
-        if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g_kernels[v], RT_BLOCK, 0), "occupancy query")) {
-            rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
-        }
-        if (per_cu < 1) per_cu = 1;
-        c->grid[v] = prop.multiProcessorCount * per_cu;
-        if (g_kernels_sphere_media[v]) {
-            per_cu = 0;
-            if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g_kernels_sphere_media[v], RT_BLOCK, 0), "occupancy query")) {
-                rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
-            }
-            if (per_cu < 1) per_cu = 1;
-            c->grid_sphere_media[v] = prop.multiProcessorCount * per_cu;
-        }
-        for (int sm = 0; sm < 2; ++sm) {
-            if (!g_kernels_ss[sm][v]) continue;
-            per_cu = 0;
-            if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g_kernels_ss[sm][v], RT_BLOCK, 0), "occupancy query")) {
-                rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
-            }
-            if (per_cu < 1) per_cu = 1;
-            c->grid_ss[sm][v] = prop.multiProcessorCount * per_cu;
-        }
-        if (g_kernels_cached[v]) {
-            per_cu = 0;
-            if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g_kernels_cached[v], RT_BLOCK, 0), "occupancy query")) {
-                rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
-            }
-            if (per_cu < 1) per_cu = 1;
-            c->grid_cached[v] = prop.multiProcessorCount * per_cu;
-        }
-        if (g_kernels_sorted[v]) {
-            per_cu = 0;
-            if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g_kernels_sorted[v], RT_SORT_BLOCK, 0), "occupancy query")) {
-                rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
-            }
-            if (per_cu < 1) per_cu = 1;
-            c->grid_sorted[v] = prop.multiProcessorCount * per_cu;
-        }
-    }
+    c->n_cu = prop.multiProcessorCount;
     c->has_media = s->has_media; c->has_tex = s->has_tex; c->has_msphere = s->has_msphere;
     c->sphere_media = s->has_media && s->media_bare_spheres;
     c->n_nodes = (uint32_t)s->flat_nodes.size();
     c->scope_depth = s->scope_depth;
     c->stack_need = s->stack_need;
     c->variant = rt_pick_variant(c->n_nodes, c->has_media, c->has_tex, c->has_msphere, c->scope_depth, s->walk_annotated != 0u);
+    /* the walk table and the kernels that keep its head in LDS: what a stack-walk scene's renders run (sphere scenes run the pair
+     * walk by default; the table serves their one-entry-per-step renders, RT1W_CLASSIC_WALK).  Built for every scene: a small
+     * scene's renders with a forced stack-walk variant (tests) go through it as well */
+    {
+        std::string why;
+        c->walk_table = build_walk_table(c, s->flat_nodes, s->flat_root, s->stack_need, why);
+    }
+    /* persistent grids of the f64 kernels: as many workgroups as are resident at once */
+    for (int w = 0; w < RT_N_WALKS; ++w)
+        for (int v = 0; v < RT_N_VARIANTS; ++v) {
+            if (!g_kernels[w][v] || ((w == RT_WALK_SS_HC || w == RT_WALK_SS_HC_SPHERE_MEDIA) && !c->walk_table)) continue;
+            RtKernel& k = c->k64[w][v];
+            k = RtKernel{RT_FORM_F64, g_walks[w].block, g_walks[w].bits, reinterpret_cast<const void*>(g_kernels[w][v])};
+            if (!(k.grid = kernel_grid(c, k, v))) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
+        }
     if (c->variant == 5 && s->stack_need + 1u <= (uint32_t)RT_PW_STACK) {
-        /* a sphere scene: records of the pair walk (rt_walk_pair.h); a scene outside its scope keeps the one-entry-per-step walk */
+        /* a sphere scene: records of the pair walk (rt_walk_pair.h); a scene outside its scope keeps the one-entry-per-step walk.  The
+         * kernel that also reorders the finished paths needs a shallower tree */
         std::vector<RtPwInner> pin; std::vector<RtPwGroup> pgr;
         if (rt_pw_build(s->flat_nodes, s->flat_root, pin, pgr, c->pw, c->pw_why)) {
-            int per_cu = 0;
-            if (!upload(&c->d_pw_inner, pin.data(), pin.size() * sizeof(RtPwInner)) || !upload(&c->d_pw_groups, pgr.data(), pgr.size() * sizeof(RtPwGroup)) ||
-                !hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rt_render_kernel_pw<RtCfgV5>, RT_BLOCK, 0), "occupancy query")) {
+            const int n_pw = s->stack_need + 1u <= (uint32_t)RT_PW_SS_STACK ? 2 : 1;
+            c->pw_k[0] = RtKernel{RT_FORM_PW, RT_BLOCK, RT_BIT_PW, reinterpret_cast<const void*>(rt_render_kernel_pw<RtCfgV5>)};
+            c->pw_k[1] = RtKernel{RT_FORM_PW, RT_BLOCK, RT_BIT_PW | RT_BIT_SS, reinterpret_cast<const void*>(rt_render_kernel_pw_ss<RtCfgV5>)};
+            if (!upload(&c->d_pw_inner, pin.data(), pin.size() * sizeof(RtPwInner)) || !upload(&c->d_pw_groups, pgr.data(), pgr.size() * sizeof(RtPwGroup))) {
                 rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
             }
             c->pw.inner = (const RtPwInner*)c->d_pw_inner; c->pw.groups = (const RtPwGroup*)c->d_pw_groups;
-            c->pw_grid = prop.multiProcessorCount * (per_cu < 1 ? 1 : per_cu);
-            c->pw_ok = true;
-            if (s->stack_need + 1u <= (uint32_t)RT_PW_SS_STACK) { /* shallow enough for the kernel that also reorders the finished paths */
-                per_cu = 0;
-                if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rt_render_kernel_pw_ss<RtCfgV5>, RT_BLOCK, 0), "occupancy query")) {
-                    rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
-                }
-                c->pw_ss_grid = prop.multiProcessorCount * (per_cu < 1 ? 1 : per_cu);
-            }
+            for (int i = 0; i < n_pw; ++i)
+                if (!(c->pw_k[i].grid = kernel_grid(c, c->pw_k[i], 5))) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
         }
     } else c->pw_why = "not a wrapper-free, media-free scene of more than 64 nodes, or its tree is deeper than the pair walk's stack";
-    {
-        /* the walk table and the kernels that keep its head in LDS: what a stack-walk scene's renders run (sphere scenes run the pair
-         * walk by default; the table serves their one-entry-per-step renders, RT1W_CLASSIC_WALK).  Built for every scene: a small
-         * scene's renders with a forced stack-walk variant (tests) go through it as well */
-        std::string why;
-        c->walk_table = build_walk_table(c, s->flat_nodes, s->flat_root, s->stack_need, why);
-        if (c->walk_table) {
-            for (int sm = 0; sm < 2; ++sm)
-                for (int v = 0; v < RT_N_VARIANTS; ++v) {
-                    if (!g_kernels_ss_hc[sm][v]) continue;
-                    int per_cu = 0;
-                    if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g_kernels_ss_hc[sm][v], RT_BLOCK, 0), "occupancy query")) {
-                        rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
-                    }
-                    c->grid_ss_hc[sm][v] = prop.multiProcessorCount * (per_cu < 1 ? 1 : per_cu);
-                }
-        }
-    }
     /* the opt-in modes' own data (f32 scene arrays, the wavefront form's walk records) are built at their first use:
      * ensure_f32_scene; the wavefront form's in librt1w_lab.so */
     c->h_nodes = s->flat_nodes; c->h_lights = s->flat_lights; c->h_materials = s->materials; c->h_textures = s->textures; c->h_perlin = s->perlin;
     if (rt1w::jit_eligible(*s)) {
-        c->jit_src = rt1w::jit_source(*s);
-        c->jit32_src = rt1w::jit_source(*s, true);
+        c->jit.src = rt1w::jit_source(*s);
+        c->jit32.src = rt1w::jit_source(*s, true);
         rt1w::JitInfo info;
-        (void)specialise(c, false, info); /* a cache hit is used from the first render on; a miss costs nothing */
+        (void)load_specialised(c, c->jit, false, info); /* a cache hit is used from the first render on; a miss costs nothing */
     }
     *out = c;
     return RT1W_OK;
@@ -772,8 +770,8 @@ void rt1w_context_destroy(rt1w_context* c) {
     if (c->d_pw_groups) (void)hipFree(c->d_pw_groups);
     lane_destroy(c->lane[0]);
     lane_destroy(c->lane[1]);
-    if (c->jit_mod) (void)hipModuleUnload(c->jit_mod);
-    if (c->jit32_mod) (void)hipModuleUnload(c->jit32_mod);
+    if (c->jit.mod) (void)hipModuleUnload(c->jit.mod);
+    if (c->jit32.mod) (void)hipModuleUnload(c->jit32.mod);
     if (c->ev_first) (void)hipEventDestroy(c->ev_first);
     delete c;
 }
@@ -782,16 +780,19 @@ int rt1w_context_specialise(rt1w_context* c, uint32_t flags, rt1w_specialise_inf
     if (!c) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
     rt1w::JitInfo info;
-    const bool had = c->jit_fn != nullptr;
-    int rc = specialise(c, !(flags & RT1W_SPECIALISE_CACHED_ONLY), info);
-    if (rc == RT1W_OK && c->jit_fn) (void)specialise_f32(c, !(flags & RT1W_SPECIALISE_CACHED_ONLY)); /* optional: a failure leaves f32 renders on the generic kernels */
+    const bool had = c->jit.k.jit != nullptr;
+    int rc = load_specialised(c, c->jit, !(flags & RT1W_SPECIALISE_CACHED_ONLY), info);
+    if (rc == RT1W_OK && c->jit.k.jit) { /* optional: a failure leaves f32 renders on the generic kernels */
+        rt1w::JitInfo info32;
+        (void)load_specialised(c, c->jit32, !(flags & RT1W_SPECIALISE_CACHED_ONLY), info32);
+    }
     if (out) {
         memset(out, 0, sizeof *out);
-        snprintf(out->key, sizeof out->key, "%s", c->jit_key.c_str());
-        out->active = c->jit_fn ? 1u : 0u;
+        snprintf(out->key, sizeof out->key, "%s", c->jit.key.c_str());
+        out->active = c->jit.k.jit ? 1u : 0u;
         out->from_cache = (had || info.from_cache) ? 1u : 0u;
         out->compile_ms = info.compile_ms;
-        out->grid = (uint32_t)c->jit_grid; out->vgprs = c->jit_vgprs;
+        out->grid = (uint32_t)c->jit.k.grid; out->vgprs = c->jit.vgprs;
     }
     return rc;
 }
@@ -818,12 +819,7 @@ int rt1w_render_u8(rt1w_context* c, const rt1w_render_params* p, uint8_t* out_rg
     auto t0 = std::chrono::steady_clock::now();
     size_t npix = (size_t)p->tile_w * p->tile_h;
     size_t bytes = npix * 3 * sizeof(double) + npix * 3; /* framebuffer + quantised image behind it */
-    if (bytes > c->out_bytes) {
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr; c->out_bytes = 0;
-        if (!hip_ok(hipMalloc((void**)&c->d_out, bytes), "hipMalloc(framebuffer)")) return RT1W_ERR_NOMEM;
-        c->out_bytes = bytes;
-    }
+    if ((rc = reserve_out(c, bytes)) < 0) return rc;
     rc = render_common(c, p, c->d_out, stats);
     if (rc < 0) return rc;
     uint8_t* d_u8 = reinterpret_cast<uint8_t*>(c->d_out + npix * 3);
@@ -846,7 +842,7 @@ int rt1w_render_rows(rt1w_context* c, const rt1w_render_params* p, uint32_t stri
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
     auto t0 = std::chrono::steady_clock::now();
     const uint32_t H = p->tile_h, W = p->tile_w;
-    const uint32_t tile_chunk = p->chunk ? p->chunk : ((c->variant >= 2) ? 1u : rt1w_default_chunk(W, H, p->spp)); /* the whole tile's chunking (rt1w_scene_default_chunk) */
+    const uint32_t tile_chunk = p->chunk ? p->chunk : default_chunk(c, p); /* the whole tile's chunking */
     if (strip_rows == 0) {
         /* about 16 strips, but never so thin that a strip has fewer than ~4M work items (pixel x sample chunk): the
          * persistent kernel needs that many to keep its tail short, and the chunking is the whole tile's by contract */
@@ -953,12 +949,7 @@ int rt1w_render(rt1w_context* c, const rt1w_render_params* p, double* out_rgb, r
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
     auto t0 = std::chrono::steady_clock::now();
     size_t bytes = (size_t)p->tile_w * p->tile_h * 3 * sizeof(double);
-    if (bytes > c->out_bytes) {
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr; c->out_bytes = 0;
-        if (!hip_ok(hipMalloc((void**)&c->d_out, bytes), "hipMalloc(framebuffer)")) return RT1W_ERR_NOMEM;
-        c->out_bytes = bytes;
-    }
+    if ((rc = reserve_out(c, bytes)) < 0) return rc;
     rc = render_common(c, p, c->d_out, stats);
     if (rc < 0) return rc;
     if (p->flags & RT1W_OUT_FRAME) {
@@ -1005,12 +996,8 @@ int aov_check_flags(uint32_t flags) {
 /* validate, launch the AOV kernel of the context's (or the forced) variant into d_out, wait, fill stats */
 int render_aov_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, rt1w_stats* stats) {
     int variant = c->variant;
-    if ((p->flags >> 8) & 0xFFu) {
-        variant = (int)((p->flags >> 8) & 0xFFu) - 1;
-        if (!rt_variant_valid(variant, c->n_nodes, c->has_media, c->has_tex, c->has_msphere, c->scope_depth)) {
-            rt1w::set_error("forced kernel variant does not cover this scene's features"); return RT1W_ERR_INVALID;
-        }
-    }
+    const int rc = forced_variant(c, p->flags, true, &variant);
+    if (rc < 0) return rc;
     RtFrame f;
     memset(&f, 0, sizeof f);
     f.width = p->width; f.height = p->height;
@@ -1057,12 +1044,7 @@ int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_ao
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
     auto t0 = std::chrono::steady_clock::now();
     const size_t bytes = (size_t)p->tile_w * p->tile_h * RT1W_AOV_CHANNELS * sizeof(double);
-    if (bytes > c->out_bytes) { /* the context's framebuffer, grown as rt1w_render_u8 grows it */
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr; c->out_bytes = 0;
-        if (!hip_ok(hipMalloc((void**)&c->d_out, bytes), "hipMalloc(framebuffer)")) return RT1W_ERR_NOMEM;
-        c->out_bytes = bytes;
-    }
+    if ((rc = reserve_out(c, bytes)) < 0) return rc; /* the context's framebuffer, as rt1w_render grows it */
     if ((rc = render_aov_common(c, p, c->d_out, stats)) < 0) return rc;
     if (!hip_ok(hipMemcpy(out_aov, c->d_out, bytes, hipMemcpyDeviceToHost), "AOV copy")) return RT1W_ERR_DEVICE;
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1167,10 +1149,10 @@ int rt1w_debug_stamps(rt1w_context* c, uint64_t out[16], int reset) {
     }
 #endif
     /* a scene-specialised kernel compiled with RT1W_JIT_STAMPS=1 in the environment carries its own counters */
-    if (c->jit_mod) {
+    if (c->jit.mod) {
         hipDeviceptr_t dptr = nullptr;
         size_t bytes = 0;
-        if (hipModuleGetGlobal(&dptr, &bytes, c->jit_mod, "g_stamp_total") == hipSuccess && bytes == 16 * sizeof(unsigned long long)) {
+        if (hipModuleGetGlobal(&dptr, &bytes, c->jit.mod, "g_stamp_total") == hipSuccess && bytes == 16 * sizeof(unsigned long long)) {
             unsigned long long h[16];
             (void)hipMemcpy(h, dptr, sizeof h, hipMemcpyDeviceToHost);
             for (int i = 0; i < 16; ++i) out[i] += h[i];

@@ -52,26 +52,26 @@ __global__ __launch_bounds__(RT_SORT_BLOCK, (Cfg::tex || Cfg::media || Cfg::msph
 
 /* called by context.hip; `view` / `frame` are the bytes of its RtSceneView / RtFrame (same layout: same headers) */
 /* mode: 0 sweep (plain kernel), 1 stack walk (plain kernel), 2 reordering kernel V0, 3 reordering kernel with every feature */
-extern "C" int rt1w_internal_ref_blocks_per_cu(int stack_walk) {
+extern "C" int rt1w_internal_ref_blocks_per_cu(int mode) {
     int per_cu = 0;
-    if (stack_walk >= 2) {
-        hipError_t e2 = stack_walk == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref_sorted<rtref::RtCfgV0>, RT_SORT_BLOCK, 0)
-                                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref_sorted<rtref::CfgSweep>, RT_SORT_BLOCK, 0);
+    if (mode >= 2) {
+        hipError_t e2 = mode == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref_sorted<rtref::RtCfgV0>, RT_SORT_BLOCK, 0)
+                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref_sorted<rtref::CfgSweep>, RT_SORT_BLOCK, 0);
         return e2 == hipSuccess && per_cu > 0 ? per_cu : 1;
     }
-    hipError_t e = stack_walk ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref<rtref::CfgStack>, RT_BLOCK, 0)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref<rtref::CfgSweep>, RT_BLOCK, 0);
+    hipError_t e = mode ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref<rtref::CfgStack>, RT_BLOCK, 0)
+                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref<rtref::CfgSweep>, RT_BLOCK, 0);
     return e == hipSuccess && per_cu > 0 ? per_cu : 1;
 }
-extern "C" int rt1w_internal_ref_launch(int stack_walk, const void* view, const void* frame, double* partial, unsigned long long* counters,
+extern "C" int rt1w_internal_ref_launch(int mode, const void* view, const void* frame, double* partial, unsigned long long* counters,
                                         int grid, hipStream_t stream) {
     rtref::RtSceneView v;
     rtref::RtFrame f;
     memcpy(&v, view, sizeof v);
     memcpy(&f, frame, sizeof f);
-    if (stack_walk == 2) hipLaunchKernelGGL(rtref::rt_render_kernel_ref_sorted<rtref::RtCfgV0>, dim3(grid), dim3(RT_SORT_BLOCK), 0, stream, v, f, partial, counters);
-    else if (stack_walk == 3) hipLaunchKernelGGL(rtref::rt_render_kernel_ref_sorted<rtref::CfgSweep>, dim3(grid), dim3(RT_SORT_BLOCK), 0, stream, v, f, partial, counters);
-    else if (stack_walk) hipLaunchKernelGGL(rtref::rt_render_kernel_ref<rtref::CfgStack>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, partial, counters);
+    if (mode == 2) hipLaunchKernelGGL(rtref::rt_render_kernel_ref_sorted<rtref::RtCfgV0>, dim3(grid), dim3(RT_SORT_BLOCK), 0, stream, v, f, partial, counters);
+    else if (mode == 3) hipLaunchKernelGGL(rtref::rt_render_kernel_ref_sorted<rtref::CfgSweep>, dim3(grid), dim3(RT_SORT_BLOCK), 0, stream, v, f, partial, counters);
+    else if (mode) hipLaunchKernelGGL(rtref::rt_render_kernel_ref<rtref::CfgStack>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, partial, counters);
     else hipLaunchKernelGGL(rtref::rt_render_kernel_ref<rtref::CfgSweep>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, partial, counters);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
