@@ -250,6 +250,10 @@ typedef struct rt1w_stats {
                               wavefront form; bit 4: reference-stream kernel (RT1W_RNG_REFERENCE); bit 5: f32 kernel; bit 7: pair walk
                               (sphere scenes); bit 8: sphere-media build of the stack walk; bit 9: finished paths reordered across the
                               workgroup at the end of every slice of the stack walk; bit 10: most visited node records in LDS (walk table) */
+    uint32_t passes;       /* launches of the trace kernel the call made: a render whose chunk partial sums exceed the budget
+                              (rt1w_render_params.partial_mib) runs as several sample passes; rt1w_render_rows sums them over its
+                              strips; 1 for the wavefront form and the AOV entries */
+    uint32_t reserved;     /* 0 */
 } rt1w_stats;
 
 /* default work-item size for a (tile, spp): deterministic, documented in DESIGN.md.  This is the scene-independent rule (what the

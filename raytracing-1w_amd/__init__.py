@@ -77,7 +77,8 @@ class SpecialiseInfo(C.Structure):
 class Stats(C.Structure):
     _fields_ = [("paths", C.c_uint64), ("segments", C.c_uint64), ("kernel_ms", C.c_double),
                 ("total_ms", C.c_double), ("chunk", C.c_uint32), ("n_chunks", C.c_uint32),
-                ("grid", C.c_uint32), ("block", C.c_uint32), ("variant", C.c_uint32), ("sorted", C.c_uint32)]
+                ("grid", C.c_uint32), ("block", C.c_uint32), ("variant", C.c_uint32), ("sorted", C.c_uint32),
+                ("passes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class SceneInfo(C.Structure):
@@ -424,20 +425,23 @@ class Context:
         _ck(_lib.rt1w_render(self._h, C.byref(p), out.ctypes.data_as(_P), C.byref(st)))
         return out, {n: getattr(st, n) for n, _ in Stats._fields_}
 
-    def render_u8(self, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, chunk=0, reference_stream=False):
+    def render_u8(self, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, chunk=0, reference_stream=False,
+                  partial_mib=0):
         """Quantised on the device, rows top-down as the reference prints them: uint8 [tile_h, tile_w, 3]."""
-        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, False, reference_stream=reference_stream)
+        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, False, reference_stream=reference_stream,
+                         partial_mib=partial_mib)
         out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.uint8)
         st = Stats()
         _ck(_lib.rt1w_render_u8(self._h, C.byref(p), out.ctypes.data_as(_P), C.byref(st)))
         return out, {n: getattr(st, n) for n, _ in Stats._fields_}
 
     def render_rows(self, width, height, spp, strip_rows=0, u8=False, progress=None, max_depth=50, tile=None,
-                    sample_offset=0, global_seed=0, chunk=0, out_sum=False, out=None, no_node_cache=False):
+                    sample_offset=0, global_seed=0, chunk=0, out_sum=False, out=None, no_node_cache=False, partial_mib=0):
         """Strip-wise render from the top row down with D2H overlapped (rt1w_render_rows).  `progress(rows_done, rows_total)`
         is called as strips land; returning a true value cancels (raises Rt1wError with code ERR_CANCELLED).
         Returns the same arrays as render() (u8=False) or render_u8() (u8=True)."""
-        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, no_node_cache=no_node_cache)
+        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, no_node_cache=no_node_cache,
+                         partial_mib=partial_mib)
         if out is None:
             out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.uint8 if u8 else np.float64)
         assert out.flags.c_contiguous and out.shape == (p.tile_h, p.tile_w, 3) and out.dtype == (np.uint8 if u8 else np.float64)
@@ -448,10 +452,10 @@ class Context:
         return out, {n: getattr(st, n) for n, _ in Stats._fields_}
 
     def render_device(self, d_ptr, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, chunk=0,
-                      out_sum=False, variant=None, unsorted=False, generic=False, strips=None, f32=False):
+                      out_sum=False, variant=None, unsorted=False, generic=False, strips=None, f32=False, partial_mib=0):
         """Same, into device memory `d_ptr` (int address, e.g. torch tensor .data_ptr()); packed tile rows."""
         p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, variant, unsorted, False, generic,
-                         False, strips, f32=f32)
+                         False, strips, f32=f32, partial_mib=partial_mib)
         st = Stats()
         _ck(_lib.rt1w_render_device(self._h, C.byref(p), C.c_void_p(d_ptr), C.byref(st)))
         return {n: getattr(st, n) for n, _ in Stats._fields_}

@@ -106,6 +106,7 @@ struct RtLane {
     unsigned long long* d_counters = nullptr;
     unsigned long long* h_counters = nullptr; /* pinned */
     void* d_strip = nullptr; void* h_strip = nullptr; size_t strip_bytes = 0; /* rt1w_render_rows: device strip + pinned host strip */
+    uint32_t passes = 0; /* sample passes of the launch in flight (render_launch), reported by render_finish */
 };
 
 /* How a kernel is launched: render_launch switches on it */
@@ -492,6 +493,7 @@ int render_launch(rt1w_context* c, RtLane& l, const rt1w_render_params* p, const
     (void)hipEventRecord(l.ev0, l.stream);
     const uint32_t cpp = chunks_per_pass(L, l.partial_bytes < L.partial_budget ? l.partial_bytes : L.partial_budget); /* what the lane's buffer holds (lane_reserve_partial), within the caller's bound */
     const uint32_t n_pass = (L.f.n_chunks + cpp - 1u) / cpp;
+    l.passes = n_pass;
     for (uint32_t pass = 0; pass < n_pass; ++pass) {
     /* this pass's chunks as a frame of their own: samples [c0 * chunk, ...) of the call, absolute sample indices through sample_offset */
     RtFrame PF = L.f;
@@ -551,6 +553,7 @@ int render_finish(RtLane& l, const RtLaunch& L, rt1w_stats* stats) {
         stats->chunk = L.f.chunk; stats->n_chunks = L.f.n_chunks;
         stats->grid = (uint32_t)L.k.grid; stats->block = (uint32_t)L.k.block;
         stats->variant = (uint32_t)L.variant; stats->sorted = L.k.bits;
+        stats->passes = l.passes; stats->reserved = 0u;
     }
     return RT1W_OK;
 }
@@ -630,6 +633,7 @@ int render_wavefront(rt1w_context* c, const rt1w_render_params* p, const RtLaunc
         (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
         stats->paths = L.npix * L.f.spp; stats->segments = k.h_segments ? *k.h_segments : 0ull; stats->kernel_ms = ms;
         stats->chunk = L.f.chunk; stats->n_chunks = L.f.n_chunks;
+        stats->passes = 1u; stats->reserved = 0u;
     }
     return RT1W_OK;
 }
@@ -915,7 +919,7 @@ int rt1w_render_rows(rt1w_context* c, const rt1w_render_params* p, uint32_t stri
         if (r < 0) return r;
         total.paths += st.paths; total.segments += st.segments;
         total.chunk = st.chunk; total.n_chunks = st.n_chunks; total.grid = st.grid; total.block = st.block;
-        total.variant = st.variant; total.sorted = st.sorted;
+        total.variant = st.variant; total.sorted = st.sorted; total.passes += st.passes;
         if (i + 1u == n_strips) { float ms = 0.f; (void)hipEventElapsedTime(&ms, c->ev_first, l.ev1); total.kernel_ms = ms; }
         if (format == RT1W_ROWS_U8) memcpy((uint8_t*)out + (size_t)F.top * W * 3, l.h_strip, (size_t)F.rows * W * 3);
         else memcpy((double*)out + (size_t)(H - F.top - F.rows) * W * 3, l.h_strip, (size_t)F.rows * W * 3 * sizeof(double));
@@ -1024,6 +1028,7 @@ int render_aov_common(rt1w_context* c, const rt1w_render_params* p, double* d_ou
         stats->chunk = p->spp; stats->n_chunks = 1u;
         stats->grid = launch[0]; stats->block = launch[1];
         stats->variant = (uint32_t)variant;
+        stats->passes = 1u;
     }
     return RT1W_OK;
 }

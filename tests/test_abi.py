@@ -69,8 +69,10 @@ def test_every_declared_entry_cites_the_reference():
         assert re.search(r"\.rs:\d+", block), f"no reference citation near {fn}"
 
 
-def test_struct_layouts_match_between_python_and_c(rt):
-    assert C.sizeof(rt.RenderParams) == 64 and C.sizeof(rt.Stats) == 56 and C.sizeof(rt.SceneInfo) == 56
+def test_struct_layouts_match_between_python_and_c_with_stats_passes(rt):
+    """rt1w_stats is 64 bytes: the 56 of its first layout, then `passes` and a reserved word."""
+    assert C.sizeof(rt.RenderParams) == 64 and C.sizeof(rt.Stats) == 64 and C.sizeof(rt.SceneInfo) == 56
+    assert rt.Stats.sorted.offset == 52 and rt.Stats.passes.offset == 56 and rt.Stats.reserved.offset == 60
     assert C.sizeof(rt.SpecialiseInfo) == 48
     for i, t in enumerate((rt.RenderParams, rt.Stats, rt.SceneInfo, rt.SpecialiseInfo)):
         assert rt._lib.rt1w_abi_sizeof(i) == C.sizeof(t)

@@ -285,6 +285,7 @@ def test_c2_random_scene_1200x800_500spp_crops(rt, gpu_ctx_factory):
     W, H, spp = 1200, 800, 500
     full, st = ctx.render(W, H, spp)
     assert st["paths"] == W * H * spp and np.isfinite(full).all()
+    assert st["chunk"] == 1 and st["passes"] == 2        # 500 chunks of 23.04 MB partial sums, 372 of them per 8 GiB pass
     for tile in ((600, 400, 8, 8), (100, 60, 8, 4)):
         b, sb = orc.flat_render(sc, W, H, spp, tile=tile, chunk=st["chunk"])
         x0, y0, w, h = tile
@@ -952,30 +953,39 @@ def test_precompiled_kernels_load_on_a_host_without_the_runtime_compiler(rt):
 def test_one_sample_per_work_item_and_sample_passes(rt, gpu_ctx_factory):
     """Scenes on the stack-walk kernels render with ONE sample per work item by default (rt1w_scene_default_chunk: free lanes of a wave restart
     together on neighbouring pixels; the pixel sum is the reference's own sequential sum, main.rs:966-992), and a render whose chunk partial
-    sums would not fit the budget (default 8 GiB; here `partial_mib` makes it a few MiB) runs as several passes over sample ranges.  What
+    sums would not fit the budget (default 8 GiB; here `partial_mib` makes it 1-2 MiB) runs as several passes over sample ranges.  What
     must hold: the default chunk is 1 and the frame equals the CPU build of the core with chunk 1 bit for bit; the same frame whatever the
-    budget (1 pass, 3 passes, a pass per sample) incl. a ragged last pass, raw sums (RT1W_OUT_SUM), a sample offset and a tile; the small
-    scenes keep the scene-independent rule; equal segment counts throughout."""
-    for arm, aspect, W, H, spp in ((0, 1.5, 96, 64, 10), (7, None, 64, 64, 7)):
+    budget (1 pass, 3 or more passes with a ragged last one, a pass per sample), raw sums (RT1W_OUT_SUM), a sample offset and a tile,
+    chunks of 3 samples with a ragged last chunk split over passes; the small scenes keep the scene-independent rule; equal segment
+    counts throughout; stats.passes as chunks_per_pass (context.hip) counts them.  The frames are large enough (589 824 and 614 400 B
+    of partial sums per chunk) that one chunk fills a 1 MiB pass and three fill 2 MiB."""
+    def passes(W, H, spp, chunk, mib):
+        n_chunks = -(-spp // chunk)
+        per_pass = min(max(1, (mib << 20) // (W * H * 24)), n_chunks)
+        return -(-n_chunks // per_pass)
+    for arm, aspect, W, H, spp in ((0, 1.5, 192, 128, 10), (7, None, 160, 160, 7)):
         sc = rt.Scene.reference(arm, build_seed=1, aspect_ratio=aspect)
         assert sc.default_chunk(W, H, spp) == 1 and sc.default_chunk(1200, 800, 500) == 1
         ctx = gpu_ctx_factory(sc)
         full, st = ctx.render(W, H, spp)
-        assert st["chunk"] == 1 and st["n_chunks"] == spp
+        assert st["chunk"] == 1 and st["n_chunks"] == spp and st["passes"] == 1
         cpu, sc_ = orc.flat_render(sc, W, H, spp, chunk=1)
         assert st["segments"] == sc_["segments"] and np.array_equal(full, cpu, equal_nan=True), arm
-        per_sample_mib = W * H * 24 / 2 ** 20
-        for mib in (max(1, int(4 * per_sample_mib)), max(1, int(per_sample_mib * 1.01) + 0)):     # ~3 passes (ragged), ~one pass per sample
+        assert passes(W, H, spp, 1, 2) >= 3 and spp % 3 != 0 and passes(W, H, spp, 1, 1) == spp and passes(W, H, spp, 3, 1) >= 3
+        for mib in (2, 1):                                                                          # 3 chunks per pass (ragged), one pass per sample
             got, sg = ctx.render(W, H, spp, partial_mib=mib)
+            assert sg["passes"] == passes(W, H, spp, 1, mib), (arm, mib, sg["passes"])
             assert sg["segments"] == st["segments"] and sg["n_chunks"] == spp and np.array_equal(got, full, equal_nan=True), (arm, mib)
         raw, sr = ctx.render(W, H, spp, out_sum=True, partial_mib=1)
-        assert np.array_equal(rt.resolve(raw, spp), full, equal_nan=True), arm
+        assert sr["passes"] == spp and np.array_equal(rt.resolve(raw, spp), full, equal_nan=True), arm
         off, so = ctx.render(W, H, 4, sample_offset=3, tile=(8, 16, 32, 24), partial_mib=1)
         cpu_off, _ = orc.flat_render(sc, W, H, 4, sample_offset=3, tile=(8, 16, 32, 24), chunk=1)
         assert np.array_equal(off, cpu_off, equal_nan=True), arm
-        three, s3 = ctx.render(W, H, spp, chunk=3, partial_mib=1)                                   # explicit chunks also run in passes
-        cpu3, _ = orc.flat_render(sc, W, H, spp, chunk=3)
-        assert s3["chunk"] == 3 and np.array_equal(three, cpu3, equal_nan=True), arm
+        cpu3, s3c = orc.flat_render(sc, W, H, spp, chunk=3)
+        for mib in (1, 2):                                                                          # explicit chunks also run in passes
+            three, s3 = ctx.render(W, H, spp, chunk=3, partial_mib=mib)
+            assert s3["chunk"] == 3 and s3["passes"] == passes(W, H, spp, 3, mib), (arm, mib, s3["passes"])
+            assert s3["segments"] == s3c["segments"] and np.array_equal(three, cpu3, equal_nan=True), (arm, mib)
         ctx.close()
     small = rt.Scene.reference(5, build_seed=1)
     assert small.default_chunk(600, 600, 1000) == rt.default_chunk(600, 600, 1000) > 1
