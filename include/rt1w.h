@@ -325,6 +325,63 @@ int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_ao
 /* same, into device memory on the context's GPU (e.g. a torch tensor); no host copy.  Synchronises the context's stream before returning. */
 int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d_out_aov, rt1w_stats* stats);
 
+/* ---- feature-guided denoiser: the consumer of the feature buffers above ----
+ * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) over an image and its first-hit feature buffers.
+ * Replaces nothing of the reference, which reaches a clean image by sample count alone (10 000 spp for final_scene, src/main.rs:939).
+ *   frame double[h][w][3], the layout of rt1w_render: means, not sums.   aov double[h][w][8], the layout of rt1w_render_aov.
+ *   out   double[h][w][3].   A tile is filtered as an image of its own: taps outside the three buffers are skipped, nothing is known of
+ *   the pixels around it.  A host that tiles one image over several GPUs denoises the gathered frame.
+ * Prepare, per pixel p.  Albedo A_p = max(albedo, eps) per channel, eps = 0.01 (also where the albedo is not finite); with
+ *   RT1W_DENOISE_KEEP_ALBEDO A_p = 1.  Value c_p = frame / A_p per channel (demodulation: texture detail stays out of the blur; the
+ *   albedo channel holds the emission on lights and the background on misses, so those come through clean).  Luminance
+ *   l_p = (0.2126 r + 0.7152 g) + 0.0722 b of c_p.  Unit normal u_p = n_p / |n_p| of the mean normal, (0, 0, 0) where |n_p|^2 is 0,
+ *   underflows or is not finite (a miss).  Depth z_p and coverage v_p as they are.
+ * Levels i = 0 .. iterations - 1, step s = 2^i.  c'_p = sum_q w(p, q) c_q / sum_q w(p, q) over the taps q = p + s (dx, dy),
+ *   dx, dy = -2 .. 2, that lie inside the image, in row order (dy outer, dx inner); l' is the luminance of c'.  The centre tap has
+ *   w = h(0, 0) whatever the guides say, so the denominator is never 0.  For the others
+ *     w = (h(dx, dy) * w_normal) * k((x_depth + x_colour) + x_coverage),
+ *   which is h * w_normal * w_depth * w_colour * w_coverage with each falloff w_x = k(x) and the three multiplied as one k of the sum:
+ *     h          = b(|dx|) * b(|dy|), b = 3/8, 1/4, 1/16 (B3 spline);
+ *     w_normal   = 1 if u_p and u_q are both (0, 0, 0); else clamp(u_p . u_q, 0, 1) ^ P by binary exponentiation, where P is
+ *                  `sigma_normal` truncated to an integer and clamped to 1 .. 4096 (default 32): exactly 0 for perpendicular or
+ *                  opposed normals and where exactly one normal is (0, 0, 0);
+ *     x_depth    = 0 if z_p == z_q (two misses: both +inf); +inf if exactly one is +inf; else |z_p - z_q| / (max(z_p, z_q) *
+ *                  sigma_depth) (default 0.1);
+ *     x_colour   = (l_p - l_q)^2 / sigma_i^2 of the current level's values, sigma_i = sigma_colour / 2^i (default 1, halved at every
+ *                  level as in the paper); level 0 has NO colour term (x_colour = 0 * (l_p - l_q)^2): the paper's remedy for fireflies
+ *                  -- a firefly in the centre pixel would otherwise reject all its neighbours and survive;
+ *     x_coverage = (v_p - v_q)^2 * 16 (sigma_coverage = 1/4, not a parameter);
+ *     k(x)       = 1 for x <= 0; exp(-x) for 0 < x < 40, evaluated as 2^-n * T13(n ln 2 - x), n = trunc(x / ln 2 + 1/2), T13 the
+ *                  Taylor polynomial of exp of degree 13 (csrc/rt_denoise.h: rt_dn_falloff); exactly 0 for x >= 40, +inf and NaN.
+ *   A tap is added only if w > 0: a tap whose value or weight is not finite contributes nothing (a value that is not finite has a
+ *   luminance that is not finite, so x_colour and with it w is 0 or NaN).  A centre pixel whose luminance is not finite is passed through
+ *   every level unchanged.
+ * After the last level out = c * A_p per channel.
+ * Arithmetic: + - * /, sqrt, comparisons, selects and integer operations in one fixed order, without FMA contraction, each output pixel
+ * whole by one lane: bit-identical to the CPU build of the same code (librt1w_lab.so: rt1w_lab_denoise_host).
+ * Known limit: the guides describe the first hit.  What is seen through a glass sphere or reflected in a metal one is filtered with the
+ * glass or metal surface's guides. */
+#define RT1W_DENOISE_KEEP_ALBEDO 1u      /* no demodulation */
+typedef struct rt1w_denoise_params {
+    uint32_t width, height;              /* of the three buffers */
+    uint32_t iterations;                 /* 0 = 5, at most 8 (RT1W_ERR_INVALID beyond) */
+    uint32_t flags;                      /* 0 or RT1W_DENOISE_KEEP_ALBEDO */
+    double sigma_colour, sigma_normal, sigma_depth;   /* 0 = default; negative or not finite: RT1W_ERR_INVALID */
+} rt1w_denoise_params;
+/* host buffers, through the context's device buffers (two colour buffers of 32 B per pixel and a guide buffer of 64 B per pixel, which
+ * grow on demand and are freed with the context).  `out` may be `frame`.  stats: kernel_ms = HIP-event time of the prepare pass and
+ * the level launches, total_ms the whole call, passes 1, grid / block of the level kernel, paths = pixels. */
+int rt1w_denoise(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, double* out, rt1w_stats* stats);
+/* same on device memory of the context's GPU (e.g. torch tensors); d_out may equal d_frame.  Synchronises the context's stream before returning. */
+int rt1w_denoise_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, void* d_out, rt1w_stats* stats);
+/* One call: rt1w_render_device of the tile into a context buffer, rt1w_render_aov_device of the same tile, spp, sample_offset and
+ * global_seed, the filter, one device->host copy into out_rgb[tile_h][tile_w][3].  Bit-identical to composing the three public calls.
+ * `d` may be NULL (all defaults); its width / height must be 0 or the tile's.  Takes the flags rt1w_render takes except RT1W_OUT_SUM,
+ * RT1W_OUT_FRAME, RT1W_RNG_REFERENCE (the AOV entries have no reference-stream form) and RT1W_PROBE_COHERENT; interleaved strips
+ * (strip_rows != 0) and RT1W_PRECISION_F32 are refused too: all RT1W_ERR_INVALID.  stats are the render's, with the AOV and filter kernel
+ * times added to kernel_ms; total_ms is the whole call; grid / block are the level kernel's. */
+int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, double* out_rgb, rt1w_stats* stats);
+
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory
  * mapping that several single-GPU processes fill with RT1W_OUT_FRAME. */
@@ -369,7 +426,7 @@ int rt1w_quantize(const double* means, uint64_t n_values, uint8_t* out);
 int64_t rt1w_format_ppm(const double* means, uint32_t width, uint32_t height, char* buf, uint64_t cap);
 
 /* sizeof of the ABI structs as this library was compiled (bindings check their own layout against it):
- * 0 rt1w_render_params, 1 rt1w_stats, 2 rt1w_scene_info, 3 rt1w_specialise_info; 0 for anything else */
+ * 0 rt1w_render_params, 1 rt1w_stats, 2 rt1w_scene_info, 3 rt1w_specialise_info, 4 rt1w_denoise_params; 0 for anything else */
 uint32_t rt1w_abi_sizeof(int what);
 
 /* ---- diagnostics ---- */

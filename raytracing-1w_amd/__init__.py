@@ -55,6 +55,7 @@ CLASSIC_WALK = 128  # sphere scenes: the one-entry-per-step walk instead of the 
 WAVEFRONT = 16  # big scenes: path state queued in HBM, trace / shade kernels per bounce
 SPECIALISE_CACHED_ONLY = 1
 AOV_CHANNELS = 8  # rt1w_render_aov: albedo rgb, normal xyz, depth, coverage per pixel
+DENOISE_KEEP_ALBEDO = 1  # rt1w_denoise: no albedo demodulation
 
 
 class Rt1wError(RuntimeError):
@@ -151,6 +152,21 @@ PROGRESS_FN = C.CFUNCTYPE(C.c_int, _P, C.c_uint32, C.c_uint32)
 _sig("rt1w_render_rows", C.c_int, _P, C.POINTER(RenderParams), C.c_uint32, C.c_int, _P, PROGRESS_FN, _P, C.POINTER(Stats))
 _sig("rt1w_render_aov", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(Stats))
 _sig("rt1w_render_aov_device", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(Stats))
+
+
+class DenoiseParams(C.Structure):
+    """rt1w_denoise_params (include/rt1w.h): 0 in iterations or a sigma means the default."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32),
+                ("sigma_colour", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
+
+
+def _denoise_params(width, height, iterations=0, keep_albedo=False, sigma_colour=0.0, sigma_normal=0.0, sigma_depth=0.0, flags=0):
+    return DenoiseParams(width, height, iterations, flags | (DENOISE_KEEP_ALBEDO if keep_albedo else 0), sigma_colour, sigma_normal, sigma_depth)
+
+
+_sig("rt1w_denoise", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_denoise_device", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_render_denoised", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(DenoiseParams), _P, C.POINTER(Stats))
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -477,6 +493,40 @@ class Context:
         _ck(_lib.rt1w_render_aov_device(self._h, C.byref(p), C.c_void_p(d_ptr), C.byref(st)))
         return {n: getattr(st, n) for n, _ in Stats._fields_}
 
+    def denoise(self, frame, aov, with_stats=False, **kw):
+        """Feature-guided filter (rt1w_denoise) of a float64 frame [h, w, 3] with its feature buffers [h, w, 8] (render_aov): the
+        denoised [h, w, 3].  kw: iterations, keep_albedo, sigma_colour, sigma_normal, sigma_depth (0 = default)."""
+        f = np.ascontiguousarray(frame, dtype=np.float64)
+        a = np.ascontiguousarray(aov, dtype=np.float64)
+        if f.ndim != 3 or f.shape[2] != 3 or a.shape != f.shape[:2] + (AOV_CHANNELS,):
+            raise ValueError("frame must be [h, w, 3] and aov [h, w, 8]")
+        p = _denoise_params(f.shape[1], f.shape[0], **kw)
+        out = np.empty_like(f)
+        st = Stats()
+        _ck(_lib.rt1w_denoise(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), out.ctypes.data_as(_P), C.byref(st)))
+        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+
+    def denoise_device(self, d_frame, d_aov, d_out, width, height, **kw):
+        """Same on device memory (int addresses of height * width * 3 / 8 / 3 float64, e.g. torch tensors' .data_ptr()); d_out may
+        equal d_frame.  Returns the stats dict."""
+        p = _denoise_params(width, height, **kw)
+        st = Stats()
+        _ck(_lib.rt1w_denoise_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_out), C.byref(st)))
+        return {n: getattr(st, n) for n, _ in Stats._fields_}
+
+    def render_denoised(self, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, denoise=None, flags=0,
+                        strips=None, precision=0, with_stats=False, **kw):
+        """Render, feature buffers and filter in one call (rt1w_render_denoised): float64 [tile_h, tile_w, 3].  `denoise`: dict of
+        the keywords of Context.denoise, None = defaults; `flags`: raw RT1W_* render flags; other kw as Context.render's."""
+        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, 0, False, kw.pop("variant", None), strips=strips, **kw)
+        p.flags |= flags
+        p.precision = precision
+        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
+        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_denoised(self._h, C.byref(p), C.byref(d) if d is not None else None, out.ctypes.data_as(_P), C.byref(st)))
+        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+
     def debug_aabb(self, cases):
         """cases[n, 14] = min3, max3, origin3, direction3, t_min, t_max -> (literal[n], fast[n]) from the device."""
         a = np.ascontiguousarray(cases, dtype=np.float64).reshape(-1, 14)
@@ -550,6 +600,25 @@ def aov_host(scene, width, height, spp, tile=None, sample_offset=0, global_seed=
     rc = f(scene._h, C.byref(p), out.ctypes.data_as(_P))
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_aov_host")
+    return out
+
+
+def denoise_host(frame, aov, **kw):
+    """CPU twin of Context.denoise (librt1w_lab.so: rt1w_lab_denoise_host, the same rt_denoise.h built for the host): the array the
+    GPU must equal bit for bit.  No GPU needed."""
+    lab = load_lab()
+    fn = lab.rt1w_lab_denoise_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(DenoiseParams), _P, _P, _P]
+    f = np.ascontiguousarray(frame, dtype=np.float64)
+    a = np.ascontiguousarray(aov, dtype=np.float64)
+    if f.ndim != 3 or f.shape[2] != 3 or a.shape != f.shape[:2] + (AOV_CHANNELS,):
+        raise ValueError("frame must be [h, w, 3] and aov [h, w, 8]")
+    p = _denoise_params(f.shape[1], f.shape[0], **kw)
+    out = np.empty_like(f)
+    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), out.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_denoise_host")
     return out
 
 

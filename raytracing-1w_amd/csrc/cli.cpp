@@ -5,7 +5,9 @@
  * values as defaults.
  *   rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B]
  *        [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic]
- *        [--reference-stream] [--f32] [--near-far] [--sah]
+ *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N]]
+ * --denoise renders through rt1w_render_denoised: the frame, its first-hit feature buffers and the feature-guided filter in one call
+ * (default 5 levels), then the PPM of the filtered frame.
  * --reference-stream draws from the reference's own StdRng per pixel (RT1W_RNG_REFERENCE): `rt1w --reference-stream` prints
  * what `cargo run` of the reference prints, byte for byte (Cornell arm, 600x600, 100 spp).  --f32: RT1W_PRECISION_F32.
  * --near-far: rt1w_scene_set_walk_order(RT1W_WALK_NEAR_FAR).  --sah: rt1w_scene_set_bvh_build(RT1W_BVH_SAH).
@@ -27,7 +29,8 @@ static int fail(const char* what) {
 
 int main(int argc, char** argv) {
     int arm = 5, device = 0;
-    bool specialise = false, generic = false, reference_stream = false, f32 = false, near_far = false, sah = false;
+    bool specialise = false, generic = false, reference_stream = false, f32 = false, near_far = false, sah = false, denoise = false;
+    long denoise_iterations = 0;
     long width = -1, height = -1, spp = -1, depth = 50; /* MAX_DEPTH main.rs:801 */
     unsigned long long build_seed = 1, seed = 0;
     std::string out_path, earth_path;
@@ -53,8 +56,10 @@ int main(int argc, char** argv) {
         else if (a == "--f32") f32 = true;
         else if (a == "--near-far") near_far = true;
         else if (a == "--sah") sah = true;
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iterations") { denoise = true; denoise_iterations = std::atol(next("--denoise-iterations")); }
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N]]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -117,7 +122,17 @@ int main(int argc, char** argv) {
     };
     rt1w_stats st;
     std::fprintf(stderr, "rt1w: scene arm %d, %ldx%ld, %ld spp, depth %ld\n", arm, width, height, spp, depth);
-    if (rt1w_render_rows(ctx, &p, 0, RT1W_ROWS_U8, img.data(), on_rows, &sink, &st) < 0) return fail("render");
+    if (denoise) {
+        rt1w_denoise_params d;
+        std::memset(&d, 0, sizeof d);
+        d.iterations = denoise_iterations > 0 ? (uint32_t)denoise_iterations : 0u;
+        std::vector<double> means((size_t)width * height * 3);
+        if (rt1w_render_denoised(ctx, &p, &d, means.data(), &st) < 0) return fail("render");
+        /* quantised as the reference prints it (color.rs:56-65), top row (j = height - 1) first (main.rs:957-960) */
+        for (uint32_t r = 0; r < p.height; ++r)
+            if (rt1w_quantize(means.data() + (size_t)(p.height - 1u - r) * p.width * 3, (uint64_t)p.width * 3, img.data() + (size_t)r * p.width * 3) < 0) return fail("quantize");
+        on_rows(&sink, p.height, p.height);
+    } else if (rt1w_render_rows(ctx, &p, 0, RT1W_ROWS_U8, img.data(), on_rows, &sink, &st) < 0) return fail("render");
     std::fprintf(stderr, "\nDone\nrt1w: %.1f ms kernels, %.1f Mpaths/s, %.2f segments/path, kernel variant V%u%s\n", st.kernel_ms,
                  (double)st.paths / st.kernel_ms / 1e3, (double)st.segments / (double)st.paths, st.variant, (st.sorted & 4u) ? " (scene-specialised)" : "");
     if (o != stdout) std::fclose(o);

@@ -41,6 +41,11 @@ extern "C" unsigned rt1w_internal_ref_sizeof(int what);
 /* aov.hip: the first-hit feature buffers (rt1w_render_aov); launch[0..1] = grid, block of the launch */
 extern "C" int rt1w_internal_aov_launch(int variant, const void* view, const void* frame, double* out, hipStream_t stream, unsigned launch[2]);
 extern "C" unsigned rt1w_internal_aov_sizeof(int what);
+/* denoise.hip: the filter of rt1w_denoise; enqueues the prepare pass and the levels; 0, -1 launch failure, -2 parameters refused */
+extern "C" int rt1w_internal_denoise_launch(uint32_t w, uint32_t h, uint32_t iterations, uint32_t flags, double sigma_colour, double sigma_normal,
+                                            double sigma_depth, const double* frame, const double* aov, double* out, void* col_a, void* col_b,
+                                            void* guide, hipStream_t stream, unsigned launch[2]);
+extern "C" unsigned rt1w_internal_denoise_sizeof(int what); /* bytes per pixel of 0 a colour buffer, 1 the guide buffer */
 /* context_f32.hip: the kernels in single precision (RT1W_PRECISION_F32) and the f32 copies of the scene arrays */
 extern "C" int rt1w_internal_f32_create(const void* nodes, uint32_t n_nodes, const void* lights, uint32_t n_lights, const void* materials,
                                         uint32_t n_materials, const void* textures, uint32_t n_textures, const void* perlin, uint32_t n_perlin,
@@ -193,6 +198,7 @@ struct rt1w_context {
     void* d_textures = nullptr; void* d_perlin = nullptr; void* d_images = nullptr;
     RtSceneView view{};
     double* d_out = nullptr; size_t out_bytes = 0;
+    void* dn_buf[3] = {nullptr, nullptr, nullptr}; size_t dn_bytes[3] = {0, 0, 0}; /* rt1w_denoise: two colour buffers and the guide buffer */
     RtKernel k64[RT_N_WALKS][RT_N_VARIANTS] = {}; /* g_kernels, queried at creation; the node-cache walks only with a walk table */
     bool walk_table = false; uint32_t walk_table_first = 0;
     bool sphere_media = false; /* every medium of the scene is bounded by a bare Sphere: the sphere-media walks serve */
@@ -766,7 +772,7 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
 void rt1w_context_destroy(rt1w_context* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    void* bufs[] = {c->d_nodes, c->d_lights, c->d_materials, c->d_textures, c->d_perlin, c->d_images, c->d_out};
+    void* bufs[] = {c->d_nodes, c->d_lights, c->d_materials, c->d_textures, c->d_perlin, c->d_images, c->d_out, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2]};
     if (c->wf_state && g_wf_destroy) g_wf_destroy(c->wf_state);
     for (void* b : bufs) if (b) (void)hipFree(b);
     rt1w_internal_f32_destroy(c->f32_scene);
@@ -1066,12 +1072,150 @@ int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d
     return RT1W_OK;
 }
 
+/* ---- feature-guided denoiser (include/rt1w.h: rt1w_denoise) ---- */
+} // extern "C"
+namespace {
+int denoise_validate(const rt1w_context* c, const rt1w_denoise_params* p) {
+    if (!c || !p) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (p->width == 0 || p->height == 0 || p->width > 0x40000000u || p->height > 0x40000000u) { rt1w::set_error("denoise: width and height must be 1 .. 2^30"); return RT1W_ERR_INVALID; }
+    if (p->iterations > 8u) { rt1w::set_error("denoise: at most 8 iterations"); return RT1W_ERR_INVALID; }
+    if (p->flags & ~RT1W_DENOISE_KEEP_ALBEDO) { rt1w::set_error("denoise: unknown flag (flags: 0 or RT1W_DENOISE_KEEP_ALBEDO)"); return RT1W_ERR_INVALID; }
+    const double sig[3] = {p->sigma_colour, p->sigma_normal, p->sigma_depth};
+    for (double v : sig)
+        if (!(v >= 0.0) || v > 1.7976931348623157e308) { rt1w::set_error("denoise: a sigma must be finite and >= 0 (0 = default)"); return RT1W_ERR_INVALID; }
+    return RT1W_OK;
+}
+/* the context's two colour buffers and guide buffer, grown to the image */
+int denoise_reserve(rt1w_context* c, size_t npix) {
+    for (int k = 0; k < 3; ++k) {
+        const size_t bytes = npix * rt1w_internal_denoise_sizeof(k == 2 ? 1 : 0);
+        if (bytes <= c->dn_bytes[k]) continue;
+        if (c->dn_buf[k]) (void)hipFree(c->dn_buf[k]);
+        c->dn_buf[k] = nullptr; c->dn_bytes[k] = 0;
+        if (!hip_ok(hipMalloc(&c->dn_buf[k], bytes), "hipMalloc(denoise buffers)")) return RT1W_ERR_NOMEM;
+        c->dn_bytes[k] = bytes;
+    }
+    return RT1W_OK;
+}
+/* prepare pass and levels on lane 0's stream, wait; *kernel_ms (optional) their HIP-event time, launch[0..1] grid / block of the level kernel */
+int denoise_common(rt1w_context* c, const rt1w_denoise_params* p, const double* d_frame, const double* d_aov, double* d_out, double* kernel_ms,
+                   unsigned launch[2]) {
+    int rc = denoise_reserve(c, (size_t)p->width * p->height);
+    if (rc < 0) return rc;
+    RtLane& l = c->lane[0];
+    (void)hipEventRecord(l.ev0, l.stream);
+    rc = rt1w_internal_denoise_launch(p->width, p->height, p->iterations, p->flags, p->sigma_colour, p->sigma_normal, p->sigma_depth, d_frame, d_aov,
+                                      d_out, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], l.stream, launch);
+    if (rc == -2) { rt1w::set_error("denoise: parameters refused"); return RT1W_ERR_INVALID; }
+    if (rc != 0) { rt1w::set_error("denoise kernel launch failed"); return RT1W_ERR_DEVICE; }
+    (void)hipEventRecord(l.ev1, l.stream);
+    if (!hip_ok(hipStreamSynchronize(l.stream), "denoise kernels")) return RT1W_ERR_DEVICE;
+    if (kernel_ms) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
+        *kernel_ms = ms;
+    }
+    return RT1W_OK;
+}
+void denoise_stats(const rt1w_denoise_params* p, double kernel_ms, const unsigned launch[2], rt1w_stats* stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->paths = (uint64_t)p->width * p->height;
+    stats->kernel_ms = kernel_ms;
+    stats->grid = launch[0]; stats->block = launch[1];
+    stats->passes = 1u;
+}
+} // namespace
+extern "C" {
+
+int rt1w_denoise(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, double* out, rt1w_stats* stats) {
+    int rc = denoise_validate(c, p);
+    if (rc < 0) return rc;
+    if (!frame || !aov || !out) { rt1w::set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t npix = (size_t)p->width * p->height;
+    /* the context's framebuffer holds the frame (filtered in place) and, behind it, the feature buffers */
+    if ((rc = reserve_out(c, npix * (3 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
+    double* d_frame = c->d_out;
+    double* d_aov = c->d_out + npix * 3;
+    if (!hip_ok(hipMemcpy(d_frame, frame, npix * 3 * sizeof(double), hipMemcpyHostToDevice), "denoise: frame copy")) return RT1W_ERR_DEVICE;
+    if (!hip_ok(hipMemcpy(d_aov, aov, npix * RT1W_AOV_CHANNELS * sizeof(double), hipMemcpyHostToDevice), "denoise: feature buffer copy")) return RT1W_ERR_DEVICE;
+    double ms = 0.0;
+    unsigned launch[2] = {0u, 0u};
+    if ((rc = denoise_common(c, p, d_frame, d_aov, d_frame, &ms, launch)) < 0) return rc;
+    if (!hip_ok(hipMemcpy(out, d_frame, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "denoise: result copy")) return RT1W_ERR_DEVICE;
+    if (stats) {
+        denoise_stats(p, ms, launch, stats);
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT1W_OK;
+}
+
+int rt1w_denoise_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, void* d_out, rt1w_stats* stats) {
+    int rc = denoise_validate(c, p);
+    if (rc < 0) return rc;
+    if (!d_frame || !d_aov || !d_out) { rt1w::set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    auto t0 = std::chrono::steady_clock::now();
+    double ms = 0.0;
+    unsigned launch[2] = {0u, 0u};
+    if ((rc = denoise_common(c, p, (const double*)d_frame, (const double*)d_aov, (double*)d_out, &ms, launch)) < 0) return rc;
+    if (stats) {
+        denoise_stats(p, ms, launch, stats);
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT1W_OK;
+}
+
+int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, double* out_rgb, rt1w_stats* stats) {
+    int rc = validate(c, p);
+    if (rc < 0) return rc;
+    if (!out_rgb) { rt1w::set_error("null output"); return RT1W_ERR_INVALID; }
+    static const struct { uint32_t bit; const char* name; } refused[] = {
+        {RT1W_OUT_SUM, "RT1W_OUT_SUM"}, {RT1W_OUT_FRAME, "RT1W_OUT_FRAME"}, {RT1W_RNG_REFERENCE, "RT1W_RNG_REFERENCE"}, {RT1W_PROBE_COHERENT, "RT1W_PROBE_COHERENT"}};
+    for (const auto& k : refused)
+        if (p->flags & k.bit) { rt1w::set_error(std::string(k.name) + " does not apply to rt1w_render_denoised"); return RT1W_ERR_INVALID; }
+    if (p->strip_rows) { rt1w::set_error("rt1w_render_denoised takes a contiguous tile (strip_rows must be 0): denoise the gathered frame with rt1w_denoise"); return RT1W_ERR_INVALID; }
+    if (p->precision != RT1W_PRECISION_F64) { rt1w::set_error("RT1W_PRECISION_F32 does not apply to rt1w_render_denoised (the filter is f64 only)"); return RT1W_ERR_INVALID; }
+    rt1w_denoise_params dp;
+    memset(&dp, 0, sizeof dp);
+    if (d) dp = *d;
+    if ((dp.width && dp.width != p->tile_w) || (dp.height && dp.height != p->tile_h)) { rt1w::set_error("denoise: width / height must be 0 or the tile's"); return RT1W_ERR_INVALID; }
+    dp.width = p->tile_w; dp.height = p->tile_h;
+    if ((rc = denoise_validate(c, &dp)) < 0) return rc;
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    auto t0 = std::chrono::steady_clock::now();
+    const size_t npix = (size_t)p->tile_w * p->tile_h;
+    if ((rc = reserve_out(c, npix * (3 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
+    double* d_frame = c->d_out;
+    double* d_aov = c->d_out + npix * 3;
+    rt1w_stats st;
+    memset(&st, 0, sizeof st);
+    if ((rc = render_common(c, p, d_frame, &st)) < 0) return rc;
+    rt1w_render_params ap = *p; /* the feature buffers of the same tile, samples and seed, by the scene's own variant */
+    ap.flags = 0u;
+    rt1w_stats sa;
+    if ((rc = render_aov_common(c, &ap, d_aov, &sa)) < 0) return rc;
+    double ms = 0.0;
+    unsigned launch[2] = {0u, 0u};
+    if ((rc = denoise_common(c, &dp, d_frame, d_aov, d_frame, &ms, launch)) < 0) return rc;
+    if (!hip_ok(hipMemcpy(out_rgb, d_frame, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "denoised frame copy")) return RT1W_ERR_DEVICE;
+    if (stats) {
+        *stats = st;
+        stats->kernel_ms = st.kernel_ms + sa.kernel_ms + ms;
+        stats->grid = launch[0]; stats->block = launch[1];
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT1W_OK;
+}
+
 uint32_t rt1w_abi_sizeof(int what) {
     switch (what) {
         case 0: return (uint32_t)sizeof(rt1w_render_params);
         case 1: return (uint32_t)sizeof(rt1w_stats);
         case 2: return (uint32_t)sizeof(rt1w_scene_info);
         case 3: return (uint32_t)sizeof(rt1w_specialise_info);
+        case 4: return (uint32_t)sizeof(rt1w_denoise_params);
         default: return 0u;
     }
 }

@@ -1,0 +1,55 @@
+/* denoise_host.cpp -- the CPU twin of the filter kernels (denoise.hip): rt_denoise.h compiled for the host (g++, -ffp-contract=off
+ * like every build of the core).  Diagnostics library only (librt1w_lab.so): the expected side of the GPU tests' bit-equality checks
+ * and what the CPU tier's property and quality tests run.  librt1w.so keeps no CPU path. */
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "rt1w.h"
+#include "rt_denoise.h"
+#include "walk_lab.h"
+
+namespace {
+/* rows dealt round-robin over at most 16 threads: every pixel is computed whole by one thread, so the result does not depend on it */
+template <class F>
+void for_rows(uint32_t h, F f) {
+    unsigned hw = std::thread::hardware_concurrency();
+    uint32_t n_threads = hw == 0u ? 1u : (hw > 16u ? 16u : hw);
+    if (n_threads > h) n_threads = h;
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back([=]() { for (uint32_t y = t; y < h; y += n_threads) f(y); });
+    for (uint32_t y = 0; y < h; y += n_threads) f(y);
+    for (auto& th : pool) th.join();
+}
+} // namespace
+
+extern "C" int rt1w_lab_denoise_host(const rt1w_denoise_params* p, const double* frame, const double* aov, double* out) {
+    if (!p || !frame || !aov || !out) return RT1W_ERR_INVALID;
+    RtDnParams P;
+    if (!rt_dn_make_params(p->width, p->height, p->iterations, p->flags, p->sigma_colour, p->sigma_normal, p->sigma_depth, P)) return RT1W_ERR_INVALID;
+    const size_t n = (size_t)P.w * P.h;
+    std::vector<RtDnCol> a(n), b(n);
+    std::vector<RtDnGuide> g(n);
+    for_rows(P.h, [&](uint32_t y) {
+        for (uint32_t x = 0; x < P.w; ++x) {
+            const size_t i = (size_t)y * P.w + x;
+            rt_dn_prepare_pixel(P, frame + i * 3, aov + i * 8, a[i], g[i]);
+        }
+    });
+    RtDnCol* src = a.data();
+    RtDnCol* dst = b.data();
+    for (uint32_t level = 0; level < P.levels; ++level) {
+        const RtDnGlobalSrc s{src, g.data(), P.w};
+        const bool last = level + 1u == P.levels;
+        for_rows(P.h, [&](uint32_t y) {
+            for (uint32_t x = 0; x < P.w; ++x) {
+                const size_t i = (size_t)y * P.w + x;
+                const RtDnCol c = rt_dn_level_pixel(P, s, x, y, level);
+                if (last) rt_dn_finish_pixel(c, g[i], out + i * 3);
+                else dst[i] = c;
+            }
+        });
+        RtDnCol* t = src; src = dst; dst = t;
+    }
+    return RT1W_OK;
+}

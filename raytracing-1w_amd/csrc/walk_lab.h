@@ -35,6 +35,10 @@ int rt1w_lab_trace(rt1w_lab* l, int mode, const uint32_t params[4], int repeats,
  * RT1W_ERR_STATE if a traversal stack overflowed */
 int rt1w_lab_aov_host(const rt1w_scene* s, const rt1w_render_params* p, double* out);
 
+/* CPU twin of rt1w_denoise (denoise_host.cpp: rt_denoise.h built for the host): the same double[h][w][3] from host buffers, no GPU.
+ * RT1W_OK, or RT1W_ERR_INVALID as the device entry (null pointers, zero sizes, iterations > 8, unknown flags, bad sigmas) */
+int rt1w_lab_denoise_host(const rt1w_denoise_params* p, const double* frame, const double* aov, double* out);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
