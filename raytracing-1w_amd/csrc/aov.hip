@@ -1,8 +1,8 @@
 /* aov.hip -- the first-hit feature buffers of rt1w_render_aov (include/rt1w.h): one kernel per scene variant V0..V5 over rt_aov.h.
  *
  * Kept out of context.hip, inside its own namespace (the pattern of context_ref.hip), so that none of the render kernels' code objects
- * and none of the run-time compiler's inputs moves with it.  The host half (validation, buffers, timing) is in context.hip, which
- * calls the launcher below.
+ * and none of the run-time compiler's inputs moves with it.  The host half (validation, buffers, launch, timing) is in context.hip, which
+ * gets the kernel's host handle and its grid from the two exports below.
  *
  * Work mapping: one lane per pixel, looping over the pixel's samples in order -- the sums have one fixed order, the same as the CPU
  * twin's (aov_host.cpp), and no partial-sum buffer is needed.  A wave covers an 8 x 8 block of the tile, so its 64 camera rays are
@@ -13,7 +13,6 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <string.h>
 #include <type_traits>
 
 namespace rtaov {
@@ -59,27 +58,16 @@ inline unsigned aov_grid(const RtFrame& f) {
     return (unsigned)((blocks8 + RT_BLOCK / 64u - 1u) / (RT_BLOCK / 64u));
 #endif
 }
+typedef void (*kernel_t)(RtSceneView, RtFrame, double*);
+static kernel_t const g_aov[RT_N_VARIANTS] = {rt_aov_kernel<RtCfgV0>, rt_aov_kernel<RtCfgV1>, rt_aov_kernel<RtCfgV2>,
+                                              rt_aov_kernel<RtCfgV3>, rt_aov_kernel<RtCfgV4>, rt_aov_kernel<RtCfgV5>};
 } // namespace rtaov
 
-/* called by context.hip; `view` / `frame` are the bytes of its RtSceneView / RtFrame (same headers, same layout: checked through
- * rt1w_internal_aov_sizeof).  Enqueues one launch on `stream`; grid / block of it in launch[0..1].  0 or -1. */
-extern "C" int rt1w_internal_aov_launch(int variant, const void* view, const void* frame, double* out, hipStream_t stream, unsigned launch[2]) {
-    using namespace rtaov;
-    RtSceneView v;
-    RtFrame f;
-    memcpy(&v, view, sizeof v);
-    memcpy(&f, frame, sizeof f);
-    const unsigned grid = aov_grid(f);
-    launch[0] = grid; launch[1] = RT_BLOCK;
-    switch (variant) {
-        case 0: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV0>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
-        case 1: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV1>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
-        case 2: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV2>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
-        case 3: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV3>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
-        case 4: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV4>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
-        case 5: hipLaunchKernelGGL(rt_aov_kernel<RtCfgV5>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, out); break;
-        default: return -1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+/* the kernel of a variant for context.hip, which launches it with RT_BLOCK work-items on (its RtSceneView, its RtFrame, out): same
+ * headers, same layout, checked through rt1w_internal_aov_sizeof.  nullptr: no such variant */
+extern "C" const void* rt1w_internal_aov_kernel(int variant) {
+    return variant >= 0 && variant < RT_N_VARIANTS ? reinterpret_cast<const void*>(rtaov::g_aov[variant]) : nullptr;
 }
+/* the workgroups of that launch; `frame` = the bytes of the RtFrame */
+extern "C" unsigned rt1w_internal_aov_grid(const void* frame) { return rtaov::aov_grid(*static_cast<const rtaov::RtFrame*>(frame)); }
 extern "C" unsigned rt1w_internal_aov_sizeof(int what) { return what == 0 ? (unsigned)sizeof(rtaov::RtSceneView) : (unsigned)sizeof(rtaov::RtFrame); }

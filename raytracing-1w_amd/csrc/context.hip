@@ -33,13 +33,13 @@
 #include "jit.h"
 #include "rt1w_internal.h"
 
-/* context_ref.hip: the plain kernels built with the reference's own random stream (RT1W_RNG_REFERENCE) */
-extern "C" int rt1w_internal_ref_blocks_per_cu(int mode); /* mode: RtKernel.mode of the reference-stream kernels */
-extern "C" int rt1w_internal_ref_launch(int mode, const void* view, const void* frame, double* partial, unsigned long long* counters,
-                                        int grid, hipStream_t stream);
-extern "C" unsigned rt1w_internal_ref_sizeof(int what);
-/* aov.hip: the first-hit feature buffers (rt1w_render_aov); launch[0..1] = grid, block of the launch */
-extern "C" int rt1w_internal_aov_launch(int variant, const void* view, const void* frame, double* out, hipStream_t stream, unsigned launch[2]);
+/* The companion units' kernels come here as host handles (nullptr: no such kernel) and are launched like this unit's own.
+ * context_ref.hip: the kernels built with the reference's own random stream (RT1W_RNG_REFERENCE), by mode (render_plan) */
+extern "C" const void* rt1w_internal_ref_kernel(int mode);
+extern "C" unsigned rt1w_internal_ref_sizeof(int what); /* bytes of its 0 RtSceneView, 1 RtFrame */
+/* aov.hip: the first-hit feature buffers (rt1w_render_aov), by variant; workgroups of RT_BLOCK work-items that cover the frame's tile */
+extern "C" const void* rt1w_internal_aov_kernel(int variant);
+extern "C" unsigned rt1w_internal_aov_grid(const void* frame);
 extern "C" unsigned rt1w_internal_aov_sizeof(int what);
 /* denoise.hip: the filter of rt1w_denoise; enqueues the prepare pass and the levels; 0, -1 launch failure, -2 parameters refused */
 extern "C" int rt1w_internal_denoise_launch(uint32_t w, uint32_t h, uint32_t iterations, uint32_t flags, double sigma_colour, double sigma_normal,
@@ -51,11 +51,9 @@ extern "C" int rt1w_internal_f32_create(const void* nodes, uint32_t n_nodes, con
                                         uint32_t n_materials, const void* textures, uint32_t n_textures, const void* perlin, uint32_t n_perlin,
                                         const void* view64, void** out);
 extern "C" void rt1w_internal_f32_destroy(void* h);
-extern "C" int rt1w_internal_f32_blocks_per_cu(int variant, int mode); /* mode: RtKernel.mode of the f32 kernels (0 plain, 1 reordering, 2 pair walk) */
+extern "C" const void* rt1w_internal_f32_kernel(int variant, int mode); /* mode: 0 plain, 1 reordering, 2 pair walk (render_plan) */
 extern "C" int rt1w_internal_f32_pw(void* h, unsigned stack_cap); /* 1: the scene has f32 pair-walk records and fits `stack_cap` entries */
-extern "C" unsigned rt1w_internal_f32_view(void* h, void* out, unsigned cap); /* bytes of the f32 RtSceneView (kernel argument) */
-extern "C" int rt1w_internal_f32_launch(void* h, int variant, int mode, const void* frame, double* partial, unsigned long long* counters, int grid,
-                                        hipStream_t stream);
+extern "C" const void* rt1w_internal_f32_view(void* h, int what); /* the kernels' 0 f32 RtSceneView, 1 f32 RtPwView (nullptr: none) */
 
 #include "rt_kernels.h"
 #include "rt_walk_table.h"
@@ -114,31 +112,21 @@ struct RtLane {
     uint32_t passes = 0; /* sample passes of the launch in flight (render_launch), reported by render_finish */
 };
 
-/* How a kernel is launched: render_launch switches on it */
-enum RtForm {
-    RT_FORM_F64,     /* a render kernel of this unit: (view, frame, partial, counters) */
-    RT_FORM_PW,      /* a pair-walk kernel of this unit (rt_walk_pair.h): (view, pair-walk view, frame, partial, counters) */
-    RT_FORM_JIT,     /* the scene-specialised kernel (jit.cpp), from its module */
-    RT_FORM_F32,     /* context_f32.hip: rt1w_internal_f32_launch(variant, mode) */
-    RT_FORM_F32_JIT, /* the f32 build of the scene-specialised kernel */
-    RT_FORM_REF,     /* context_ref.hip: rt1w_internal_ref_launch(mode) */
-};
-
 /* the rt1w_stats.sorted bits (include/rt1w.h) a kernel reports; bit 3, the wavefront form, is filled by wavefront.hip */
 enum : uint32_t {
     RT_BIT_SORTED = 1u, RT_BIT_LDS_NODES = 2u, RT_BIT_JIT = 4u, RT_BIT_REF = 16u, RT_BIT_F32 = 32u, RT_BIT_PW = 128u, RT_BIT_SPHERE_MEDIA = 256u,
     RT_BIT_SS = 512u, RT_BIT_HC = 1024u
 };
 
-/* one runnable kernel: its launch form, workgroup size, stats bits, what the launch needs, and its persistent grid (0: not built for
- * this context, or not queried yet) */
+/* one runnable kernel: what to call, with which scene arguments in front of (frame, partial sums, counters), its workgroup size and
+ * stats bits, and its persistent grid (0: not built for this context, or not resolved yet) */
 struct RtKernel {
-    RtForm form;
     int block;
     uint32_t bits;
-    const void* fn = nullptr;     /* RT_FORM_F64, RT_FORM_PW: the __global__ */
-    int mode = 0;                 /* RT_FORM_REF, RT_FORM_F32: the companion unit's kernel index */
-    hipFunction_t jit = nullptr;  /* RT_FORM_JIT, RT_FORM_F32_JIT */
+    const void* fn = nullptr;     /* a __global__ of this library (this unit, context_ref.hip, context_f32.hip) ... */
+    hipFunction_t jit = nullptr;  /* ... or the scene-specialised kernel (jit.cpp), from its module */
+    bool f32 = false;             /* takes the f32 scene's views (context_f32.hip) instead of the context's */
+    bool pw = false;              /* takes the pair-walk view (rt_walk_pair.h) in second place */
     int grid = 0;
 };
 
@@ -175,7 +163,7 @@ static const struct { int block; uint32_t bits; } g_walks[RT_N_WALKS] = {
  * (load_specialised) */
 struct RtJitSlot {
     const char* what;          /* for error texts */
-    RtForm form;               /* RT_FORM_JIT or RT_FORM_F32_JIT */
+    bool f32;                  /* the f32 build of the kernel */
     bool recompile_refused;    /* f64: compile once more when the driver refuses a cached object */
     bool block_from_bounds;    /* f64: the workgroup size is the kernel's launch bound = its sort domain (experiments build it for 512) */
     bool sticky;               /* f32: honours RT1W_NO_JIT, renders look at the caches once per context, a failure is remembered with
@@ -207,7 +195,7 @@ struct rt1w_context {
     uint32_t n_nodes = 0, scope_depth = 0;
     void* wf_state = nullptr; /* the wavefront form's own state (librt1w_lab.so: wavefront.hip), freed through its destroy hook */
     uint32_t stack_need = 0;
-    RtKernel ref[4] = {}; /* reference-stream kernels by rt1w_internal_ref_* mode: sweep, stack walk, reordering V0, reordering every-feature */
+    RtKernel ref[4] = {}; /* reference-stream kernels by rt1w_internal_ref_kernel mode: sweep, stack walk, reordering V0, reordering every-feature */
     void* f32_scene = nullptr;   /* context_f32.hip: f32 copies of the scene arrays, built at the first f32 render */
     bool f32_tried = false;
     /* pair walk (rt_walk_pair.h): records of an eligible scene (sphere-only, variant 5); its kernels, plain and reordering (grid 0: the
@@ -218,9 +206,9 @@ struct rt1w_context {
     RtKernel pw_k[2] = {};
     /* host copies of the flat arrays the two opt-in modes convert on first use (a scene may be destroyed before its contexts) */
     std::vector<RtNode> h_nodes, h_lights; std::vector<RtMaterial> h_materials; std::vector<RtTexture> h_textures; std::vector<RtPerlin> h_perlin;
-    RtKernel k32[RT_N_VARIANTS][3] = {}; /* f32 kernels by variant and rt1w_internal_f32_* mode: plain, reordering, pair walk */
-    RtJitSlot jit{"specialised kernel", RT_FORM_JIT, true, true, false};
-    RtJitSlot jit32{"f32 specialised kernel", RT_FORM_F32_JIT, false, false, true}; /* loaded only where `jit` is */
+    RtKernel k32[RT_N_VARIANTS][3] = {}; /* f32 kernels by variant and rt1w_internal_f32_kernel mode: plain, reordering, pair walk */
+    RtJitSlot jit{"specialised kernel", false, true, true, false};
+    RtJitSlot jit32{"f32 specialised kernel", true, false, false, true}; /* loaded only where `jit` is */
 };
 
 namespace {
@@ -351,27 +339,49 @@ void lane_destroy(RtLane& l) {
 #endif
 struct RtLaunch { RtFrame f; unsigned long long npix; unsigned long long partial_budget = RT_PARTIAL_BUDGET; int variant; RtKernel k; };
 
-/* the persistent grid of a kernel: as many workgroups as are resident at once, at least one per CU; 0 if the occupancy query failed */
-int kernel_grid(const rt1w_context* c, const RtKernel& k, int variant) {
+/* the persistent grid of a kernel: as many workgroups as are resident at once, at least one per CU; 0, with the error set, if the
+ * occupancy query failed */
+int kernel_grid(const rt1w_context* c, const RtKernel& k) {
     int per_cu = 0;
-    switch (k.form) {
-        case RT_FORM_F64: case RT_FORM_PW:
-            if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, k.block, 0), "occupancy query")) return 0;
-            break;
-        case RT_FORM_JIT: case RT_FORM_F32_JIT:
-            if (!hip_ok(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.jit, k.block, 0), "occupancy query")) return 0;
-            break;
-        case RT_FORM_REF: per_cu = rt1w_internal_ref_blocks_per_cu(k.mode); break;
-        case RT_FORM_F32: per_cu = rt1w_internal_f32_blocks_per_cu(variant, k.mode); break;
-    }
+    if (!hip_ok(k.jit ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.jit, k.block, 0)
+                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, k.block, 0), "occupancy query")) return 0;
     return c->n_cu * (per_cu < 1 ? 1 : per_cu);
 }
 
-/* the kernels whose grid is queried at their first use (reference stream, f32): `slot` becomes `k` with its grid */
-const RtKernel& first_use(const rt1w_context* c, RtKernel& slot, const RtKernel& k, int variant) {
-    if (!slot.grid) { slot = k; slot.grid = kernel_grid(c, slot, variant); }
-    return slot;
+/* the kernels that are resolved at their first use (reference stream, f32): `slot` becomes `k` with its grid */
+int first_use(const rt1w_context* c, RtKernel& slot, const RtKernel& k) {
+    if (slot.grid) return RT1W_OK;
+    if (!k.fn) { rt1w::set_error("no kernel of this mode for the scene's variant"); return RT1W_ERR_DEVICE; }
+    const int grid = kernel_grid(c, k);
+    if (!grid) return RT1W_ERR_DEVICE;
+    slot = k; slot.grid = grid;
+    return RT1W_OK;
 }
+
+/* the frame of a render of `p`, but for its chunking (chunk, n_chunks: the caller's) */
+RtFrame frame_of(const rt1w_render_params* p) {
+    RtFrame f{};
+    f.width = p->width; f.height = p->height;
+    f.x0 = p->x0; f.y0 = p->y0; f.tile_w = p->tile_w; f.tile_h = p->tile_h;
+    f.spp = p->spp; f.sample_offset = p->sample_offset; f.max_depth = p->max_depth;
+    f.global_seed = p->global_seed;
+    f.strip_rows = p->strip_rows; f.strip_period = p->strip_period;
+    f.probe = (p->flags & RT1W_PROBE_COHERENT) ? 1u : 0u;
+    return f;
+}
+
+/* ms between the two events of the lane, once its stream has drained */
+double lane_ms(const RtLane& l) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
+    return ms;
+}
+
+/* the host clock of an entry, for rt1w_stats.total_ms */
+struct RtTimer {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
 
 /* RT1W_FORCE_VARIANT: `*v` becomes the variant the flags name, if they name one (allow_v4: the order-aware V4, which exists in f64 only) */
 int forced_variant(const rt1w_context* c, uint32_t flags, bool allow_v4, int* v) {
@@ -393,13 +403,7 @@ int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::Ji
 
 /* what the launch will need, without launching: frame, variant, kernel */
 int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
-    RtFrame& f = L.f;
-    f.width = p->width; f.height = p->height;
-    f.x0 = p->x0; f.y0 = p->y0; f.tile_w = p->tile_w; f.tile_h = p->tile_h;
-    f.spp = p->spp; f.sample_offset = p->sample_offset; f.max_depth = p->max_depth;
-    f.global_seed = p->global_seed;
-    f.strip_rows = p->strip_rows; f.strip_period = p->strip_period;
-    f.probe = (p->flags & RT1W_PROBE_COHERENT) ? 1u : 0u;
+    RtFrame& f = L.f = frame_of(p);
     f.chunk = p->chunk ? p->chunk : default_chunk(c, p); /* the reference stream sets its own below */
     if (f.chunk > f.spp) f.chunk = f.spp;
     f.n_chunks = (f.spp + f.chunk - 1u) / f.chunk;
@@ -426,7 +430,8 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
         const int mode = (fl & RT1W_UNSORTED) ? 0
                        : (v == 5 && !(fl & RT1W_CLASSIC_WALK) && rt1w_internal_f32_pw(c->f32_scene, (unsigned)RT_PW_SS_STACK) == 1) ? 2 : 1;
         const uint32_t bits = RT_BIT_F32 | (mode == 2 ? RT_BIT_PW | RT_BIT_SS : mode == 1 ? (v >= 2 ? RT_BIT_SS : RT_BIT_SORTED) : 0u);
-        L.k = first_use(c, c->k32[v][mode], RtKernel{RT_FORM_F32, mode ? RT_SORT_BLOCK : RT_BLOCK, bits, nullptr, mode}, v);
+        if ((rc = first_use(c, c->k32[v][mode], RtKernel{mode ? RT_SORT_BLOCK : RT_BLOCK, bits, rt1w_internal_f32_kernel(v, mode), nullptr, true, mode == 2})) < 0) return rc;
+        L.k = c->k32[v][mode];
         return RT1W_OK;
     }
     if (fl & RT1W_RNG_REFERENCE) {
@@ -437,7 +442,11 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
         /* small scenes: through the workgroup-level path reordering (the stream's state travels with the path) unless RT1W_UNSORTED */
         const int mode = stack_walk ? 1 : ((fl & RT1W_UNSORTED) ? 0 : (c->variant == 0 ? 2 : 3));
         L.variant = stack_walk ? 3 : (mode == 2 ? 0 : 1);
-        L.k = first_use(c, c->ref[mode], RtKernel{RT_FORM_REF, mode >= 2 ? RT_SORT_BLOCK : RT_BLOCK, RT_BIT_REF | (mode >= 2 ? RT_BIT_SORTED : 0u), nullptr, mode}, 0);
+        if (!c->ref[mode].grid && (rt1w_internal_ref_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_ref_sizeof(1) != sizeof(RtFrame))) {
+            rt1w::set_error("reference-stream kernels built against another scene layout"); return RT1W_ERR_DEVICE;
+        }
+        if ((rc = first_use(c, c->ref[mode], RtKernel{mode >= 2 ? RT_SORT_BLOCK : RT_BLOCK, RT_BIT_REF | (mode >= 2 ? RT_BIT_SORTED : 0u), rt1w_internal_ref_kernel(mode)})) < 0) return rc;
+        L.k = c->ref[mode];
         return RT1W_OK;
     }
     L.variant = c->variant;
@@ -496,6 +505,10 @@ void launch_resolve(hipStream_t stream, const double* partial, double* out, unsi
 /* enqueue on the lane's stream: counters, trace kernel, resolve into d_out, counters back to pinned memory.  No host wait. */
 int render_launch(rt1w_context* c, RtLane& l, const rt1w_render_params* p, const RtLaunch& L, double* d_out) {
     const RtKernel& k = L.k;
+    /* the kernel's arguments: its scene view, the pair-walk view of the same precision where it takes one, frame, partial sums, counters */
+    const void* view = k.f32 ? rt1w_internal_f32_view(c->f32_scene, 0) : &c->view;
+    const void* pw = k.f32 ? rt1w_internal_f32_view(c->f32_scene, 1) : &c->pw;
+    if (!view || (k.pw && !pw)) { rt1w::set_error("single-precision scene missing"); return RT1W_ERR_DEVICE; }
     (void)hipEventRecord(l.ev0, l.stream);
     const uint32_t cpp = chunks_per_pass(L, l.partial_bytes < L.partial_budget ? l.partial_bytes : L.partial_budget); /* what the lane's buffer holds (lane_reserve_partial), within the caller's bound */
     const uint32_t n_pass = (L.f.n_chunks + cpp - 1u) / cpp;
@@ -508,37 +521,15 @@ int render_launch(rt1w_context* c, RtLane& l, const rt1w_render_params* p, const
     PF.sample_offset = L.f.sample_offset + c0 * L.f.chunk;
     PF.spp = (L.f.spp - c0 * L.f.chunk < PF.n_chunks * L.f.chunk) ? L.f.spp - c0 * L.f.chunk : PF.n_chunks * L.f.chunk;
     hipLaunchKernelGGL(rt_init_counters_kernel, dim3(1), dim3(1), 0, l.stream, l.d_counters, (unsigned long long)k.grid * k.block, pass ? 1u : 0u);
-    RtSceneView view = c->view;
-    RtPwView pw = c->pw;
     double* partial = l.d_partial;
     unsigned long long* counters = l.d_counters;
-    void* args[] = {&view, &PF, &partial, &counters};
-    void* pw_args[] = {&view, &pw, &PF, &partial, &counters};
-    switch (k.form) {
-        case RT_FORM_F64: (void)hipLaunchKernel(k.fn, dim3(k.grid), dim3(k.block), args, 0, l.stream); break;
-        case RT_FORM_PW: (void)hipLaunchKernel(k.fn, dim3(k.grid), dim3(k.block), pw_args, 0, l.stream); break;
-        case RT_FORM_JIT:
-            if (!hip_ok(hipModuleLaunchKernel(k.jit, (unsigned)k.grid, 1, 1, (unsigned)k.block, 1, 1, 0, l.stream, args, nullptr), "specialised kernel launch")) return RT1W_ERR_DEVICE;
-            break;
-        case RT_FORM_F32_JIT: {
-            unsigned char view32[512];
-            if (!c->f32_scene || rt1w_internal_f32_view(c->f32_scene, view32, sizeof view32) == 0u) { rt1w::set_error("single-precision scene missing"); return RT1W_ERR_DEVICE; }
-            void* args32[] = {view32, &PF, &partial, &counters};
-            if (!hip_ok(hipModuleLaunchKernel(k.jit, (unsigned)k.grid, 1, 1, (unsigned)k.block, 1, 1, 0, l.stream, args32, nullptr), "specialised f32 kernel launch")) return RT1W_ERR_DEVICE;
-            break;
-        }
-        case RT_FORM_F32:
-            if (!c->f32_scene || rt1w_internal_f32_launch(c->f32_scene, L.variant, k.mode, &PF, l.d_partial, l.d_counters, k.grid, l.stream) != 0) {
-                rt1w::set_error("single-precision kernel launch failed"); return RT1W_ERR_DEVICE;
-            }
-            break;
-        case RT_FORM_REF:
-            if (rt1w_internal_ref_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_ref_sizeof(1) != sizeof(RtFrame) ||
-                rt1w_internal_ref_launch(k.mode, &c->view, &PF, l.d_partial, l.d_counters, k.grid, l.stream) != 0) {
-                rt1w::set_error("reference-stream kernel launch failed"); return RT1W_ERR_DEVICE;
-            }
-            break;
-    }
+    void* args[5];
+    int n = 0;
+    args[n++] = const_cast<void*>(view);
+    if (k.pw) args[n++] = const_cast<void*>(pw);
+    args[n++] = &PF; args[n++] = &partial; args[n++] = &counters;
+    if (!hip_ok(k.jit ? hipModuleLaunchKernel(k.jit, (unsigned)k.grid, 1, 1, (unsigned)k.block, 1, 1, 0, l.stream, args, nullptr)
+                      : hipLaunchKernel(k.fn, dim3(k.grid), dim3(k.block), args, 0, l.stream), "render kernel launch")) return RT1W_ERR_DEVICE;
     launch_resolve(l.stream, l.d_partial, d_out, L.npix, PF.n_chunks, L.f.spp, p, (pass ? 1u : 0u) | (pass + 1u < n_pass ? 2u : 0u));
     } /* passes */
     (void)hipEventRecord(l.ev1, l.stream);
@@ -551,11 +542,9 @@ int render_launch(rt1w_context* c, RtLane& l, const rt1w_render_params* p, const
 int render_finish(RtLane& l, const RtLaunch& L, rt1w_stats* stats) {
     if (!hip_ok(hipStreamSynchronize(l.stream), "render kernel")) return RT1W_ERR_DEVICE;
     if (stats) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
         stats->paths = L.npix * L.f.spp;
         stats->segments = l.h_counters[1];
-        stats->kernel_ms = ms;
+        stats->kernel_ms = lane_ms(l);
         stats->chunk = L.f.chunk; stats->n_chunks = L.f.n_chunks;
         stats->grid = (uint32_t)L.k.grid; stats->block = (uint32_t)L.k.block;
         stats->variant = (uint32_t)L.variant; stats->sorted = L.k.bits;
@@ -591,12 +580,12 @@ int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::Ji
         if ((rc = rt1w::jit_get_code(s.src, true, code, info, true)) < 0) { rt1w::set_error(what + ": " + info.message); return rc; }
         if (!(ok = hip_ok(hipModuleLoadData(&s.mod, code.data()), ("hipModuleLoadData(" + what + ")").c_str()))) s.mod = nullptr;
     }
-    RtKernel k{s.form, RT_SORT_BLOCK, RT_BIT_SORTED | RT_BIT_JIT | (s.form == RT_FORM_F32_JIT ? RT_BIT_F32 : 0u)};
+    RtKernel k{RT_SORT_BLOCK, RT_BIT_SORTED | RT_BIT_JIT | (s.f32 ? RT_BIT_F32 : 0u), nullptr, nullptr, s.f32};
     int max_threads = 0;
     ok = ok && hip_ok(hipModuleGetFunction(&k.jit, s.mod, "rt_jit_sorted"), ("hipModuleGetFunction(" + what + ")").c_str());
     if (ok && s.block_from_bounds && hipFuncGetAttribute(&max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, k.jit) == hipSuccess &&
         (max_threads == 512 || max_threads == 128)) k.block = max_threads;
-    if (ok) ok = (k.grid = kernel_grid(c, k, 0)) > 0;
+    if (ok) ok = (k.grid = kernel_grid(c, k)) > 0;
     if (!ok) {
         if (s.mod) (void)hipModuleUnload(s.mod);
         s.mod = nullptr;
@@ -635,9 +624,7 @@ int render_wavefront(rt1w_context* c, const rt1w_render_params* p, const RtLaunc
     (void)hipEventRecord(l.ev1, l.stream);
     if (!hip_ok(hipGetLastError(), "kernel launch") || !hip_ok(hipStreamSynchronize(l.stream), "wavefront render")) return RT1W_ERR_DEVICE;
     if (stats) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
-        stats->paths = L.npix * L.f.spp; stats->segments = k.h_segments ? *k.h_segments : 0ull; stats->kernel_ms = ms;
+        stats->paths = L.npix * L.f.spp; stats->segments = k.h_segments ? *k.h_segments : 0ull; stats->kernel_ms = lane_ms(l);
         stats->chunk = L.f.chunk; stats->n_chunks = L.f.n_chunks;
         stats->passes = 1u; stats->reserved = 0u;
     }
@@ -659,8 +646,9 @@ int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, r
     if (rc < 0) return rc;
     RtLane& l = c->lane[0];
     if ((rc = lane_reserve_partial(l, L)) < 0) return rc;
-    /* the wavefront form stands in for the generic f64 kernels other than the reordering kernel */
-    if ((p->flags & RT1W_WAVEFRONT) && L.k.form == RT_FORM_F64 && !(L.k.bits & RT_BIT_SORTED)) {
+    /* the wavefront form stands in for the generic f64 kernels other than the reordering kernel: with the flag the plan holds one of those,
+     * the scene-specialised kernel (a reordering kernel too) or a reference-stream kernel */
+    if ((p->flags & RT1W_WAVEFRONT) && !(L.k.bits & (RT_BIT_SORTED | RT_BIT_REF))) {
         if (chunks_per_pass(L, L.partial_budget) < L.f.n_chunks) { rt1w::set_error("RT1W_WAVEFRONT renders in one pass: its chunk partial sums must fit the budget (rt1w_render_params.partial_mib)"); return RT1W_ERR_UNSUPPORTED; }
         return render_wavefront(c, p, L, d_out, stats);
     }
@@ -737,8 +725,8 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
         for (int v = 0; v < RT_N_VARIANTS; ++v) {
             if (!g_kernels[w][v] || ((w == RT_WALK_SS_HC || w == RT_WALK_SS_HC_SPHERE_MEDIA) && !c->walk_table)) continue;
             RtKernel& k = c->k64[w][v];
-            k = RtKernel{RT_FORM_F64, g_walks[w].block, g_walks[w].bits, reinterpret_cast<const void*>(g_kernels[w][v])};
-            if (!(k.grid = kernel_grid(c, k, v))) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
+            k = RtKernel{g_walks[w].block, g_walks[w].bits, reinterpret_cast<const void*>(g_kernels[w][v])};
+            if (!(k.grid = kernel_grid(c, k))) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
         }
     if (c->variant == 5 && s->stack_need + 1u <= (uint32_t)RT_PW_STACK) {
         /* a sphere scene: records of the pair walk (rt_walk_pair.h); a scene outside its scope keeps the one-entry-per-step walk.  The
@@ -746,14 +734,14 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
         std::vector<RtPwInner> pin; std::vector<RtPwGroup> pgr;
         if (rt_pw_build(s->flat_nodes, s->flat_root, pin, pgr, c->pw, c->pw_why)) {
             const int n_pw = s->stack_need + 1u <= (uint32_t)RT_PW_SS_STACK ? 2 : 1;
-            c->pw_k[0] = RtKernel{RT_FORM_PW, RT_BLOCK, RT_BIT_PW, reinterpret_cast<const void*>(rt_render_kernel_pw<RtCfgV5>)};
-            c->pw_k[1] = RtKernel{RT_FORM_PW, RT_BLOCK, RT_BIT_PW | RT_BIT_SS, reinterpret_cast<const void*>(rt_render_kernel_pw_ss<RtCfgV5>)};
+            c->pw_k[0] = RtKernel{RT_BLOCK, RT_BIT_PW, reinterpret_cast<const void*>(rt_render_kernel_pw<RtCfgV5>), nullptr, false, true};
+            c->pw_k[1] = RtKernel{RT_BLOCK, RT_BIT_PW | RT_BIT_SS, reinterpret_cast<const void*>(rt_render_kernel_pw_ss<RtCfgV5>), nullptr, false, true};
             if (!upload(&c->d_pw_inner, pin.data(), pin.size() * sizeof(RtPwInner)) || !upload(&c->d_pw_groups, pgr.data(), pgr.size() * sizeof(RtPwGroup))) {
                 rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
             }
             c->pw.inner = (const RtPwInner*)c->d_pw_inner; c->pw.groups = (const RtPwGroup*)c->d_pw_groups;
             for (int i = 0; i < n_pw; ++i)
-                if (!(c->pw_k[i].grid = kernel_grid(c, c->pw_k[i], 5))) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
+                if (!(c->pw_k[i].grid = kernel_grid(c, c->pw_k[i]))) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
         }
     } else c->pw_why = "not a wrapper-free, media-free scene of more than 64 nodes, or its tree is deeper than the pair walk's stack";
     /* the opt-in modes' own data (f32 scene arrays, the wavefront form's walk records) are built at their first use:
@@ -813,9 +801,9 @@ int rt1w_render_device(rt1w_context* c, const rt1w_render_params* p, void* d_out
     if (!d_out_rgb) { rt1w::set_error("null output"); return RT1W_ERR_INVALID; }
     if (p->flags & RT1W_OUT_FRAME) { rt1w::set_error("RT1W_OUT_FRAME is a host-output mode (rt1w_render)"); return RT1W_ERR_INVALID; }
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    auto t0 = std::chrono::steady_clock::now();
+    const RtTimer timer;
     rc = render_common(c, p, (double*)d_out_rgb, stats);
-    if (rc == RT1W_OK && stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc == RT1W_OK && stats) stats->total_ms = timer.ms();
     return rc;
 }
 
@@ -826,7 +814,7 @@ int rt1w_render_u8(rt1w_context* c, const rt1w_render_params* p, uint8_t* out_rg
     if (p->flags & RT1W_OUT_SUM) { rt1w::set_error("RT1W_OUT_SUM has no 8-bit form"); return RT1W_ERR_INVALID; }
     if ((p->flags & RT1W_OUT_FRAME) || p->strip_rows) { rt1w::set_error("rt1w_render_u8 takes contiguous tiles only"); return RT1W_ERR_INVALID; }
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    auto t0 = std::chrono::steady_clock::now();
+    const RtTimer timer;
     size_t npix = (size_t)p->tile_w * p->tile_h;
     size_t bytes = npix * 3 * sizeof(double) + npix * 3; /* framebuffer + quantised image behind it */
     if ((rc = reserve_out(c, bytes)) < 0) return rc;
@@ -836,7 +824,7 @@ int rt1w_render_u8(rt1w_context* c, const rt1w_render_params* p, uint8_t* out_rg
     hipLaunchKernelGGL(rt_quantize_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c->lane[0].stream, c->d_out, d_u8, p->tile_w, p->tile_h);
     if (!hip_ok(hipMemcpyAsync(out_rgb8, d_u8, npix * 3, hipMemcpyDeviceToHost, c->lane[0].stream), "quantised image copy") ||
         !hip_ok(hipStreamSynchronize(c->lane[0].stream), "quantise kernel")) return RT1W_ERR_DEVICE;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) stats->total_ms = timer.ms();
     return RT1W_OK;
 }
 
@@ -850,7 +838,7 @@ int rt1w_render_rows(rt1w_context* c, const rt1w_render_params* p, uint32_t stri
     if ((p->flags & RT1W_OUT_FRAME) || p->strip_rows) { rt1w::set_error("rt1w_render_rows takes contiguous tiles only"); return RT1W_ERR_INVALID; }
     if (p->flags & RT1W_WAVEFRONT) { rt1w::set_error("rt1w_render_rows runs the persistent kernels only (RT1W_WAVEFRONT is a one-shot form)"); return RT1W_ERR_UNSUPPORTED; }
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    auto t0 = std::chrono::steady_clock::now();
+    const RtTimer timer;
     const uint32_t H = p->tile_h, W = p->tile_w;
     const uint32_t tile_chunk = p->chunk ? p->chunk : default_chunk(c, p); /* the whole tile's chunking */
     if (strip_rows == 0) {
@@ -947,7 +935,7 @@ int rt1w_render_rows(rt1w_context* c, const rt1w_render_params* p, uint32_t stri
     }
     if (stats) {
         *stats = total; /* kernel_ms: first strip's start to last strip's end on the device (the strips overlap) */
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = timer.ms();
     }
     return RT1W_OK;
 }
@@ -957,7 +945,7 @@ int rt1w_render(rt1w_context* c, const rt1w_render_params* p, double* out_rgb, r
     if (rc < 0) return rc;
     if (!out_rgb) { rt1w::set_error("null output"); return RT1W_ERR_INVALID; }
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    auto t0 = std::chrono::steady_clock::now();
+    const RtTimer timer;
     size_t bytes = (size_t)p->tile_w * p->tile_h * 3 * sizeof(double);
     if ((rc = reserve_out(c, bytes)) < 0) return rc;
     rc = render_common(c, p, c->d_out, stats);
@@ -980,7 +968,7 @@ int rt1w_render(rt1w_context* c, const rt1w_render_params* p, double* out_rgb, r
         }
         if (!hip_ok(hipStreamSynchronize(st), "framebuffer copy")) return RT1W_ERR_DEVICE;
     } else if (!hip_ok(hipMemcpy(out_rgb, c->d_out, bytes, hipMemcpyDeviceToHost), "framebuffer copy")) return RT1W_ERR_DEVICE;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) stats->total_ms = timer.ms();
     return RT1W_OK;
 }
 
@@ -1008,31 +996,27 @@ int render_aov_common(rt1w_context* c, const rt1w_render_params* p, double* d_ou
     int variant = c->variant;
     const int rc = forced_variant(c, p->flags, true, &variant);
     if (rc < 0) return rc;
-    RtFrame f;
-    memset(&f, 0, sizeof f);
-    f.width = p->width; f.height = p->height;
-    f.x0 = p->x0; f.y0 = p->y0; f.tile_w = p->tile_w; f.tile_h = p->tile_h;
-    f.spp = p->spp; f.sample_offset = p->sample_offset; f.global_seed = p->global_seed;
+    RtFrame f = frame_of(p);
     f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u; /* not read by the AOV kernels */
-    f.strip_rows = p->strip_rows; f.strip_period = p->strip_period;
     RtLane& l = c->lane[0];
     if (rt1w_internal_aov_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_aov_sizeof(1) != sizeof(RtFrame)) {
         rt1w::set_error("AOV kernels built against another scene layout"); return RT1W_ERR_DEVICE;
     }
-    unsigned launch[2] = {0u, 0u};
+    const void* fn = rt1w_internal_aov_kernel(variant);
+    if (!fn) { rt1w::set_error("no AOV kernel of this variant"); return RT1W_ERR_DEVICE; }
+    const unsigned grid = rt1w_internal_aov_grid(&f);
+    void* args[] = {&c->view, &f, &d_out};
     (void)hipEventRecord(l.ev0, l.stream);
-    if (rt1w_internal_aov_launch(variant, &c->view, &f, d_out, l.stream, launch) != 0) { rt1w::set_error("AOV kernel launch failed"); return RT1W_ERR_DEVICE; }
+    if (!hip_ok(hipLaunchKernel(fn, dim3(grid), dim3(RT_BLOCK), args, 0, l.stream), "AOV kernel launch")) return RT1W_ERR_DEVICE;
     (void)hipEventRecord(l.ev1, l.stream);
     if (!hip_ok(hipStreamSynchronize(l.stream), "AOV kernel")) return RT1W_ERR_DEVICE;
     if (stats) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
         memset(stats, 0, sizeof *stats);
         stats->paths = (uint64_t)p->tile_w * p->tile_h * p->spp;
         stats->segments = stats->paths; /* one camera ray per sample */
-        stats->kernel_ms = ms;
+        stats->kernel_ms = lane_ms(l);
         stats->chunk = p->spp; stats->n_chunks = 1u;
-        stats->grid = launch[0]; stats->block = launch[1];
+        stats->grid = grid; stats->block = RT_BLOCK;
         stats->variant = (uint32_t)variant;
         stats->passes = 1u;
     }
@@ -1053,12 +1037,12 @@ int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_ao
     int rc = aov_validate(c, p, out_aov);
     if (rc < 0) return rc;
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    auto t0 = std::chrono::steady_clock::now();
+    const RtTimer timer;
     const size_t bytes = (size_t)p->tile_w * p->tile_h * RT1W_AOV_CHANNELS * sizeof(double);
     if ((rc = reserve_out(c, bytes)) < 0) return rc; /* the context's framebuffer, as rt1w_render grows it */
     if ((rc = render_aov_common(c, p, c->d_out, stats)) < 0) return rc;
     if (!hip_ok(hipMemcpy(out_aov, c->d_out, bytes, hipMemcpyDeviceToHost), "AOV copy")) return RT1W_ERR_DEVICE;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) stats->total_ms = timer.ms();
     return RT1W_OK;
 }
 
@@ -1066,9 +1050,9 @@ int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d
     int rc = aov_validate(c, p, d_out_aov);
     if (rc < 0) return rc;
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    auto t0 = std::chrono::steady_clock::now();
+    const RtTimer timer;
     if ((rc = render_aov_common(c, p, (double*)d_out_aov, stats)) < 0) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) stats->total_ms = timer.ms();
     return RT1W_OK;
 }
 
@@ -1110,11 +1094,7 @@ int denoise_common(rt1w_context* c, const rt1w_denoise_params* p, const double* 
     if (rc != 0) { rt1w::set_error("denoise kernel launch failed"); return RT1W_ERR_DEVICE; }
     (void)hipEventRecord(l.ev1, l.stream);
     if (!hip_ok(hipStreamSynchronize(l.stream), "denoise kernels")) return RT1W_ERR_DEVICE;
-    if (kernel_ms) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
-        *kernel_ms = ms;
-    }
+    if (kernel_ms) *kernel_ms = lane_ms(l);
     return RT1W_OK;
 }
 void denoise_stats(const rt1w_denoise_params* p, double kernel_ms, const unsigned launch[2], rt1w_stats* stats) {
@@ -1132,7 +1112,7 @@ int rt1w_denoise(rt1w_context* c, const rt1w_denoise_params* p, const double* fr
     if (rc < 0) return rc;
     if (!frame || !aov || !out) { rt1w::set_error("null buffer"); return RT1W_ERR_INVALID; }
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    auto t0 = std::chrono::steady_clock::now();
+    const RtTimer timer;
     const size_t npix = (size_t)p->width * p->height;
     /* the context's framebuffer holds the frame (filtered in place) and, behind it, the feature buffers */
     if ((rc = reserve_out(c, npix * (3 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
@@ -1146,7 +1126,7 @@ int rt1w_denoise(rt1w_context* c, const rt1w_denoise_params* p, const double* fr
     if (!hip_ok(hipMemcpy(out, d_frame, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "denoise: result copy")) return RT1W_ERR_DEVICE;
     if (stats) {
         denoise_stats(p, ms, launch, stats);
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = timer.ms();
     }
     return RT1W_OK;
 }
@@ -1156,13 +1136,13 @@ int rt1w_denoise_device(rt1w_context* c, const rt1w_denoise_params* p, const voi
     if (rc < 0) return rc;
     if (!d_frame || !d_aov || !d_out) { rt1w::set_error("null buffer"); return RT1W_ERR_INVALID; }
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    auto t0 = std::chrono::steady_clock::now();
+    const RtTimer timer;
     double ms = 0.0;
     unsigned launch[2] = {0u, 0u};
     if ((rc = denoise_common(c, p, (const double*)d_frame, (const double*)d_aov, (double*)d_out, &ms, launch)) < 0) return rc;
     if (stats) {
         denoise_stats(p, ms, launch, stats);
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = timer.ms();
     }
     return RT1W_OK;
 }
@@ -1184,7 +1164,7 @@ int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1
     dp.width = p->tile_w; dp.height = p->tile_h;
     if ((rc = denoise_validate(c, &dp)) < 0) return rc;
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    auto t0 = std::chrono::steady_clock::now();
+    const RtTimer timer;
     const size_t npix = (size_t)p->tile_w * p->tile_h;
     if ((rc = reserve_out(c, npix * (3 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
     double* d_frame = c->d_out;
@@ -1204,7 +1184,7 @@ int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1
         *stats = st;
         stats->kernel_ms = st.kernel_ms + sa.kernel_ms + ms;
         stats->grid = launch[0]; stats->block = launch[1];
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms = timer.ms();
     }
     return RT1W_OK;
 }

@@ -198,43 +198,21 @@ extern "C" int rt1w_internal_f32_pw(void* h, unsigned stack_cap) {
     return (s && s->pw_ok && s->pw_stack <= stack_cap) ? 1 : 0;
 }
 
-extern "C" unsigned rt1w_internal_f32_view(void* h, void* out, unsigned cap) {
+/* the kernels' scene arguments, which context.hip passes by address: what 0 the f32 RtSceneView, 1 the f32 RtPwView (nullptr: the
+ * scene has no pair-walk records).  They live as long as the scene */
+extern "C" const void* rt1w_internal_f32_view(void* h, int what) {
     F32Scene* s = static_cast<F32Scene*>(h);
-    if (!s || cap < sizeof s->view) return 0u;
-    memcpy(out, &s->view, sizeof s->view);
-    return (unsigned)sizeof s->view;
+    if (!s) return nullptr;
+    return what == 0 ? static_cast<const void*>(&s->view) : (what == 1 && s->pw_ok) ? static_cast<const void*>(&s->pw) : nullptr;
 }
 
-/* mode 0: the plain kernel; 1: the reordering kernel of the sweep variants, the slice-end reordering of the stack walks (g_sorted);
- * 2: the pair-walk kernel of sphere scenes (variant 5 only; the caller asked rt1w_internal_f32_pw first) */
-extern "C" int rt1w_internal_f32_blocks_per_cu(int variant, int mode) {
-    int per_cu = 0;
-    if (variant < 0 || variant >= RT_N_VARIANTS) return 0;
-    if (mode == 2) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtf32::rt_render_kernel_pw_ss_f32, RT_BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        return per_cu;
-    }
-    rtf32::kernel_t k = mode ? rtf32::g_sorted[variant] : rtf32::g_plain[variant];
-    if (!k) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, mode ? RT_SORT_BLOCK : RT_BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    return per_cu;
-}
-
-/* `frame` = the bytes of an RtFrame (no floating-point fields: same layout in both builds); `mode` as above */
-extern "C" int rt1w_internal_f32_launch(void* h, int variant, int mode, const void* frame, double* partial, unsigned long long* counters, int grid,
-                                        hipStream_t stream) {
-    F32Scene* s = static_cast<F32Scene*>(h);
-    if (variant < 0 || variant >= RT_N_VARIANTS) return -1;
-    rtf32::kernel_t k = mode ? rtf32::g_sorted[variant] : rtf32::g_plain[variant];
-    if (!s || !k) return -1;
-    rtf32::RtFrame f;
-    static_assert(sizeof(rtf32::RtFrame) == sizeof(::RtFrame), "RtFrame has no floating-point fields");
-    memcpy(&f, frame, sizeof f);
-    if (mode == 2) {
-        if (variant != 5 || !s->pw_ok) return -1;
-        hipLaunchKernelGGL(rtf32::rt_render_kernel_pw_ss_f32, dim3(grid), dim3(RT_BLOCK), 0, stream, s->view, s->pw, f, partial, counters);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    hipLaunchKernelGGL(k, dim3(grid), dim3(mode ? RT_SORT_BLOCK : RT_BLOCK), 0, stream, s->view, f, partial, counters);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+/* The kernels' host handles for context.hip, which launches them like its own; nullptr: no such kernel.  mode 0: the plain kernel;
+ * 1: the reordering kernel of the sweep variants, the slice-end reordering of the stack walks (g_sorted); 2: the pair-walk kernel of
+ * sphere scenes (variant 5 only; takes the RtPwView in second place, the caller asked rt1w_internal_f32_pw first).  After the view(s)
+ * the kernels take the caller's RtFrame as it is: */
+static_assert(sizeof(rtf32::RtFrame) == sizeof(::RtFrame), "RtFrame has no floating-point fields: same layout in both builds");
+extern "C" const void* rt1w_internal_f32_kernel(int variant, int mode) {
+    if (variant < 0 || variant >= RT_N_VARIANTS) return nullptr;
+    if (mode == 2) return variant == 5 ? reinterpret_cast<const void*>(rtf32::rt_render_kernel_pw_ss_f32) : nullptr;
+    return reinterpret_cast<const void*>(mode ? rtf32::g_sorted[variant] : rtf32::g_plain[variant]);
 }

@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <string.h>
 #include <type_traits>
 
 #define RT_RNG_REFSTREAM 1
@@ -48,31 +47,21 @@ __global__ __launch_bounds__(RT_SORT_BLOCK, (Cfg::tex || Cfg::media || Cfg::msph
                                                                                            unsigned long long* __restrict__ counters) {
     rt_render_sorted_body<Cfg>(sc, f, partial, counters);
 }
+/* The code object holds the kernels in the order in which they are instantiated, and the addresses in their code follow from it:
+ * these explicit instantiations fix that order, whatever order the table below names them in */
+template __global__ void rt_render_kernel_ref_sorted<RtCfgV0>(RtSceneView, RtFrame, double*, unsigned long long*);
+template __global__ void rt_render_kernel_ref_sorted<CfgSweep>(RtSceneView, RtFrame, double*, unsigned long long*);
+template __global__ void rt_render_kernel_ref<CfgStack>(RtSceneView, RtFrame, double*, unsigned long long*);
+template __global__ void rt_render_kernel_ref<CfgSweep>(RtSceneView, RtFrame, double*, unsigned long long*);
+/* by mode: 0 sweep (plain kernel), 1 stack walk (plain kernel), 2 reordering kernel V0, 3 reordering kernel with every feature */
+typedef void (*kernel_t)(RtSceneView, RtFrame, double*, unsigned long long*);
+static kernel_t const g_ref[4] = {rt_render_kernel_ref<CfgSweep>, rt_render_kernel_ref<CfgStack>, rt_render_kernel_ref_sorted<RtCfgV0>,
+                                  rt_render_kernel_ref_sorted<CfgSweep>};
 } // namespace rtref
 
-/* called by context.hip; `view` / `frame` are the bytes of its RtSceneView / RtFrame (same layout: same headers) */
-/* mode: 0 sweep (plain kernel), 1 stack walk (plain kernel), 2 reordering kernel V0, 3 reordering kernel with every feature */
-extern "C" int rt1w_internal_ref_blocks_per_cu(int mode) {
-    int per_cu = 0;
-    if (mode >= 2) {
-        hipError_t e2 = mode == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref_sorted<rtref::RtCfgV0>, RT_SORT_BLOCK, 0)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref_sorted<rtref::CfgSweep>, RT_SORT_BLOCK, 0);
-        return e2 == hipSuccess && per_cu > 0 ? per_cu : 1;
-    }
-    hipError_t e = mode ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref<rtref::CfgStack>, RT_BLOCK, 0)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rtref::rt_render_kernel_ref<rtref::CfgSweep>, RT_BLOCK, 0);
-    return e == hipSuccess && per_cu > 0 ? per_cu : 1;
-}
-extern "C" int rt1w_internal_ref_launch(int mode, const void* view, const void* frame, double* partial, unsigned long long* counters,
-                                        int grid, hipStream_t stream) {
-    rtref::RtSceneView v;
-    rtref::RtFrame f;
-    memcpy(&v, view, sizeof v);
-    memcpy(&f, frame, sizeof f);
-    if (mode == 2) hipLaunchKernelGGL(rtref::rt_render_kernel_ref_sorted<rtref::RtCfgV0>, dim3(grid), dim3(RT_SORT_BLOCK), 0, stream, v, f, partial, counters);
-    else if (mode == 3) hipLaunchKernelGGL(rtref::rt_render_kernel_ref_sorted<rtref::CfgSweep>, dim3(grid), dim3(RT_SORT_BLOCK), 0, stream, v, f, partial, counters);
-    else if (mode) hipLaunchKernelGGL(rtref::rt_render_kernel_ref<rtref::CfgStack>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, partial, counters);
-    else hipLaunchKernelGGL(rtref::rt_render_kernel_ref<rtref::CfgSweep>, dim3(grid), dim3(RT_BLOCK), 0, stream, v, f, partial, counters);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+/* the kernels' host handles for context.hip, which launches them like its own: their arguments are the bytes of its RtSceneView /
+ * RtFrame (same headers, same layout: checked through rt1w_internal_ref_sizeof).  nullptr: no such mode */
+extern "C" const void* rt1w_internal_ref_kernel(int mode) {
+    return mode >= 0 && mode < 4 ? reinterpret_cast<const void*>(rtref::g_ref[mode]) : nullptr;
 }
 extern "C" unsigned rt1w_internal_ref_sizeof(int what) { return what == 0 ? (unsigned)sizeof(rtref::RtSceneView) : (unsigned)sizeof(rtref::RtFrame); }
