@@ -325,6 +325,33 @@ int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_ao
 /* same, into device memory on the context's GPU (e.g. a torch tensor); no host copy.  Synchronises the context's stream before returning. */
 int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d_out_aov, rt1w_stats* stats);
 
+/* ---- deep feature buffers: the same 8 channels at the first vertex of the sample's path that is not a specular surface ----
+ * What is seen through glass or in a mirror gets the guides of what is seen, not of the glass or the mirror.  For every pixel of the
+ * tile and every sample k of sample_offset .. sample_offset + spp - 1:
+ *   1. start as rt1w_render_aov does: the camera ray of beauty sample k, world.hit(ray, 0.001, inf) (main.rs:62);
+ *   2. continue while the ray hits, the hit material is SPECULAR -- a Dielectric, or a Metal whose fuzz <= max_fuzz -- and fewer than
+ *      max_specular bounces have been followed;
+ *   3. to continue, scatter exactly as the beauty path does: Dielectric::scatter (material.rs:133-160) with its one draw,
+ *      Metal::scatter (material.rs:99-111) with its random_in_unit_sphere even at fuzz 0; a throughput beta (1 at the start) is
+ *      multiplied by the attenuation, the scattered ray keeps the ray's time.  The stream stays in step with rt1w_render's, so the
+ *      chain followed is the chain beauty sample k follows (as long as that path is alive: max_depth is not looked at here);
+ *   4. at the vertex where it stops:
+ *        0-2 albedo   beta (.) the albedo rule of rt1w_render_aov at that vertex; beta (.) background if the last ray missed;
+ *        3-5 normal   that vertex's HitRecord.normal; (0, 0, 0) if the last ray missed;
+ *        6 depth      the sum of t * |d| over all segments of the chain that hit (the length of the folded-out path);
+ *        7 coverage   1 if the last ray hit, 0 if it missed;
+ *   5. a chain still on a specular surface after max_specular bounces stops there and takes that surface as its vertex.
+ * Sums, divisions (depth: over the samples whose last ray hit, +inf if none), layout, tiles, strips, flags, precision and argument
+ * checks are those of rt1w_render_aov.  max_specular = 0 is rt1w_render_aov, bit for bit; with max_fuzz = 0 only Dielectrics and
+ * perfect mirrors are followed.  max_specular > 64, or a max_fuzz that is negative or not finite: RT1W_ERR_INVALID.
+ * stats: paths = pixels * spp; segments = the rays actually traced (counted per lane, summed per wave, one atomic add per wave);
+ * kernel_ms, total_ms, grid, block, variant as rt1w_render_aov.  One lane per pixel runs its samples in order: bit-identical to the CPU
+ * build of the same code (librt1w_lab.so: rt1w_lab_aov_deep_host).  None of the render kernels is involved. */
+int rt1w_render_aov_deep(rt1w_context* c, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, double* out_aov, rt1w_stats* stats);
+/* same, into device memory on the context's GPU; no host copy.  Synchronises the context's stream before returning. */
+int rt1w_render_aov_deep_device(rt1w_context* c, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, void* d_out_aov,
+                                rt1w_stats* stats);
+
 /* ---- feature-guided denoiser: the consumer of the feature buffers above ----
  * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) over an image and its first-hit feature buffers.
  * Replaces nothing of the reference, which reaches a clean image by sample count alone (10 000 spp for final_scene, src/main.rs:939).
@@ -359,8 +386,9 @@ int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d
  * After the last level out = c * A_p per channel.
  * Arithmetic: + - * /, sqrt, comparisons, selects and integer operations in one fixed order, without FMA contraction, each output pixel
  * whole by one lane: bit-identical to the CPU build of the same code (librt1w_lab.so: rt1w_lab_denoise_host).
- * Known limit: the guides describe the first hit.  What is seen through a glass sphere or reflected in a metal one is filtered with the
- * glass or metal surface's guides. */
+ * Known limit: with the first-hit buffers the guides describe the first hit: what is seen through a glass sphere or reflected in a
+ * metal one is filtered with the glass or metal surface's guides.  The deep buffers (rt1w_render_aov_deep, rt1w_render_denoised_deep)
+ * lift it for Dielectrics and for Metals up to a chosen fuzz. */
 #define RT1W_DENOISE_KEEP_ALBEDO 1u      /* no demodulation */
 typedef struct rt1w_denoise_params {
     uint32_t width, height;              /* of the three buffers */
@@ -381,6 +409,11 @@ int rt1w_denoise_device(rt1w_context* c, const rt1w_denoise_params* p, const voi
  * (strip_rows != 0) and RT1W_PRECISION_F32 are refused too: all RT1W_ERR_INVALID.  stats are the render's, with the AOV and filter kernel
  * times added to kernel_ms; total_ms is the whole call; grid / block are the level kernel's. */
 int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, double* out_rgb, rt1w_stats* stats);
+/* rt1w_render_denoised with the deep feature buffers (rt1w_render_aov_deep_device with max_specular, max_fuzz) in place of the first-hit
+ * ones: bit-identical to composing rt1w_render_device, rt1w_render_aov_deep_device and rt1w_denoise_device.  Refuses what
+ * rt1w_render_denoised refuses, and max_specular / max_fuzz as rt1w_render_aov_deep does. */
+int rt1w_render_denoised_deep(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, uint32_t max_specular, double max_fuzz,
+                              double* out_rgb, rt1w_stats* stats);
 
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory

@@ -152,6 +152,8 @@ PROGRESS_FN = C.CFUNCTYPE(C.c_int, _P, C.c_uint32, C.c_uint32)
 _sig("rt1w_render_rows", C.c_int, _P, C.POINTER(RenderParams), C.c_uint32, C.c_int, _P, PROGRESS_FN, _P, C.POINTER(Stats))
 _sig("rt1w_render_aov", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(Stats))
 _sig("rt1w_render_aov_device", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(Stats))
+_sig("rt1w_render_aov_deep", C.c_int, _P, C.POINTER(RenderParams), C.c_uint32, C.c_double, _P, C.POINTER(Stats))
+_sig("rt1w_render_aov_deep_device", C.c_int, _P, C.POINTER(RenderParams), C.c_uint32, C.c_double, _P, C.POINTER(Stats))
 
 
 class DenoiseParams(C.Structure):
@@ -167,6 +169,7 @@ def _denoise_params(width, height, iterations=0, keep_albedo=False, sigma_colour
 _sig("rt1w_denoise", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.POINTER(Stats))
 _sig("rt1w_denoise_device", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.POINTER(Stats))
 _sig("rt1w_render_denoised", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(DenoiseParams), _P, C.POINTER(Stats))
+_sig("rt1w_render_denoised_deep", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(DenoiseParams), C.c_uint32, C.c_double, _P, C.POINTER(Stats))
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -493,6 +496,25 @@ class Context:
         _ck(_lib.rt1w_render_aov_device(self._h, C.byref(p), C.c_void_p(d_ptr), C.byref(st)))
         return {n: getattr(st, n) for n, _ in Stats._fields_}
 
+    def render_aov_deep(self, width, height, spp, max_specular=8, max_fuzz=0.0, tile=None, sample_offset=0, global_seed=0, variant=None,
+                        strips=None, with_stats=False):
+        """Deep feature buffers of the tile (rt1w_render_aov_deep): the 8 channels of render_aov at the first vertex of each sample's
+        path that is neither a Dielectric nor a Metal of fuzz <= max_fuzz, after at most max_specular bounces.  stats["segments"] is
+        the number of rays traced."""
+        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
+        out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_aov_deep(self._h, C.byref(p), max_specular, max_fuzz, out.ctypes.data_as(_P), C.byref(st)))
+        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+
+    def render_aov_deep_device(self, d_ptr, width, height, spp, max_specular=8, max_fuzz=0.0, tile=None, sample_offset=0, global_seed=0,
+                               variant=None, strips=None):
+        """Same, into device memory `d_ptr` (int address of tile_h * tile_w * 8 float64); returns the stats dict."""
+        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
+        st = Stats()
+        _ck(_lib.rt1w_render_aov_deep_device(self._h, C.byref(p), max_specular, max_fuzz, C.c_void_p(d_ptr), C.byref(st)))
+        return {n: getattr(st, n) for n, _ in Stats._fields_}
+
     def denoise(self, frame, aov, with_stats=False, **kw):
         """Feature-guided filter (rt1w_denoise) of a float64 frame [h, w, 3] with its feature buffers [h, w, 8] (render_aov): the
         denoised [h, w, 3].  kw: iterations, keep_albedo, sigma_colour, sigma_normal, sigma_depth (0 = default)."""
@@ -525,6 +547,19 @@ class Context:
         out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
         st = Stats()
         _ck(_lib.rt1w_render_denoised(self._h, C.byref(p), C.byref(d) if d is not None else None, out.ctypes.data_as(_P), C.byref(st)))
+        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+
+    def render_denoised_deep(self, width, height, spp, max_specular=8, max_fuzz=0.0, max_depth=50, tile=None, sample_offset=0, global_seed=0,
+                             denoise=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
+        """render_denoised with the deep feature buffers (rt1w_render_denoised_deep) in place of the first-hit ones."""
+        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, 0, False, kw.pop("variant", None), strips=strips, **kw)
+        p.flags |= flags
+        p.precision = precision
+        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
+        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_denoised_deep(self._h, C.byref(p), C.byref(d) if d is not None else None, max_specular, max_fuzz,
+                                           out.ctypes.data_as(_P), C.byref(st)))
         return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
 
     def debug_aabb(self, cases):
@@ -588,19 +623,31 @@ def host_unregister(array):
     _ck(_lib.rt1w_host_unregister(C.c_void_p(array.ctypes.data)))
 
 
-def aov_host(scene, width, height, spp, tile=None, sample_offset=0, global_seed=0, variant=None, strips=None):
+def aov_host(scene, width, height, spp, tile=None, sample_offset=0, global_seed=0, variant=None, strips=None, max_specular=None,
+             max_fuzz=0.0, with_stats=False):
     """CPU twin of Context.render_aov (librt1w_lab.so: rt1w_lab_aov_host, the same rt_aov.h built for the host): the array the GPU
-    must equal bit for bit.  No GPU needed."""
+    must equal bit for bit.  No GPU needed.  max_specular not None: the twin of Context.render_aov_deep (rt1w_lab_aov_deep_host,
+    rt_aov_deep.h); with_stats then returns (array, {"segments": rays traced, "lengths": uint8 [tile_h, tile_w, spp] rays per sample})."""
     lab = load_lab()
-    f = lab.rt1w_lab_aov_host
-    f.restype = C.c_int
-    f.argtypes = [_P, C.POINTER(RenderParams), _P]
     p = Context._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
     out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
-    rc = f(scene._h, C.byref(p), out.ctypes.data_as(_P))
+    if max_specular is None:
+        f = lab.rt1w_lab_aov_host
+        f.restype = C.c_int
+        f.argtypes = [_P, C.POINTER(RenderParams), _P]
+        rc = f(scene._h, C.byref(p), out.ctypes.data_as(_P))
+        if rc < 0:
+            raise Rt1wError(rc, "rt1w_lab_aov_host")
+        return (out, {"segments": p.tile_w * p.tile_h * spp}) if with_stats else out
+    f = lab.rt1w_lab_aov_deep_host
+    f.restype = C.c_int
+    f.argtypes = [_P, C.POINTER(RenderParams), C.c_uint32, C.c_double, _P, C.POINTER(C.c_uint64), _P]
+    seg = C.c_uint64()
+    lengths = np.zeros((p.tile_h, p.tile_w, spp), dtype=np.uint8) if with_stats else None
+    rc = f(scene._h, C.byref(p), max_specular, max_fuzz, out.ctypes.data_as(_P), C.byref(seg), lengths.ctypes.data_as(_P) if with_stats else None)
     if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_aov_host")
-    return out
+        raise Rt1wError(rc, "rt1w_lab_aov_deep_host")
+    return (out, {"segments": seg.value, "lengths": lengths}) if with_stats else out
 
 
 def denoise_host(frame, aov, **kw):

@@ -39,6 +39,7 @@ extern "C" const void* rt1w_internal_ref_kernel(int mode);
 extern "C" unsigned rt1w_internal_ref_sizeof(int what); /* bytes of its 0 RtSceneView, 1 RtFrame */
 /* aov.hip: the first-hit feature buffers (rt1w_render_aov), by variant; workgroups of RT_BLOCK work-items that cover the frame's tile */
 extern "C" const void* rt1w_internal_aov_kernel(int variant);
+extern "C" const void* rt1w_internal_aov_deep_kernel(int variant); /* rt1w_render_aov_deep: + (max_specular, max_fuzz) before out, a segment counter after */
 extern "C" unsigned rt1w_internal_aov_grid(const void* frame);
 extern "C" unsigned rt1w_internal_aov_sizeof(int what);
 /* denoise.hip: the filter of rt1w_denoise; enqueues the prepare pass and the levels; 0, -1 launch failure, -2 parameters refused */
@@ -56,6 +57,7 @@ extern "C" int rt1w_internal_f32_pw(void* h, unsigned stack_cap); /* 1: the scen
 extern "C" const void* rt1w_internal_f32_view(void* h, int what); /* the kernels' 0 f32 RtSceneView, 1 f32 RtPwView (nullptr: none) */
 
 #include "rt_kernels.h"
+#include "rt_aov_deep.h" /* rt_aov_deep_args_ok only: no kernel of this unit instantiates its templates */
 #include "rt_walk_table.h"
 
 namespace {
@@ -991,8 +993,16 @@ int aov_check_flags(uint32_t flags) {
     return RT1W_ERR_INVALID;
 }
 
+/* the deep entries' two extra arguments (include/rt1w.h: rt1w_render_aov_deep); null = the first-hit buffers */
+struct AovDeep { uint32_t max_specular; double max_fuzz; };
+int aov_deep_validate(uint32_t max_specular, double max_fuzz) {
+    if (rt_aov_deep_args_ok(max_specular, max_fuzz)) return RT1W_OK;
+    rt1w::set_error("max_specular must be 0 .. 64 and max_fuzz finite and >= 0");
+    return RT1W_ERR_INVALID;
+}
+
 /* validate, launch the AOV kernel of the context's (or the forced) variant into d_out, wait, fill stats */
-int render_aov_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, rt1w_stats* stats) {
+int render_aov_common(rt1w_context* c, const rt1w_render_params* p, const AovDeep* deep, double* d_out, rt1w_stats* stats) {
     int variant = c->variant;
     const int rc = forced_variant(c, p->flags, true, &variant);
     if (rc < 0) return rc;
@@ -1002,18 +1012,25 @@ int render_aov_common(rt1w_context* c, const rt1w_render_params* p, double* d_ou
     if (rt1w_internal_aov_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_aov_sizeof(1) != sizeof(RtFrame)) {
         rt1w::set_error("AOV kernels built against another scene layout"); return RT1W_ERR_DEVICE;
     }
-    const void* fn = rt1w_internal_aov_kernel(variant);
+    const void* fn = deep ? rt1w_internal_aov_deep_kernel(variant) : rt1w_internal_aov_kernel(variant);
     if (!fn) { rt1w::set_error("no AOV kernel of this variant"); return RT1W_ERR_DEVICE; }
     const unsigned grid = rt1w_internal_aov_grid(&f);
-    void* args[] = {&c->view, &f, &d_out};
+    /* (view, frame, out), the deep kernel's (view, frame, max_specular, max_fuzz, out, rays traced): the lane's second counter, the
+     * one the render kernels count their segments in */
+    AovDeep dv = deep ? *deep : AovDeep{0u, 0.0};
+    unsigned long long* d_rays = l.d_counters + 1;
+    void* args_first[] = {&c->view, &f, &d_out};
+    void* args_deep[] = {&c->view, &f, &dv.max_specular, &dv.max_fuzz, &d_out, &d_rays};
+    if (deep && !hip_ok(hipMemsetAsync(d_rays, 0, sizeof *d_rays, l.stream), "AOV counter")) return RT1W_ERR_DEVICE;
     (void)hipEventRecord(l.ev0, l.stream);
-    if (!hip_ok(hipLaunchKernel(fn, dim3(grid), dim3(RT_BLOCK), args, 0, l.stream), "AOV kernel launch")) return RT1W_ERR_DEVICE;
+    if (!hip_ok(hipLaunchKernel(fn, dim3(grid), dim3(RT_BLOCK), deep ? args_deep : args_first, 0, l.stream), "AOV kernel launch")) return RT1W_ERR_DEVICE;
     (void)hipEventRecord(l.ev1, l.stream);
+    if (deep && !hip_ok(hipMemcpyAsync(l.h_counters + 1, d_rays, sizeof *d_rays, hipMemcpyDeviceToHost, l.stream), "AOV counter copy")) return RT1W_ERR_DEVICE;
     if (!hip_ok(hipStreamSynchronize(l.stream), "AOV kernel")) return RT1W_ERR_DEVICE;
     if (stats) {
         memset(stats, 0, sizeof *stats);
         stats->paths = (uint64_t)p->tile_w * p->tile_h * p->spp;
-        stats->segments = stats->paths; /* one camera ray per sample */
+        stats->segments = deep ? l.h_counters[1] : stats->paths; /* first hit: one camera ray per sample */
         stats->kernel_ms = lane_ms(l);
         stats->chunk = p->spp; stats->n_chunks = 1u;
         stats->grid = grid; stats->block = RT_BLOCK;
@@ -1030,30 +1047,44 @@ int aov_validate(const rt1w_context* c, const rt1w_render_params* p, const void*
     if (p->precision != RT1W_PRECISION_F64) { rt1w::set_error("the AOV entries are f64 only (RT1W_PRECISION_F64)"); return RT1W_ERR_UNSUPPORTED; }
     return RT1W_OK;
 }
-} // namespace
-extern "C" {
-
-int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_aov, rt1w_stats* stats) {
-    int rc = aov_validate(c, p, out_aov);
+/* the host-memory entries: through the context's framebuffer, as rt1w_render grows it */
+int render_aov_host(rt1w_context* c, const rt1w_render_params* p, const AovDeep* deep, double* out_aov, rt1w_stats* stats) {
+    int rc = deep ? aov_deep_validate(deep->max_specular, deep->max_fuzz) : RT1W_OK; /* first: needs no context */
     if (rc < 0) return rc;
+    if ((rc = aov_validate(c, p, out_aov)) < 0) return rc;
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
     const RtTimer timer;
     const size_t bytes = (size_t)p->tile_w * p->tile_h * RT1W_AOV_CHANNELS * sizeof(double);
-    if ((rc = reserve_out(c, bytes)) < 0) return rc; /* the context's framebuffer, as rt1w_render grows it */
-    if ((rc = render_aov_common(c, p, c->d_out, stats)) < 0) return rc;
+    if ((rc = reserve_out(c, bytes)) < 0) return rc;
+    if ((rc = render_aov_common(c, p, deep, c->d_out, stats)) < 0) return rc;
     if (!hip_ok(hipMemcpy(out_aov, c->d_out, bytes, hipMemcpyDeviceToHost), "AOV copy")) return RT1W_ERR_DEVICE;
     if (stats) stats->total_ms = timer.ms();
     return RT1W_OK;
 }
-
-int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d_out_aov, rt1w_stats* stats) {
-    int rc = aov_validate(c, p, d_out_aov);
+/* the device-memory entries */
+int render_aov_device(rt1w_context* c, const rt1w_render_params* p, const AovDeep* deep, void* d_out_aov, rt1w_stats* stats) {
+    int rc = deep ? aov_deep_validate(deep->max_specular, deep->max_fuzz) : RT1W_OK;
     if (rc < 0) return rc;
+    if ((rc = aov_validate(c, p, d_out_aov)) < 0) return rc;
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
     const RtTimer timer;
-    if ((rc = render_aov_common(c, p, (double*)d_out_aov, stats)) < 0) return rc;
+    if ((rc = render_aov_common(c, p, deep, (double*)d_out_aov, stats)) < 0) return rc;
     if (stats) stats->total_ms = timer.ms();
     return RT1W_OK;
+}
+} // namespace
+extern "C" {
+
+int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_aov, rt1w_stats* stats) { return render_aov_host(c, p, nullptr, out_aov, stats); }
+int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d_out_aov, rt1w_stats* stats) { return render_aov_device(c, p, nullptr, d_out_aov, stats); }
+
+int rt1w_render_aov_deep(rt1w_context* c, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, double* out_aov, rt1w_stats* stats) {
+    const AovDeep deep{max_specular, max_fuzz};
+    return render_aov_host(c, p, &deep, out_aov, stats);
+}
+int rt1w_render_aov_deep_device(rt1w_context* c, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, void* d_out_aov, rt1w_stats* stats) {
+    const AovDeep deep{max_specular, max_fuzz};
+    return render_aov_device(c, p, &deep, d_out_aov, stats);
 }
 
 /* ---- feature-guided denoiser (include/rt1w.h: rt1w_denoise) ---- */
@@ -1147,9 +1178,13 @@ int rt1w_denoise_device(rt1w_context* c, const rt1w_denoise_params* p, const voi
     return RT1W_OK;
 }
 
-int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, double* out_rgb, rt1w_stats* stats) {
-    int rc = validate(c, p);
+} // extern "C"
+namespace {
+/* rt1w_render_denoised and, with `deep`, rt1w_render_denoised_deep */
+int render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, const AovDeep* deep, double* out_rgb, rt1w_stats* stats) {
+    int rc = deep ? aov_deep_validate(deep->max_specular, deep->max_fuzz) : RT1W_OK;
     if (rc < 0) return rc;
+    if ((rc = validate(c, p)) < 0) return rc;
     if (!out_rgb) { rt1w::set_error("null output"); return RT1W_ERR_INVALID; }
     static const struct { uint32_t bit; const char* name; } refused[] = {
         {RT1W_OUT_SUM, "RT1W_OUT_SUM"}, {RT1W_OUT_FRAME, "RT1W_OUT_FRAME"}, {RT1W_RNG_REFERENCE, "RT1W_RNG_REFERENCE"}, {RT1W_PROBE_COHERENT, "RT1W_PROBE_COHERENT"}};
@@ -1175,7 +1210,7 @@ int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1
     rt1w_render_params ap = *p; /* the feature buffers of the same tile, samples and seed, by the scene's own variant */
     ap.flags = 0u;
     rt1w_stats sa;
-    if ((rc = render_aov_common(c, &ap, d_aov, &sa)) < 0) return rc;
+    if ((rc = render_aov_common(c, &ap, deep, d_aov, &sa)) < 0) return rc;
     double ms = 0.0;
     unsigned launch[2] = {0u, 0u};
     if ((rc = denoise_common(c, &dp, d_frame, d_aov, d_frame, &ms, launch)) < 0) return rc;
@@ -1187,6 +1222,17 @@ int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1
         stats->total_ms = timer.ms();
     }
     return RT1W_OK;
+}
+} // namespace
+extern "C" {
+
+int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, double* out_rgb, rt1w_stats* stats) {
+    return render_denoised(c, p, d, nullptr, out_rgb, stats);
+}
+int rt1w_render_denoised_deep(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, uint32_t max_specular, double max_fuzz,
+                              double* out_rgb, rt1w_stats* stats) {
+    const AovDeep deep{max_specular, max_fuzz};
+    return render_denoised(c, p, d, &deep, out_rgb, stats);
 }
 
 uint32_t rt1w_abi_sizeof(int what) {

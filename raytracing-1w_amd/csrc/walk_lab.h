@@ -34,6 +34,11 @@ int rt1w_lab_trace(rt1w_lab* l, int mode, const uint32_t params[4], int repeats,
  * same variant choice (or p->flags' RT1W_FORCE_VARIANT), no GPU.  RT1W_OK, RT1W_ERR_INVALID / _UNSUPPORTED as the device entry,
  * RT1W_ERR_STATE if a traversal stack overflowed */
 int rt1w_lab_aov_host(const rt1w_scene* s, const rt1w_render_params* p, double* out);
+/* CPU twin of rt1w_render_aov_deep (aov_host.cpp: rt_aov_deep.h built for the host), same returns; max_specular / max_fuzz refused as
+ * the device entry refuses them.  Optional: *segments = the rays traced (rt1w_stats.segments of the device entry),
+ * lengths[tile_h][tile_w][spp] = the rays of every sample, 1 .. max_specular + 1 */
+int rt1w_lab_aov_deep_host(const rt1w_scene* s, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, double* out,
+                           uint64_t* segments, uint8_t* lengths);
 
 /* CPU twin of rt1w_denoise (denoise_host.cpp: rt_denoise.h built for the host): the same double[h][w][3] from host buffers, no GPU.
  * RT1W_OK, or RT1W_ERR_INVALID as the device entry (null pointers, zero sizes, iterations > 8, unknown flags, bad sigmas) */
