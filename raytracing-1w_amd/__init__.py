@@ -203,6 +203,17 @@ def _ck(rc):
     return rc
 
 
+def _stats_dict(st):
+    return {n: getattr(st, n) for n, _ in Stats._fields_}
+
+
+def _frame_and_aov(frame, aov):
+    f, a = (np.ascontiguousarray(x, dtype=np.float64) for x in (frame, aov))
+    if f.ndim != 3 or f.shape[2] != 3 or a.shape != f.shape[:2] + (AOV_CHANNELS,):
+        raise ValueError("frame must be [h, w, 3] and aov [h, w, 8]")
+    return f, a
+
+
 def _v3(v):
     return _D3(float(v[0]), float(v[1]), float(v[2]))
 
@@ -442,7 +453,7 @@ class Context:
             assert out.dtype == np.float64 and out.shape == (p.tile_h, p.tile_w, 3) and out.flags.c_contiguous
         st = Stats()
         _ck(_lib.rt1w_render(self._h, C.byref(p), out.ctypes.data_as(_P), C.byref(st)))
-        return out, {n: getattr(st, n) for n, _ in Stats._fields_}
+        return out, _stats_dict(st)
 
     def render_u8(self, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, chunk=0, reference_stream=False,
                   partial_mib=0):
@@ -452,7 +463,7 @@ class Context:
         out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.uint8)
         st = Stats()
         _ck(_lib.rt1w_render_u8(self._h, C.byref(p), out.ctypes.data_as(_P), C.byref(st)))
-        return out, {n: getattr(st, n) for n, _ in Stats._fields_}
+        return out, _stats_dict(st)
 
     def render_rows(self, width, height, spp, strip_rows=0, u8=False, progress=None, max_depth=50, tile=None,
                     sample_offset=0, global_seed=0, chunk=0, out_sum=False, out=None, no_node_cache=False, partial_mib=0):
@@ -468,7 +479,7 @@ class Context:
         cb = PROGRESS_FN((lambda user, done, total: 1 if progress(done, total) else 0) if progress else 0)
         _ck(_lib.rt1w_render_rows(self._h, C.byref(p), strip_rows, ROWS_U8 if u8 else ROWS_F64, out.ctypes.data_as(_P), cb,
                                   None, C.byref(st)))
-        return out, {n: getattr(st, n) for n, _ in Stats._fields_}
+        return out, _stats_dict(st)
 
     def render_device(self, d_ptr, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, chunk=0,
                       out_sum=False, variant=None, unsorted=False, generic=False, strips=None, f32=False, partial_mib=0):
@@ -477,56 +488,53 @@ class Context:
                          False, strips, f32=f32, partial_mib=partial_mib)
         st = Stats()
         _ck(_lib.rt1w_render_device(self._h, C.byref(p), C.c_void_p(d_ptr), C.byref(st)))
-        return {n: getattr(st, n) for n, _ in Stats._fields_}
+        return _stats_dict(st)
+
+    # deep: () for the first-hit entries, (max_specular, max_fuzz) for the deep ones
+    def _render_aov(self, deep, width, height, spp, tile, sample_offset, global_seed, variant, strips, with_stats):
+        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
+        out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
+        st = Stats()
+        _ck((_lib.rt1w_render_aov_deep if deep else _lib.rt1w_render_aov)(self._h, C.byref(p), *deep, out.ctypes.data_as(_P), C.byref(st)))
+        return (out, _stats_dict(st)) if with_stats else out
+
+    def _render_aov_device(self, deep, d_ptr, width, height, spp, tile, sample_offset, global_seed, variant, strips):
+        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
+        st = Stats()
+        _ck((_lib.rt1w_render_aov_deep_device if deep else _lib.rt1w_render_aov_device)(self._h, C.byref(p), *deep, C.c_void_p(d_ptr), C.byref(st)))
+        return _stats_dict(st)
 
     def render_aov(self, width, height, spp, tile=None, sample_offset=0, global_seed=0, variant=None, strips=None, with_stats=False):
         """First-hit feature buffers of the tile (rt1w_render_aov): float64 [tile_h, tile_w, 8] = albedo rgb, normal xyz, depth,
         coverage, row 0 = reference row j = y0 (include/rt1w.h has the semantics).  with_stats: returns (array, stats dict)."""
-        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
-        out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_aov(self._h, C.byref(p), out.ctypes.data_as(_P), C.byref(st)))
-        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+        return self._render_aov((), width, height, spp, tile, sample_offset, global_seed, variant, strips, with_stats)
 
     def render_aov_device(self, d_ptr, width, height, spp, tile=None, sample_offset=0, global_seed=0, variant=None, strips=None):
         """Same, into device memory `d_ptr` (int address of tile_h * tile_w * 8 float64, e.g. a torch tensor's .data_ptr());
         returns the stats dict."""
-        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
-        st = Stats()
-        _ck(_lib.rt1w_render_aov_device(self._h, C.byref(p), C.c_void_p(d_ptr), C.byref(st)))
-        return {n: getattr(st, n) for n, _ in Stats._fields_}
+        return self._render_aov_device((), d_ptr, width, height, spp, tile, sample_offset, global_seed, variant, strips)
 
     def render_aov_deep(self, width, height, spp, max_specular=8, max_fuzz=0.0, tile=None, sample_offset=0, global_seed=0, variant=None,
                         strips=None, with_stats=False):
         """Deep feature buffers of the tile (rt1w_render_aov_deep): the 8 channels of render_aov at the first vertex of each sample's
         path that is neither a Dielectric nor a Metal of fuzz <= max_fuzz, after at most max_specular bounces.  stats["segments"] is
         the number of rays traced."""
-        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
-        out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_aov_deep(self._h, C.byref(p), max_specular, max_fuzz, out.ctypes.data_as(_P), C.byref(st)))
-        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+        return self._render_aov((max_specular, max_fuzz), width, height, spp, tile, sample_offset, global_seed, variant, strips, with_stats)
 
     def render_aov_deep_device(self, d_ptr, width, height, spp, max_specular=8, max_fuzz=0.0, tile=None, sample_offset=0, global_seed=0,
                                variant=None, strips=None):
         """Same, into device memory `d_ptr` (int address of tile_h * tile_w * 8 float64); returns the stats dict."""
-        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
-        st = Stats()
-        _ck(_lib.rt1w_render_aov_deep_device(self._h, C.byref(p), max_specular, max_fuzz, C.c_void_p(d_ptr), C.byref(st)))
-        return {n: getattr(st, n) for n, _ in Stats._fields_}
+        return self._render_aov_device((max_specular, max_fuzz), d_ptr, width, height, spp, tile, sample_offset, global_seed, variant, strips)
 
     def denoise(self, frame, aov, with_stats=False, **kw):
         """Feature-guided filter (rt1w_denoise) of a float64 frame [h, w, 3] with its feature buffers [h, w, 8] (render_aov): the
         denoised [h, w, 3].  kw: iterations, keep_albedo, sigma_colour, sigma_normal, sigma_depth (0 = default)."""
-        f = np.ascontiguousarray(frame, dtype=np.float64)
-        a = np.ascontiguousarray(aov, dtype=np.float64)
-        if f.ndim != 3 or f.shape[2] != 3 or a.shape != f.shape[:2] + (AOV_CHANNELS,):
-            raise ValueError("frame must be [h, w, 3] and aov [h, w, 8]")
+        f, a = _frame_and_aov(frame, aov)
         p = _denoise_params(f.shape[1], f.shape[0], **kw)
         out = np.empty_like(f)
         st = Stats()
         _ck(_lib.rt1w_denoise(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), out.ctypes.data_as(_P), C.byref(st)))
-        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+        return (out, _stats_dict(st)) if with_stats else out
 
     def denoise_device(self, d_frame, d_aov, d_out, width, height, **kw):
         """Same on device memory (int addresses of height * width * 3 / 8 / 3 float64, e.g. torch tensors' .data_ptr()); d_out may
@@ -534,33 +542,28 @@ class Context:
         p = _denoise_params(width, height, **kw)
         st = Stats()
         _ck(_lib.rt1w_denoise_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_out), C.byref(st)))
-        return {n: getattr(st, n) for n, _ in Stats._fields_}
+        return _stats_dict(st)
+
+    def _render_denoised(self, deep, width, height, spp, max_depth, tile, sample_offset, global_seed, denoise, flags, strips, precision, with_stats, kw):
+        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, 0, False, kw.pop("variant", None), strips=strips, **kw)
+        p.flags |= flags
+        p.precision = precision
+        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
+        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
+        st = Stats()
+        _ck((_lib.rt1w_render_denoised_deep if deep else _lib.rt1w_render_denoised)(self._h, C.byref(p), C.byref(d) if d is not None else None, *deep, out.ctypes.data_as(_P), C.byref(st)))
+        return (out, _stats_dict(st)) if with_stats else out
 
     def render_denoised(self, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, denoise=None, flags=0,
                         strips=None, precision=0, with_stats=False, **kw):
         """Render, feature buffers and filter in one call (rt1w_render_denoised): float64 [tile_h, tile_w, 3].  `denoise`: dict of
         the keywords of Context.denoise, None = defaults; `flags`: raw RT1W_* render flags; other kw as Context.render's."""
-        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, 0, False, kw.pop("variant", None), strips=strips, **kw)
-        p.flags |= flags
-        p.precision = precision
-        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
-        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_denoised(self._h, C.byref(p), C.byref(d) if d is not None else None, out.ctypes.data_as(_P), C.byref(st)))
-        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+        return self._render_denoised((), width, height, spp, max_depth, tile, sample_offset, global_seed, denoise, flags, strips, precision, with_stats, kw)
 
     def render_denoised_deep(self, width, height, spp, max_specular=8, max_fuzz=0.0, max_depth=50, tile=None, sample_offset=0, global_seed=0,
                              denoise=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
         """render_denoised with the deep feature buffers (rt1w_render_denoised_deep) in place of the first-hit ones."""
-        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, 0, False, kw.pop("variant", None), strips=strips, **kw)
-        p.flags |= flags
-        p.precision = precision
-        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
-        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_denoised_deep(self._h, C.byref(p), C.byref(d) if d is not None else None, max_specular, max_fuzz,
-                                           out.ctypes.data_as(_P), C.byref(st)))
-        return (out, {n: getattr(st, n) for n, _ in Stats._fields_}) if with_stats else out
+        return self._render_denoised((max_specular, max_fuzz), width, height, spp, max_depth, tile, sample_offset, global_seed, denoise, flags, strips, precision, with_stats, kw)
 
     def debug_aabb(self, cases):
         """cases[n, 14] = min3, max3, origin3, direction3, t_min, t_max -> (literal[n], fast[n]) from the device."""
@@ -657,10 +660,7 @@ def denoise_host(frame, aov, **kw):
     fn = lab.rt1w_lab_denoise_host
     fn.restype = C.c_int
     fn.argtypes = [C.POINTER(DenoiseParams), _P, _P, _P]
-    f = np.ascontiguousarray(frame, dtype=np.float64)
-    a = np.ascontiguousarray(aov, dtype=np.float64)
-    if f.ndim != 3 or f.shape[2] != 3 or a.shape != f.shape[:2] + (AOV_CHANNELS,):
-        raise ValueError("frame must be [h, w, 3] and aov [h, w, 8]")
+    f, a = _frame_and_aov(frame, aov)
     p = _denoise_params(f.shape[1], f.shape[0], **kw)
     out = np.empty_like(f)
     rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), out.ctypes.data_as(_P))

@@ -2,7 +2,7 @@
  * below them the deep feature buffers of rt1w_render_aov_deep over rt_aov_deep.h, in a namespace of their own.
  *
  * Kept out of context.hip, inside its own namespace (the pattern of context_ref.hip), so that none of the render kernels' code objects
- * and none of the run-time compiler's inputs moves with it.  The host half (validation, buffers, launch, timing) is in context.hip, which
+ * and none of the run-time compiler's inputs moves with it.  The host half (validation, buffers, launch, timing) is in features.hip, which
  * gets the kernel's host handle and its grid from the two exports below.
  *
  * Work mapping: one lane per pixel, looping over the pixel's samples in order -- the sums have one fixed order, the same as the CPU

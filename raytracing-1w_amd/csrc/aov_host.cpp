@@ -1,11 +1,10 @@
 /* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip): rt_aov.h and rt_aov_deep.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core) and run over a committed scene's flat arrays.  Diagnostics library only (librt1w_lab.so): the expected side of the GPU
  * tests' bit-equality checks and of the CPU tier's checks against the literal oracle.  librt1w.so keeps no CPU render path. */
-#include <cstring>
 #include <thread>
 #include <vector>
 
-#include "scene.h"
+#include "render_params.h"
 #include "rt_aov_deep.h"
 #include "walk_lab.h"
 
@@ -57,9 +56,7 @@ bool aov_rows_variant(int v, const RtSceneView& sc, const RtFrame& f, const AovD
 
 int aov_host_run(const rt1w_scene* s, const rt1w_render_params* p, const AovDeep& deep, double* out, uint64_t* segments) {
     if (!s || !p || !out || !s->committed) return RT1W_ERR_INVALID;
-    if (p->width < 2 || p->height < 2 || p->tile_w == 0 || p->tile_h == 0 || p->spp == 0 ||
-        (uint64_t)p->x0 + p->tile_w > p->width || (uint64_t)p->y0 + p->tile_h > p->height) return RT1W_ERR_INVALID;
-    if ((p->strip_rows == 0) != (p->strip_period == 0) || p->strip_period < p->strip_rows) return RT1W_ERR_INVALID;
+    if (const int rc = rt1w::params_check(p, nullptr); rc < 0) return rc; /* the entries' own check: the twin refuses what they refuse */
     if ((p->flags & ~(0xFFu << 8)) != 0u) return RT1W_ERR_INVALID;
     if (p->precision != RT1W_PRECISION_F64) return RT1W_ERR_UNSUPPORTED;
     const uint32_t n_nodes = (uint32_t)s->flat_nodes.size();
@@ -70,18 +67,11 @@ int aov_host_run(const rt1w_scene* s, const rt1w_render_params* p, const AovDeep
     }
     std::vector<RtNode> nodes(s->flat_nodes);
     nodes.push_back(RtNode{}); /* the spare record the context's node array carries */
-    RtSceneView sc;
-    std::memset(&sc, 0, sizeof sc);
+    RtSceneView sc = rt1w::view_of(*s);
     sc.nodes = nodes.data(); sc.lights = s->flat_lights.data(); sc.materials = s->materials.data(); sc.textures = s->textures.data();
     sc.perlin = s->perlin.data(); sc.images = s->images.data();
-    sc.root = s->flat_root; sc.n_nodes = n_nodes; sc.n_lights = (uint32_t)s->flat_lights.size();
-    sc.n_materials = (uint32_t)s->materials.size(); sc.n_textures = (uint32_t)s->textures.size();
-    sc.camera = s->camera; sc.background = s->background;
-    RtFrame f;
-    std::memset(&f, 0, sizeof f);
-    f.width = p->width; f.height = p->height; f.x0 = p->x0; f.y0 = p->y0; f.tile_w = p->tile_w; f.tile_h = p->tile_h;
-    f.spp = p->spp; f.sample_offset = p->sample_offset; f.global_seed = p->global_seed; f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u;
-    f.strip_rows = p->strip_rows; f.strip_period = p->strip_period;
+    RtFrame f = rt1w::frame_of(p);
+    f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u;
     /* rows dealt round-robin over at most 16 threads: every pixel is computed whole by one thread, so the result does not depend on it */
     unsigned hw = std::thread::hardware_concurrency();
     uint32_t n_threads = hw == 0u ? 1u : (hw > 16u ? 16u : hw);

@@ -1,0 +1,120 @@
+/* context.h -- the device context as the library's own units see it: context.hip (the context, the render kernels' plan and launch, the
+ * render entries) and features.hip (the entries of the feature buffers and the denoiser), with the helpers of the first that the second
+ * calls.  Private: nothing here is exported (-fvisibility=hidden, librt1w.map). */
+#ifndef RT1W_CONTEXT_H
+#define RT1W_CONTEXT_H
+
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <string>
+#include <vector>
+
+#include "rt_kernel_plain.h"
+#include "render_params.h"
+
+/* Everything one in-flight render needs.  Lane 0 serves the one-shot entries; rt1w_render_rows keeps two strips in
+ * flight, one per lane, so that the next strip's workgroups fill the CUs as the previous strip's persistent kernel tails off
+ * and its device->host copy runs under the other lane's tracing. */
+struct RtLane {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    double* d_partial = nullptr; size_t partial_bytes = 0;
+    unsigned long long* d_counters = nullptr;
+    unsigned long long* h_counters = nullptr; /* pinned */
+    void* d_strip = nullptr; void* h_strip = nullptr; size_t strip_bytes = 0; /* rt1w_render_rows: device strip + pinned host strip */
+    uint32_t passes = 0; /* sample passes of the launch in flight (render_launch), reported by render_finish */
+};
+
+/* one runnable kernel: what to call, with which scene arguments in front of (frame, partial sums, counters), its workgroup size and
+ * stats bits, and its persistent grid (0: not built for this context, or not resolved yet) */
+struct RtKernel {
+    int block;
+    uint32_t bits;
+    const void* fn = nullptr;     /* a __global__ of this library (context.hip, context_ref.hip, context_f32.hip) ... */
+    hipFunction_t jit = nullptr;  /* ... or the scene-specialised kernel (jit.cpp), from its module */
+    bool f32 = false;             /* takes the f32 scene's views (context_f32.hip) instead of the context's */
+    bool pw = false;              /* takes the pair-walk view (rt_walk_pair.h) in second place */
+    int grid = 0;
+};
+
+/* The f64 render kernels by walk form and variant (context.hip: g_kernels).  Every walk form is followed by its build for
+ * scenes whose media are all bounded by a bare Sphere (rt_flat.h: RtCfgSphereMedia): form + 1. */
+enum RtWalkForm {
+    RT_WALK_PLAIN, RT_WALK_SPHERE_MEDIA,
+    RT_WALK_SS, RT_WALK_SS_SPHERE_MEDIA,       /* finished paths reordered across the workgroup at the end of every slice (rt_render_ss_body) */
+    RT_WALK_SS_HC, RT_WALK_SS_HC_SPHERE_MEDIA, /* ... and the scene's most visited nodes in LDS (rt_walk_table.h): a context with a walk table */
+    RT_WALK_LDS_NODES,                         /* all nodes in LDS (scenes of <= RT_LDS_NODE_CAP nodes; opt-in: RT1W_LDS_NODES) */
+    RT_WALK_SORTED,                            /* the reordering kernel (rt_kernel_sorted.h) */
+    RT_N_WALKS
+};
+
+/* a scene-specialised kernel (jit.cpp) of one precision.  The first five members say how loading it differs between the two
+ * (load_specialised) */
+struct RtJitSlot {
+    const char* what;          /* for error texts */
+    bool f32;                  /* the f32 build of the kernel */
+    bool recompile_refused;    /* f64: compile once more when the driver refuses a cached object */
+    bool block_from_bounds;    /* f64: the workgroup size is the kernel's launch bound = its sort domain (experiments build it for 512) */
+    bool sticky;               /* f32: honours RT1W_NO_JIT, renders look at the caches once per context, a failure is remembered with
+                                * its reason (rt1w_context_specialise reports it) */
+    std::string src, key;      /* generated source (empty: scene not eligible), cache key */
+    hipModule_t mod = nullptr;
+    RtKernel k{};              /* k.jit != nullptr once loaded */
+    uint32_t vgprs = 0;
+    bool tried = false;
+    bool failed = false;       /* f64: a compile was tried and failed, renders do not try again (render_common); f32: see `sticky` */
+    std::string error;
+};
+
+struct rt1w_context {
+    int device = 0;
+    int n_cu = 0; /* compute units: a persistent grid is n_cu x the workgroups resident per CU (kernel_grid) */
+    RtLane lane[2];
+    hipEvent_t ev_first = nullptr;
+    void* d_nodes = nullptr; void* d_lights = nullptr; void* d_materials = nullptr;
+    void* d_textures = nullptr; void* d_perlin = nullptr; void* d_images = nullptr;
+    RtSceneView view{};
+    double* d_out = nullptr; size_t out_bytes = 0;
+    void* dn_buf[3] = {nullptr, nullptr, nullptr}; size_t dn_bytes[3] = {0, 0, 0}; /* rt1w_denoise: two colour buffers and the guide buffer */
+    RtKernel k64[RT_N_WALKS][RT_N_VARIANTS] = {}; /* g_kernels, queried at creation; the node-cache walks only with a walk table */
+    bool walk_table = false; uint32_t walk_table_first = 0;
+    bool sphere_media = false; /* every medium of the scene is bounded by a bare Sphere: the sphere-media walks serve */
+    int variant = 0;
+    bool has_media = false, has_tex = false, has_msphere = false;
+    uint32_t n_nodes = 0, scope_depth = 0;
+    void* wf_state = nullptr; /* the wavefront form's own state (librt1w_lab.so: wavefront.hip), freed through its destroy hook */
+    uint32_t stack_need = 0;
+    RtKernel ref[4] = {}; /* reference-stream kernels by rt1w_internal_ref_kernel mode: sweep, stack walk, reordering V0, reordering every-feature */
+    void* f32_scene = nullptr;   /* context_f32.hip: f32 copies of the scene arrays, built at the first f32 render */
+    bool f32_tried = false;
+    /* pair walk (rt_walk_pair.h): records of an eligible scene (sphere-only, variant 5); its kernels, plain and reordering (grid 0: the
+     * scene is not eligible) */
+    void* d_pw_inner = nullptr; void* d_pw_groups = nullptr;
+    RtPwView pw{};
+    std::string pw_why;
+    RtKernel pw_k[2] = {};
+    /* host copies of the flat arrays the two opt-in modes convert on first use (a scene may be destroyed before its contexts) */
+    std::vector<RtNode> h_nodes, h_lights; std::vector<RtMaterial> h_materials; std::vector<RtTexture> h_textures; std::vector<RtPerlin> h_perlin;
+    RtKernel k32[RT_N_VARIANTS][3] = {}; /* f32 kernels by variant and rt1w_internal_f32_kernel mode: plain, reordering, pair walk */
+    RtJitSlot jit{"specialised kernel", false, true, true, false};
+    RtJitSlot jit32{"f32 specialised kernel", true, false, false, true}; /* loaded only where `jit` is */
+};
+
+namespace rt1w {
+bool hip_ok(hipError_t e, const char* what); /* false with the error set */
+int validate(const rt1w_context* c, const rt1w_render_params* p); /* null arguments and params_check (render_params.h), with the error set */
+/* RT1W_FORCE_VARIANT: `*v` becomes the variant the flags name, if they name one (allow_v4: the order-aware V4, which exists in f64 only) */
+int forced_variant(const rt1w_context* c, uint32_t flags, bool allow_v4, int* v);
+double lane_ms(const RtLane& l); /* ms between the two events of the lane, once its stream has drained */
+int reserve_out(rt1w_context* c, size_t bytes); /* the context's framebuffer, grown to at least `bytes` */
+/* plan, launch on lane 0, wait, stats: what every one-shot render entry runs */
+int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, rt1w_stats* stats);
+/* the host clock of an entry, for rt1w_stats.total_ms */
+struct RtTimer {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+} // namespace rt1w
+
+#endif

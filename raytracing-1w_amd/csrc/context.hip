@@ -19,17 +19,11 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-#include <type_traits>
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <string>
-#include <vector>
 
-#include "rt1w.h"
-#include "rt_kernel_plain.h"
-#include "scene.h"
+#include "context.h"
 #include "jit.h"
 #include "rt1w_internal.h"
 
@@ -37,16 +31,6 @@
  * context_ref.hip: the kernels built with the reference's own random stream (RT1W_RNG_REFERENCE), by mode (render_plan) */
 extern "C" const void* rt1w_internal_ref_kernel(int mode);
 extern "C" unsigned rt1w_internal_ref_sizeof(int what); /* bytes of its 0 RtSceneView, 1 RtFrame */
-/* aov.hip: the first-hit feature buffers (rt1w_render_aov), by variant; workgroups of RT_BLOCK work-items that cover the frame's tile */
-extern "C" const void* rt1w_internal_aov_kernel(int variant);
-extern "C" const void* rt1w_internal_aov_deep_kernel(int variant); /* rt1w_render_aov_deep: + (max_specular, max_fuzz) before out, a segment counter after */
-extern "C" unsigned rt1w_internal_aov_grid(const void* frame);
-extern "C" unsigned rt1w_internal_aov_sizeof(int what);
-/* denoise.hip: the filter of rt1w_denoise; enqueues the prepare pass and the levels; 0, -1 launch failure, -2 parameters refused */
-extern "C" int rt1w_internal_denoise_launch(uint32_t w, uint32_t h, uint32_t iterations, uint32_t flags, double sigma_colour, double sigma_normal,
-                                            double sigma_depth, const double* frame, const double* aov, double* out, void* col_a, void* col_b,
-                                            void* guide, hipStream_t stream, unsigned launch[2]);
-extern "C" unsigned rt1w_internal_denoise_sizeof(int what); /* bytes per pixel of 0 a colour buffer, 1 the guide buffer */
 /* context_f32.hip: the kernels in single precision (RT1W_PRECISION_F32) and the f32 copies of the scene arrays */
 extern "C" int rt1w_internal_f32_create(const void* nodes, uint32_t n_nodes, const void* lights, uint32_t n_lights, const void* materials,
                                         uint32_t n_materials, const void* textures, uint32_t n_textures, const void* perlin, uint32_t n_perlin,
@@ -57,7 +41,6 @@ extern "C" int rt1w_internal_f32_pw(void* h, unsigned stack_cap); /* 1: the scen
 extern "C" const void* rt1w_internal_f32_view(void* h, int what); /* the kernels' 0 f32 RtSceneView, 1 f32 RtPwView (nullptr: none) */
 
 #include "rt_kernels.h"
-#include "rt_aov_deep.h" /* rt_aov_deep_args_ok only: no kernel of this unit instantiates its templates */
 #include "rt_walk_table.h"
 
 namespace {
@@ -93,26 +76,35 @@ __global__ void rt_debug_eval_kernel(int fn, const double* a, const double* b, d
     out[i] = r;
 }
 
+} // namespace
+
+namespace rt1w {
 bool hip_ok(hipError_t e, const char* what) {
     if (e == hipSuccess) return true;
     rt1w::set_error(std::string(what) + ": " + hipGetErrorString(e));
     return false;
 }
-
-} // namespace
-
-/* Everything one in-flight render needs.  Lane 0 serves the one-shot entries; rt1w_render_rows keeps two strips in
- * flight, one per lane, so that the next strip's workgroups fill the CUs as the previous strip's persistent kernel tails off
- * and its device->host copy runs under the other lane's tracing. */
-struct RtLane {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double* d_partial = nullptr; size_t partial_bytes = 0;
-    unsigned long long* d_counters = nullptr;
-    unsigned long long* h_counters = nullptr; /* pinned */
-    void* d_strip = nullptr; void* h_strip = nullptr; size_t strip_bytes = 0; /* rt1w_render_rows: device strip + pinned host strip */
-    uint32_t passes = 0; /* sample passes of the launch in flight (render_launch), reported by render_finish */
-};
+int validate(const rt1w_context* c, const rt1w_render_params* p) {
+    const char* why = "null argument";
+    const int rc = (c && p) ? params_check(p, &why) : RT1W_ERR_INVALID;
+    if (rc < 0) set_error(why);
+    return rc;
+}
+double lane_ms(const RtLane& l) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
+    return ms;
+}
+int forced_variant(const rt1w_context* c, uint32_t flags, bool allow_v4, int* v) {
+    if (!((flags >> 8) & 0xFFu)) return RT1W_OK;
+    *v = (int)((flags >> 8) & 0xFFu) - 1;
+    if ((*v == 4 && !allow_v4) || !rt_variant_valid(*v, c->n_nodes, c->has_media, c->has_tex, c->has_msphere, c->scope_depth)) {
+        rt1w::set_error("forced kernel variant does not cover this scene's features"); return RT1W_ERR_INVALID;
+    }
+    return RT1W_OK;
+}
+} // namespace rt1w
+using namespace rt1w;
 
 /* the rt1w_stats.sorted bits (include/rt1w.h) a kernel reports; bit 3, the wavefront form, is filled by wavefront.hip */
 enum : uint32_t {
@@ -120,28 +112,7 @@ enum : uint32_t {
     RT_BIT_SS = 512u, RT_BIT_HC = 1024u
 };
 
-/* one runnable kernel: what to call, with which scene arguments in front of (frame, partial sums, counters), its workgroup size and
- * stats bits, and its persistent grid (0: not built for this context, or not resolved yet) */
-struct RtKernel {
-    int block;
-    uint32_t bits;
-    const void* fn = nullptr;     /* a __global__ of this library (this unit, context_ref.hip, context_f32.hip) ... */
-    hipFunction_t jit = nullptr;  /* ... or the scene-specialised kernel (jit.cpp), from its module */
-    bool f32 = false;             /* takes the f32 scene's views (context_f32.hip) instead of the context's */
-    bool pw = false;              /* takes the pair-walk view (rt_walk_pair.h) in second place */
-    int grid = 0;
-};
-
-/* The f64 render kernels by walk form and variant; nullptr: not built for that variant.  Every walk form is followed by its build for
- * scenes whose media are all bounded by a bare Sphere (rt_flat.h: RtCfgSphereMedia): form + 1. */
-enum RtWalkForm {
-    RT_WALK_PLAIN, RT_WALK_SPHERE_MEDIA,
-    RT_WALK_SS, RT_WALK_SS_SPHERE_MEDIA,       /* finished paths reordered across the workgroup at the end of every slice (rt_render_ss_body) */
-    RT_WALK_SS_HC, RT_WALK_SS_HC_SPHERE_MEDIA, /* ... and the scene's most visited nodes in LDS (rt_walk_table.h): a context with a walk table */
-    RT_WALK_LDS_NODES,                         /* all nodes in LDS (scenes of <= RT_LDS_NODE_CAP nodes; opt-in: RT1W_LDS_NODES) */
-    RT_WALK_SORTED,                            /* the reordering kernel (rt_kernel_sorted.h) */
-    RT_N_WALKS
-};
+/* The f64 render kernels by walk form (context.h: RtWalkForm) and variant; nullptr: not built for that variant. */
 typedef void (*render_kernel_t)(RtSceneView, RtFrame, double*, unsigned long long*);
 static render_kernel_t const g_kernels[RT_N_WALKS][RT_N_VARIANTS] = {
     {rt_render_kernel<RtCfgV0>, rt_render_kernel<RtCfgV1>, rt_render_kernel<RtCfgV2>, rt_render_kernel<RtCfgV3>, rt_render_kernel<RtCfgV4>,
@@ -160,58 +131,6 @@ static render_kernel_t const g_kernels[RT_N_WALKS][RT_N_VARIANTS] = {
 static const struct { int block; uint32_t bits; } g_walks[RT_N_WALKS] = {
     {RT_BLOCK, 0u}, {RT_BLOCK, RT_BIT_SPHERE_MEDIA}, {RT_BLOCK, RT_BIT_SS}, {RT_BLOCK, RT_BIT_SS | RT_BIT_SPHERE_MEDIA},
     {RT_BLOCK, RT_BIT_SS | RT_BIT_HC}, {RT_BLOCK, RT_BIT_SS | RT_BIT_HC | RT_BIT_SPHERE_MEDIA}, {RT_BLOCK, RT_BIT_LDS_NODES}, {RT_SORT_BLOCK, RT_BIT_SORTED}};
-
-/* a scene-specialised kernel (jit.cpp) of one precision.  The first five members say how loading it differs between the two
- * (load_specialised) */
-struct RtJitSlot {
-    const char* what;          /* for error texts */
-    bool f32;                  /* the f32 build of the kernel */
-    bool recompile_refused;    /* f64: compile once more when the driver refuses a cached object */
-    bool block_from_bounds;    /* f64: the workgroup size is the kernel's launch bound = its sort domain (experiments build it for 512) */
-    bool sticky;               /* f32: honours RT1W_NO_JIT, renders look at the caches once per context, a failure is remembered with
-                                * its reason (rt1w_context_specialise reports it) */
-    std::string src, key;      /* generated source (empty: scene not eligible), cache key */
-    hipModule_t mod = nullptr;
-    RtKernel k{};              /* k.jit != nullptr once loaded */
-    uint32_t vgprs = 0;
-    bool tried = false;
-    bool failed = false;       /* f64: a compile was tried and failed, renders do not try again (render_common); f32: see `sticky` */
-    std::string error;
-};
-
-struct rt1w_context {
-    int device = 0;
-    int n_cu = 0; /* compute units: a persistent grid is n_cu x the workgroups resident per CU (kernel_grid) */
-    RtLane lane[2];
-    hipEvent_t ev_first = nullptr;
-    void* d_nodes = nullptr; void* d_lights = nullptr; void* d_materials = nullptr;
-    void* d_textures = nullptr; void* d_perlin = nullptr; void* d_images = nullptr;
-    RtSceneView view{};
-    double* d_out = nullptr; size_t out_bytes = 0;
-    void* dn_buf[3] = {nullptr, nullptr, nullptr}; size_t dn_bytes[3] = {0, 0, 0}; /* rt1w_denoise: two colour buffers and the guide buffer */
-    RtKernel k64[RT_N_WALKS][RT_N_VARIANTS] = {}; /* g_kernels, queried at creation; the node-cache walks only with a walk table */
-    bool walk_table = false; uint32_t walk_table_first = 0;
-    bool sphere_media = false; /* every medium of the scene is bounded by a bare Sphere: the sphere-media walks serve */
-    int variant = 0;
-    bool has_media = false, has_tex = false, has_msphere = false;
-    uint32_t n_nodes = 0, scope_depth = 0;
-    void* wf_state = nullptr; /* the wavefront form's own state (librt1w_lab.so: wavefront.hip), freed through its destroy hook */
-    uint32_t stack_need = 0;
-    RtKernel ref[4] = {}; /* reference-stream kernels by rt1w_internal_ref_kernel mode: sweep, stack walk, reordering V0, reordering every-feature */
-    void* f32_scene = nullptr;   /* context_f32.hip: f32 copies of the scene arrays, built at the first f32 render */
-    bool f32_tried = false;
-    /* pair walk (rt_walk_pair.h): records of an eligible scene (sphere-only, variant 5); its kernels, plain and reordering (grid 0: the
-     * scene is not eligible) */
-    void* d_pw_inner = nullptr; void* d_pw_groups = nullptr;
-    RtPwView pw{};
-    std::string pw_why;
-    RtKernel pw_k[2] = {};
-    /* host copies of the flat arrays the two opt-in modes convert on first use (a scene may be destroyed before its contexts) */
-    std::vector<RtNode> h_nodes, h_lights; std::vector<RtMaterial> h_materials; std::vector<RtTexture> h_textures; std::vector<RtPerlin> h_perlin;
-    RtKernel k32[RT_N_VARIANTS][3] = {}; /* f32 kernels by variant and rt1w_internal_f32_kernel mode: plain, reordering, pair walk */
-    RtJitSlot jit{"specialised kernel", false, true, true, false};
-    RtJitSlot jit32{"f32 specialised kernel", true, false, false, true}; /* loaded only where `jit` is */
-};
 
 namespace {
 
@@ -278,25 +197,6 @@ int ensure_f32_scene(rt1w_context* c) {
     }
     return RT1W_OK;
 }
-int validate(const rt1w_context* c, const rt1w_render_params* p) {
-    if (!c || !p) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }
-    if (p->width < 2 || p->height < 2) { rt1w::set_error("width and height must be >= 2 (u,v divide by W-1, H-1; main.rs:968-969)"); return RT1W_ERR_INVALID; }
-    if (p->tile_w == 0 || p->tile_h == 0 || (uint64_t)p->x0 + p->tile_w > p->width || (uint64_t)p->y0 + p->tile_h > p->height) {
-        rt1w::set_error("tile outside the image"); return RT1W_ERR_INVALID;
-    }
-    if (p->spp == 0) { rt1w::set_error("spp must be > 0"); return RT1W_ERR_INVALID; }
-    if ((p->strip_rows == 0) != (p->strip_period == 0) || p->strip_period < p->strip_rows) {
-        rt1w::set_error("strip_rows / strip_period: both 0, or 0 < strip_rows <= strip_period"); return RT1W_ERR_INVALID;
-    }
-    if (p->precision != RT1W_PRECISION_F64 && p->precision != RT1W_PRECISION_F32) { rt1w::set_error("unknown precision"); return RT1W_ERR_UNSUPPORTED; }
-    if (p->strip_rows) {
-        const uint64_t last = (uint64_t)p->tile_h - 1u;
-        const uint64_t j = (uint64_t)p->y0 + (last / p->strip_rows) * p->strip_period + last % p->strip_rows;
-        if (j >= p->height) { rt1w::set_error("interleaved tile: last strip outside the image"); return RT1W_ERR_INVALID; }
-    }
-    if ((uint64_t)p->sample_offset + p->spp > 0xFFFFFFFFull) { rt1w::set_error("sample index overflow"); return RT1W_ERR_INVALID; }
-    return RT1W_OK;
-}
 
 /* the shading-side leaf functions ON THE DEVICE, for known-answer tests of what no artefact of the reference pins:
  * mode 0 Texture::value(u, v, p) of texture `tex` (texture.rs:40-89); mode 1 Perlin::noise(p) and Perlin::turb(p, 7) of
@@ -357,41 +257,6 @@ int first_use(const rt1w_context* c, RtKernel& slot, const RtKernel& k) {
     const int grid = kernel_grid(c, k);
     if (!grid) return RT1W_ERR_DEVICE;
     slot = k; slot.grid = grid;
-    return RT1W_OK;
-}
-
-/* the frame of a render of `p`, but for its chunking (chunk, n_chunks: the caller's) */
-RtFrame frame_of(const rt1w_render_params* p) {
-    RtFrame f{};
-    f.width = p->width; f.height = p->height;
-    f.x0 = p->x0; f.y0 = p->y0; f.tile_w = p->tile_w; f.tile_h = p->tile_h;
-    f.spp = p->spp; f.sample_offset = p->sample_offset; f.max_depth = p->max_depth;
-    f.global_seed = p->global_seed;
-    f.strip_rows = p->strip_rows; f.strip_period = p->strip_period;
-    f.probe = (p->flags & RT1W_PROBE_COHERENT) ? 1u : 0u;
-    return f;
-}
-
-/* ms between the two events of the lane, once its stream has drained */
-double lane_ms(const RtLane& l) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
-    return ms;
-}
-
-/* the host clock of an entry, for rt1w_stats.total_ms */
-struct RtTimer {
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
-
-/* RT1W_FORCE_VARIANT: `*v` becomes the variant the flags name, if they name one (allow_v4: the order-aware V4, which exists in f64 only) */
-int forced_variant(const rt1w_context* c, uint32_t flags, bool allow_v4, int* v) {
-    if (!((flags >> 8) & 0xFFu)) return RT1W_OK;
-    *v = (int)((flags >> 8) & 0xFFu) - 1;
-    if ((*v == 4 && !allow_v4) || !rt_variant_valid(*v, c->n_nodes, c->has_media, c->has_tex, c->has_msphere, c->scope_depth)) {
-        rt1w::set_error("forced kernel variant does not cover this scene's features"); return RT1W_ERR_INVALID;
-    }
     return RT1W_OK;
 }
 
@@ -633,6 +498,9 @@ int render_wavefront(rt1w_context* c, const rt1w_render_params* p, const RtLaunc
     return RT1W_OK;
 }
 
+} // namespace
+
+namespace rt1w {
 int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, rt1w_stats* stats) {
     /* a render this long repays the 1-8 s of the compiler: 2^35 paths where the gain is ~1.3x (scenes the generic sweep
      * handles), 2^32 where it is 1.5-2.3x (scenes the generic code hands to the stack walk).  RT1W_NO_JIT: never compile
@@ -658,7 +526,6 @@ int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, r
     return render_finish(l, L, stats);
 }
 
-/* the context's framebuffer, grown to at least `bytes` */
 int reserve_out(rt1w_context* c, size_t bytes) {
     if (bytes <= c->out_bytes) return RT1W_OK;
     if (c->d_out) (void)hipFree(c->d_out);
@@ -667,11 +534,9 @@ int reserve_out(rt1w_context* c, size_t bytes) {
     c->out_bytes = bytes;
     return RT1W_OK;
 }
-
-} // namespace
+} // namespace rt1w
 
 extern "C" {
-
 
 int rt1w_device_count(void) {
     int n = 0;
@@ -699,13 +564,10 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
               upload(&c->d_perlin, s->perlin.data(), s->perlin.size() * sizeof(RtPerlin)) &&
               upload(&c->d_images, s->images.data(), s->images.size());
     if (!ok) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
-    RtSceneView& v = c->view;
+    RtSceneView& v = c->view = view_of(*s);
     v.nodes = (const RtNode*)c->d_nodes; v.lights = (const RtNode*)c->d_lights;
     v.materials = (const RtMaterial*)c->d_materials; v.textures = (const RtTexture*)c->d_textures;
     v.perlin = (const RtPerlin*)c->d_perlin; v.images = (const uint8_t*)c->d_images;
-    v.root = s->flat_root; v.n_nodes = (uint32_t)s->flat_nodes.size(); v.n_lights = (uint32_t)s->flat_lights.size();
-    v.n_materials = (uint32_t)s->materials.size(); v.n_textures = (uint32_t)s->textures.size(); v.pad = 0;
-    v.camera = s->camera; v.background = s->background;
     hipDeviceProp_t prop;
     if (!hip_ok(hipGetDeviceProperties(&prop, device_id), "hipGetDeviceProperties")) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
     c->n_cu = prop.multiProcessorCount;
@@ -972,267 +834,6 @@ int rt1w_render(rt1w_context* c, const rt1w_render_params* p, double* out_rgb, r
     } else if (!hip_ok(hipMemcpy(out_rgb, c->d_out, bytes, hipMemcpyDeviceToHost), "framebuffer copy")) return RT1W_ERR_DEVICE;
     if (stats) stats->total_ms = timer.ms();
     return RT1W_OK;
-}
-
-/* ---- first-hit feature buffers (include/rt1w.h: rt1w_render_aov) ---- */
-} // extern "C"
-namespace {
-/* the one flag the AOV entries take besides RT1W_FORCE_VARIANT: everything else is named and refused */
-int aov_check_flags(uint32_t flags) {
-    static const struct { uint32_t bit; const char* name; } known[] = {
-        {RT1W_OUT_SUM, "RT1W_OUT_SUM"}, {RT1W_UNSORTED, "RT1W_UNSORTED"}, {RT1W_LDS_NODES, "RT1W_LDS_NODES"}, {RT1W_GENERIC, "RT1W_GENERIC"},
-        {RT1W_WAVEFRONT, "RT1W_WAVEFRONT"}, {RT1W_OUT_FRAME, "RT1W_OUT_FRAME"}, {RT1W_RNG_REFERENCE, "RT1W_RNG_REFERENCE"},
-        {RT1W_CLASSIC_WALK, "RT1W_CLASSIC_WALK"}, {RT1W_NO_NODE_CACHE, "RT1W_NO_NODE_CACHE"}, {RT1W_PROBE_COHERENT, "RT1W_PROBE_COHERENT"}};
-    const uint32_t bad = flags & ~(0xFFu << 8);
-    if (!bad) return RT1W_OK;
-    for (const auto& k : known)
-        if (bad & k.bit) { rt1w::set_error(std::string(k.name) + " does not apply to the AOV entries (flags: 0 or RT1W_FORCE_VARIANT)"); return RT1W_ERR_INVALID; }
-    char buf[96];
-    snprintf(buf, sizeof buf, "unknown flag 0x%x for the AOV entries (flags: 0 or RT1W_FORCE_VARIANT)", bad & (0u - bad));
-    rt1w::set_error(buf);
-    return RT1W_ERR_INVALID;
-}
-
-/* the deep entries' two extra arguments (include/rt1w.h: rt1w_render_aov_deep); null = the first-hit buffers */
-struct AovDeep { uint32_t max_specular; double max_fuzz; };
-int aov_deep_validate(uint32_t max_specular, double max_fuzz) {
-    if (rt_aov_deep_args_ok(max_specular, max_fuzz)) return RT1W_OK;
-    rt1w::set_error("max_specular must be 0 .. 64 and max_fuzz finite and >= 0");
-    return RT1W_ERR_INVALID;
-}
-
-/* validate, launch the AOV kernel of the context's (or the forced) variant into d_out, wait, fill stats */
-int render_aov_common(rt1w_context* c, const rt1w_render_params* p, const AovDeep* deep, double* d_out, rt1w_stats* stats) {
-    int variant = c->variant;
-    const int rc = forced_variant(c, p->flags, true, &variant);
-    if (rc < 0) return rc;
-    RtFrame f = frame_of(p);
-    f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u; /* not read by the AOV kernels */
-    RtLane& l = c->lane[0];
-    if (rt1w_internal_aov_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_aov_sizeof(1) != sizeof(RtFrame)) {
-        rt1w::set_error("AOV kernels built against another scene layout"); return RT1W_ERR_DEVICE;
-    }
-    const void* fn = deep ? rt1w_internal_aov_deep_kernel(variant) : rt1w_internal_aov_kernel(variant);
-    if (!fn) { rt1w::set_error("no AOV kernel of this variant"); return RT1W_ERR_DEVICE; }
-    const unsigned grid = rt1w_internal_aov_grid(&f);
-    /* (view, frame, out), the deep kernel's (view, frame, max_specular, max_fuzz, out, rays traced): the lane's second counter, the
-     * one the render kernels count their segments in */
-    AovDeep dv = deep ? *deep : AovDeep{0u, 0.0};
-    unsigned long long* d_rays = l.d_counters + 1;
-    void* args_first[] = {&c->view, &f, &d_out};
-    void* args_deep[] = {&c->view, &f, &dv.max_specular, &dv.max_fuzz, &d_out, &d_rays};
-    if (deep && !hip_ok(hipMemsetAsync(d_rays, 0, sizeof *d_rays, l.stream), "AOV counter")) return RT1W_ERR_DEVICE;
-    (void)hipEventRecord(l.ev0, l.stream);
-    if (!hip_ok(hipLaunchKernel(fn, dim3(grid), dim3(RT_BLOCK), deep ? args_deep : args_first, 0, l.stream), "AOV kernel launch")) return RT1W_ERR_DEVICE;
-    (void)hipEventRecord(l.ev1, l.stream);
-    if (deep && !hip_ok(hipMemcpyAsync(l.h_counters + 1, d_rays, sizeof *d_rays, hipMemcpyDeviceToHost, l.stream), "AOV counter copy")) return RT1W_ERR_DEVICE;
-    if (!hip_ok(hipStreamSynchronize(l.stream), "AOV kernel")) return RT1W_ERR_DEVICE;
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->paths = (uint64_t)p->tile_w * p->tile_h * p->spp;
-        stats->segments = deep ? l.h_counters[1] : stats->paths; /* first hit: one camera ray per sample */
-        stats->kernel_ms = lane_ms(l);
-        stats->chunk = p->spp; stats->n_chunks = 1u;
-        stats->grid = grid; stats->block = RT_BLOCK;
-        stats->variant = (uint32_t)variant;
-        stats->passes = 1u;
-    }
-    return RT1W_OK;
-}
-int aov_validate(const rt1w_context* c, const rt1w_render_params* p, const void* out) {
-    int rc = validate(c, p);
-    if (rc < 0) return rc;
-    if (!out) { rt1w::set_error("null output"); return RT1W_ERR_INVALID; }
-    if ((rc = aov_check_flags(p->flags)) < 0) return rc;
-    if (p->precision != RT1W_PRECISION_F64) { rt1w::set_error("the AOV entries are f64 only (RT1W_PRECISION_F64)"); return RT1W_ERR_UNSUPPORTED; }
-    return RT1W_OK;
-}
-/* the host-memory entries: through the context's framebuffer, as rt1w_render grows it */
-int render_aov_host(rt1w_context* c, const rt1w_render_params* p, const AovDeep* deep, double* out_aov, rt1w_stats* stats) {
-    int rc = deep ? aov_deep_validate(deep->max_specular, deep->max_fuzz) : RT1W_OK; /* first: needs no context */
-    if (rc < 0) return rc;
-    if ((rc = aov_validate(c, p, out_aov)) < 0) return rc;
-    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    const RtTimer timer;
-    const size_t bytes = (size_t)p->tile_w * p->tile_h * RT1W_AOV_CHANNELS * sizeof(double);
-    if ((rc = reserve_out(c, bytes)) < 0) return rc;
-    if ((rc = render_aov_common(c, p, deep, c->d_out, stats)) < 0) return rc;
-    if (!hip_ok(hipMemcpy(out_aov, c->d_out, bytes, hipMemcpyDeviceToHost), "AOV copy")) return RT1W_ERR_DEVICE;
-    if (stats) stats->total_ms = timer.ms();
-    return RT1W_OK;
-}
-/* the device-memory entries */
-int render_aov_device(rt1w_context* c, const rt1w_render_params* p, const AovDeep* deep, void* d_out_aov, rt1w_stats* stats) {
-    int rc = deep ? aov_deep_validate(deep->max_specular, deep->max_fuzz) : RT1W_OK;
-    if (rc < 0) return rc;
-    if ((rc = aov_validate(c, p, d_out_aov)) < 0) return rc;
-    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    const RtTimer timer;
-    if ((rc = render_aov_common(c, p, deep, (double*)d_out_aov, stats)) < 0) return rc;
-    if (stats) stats->total_ms = timer.ms();
-    return RT1W_OK;
-}
-} // namespace
-extern "C" {
-
-int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_aov, rt1w_stats* stats) { return render_aov_host(c, p, nullptr, out_aov, stats); }
-int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d_out_aov, rt1w_stats* stats) { return render_aov_device(c, p, nullptr, d_out_aov, stats); }
-
-int rt1w_render_aov_deep(rt1w_context* c, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, double* out_aov, rt1w_stats* stats) {
-    const AovDeep deep{max_specular, max_fuzz};
-    return render_aov_host(c, p, &deep, out_aov, stats);
-}
-int rt1w_render_aov_deep_device(rt1w_context* c, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, void* d_out_aov, rt1w_stats* stats) {
-    const AovDeep deep{max_specular, max_fuzz};
-    return render_aov_device(c, p, &deep, d_out_aov, stats);
-}
-
-/* ---- feature-guided denoiser (include/rt1w.h: rt1w_denoise) ---- */
-} // extern "C"
-namespace {
-int denoise_validate(const rt1w_context* c, const rt1w_denoise_params* p) {
-    if (!c || !p) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }
-    if (p->width == 0 || p->height == 0 || p->width > 0x40000000u || p->height > 0x40000000u) { rt1w::set_error("denoise: width and height must be 1 .. 2^30"); return RT1W_ERR_INVALID; }
-    if (p->iterations > 8u) { rt1w::set_error("denoise: at most 8 iterations"); return RT1W_ERR_INVALID; }
-    if (p->flags & ~RT1W_DENOISE_KEEP_ALBEDO) { rt1w::set_error("denoise: unknown flag (flags: 0 or RT1W_DENOISE_KEEP_ALBEDO)"); return RT1W_ERR_INVALID; }
-    const double sig[3] = {p->sigma_colour, p->sigma_normal, p->sigma_depth};
-    for (double v : sig)
-        if (!(v >= 0.0) || v > 1.7976931348623157e308) { rt1w::set_error("denoise: a sigma must be finite and >= 0 (0 = default)"); return RT1W_ERR_INVALID; }
-    return RT1W_OK;
-}
-/* the context's two colour buffers and guide buffer, grown to the image */
-int denoise_reserve(rt1w_context* c, size_t npix) {
-    for (int k = 0; k < 3; ++k) {
-        const size_t bytes = npix * rt1w_internal_denoise_sizeof(k == 2 ? 1 : 0);
-        if (bytes <= c->dn_bytes[k]) continue;
-        if (c->dn_buf[k]) (void)hipFree(c->dn_buf[k]);
-        c->dn_buf[k] = nullptr; c->dn_bytes[k] = 0;
-        if (!hip_ok(hipMalloc(&c->dn_buf[k], bytes), "hipMalloc(denoise buffers)")) return RT1W_ERR_NOMEM;
-        c->dn_bytes[k] = bytes;
-    }
-    return RT1W_OK;
-}
-/* prepare pass and levels on lane 0's stream, wait; *kernel_ms (optional) their HIP-event time, launch[0..1] grid / block of the level kernel */
-int denoise_common(rt1w_context* c, const rt1w_denoise_params* p, const double* d_frame, const double* d_aov, double* d_out, double* kernel_ms,
-                   unsigned launch[2]) {
-    int rc = denoise_reserve(c, (size_t)p->width * p->height);
-    if (rc < 0) return rc;
-    RtLane& l = c->lane[0];
-    (void)hipEventRecord(l.ev0, l.stream);
-    rc = rt1w_internal_denoise_launch(p->width, p->height, p->iterations, p->flags, p->sigma_colour, p->sigma_normal, p->sigma_depth, d_frame, d_aov,
-                                      d_out, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], l.stream, launch);
-    if (rc == -2) { rt1w::set_error("denoise: parameters refused"); return RT1W_ERR_INVALID; }
-    if (rc != 0) { rt1w::set_error("denoise kernel launch failed"); return RT1W_ERR_DEVICE; }
-    (void)hipEventRecord(l.ev1, l.stream);
-    if (!hip_ok(hipStreamSynchronize(l.stream), "denoise kernels")) return RT1W_ERR_DEVICE;
-    if (kernel_ms) *kernel_ms = lane_ms(l);
-    return RT1W_OK;
-}
-void denoise_stats(const rt1w_denoise_params* p, double kernel_ms, const unsigned launch[2], rt1w_stats* stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->paths = (uint64_t)p->width * p->height;
-    stats->kernel_ms = kernel_ms;
-    stats->grid = launch[0]; stats->block = launch[1];
-    stats->passes = 1u;
-}
-} // namespace
-extern "C" {
-
-int rt1w_denoise(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, double* out, rt1w_stats* stats) {
-    int rc = denoise_validate(c, p);
-    if (rc < 0) return rc;
-    if (!frame || !aov || !out) { rt1w::set_error("null buffer"); return RT1W_ERR_INVALID; }
-    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    const RtTimer timer;
-    const size_t npix = (size_t)p->width * p->height;
-    /* the context's framebuffer holds the frame (filtered in place) and, behind it, the feature buffers */
-    if ((rc = reserve_out(c, npix * (3 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
-    double* d_frame = c->d_out;
-    double* d_aov = c->d_out + npix * 3;
-    if (!hip_ok(hipMemcpy(d_frame, frame, npix * 3 * sizeof(double), hipMemcpyHostToDevice), "denoise: frame copy")) return RT1W_ERR_DEVICE;
-    if (!hip_ok(hipMemcpy(d_aov, aov, npix * RT1W_AOV_CHANNELS * sizeof(double), hipMemcpyHostToDevice), "denoise: feature buffer copy")) return RT1W_ERR_DEVICE;
-    double ms = 0.0;
-    unsigned launch[2] = {0u, 0u};
-    if ((rc = denoise_common(c, p, d_frame, d_aov, d_frame, &ms, launch)) < 0) return rc;
-    if (!hip_ok(hipMemcpy(out, d_frame, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "denoise: result copy")) return RT1W_ERR_DEVICE;
-    if (stats) {
-        denoise_stats(p, ms, launch, stats);
-        stats->total_ms = timer.ms();
-    }
-    return RT1W_OK;
-}
-
-int rt1w_denoise_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, void* d_out, rt1w_stats* stats) {
-    int rc = denoise_validate(c, p);
-    if (rc < 0) return rc;
-    if (!d_frame || !d_aov || !d_out) { rt1w::set_error("null buffer"); return RT1W_ERR_INVALID; }
-    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    const RtTimer timer;
-    double ms = 0.0;
-    unsigned launch[2] = {0u, 0u};
-    if ((rc = denoise_common(c, p, (const double*)d_frame, (const double*)d_aov, (double*)d_out, &ms, launch)) < 0) return rc;
-    if (stats) {
-        denoise_stats(p, ms, launch, stats);
-        stats->total_ms = timer.ms();
-    }
-    return RT1W_OK;
-}
-
-} // extern "C"
-namespace {
-/* rt1w_render_denoised and, with `deep`, rt1w_render_denoised_deep */
-int render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, const AovDeep* deep, double* out_rgb, rt1w_stats* stats) {
-    int rc = deep ? aov_deep_validate(deep->max_specular, deep->max_fuzz) : RT1W_OK;
-    if (rc < 0) return rc;
-    if ((rc = validate(c, p)) < 0) return rc;
-    if (!out_rgb) { rt1w::set_error("null output"); return RT1W_ERR_INVALID; }
-    static const struct { uint32_t bit; const char* name; } refused[] = {
-        {RT1W_OUT_SUM, "RT1W_OUT_SUM"}, {RT1W_OUT_FRAME, "RT1W_OUT_FRAME"}, {RT1W_RNG_REFERENCE, "RT1W_RNG_REFERENCE"}, {RT1W_PROBE_COHERENT, "RT1W_PROBE_COHERENT"}};
-    for (const auto& k : refused)
-        if (p->flags & k.bit) { rt1w::set_error(std::string(k.name) + " does not apply to rt1w_render_denoised"); return RT1W_ERR_INVALID; }
-    if (p->strip_rows) { rt1w::set_error("rt1w_render_denoised takes a contiguous tile (strip_rows must be 0): denoise the gathered frame with rt1w_denoise"); return RT1W_ERR_INVALID; }
-    if (p->precision != RT1W_PRECISION_F64) { rt1w::set_error("RT1W_PRECISION_F32 does not apply to rt1w_render_denoised (the filter is f64 only)"); return RT1W_ERR_INVALID; }
-    rt1w_denoise_params dp;
-    memset(&dp, 0, sizeof dp);
-    if (d) dp = *d;
-    if ((dp.width && dp.width != p->tile_w) || (dp.height && dp.height != p->tile_h)) { rt1w::set_error("denoise: width / height must be 0 or the tile's"); return RT1W_ERR_INVALID; }
-    dp.width = p->tile_w; dp.height = p->tile_h;
-    if ((rc = denoise_validate(c, &dp)) < 0) return rc;
-    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    const RtTimer timer;
-    const size_t npix = (size_t)p->tile_w * p->tile_h;
-    if ((rc = reserve_out(c, npix * (3 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
-    double* d_frame = c->d_out;
-    double* d_aov = c->d_out + npix * 3;
-    rt1w_stats st;
-    memset(&st, 0, sizeof st);
-    if ((rc = render_common(c, p, d_frame, &st)) < 0) return rc;
-    rt1w_render_params ap = *p; /* the feature buffers of the same tile, samples and seed, by the scene's own variant */
-    ap.flags = 0u;
-    rt1w_stats sa;
-    if ((rc = render_aov_common(c, &ap, deep, d_aov, &sa)) < 0) return rc;
-    double ms = 0.0;
-    unsigned launch[2] = {0u, 0u};
-    if ((rc = denoise_common(c, &dp, d_frame, d_aov, d_frame, &ms, launch)) < 0) return rc;
-    if (!hip_ok(hipMemcpy(out_rgb, d_frame, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "denoised frame copy")) return RT1W_ERR_DEVICE;
-    if (stats) {
-        *stats = st;
-        stats->kernel_ms = st.kernel_ms + sa.kernel_ms + ms;
-        stats->grid = launch[0]; stats->block = launch[1];
-        stats->total_ms = timer.ms();
-    }
-    return RT1W_OK;
-}
-} // namespace
-extern "C" {
-
-int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, double* out_rgb, rt1w_stats* stats) {
-    return render_denoised(c, p, d, nullptr, out_rgb, stats);
-}
-int rt1w_render_denoised_deep(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, uint32_t max_specular, double max_fuzz,
-                              double* out_rgb, rt1w_stats* stats) {
-    const AovDeep deep{max_specular, max_fuzz};
-    return render_denoised(c, p, d, &deep, out_rgb, stats);
 }
 
 uint32_t rt1w_abi_sizeof(int what) {

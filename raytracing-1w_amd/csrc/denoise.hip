@@ -1,7 +1,7 @@
 /* denoise.hip -- the filter kernels of rt1w_denoise (include/rt1w.h): a prepare pass and one launch per a-trous level over rt_denoise.h.
  *
  * Kept out of context.hip, inside its own namespace (the pattern of aov.hip), so that none of the render kernels' code objects and none
- * of the run-time compiler's inputs moves with it.  The host half (validation, buffers, timing, copies) is in context.hip, which calls
+ * of the run-time compiler's inputs moves with it.  The host half (validation, buffers, timing, copies) is in features.hip, which calls
  * the launcher below.
  *
  * Work mapping: one lane per pixel, an 8 x 8 pixel block per wave, 2 x 2 blocks (16 x 16 pixels) per workgroup of 256 lanes.  Every

@@ -171,6 +171,54 @@ def test_aov_abi_surface(rt):
     assert rt._lib.rt1w_render_aov_device(None, None, C.c_void_p(16), None) == rt.ERR_INVALID
 
 
+# what every entry refuses in an rt1w_render_params (include/rt1w.h; csrc/render_params.h: params_check, the text the entries and the
+# twin share): name -> (fields changed in a good 64 x 16 frame with an 8-row tile, the documented return code)
+_BAD_PARAMS = {
+    "tile outside the image": (dict(x0=60, tile_w=8), "ERR_INVALID"),
+    "tile below the image": (dict(y0=12), "ERR_INVALID"),
+    "spp 0": (dict(spp=0), "ERR_INVALID"),
+    "strip_rows without strip_period": (dict(strip_rows=2), "ERR_INVALID"),
+    "strip_period without strip_rows": (dict(strip_period=4), "ERR_INVALID"),
+    "strip_period below strip_rows": (dict(strip_rows=4, strip_period=2), "ERR_INVALID"),
+    # tile row 7 is image row 0 + (7 // 2) * 8 + 7 % 2 = 25 of 16, while y0 + tile_h = 8 fits: the twin used to render this
+    "last interleaved strip outside the image": (dict(strip_rows=2, strip_period=8), "ERR_INVALID"),
+    # the last sample index would be 2^32: the twin used to render this too
+    "sample_offset + spp over 2^32 - 1": (dict(sample_offset=0xFFFFFFFF, spp=1), "ERR_INVALID"),
+    "sample_offset + spp over 2^32 - 1, large spp": (dict(sample_offset=0x80000000, spp=0x80000000), "ERR_INVALID"),
+    "unknown precision": (dict(precision=7), "ERR_UNSUPPORTED"),
+    "f32": (dict(precision=1), "ERR_UNSUPPORTED"),   # a known precision, but the AOV entries are f64 only
+}
+
+
+@pytest.mark.parametrize("case", sorted(_BAD_PARAMS))
+def test_twin_refuses_what_the_entries_refuse(rt, case):
+    """The twin is the expected side of the GPU bit-equality tests, so it must refuse the parameter sets the entries refuse, with
+    the same code: both twins (first hit and deep) run the entries' own check.  The unchanged frame, the largest sample range and
+    an interleaved tile whose last strip just fits are accepted."""
+    lab = rt.load_lab()
+    sc = rt.Scene.reference(5, build_seed=1)
+    out = np.zeros(8 * 64 * 8)
+
+    def twins(p):
+        lab.rt1w_lab_aov_host.restype = lab.rt1w_lab_aov_deep_host.restype = C.c_int
+        lab.rt1w_lab_aov_host.argtypes = [C.c_void_p, C.POINTER(rt.RenderParams), C.c_void_p]
+        lab.rt1w_lab_aov_deep_host.argtypes = [C.c_void_p, C.POINTER(rt.RenderParams), C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        return (lab.rt1w_lab_aov_host(sc._h, C.byref(p), out.ctypes.data_as(C.c_void_p)),
+                lab.rt1w_lab_aov_deep_host(sc._h, C.byref(p), 2, 0.0, out.ctypes.data_as(C.c_void_p), None, None))
+
+    def params(**changed):
+        p = rt.RenderParams(64, 16, 0, 0, 64, 8, 1, 0, 50, 0, 0, 0, 0, 0, 0, 0)
+        for k, v in changed.items():
+            setattr(p, k, v)
+        return p
+
+    assert twins(params()) == (rt.OK, rt.OK)
+    assert twins(params(sample_offset=0xFFFFFFFE, spp=1)) == (rt.OK, rt.OK)
+    assert twins(params(strip_rows=2, strip_period=4)) == (rt.OK, rt.OK)   # tile row 7 is image row 13 of 16
+    changed, code = _BAD_PARAMS[case]
+    assert twins(params(**changed)) == (getattr(rt, code), getattr(rt, code)), case
+
+
 # ------------------------------------------------------------------------------------------------------------------ GPU tier --
 
 def _valid_variants(info):
