@@ -51,9 +51,18 @@ struct HostStack {
 };
 }
 
+/* the pixel sums exactly as the kernels keep them (rt_kernel_plain.h; rt_kernels.h: rt_resolve_kernel): a chunk's samples are added
+ * in 64 bits (RtV3d, rt_v3d_add), the chunk sums are added in order in 64 bits, the mean is taken in 64 bits -- in the f32 build of this
+ * file too, where RtV3 is three floats */
+static RtV3d into_sampled64(RtV3d sum, uint32_t samples_per_pixel) { /* rt_into_sampled (color.rs:14-21) of the f64 build */
+    const rt_f64 scale = 1.0 / (rt_f64)samples_per_pixel;
+    const rt_f64 r = rt_isnan64(sum.x) ? 0.0 : sum.x, g = rt_isnan64(sum.y) ? 0.0 : sum.y, b = rt_isnan64(sum.z) ? 0.0 : sum.z;
+    return rt_v3d(r * scale, g * scale, b * scale);
+}
+
 template <class Cfg>
 static void run_path(const RtSceneView& sc, const RtFrame& f, uint32_t px, uint32_t py, uint32_t s, HostStack& stk,
-                     RtV3& sum, uint64_t& segs, RtPath& path) { /* `path` lives as long as the pixel: the reference-stream build
+                     RtV3d& sum, uint64_t& segs, RtPath& path) { /* `path` lives as long as the pixel: the reference-stream build
                                                                    (-DRT_RNG_REFSTREAM) draws all samples of a pixel from one stream */
     rt_path_begin(sc, f, f.x0 + px, rt_frame_row(f, py), f.sample_offset + s, path);
     while (path.alive) {
@@ -61,26 +70,97 @@ static void run_path(const RtSceneView& sc, const RtFrame& f, uint32_t px, uint3
         RtGlobalNodes ns{sc.nodes};
         rt_path_step<Cfg>(sc, ns, path, stk);
     }
-    sum = sum + path.radiance;
+    sum = rt_v3d_add(sum, path.radiance);
 }
+
+#if !defined(RT_RNG_REFSTREAM)
+namespace {
+/* an array the pair walk's lane functions index like their LDS columns, bounds checked: a write or read outside is recorded, not done */
+template <class T>
+struct Checked {
+    std::vector<T> v;
+    bool* fault;
+    T dummy{};
+    T& operator[](long i) {
+        if (i < 0 || (size_t)i >= v.size()) { *fault = true; return dummy; }
+        return v[(size_t)i];
+    }
+};
+}
+namespace {
+/* one lane's pair-walk stack and queue (the kernels' LDS columns), bound-checked */
+struct PwMem {
+    bool fault = false;
+    RtPwLds<1, Checked<uint32_t>, Checked<float>, Checked<uint32_t>> m;
+    explicit PwMem(uint32_t stack_cap)
+        : m{{std::vector<uint32_t>(stack_cap), &fault}, {std::vector<float>(stack_cap), &fault}, {std::vector<uint32_t>(RT_PW_QCAP), &fault}} {}
+};
+}
+/* A path of a sphere scene as the pair-walk kernels run it (rt_kernel_plain.h: the PW arm of rt_render_ss_body / rt_render_plain_body):
+ * every segment's closest hit by the pair walk -- the root's box, then box work and leaf work in the order a lane alone in its wave
+ * takes them (box steps while it can, a pending group when it cannot), the NaN hand-overs to the one-entry-per-step walk -- and the
+ * second half of the step, rt_path_shade, on that hit.  Stack (`m`: the kernel's entries per lane) and queue are bound-checked. */
+static void run_path_pw(const RtSceneView& sc, const RtPwView& pw, const RtFrame& f, uint32_t px, uint32_t py, uint32_t s, HostStack& stk, PwMem& mem,
+                        RtV3d& sum, uint64_t& segs, RtPath& path) {
+    typedef RtCfgV5 Cfg;
+    RtGlobalNodes ns{sc.nodes};
+    rt_path_begin(sc, f, f.x0 + px, rt_frame_row(f, py), f.sample_offset + s, path);
+    while (path.alive) {
+        segs += path.depth_left != 0u ? 1u : 0u;
+        RtTrace tr;
+        tr.t = RT_R(0.0); tr.prim = RT_NONE; tr.scope = RT_NONE; tr.cls = RT_CLS_TERMINAL;
+        if (path.depth_left != 0u) {
+            RtPwLane L; L.cur = RT_PW_NONE; L.qh = 0u; L.qn = 0u; L.sp = 0;
+            double best_t = RT_INF; uint32_t best_prim = RT_NONE;
+            const RtV3 o = path.ray.o, d = path.ray.d, inv = rt_inv3(d);
+            const double frac = (path.ray.time - pw.ms_time0) / (pw.ms_time1 - pw.ms_time0);
+            bool bad = rt_isnan(frac), walking = bad;
+            if (!bad) walking = rt_pw_begin(pw, L, mem.m, o, inv, RT_R(0.001));
+            if (walking) {
+                while (!bad && !rt_pw_done(L) && !mem.fault) {
+                    if (rt_pw_can_box(L)) {
+                        rt_pw_box_step(pw, L, mem.m, o, inv, RT_R(0.001), best_t);
+                    } else if (L.qn > 0u) {
+                        rt_pw_group_step(pw, L, mem.m, o, d, inv, frac, RT_R(0.001), best_t, best_prim);
+                        if (rt_isnan(best_t)) bad = true;
+                    } else { mem.fault = true; } /* neither kind of work and not done: the state machine is stuck */
+                }
+                if (bad) { /* the hand-over of the kernels: the segment is redone by the one-entry-per-step walk */
+                    uint32_t scope_;
+                    best_t = RT_INF; best_prim = RT_NONE;
+                    rt_traverse_stack<Cfg, true>(sc, ns, sc.root, path.ray, RT_R(0.001), RT_INF, path.rng, stk, best_t, best_prim, scope_);
+                }
+                tr.t = best_t; tr.prim = best_prim; tr.scope = RT_NONE;
+                if (tr.prim != RT_NONE) {
+                    const uint32_t mk = RT_MAT_KINDF(ns.hot(tr.prim).mat) & 0xFFu;
+                    tr.cls = mk == RT_MAT_LAMBERTIAN ? RT_CLS_LAMBERT : mk == RT_MAT_DIELECTRIC ? RT_CLS_DIELECTRIC
+                           : mk == RT_MAT_METAL ? RT_CLS_METAL : mk == RT_MAT_ISOTROPIC ? RT_CLS_OTHER : RT_CLS_TERMINAL;
+                }
+            }
+        }
+        path.radiance = rt_v3(RT_R(0.0), RT_R(0.0), RT_R(0.0)); /* written by the terminal only: not carried across the walk */
+        rt_path_shade<Cfg>(sc, path, tr);
+    }
+    sum = rt_v3d_add(sum, path.radiance);
+}
+#else
+struct RtPwView;
+#endif
 
 extern "C" {
 
 struct orcflat_cam_bg { RtCamera cam; RtV3 bg; uint32_t root, pad; };
 
-/* arrays are the bytes of rt1w_scene_copy_flat selectors 0..6 */
-int orcflat_render(const void* nodes, uint32_t n_nodes, const void* lights, uint32_t n_lights, const void* materials,
-                   uint32_t n_materials, const void* textures, uint32_t n_textures, const void* perlin, const void* images,
-                   const void* cam_bg, const RtFrame* frame, int variant, int out_sum, int threads, double* out,
-                   uint64_t* segments_out, uint32_t* max_stack_out) {
-    RtSceneView sc;
-    std::memset(&sc, 0, sizeof sc);
-    const orcflat_cam_bg* cb = (const orcflat_cam_bg*)cam_bg;
-    sc.nodes = (const RtNode*)nodes; sc.lights = (const RtNode*)lights;
-    sc.materials = (const RtMaterial*)materials; sc.textures = (const RtTexture*)textures;
-    sc.perlin = (const RtPerlin*)perlin; sc.images = (const uint8_t*)images;
-    sc.root = cb->root; sc.n_nodes = n_nodes; sc.n_lights = n_lights; sc.n_materials = n_materials; sc.n_textures = n_textures;
-    sc.camera = cb->cam; sc.background = cb->bg;
+} /* extern "C" */
+
+/* the kernels' work decomposition over a scene view: chunk partial sums, then resolve.  `pw` (with variant 5): the pair-walk form,
+ * `pw_stack` stack entries per lane; nullptr: the one-entry-per-step walk.  0, -2 a traversal stack overflowed, -3 an index of the
+ * pair walk left its stack or queue */
+static int render_view(const RtSceneView& sc, const RtPwView* pw, uint32_t pw_stack, const RtFrame* frame, int variant, int out_sum, int threads,
+                       rt_f64* out, uint64_t* segments_out, uint32_t* max_stack_out) {
+#if defined(RT_RNG_REFSTREAM)
+    if (pw) return -1;
+#endif
     RtFrame f = *frame;
     if (f.chunk == 0 || f.chunk > f.spp) f.chunk = f.spp;
     f.n_chunks = (f.spp + f.chunk - 1u) / f.chunk;
@@ -90,18 +170,24 @@ int orcflat_render(const void* nodes, uint32_t n_nodes, const void* lights, uint
     std::atomic<int> bad(0);
     auto worker = [&]() {
         HostStack stk;
+#if !defined(RT_RNG_REFSTREAM)
+        PwMem pwmem(pw ? pw_stack : 1u);
+#endif
         uint64_t segs = 0;
         for (;;) {
             uint64_t p = next.fetch_add(1);
             if (p >= npix) break;
             uint32_t px = (uint32_t)(p % f.tile_w), py = (uint32_t)(p / f.tile_w);
-            RtV3 total = rt_v3(0.0, 0.0, 0.0);
+            RtV3d total = rt_v3d(0.0, 0.0, 0.0);
             RtPath path;
             for (uint32_t c = 0; c < f.n_chunks; ++c) {
                 uint32_t s = c * f.chunk;
                 uint32_t s_end = s + f.chunk < f.spp ? s + f.chunk : f.spp;
-                RtV3 sum = rt_v3(0.0, 0.0, 0.0);
+                RtV3d sum = rt_v3d(0.0, 0.0, 0.0);
                 for (; s < s_end; ++s) {
+#if !defined(RT_RNG_REFSTREAM)
+                    if (pw && variant == 5) { run_path_pw(sc, *pw, f, px, py, s, stk, pwmem, sum, segs, path); continue; }
+#endif
                     switch (variant) { /* the same feature-specialised variants the GPU library builds */
                         case 0: run_path<RtCfgV0>(sc, f, px, py, s, stk, sum, segs, path); break;
                         case 1: run_path<RtCfgV1>(sc, f, px, py, s, stk, sum, segs, path); break;
@@ -114,15 +200,18 @@ int orcflat_render(const void* nodes, uint32_t n_nodes, const void* lights, uint
                         default: run_path<RtCfgV3>(sc, f, px, py, s, stk, sum, segs, path); break;
                     }
                 }
-                total = total + sum;
+                total = rt_v3d(total.x + sum.x, total.y + sum.y, total.z + sum.z);
             }
-            if (!out_sum) total = rt_into_sampled(total, f.spp);
+            if (!out_sum) total = into_sampled64(total, f.spp);
             out[p * 3 + 0] = total.x; out[p * 3 + 1] = total.y; out[p * 3 + 2] = total.z;
         }
         seg_total += segs;
         uint32_t m = (uint32_t)stk.max_sp, cur = max_stack.load();
         while (m > cur && !max_stack.compare_exchange_weak(cur, m)) {}
         if (stk.overflow) bad = 1;
+#if !defined(RT_RNG_REFSTREAM)
+        if (pwmem.fault) bad = 2;
+#endif
     };
     if (threads < 1) threads = 1;
     std::vector<std::thread> pool;
@@ -131,7 +220,25 @@ int orcflat_render(const void* nodes, uint32_t n_nodes, const void* lights, uint
     for (auto& t : pool) t.join();
     if (segments_out) *segments_out = seg_total.load();
     if (max_stack_out) *max_stack_out = max_stack.load();
-    return bad.load() ? -2 : 0;
+    return bad.load() == 2 ? -3 : bad.load() ? -2 : 0;
+}
+
+extern "C" {
+
+/* arrays are the bytes of rt1w_scene_copy_flat selectors 0..6 */
+int orcflat_render(const void* nodes, uint32_t n_nodes, const void* lights, uint32_t n_lights, const void* materials,
+                   uint32_t n_materials, const void* textures, uint32_t n_textures, const void* perlin, const void* images,
+                   const void* cam_bg, const RtFrame* frame, int variant, int out_sum, int threads, rt_f64* out,
+                   uint64_t* segments_out, uint32_t* max_stack_out) {
+    RtSceneView sc;
+    std::memset(&sc, 0, sizeof sc);
+    const orcflat_cam_bg* cb = (const orcflat_cam_bg*)cam_bg;
+    sc.nodes = (const RtNode*)nodes; sc.lights = (const RtNode*)lights;
+    sc.materials = (const RtMaterial*)materials; sc.textures = (const RtTexture*)textures;
+    sc.perlin = (const RtPerlin*)perlin; sc.images = (const uint8_t*)images;
+    sc.root = cb->root; sc.n_nodes = n_nodes; sc.n_lights = n_lights; sc.n_materials = n_materials; sc.n_textures = n_textures;
+    sc.camera = cb->cam; sc.background = cb->bg;
+    return render_view(sc, nullptr, 0u, frame, variant, out_sum, threads, out, segments_out, max_stack_out);
 }
 
 /* 1: built with -DRT_RNG_REFSTREAM (the reference's ChaCha12 stream per pixel; include/rt1w_num.h) */
@@ -216,19 +323,39 @@ extern "C" int orcflat_walk_table_check(const void* nodes_, uint32_t n_nodes, ui
 }
 
 #if !defined(RT_RNG_REFSTREAM)
-namespace {
-/* an array the pair walk's lane functions index like their LDS columns, bounds checked: a write or read outside is recorded, not done */
-template <class T>
-struct Checked {
-    std::vector<T> v;
-    bool* fault;
-    T dummy{};
-    T& operator[](long i) {
-        if (i < 0 || (size_t)i >= v.size()) { *fault = true; return dummy; }
-        return v[(size_t)i];
-    }
-};
+/* Every consumer of a uniform draw in the core, fed ONE chosen draw: the generator's buffer is loaded so that each 64-bit take returns
+ * `bits` (all ones: the largest draw, 1 - 2^-53, which the f32 build rounds to 1.0f -- a value rand's own f32 shapes never return;
+ * 0: the smallest).  out[12], in 64 bits whatever the build: 0-2 rt_random_cosine_direction, 3-5 rt_random_to_sphere(0.5, 4),
+ * 6 the light rectangle's coordinate in [213, 343), 7 the free flight -100 ln(r), 8 the draw as the Schlick test compares it,
+ * 9-10 rt_random_in_unit_disk (first try from `bits`, further tries from the stream), 11 the shutter time in [0, 1) */
+extern "C" void orcflat_draw_probe(uint64_t bits, rt_f64* out) {
+    auto loaded = [bits]() {
+        RtRng r = rt_rng_pixel_sample(1u, 2u, 3u);
+        r.left = 4u; r.a0 = r.a2 = (uint32_t)bits; r.a1 = r.a3 = (uint32_t)(bits >> 32);
+        return r;
+    };
+    RtRng r = loaded();
+    RtV3 v = rt_random_cosine_direction(r);
+    out[0] = v.x; out[1] = v.y; out[2] = v.z;
+    r = loaded();
+    v = rt_random_to_sphere(RT_R(0.5), RT_R(4.0), r);
+    out[3] = v.x; out[4] = v.y; out[5] = v.z;
+    const double x = rt_range_from_bits(bits, RT_R(213.0), RT_R(343.0));
+    out[6] = x;
+    r = loaded();
+    const double flight = RT_R(-100.0) * rt_log(rt_take_f64(r));
+    out[7] = flight;
+    r = loaded();
+    const double draw = rt_take_f64(r);
+    out[8] = draw;
+    r = loaded();
+    v = rt_random_in_unit_disk(r);
+    out[9] = v.x; out[10] = v.y;
+    r = loaded();
+    const double time = rt_take_range(r, RT_R(0.0), RT_R(1.0));
+    out[11] = time;
 }
+
 /* The pair walk (rt_walk_pair.h) on the CPU, ray by ray, against the one-entry-per-step walk.  `rays[n][8]` = origin, direction, time, unused.
  * Each ray is walked as ONE lane would be by rt_render_ss_body / rt_render_plain_body -- the root's box, then box work and leaf work,
  * the NaN hand-overs (a NaN shutter fraction; a closest hit that turns NaN) -- under a RANDOM schedule (seeded): whether the lane does

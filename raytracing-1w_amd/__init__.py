@@ -466,12 +466,12 @@ class Context:
         return out, _stats_dict(st)
 
     def render_rows(self, width, height, spp, strip_rows=0, u8=False, progress=None, max_depth=50, tile=None,
-                    sample_offset=0, global_seed=0, chunk=0, out_sum=False, out=None, no_node_cache=False, partial_mib=0):
+                    sample_offset=0, global_seed=0, chunk=0, out_sum=False, out=None, no_node_cache=False, partial_mib=0, f32=False, generic=False):
         """Strip-wise render from the top row down with D2H overlapped (rt1w_render_rows).  `progress(rows_done, rows_total)`
         is called as strips land; returning a true value cancels (raises Rt1wError with code ERR_CANCELLED).
         Returns the same arrays as render() (u8=False) or render_u8() (u8=True)."""
         p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, no_node_cache=no_node_cache,
-                         partial_mib=partial_mib)
+                         partial_mib=partial_mib, f32=f32, generic=generic)
         if out is None:
             out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.uint8 if u8 else np.float64)
         assert out.flags.c_contiguous and out.shape == (p.tile_h, p.tile_w, 3) and out.dtype == (np.uint8 if u8 else np.float64)
@@ -666,6 +666,39 @@ def denoise_host(frame, aov, **kw):
     rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), out.ctypes.data_as(_P))
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_denoise_host")
+    return out
+
+
+class f32_exact:
+    """Diagnostics (librt1w_lab.so: rt1w_lab_f32_exact), a context manager: inside it every f32 render of the process runs the f32
+    kernels built with 64-bit elementary functions instead of the product's -- the build that equals the CPU twin of the f32 core
+    (oracle/oracle_flat_f32.cpp) bit for bit.  Same plan, launch, resolve and stats as any f32 render; generic kernels only."""
+
+    def __enter__(self):
+        self._was = load_lab().rt1w_lab_f32_exact(1)
+        return self
+
+    def __exit__(self, *exc):
+        load_lab().rt1w_lab_f32_exact(self._was)
+        return False
+
+
+F32_ELEMENTARY = ("sin", "cos", "atan2", "acos", "log")
+
+
+def f32_elementary(name, x, y=None, device=0):
+    """Diagnostics (librt1w_lab.so: rt1w_lab_f32_elementary): the device's single-precision function `name` of F32_ELEMENTARY over
+    float32 arrays, as the product's f32 kernels call it (atan2: of (x, y) = atan2f(x, y))."""
+    fn = load_lab().rt1w_lab_f32_elementary
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.c_int, _P, _P, C.c_uint64, _P]
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y if y is not None else np.zeros_like(x), dtype=np.float32)
+    assert x.shape == y.shape and x.ndim == 1 and x.size > 0
+    out = np.empty_like(x)
+    rc = fn(device, F32_ELEMENTARY.index(name), x.ctypes.data_as(_P), y.ctypes.data_as(_P), x.size, out.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_f32_elementary")
     return out
 
 

@@ -97,6 +97,7 @@ struct rt1w_context {
     /* host copies of the flat arrays the two opt-in modes convert on first use (a scene may be destroyed before its contexts) */
     std::vector<RtNode> h_nodes, h_lights; std::vector<RtMaterial> h_materials; std::vector<RtTexture> h_textures; std::vector<RtPerlin> h_perlin;
     RtKernel k32[RT_N_VARIANTS][3] = {}; /* f32 kernels by variant and rt1w_internal_f32_kernel mode: plain, reordering, pair walk */
+    RtKernel k32x[RT_N_VARIANTS][3] = {}; /* the same slots for the kernels a registered rt1w_f32_kernel_fn hands out (rt1w_internal.h) */
     RtJitSlot jit{"specialised kernel", false, true, true, false};
     RtJitSlot jit32{"f32 specialised kernel", true, false, false, true}; /* loaded only where `jit` is */
 };

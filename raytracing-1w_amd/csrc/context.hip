@@ -268,6 +268,16 @@ uint32_t default_chunk(const rt1w_context* c, const rt1w_render_params* p) {
 
 int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::JitInfo& info);
 
+/* the f32 kernel of (variant, mode): the product's own (context_f32.hip), unless librt1w_lab.so has registered a function that hands
+ * out another build of the same kernel (rt1w_internal.h: rt1w_f32_kernel_fn; f32_exact.hip).  While that function answers, the
+ * scene-specialised f32 kernel stands back too (mode 1 exists for every variant: the plan asks with it) */
+static rt1w_f32_kernel_fn g_f32_kernel_of = nullptr;
+const void* f32_kernel_of(int variant, int mode, bool& own) {
+    const void* fn = g_f32_kernel_of ? g_f32_kernel_of(variant, mode) : nullptr;
+    own = fn == nullptr;
+    return own ? rt1w_internal_f32_kernel(variant, mode) : fn;
+}
+
 /* what the launch will need, without launching: frame, variant, kernel */
 int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
     RtFrame& f = L.f = frame_of(p);
@@ -283,11 +293,13 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
     if (p->precision == RT1W_PRECISION_F32) {
         if (fl & (RT1W_RNG_REFERENCE | RT1W_WAVEFRONT | RT1W_LDS_NODES)) { rt1w::set_error("RT1W_PRECISION_F32 has the default kernels only"); return RT1W_ERR_INVALID; }
         if ((rc = ensure_f32_scene(c)) < 0) return rc;
+        bool own = true;
         L.variant = c->variant == 4 ? 3 : c->variant; /* the order-aware variant exists in f64 only */
         if ((rc = forced_variant(c, fl, false, &L.variant)) < 0) return rc;
+        (void)f32_kernel_of(L.variant, 1, own); /* own: the product's kernels serve, the scene-specialised one among them */
         /* a context that runs a scene-specialised kernel in f64 uses the f32 build of that kernel too -- from the kernel
          * caches only: renders never compile (rt1w_context_specialise does, for both precisions) */
-        if (!(fl & (RT1W_GENERIC | RT1W_UNSORTED)) && !forced && c->jit.k.jit && load_specialised(c, c->jit32, false, info) == RT1W_OK) {
+        if (!(fl & (RT1W_GENERIC | RT1W_UNSORTED)) && !forced && c->jit.k.jit && own && load_specialised(c, c->jit32, false, info) == RT1W_OK) {
             L.k = c->jit32.k;
             return RT1W_OK;
         }
@@ -297,8 +309,10 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
         const int mode = (fl & RT1W_UNSORTED) ? 0
                        : (v == 5 && !(fl & RT1W_CLASSIC_WALK) && rt1w_internal_f32_pw(c->f32_scene, (unsigned)RT_PW_SS_STACK) == 1) ? 2 : 1;
         const uint32_t bits = RT_BIT_F32 | (mode == 2 ? RT_BIT_PW | RT_BIT_SS : mode == 1 ? (v >= 2 ? RT_BIT_SS : RT_BIT_SORTED) : 0u);
-        if ((rc = first_use(c, c->k32[v][mode], RtKernel{mode ? RT_SORT_BLOCK : RT_BLOCK, bits, rt1w_internal_f32_kernel(v, mode), nullptr, true, mode == 2})) < 0) return rc;
-        L.k = c->k32[v][mode];
+        const void* fn = f32_kernel_of(v, mode, own);
+        RtKernel& slot = own ? c->k32[v][mode] : c->k32x[v][mode];
+        if ((rc = first_use(c, slot, RtKernel{mode ? RT_SORT_BLOCK : RT_BLOCK, bits, fn, nullptr, true, mode == 2})) < 0) return rc;
+        L.k = slot;
         return RT1W_OK;
     }
     if (fl & RT1W_RNG_REFERENCE) {
@@ -863,6 +877,7 @@ int rt1w_host_unregister(void* p) { if (p && !hip_ok(hipHostUnregister(p), "hipH
 
 /* for walk_lab.hip (diagnostics): the scene view the kernels get, and the device */
 void rt1w_internal_register_wavefront(rt1w_wf_render_fn render, rt1w_wf_destroy_fn destroy) { g_wf_render = render; g_wf_destroy = destroy; }
+void rt1w_internal_register_f32_kernels(rt1w_f32_kernel_fn kernel_of) { g_f32_kernel_of = kernel_of; }
 const void* rt1w_internal_view(const rt1w_context* c) { return &c->view; }
 int rt1w_internal_device(const rt1w_context* c) { return c->device; }
 

@@ -1,5 +1,6 @@
-/* rt1w_internal.h -- the four hooks librt1w.so exports beside include/rt1w.h, for its own diagnostics library librt1w_lab.so
- * (walk_lab.hip: the trace-only harness; wavefront.hip: the wavefront form behind RT1W_WAVEFRONT).  Not an interface for anybody else. */
+/* rt1w_internal.h -- the five hooks librt1w.so exports beside include/rt1w.h, for its own diagnostics library librt1w_lab.so
+ * (walk_lab.hip: the trace-only harness; wavefront.hip: the wavefront form behind RT1W_WAVEFRONT; f32_exact.hip: the f32 kernels built
+ * with 64-bit elementary functions, the device side of the f32 CPU twin).  Not an interface for anybody else. */
 #ifndef RT1W_INTERNAL_H
 #define RT1W_INTERNAL_H
 #include "rt1w.h"
@@ -23,8 +24,12 @@ typedef struct rt1w_wf_call {
 } rt1w_wf_call;
 typedef int (*rt1w_wf_render_fn)(rt1w_wf_call*);
 typedef void (*rt1w_wf_destroy_fn)(void* state);
+/* stands in for rt1w_internal_f32_kernel (context_f32.hip) in the plan of an RT1W_PRECISION_F32 render: the host handle of the kernel of
+ * (variant, mode) with the same arguments, workgroup size and launch bounds, or nullptr: the product's own kernel runs */
+typedef const void* (*rt1w_f32_kernel_fn)(int variant, int mode);
 #pragma GCC visibility push(default)
 void rt1w_internal_register_wavefront(rt1w_wf_render_fn render, rt1w_wf_destroy_fn destroy); /* called by librt1w_lab.so when it is loaded */
+void rt1w_internal_register_f32_kernels(rt1w_f32_kernel_fn kernel_of);                        /* likewise (f32_exact.hip) */
 const void* rt1w_internal_view(const rt1w_context* c); /* the context's RtSceneView (device pointers) */
 int rt1w_internal_device(const rt1w_context* c);
 void rt1w_internal_set_error(const char* msg);         /* what rt1w_last_error() will return on this thread */

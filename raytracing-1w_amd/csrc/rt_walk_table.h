@@ -70,7 +70,7 @@ inline bool rt_walk_table_build(const std::vector<RtNode>& N, uint32_t root, con
     struct Less { bool operator()(const Item& a, const Item& b) const { return a.p < b.p || (a.p == b.p && a.seq > b.seq); } };
     std::priority_queue<Item, std::vector<Item>, Less> heap;
     uint32_t seq = 0;
-    heap.push({RT_INF, seq++, root});
+    heap.push({RT_R(RT_INF), seq++, root});
     while (!heap.empty() && next_id < RT_WT_CACHE_MAX) {
         const Item it = heap.top(); heap.pop();
         if (it.node >= n || T.id_of[it.node] != RT_NONE) { why = "a node is reached twice"; return false; }

@@ -44,6 +44,13 @@ int rt1w_lab_aov_deep_host(const rt1w_scene* s, const rt1w_render_params* p, uin
  * RT1W_OK, or RT1W_ERR_INVALID as the device entry (null pointers, zero sizes, iterations > 8, unknown flags, bad sigmas) */
 int rt1w_lab_denoise_host(const rt1w_denoise_params* p, const double* frame, const double* aov, double* out);
 
+/* f32_exact.hip.  rt1w_lab_f32_exact: on != 0 makes every RT1W_PRECISION_F32 render of the process run the f32 kernels built with 64-bit
+ * elementary functions (generic kernels only; the build the CPU twin oracle/oracle_flat_f32.cpp equals bit for bit) instead of the
+ * product's; returns the previous setting.  rt1w_lab_f32_elementary: out[i] = the device's single-precision fn of (x[i], y[i]) as the
+ * product's f32 kernels call it -- fn 0 sinf(x), 1 cosf(x), 2 atan2f(x, y), 3 acosf(x), 4 logf(x) */
+int rt1w_lab_f32_exact(int on);
+int rt1w_lab_f32_elementary(int device, int fn, const float* x, const float* y, uint64_t n, float* out);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

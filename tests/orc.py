@@ -13,7 +13,8 @@ _P = C.c_void_p
 
 
 def _build():
-    need = [os.path.join(ORACLE_DIR, n) for n in ("liborc_rt1w.so", "liborc_flat.so", "liborc_ref.so", "liborc_flat_ref.so")]
+    need = [os.path.join(ORACLE_DIR, n) for n in ("liborc_rt1w.so", "liborc_flat.so", "liborc_ref.so", "liborc_flat_ref.so", "liborc_f32.so",
+                                                 "liborc_flat_f32.so")]
     if not all(os.path.exists(p) for p in need):
         subprocess.check_call(["make", "-C", ORACLE_DIR, "-s"])
 
@@ -173,6 +174,74 @@ def flat_ref_lib():
     lib = declare_flat(C.CDLL(os.path.join(ORACLE_DIR, "liborc_flat_ref.so")))
     assert lib.orcflat_is_refstream() == 1
     return lib
+
+
+_F32_ARRAYS = [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]
+
+
+def flat_f32_lib(name="liborc_flat_f32.so"):
+    """CPU twin of the single-precision kernels: the kernel core built for the host with `double` = `float` over the records of the
+    product's own f64 -> f32 conversion (oracle/oracle_flat_f32.cpp, csrc/rt_f32_scene.h)."""
+    lib = C.CDLL(os.path.join(ORACLE_DIR, name))
+    lib.orcflat_f32_render.restype = C.c_int
+    lib.orcflat_f32_render.argtypes = _F32_ARRAYS + [_P, _P, C.POINTER(Frame), C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, _P,
+                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    lib.orcflat_f32_records.restype = C.c_uint64
+    lib.orcflat_f32_records.argtypes = _F32_ARRAYS + [_P, C.c_int, _P, C.c_uint64]
+    lib.orcflat_f32_sizeof.restype = C.c_uint32
+    lib.orcflat_f32_elementary.argtypes = [C.c_int, _P, _P, C.c_uint64, _P]
+    return lib
+
+
+_F32 = None
+PW_SS_STACK = 12   # rt_kernel_plain.h: RT_PW_SS_STACK, the stack entries per lane of the f32 pair-walk kernel
+
+
+def _f32_array_args(scene):
+    arrs = [scene.flat(i) for i in range(7)]
+    arrs[0] = np.concatenate([arrs[0], np.zeros(96, dtype=np.uint8)])
+    info = scene.info()
+    ptr = [a.ctypes.data_as(_P) for a in arrs]
+    n_perlin = arrs[4].size // B.orcflat_sizeof(3)
+    return arrs, info, ptr, [ptr[0], info["n_nodes"], ptr[1], info["n_lights"], ptr[2], info["n_materials"], ptr[3], info["n_textures"], ptr[4], n_perlin]
+
+
+def flat_f32_render(scene, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, chunk=0, out_sum=False,
+                    threads=None, variant=None, pair_walk=False, lib=None, strips=None):
+    """flat_render through the f32 twin.  variant: default = the one the library picks for f32 renders (the order-aware V4 exists in
+    f64 only: 3 serves).  pair_walk: the pair-walk form of variant 5, with the f32 kernel's stack entries per lane."""
+    global _F32
+    if lib is None:
+        lib = _F32 = _F32 or flat_f32_lib()
+    x0, y0, tw, th = tile if tile is not None else (0, 0, width, height)
+    arrs, info, ptr, head = _f32_array_args(scene)
+    if variant is None:
+        variant = 3 if info["variant"] == 4 else info["variant"]
+    if chunk == 0:
+        chunk = scene.default_chunk(tw, th, spp)
+    f = Frame(width, height, x0, y0, tw, th, spp, sample_offset, max_depth, global_seed, chunk, 0, *(strips or (0, 0)))
+    out = np.empty((th, tw, 3), dtype=np.float64)
+    seg = C.c_uint64()
+    mx = C.c_uint32()
+    threads = threads or min(16, os.cpu_count() or 1)
+    rc = lib.orcflat_f32_render(*head, ptr[5], ptr[6], C.byref(f), variant, 1 if pair_walk else 0, PW_SS_STACK, 1 if out_sum else 0,
+                                threads, out.ctypes.data_as(_P), C.byref(seg), C.byref(mx))
+    assert rc == 0, {-2: "f32 flat core reported a traversal stack overflow", -3: "the f32 pair walk left its stack or queue",
+                     -4: "the scene has no f32 pair-walk records that fit the kernel's stack"}.get(rc, rc)
+    return out, {"segments": seg.value, "paths": tw * th * spp, "max_stack": mx.value}
+
+
+def flat_f32_records(scene, what, lib=None):
+    """Bytes of the converted f32 records (orcflat_f32_records: 0 nodes, 1 lights, 2 materials, 3 textures, 4 perlin, 5 camera + background,
+    6 pair-walk inner records, 7 pair-walk groups, 8 pair-walk root box)."""
+    global _F32
+    if lib is None:
+        lib = _F32 = _F32 or flat_f32_lib()
+    arrs, info, ptr, head = _f32_array_args(scene)
+    n = lib.orcflat_f32_records(*head, ptr[6], what, None, 0)
+    buf = np.zeros(max(int(n), 1), dtype=np.uint8)
+    lib.orcflat_f32_records(*head, ptr[6], what, buf.ctypes.data_as(_P), int(n))
+    return buf[:int(n)]
 
 
 def declare_flat(lib):

@@ -33,7 +33,7 @@ def test_library_exports_nothing_else(rt):
     import subprocess
     out = subprocess.check_output(["nm", "-D", "--defined-only", rt.LIB_PATH]).decode()
     exported = sorted({line.split()[-1] for line in out.splitlines() if line.strip()})
-    internal = ["rt1w_internal_device", "rt1w_internal_register_wavefront", "rt1w_internal_set_error", "rt1w_internal_view"]
+    internal = ["rt1w_internal_device", "rt1w_internal_register_f32_kernels", "rt1w_internal_register_wavefront", "rt1w_internal_set_error", "rt1w_internal_view"]
     assert exported == sorted(set(declared_functions()) | set(internal)), sorted(set(exported) ^ (set(declared_functions()) | set(internal)))
     lab = os.path.join(os.path.dirname(rt.LIB_PATH), "librt1w_lab.so")
     lab_syms = subprocess.check_output(["nm", "-D", "--defined-only", lab]).decode()

@@ -6,7 +6,8 @@ change by a bit.  rt1w_stats.passes reports how many launches ran; every render 
 restatement of chunks_per_pass (csrc/context.hip).
 
 Expected sides: the CPU build of the kernel core (orc.flat_render) with the same chunking for the f64 Philox kernels; the same kernel's
-one-pass frame for the f32 kernels, which have no CPU twin; the reference-stream CPU core for the reference stream.
+one-pass frame for the f32 kernels (their CPU twin, orc.flat_f32_render, is compared with the exact build of the same kernels in
+test_f32_twin.py: the product's own f32 frame differs from it in five elementary functions); the reference-stream CPU core for the reference stream.
 """
 import ctypes as C
 import json

@@ -27,6 +27,15 @@ SCRIPT = textwrap.dedent("""
             img, st = orc.flat_render(sc, W, H, spp, variant=v, threads=1)
             ref = img if ref is None else ref
             assert np.array_equal(img, ref, equal_nan=True)
+    # the single-precision build of the core over the converted records (oracle_flat_f32.cpp): an arm with media, and arm 0 through the pair walk
+    f32 = orc.flat_f32_lib('liborc_flat_f32_asan.so')
+    a7, s7 = orc.flat_f32_render(rt.Scene.reference(7, build_seed=1), 16, 16, 4, threads=1, lib=f32)
+    b7, t7 = orc.flat_f32_render(rt.Scene.reference(7, build_seed=1), 16, 16, 4, threads=1, lib=f32, variant=1)
+    assert s7['segments'] == t7['segments'] and np.array_equal(a7, b7, equal_nan=True)
+    sc0 = rt.Scene.reference(0, build_seed=1, aspect_ratio=1.5)
+    a0, s0 = orc.flat_f32_render(sc0, 24, 16, 2, threads=1, lib=f32)
+    b0, t0 = orc.flat_f32_render(sc0, 24, 16, 2, threads=1, lib=f32, pair_walk=True)
+    assert s0['segments'] == t0['segments'] and np.array_equal(a0, b0, equal_nan=True)
     # the pair walk's lane functions (rt_walk_pair.h) with their bound-checked host arrays, finite and non-finite rays
     import test_pair_walk_host as pw
     rng = np.random.default_rng(3)
@@ -49,7 +58,7 @@ SCRIPT = textwrap.dedent("""
 
 def test_kernel_core_under_asan_ubsan(rt):
     so = os.path.join(orc.ORACLE_DIR, "liborc_flat_asan.so")
-    subprocess.check_call(["make", "-C", orc.ORACLE_DIR, "-s", "liborc_flat_asan.so"])
+    subprocess.check_call(["make", "-C", orc.ORACLE_DIR, "-s", "liborc_flat_asan.so", "liborc_flat_f32_asan.so"])
     assert os.path.exists(so)
     asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"]).decode().strip()
     env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
