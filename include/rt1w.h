@@ -415,6 +415,57 @@ int rt1w_render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1
 int rt1w_render_denoised_deep(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, uint32_t max_specular, double max_fuzz,
                               double* out_rgb, rt1w_stats* stats);
 
+/* ---- variance-guided denoiser: the filter above with a colour term that follows the frame's own noise ----
+ * rt1w_denoise's colour falloff has a fixed width (sigma_colour), so it blurs a converged frame as hard as a noisy one and its error has a
+ * floor that more samples do not lower.  Here the width is each pixel's estimated variance (Schied et al. 2017, SVGF; the estimate from
+ * sample batches as Rousselle et al. 2012 take theirs from two half buffers): the filter fades out as the frame converges.  Like
+ * rt1w_denoise it replaces nothing of the reference, which has sample count alone (src/main.rs:939).
+ *
+ * Batch variance.  sums double[K][h][w][3]: the raw sums S_0 .. S_(K-1) of K disjoint batches of n samples each, as K renders with
+ *   RT1W_OUT_SUM, spp = n and sample_offset = k n return them.  aov double[h][w][8].  flags 0 or RT1W_DENOISE_KEEP_ALBEDO.  Per pixel:
+ *     frame = Color::into_sampled (color.rs:14-21, rt1w_resolve) of ((S_0 + S_1) + ...) with spp = K n: NaN of the sum to 0, times 1 / (K n).
+ *             This is the sum of the BATCH sums: not bit-equal to rt1w_render of K n samples in general, which adds its chunks in another
+ *             association (equal where every batch is one chunk and the render's chunk is n);
+ *     A     = the albedo floor of rt1w_denoise's prepare pass (max(albedo, 0.01), 0.01 where not finite; 1 with KEEP_ALBEDO);
+ *     l_k   = luminance of (S_k * (1 / n)) / A per channel, (0.2126 r + 0.7152 g) + 0.0722 b;
+ *     lbar  = (((0 + l_0) + l_1) + ...) / K;     var = (((0 + (l_0 - lbar)^2) + (l_1 - lbar)^2) + ...) / (K (K - 1)):
+ *             the variance of the mean demodulated luminance.  Where that is negative or not finite (a NaN or inf sample) var = 0: no
+ *             usable estimate, and the filter's handling of values that are not finite covers the pixel.
+ *   K = 2 .. 16, n >= 1, K n <= 2^32 - 1, width / height as rt1w_denoise: RT1W_ERR_INVALID otherwise.  One lane per pixel, bit-identical
+ *   to the CPU build (librt1w_lab.so: rt1w_lab_batch_variance_host).
+ * Filter.  rt1w_denoise with a variance buffer var double[h][w] and `sigma_variance` (0 = the default 3; negative or not finite:
+ *   RT1W_ERR_INVALID); p->sigma_colour is ignored.  The prepare pass takes v_p = var, 0 where var is negative or not finite.  Every
+ *   definition of rt1w_denoise holds but for these:
+ *     x_colour   = 0 where l_p == l_q; else (l_p - l_q)^2 / (sigma_variance^2 * (v_p + v_q)) of the current level's values.  A zero
+ *                  denominator gives +inf, so weight 0: a converged pixel (v = 0 all around) keeps its value.  The term applies on EVERY
+ *                  level, level 0 included, and sigma_variance is not halved: the variance itself shrinks from level to level.  A
+ *                  firefly has a large variance of its own and so accepts its neighbours, which replaces the level-0 exemption;
+ *     variance   v'_p = sum_q w(p, q)^2 v_q / (sum_q w(p, q))^2 over the taps that the colour takes, in the same order;
+ *   the variance is not prefiltered in space.  Bit-identical to the CPU build (librt1w_lab.so: rt1w_lab_denoise_var_host).
+ * Buffers of the host forms: two colour buffers of 40 B per pixel, the guide buffer of 64 B per pixel and a buffer for the batch sums,
+ * owned by the context, grown on demand, freed with it.  stats as rt1w_denoise. */
+int rt1w_batch_variance(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batches, uint32_t batch_spp, uint32_t flags, const double* sums,
+                        const double* aov, double* frame, double* var, rt1w_stats* stats);
+/* same on device memory of the context's GPU; the four buffers are distinct.  Synchronises the context's stream before returning. */
+int rt1w_batch_variance_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batches, uint32_t batch_spp, uint32_t flags, const void* d_sums,
+                               const void* d_aov, void* d_frame, void* d_var, rt1w_stats* stats);
+/* `out` may be `frame` */
+int rt1w_denoise_var(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, double sigma_variance,
+                     double* out, rt1w_stats* stats);
+/* same on device memory of the context's GPU; d_out may equal d_frame.  Synchronises the context's stream before returning. */
+int rt1w_denoise_var_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, const void* d_var,
+                            double sigma_variance, void* d_out, rt1w_stats* stats);
+/* One call.  K = `batches` (0 = 4; p->spp must be a multiple of K, n = spp / K): K rt1w_render_device calls with RT1W_OUT_SUM, spp = n,
+ * sample_offset = p->sample_offset + k n and p->chunk (0: every batch gets the default of a render of n samples,
+ * rt1w_scene_default_chunk(scene, tile_w, tile_h, n)) into the context's batch buffer; rt1w_render_aov_deep_device over all K n samples
+ * (max_specular = 0: the first-hit buffers); rt1w_batch_variance_device; rt1w_denoise_var_device; one device->host copy into
+ * out_rgb[tile_h][tile_w][3].  Bit-identical to composing those public calls.  The frame that is filtered is the batch sum defined above,
+ * NOT in general the bits of rt1w_render at K n samples.  Refuses what rt1w_render_denoised_deep refuses, a K outside 2 .. 16 or that does
+ * not divide spp, and sigma_variance as rt1w_denoise_var does.  stats: the renders' sums (paths, segments, passes), all kernel times added
+ * in kernel_ms; total_ms the whole call; grid / block the level kernel's; chunk / n_chunks of one batch. */
+int rt1w_render_denoised_var(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, uint32_t batches, double sigma_variance,
+                             uint32_t max_specular, double max_fuzz, double* out_rgb, rt1w_stats* stats);
+
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory
  * mapping that several single-GPU processes fill with RT1W_OUT_FRAME. */

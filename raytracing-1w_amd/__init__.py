@@ -170,6 +170,12 @@ _sig("rt1w_denoise", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.POINTE
 _sig("rt1w_denoise_device", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.POINTER(Stats))
 _sig("rt1w_render_denoised", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(DenoiseParams), _P, C.POINTER(Stats))
 _sig("rt1w_render_denoised_deep", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(DenoiseParams), C.c_uint32, C.c_double, _P, C.POINTER(Stats))
+_sig("rt1w_batch_variance", C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_batch_variance_device", C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_denoise_var", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.c_double, _P, C.POINTER(Stats))
+_sig("rt1w_denoise_var_device", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.c_double, _P, C.POINTER(Stats))
+_sig("rt1w_render_denoised_var", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(DenoiseParams), C.c_uint32, C.c_double, C.c_uint32, C.c_double, _P,
+     C.POINTER(Stats))
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -212,6 +218,20 @@ def _frame_and_aov(frame, aov):
     if f.ndim != 3 or f.shape[2] != 3 or a.shape != f.shape[:2] + (AOV_CHANNELS,):
         raise ValueError("frame must be [h, w, 3] and aov [h, w, 8]")
     return f, a
+
+
+def _sums_and_aov(sums, aov):
+    s, a = (np.ascontiguousarray(x, dtype=np.float64) for x in (sums, aov))
+    if s.ndim != 4 or s.shape[3] != 3 or a.shape != s.shape[1:3] + (AOV_CHANNELS,):
+        raise ValueError("sums must be [batches, h, w, 3] and aov [h, w, 8]")
+    return s, a
+
+
+def _variance_of(var, frame):
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if v.shape != frame.shape[:2]:
+        raise ValueError("var must be [h, w]")
+    return v
 
 
 def _v3(v):
@@ -565,6 +585,60 @@ class Context:
         """render_denoised with the deep feature buffers (rt1w_render_denoised_deep) in place of the first-hit ones."""
         return self._render_denoised((max_specular, max_fuzz), width, height, spp, max_depth, tile, sample_offset, global_seed, denoise, flags, strips, precision, with_stats, kw)
 
+    def batch_variance(self, sums, aov, batch_spp, keep_albedo=False, with_stats=False):
+        """Frame and variance from K sample batches (rt1w_batch_variance): `sums` float64 [K, h, w, 3], the raw sums of K renders with
+        out_sum=True, spp=batch_spp and sample_offset = k * batch_spp; `aov` [h, w, 8].  Returns (frame [h, w, 3], var [h, w]): the mean
+        over all K * batch_spp samples and the variance of the mean demodulated luminance."""
+        s, a = _sums_and_aov(sums, aov)
+        frame = np.empty(s.shape[1:], dtype=np.float64)
+        var = np.empty(s.shape[1:3], dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_batch_variance(self._h, s.shape[2], s.shape[1], s.shape[0], batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0,
+                                     s.ctypes.data_as(_P), a.ctypes.data_as(_P), frame.ctypes.data_as(_P), var.ctypes.data_as(_P), C.byref(st)))
+        return (frame, var, _stats_dict(st)) if with_stats else (frame, var)
+
+    def batch_variance_device(self, d_sums, d_aov, d_frame, d_var, width, height, batches, batch_spp, keep_albedo=False):
+        """Same on device memory (int addresses of batches * height * width * 3, height * width * 8 / 3 / 1 float64).  Returns the stats dict."""
+        st = Stats()
+        _ck(_lib.rt1w_batch_variance_device(self._h, width, height, batches, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0,
+                                            C.c_void_p(d_sums), C.c_void_p(d_aov), C.c_void_p(d_frame), C.c_void_p(d_var), C.byref(st)))
+        return _stats_dict(st)
+
+    def denoise_var(self, frame, aov, var, sigma_variance=0.0, with_stats=False, **kw):
+        """Variance-guided filter (rt1w_denoise_var) of a float64 frame [h, w, 3] with its feature buffers [h, w, 8] and the variance
+        [h, w] of batch_variance: the denoised [h, w, 3].  kw: iterations, keep_albedo, sigma_normal, sigma_depth (0 = default)."""
+        f, a = _frame_and_aov(frame, aov)
+        v = _variance_of(var, f)
+        p = _denoise_params(f.shape[1], f.shape[0], **kw)
+        out = np.empty_like(f)
+        st = Stats()
+        _ck(_lib.rt1w_denoise_var(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), sigma_variance,
+                                  out.ctypes.data_as(_P), C.byref(st)))
+        return (out, _stats_dict(st)) if with_stats else out
+
+    def denoise_var_device(self, d_frame, d_aov, d_var, d_out, width, height, sigma_variance=0.0, **kw):
+        """Same on device memory (int addresses of height * width * 3 / 8 / 1 / 3 float64); d_out may equal d_frame.  Returns the stats dict."""
+        p = _denoise_params(width, height, **kw)
+        st = Stats()
+        _ck(_lib.rt1w_denoise_var_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_var), sigma_variance,
+                                         C.c_void_p(d_out), C.byref(st)))
+        return _stats_dict(st)
+
+    def render_denoised_var(self, width, height, spp, batches=0, sigma_variance=0.0, max_specular=0, max_fuzz=0.0, max_depth=50, tile=None,
+                            sample_offset=0, global_seed=0, chunk=0, denoise=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
+        """Batches, feature buffers, batch variance and the variance-guided filter in one call (rt1w_render_denoised_var): float64
+        [tile_h, tile_w, 3].  `spp` must be a multiple of `batches` (0 = 4); max_specular > 0 takes the deep feature buffers; other
+        arguments as render_denoised."""
+        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, False, kw.pop("variant", None), strips=strips, **kw)
+        p.flags |= flags
+        p.precision = precision
+        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
+        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_denoised_var(self._h, C.byref(p), C.byref(d) if d is not None else None, batches, sigma_variance, max_specular, max_fuzz,
+                                          out.ctypes.data_as(_P), C.byref(st)))
+        return (out, _stats_dict(st)) if with_stats else out
+
     def debug_aabb(self, cases):
         """cases[n, 14] = min3, max3, origin3, direction3, t_min, t_max -> (literal[n], fast[n]) from the device."""
         a = np.ascontiguousarray(cases, dtype=np.float64).reshape(-1, 14)
@@ -666,6 +740,37 @@ def denoise_host(frame, aov, **kw):
     rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), out.ctypes.data_as(_P))
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_denoise_host")
+    return out
+
+
+def batch_variance_host(sums, aov, batch_spp, keep_albedo=False):
+    """CPU twin of Context.batch_variance (librt1w_lab.so: rt1w_lab_batch_variance_host, rt_denoise_var.h built for the host): the
+    (frame, var) the GPU must equal bit for bit.  No GPU needed."""
+    fn = load_lab().rt1w_lab_batch_variance_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P]
+    s, a = _sums_and_aov(sums, aov)
+    frame = np.empty(s.shape[1:], dtype=np.float64)
+    var = np.empty(s.shape[1:3], dtype=np.float64)
+    rc = fn(s.shape[2], s.shape[1], s.shape[0], batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, s.ctypes.data_as(_P), a.ctypes.data_as(_P),
+            frame.ctypes.data_as(_P), var.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_batch_variance_host")
+    return frame, var
+
+
+def denoise_var_host(frame, aov, var, sigma_variance=0.0, **kw):
+    """CPU twin of Context.denoise_var (librt1w_lab.so: rt1w_lab_denoise_var_host): the array the GPU must equal bit for bit."""
+    fn = load_lab().rt1w_lab_denoise_var_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(DenoiseParams), _P, _P, _P, C.c_double, _P]
+    f, a = _frame_and_aov(frame, aov)
+    v = _variance_of(var, f)
+    p = _denoise_params(f.shape[1], f.shape[0], **kw)
+    out = np.empty_like(f)
+    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), sigma_variance, out.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_denoise_var_host")
     return out
 
 

@@ -5,10 +5,12 @@
  * values as defaults.
  *   rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B]
  *        [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic]
- *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]]]
+ *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
  * --denoise renders through rt1w_render_denoised: the frame, its first-hit feature buffers and the feature-guided filter in one call
  * (default 5 levels), then the PPM of the filtered frame.  --deep-guides [N] (implies --denoise) takes the guides through glass and
  * perfect mirrors instead, up to N specular bounces (default 8, at most 64): rt1w_render_denoised_deep with max_fuzz 0.
+ * --variance [K] (implies --denoise) renders the samples as K batches (default 4; --spp must be a multiple of K) and filters with the
+ * variance-guided filter, which fades out as the frame converges: rt1w_render_denoised_var, with the guides --deep-guides asks for.
  * --reference-stream draws from the reference's own StdRng per pixel (RT1W_RNG_REFERENCE): `rt1w --reference-stream` prints
  * what `cargo run` of the reference prints, byte for byte (Cornell arm, 600x600, 100 spp).  --f32: RT1W_PRECISION_F32.
  * --near-far: rt1w_scene_set_walk_order(RT1W_WALK_NEAR_FAR).  --sah: rt1w_scene_set_bvh_build(RT1W_BVH_SAH).
@@ -31,7 +33,7 @@ static int fail(const char* what) {
 int main(int argc, char** argv) {
     int arm = 5, device = 0;
     bool specialise = false, generic = false, reference_stream = false, f32 = false, near_far = false, sah = false, denoise = false;
-    long denoise_iterations = 0, deep_guides = -1; /* -1: first-hit guides */
+    long denoise_iterations = 0, deep_guides = -1, variance = -1; /* -1: first-hit guides; -1: the fixed-sigma filter */
     long width = -1, height = -1, spp = -1, depth = 50; /* MAX_DEPTH main.rs:801 */
     unsigned long long build_seed = 1, seed = 0;
     std::string out_path, earth_path;
@@ -63,8 +65,12 @@ int main(int argc, char** argv) {
             denoise = true; deep_guides = 8;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') deep_guides = std::atol(argv[++i]);
         }
+        else if (a == "--variance") {
+            denoise = true; variance = 0;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') variance = std::atol(argv[++i]);
+        }
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -132,8 +138,9 @@ int main(int argc, char** argv) {
         std::memset(&d, 0, sizeof d);
         d.iterations = denoise_iterations > 0 ? (uint32_t)denoise_iterations : 0u;
         std::vector<double> means((size_t)width * height * 3);
-        if ((deep_guides >= 0 ? rt1w_render_denoised_deep(ctx, &p, &d, (uint32_t)deep_guides, 0.0, means.data(), &st)
-                              : rt1w_render_denoised(ctx, &p, &d, means.data(), &st)) < 0) return fail("render");
+        if ((variance >= 0 ? rt1w_render_denoised_var(ctx, &p, &d, (uint32_t)variance, 0.0, deep_guides >= 0 ? (uint32_t)deep_guides : 0u, 0.0, means.data(), &st)
+             : deep_guides >= 0 ? rt1w_render_denoised_deep(ctx, &p, &d, (uint32_t)deep_guides, 0.0, means.data(), &st)
+             : rt1w_render_denoised(ctx, &p, &d, means.data(), &st)) < 0) return fail("render");
         /* quantised as the reference prints it (color.rs:56-65), top row (j = height - 1) first (main.rs:957-960) */
         for (uint32_t r = 0; r < p.height; ++r)
             if (rt1w_quantize(means.data() + (size_t)(p.height - 1u - r) * p.width * 3, (uint64_t)p.width * 3, img.data() + (size_t)r * p.width * 3) < 0) return fail("quantize");

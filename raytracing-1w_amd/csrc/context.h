@@ -76,7 +76,8 @@ struct rt1w_context {
     void* d_textures = nullptr; void* d_perlin = nullptr; void* d_images = nullptr;
     RtSceneView view{};
     double* d_out = nullptr; size_t out_bytes = 0;
-    void* dn_buf[3] = {nullptr, nullptr, nullptr}; size_t dn_bytes[3] = {0, 0, 0}; /* rt1w_denoise: two colour buffers and the guide buffer */
+    void* dn_buf[3] = {nullptr, nullptr, nullptr}; size_t dn_bytes[3] = {0, 0, 0}; /* rt1w_denoise, rt1w_denoise_var: two colour buffers and the guide buffer */
+    double* d_batches = nullptr; size_t batches_bytes = 0; /* rt1w_batch_variance, rt1w_render_denoised_var: the sums of the sample batches */
     RtKernel k64[RT_N_WALKS][RT_N_VARIANTS] = {}; /* g_kernels, queried at creation; the node-cache walks only with a walk table */
     bool walk_table = false; uint32_t walk_table_first = 0;
     bool sphere_media = false; /* every medium of the scene is bounded by a bare Sphere: the sphere-media walks serve */

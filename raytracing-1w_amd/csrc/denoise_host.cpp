@@ -1,4 +1,4 @@
-/* denoise_host.cpp -- the CPU twin of the filter kernels (denoise.hip): rt_denoise.h compiled for the host (g++, -ffp-contract=off
+/* denoise_host.cpp -- the CPU twin of the filter kernels (denoise.hip, denoise_var.hip): rt_denoise.h and rt_denoise_var.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core).  Diagnostics library only (librt1w_lab.so): the expected side of the GPU tests' bit-equality checks
  * and what the CPU tier's property and quality tests run.  librt1w.so keeps no CPU path. */
 #include <cstring>
@@ -7,6 +7,7 @@
 
 #include "rt1w.h"
 #include "rt_denoise.h"
+#include "rt_denoise_var.h"
 #include "walk_lab.h"
 
 namespace {
@@ -51,5 +52,62 @@ extern "C" int rt1w_lab_denoise_host(const rt1w_denoise_params* p, const double*
         });
         RtDnCol* t = src; src = dst; dst = t;
     }
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_batch_variance_host(uint32_t width, uint32_t height, uint32_t batches, uint32_t batch_spp, uint32_t flags, const double* sums,
+                                            const double* aov, double* frame, double* var) {
+    if (!sums || !aov || !frame || !var) return RT1W_ERR_INVALID;
+    RtDnParams P;
+    if (!rt_dn_make_params(width, height, 0u, flags, 0.0, 0.0, 0.0, P) || !rt_dv_batches_ok(batches, batch_spp)) return RT1W_ERR_INVALID;
+    const unsigned long long stride = (unsigned long long)P.w * P.h * 3u;
+    for_rows(P.h, [&](uint32_t y) {
+        for (uint32_t x = 0; x < P.w; ++x) {
+            const size_t i = (size_t)y * P.w + x;
+            rt_dv_variance_pixel(batches, batch_spp, P.keep_albedo != 0u, sums + i * 3, stride, aov + i * 8, frame + i * 3, var + i);
+        }
+    });
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_denoise_var_host(const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, double sigma_variance,
+                                         double* out) {
+    if (!p || !frame || !aov || !var || !out) return RT1W_ERR_INVALID;
+    RtDnParams P;
+    double sv;
+    if (!rt_dn_make_params(p->width, p->height, p->iterations, p->flags, 0.0, p->sigma_normal, p->sigma_depth, P) || !rt_dv_sigma(sigma_variance, sv)) return RT1W_ERR_INVALID;
+    const double sv2 = sv * sv;
+    const size_t n = (size_t)P.w * P.h;
+    std::vector<RtDvCol> a(n), b(n);
+    std::vector<RtDnGuide> g(n);
+    for_rows(P.h, [&](uint32_t y) {
+        for (uint32_t x = 0; x < P.w; ++x) {
+            const size_t i = (size_t)y * P.w + x;
+            rt_dv_prepare_pixel(P, frame + i * 3, aov + i * 8, var[i], a[i], g[i]);
+        }
+    });
+    RtDvCol* src = a.data();
+    RtDvCol* dst = b.data();
+    for (uint32_t level = 0; level < P.levels; ++level) {
+        const RtDvGlobalSrc s{src, g.data(), P.w};
+        const bool last = level + 1u == P.levels;
+        for_rows(P.h, [&](uint32_t y) {
+            for (uint32_t x = 0; x < P.w; ++x) {
+                const size_t i = (size_t)y * P.w + x;
+                const RtDvCol c = rt_dv_level_pixel(P, sv2, s, x, y, level);
+                if (last) rt_dv_finish_pixel(c, g[i], out + i * 3);
+                else dst[i] = c;
+            }
+        });
+        RtDvCol* t = src; src = dst; dst = t;
+    }
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_denoised_var_split(uint32_t spp, uint32_t batches, double sigma_variance, uint32_t out[2]) {
+    double sv;
+    uint32_t k = 0u, n = 0u;
+    if (!rt_dv_sigma(sigma_variance, sv) || !rt_dv_split(spp, batches, k, n)) return RT1W_ERR_INVALID;
+    if (out) { out[0] = k; out[1] = n; }
     return RT1W_OK;
 }

@@ -1,12 +1,13 @@
 /* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_denoise*,
- * rt1w_render_denoised*): validation, buffers, launch, timing, copies.  Host code only, built without a device pass: the kernels belong to
- * aov.hip and denoise.hip and are launched through their host handles, the context and its render path to context.hip (context.h), so a
+ * rt1w_render_denoised*, rt1w_batch_variance*): validation, buffers, launch, timing, copies.  Host code only, built without a device pass: the
+ * kernels belong to aov.hip, denoise.hip and denoise_var.hip and are launched through their host handles, the context and its render path to context.hip (context.h), so a
  * change here rebuilds none of the code objects. */
 #include <cstdio>
 #include <cstring>
 
 #include "context.h"
 #include "rt_aov_deep.h" /* rt_aov_deep_args_ok only */
+#include "rt_denoise_var.h" /* rt_dv_batches_ok, rt_dv_sigma, rt_dv_split only */
 
 /* aov.hip: the first-hit feature buffers (rt1w_render_aov), by variant; workgroups of RT_BLOCK work-items that cover the frame's tile */
 extern "C" const void* rt1w_internal_aov_kernel(int variant);
@@ -18,6 +19,13 @@ extern "C" int rt1w_internal_denoise_launch(uint32_t w, uint32_t h, uint32_t ite
                                             double sigma_depth, const double* frame, const double* aov, double* out, void* col_a, void* col_b,
                                             void* guide, hipStream_t stream, unsigned launch[2]);
 extern "C" unsigned rt1w_internal_denoise_sizeof(int what); /* bytes per pixel of 0 a colour buffer, 1 the guide buffer */
+/* denoise_var.hip: the batch-variance pass and the variance-guided filter; returns as rt1w_internal_denoise_launch */
+extern "C" int rt1w_internal_batch_variance_launch(uint32_t w, uint32_t h, uint32_t batches, uint32_t batch_spp, uint32_t flags, const double* sums,
+                                                   const double* aov, double* frame, double* var, hipStream_t stream, unsigned launch[2]);
+extern "C" int rt1w_internal_denoise_var_launch(uint32_t w, uint32_t h, uint32_t iterations, uint32_t flags, double sigma_normal, double sigma_depth,
+                                                double sigma_variance, const double* frame, const double* aov, const double* var, double* out,
+                                                void* col_a, void* col_b, void* guide, hipStream_t stream, unsigned launch[2]);
+extern "C" unsigned rt1w_internal_denoise_var_sizeof(void); /* bytes per pixel of one of its colour buffers */
 
 using namespace rt1w;
 namespace {
@@ -119,10 +127,10 @@ int denoise_validate(const rt1w_context* c, const rt1w_denoise_params* p) {
         if (!(v >= 0.0) || v > 1.7976931348623157e308) { set_error("denoise: a sigma must be finite and >= 0 (0 = default)"); return RT1W_ERR_INVALID; }
     return RT1W_OK;
 }
-/* the context's two colour buffers and guide buffer, grown to the image */
-int denoise_reserve(rt1w_context* c, size_t npix) {
+/* the context's two colour buffers (col_bytes per pixel) and guide buffer, grown to the image */
+int denoise_reserve(rt1w_context* c, size_t npix, size_t col_bytes) {
     for (int k = 0; k < 3; ++k) {
-        const size_t bytes = npix * rt1w_internal_denoise_sizeof(k == 2 ? 1 : 0);
+        const size_t bytes = npix * (k == 2 ? rt1w_internal_denoise_sizeof(1) : col_bytes);
         if (bytes <= c->dn_bytes[k]) continue;
         if (c->dn_buf[k]) (void)hipFree(c->dn_buf[k]);
         c->dn_buf[k] = nullptr; c->dn_bytes[k] = 0;
@@ -133,7 +141,7 @@ int denoise_reserve(rt1w_context* c, size_t npix) {
 }
 /* prepare pass and levels on lane 0's stream, wait; *stats but for total_ms: their HIP-event time, grid / block of the level kernel */
 int denoise_common(rt1w_context* c, const rt1w_denoise_params* p, const double* d_frame, const double* d_aov, double* d_out, rt1w_stats* stats) {
-    int rc = denoise_reserve(c, (size_t)p->width * p->height);
+    int rc = denoise_reserve(c, (size_t)p->width * p->height, rt1w_internal_denoise_sizeof(0));
     if (rc < 0) return rc;
     RtLane& l = c->lane[0];
     unsigned launch[2] = {0u, 0u};
@@ -212,6 +220,174 @@ int render_denoised(rt1w_context* c, const rt1w_render_params* p, const rt1w_den
     return RT1W_OK;
 }
 
+/* ---- variance-guided denoiser (include/rt1w.h: rt1w_batch_variance, rt1w_denoise_var, rt1w_render_denoised_var) ---- */
+int batches_validate(uint32_t batches, uint32_t batch_spp) {
+    if (rt_dv_batches_ok(batches, batch_spp)) return RT1W_OK;
+    set_error("batch variance: 2 .. 16 batches of >= 1 samples each, at most 2^32 - 1 samples in all");
+    return RT1W_ERR_INVALID;
+}
+int sigma_variance_validate(double sigma_variance) {
+    double sv;
+    if (rt_dv_sigma(sigma_variance, sv)) return RT1W_OK;
+    set_error("denoise: sigma_variance must be finite and >= 0 (0 = default)");
+    return RT1W_ERR_INVALID;
+}
+/* the context's buffer of batch sums, grown to `bytes` */
+int batches_reserve(rt1w_context* c, size_t bytes) {
+    if (bytes <= c->batches_bytes) return RT1W_OK;
+    if (c->d_batches) (void)hipFree(c->d_batches);
+    c->d_batches = nullptr; c->batches_bytes = 0;
+    if (!hip_ok(hipMalloc((void**)&c->d_batches, bytes), "hipMalloc(batch sums)")) return RT1W_ERR_NOMEM;
+    c->batches_bytes = bytes;
+    return RT1W_OK;
+}
+/* the two passes on lane 0's stream, wait; *stats as denoise_common fills them */
+int lane_finish(rt1w_context* c, int rc, const unsigned launch[2], uint64_t npix, const char* what, rt1w_stats* stats) {
+    RtLane& l = c->lane[0];
+    if (rc == -2) { set_error(std::string(what) + ": parameters refused"); return RT1W_ERR_INVALID; }
+    if (rc != 0) { set_error(std::string(what) + " kernel launch failed"); return RT1W_ERR_DEVICE; }
+    (void)hipEventRecord(l.ev1, l.stream);
+    if (!hip_ok(hipStreamSynchronize(l.stream), what)) return RT1W_ERR_DEVICE;
+    memset(stats, 0, sizeof *stats);
+    stats->paths = npix; stats->kernel_ms = lane_ms(l);
+    stats->grid = launch[0]; stats->block = launch[1]; stats->passes = 1u;
+    return RT1W_OK;
+}
+int batch_variance_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batches, uint32_t batch_spp, uint32_t flags, const double* d_sums,
+                          const double* d_aov, double* d_frame, double* d_var, rt1w_stats* stats) {
+    RtLane& l = c->lane[0];
+    unsigned launch[2] = {0u, 0u};
+    (void)hipEventRecord(l.ev0, l.stream);
+    const int rc = rt1w_internal_batch_variance_launch(w, h, batches, batch_spp, flags, d_sums, d_aov, d_frame, d_var, l.stream, launch);
+    return lane_finish(c, rc, launch, (uint64_t)w * h, "batch variance", stats);
+}
+int denoise_var_common(rt1w_context* c, const rt1w_denoise_params* p, double sigma_variance, const double* d_frame, const double* d_aov,
+                       const double* d_var, double* d_out, rt1w_stats* stats) {
+    int rc = denoise_reserve(c, (size_t)p->width * p->height, rt1w_internal_denoise_var_sizeof());
+    if (rc < 0) return rc;
+    RtLane& l = c->lane[0];
+    unsigned launch[2] = {0u, 0u};
+    (void)hipEventRecord(l.ev0, l.stream);
+    rc = rt1w_internal_denoise_var_launch(p->width, p->height, p->iterations, p->flags, p->sigma_normal, p->sigma_depth, sigma_variance, d_frame, d_aov,
+                                          d_var, d_out, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], l.stream, launch);
+    return lane_finish(c, rc, launch, (uint64_t)p->width * p->height, "denoise", stats);
+}
+/* the two batch-variance entries.  Device memory, or (host) host memory: the batch sums then go through the context's batch buffer and
+ * the framebuffer holds frame, var and, behind them, the feature buffers */
+int batch_variance(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batches, uint32_t batch_spp, uint32_t flags, const double* sums, const double* aov,
+                   double* frame, double* var, bool host, rt1w_stats* stats) {
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    rt1w_denoise_params dp;
+    memset(&dp, 0, sizeof dp);
+    dp.width = w; dp.height = h; dp.flags = flags;
+    int rc = denoise_validate(c, &dp);
+    if (rc < 0) return rc;
+    if ((rc = batches_validate(batches, batch_spp)) < 0) return rc;
+    if (!sums || !aov || !frame || !var) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const size_t npix = (size_t)w * h;
+    const double *d_sums = sums, *d_aov = aov;
+    double *d_frame = frame, *d_var = var;
+    if (host) {
+        if ((rc = reserve_out(c, npix * (4 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
+        if ((rc = batches_reserve(c, npix * 3 * batches * sizeof(double))) < 0) return rc;
+        d_frame = c->d_out; d_var = c->d_out + npix * 3;
+        double* d_a = c->d_out + npix * 4;
+        if (!hip_ok(hipMemcpy(c->d_batches, sums, npix * 3 * batches * sizeof(double), hipMemcpyHostToDevice), "batch variance: sums copy")) return RT1W_ERR_DEVICE;
+        if (!hip_ok(hipMemcpy(d_a, aov, npix * RT1W_AOV_CHANNELS * sizeof(double), hipMemcpyHostToDevice), "batch variance: feature buffer copy")) return RT1W_ERR_DEVICE;
+        d_sums = c->d_batches; d_aov = d_a;
+    }
+    rt1w_stats st;
+    if ((rc = batch_variance_common(c, w, h, batches, batch_spp, flags, d_sums, d_aov, d_frame, d_var, &st)) < 0) return rc;
+    if (host && !hip_ok(hipMemcpy(frame, d_frame, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "batch variance: frame copy")) return RT1W_ERR_DEVICE;
+    if (host && !hip_ok(hipMemcpy(var, d_var, npix * sizeof(double), hipMemcpyDeviceToHost), "batch variance: variance copy")) return RT1W_ERR_DEVICE;
+    if (stats) { *stats = st; stats->total_ms = timer.ms(); }
+    return RT1W_OK;
+}
+/* the two rt1w_denoise_var entries: as denoise(), with the variance buffer behind the feature buffers */
+int denoise_var(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, double sigma_variance,
+                double* out, bool host, rt1w_stats* stats) {
+    int rc = denoise_validate(c, p);
+    if (rc < 0) return rc;
+    if ((rc = sigma_variance_validate(sigma_variance)) < 0) return rc;
+    if (!frame || !aov || !var || !out) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const size_t npix = (size_t)p->width * p->height;
+    const double *d_frame = frame, *d_aov = aov, *d_var = var;
+    double* d_out = out;
+    if (host) {
+        if ((rc = reserve_out(c, npix * (4 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
+        d_frame = d_out = c->d_out;
+        d_var = c->d_out + npix * 3;
+        d_aov = c->d_out + npix * 4;
+        if (!hip_ok(hipMemcpy(d_out, frame, npix * 3 * sizeof(double), hipMemcpyHostToDevice), "denoise: frame copy")) return RT1W_ERR_DEVICE;
+        if (!hip_ok(hipMemcpy(d_out + npix * 3, var, npix * sizeof(double), hipMemcpyHostToDevice), "denoise: variance copy")) return RT1W_ERR_DEVICE;
+        if (!hip_ok(hipMemcpy(d_out + npix * 4, aov, npix * RT1W_AOV_CHANNELS * sizeof(double), hipMemcpyHostToDevice), "denoise: feature buffer copy")) return RT1W_ERR_DEVICE;
+    }
+    rt1w_stats st;
+    if ((rc = denoise_var_common(c, p, sigma_variance, d_frame, d_aov, d_var, d_out, &st)) < 0) return rc;
+    if (host && !hip_ok(hipMemcpy(out, d_out, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "denoise: result copy")) return RT1W_ERR_DEVICE;
+    if (stats) { *stats = st; stats->total_ms = timer.ms(); }
+    return RT1W_OK;
+}
+/* rt1w_render_denoised_var: the batches' sums into the context's batch buffer; frame, var and the deep feature buffers in the framebuffer */
+int render_denoised_var(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, uint32_t batches, double sigma_variance,
+                        const AovDeep& deep, double* out_rgb, rt1w_stats* stats) {
+    int rc = aov_deep_validate(&deep);
+    if (rc < 0) return rc;
+    if ((rc = sigma_variance_validate(sigma_variance)) < 0) return rc;
+    if ((rc = validate(c, p)) < 0) return rc;
+    if (!out_rgb) { set_error("null output"); return RT1W_ERR_INVALID; }
+    if ((rc = refuse_named_flag(p->flags, true, " does not apply to rt1w_render_denoised")) < 0) return rc;
+    if (p->strip_rows) { set_error("rt1w_render_denoised takes a contiguous tile (strip_rows must be 0): denoise the gathered frame with rt1w_denoise"); return RT1W_ERR_INVALID; }
+    if (p->precision != RT1W_PRECISION_F64) { set_error("RT1W_PRECISION_F32 does not apply to rt1w_render_denoised (the filter is f64 only)"); return RT1W_ERR_INVALID; }
+    uint32_t k = 0u, n = 0u;
+    if (!rt_dv_split(p->spp, batches, k, n)) { set_error("rt1w_render_denoised_var: 2 .. 16 batches (0 = 4), and spp a multiple of their number"); return RT1W_ERR_INVALID; }
+    rt1w_denoise_params dp;
+    memset(&dp, 0, sizeof dp);
+    if (d) dp = *d;
+    if ((dp.width && dp.width != p->tile_w) || (dp.height && dp.height != p->tile_h)) { set_error("denoise: width / height must be 0 or the tile's"); return RT1W_ERR_INVALID; }
+    dp.width = p->tile_w; dp.height = p->tile_h;
+    if ((rc = denoise_validate(c, &dp)) < 0) return rc;
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const size_t npix = (size_t)p->tile_w * p->tile_h;
+    if ((rc = reserve_out(c, npix * (4 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
+    if ((rc = batches_reserve(c, npix * 3 * k * sizeof(double))) < 0) return rc;
+    double* d_frame = c->d_out;
+    double* d_var = c->d_out + npix * 3;
+    double* d_aov = c->d_out + npix * 4;
+    rt1w_stats st;
+    memset(&st, 0, sizeof st);
+    rt1w_render_params bp = *p; /* batch b: samples sample_offset + b n .. + n - 1 as raw sums; one chunk size for all, the default of n samples */
+    bp.flags |= RT1W_OUT_SUM;
+    bp.spp = n;
+    for (uint32_t b = 0; b < k; ++b) {
+        bp.sample_offset = p->sample_offset + b * n;
+        rt1w_stats sb;
+        memset(&sb, 0, sizeof sb);
+        if ((rc = render_common(c, &bp, c->d_batches + npix * 3 * b, &sb)) < 0) return rc;
+        if (b == 0u) st = sb;
+        else { st.paths += sb.paths; st.segments += sb.segments; st.kernel_ms += sb.kernel_ms; st.passes += sb.passes; }
+    }
+    rt1w_render_params ap = *p; /* the feature buffers of the same tile, all k n samples and seed, by the scene's own variant */
+    ap.flags = 0u;
+    rt1w_stats sa, sv, sd;
+    if ((rc = render_aov_common(c, &ap, &deep, d_aov, &sa)) < 0) return rc;
+    if ((rc = batch_variance_common(c, dp.width, dp.height, k, n, dp.flags, c->d_batches, d_aov, d_frame, d_var, &sv)) < 0) return rc;
+    if ((rc = denoise_var_common(c, &dp, sigma_variance, d_frame, d_aov, d_var, d_frame, &sd)) < 0) return rc;
+    if (!hip_ok(hipMemcpy(out_rgb, d_frame, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "denoised frame copy")) return RT1W_ERR_DEVICE;
+    if (stats) {
+        *stats = st;
+        stats->kernel_ms = st.kernel_ms + sa.kernel_ms + sv.kernel_ms + sd.kernel_ms;
+        stats->grid = sd.grid; stats->block = sd.block;
+        stats->total_ms = timer.ms();
+    }
+    return RT1W_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -234,5 +410,26 @@ int rt1w_render_denoised_deep(rt1w_context* c, const rt1w_render_params* p, cons
                               double* out_rgb, rt1w_stats* stats) {
     const AovDeep deep{max_specular, max_fuzz};
     return render_denoised(c, p, d, &deep, out_rgb, stats);
+}
+int rt1w_batch_variance(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batches, uint32_t batch_spp, uint32_t flags, const double* sums,
+                        const double* aov, double* frame, double* var, rt1w_stats* stats) {
+    return batch_variance(c, width, height, batches, batch_spp, flags, sums, aov, frame, var, true, stats);
+}
+int rt1w_batch_variance_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batches, uint32_t batch_spp, uint32_t flags, const void* d_sums,
+                               const void* d_aov, void* d_frame, void* d_var, rt1w_stats* stats) {
+    return batch_variance(c, width, height, batches, batch_spp, flags, (const double*)d_sums, (const double*)d_aov, (double*)d_frame, (double*)d_var, false, stats);
+}
+int rt1w_denoise_var(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, double sigma_variance,
+                     double* out, rt1w_stats* stats) {
+    return denoise_var(c, p, frame, aov, var, sigma_variance, out, true, stats);
+}
+int rt1w_denoise_var_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, const void* d_var,
+                            double sigma_variance, void* d_out, rt1w_stats* stats) {
+    return denoise_var(c, p, (const double*)d_frame, (const double*)d_aov, (const double*)d_var, sigma_variance, (double*)d_out, false, stats);
+}
+int rt1w_render_denoised_var(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, uint32_t batches, double sigma_variance,
+                             uint32_t max_specular, double max_fuzz, double* out_rgb, rt1w_stats* stats) {
+    const AovDeep deep{max_specular, max_fuzz};
+    return render_denoised_var(c, p, d, batches, sigma_variance, deep, out_rgb, stats);
 }
 } /* extern "C" */

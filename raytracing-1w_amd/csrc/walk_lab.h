@@ -43,6 +43,15 @@ int rt1w_lab_aov_deep_host(const rt1w_scene* s, const rt1w_render_params* p, uin
 /* CPU twin of rt1w_denoise (denoise_host.cpp: rt_denoise.h built for the host): the same double[h][w][3] from host buffers, no GPU.
  * RT1W_OK, or RT1W_ERR_INVALID as the device entry (null pointers, zero sizes, iterations > 8, unknown flags, bad sigmas) */
 int rt1w_lab_denoise_host(const rt1w_denoise_params* p, const double* frame, const double* aov, double* out);
+/* CPU twins of rt1w_batch_variance and rt1w_denoise_var (denoise_host.cpp: rt_denoise_var.h built for the host): the same frame[h][w][3] and
+ * var[h][w], the same out[h][w][3], from host buffers, no GPU; RT1W_ERR_INVALID as the device entries */
+int rt1w_lab_batch_variance_host(uint32_t width, uint32_t height, uint32_t batches, uint32_t batch_spp, uint32_t flags, const double* sums,
+                                 const double* aov, double* frame, double* var);
+int rt1w_lab_denoise_var_host(const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, double sigma_variance,
+                              double* out);
+/* how rt1w_render_denoised_var takes its `batches` and `sigma_variance` for a render of `spp` samples: out = {batches K, samples per batch n},
+ * or RT1W_ERR_INVALID exactly where that entry refuses them (K outside 2 .. 16, spp not a multiple of K, sigma negative or not finite) */
+int rt1w_lab_denoised_var_split(uint32_t spp, uint32_t batches, double sigma_variance, uint32_t out[2]);
 
 /* f32_exact.hip.  rt1w_lab_f32_exact: on != 0 makes every RT1W_PRECISION_F32 render of the process run the f32 kernels built with 64-bit
  * elementary functions (generic kernels only; the build the CPU twin oracle/oracle_flat_f32.cpp equals bit for bit) instead of the
