@@ -807,6 +807,28 @@ def f32_elementary(name, x, y=None, device=0):
     return out
 
 
+DENOISE_ELEMENTARY = ("falloff", "powi")
+
+
+def denoise_elementary(name, x, e=None, device=0):
+    """Diagnostics (librt1w_lab.so: rt1w_lab_denoise_elementary): the function `name` of DENOISE_ELEMENTARY of csrc/rt_denoise.h over a
+    float64 array -- rt_dn_falloff(x), or rt_dn_powi(x, e) with uint32 exponents e.  device 0: the host build (no GPU); 1: a kernel on
+    GPU 0."""
+    fn = load_lab().rt1w_lab_denoise_elementary
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.c_int, _P, _P, C.c_uint64, _P]
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    assert x.ndim == 1 and x.size > 0
+    if e is not None:
+        e = np.ascontiguousarray(np.broadcast_to(np.asarray(e, dtype=np.uint32), x.shape))
+    out = np.empty_like(x)
+    rc = fn(device, DENOISE_ELEMENTARY.index(name), x.ctypes.data_as(_P), e.ctypes.data_as(_P) if e is not None else None, x.size,
+            out.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_denoise_elementary")
+    return out
+
+
 def resolve(sums, spp):
     s = np.ascontiguousarray(sums, dtype=np.float64)
     out = np.empty_like(s)

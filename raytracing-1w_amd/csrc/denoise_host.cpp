@@ -104,6 +104,16 @@ extern "C" int rt1w_lab_denoise_var_host(const rt1w_denoise_params* p, const dou
     return RT1W_OK;
 }
 
+/* f32_exact.hip: the same two functions of rt_denoise.h, one lane per element, on GPU 0 */
+int rt_lab_denoise_elementary_device(int fn, const double* x, const uint32_t* e, uint64_t n, double* out);
+
+extern "C" int rt1w_lab_denoise_elementary(int device, int fn, const double* x, const uint32_t* e, uint64_t n, double* out) {
+    if ((device != 0 && device != 1) || (fn != 0 && fn != 1) || !x || !out || (fn == 1 && !e) || n == 0u) return RT1W_ERR_INVALID;
+    if (device == 1) return rt_lab_denoise_elementary_device(fn, x, e, n, out);
+    for (uint64_t i = 0; i < n; ++i) out[i] = fn == 0 ? rt_dn_falloff(x[i]) : rt_dn_powi(x[i], e[i]);
+    return RT1W_OK;
+}
+
 extern "C" int rt1w_lab_denoised_var_split(uint32_t spp, uint32_t batches, double sigma_variance, uint32_t out[2]) {
     double sv;
     uint32_t k = 0u, n = 0u;

@@ -9,11 +9,15 @@
  *
  * The kernels reach the product's own plan, launch, resolve and statistics: when the library is loaded it registers exact_kernel_of
  * with librt1w.so (rt1w_internal.h: rt1w_internal_register_f32_kernels), which answers nullptr -- the product's kernel runs -- until
- * rt1w_lab_f32_exact(1) switches it on.  No public flag, no entry of include/rt1w.h, no kernel-choice row: not a product mode. */
+ * rt1w_lab_f32_exact(1) switches it on.  No public flag, no entry of include/rt1w.h, no kernel-choice row: not a product mode.
+ *
+ * Also here, as the library's other per-element probe: the device half of rt1w_lab_denoise_elementary (rt_denoise.h's falloff and
+ * integer power, which the macro above does not touch). */
 #define RT_F32_NS rtf32x
 #include "rt_f32_kernels.h"
 
 #include "rt1w_internal.h"
+#include "rt_denoise.h"
 #include "walk_lab.h"
 
 #if !defined(RT_F32_ELEMENTARY_F64)
@@ -49,7 +53,35 @@ __global__ void f32_elementary_kernel(int fn, const float* __restrict__ x, const
     }
 }
 
+/* the two functions the filter kernels build their weights from (rt_denoise.h), one argument per lane: what the device makes of the
+ * text that denoise_host.cpp compiles for the host */
+__global__ void denoise_elementary_kernel(int fn, const double* __restrict__ x, const uint32_t* __restrict__ e, unsigned long long n, double* __restrict__ out) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x)
+        out[i] = fn == 0 ? rt_dn_falloff(x[i]) : rt_dn_powi(x[i], e[i]);
+}
+
 } // namespace
+
+/* the device half of rt1w_lab_denoise_elementary (denoise_host.cpp checks the arguments and has the host half); e is read for fn 1 only */
+int rt_lab_denoise_elementary_device(int fn, const double* x, const uint32_t* e, uint64_t n, double* out) {
+    double *dx = nullptr, *dout = nullptr;
+    uint32_t* de = nullptr;
+    const size_t bytes = (size_t)n * sizeof(double), ebytes = (size_t)n * sizeof(uint32_t);
+    bool ok = hipSetDevice(0) == hipSuccess && hipMalloc((void**)&dx, bytes) == hipSuccess && hipMalloc((void**)&dout, bytes) == hipSuccess &&
+              hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && fn == 1) ok = hipMalloc((void**)&de, ebytes) == hipSuccess && hipMemcpy(de, e, ebytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        const unsigned int block = 256;
+        const unsigned long long want = (n + block - 1u) / block;
+        hipLaunchKernelGGL(denoise_elementary_kernel, dim3((unsigned int)(want < 4096ull ? want : 4096ull)), dim3(block), 0, 0, fn, dx, de, (unsigned long long)n, dout);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (dx) (void)hipFree(dx);
+    if (de) (void)hipFree(de);
+    if (dout) (void)hipFree(dout);
+    if (!ok) { rt1w_internal_set_error("rt1w_lab_denoise_elementary: device error"); return RT1W_ERR_DEVICE; }
+    return RT1W_OK;
+}
 
 extern "C" int rt1w_lab_f32_exact(int on) {
     const int was = g_exact_on ? 1 : 0;

@@ -52,6 +52,10 @@ int rt1w_lab_denoise_var_host(const rt1w_denoise_params* p, const double* frame,
 /* how rt1w_render_denoised_var takes its `batches` and `sigma_variance` for a render of `spp` samples: out = {batches K, samples per batch n},
  * or RT1W_ERR_INVALID exactly where that entry refuses them (K outside 2 .. 16, spp not a multiple of K, sigma negative or not finite) */
 int rt1w_lab_denoised_var_split(uint32_t spp, uint32_t batches, double sigma_variance, uint32_t out[2]);
+/* the two functions the filters build their weights from (rt_denoise.h), on their own: out[i] = rt_dn_falloff(x[i]) (fn 0; e may be
+ * null) or rt_dn_powi(x[i], e[i]) (fn 1).  device 0: the host build of denoise_host.cpp, no GPU; device 1: one lane per element on
+ * GPU 0 (f32_exact.hip).  RT1W_ERR_INVALID for anything else, null pointers or n = 0 */
+int rt1w_lab_denoise_elementary(int device, int fn, const double* x, const uint32_t* e, uint64_t n, double* out);
 
 /* f32_exact.hip.  rt1w_lab_f32_exact: on != 0 makes every RT1W_PRECISION_F32 render of the process run the f32 kernels built with 64-bit
  * elementary functions (generic kernels only; the build the CPU twin oracle/oracle_flat_f32.cpp equals bit for bit) instead of the
