@@ -466,6 +466,106 @@ int rt1w_denoise_var_device(rt1w_context* c, const rt1w_denoise_params* p, const
 int rt1w_render_denoised_var(rt1w_context* c, const rt1w_render_params* p, const rt1w_denoise_params* d, uint32_t batches, double sigma_variance,
                              uint32_t max_specular, double max_fuzz, double* out_rgb, rt1w_stats* stats);
 
+/* ---- adaptive sampling: a sample budget spent where the frame is noisy ----
+ * The consumer of the batch variance that the entries above lack: instead of giving every pixel the same count, render a short pilot,
+ * estimate the error of every tile from the spread of its sample batches, and give further batches to the tiles that need them, until a
+ * budget is spent.  Replaces nothing of the reference, which reaches a clean image by sample count alone (src/main.rs:939).  No render
+ * kernel is involved beyond being called: a batch of a rectangle is rt1w_render_device with RT1W_OUT_SUM, whose bits depend on (pixel,
+ * sample index, chunk) only, not on the rectangle.
+ * KNOWN PROPERTY: a pixel's sample count depends on its earlier samples, so the estimator is slightly biased (a pixel that looks converged
+ * by chance stops early).  This is adaptive sampling's known bias; the pilot, which every pixel gets whatever it shows, bounds it.
+ *
+ * Accumulator.  acc double[h][w][8], caller-owned, 64 B per pixel; all zero = empty.  Per pixel:
+ *     0-2 S        the sum of the batch sums, added in merge order (the first batch is taken as it is);
+ *     3   m        the number of batches merged.  Every merge into one accumulator uses the same batch_spp = n: the count is m n;
+ *     4,5 mean_d, M2_d   Welford's mean and sum of squared deviations of the DEMODULATED batch luminance l_k, exactly
+ *                  rt1w_batch_variance's l_k: luminance of (S_k * (1 / n)) / A, A the albedo floor (1 with RT1W_DENOISE_KEEP_ALBEDO);
+ *     6,7 mean_p, M2_p   the same of the PLAIN luminance, of S_k * (1 / n).
+ *   Welford, in this order, without FMA contraction:  m += 1;  d = l - mean;  mean = mean + d / m;  M2 = M2 + d * (l - mean).
+ *   A batch whose demodulated or plain luminance is not finite is still added to S and m, but updates neither pair and writes
+ *   RT1W_ACCUM_NO_ESTIMATE into M2_d and M2_p; a pixel so marked stays marked (later batches add to S and m only).  A Welford M2 is
+ *   never negative, so the marker cannot be met otherwise.
+ * rt1w_accum_merge: one rendered batch of the rectangle (x0, y0, tile_w, tile_h) of a width x height frame into acc.
+ *   tile_sums double[tile_h][tile_w][3] as rt1w_render with RT1W_OUT_SUM and spp = batch_spp returns it; aov double[height][width][8] of
+ *   the WHOLE frame; flags 0 or RT1W_DENOISE_KEEP_ALBEDO.  One lane per pixel of the rectangle, 8 x 8 per wave, 16 x 16 per workgroup:
+ *   stats grid = ceil(tile_w / 16) * ceil(tile_h / 16), block 256.  A rectangle outside the frame, batch_spp 0: RT1W_ERR_INVALID.
+ * rt1w_accum_resolve: acc -> frame double[h][w][3], var double[h][w], spp double[h][w].
+ *     frame = rt1w_resolve's rule on S with the pixel's own count: NaN of S to 0, times 1 / (m n); (0, 0, 0) for an empty pixel;
+ *     var   = M2_d / (m (m - 1)), the variance of the mean demodulated luminance that rt1w_denoise_var takes; 0 where m < 2, where the
+ *             value is negative or not finite, and where the pixel has no estimate;
+ *     spp   = m n as a double.
+ *   grid = ceil(w / 16) * ceil(h / 16), block 256.
+ * rt1w_accum_tile_error: acc -> err double[ceil(h / tile)][ceil(w / tile)]; tile a multiple of 16 in 16 .. 256.
+ *     e_p   = (M2_p / (m (m - 1))) / (max(mean_p, 0) + 0.01): the estimated variance of the pixel's mean over its brightness, which is
+ *             the squared error of the DISPLAYED value sqrt(c) (color.rs:56-65) up to a factor 4 -- d sqrt(c) = dc / (2 sqrt(c)); the
+ *             0.01 keeps dark pixels from dividing by 0.  0 where m < 2, where the pixel has no estimate or the value is not finite;
+ *     err   = (sum of the tile's e_p) / (pixels of the tile inside the frame), summed in this order: within each 16 x 16 block of the
+ *             tile, 256 values at the pixels' row-major index in the block (0 for a pixel outside the frame), added by the binary tree
+ *             v[i] += v[i + stride] for i < stride, stride = 128, 64 .. 1; then the blocks of the tile that hold a pixel of the frame in
+ *             row-major order, 0 + b_0 + b_1 ..., by one lane.  No atomics.
+ *   grid = the number of tiles (one workgroup each), block 256.
+ * All three are bit-identical to the CPU build (librt1w_lab.so: rt1w_lab_accum_merge_host, rt1w_lab_accum_resolve_host,
+ * rt1w_lab_tile_error_host).  The host forms go through context buffers (grown on demand, freed with the context); stats as
+ * rt1w_batch_variance (paths = pixels touched, passes 1, kernel_ms, total_ms). */
+#define RT1W_ACCUM_NO_ESTIMATE (-1.0)
+int rt1w_accum_merge(rt1w_context* c, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h, uint32_t batch_spp,
+                     uint32_t flags, const double* tile_sums, const double* aov, double* acc, rt1w_stats* stats);
+/* same on device memory of the context's GPU; the three buffers are distinct.  Synchronises the context's stream before returning. */
+int rt1w_accum_merge_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h,
+                            uint32_t batch_spp, uint32_t flags, const void* d_tile_sums, const void* d_aov, void* d_acc, rt1w_stats* stats);
+int rt1w_accum_resolve(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc, double* frame, double* var,
+                       double* spp, rt1w_stats* stats);
+int rt1w_accum_resolve_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batch_spp, const void* d_acc, void* d_frame, void* d_var,
+                              void* d_spp, rt1w_stats* stats);
+int rt1w_accum_tile_error(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const double* acc, double* err, rt1w_stats* stats);
+int rt1w_accum_tile_error_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const void* d_acc, void* d_err, rt1w_stats* stats);
+
+/* The plan.  Zero means the default for every member but `size`, which is sizeof(rt1w_adaptive_params) as the caller compiled it (anything
+ * else: RT1W_ERR_INVALID; the struct is not one of rt1w_abi_sizeof's).
+ *   Pilot.   pilot_batches batches of batch_spp samples on the whole frame.
+ *   Rounds.  While budget remains: (1) rt1w_accum_tile_error; (2) the candidates are the tiles with err > target_error and
+ *            (m + 1) * batch_spp <= max_spp; (3) ordered by err descending, ties by tile index (row-major) ascending; (4) taken in that
+ *            order WHILE both hold -- the pixels taken this round stay <= round_share * width * height (the first candidate is taken
+ *            whatever its size), and the pixel-samples spent in all, the candidate's included, stay <= budget_spp * width * height: the
+ *            first candidate that breaks either ends the round; (5) a round that takes nothing ends the loop.
+ *   Batch.   Every taken tile gets one more batch: rt1w_render_device of its rectangle with RT1W_OUT_SUM, spp = batch_spp,
+ *            sample_offset = p->sample_offset + m * batch_spp, and chunk = p->chunk or, if that is 0,
+ *            rt1w_scene_default_chunk(scene, width, height, batch_spp) of the WHOLE frame, passed explicitly: with that the bits do not
+ *            depend on how tiles are grouped into launches.
+ *   Launches. Taken tiles that are adjacent in one tile row and have equal m are rendered as one rectangle and merged by one
+ *            rt1w_accum_merge (bits-neutral by the above). */
+typedef struct rt1w_adaptive_params {
+    uint32_t size;           /* sizeof(rt1w_adaptive_params) */
+    uint32_t tile;           /* side of the square tiles, a multiple of 16 in 16 .. 256; 0 = 16 */
+    uint32_t batch_spp;      /* samples per batch n; 0 = max(1, budget_spp / 8): the default pilot is half of the budget */
+    uint32_t pilot_batches;  /* 2 .. 16; 0 = 4 */
+    uint32_t budget_spp;     /* mean samples per pixel to spend, at least the pilot's pilot_batches * batch_spp; 0 = 64 */
+    uint32_t max_spp;        /* most samples of one pixel, at least the pilot's; 0 = 8 * budget_spp */
+    double target_error;     /* tiles at or below it get no more samples; finite, >= 0; 0 (default): the budget alone decides */
+    double round_share;      /* share of the frame's pixels one round may take, in (0, 1]; 0 = 1/4 */
+    uint32_t flags;          /* 0 or RT1W_DENOISE_KEEP_ALBEDO: how the merges demodulate */
+} rt1w_adaptive_params;
+/* One round of the plan, on the host, without a GPU or a context: err and m_per_tile are [n_tiles_y][n_tiles_x] of a width x height frame
+ * (n_tiles_x = ceil(width / tile), likewise y: RT1W_ERR_INVALID otherwise); the pixel-samples spent so far are those m_per_tile says.
+ * Returns the number of tiles taken (0 ends the loop) and writes their row-major indices, in the order taken, to out_tiles -- as many as
+ * `capacity` holds (out_tiles may be NULL with capacity 0, to ask for the number). */
+int rt1w_adaptive_select(const rt1w_adaptive_params* params, uint32_t n_tiles_x, uint32_t n_tiles_y, uint32_t width, uint32_t height, const double* err,
+                         const uint32_t* m_per_tile, uint32_t* out_tiles, uint32_t capacity);
+/* One call.  p is the frame: its tile must be the whole image (x0 = y0 = 0, tile_w = width, tile_h = height), p->spp is ignored (the budget
+ * decides).  In this order: rt1w_render_aov_device over the PILOT's samples only (spp = pilot_batches * batch_spp at p->sample_offset) --
+ * these feature buffers demodulate every merge and guide the filter, a stated limit: the guides have the pilot's sample count; the pilot
+ * and the rounds as above, every batch merged by rt1w_accum_merge_device, one device->host copy of err per round; rt1w_accum_resolve_device;
+ * if `d` is not NULL rt1w_denoise_var_device with `d` and sigma_variance (d's width / height must be 0 or the frame's; with d NULL
+ * sigma_variance is still validated); one device->host copy into out_rgb[height][width][3] and, if not NULL, out_spp[height][width] (the
+ * per-pixel sample counts as doubles).  Bit-identical to composing these public entries.  Refuses what rt1w_render_denoised_var refuses
+ * (RT1W_OUT_SUM, RT1W_OUT_FRAME, RT1W_RNG_REFERENCE, RT1W_PROBE_COHERENT, interleaved strips, RT1W_PRECISION_F32), a tile that is not the
+ * frame, the plan's refusals above and a p->sample_offset + max_spp beyond 2^32 - 1: all RT1W_ERR_INVALID.
+ * stats: the renders' sums -- paths = the samples actually spent (= the sum of the spp map), segments, passes; kernel_ms every kernel of
+ * the call; total_ms the whole call; chunk the batches' chunk; n_chunks = the number of ROUNDS after the pilot (not a chunk count here);
+ * grid / block of the last kernel (the filter's level kernel, or the resolve kernel).  Buffers are the context's, grown on demand. */
+int rt1w_render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d /* NULL: no filter */,
+                         double sigma_variance, double* out_rgb, double* out_spp /* may be NULL */, rt1w_stats* stats);
+
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory
  * mapping that several single-GPU processes fill with RT1W_OUT_FRAME. */

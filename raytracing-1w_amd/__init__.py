@@ -176,6 +176,30 @@ _sig("rt1w_denoise_var", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.c_
 _sig("rt1w_denoise_var_device", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.c_double, _P, C.POINTER(Stats))
 _sig("rt1w_render_denoised_var", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(DenoiseParams), C.c_uint32, C.c_double, C.c_uint32, C.c_double, _P,
      C.POINTER(Stats))
+
+
+class AdaptiveParams(C.Structure):
+    """rt1w_adaptive_params (include/rt1w.h): `size` is sizeof as this binding lays the struct out; 0 elsewhere means the default."""
+    _fields_ = [("size", C.c_uint32), ("tile", C.c_uint32), ("batch_spp", C.c_uint32), ("pilot_batches", C.c_uint32), ("budget_spp", C.c_uint32),
+                ("max_spp", C.c_uint32), ("target_error", C.c_double), ("round_share", C.c_double), ("flags", C.c_uint32)]
+
+
+def adaptive_params(tile=0, batch_spp=0, pilot_batches=0, budget_spp=0, max_spp=0, target_error=0.0, round_share=0.0, keep_albedo=False, flags=0,
+                    size=None):
+    return AdaptiveParams(C.sizeof(AdaptiveParams) if size is None else size, tile, batch_spp, pilot_batches, budget_spp, max_spp, target_error,
+                          round_share, flags | (DENOISE_KEEP_ALBEDO if keep_albedo else 0))
+
+
+_U = C.c_uint32
+_sig("rt1w_accum_merge", C.c_int, _P, _U, _U, _U, _U, _U, _U, _U, _U, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_accum_merge_device", C.c_int, _P, _U, _U, _U, _U, _U, _U, _U, _U, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_accum_resolve", C.c_int, _P, _U, _U, _U, _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_accum_resolve_device", C.c_int, _P, _U, _U, _U, _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_accum_tile_error", C.c_int, _P, _U, _U, _U, _P, _P, C.POINTER(Stats))
+_sig("rt1w_accum_tile_error_device", C.c_int, _P, _U, _U, _U, _P, _P, C.POINTER(Stats))
+_sig("rt1w_adaptive_select", C.c_int, C.POINTER(AdaptiveParams), _U, _U, _U, _U, _P, _P, _P, _U)
+_sig("rt1w_render_adaptive", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(DenoiseParams), C.c_double, _P, _P,
+     C.POINTER(Stats))
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -232,6 +256,29 @@ def _variance_of(var, frame):
     if v.shape != frame.shape[:2]:
         raise ValueError("var must be [h, w]")
     return v
+
+
+ACCUM_RECORD = 8  # rt1w_accum_*: S rgb, m, mean_d, M2_d, mean_p, M2_p per pixel
+ACCUM_NO_ESTIMATE = -1.0
+
+
+def _accum_of(acc):
+    a = np.ascontiguousarray(acc, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != ACCUM_RECORD:
+        raise ValueError("acc must be [h, w, 8]")
+    return a
+
+
+def _merge_args(acc, tile_sums, aov, x0, y0):
+    a = _accum_of(acc).copy()
+    s, g = (np.ascontiguousarray(x, dtype=np.float64) for x in (tile_sums, aov))
+    if s.ndim != 3 or s.shape[2] != 3 or g.shape != a.shape[:2] + (AOV_CHANNELS,):
+        raise ValueError("tile_sums must be [tile_h, tile_w, 3] and aov [h, w, 8]")
+    return a, s, g, (a.shape[1], a.shape[0], x0, y0, s.shape[1], s.shape[0])
+
+
+def _tiles_of(width, height, tile):
+    return (width + tile - 1) // tile, (height + tile - 1) // tile
 
 
 def _v3(v):
@@ -639,6 +686,68 @@ class Context:
                                           out.ctypes.data_as(_P), C.byref(st)))
         return (out, _stats_dict(st)) if with_stats else out
 
+    def accum_merge(self, acc, tile_sums, aov, batch_spp, x0=0, y0=0, keep_albedo=False, with_stats=False):
+        """One rendered batch of a rectangle into an accumulator (rt1w_accum_merge): `acc` float64 [h, w, 8] (zeros = empty), `tile_sums`
+        [tile_h, tile_w, 3] the raw sums of a render with out_sum=True, spp=batch_spp of the rectangle at (x0, y0), `aov` [h, w, 8] of the
+        whole frame.  Returns the merged accumulator (a new array)."""
+        a, s, g, rect = _merge_args(acc, tile_sums, aov, x0, y0)
+        st = Stats()
+        _ck(_lib.rt1w_accum_merge(self._h, *rect, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, s.ctypes.data_as(_P), g.ctypes.data_as(_P),
+                                  a.ctypes.data_as(_P), C.byref(st)))
+        return (a, _stats_dict(st)) if with_stats else a
+
+    def accum_merge_device(self, d_acc, d_tile_sums, d_aov, width, height, rect, batch_spp, keep_albedo=False):
+        """Same on device memory (int addresses); rect = (x0, y0, tile_w, tile_h).  Returns the stats dict."""
+        st = Stats()
+        _ck(_lib.rt1w_accum_merge_device(self._h, width, height, *rect, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, C.c_void_p(d_tile_sums),
+                                         C.c_void_p(d_aov), C.c_void_p(d_acc), C.byref(st)))
+        return _stats_dict(st)
+
+    def accum_resolve(self, acc, batch_spp, with_stats=False):
+        """(frame [h, w, 3], var [h, w], spp [h, w]) of an accumulator (rt1w_accum_resolve)."""
+        a = _accum_of(acc)
+        frame, var, spp = np.empty(a.shape[:2] + (3,)), np.empty(a.shape[:2]), np.empty(a.shape[:2])
+        st = Stats()
+        _ck(_lib.rt1w_accum_resolve(self._h, a.shape[1], a.shape[0], batch_spp, a.ctypes.data_as(_P), frame.ctypes.data_as(_P), var.ctypes.data_as(_P),
+                                    spp.ctypes.data_as(_P), C.byref(st)))
+        return (frame, var, spp, _stats_dict(st)) if with_stats else (frame, var, spp)
+
+    def accum_resolve_device(self, d_acc, d_frame, d_var, d_spp, width, height, batch_spp):
+        st = Stats()
+        _ck(_lib.rt1w_accum_resolve_device(self._h, width, height, batch_spp, C.c_void_p(d_acc), C.c_void_p(d_frame), C.c_void_p(d_var),
+                                           C.c_void_p(d_spp), C.byref(st)))
+        return _stats_dict(st)
+
+    def accum_tile_error(self, acc, tile, with_stats=False):
+        """The error of every tile of an accumulator (rt1w_accum_tile_error): float64 [ceil(h / tile), ceil(w / tile)]."""
+        a = _accum_of(acc)
+        tx, ty = _tiles_of(a.shape[1], a.shape[0], max(int(tile), 1))
+        err = np.empty((ty, tx))
+        st = Stats()
+        _ck(_lib.rt1w_accum_tile_error(self._h, a.shape[1], a.shape[0], tile, a.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
+        return (err, _stats_dict(st)) if with_stats else err
+
+    def accum_tile_error_device(self, d_acc, d_err, width, height, tile):
+        st = Stats()
+        _ck(_lib.rt1w_accum_tile_error_device(self._h, width, height, tile, C.c_void_p(d_acc), C.c_void_p(d_err), C.byref(st)))
+        return _stats_dict(st)
+
+    def render_adaptive(self, width, height, adaptive=None, denoise=None, filter=False, sigma_variance=0.0, max_depth=50, sample_offset=0,
+                        global_seed=0, chunk=0, tile=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
+        """Adaptive sampling in one call (rt1w_render_adaptive): (frame [h, w, 3], spp [h, w]).  `adaptive`: dict of the keywords of
+        adaptive_params, None = defaults; `filter` or a `denoise` dict (keywords of Context.denoise_var) adds the variance-guided filter."""
+        p = self._params(width, height, 0, max_depth, tile, sample_offset, global_seed, chunk, False, kw.pop("variant", None), strips=strips, **kw)
+        p.flags |= flags
+        p.precision = precision
+        a = adaptive_params(**(adaptive or {}))
+        d = _denoise_params(0, 0, **(denoise or {})) if (filter or denoise is not None) else None
+        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
+        spp = np.empty((p.tile_h, p.tile_w), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_adaptive(self._h, C.byref(p), C.byref(a), C.byref(d) if d is not None else None, sigma_variance, out.ctypes.data_as(_P),
+                                      spp.ctypes.data_as(_P), C.byref(st)))
+        return (out, spp, _stats_dict(st)) if with_stats else (out, spp)
+
     def debug_aabb(self, cases):
         """cases[n, 14] = min3, max3, origin3, direction3, t_min, t_max -> (literal[n], fast[n]) from the device."""
         a = np.ascontiguousarray(cases, dtype=np.float64).reshape(-1, 14)
@@ -772,6 +881,59 @@ def denoise_var_host(frame, aov, var, sigma_variance=0.0, **kw):
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_denoise_var_host")
     return out
+
+
+def accum_merge_host(acc, tile_sums, aov, batch_spp, x0=0, y0=0, keep_albedo=False):
+    """CPU twin of Context.accum_merge (librt1w_lab.so: rt1w_lab_accum_merge_host): the accumulator the GPU must equal bit for bit."""
+    fn = load_lab().rt1w_lab_accum_merge_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32] * 8 + [_P, _P, _P]
+    a, s, g, rect = _merge_args(acc, tile_sums, aov, x0, y0)
+    rc = fn(*rect, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, s.ctypes.data_as(_P), g.ctypes.data_as(_P), a.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_accum_merge_host")
+    return a
+
+
+def accum_resolve_host(acc, batch_spp):
+    """CPU twin of Context.accum_resolve (rt1w_lab_accum_resolve_host): (frame, var, spp)."""
+    fn = load_lab().rt1w_lab_accum_resolve_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32] * 3 + [_P] * 4
+    a = _accum_of(acc)
+    frame, var, spp = np.empty(a.shape[:2] + (3,)), np.empty(a.shape[:2]), np.empty(a.shape[:2])
+    rc = fn(a.shape[1], a.shape[0], batch_spp, a.ctypes.data_as(_P), frame.ctypes.data_as(_P), var.ctypes.data_as(_P), spp.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_accum_resolve_host")
+    return frame, var, spp
+
+
+def tile_error_host(acc, tile):
+    """CPU twin of Context.accum_tile_error (rt1w_lab_tile_error_host)."""
+    fn = load_lab().rt1w_lab_tile_error_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32] * 3 + [_P] * 2
+    a = _accum_of(acc)
+    tx, ty = _tiles_of(a.shape[1], a.shape[0], max(int(tile), 1))
+    err = np.empty((ty, tx))
+    rc = fn(a.shape[1], a.shape[0], tile, a.ctypes.data_as(_P), err.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_tile_error_host")
+    return err
+
+
+def adaptive_select(width, height, err, m_per_tile, **adaptive):
+    """One round of the plan of rt1w_render_adaptive (rt1w_adaptive_select; host only, no GPU): the row-major indices of the tiles taken, in
+    the order taken.  err, m_per_tile: [tiles_y, tiles_x]; adaptive: the keywords of adaptive_params."""
+    a = adaptive_params(**adaptive)
+    e = np.ascontiguousarray(err, dtype=np.float64)
+    m = np.ascontiguousarray(m_per_tile, dtype=np.uint32)
+    if e.ndim != 2 or m.shape != e.shape:
+        raise ValueError("err and m_per_tile must be [tiles_y, tiles_x]")
+    out = np.zeros(max(e.size, 1), dtype=np.uint32)
+    n = _ck(_lib.rt1w_adaptive_select(C.byref(a), e.shape[1], e.shape[0], width, height, e.ctypes.data_as(_P), m.ctypes.data_as(_P),
+                                      out.ctypes.data_as(_P), e.size))
+    return [int(t) for t in out[:n]]
 
 
 class f32_exact:

@@ -1,0 +1,121 @@
+/* adaptive.hip -- the kernels of rt1w_accum_merge, rt1w_accum_resolve and rt1w_accum_tile_error (include/rt1w.h) over rt_adaptive.h.
+ *
+ * A unit of its own, inside its own namespace (the pattern of denoise_var.hip), so that no other code object moves with it.  The host
+ * half is in features.hip, which calls the three launchers below.
+ *
+ * Work mapping: that of denoise_var.hip -- one lane per pixel, an 8 x 8 pixel block per wave, 2 x 2 blocks (16 x 16 pixels) per
+ * workgroup of 256 lanes.  Merge and resolve compute every pixel whole by one lane.  The tile error runs one workgroup per tile: for
+ * each 16 x 16 block of the tile in row-major order every lane writes its pixel's e_p (0 outside the frame) into 2 KiB of LDS at the
+ * pixel's row-major index, the workgroup adds them by the binary tree of the header (stride 128 .. 1, a barrier per step), and lane 0
+ * adds the block's sum to the tile's: no atomics, one fixed order, the same bits as the CPU twin (adaptive_host.cpp).  The accumulator
+ * record is 64 bytes per pixel, read and written by its lane as 8 doubles. */
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <string.h>
+
+namespace rtad {
+#include "rt1w_num.h"
+#include "rt_adaptive.h"
+
+#define RT_AD_WG 256
+
+/* pixel of this lane inside its workgroup's 16 x 16 block: 8 x 8 per wave, 2 x 2 waves */
+__device__ __forceinline__ void rt_ad_lane_xy(uint32_t& lx, uint32_t& ly) {
+    const uint32_t wv = threadIdx.x >> 6, in = threadIdx.x & 63u;
+    lx = (wv & 1u) * 8u + (in & 7u);
+    ly = (wv >> 1) * 8u + (in >> 3);
+}
+
+/* tile_sums[th][tw][3], aov[h][w][8] -> acc[h][w][8]; workgroups in row order over the rectangle */
+__global__ __launch_bounds__(RT_AD_WG) void rt_ad_merge_kernel(uint32_t w, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, uint32_t batch_spp,
+                                                                uint32_t keep_albedo, const double* __restrict__ sums, const double* __restrict__ aov,
+                                                                double* __restrict__ acc) {
+    const uint32_t blocks_x = (tw + RT_AD_BLOCK - 1u) / RT_AD_BLOCK;
+    uint32_t lx, ly;
+    rt_ad_lane_xy(lx, ly);
+    const uint32_t rx = (blockIdx.x % blocks_x) * RT_AD_BLOCK + lx, ry = (blockIdx.x / blocks_x) * RT_AD_BLOCK + ly;
+    if (rx >= tw || ry >= th) return;
+    const unsigned long long i = (unsigned long long)(y0 + ry) * w + (x0 + rx);
+    const unsigned long long t = (unsigned long long)ry * tw + rx;
+    rt_ad_merge_pixel(batch_spp, keep_albedo != 0u, sums + t * 3u, aov + i * 8u, acc + i * RT_AD_RECORD);
+}
+
+/* acc[h][w][8] -> frame[h][w][3], var[h][w], spp[h][w] */
+__global__ __launch_bounds__(RT_AD_WG) void rt_ad_resolve_kernel(uint32_t w, uint32_t h, uint32_t batch_spp, const double* __restrict__ acc,
+                                                                  double* __restrict__ frame, double* __restrict__ var, double* __restrict__ spp) {
+    const uint32_t blocks_x = (w + RT_AD_BLOCK - 1u) / RT_AD_BLOCK;
+    uint32_t lx, ly;
+    rt_ad_lane_xy(lx, ly);
+    const uint32_t x = (blockIdx.x % blocks_x) * RT_AD_BLOCK + lx, y = (blockIdx.x / blocks_x) * RT_AD_BLOCK + ly;
+    if (x >= w || y >= h) return;
+    const unsigned long long i = (unsigned long long)y * w + x;
+    double f[3], v, s;
+    rt_ad_resolve_pixel(batch_spp, acc + i * RT_AD_RECORD, f, &v, &s);
+    frame[i * 3u] = f[0]; frame[i * 3u + 1u] = f[1]; frame[i * 3u + 2u] = f[2];
+    var[i] = v;
+    spp[i] = s;
+}
+
+/* acc[h][w][8] -> err[tiles_y][tiles_x]; one workgroup per tile */
+__global__ __launch_bounds__(RT_AD_WG) void rt_ad_tile_error_kernel(uint32_t w, uint32_t h, uint32_t tile, const double* __restrict__ acc,
+                                                                     double* __restrict__ err) {
+    __shared__ double v[RT_AD_WG];
+    const uint32_t tiles_x = (w + tile - 1u) / tile;
+    const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+    const uint32_t px0 = tx * tile, py0 = ty * tile; /* inside the frame: tile <= 256 and tx < tiles_x */
+    const uint32_t bw = tile / RT_AD_BLOCK;
+    uint32_t lx, ly;
+    rt_ad_lane_xy(lx, ly);
+    double total = 0.0;
+    for (uint32_t by = 0; by < bw; ++by) {
+        if (py0 + by * RT_AD_BLOCK >= h) break; /* uniform over the workgroup: blocks without a pixel of the frame are not added */
+        for (uint32_t bx = 0; bx < bw; ++bx) {
+            if (px0 + bx * RT_AD_BLOCK >= w) break;
+            const uint32_t x = px0 + bx * RT_AD_BLOCK + lx, y = py0 + by * RT_AD_BLOCK + ly;
+            double e = 0.0;
+            if (x < w && y < h) e = rt_ad_pixel_error(acc + ((unsigned long long)y * w + x) * RT_AD_RECORD);
+            v[ly * RT_AD_BLOCK + lx] = e;
+            __syncthreads();
+            for (uint32_t stride = 128u; stride >= 1u; stride >>= 1) {
+                if (threadIdx.x < stride) v[threadIdx.x] = v[threadIdx.x] + v[threadIdx.x + stride];
+                __syncthreads();
+            }
+            if (threadIdx.x == 0u) total = total + v[0];
+            __syncthreads(); /* v[0] is read before the next block's values are written */
+        }
+    }
+    if (threadIdx.x == 0u) err[blockIdx.x] = total / (double)rt_ad_tile_pixels(w, h, tile, tx, ty);
+}
+} // namespace rtad
+
+/* called by features.hip.  Each enqueues one kernel on `stream`; launch[0..1] = grid, block.  0, -1 (launch failure) or -2 (parameters
+ * refused). */
+extern "C" int rt1w_internal_accum_merge_launch(uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, uint32_t batch_spp,
+                                                uint32_t flags, const double* sums, const double* aov, double* acc, hipStream_t stream,
+                                                unsigned launch[2]) {
+    using namespace rtad;
+    if (!rt_ad_rect_ok(w, h, x0, y0, tw, th, batch_spp, flags)) return -2;
+    const unsigned grid = ((tw + RT_AD_BLOCK - 1u) / RT_AD_BLOCK) * ((th + RT_AD_BLOCK - 1u) / RT_AD_BLOCK);
+    launch[0] = grid; launch[1] = RT_AD_WG;
+    hipLaunchKernelGGL(rt_ad_merge_kernel, dim3(grid), dim3(RT_AD_WG), 0, stream, w, x0, y0, tw, th, batch_spp, flags & RT_DN_KEEP_ALBEDO, sums, aov, acc);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int rt1w_internal_accum_resolve_launch(uint32_t w, uint32_t h, uint32_t batch_spp, const double* acc, double* frame, double* var,
+                                                  double* spp, hipStream_t stream, unsigned launch[2]) {
+    using namespace rtad;
+    if (!rt_ad_frame_ok(w, h) || batch_spp == 0u) return -2;
+    const unsigned grid = ((w + RT_AD_BLOCK - 1u) / RT_AD_BLOCK) * ((h + RT_AD_BLOCK - 1u) / RT_AD_BLOCK);
+    launch[0] = grid; launch[1] = RT_AD_WG;
+    hipLaunchKernelGGL(rt_ad_resolve_kernel, dim3(grid), dim3(RT_AD_WG), 0, stream, w, h, batch_spp, acc, frame, var, spp);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int rt1w_internal_accum_tile_error_launch(uint32_t w, uint32_t h, uint32_t tile, const double* acc, double* err, hipStream_t stream,
+                                                     unsigned launch[2]) {
+    using namespace rtad;
+    if (!rt_ad_frame_ok(w, h) || !rt_ad_tile_ok(tile)) return -2;
+    const unsigned grid = ((w + tile - 1u) / tile) * ((h + tile - 1u) / tile);
+    launch[0] = grid; launch[1] = RT_AD_WG;
+    hipLaunchKernelGGL(rt_ad_tile_error_kernel, dim3(grid), dim3(RT_AD_WG), 0, stream, w, h, tile, acc, err);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -78,6 +78,7 @@ struct rt1w_context {
     double* d_out = nullptr; size_t out_bytes = 0;
     void* dn_buf[3] = {nullptr, nullptr, nullptr}; size_t dn_bytes[3] = {0, 0, 0}; /* rt1w_denoise, rt1w_denoise_var: two colour buffers and the guide buffer */
     double* d_batches = nullptr; size_t batches_bytes = 0; /* rt1w_batch_variance, rt1w_render_denoised_var: the sums of the sample batches */
+    double* d_accum = nullptr; size_t accum_bytes = 0; /* rt1w_accum_*, rt1w_render_adaptive: the accumulator and, behind it, the tile errors */
     RtKernel k64[RT_N_WALKS][RT_N_VARIANTS] = {}; /* g_kernels, queried at creation; the node-cache walks only with a walk table */
     bool walk_table = false; uint32_t walk_table_first = 0;
     bool sphere_media = false; /* every medium of the scene is bounded by a bare Sphere: the sphere-media walks serve */

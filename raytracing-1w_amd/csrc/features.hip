@@ -1,6 +1,6 @@
 /* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_denoise*,
- * rt1w_render_denoised*, rt1w_batch_variance*): validation, buffers, launch, timing, copies.  Host code only, built without a device pass: the
- * kernels belong to aov.hip, denoise.hip and denoise_var.hip and are launched through their host handles, the context and its render path to context.hip (context.h), so a
+ * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_render_adaptive): validation, buffers, launch, timing, copies.  Host code only, built without a device pass: the
+ * kernels belong to aov.hip, denoise.hip, denoise_var.hip and adaptive.hip and are launched through their host handles, the context and its render path to context.hip (context.h), so a
  * change here rebuilds none of the code objects. */
 #include <cstdio>
 #include <cstring>
@@ -8,6 +8,7 @@
 #include "context.h"
 #include "rt_aov_deep.h" /* rt_aov_deep_args_ok only */
 #include "rt_denoise_var.h" /* rt_dv_batches_ok, rt_dv_sigma, rt_dv_split only */
+#include "rt_adaptive_plan.h" /* the plan of rt1w_render_adaptive and rt1w_adaptive_select; rt_ad_*_ok of rt_adaptive.h */
 
 /* aov.hip: the first-hit feature buffers (rt1w_render_aov), by variant; workgroups of RT_BLOCK work-items that cover the frame's tile */
 extern "C" const void* rt1w_internal_aov_kernel(int variant);
@@ -26,6 +27,14 @@ extern "C" int rt1w_internal_denoise_var_launch(uint32_t w, uint32_t h, uint32_t
                                                 double sigma_variance, const double* frame, const double* aov, const double* var, double* out,
                                                 void* col_a, void* col_b, void* guide, hipStream_t stream, unsigned launch[2]);
 extern "C" unsigned rt1w_internal_denoise_var_sizeof(void); /* bytes per pixel of one of its colour buffers */
+/* adaptive.hip: the accumulator kernels; returns as rt1w_internal_denoise_launch */
+extern "C" int rt1w_internal_accum_merge_launch(uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, uint32_t batch_spp,
+                                                uint32_t flags, const double* sums, const double* aov, double* acc, hipStream_t stream,
+                                                unsigned launch[2]);
+extern "C" int rt1w_internal_accum_resolve_launch(uint32_t w, uint32_t h, uint32_t batch_spp, const double* acc, double* frame, double* var,
+                                                  double* spp, hipStream_t stream, unsigned launch[2]);
+extern "C" int rt1w_internal_accum_tile_error_launch(uint32_t w, uint32_t h, uint32_t tile, const double* acc, double* err, hipStream_t stream,
+                                                     unsigned launch[2]);
 
 using namespace rt1w;
 namespace {
@@ -388,6 +397,225 @@ int render_denoised_var(rt1w_context* c, const rt1w_render_params* p, const rt1w
     return RT1W_OK;
 }
 
+/* ---- adaptive sampling (include/rt1w.h: rt1w_accum_merge, rt1w_accum_resolve, rt1w_accum_tile_error, rt1w_render_adaptive) ---- */
+/* the context's accumulator buffer (the accumulator and, behind it, the tile errors), grown to `bytes` */
+int accum_reserve(rt1w_context* c, size_t bytes) {
+    if (bytes <= c->accum_bytes) return RT1W_OK;
+    if (c->d_accum) (void)hipFree(c->d_accum);
+    c->d_accum = nullptr; c->accum_bytes = 0;
+    if (!hip_ok(hipMalloc((void**)&c->d_accum, bytes), "hipMalloc(accumulator)")) return RT1W_ERR_NOMEM;
+    c->accum_bytes = bytes;
+    return RT1W_OK;
+}
+int accum_frame_validate(const rt1w_context* c, uint32_t w, uint32_t h) {
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (rt_ad_frame_ok(w, h)) return RT1W_OK;
+    set_error("accumulator: width and height must be 1 .. 2^30");
+    return RT1W_ERR_INVALID;
+}
+int accum_merge_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, uint32_t batch_spp, uint32_t flags,
+                       const double* d_sums, const double* d_aov, double* d_acc, rt1w_stats* stats) {
+    RtLane& l = c->lane[0];
+    unsigned launch[2] = {0u, 0u};
+    (void)hipEventRecord(l.ev0, l.stream);
+    const int rc = rt1w_internal_accum_merge_launch(w, h, x0, y0, tw, th, batch_spp, flags, d_sums, d_aov, d_acc, l.stream, launch);
+    return lane_finish(c, rc, launch, (uint64_t)tw * th, "accumulator merge", stats);
+}
+int accum_resolve_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batch_spp, const double* d_acc, double* d_frame, double* d_var, double* d_spp,
+                         rt1w_stats* stats) {
+    RtLane& l = c->lane[0];
+    unsigned launch[2] = {0u, 0u};
+    (void)hipEventRecord(l.ev0, l.stream);
+    const int rc = rt1w_internal_accum_resolve_launch(w, h, batch_spp, d_acc, d_frame, d_var, d_spp, l.stream, launch);
+    return lane_finish(c, rc, launch, (uint64_t)w * h, "accumulator resolve", stats);
+}
+int accum_tile_error_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const double* d_acc, double* d_err, rt1w_stats* stats) {
+    RtLane& l = c->lane[0];
+    unsigned launch[2] = {0u, 0u};
+    (void)hipEventRecord(l.ev0, l.stream);
+    const int rc = rt1w_internal_accum_tile_error_launch(w, h, tile, d_acc, d_err, l.stream, launch);
+    return lane_finish(c, rc, launch, (uint64_t)w * h, "tile error", stats);
+}
+/* the two rt1w_accum_merge entries.  Device memory, or (host) host memory: the accumulator then goes through the context's accumulator
+ * buffer, the feature buffers and the batch through the framebuffer */
+int accum_merge(rt1w_context* c, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, uint32_t batch_spp, uint32_t flags,
+                const double* sums, const double* aov, double* acc, bool host, rt1w_stats* stats) {
+    int rc = accum_frame_validate(c, w, h);
+    if (rc < 0) return rc;
+    if (!rt_ad_rect_ok(w, h, x0, y0, tw, th, batch_spp, flags)) {
+        set_error("accumulator merge: the rectangle must lie inside the frame, batch_spp >= 1, flags 0 or RT1W_DENOISE_KEEP_ALBEDO");
+        return RT1W_ERR_INVALID;
+    }
+    if (!sums || !aov || !acc) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const size_t npix = (size_t)w * h, tpix = (size_t)tw * th;
+    const double *d_sums = sums, *d_aov = aov;
+    double* d_acc = acc;
+    if (host) {
+        if ((rc = reserve_out(c, (npix * RT1W_AOV_CHANNELS + tpix * 3) * sizeof(double))) < 0) return rc;
+        if ((rc = accum_reserve(c, npix * RT_AD_RECORD * sizeof(double))) < 0) return rc;
+        double* d_s = c->d_out + npix * RT1W_AOV_CHANNELS;
+        if (!hip_ok(hipMemcpy(c->d_out, aov, npix * RT1W_AOV_CHANNELS * sizeof(double), hipMemcpyHostToDevice), "accumulator merge: feature buffer copy")) return RT1W_ERR_DEVICE;
+        if (!hip_ok(hipMemcpy(d_s, sums, tpix * 3 * sizeof(double), hipMemcpyHostToDevice), "accumulator merge: sums copy")) return RT1W_ERR_DEVICE;
+        if (!hip_ok(hipMemcpy(c->d_accum, acc, npix * RT_AD_RECORD * sizeof(double), hipMemcpyHostToDevice), "accumulator merge: accumulator copy")) return RT1W_ERR_DEVICE;
+        d_aov = c->d_out; d_sums = d_s; d_acc = c->d_accum;
+    }
+    rt1w_stats st;
+    if ((rc = accum_merge_common(c, w, h, x0, y0, tw, th, batch_spp, flags, d_sums, d_aov, d_acc, &st)) < 0) return rc;
+    if (host && !hip_ok(hipMemcpy(acc, d_acc, npix * RT_AD_RECORD * sizeof(double), hipMemcpyDeviceToHost), "accumulator merge: result copy")) return RT1W_ERR_DEVICE;
+    if (stats) { *stats = st; stats->total_ms = timer.ms(); }
+    return RT1W_OK;
+}
+int accum_resolve(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batch_spp, const double* acc, double* frame, double* var, double* spp, bool host,
+                  rt1w_stats* stats) {
+    int rc = accum_frame_validate(c, w, h);
+    if (rc < 0) return rc;
+    if (batch_spp == 0u) { set_error("accumulator resolve: batch_spp must be >= 1"); return RT1W_ERR_INVALID; }
+    if (!acc || !frame || !var || !spp) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const size_t npix = (size_t)w * h;
+    const double* d_acc = acc;
+    double *d_frame = frame, *d_var = var, *d_spp = spp;
+    if (host) {
+        if ((rc = reserve_out(c, npix * 5 * sizeof(double))) < 0) return rc;
+        if ((rc = accum_reserve(c, npix * RT_AD_RECORD * sizeof(double))) < 0) return rc;
+        if (!hip_ok(hipMemcpy(c->d_accum, acc, npix * RT_AD_RECORD * sizeof(double), hipMemcpyHostToDevice), "accumulator resolve: accumulator copy")) return RT1W_ERR_DEVICE;
+        d_acc = c->d_accum; d_frame = c->d_out; d_var = c->d_out + npix * 3; d_spp = c->d_out + npix * 4;
+    }
+    rt1w_stats st;
+    if ((rc = accum_resolve_common(c, w, h, batch_spp, d_acc, d_frame, d_var, d_spp, &st)) < 0) return rc;
+    if (host) {
+        if (!hip_ok(hipMemcpy(frame, d_frame, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "accumulator resolve: frame copy")) return RT1W_ERR_DEVICE;
+        if (!hip_ok(hipMemcpy(var, d_var, npix * sizeof(double), hipMemcpyDeviceToHost), "accumulator resolve: variance copy")) return RT1W_ERR_DEVICE;
+        if (!hip_ok(hipMemcpy(spp, d_spp, npix * sizeof(double), hipMemcpyDeviceToHost), "accumulator resolve: count copy")) return RT1W_ERR_DEVICE;
+    }
+    if (stats) { *stats = st; stats->total_ms = timer.ms(); }
+    return RT1W_OK;
+}
+int accum_tile_error(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const double* acc, double* err, bool host, rt1w_stats* stats) {
+    int rc = accum_frame_validate(c, w, h);
+    if (rc < 0) return rc;
+    if (!rt_ad_tile_ok(tile)) { set_error("tile error: tile must be a multiple of 16 in 16 .. 256"); return RT1W_ERR_INVALID; }
+    if (!acc || !err) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const size_t npix = (size_t)w * h, ntiles = (size_t)((w + tile - 1u) / tile) * ((h + tile - 1u) / tile);
+    const double* d_acc = acc;
+    double* d_err = err;
+    if (host) {
+        if ((rc = accum_reserve(c, (npix * RT_AD_RECORD + ntiles) * sizeof(double))) < 0) return rc;
+        if (!hip_ok(hipMemcpy(c->d_accum, acc, npix * RT_AD_RECORD * sizeof(double), hipMemcpyHostToDevice), "tile error: accumulator copy")) return RT1W_ERR_DEVICE;
+        d_acc = c->d_accum; d_err = c->d_accum + npix * RT_AD_RECORD;
+    }
+    rt1w_stats st;
+    if ((rc = accum_tile_error_common(c, w, h, tile, d_acc, d_err, &st)) < 0) return rc;
+    if (host && !hip_ok(hipMemcpy(err, d_err, ntiles * sizeof(double), hipMemcpyDeviceToHost), "tile error: result copy")) return RT1W_ERR_DEVICE;
+    if (stats) { *stats = st; stats->total_ms = timer.ms(); }
+    return RT1W_OK;
+}
+/* rt1w_render_aov_device, then per batch rt1w_render_device + rt1w_accum_merge_device, per round rt1w_accum_tile_error_device and the plan,
+ * rt1w_accum_resolve_device and (d) rt1w_denoise_var_device: frame, var, spp and the feature buffers in the framebuffer, a batch's sums in
+ * the batch buffer, the accumulator and the tile errors in the accumulator buffer */
+int render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d, double sigma_variance,
+                    double* out_rgb, double* out_spp, rt1w_stats* stats) {
+    int rc = sigma_variance_validate(sigma_variance);
+    if (rc < 0) return rc;
+    RtAdPlan plan;
+    if (const char* why = rt_ad_make_plan(a, &plan)) { set_error(why); return RT1W_ERR_INVALID; }
+    rt1w_render_params q;
+    if (p) { q = *p; q.spp = plan.batch_spp; } /* p->spp is ignored: validated as one batch */
+    if ((rc = validate(c, p ? &q : nullptr)) < 0) return rc;
+    if (!out_rgb) { set_error("null output"); return RT1W_ERR_INVALID; }
+    if ((rc = refuse_named_flag(p->flags, true, " does not apply to rt1w_render_denoised")) < 0) return rc;
+    if (p->strip_rows) { set_error("rt1w_render_denoised takes a contiguous tile (strip_rows must be 0): denoise the gathered frame with rt1w_denoise"); return RT1W_ERR_INVALID; }
+    if (p->precision != RT1W_PRECISION_F64) { set_error("RT1W_PRECISION_F32 does not apply to rt1w_render_denoised (the filter is f64 only)"); return RT1W_ERR_INVALID; }
+    if (p->x0 || p->y0 || p->tile_w != p->width || p->tile_h != p->height) { set_error("rt1w_render_adaptive takes the whole frame (x0 = y0 = 0, tile_w = width, tile_h = height)"); return RT1W_ERR_INVALID; }
+    if ((unsigned long long)p->sample_offset + plan.max_spp > 0xFFFFFFFFull) { set_error("adaptive: sample_offset + max_spp exceeds 2^32 - 1"); return RT1W_ERR_INVALID; }
+    const uint32_t W = p->width, H = p->height;
+    rt1w_denoise_params dp;
+    memset(&dp, 0, sizeof dp);
+    if (d) dp = *d;
+    if ((dp.width && dp.width != W) || (dp.height && dp.height != H)) { set_error("denoise: width / height must be 0 or the tile's"); return RT1W_ERR_INVALID; }
+    dp.width = W; dp.height = H;
+    if ((rc = denoise_validate(c, &dp)) < 0) return rc;
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const size_t npix = (size_t)W * H;
+    const uint32_t tiles_x = (W + plan.tile - 1u) / plan.tile, tiles_y = (H + plan.tile - 1u) / plan.tile;
+    const size_t ntiles = (size_t)tiles_x * tiles_y;
+    if ((rc = reserve_out(c, npix * (5 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
+    if ((rc = batches_reserve(c, npix * 3 * sizeof(double))) < 0) return rc;
+    if ((rc = accum_reserve(c, (npix * RT_AD_RECORD + ntiles) * sizeof(double))) < 0) return rc;
+    double* d_frame = c->d_out;
+    double* d_var = c->d_out + npix * 3;
+    double* d_spp = c->d_out + npix * 4;
+    double* d_aov = c->d_out + npix * 5;
+    double* d_acc = c->d_accum;
+    double* d_err = c->d_accum + npix * RT_AD_RECORD;
+    RtLane& l = c->lane[0];
+    if (!hip_ok(hipMemsetAsync(d_acc, 0, npix * RT_AD_RECORD * sizeof(double), l.stream), "accumulator clear")) return RT1W_ERR_DEVICE;
+    rt1w_stats st, sk;
+    memset(&st, 0, sizeof st);
+    rt1w_render_params ap = *p; /* the feature buffers of the pilot's samples, by the scene's own variant */
+    ap.flags = 0u; ap.spp = plan.pilot * plan.batch_spp;
+    if ((rc = render_aov_common(c, &ap, nullptr, d_aov, &sk)) < 0) return rc;
+    double kernel_ms = sk.kernel_ms;
+    rt1w_render_params bp = *p;
+    bp.flags |= RT1W_OUT_SUM;
+    bp.spp = plan.batch_spp;
+    bp.chunk = p->chunk ? p->chunk : (c->variant >= 2 ? 1u : rt1w_default_chunk(W, H, plan.batch_spp)); /* rt1w_scene_default_chunk of the whole frame */
+    bool first = true;
+    /* one batch of a rectangle whose pixels all hold m batches: render, merge */
+    auto batch = [&](uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, uint32_t m) -> int {
+        bp.x0 = x0; bp.y0 = y0; bp.tile_w = tw; bp.tile_h = th;
+        bp.sample_offset = p->sample_offset + m * plan.batch_spp;
+        rt1w_stats sb;
+        memset(&sb, 0, sizeof sb);
+        int r = render_common(c, &bp, c->d_batches, &sb);
+        if (r < 0) return r;
+        if (first) { st = sb; first = false; }
+        else { st.paths += sb.paths; st.segments += sb.segments; st.passes += sb.passes; }
+        kernel_ms += sb.kernel_ms;
+        if ((r = accum_merge_common(c, W, H, x0, y0, tw, th, plan.batch_spp, plan.flags, c->d_batches, d_aov, d_acc, &sk)) < 0) return r;
+        kernel_ms += sk.kernel_ms;
+        return RT1W_OK;
+    };
+    for (uint32_t b = 0; b < plan.pilot; ++b)
+        if ((rc = batch(0u, 0u, W, H, b)) < 0) return rc;
+    std::vector<uint32_t> m(ntiles, plan.pilot);
+    std::vector<double> err(ntiles);
+    uint32_t rounds = 0;
+    for (;;) {
+        if ((rc = accum_tile_error_common(c, W, H, plan.tile, d_acc, d_err, &sk)) < 0) return rc;
+        kernel_ms += sk.kernel_ms;
+        if (!hip_ok(hipMemcpy(err.data(), d_err, ntiles * sizeof(double), hipMemcpyDeviceToHost), "tile error copy")) return RT1W_ERR_DEVICE;
+        const std::vector<uint32_t> taken = rt_ad_select(plan, tiles_x, tiles_y, W, H, err.data(), m.data());
+        if (taken.empty()) break;
+        ++rounds;
+        for (const RtAdRun& r : rt_ad_group(plan, tiles_x, W, H, taken, m.data()))
+            if ((rc = batch(r.x0, r.y0, r.w, r.h, r.m)) < 0) return rc;
+        for (uint32_t t : taken) ++m[t];
+    }
+    if ((rc = accum_resolve_common(c, W, H, plan.batch_spp, d_acc, d_frame, d_var, d_spp, &sk)) < 0) return rc;
+    kernel_ms += sk.kernel_ms;
+    if (d) {
+        if ((rc = denoise_var_common(c, &dp, sigma_variance, d_frame, d_aov, d_var, d_frame, &sk)) < 0) return rc;
+        kernel_ms += sk.kernel_ms;
+    }
+    if (!hip_ok(hipMemcpy(out_rgb, d_frame, npix * 3 * sizeof(double), hipMemcpyDeviceToHost), "adaptive frame copy")) return RT1W_ERR_DEVICE;
+    if (out_spp && !hip_ok(hipMemcpy(out_spp, d_spp, npix * sizeof(double), hipMemcpyDeviceToHost), "adaptive count copy")) return RT1W_ERR_DEVICE;
+    if (stats) {
+        *stats = st;
+        stats->kernel_ms = kernel_ms;
+        stats->chunk = bp.chunk; stats->n_chunks = rounds;
+        stats->grid = sk.grid; stats->block = sk.block;
+        stats->total_ms = timer.ms();
+    }
+    return RT1W_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -431,5 +659,43 @@ int rt1w_render_denoised_var(rt1w_context* c, const rt1w_render_params* p, const
                              uint32_t max_specular, double max_fuzz, double* out_rgb, rt1w_stats* stats) {
     const AovDeep deep{max_specular, max_fuzz};
     return render_denoised_var(c, p, d, batches, sigma_variance, deep, out_rgb, stats);
+}
+int rt1w_accum_merge(rt1w_context* c, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h, uint32_t batch_spp,
+                     uint32_t flags, const double* tile_sums, const double* aov, double* acc, rt1w_stats* stats) {
+    return accum_merge(c, width, height, x0, y0, tile_w, tile_h, batch_spp, flags, tile_sums, aov, acc, true, stats);
+}
+int rt1w_accum_merge_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h,
+                            uint32_t batch_spp, uint32_t flags, const void* d_tile_sums, const void* d_aov, void* d_acc, rt1w_stats* stats) {
+    return accum_merge(c, width, height, x0, y0, tile_w, tile_h, batch_spp, flags, (const double*)d_tile_sums, (const double*)d_aov, (double*)d_acc, false, stats);
+}
+int rt1w_accum_resolve(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc, double* frame, double* var,
+                       double* spp, rt1w_stats* stats) {
+    return accum_resolve(c, width, height, batch_spp, acc, frame, var, spp, true, stats);
+}
+int rt1w_accum_resolve_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batch_spp, const void* d_acc, void* d_frame, void* d_var,
+                              void* d_spp, rt1w_stats* stats) {
+    return accum_resolve(c, width, height, batch_spp, (const double*)d_acc, (double*)d_frame, (double*)d_var, (double*)d_spp, false, stats);
+}
+int rt1w_accum_tile_error(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const double* acc, double* err, rt1w_stats* stats) {
+    return accum_tile_error(c, width, height, tile, acc, err, true, stats);
+}
+int rt1w_accum_tile_error_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const void* d_acc, void* d_err, rt1w_stats* stats) {
+    return accum_tile_error(c, width, height, tile, (const double*)d_acc, (double*)d_err, false, stats);
+}
+int rt1w_adaptive_select(const rt1w_adaptive_params* params, uint32_t n_tiles_x, uint32_t n_tiles_y, uint32_t width, uint32_t height, const double* err,
+                         const uint32_t* m_per_tile, uint32_t* out_tiles, uint32_t capacity) {
+    RtAdPlan plan;
+    if (const char* why = rt_ad_make_plan(params, &plan)) { set_error(why); return RT1W_ERR_INVALID; }
+    if (!rt_ad_frame_ok(width, height) || n_tiles_x != (width + plan.tile - 1u) / plan.tile || n_tiles_y != (height + plan.tile - 1u) / plan.tile) {
+        set_error("adaptive select: n_tiles_x / n_tiles_y must be ceil(width / tile), ceil(height / tile)"); return RT1W_ERR_INVALID;
+    }
+    if (!err || !m_per_tile || (!out_tiles && capacity)) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    const std::vector<uint32_t> taken = rt_ad_select(plan, n_tiles_x, n_tiles_y, width, height, err, m_per_tile);
+    for (size_t i = 0; i < taken.size() && i < capacity; ++i) out_tiles[i] = taken[i];
+    return (int)taken.size();
+}
+int rt1w_render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d, double sigma_variance,
+                         double* out_rgb, double* out_spp, rt1w_stats* stats) {
+    return render_adaptive(c, p, a, d, sigma_variance, out_rgb, out_spp, stats);
 }
 } /* extern "C" */

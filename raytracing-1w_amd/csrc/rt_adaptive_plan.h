@@ -1,0 +1,96 @@
+/* rt_adaptive_plan.h -- the plan of adaptive sampling (include/rt1w.h: rt1w_adaptive_params, rt1w_adaptive_select,
+ * rt1w_render_adaptive): the parameters with their defaults, one round's choice of tiles, and the grouping of the chosen tiles into
+ * rectangles.  Host code; rt1w_render_adaptive and rt1w_adaptive_select (features.hip) both run exactly this, so a host that composes
+ * the public entries itself makes the one call's choices. */
+#ifndef RT_ADAPTIVE_PLAN_H
+#define RT_ADAPTIVE_PLAN_H
+
+#include <algorithm>
+#include <vector>
+
+#include "rt1w.h"
+#include "rt_adaptive.h"
+
+/* the defaults, chosen with the CPU twins on the three scenes of tests/test_adaptive.py */
+#define RT_AD_DEFAULT_TILE 16u
+#define RT_AD_DEFAULT_BATCH_DIV 8u /* batch_spp = max(1, budget_spp / 8): with 4 pilot batches the pilot is half of the budget at any budget */
+#define RT_AD_DEFAULT_PILOT 4u
+#define RT_AD_DEFAULT_BUDGET 64u
+#define RT_AD_DEFAULT_MAX_FACTOR 8u /* max_spp = 8 x budget_spp */
+#define RT_AD_DEFAULT_ROUND_SHARE 0.25
+
+/* rt1w_adaptive_params with the defaults filled in */
+struct RtAdPlan {
+    uint32_t tile, batch_spp, pilot, budget_spp, max_spp, flags;
+    double target_error, round_share;
+};
+
+/* nullptr: accepted, *out filled; else why not (RT1W_ERR_INVALID) */
+inline const char* rt_ad_make_plan(const rt1w_adaptive_params* a, RtAdPlan* out) {
+    if (!a) return "adaptive: null parameters";
+    if (a->size != (uint32_t)sizeof(rt1w_adaptive_params)) return "adaptive: rt1w_adaptive_params.size is not this library's sizeof(rt1w_adaptive_params)";
+    RtAdPlan p;
+    p.tile = a->tile ? a->tile : RT_AD_DEFAULT_TILE;
+    p.budget_spp = a->budget_spp ? a->budget_spp : RT_AD_DEFAULT_BUDGET;
+    p.batch_spp = a->batch_spp ? a->batch_spp : std::max(1u, p.budget_spp / RT_AD_DEFAULT_BATCH_DIV);
+    p.pilot = a->pilot_batches ? a->pilot_batches : RT_AD_DEFAULT_PILOT;
+    p.flags = a->flags;
+    p.target_error = a->target_error;
+    p.round_share = a->round_share == 0.0 ? RT_AD_DEFAULT_ROUND_SHARE : a->round_share;
+    if (!rt_ad_tile_ok(p.tile)) return "adaptive: tile must be a multiple of 16 in 16 .. 256";
+    if (p.pilot < 2u || p.pilot > 16u) return "adaptive: pilot_batches must be 2 .. 16";
+    const unsigned long long pilot_spp = (unsigned long long)p.pilot * p.batch_spp;
+    const unsigned long long mx = a->max_spp ? a->max_spp : std::min<unsigned long long>((unsigned long long)p.budget_spp * RT_AD_DEFAULT_MAX_FACTOR, 0xFFFFFFFFull);
+    if (pilot_spp > 0xFFFFFFFFull || mx < pilot_spp) return "adaptive: max_spp is less than the pilot's pilot_batches * batch_spp samples";
+    if (p.budget_spp < pilot_spp) return "adaptive: budget_spp is less than the pilot's pilot_batches * batch_spp samples";
+    p.max_spp = (uint32_t)mx;
+    if (!(p.target_error >= 0.0) || !rt_dn_finite(p.target_error)) return "adaptive: target_error must be finite and >= 0";
+    if (!(p.round_share > 0.0) || !(p.round_share <= 1.0)) return "adaptive: round_share must be in (0, 1] (0 = default)";
+    if (p.flags & ~RT1W_DENOISE_KEEP_ALBEDO) return "adaptive: unknown flag (flags: 0 or RT1W_DENOISE_KEEP_ALBEDO)";
+    *out = p;
+    return nullptr;
+}
+
+/* One round.  err and m by tile, row-major over tiles_x x tiles_y tiles of a w x h frame; the tiles taken, in the order taken */
+inline std::vector<uint32_t> rt_ad_select(const RtAdPlan& p, uint32_t tiles_x, uint32_t tiles_y, uint32_t w, uint32_t h, const double* err,
+                                          const uint32_t* m) {
+    const uint32_t n = tiles_x * tiles_y;
+    const double frame_px = (double)w * (double)h;
+    const double budget = (double)p.budget_spp * frame_px, share = p.round_share * frame_px;
+    double spent = 0.0; /* pixel-samples so far: whole numbers below 2^53, exact */
+    for (uint32_t t = 0; t < n; ++t) spent += (double)m[t] * (double)p.batch_spp * (double)rt_ad_tile_pixels(w, h, p.tile, t % tiles_x, t / tiles_x);
+    std::vector<uint32_t> cand;
+    for (uint32_t t = 0; t < n; ++t)
+        if (err[t] > p.target_error && ((unsigned long long)m[t] + 1u) * p.batch_spp <= p.max_spp) cand.push_back(t);
+    std::stable_sort(cand.begin(), cand.end(), [&](uint32_t a, uint32_t b) { return err[a] > err[b]; }); /* ties: tile index ascending */
+    std::vector<uint32_t> taken;
+    double round_px = 0.0;
+    for (uint32_t t : cand) {
+        const double px = (double)rt_ad_tile_pixels(w, h, p.tile, t % tiles_x, t / tiles_x);
+        if (!taken.empty() && round_px + px > share) break;
+        if (spent + px * (double)p.batch_spp > budget) break;
+        taken.push_back(t);
+        round_px += px;
+        spent += px * (double)p.batch_spp;
+    }
+    return taken;
+}
+
+/* a run of taken tiles that are adjacent in one tile row and have equal m: rendered as one rectangle, merged by one rt1w_accum_merge */
+struct RtAdRun { uint32_t x0, y0, w, h, m; };
+inline std::vector<RtAdRun> rt_ad_group(const RtAdPlan& p, uint32_t tiles_x, uint32_t w, uint32_t h, std::vector<uint32_t> taken, const uint32_t* m) {
+    std::sort(taken.begin(), taken.end());
+    std::vector<RtAdRun> runs;
+    uint32_t prev = 0;
+    for (size_t i = 0; i < taken.size(); ++i) {
+        const uint32_t t = taken[i], tx = t % tiles_x, ty = t / tiles_x;
+        const uint32_t x0 = tx * p.tile, y0 = ty * p.tile;
+        const uint32_t tw = std::min(p.tile, w - x0), th = std::min(p.tile, h - y0);
+        if (i > 0 && t == prev + 1u && tx != 0u && m[t] == runs.back().m) runs.back().w += tw;
+        else runs.push_back(RtAdRun{x0, y0, tw, th, m[t]});
+        prev = t;
+    }
+    return runs;
+}
+
+#endif

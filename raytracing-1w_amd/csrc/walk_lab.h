@@ -52,6 +52,12 @@ int rt1w_lab_denoise_var_host(const rt1w_denoise_params* p, const double* frame,
 /* how rt1w_render_denoised_var takes its `batches` and `sigma_variance` for a render of `spp` samples: out = {batches K, samples per batch n},
  * or RT1W_ERR_INVALID exactly where that entry refuses them (K outside 2 .. 16, spp not a multiple of K, sigma negative or not finite) */
 int rt1w_lab_denoised_var_split(uint32_t spp, uint32_t batches, double sigma_variance, uint32_t out[2]);
+/* CPU twins of rt1w_accum_merge, rt1w_accum_resolve and rt1w_accum_tile_error (adaptive_host.cpp: rt_adaptive.h built for the host): the
+ * same accumulator, the same frame / var / spp and the same tile errors from host buffers, no GPU; RT1W_ERR_INVALID as the device entries */
+int rt1w_lab_accum_merge_host(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h, uint32_t batch_spp,
+                              uint32_t flags, const double* tile_sums, const double* aov, double* acc);
+int rt1w_lab_accum_resolve_host(uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc, double* frame, double* var, double* spp);
+int rt1w_lab_tile_error_host(uint32_t width, uint32_t height, uint32_t tile, const double* acc, double* err);
 /* the two functions the filters build their weights from (rt_denoise.h), on their own: out[i] = rt_dn_falloff(x[i]) (fn 0; e may be
  * null) or rt_dn_powi(x[i], e[i]) (fn 1).  device 0: the host build of denoise_host.cpp, no GPU; device 1: one lane per element on
  * GPU 0 (f32_exact.hip).  RT1W_ERR_INVALID for anything else, null pointers or n = 0 */

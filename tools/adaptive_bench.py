@@ -1,0 +1,174 @@
+#!/usr/bin/env python3
+"""Cost of adaptive sampling (rt1w_render_adaptive, csrc/adaptive.hip + the plan in csrc/rt_adaptive_plan.h) against one render of the same
+samples.
+
+For C3 (Cornell 600 x 600) and C4 (final_scene 800 x 800) at budgets of 64 and 256 mean samples per pixel, default parameters, one child
+process per case:
+  * the whole call rt1w_render_adaptive (median total_ms of `--reps` calls after one warm-up), its rounds and render launches;
+  * rt1w_render of the same total samples (spp = the budget: the call spends it to within one tile), in the same process and, with
+    `--parent-root DIR` (a built checkout of the parent commit), in a child of its own that imports that checkout's package and so runs
+    the parent commit's librt1w.so: the comparison the feature answers to;
+  * the difference in beauty samples per pixel: (adaptive - uniform) / (uniform / spp);
+  * the split of the call, from one composition of the public device entries whose own timers are summed by kind: the render launches
+    (total_ms of every rt1w_render_device, kernel_ms alongside), the merge and tile-error kernels (total_ms and kernel_ms), and the
+    per-round device->host copy of the tile errors (host clock around the copy).
+Writes one JSON file (default profiles/adaptive_bench.json).  Times are wall-clock medians of a few calls on a shared machine: read them
+to two digits.
+
+usage: python3 tools/adaptive_bench.py [--out FILE] [--reps N] [--parent-root BUILT-CHECKOUT-OF-THE-PARENT]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CONFIGS = [("c3", 5, 600, 600), ("c4", 7, 800, 800)]
+BUDGETS = (64, 256)
+TILE, PILOT, SHARE, BATCH_DIV, MAX_FACTOR = 16, 4, 0.25, 8, 8   # the defaults of rt1w_adaptive_params, spelled out for the composition
+
+
+def _rt():
+    import importlib
+    sys.path.insert(0, os.environ.get("ADAPTIVE_BENCH_ROOT") or ROOT)
+    return importlib.import_module("raytracing-1w_amd")
+
+
+def child_uniform(arm, W, H, spp, reps):
+    rt = _rt()
+    ctx = rt.Context(rt.Scene.reference(arm, build_seed=1), 0)
+    tot, ker = [], []
+    for i in range(1 + reps):
+        _, st = ctx.render(W, H, spp)
+        if i:
+            tot.append(st["total_ms"]); ker.append(st["kernel_ms"])
+    ctx.close()
+    print("ADJSON " + json.dumps({"total_ms": tot, "kernel_ms": ker, "lib": rt.LIB_PATH}), flush=True)
+
+
+def _runs(taken, m, tx_n, W, H):
+    runs, prev = [], None
+    for t in sorted(taken):
+        tx, ty = t % tx_n, t // tx_n
+        x0, y0 = tx * TILE, ty * TILE
+        tw, th, mt = min(TILE, W - x0), min(TILE, H - y0), int(m.flat[t])
+        if prev is not None and t == prev + 1 and tx != 0 and runs[-1][4] == mt:
+            runs[-1][2] += tw
+        else:
+            runs.append([x0, y0, tw, th, mt])
+        prev = t
+    return runs
+
+
+def child_adaptive(arm, W, H, budget, reps):
+    import numpy as np
+    rt = _rt()
+    sc = rt.Scene.reference(arm, build_seed=1)
+    ctx = rt.Context(sc, 0)
+    ad = dict(budget_spp=budget)
+    calls = []
+    for i in range(1 + reps):
+        _, spp, st = ctx.render_adaptive(W, H, adaptive=ad, with_stats=True)
+        if i:
+            calls.append(st)
+    # the split: the same plan over the public device entries, their own timers summed by kind
+    hip = C.CDLL("libamdhip64.so")
+
+    def alloc(nbytes):
+        p = C.c_void_p()
+        assert hip.hipMalloc(C.byref(p), C.c_size_t(nbytes)) == 0
+        return p.value
+    n = max(1, budget // BATCH_DIV)
+    full = dict(tile=TILE, batch_spp=n, pilot_batches=PILOT, budget_spp=budget, max_spp=MAX_FACTOR * budget, round_share=SHARE)
+    npix = W * H
+    tx_n, ty_n = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
+    chunk = sc.default_chunk(W, H, n)
+    d_aov, d_sums, d_acc, d_err = alloc(npix * 64), alloc(npix * 24), alloc(npix * 64), alloc(tx_n * ty_n * 8)
+    assert hip.hipMemset(C.c_void_p(d_acc), 0, C.c_size_t(npix * 64)) == 0
+    ctx.render_aov_device(d_aov, W, H, PILOT * n)
+    part = {k: 0.0 for k in ("render_total_ms", "render_kernel_ms", "merge_total_ms", "merge_kernel_ms", "error_total_ms", "error_kernel_ms", "copy_ms")}
+    launches = 0
+
+    def batch(rect, mt):
+        nonlocal launches
+        s = ctx.render_device(d_sums, W, H, n, tile=tuple(rect), sample_offset=mt * n, chunk=chunk, out_sum=True)
+        g = ctx.accum_merge_device(d_acc, d_sums, d_aov, W, H, tuple(rect), n)
+        part["render_total_ms"] += s["total_ms"]; part["render_kernel_ms"] += s["kernel_ms"]
+        part["merge_total_ms"] += g["total_ms"]; part["merge_kernel_ms"] += g["kernel_ms"]
+        launches += 1
+    for b in range(PILOT):
+        batch((0, 0, W, H), b)
+    m = np.full((ty_n, tx_n), PILOT, dtype=np.uint32)
+    err = np.empty((ty_n, tx_n))
+    rounds = 0
+    while True:
+        e = ctx.accum_tile_error_device(d_acc, d_err, W, H, TILE)
+        part["error_total_ms"] += e["total_ms"]; part["error_kernel_ms"] += e["kernel_ms"]
+        t0 = time.perf_counter()
+        assert hip.hipMemcpy(err.ctypes.data_as(C.c_void_p), C.c_void_p(d_err), C.c_size_t(err.nbytes), 2) == 0
+        part["copy_ms"] += (time.perf_counter() - t0) * 1e3
+        taken = rt.adaptive_select(W, H, err, m, **full)
+        if not taken:
+            break
+        rounds += 1
+        for r in _runs(taken, m, tx_n, W, H):
+            batch(r[:4], r[4])
+        for t in taken:
+            m.flat[t] += 1
+    assert rounds == calls[-1]["n_chunks"] and launches <= calls[-1]["passes"], "the composition is not the call's plan"
+    for p in (d_aov, d_sums, d_acc, d_err):
+        hip.hipFree(C.c_void_p(p))
+    ctx.close()
+    print("ADJSON " + json.dumps({"total_ms": [c["total_ms"] for c in calls], "kernel_ms": [c["kernel_ms"] for c in calls], "rounds": rounds,
+                                  "launches": launches, "passes": calls[-1]["passes"], "spent_spp": float(spp.mean()), "max_spp": float(spp.max()),
+                                  "min_spp": float(spp.min()), "split": part}), flush=True)
+
+
+def run_child(args, root=None):
+    env = dict(os.environ)
+    if root:
+        env["ADAPTIVE_BENCH_ROOT"] = os.path.abspath(root)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__)] + [str(a) for a in args], env=env, capture_output=True, text=True, timeout=900)
+    for line in out.stdout.splitlines():
+        if line.startswith("ADJSON "):
+            return json.loads(line[7:])
+    raise RuntimeError(f"child {args} failed:\n{out.stdout[-2000:]}\n{out.stderr[-2000:]}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "adaptive_bench.json"))
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--parent-root", default=None)
+    ap.add_argument("--child", nargs="*")
+    a = ap.parse_args()
+    if a.child:
+        kind, arm, W, H, n, reps = a.child[0], *map(int, a.child[1:])
+        return (child_uniform if kind == "uniform" else child_adaptive)(arm, W, H, n, reps)
+    rows = []
+    for name, arm, W, H in CONFIGS:
+        for budget in BUDGETS:
+            ad = run_child(["--child", "adaptive", arm, W, H, budget, a.reps])
+            un = run_child(["--child", "uniform", arm, W, H, budget, a.reps])
+            par = run_child(["--child", "uniform", arm, W, H, budget, a.reps], root=a.parent_root) if a.parent_root else None
+            base = statistics.median((par or un)["total_ms"])
+            call = statistics.median(ad["total_ms"])
+            row = {"config": name, "arm": arm, "width": W, "height": H, "budget_spp": budget, "adaptive": ad, "uniform_this_library": un,
+                   "uniform_parent_library": par, "adaptive_total_ms": call, "uniform_total_ms": base,
+                   "baseline": "parent library" if par else "this library",
+                   "extra_beauty_spp": (call - base) / (base / budget)}
+            print(f"{name} budget {budget}: adaptive {call:.1f} ms ({ad['rounds']} rounds, {ad['launches']} launches), uniform {base:.1f} ms, "
+                  f"+{row['extra_beauty_spp']:.1f} beauty spp; split {ad['split']}", flush=True)
+            rows.append(row)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump({"tool": "tools/adaptive_bench.py", "reps": a.reps, "rows": rows}, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
