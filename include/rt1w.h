@@ -256,6 +256,27 @@ typedef struct rt1w_stats {
     uint32_t reserved;     /* 0 */
 } rt1w_stats;
 
+/* ---- a list of tiles in one launch ----
+ * One record of the list, 16 bytes (not one of rt1w_abi_sizeof's: bindings assert the 16 themselves). */
+typedef struct rt1w_tile { uint32_t x0, y0, sample_offset, reserved; } rt1w_tile;   /* 16 bytes, reserved = 0 */
+/* Renders n_tiles square tiles of side `tile` (a multiple of 16 in 16 .. 256; x0 and y0 multiples of it, inside the p->width x p->height
+ * frame; n_tiles 1 .. 2^20) by ONE launch of the trace kernel per sample pass.  `tiles` is HOST memory in both forms (uploaded into a
+ * context buffer that grows on demand).  From p: width, height, spp (the same for every tile), max_depth, global_seed, chunk, partial_mib,
+ * flags; p->x0, y0, tile_w, tile_h are ignored; p->sample_offset is added to every tile's own (a sum + spp beyond 2^32 - 1:
+ * RT1W_ERR_INVALID).  chunk 0 means rt1w_scene_default_chunk(scene, width, height, spp) of the WHOLE frame.
+ * out: double[n_tiles][tile][tile][3], tile k's row 0 = image row y0_k; raw sums with RT1W_OUT_SUM, else into_sampled means.  A pixel of
+ * a tile beyond the frame's right or top edge is never traced and comes back as +0.0.
+ * CONTRACT: tile k's pixels inside the frame are bit-identical to rt1w_render_device of the rectangle (x0_k, y0_k, min(tile, width - x0_k),
+ * min(tile, height - y0_k)) with the same spp and seed, the tile's absolute sample offset and the same chunk passed explicitly.  The order
+ * of the list, repeats of a tile with other offsets and partial_mib do not change a bit.
+ * Flags: 0, RT1W_OUT_SUM, RT1W_GENERIC (a no-op: the tile entries always run the generic kernels -- the scene-specialised ones have no
+ * tile form and render the same bits); any other flag, interleaved strips or a non-zero `reserved`: RT1W_ERR_INVALID;
+ * RT1W_PRECISION_F32: RT1W_ERR_UNSUPPORTED.
+ * stats: paths = pixels inside the frame x spp; segments = rays traced (the sum over the per-rectangle renders); passes = launches of the
+ * trace kernel; variant / sorted / grid / block / chunk / n_chunks as rt1w_render with RT1W_GENERIC. */
+int rt1w_render_tiles(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out, rt1w_stats* stats);
+int rt1w_render_tiles_device(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, void* d_out, rt1w_stats* stats);
+
 /* default work-item size for a (tile, spp): deterministic, documented in DESIGN.md.  This is the scene-independent rule (what the
  * small scenes' reordering kernels run with); see rt1w_scene_default_chunk for what a render of a given scene uses */
 uint32_t rt1w_default_chunk(uint32_t tile_w, uint32_t tile_h, uint32_t spp);
@@ -520,6 +541,17 @@ int rt1w_accum_resolve_device(rt1w_context* c, uint32_t width, uint32_t height, 
 int rt1w_accum_tile_error(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const double* acc, double* err, rt1w_stats* stats);
 int rt1w_accum_tile_error_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const void* d_acc, void* d_err, rt1w_stats* stats);
 
+/* rt1w_accum_merge for a LIST of square tiles in one launch (the tiles of rt1w_render_tiles: `tile` a multiple of 16 in 16 .. 256, x0 and y0
+ * multiples of it inside the frame, reserved 0, n_tiles 1 .. 2^20; sample_offset is ignored here).  tile_sums double[n_tiles][tile][tile][3]
+ * as rt1w_render_tiles writes them with RT1W_OUT_SUM; a pixel of a tile beyond the frame's edge is skipped.  The tiles of one call are
+ * disjoint -- a tile named twice is RT1W_ERR_INVALID (two lanes would update one record) -- so the result is bit-identical to n_tiles calls
+ * of rt1w_accum_merge on the clipped rectangles, in any order.  One lane per pixel, 16 x 16 pixels per workgroup, grid = n_tiles x
+ * (tile / 16)^2; the list is HOST memory in both forms.  CPU twin: rt1w_lab_accum_merge_tiles_host (librt1w_lab.so). */
+int rt1w_accum_merge_tiles(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t batch_spp,
+                           uint32_t flags, const double* tile_sums, const double* aov, double* acc, rt1w_stats* stats);
+int rt1w_accum_merge_tiles_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles,
+                                  uint32_t batch_spp, uint32_t flags, const void* d_tile_sums, const void* d_aov, void* d_acc, rt1w_stats* stats);
+
 /* The plan.  Zero means the default for every member but `size`, which is sizeof(rt1w_adaptive_params) as the caller compiled it (anything
  * else: RT1W_ERR_INVALID; the struct is not one of rt1w_abi_sizeof's).
  *   Pilot.   pilot_batches batches of batch_spp samples on the whole frame.
@@ -533,7 +565,13 @@ int rt1w_accum_tile_error_device(rt1w_context* c, uint32_t width, uint32_t heigh
  *            rt1w_scene_default_chunk(scene, width, height, batch_spp) of the WHOLE frame, passed explicitly: with that the bits do not
  *            depend on how tiles are grouped into launches.
  *   Launches. Taken tiles that are adjacent in one tile row and have equal m are rendered as one rectangle and merged by one
- *            rt1w_accum_merge (bits-neutral by the above). */
+ *            rt1w_accum_merge (bits-neutral by the above).
+ *   One launch per round.  With RT1W_ADAPTIVE_ONE_LAUNCH in `flags` every ROUND is instead one rt1w_render_tiles_device of all its taken
+ *            tiles (each with sample_offset = m * batch_spp, RT1W_OUT_SUM, the same spp and chunk) and one rt1w_accum_merge_tiles_device;
+ *            the pilot stays whole-frame.  Frame, spp map, paths, segments and n_chunks are the bits of the call without the flag;
+ *            passes falls to the pilot's launches + one per round (times its sample passes).  The tile entries run the generic
+ *            kernels, so p->flags must then be 0 or RT1W_GENERIC.  rt1w_adaptive_select accepts the flag and ignores it. */
+#define RT1W_ADAPTIVE_ONE_LAUNCH 0x100u
 typedef struct rt1w_adaptive_params {
     uint32_t size;           /* sizeof(rt1w_adaptive_params) */
     uint32_t tile;           /* side of the square tiles, a multiple of 16 in 16 .. 256; 0 = 16 */
@@ -543,7 +581,7 @@ typedef struct rt1w_adaptive_params {
     uint32_t max_spp;        /* most samples of one pixel, at least the pilot's; 0 = 8 * budget_spp */
     double target_error;     /* tiles at or below it get no more samples; finite, >= 0; 0 (default): the budget alone decides */
     double round_share;      /* share of the frame's pixels one round may take, in (0, 1]; 0 = 1/4 */
-    uint32_t flags;          /* 0 or RT1W_DENOISE_KEEP_ALBEDO: how the merges demodulate */
+    uint32_t flags;          /* RT1W_DENOISE_KEEP_ALBEDO: how the merges demodulate; RT1W_ADAPTIVE_ONE_LAUNCH: one render launch per round */
 } rt1w_adaptive_params;
 /* One round of the plan, on the host, without a GPU or a context: err and m_per_tile are [n_tiles_y][n_tiles_x] of a width x height frame
  * (n_tiles_x = ceil(width / tile), likewise y: RT1W_ERR_INVALID otherwise); the pixel-samples spent so far are those m_per_tile says.

@@ -56,6 +56,7 @@ WAVEFRONT = 16  # big scenes: path state queued in HBM, trace / shade kernels pe
 SPECIALISE_CACHED_ONLY = 1
 AOV_CHANNELS = 8  # rt1w_render_aov: albedo rgb, normal xyz, depth, coverage per pixel
 DENOISE_KEEP_ALBEDO = 1  # rt1w_denoise: no albedo demodulation
+ADAPTIVE_ONE_LAUNCH = 0x100  # rt1w_adaptive_params.flags: every round is one rt1w_render_tiles launch and one rt1w_accum_merge_tiles
 
 
 class Rt1wError(RuntimeError):
@@ -185,14 +186,32 @@ class AdaptiveParams(C.Structure):
 
 
 def adaptive_params(tile=0, batch_spp=0, pilot_batches=0, budget_spp=0, max_spp=0, target_error=0.0, round_share=0.0, keep_albedo=False, flags=0,
-                    size=None):
+                    size=None, one_launch=False):
     return AdaptiveParams(C.sizeof(AdaptiveParams) if size is None else size, tile, batch_spp, pilot_batches, budget_spp, max_spp, target_error,
-                          round_share, flags | (DENOISE_KEEP_ALBEDO if keep_albedo else 0))
+                          round_share, flags | (DENOISE_KEEP_ALBEDO if keep_albedo else 0) | (ADAPTIVE_ONE_LAUNCH if one_launch else 0))
+
+
+class Tile(C.Structure):
+    """rt1w_tile (include/rt1w.h): one square tile of a list, 16 bytes; reserved = 0."""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("sample_offset", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(Tile) == 16, "rt1w_tile is 16 bytes (include/rt1w.h); it is not one of rt1w_abi_sizeof's"
+
+
+def _tile_list(tiles):
+    """tiles: Tile objects or (x0, y0[, sample_offset[, reserved]]) tuples -> (ctypes array, n)"""
+    rec = [t if isinstance(t, Tile) else Tile(*t) for t in tiles]
+    return (Tile * max(len(rec), 1))(*rec), len(rec)
 
 
 _U = C.c_uint32
 _sig("rt1w_accum_merge", C.c_int, _P, _U, _U, _U, _U, _U, _U, _U, _U, _P, _P, _P, C.POINTER(Stats))
 _sig("rt1w_accum_merge_device", C.c_int, _P, _U, _U, _U, _U, _U, _U, _U, _U, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_accum_merge_tiles", C.c_int, _P, _U, _U, _U, _P, _U, _U, _U, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_accum_merge_tiles_device", C.c_int, _P, _U, _U, _U, _P, _U, _U, _U, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_render_tiles", C.c_int, _P, C.POINTER(RenderParams), _U, _P, _U, _P, C.POINTER(Stats))
+_sig("rt1w_render_tiles_device", C.c_int, _P, C.POINTER(RenderParams), _U, _P, _U, _P, C.POINTER(Stats))
 _sig("rt1w_accum_resolve", C.c_int, _P, _U, _U, _U, _P, _P, _P, _P, C.POINTER(Stats))
 _sig("rt1w_accum_resolve_device", C.c_int, _P, _U, _U, _U, _P, _P, _P, _P, C.POINTER(Stats))
 _sig("rt1w_accum_tile_error", C.c_int, _P, _U, _U, _U, _P, _P, C.POINTER(Stats))
@@ -275,6 +294,14 @@ def _merge_args(acc, tile_sums, aov, x0, y0):
     if s.ndim != 3 or s.shape[2] != 3 or g.shape != a.shape[:2] + (AOV_CHANNELS,):
         raise ValueError("tile_sums must be [tile_h, tile_w, 3] and aov [h, w, 8]")
     return a, s, g, (a.shape[1], a.shape[0], x0, y0, s.shape[1], s.shape[0])
+
+
+def _merge_tiles_args(acc, tile_sums, aov, tile, tiles):
+    a = _accum_of(acc).copy()
+    s, g = (np.ascontiguousarray(x, dtype=np.float64) for x in (tile_sums, aov))
+    if s.shape != (len(tiles), tile, tile, 3) or g.shape != a.shape[:2] + (AOV_CHANNELS,):
+        raise ValueError("tile_sums must be [n_tiles, tile, tile, 3] and aov [h, w, 8]")
+    return a, s, g
 
 
 def _tiles_of(width, height, tile):
@@ -557,6 +584,29 @@ class Context:
         _ck(_lib.rt1w_render_device(self._h, C.byref(p), C.c_void_p(d_ptr), C.byref(st)))
         return _stats_dict(st)
 
+    def render_tiles(self, width, height, spp, tile, tiles, max_depth=50, sample_offset=0, global_seed=0, chunk=0, out_sum=False, generic=False,
+                     partial_mib=0, flags=0, strips=None, f32=False):
+        """A list of square tiles of side `tile` in one launch (rt1w_render_tiles): `tiles` = Tile objects or (x0, y0, sample_offset)
+        tuples.  Returns (float64 [n, tile, tile, 3], stats); tile k's row 0 = image row y0_k, pixels beyond the frame's edge are +0.0."""
+        p = self._params(width, height, spp, max_depth, None, sample_offset, global_seed, chunk, out_sum, generic=generic, partial_mib=partial_mib,
+                         strips=strips, f32=f32)
+        p.flags |= flags
+        rec, n = _tile_list(tiles)
+        out = np.empty((n, tile, tile, 3), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_tiles(self._h, C.byref(p), tile, rec, n, out.ctypes.data_as(_P), C.byref(st)))
+        return out, _stats_dict(st)
+
+    def render_tiles_device(self, d_ptr, width, height, spp, tile, tiles, max_depth=50, sample_offset=0, global_seed=0, chunk=0, out_sum=False,
+                            generic=False, partial_mib=0, flags=0):
+        """Same, into device memory `d_ptr` (int address) of n * tile * tile * 3 doubles; the list itself is host memory.  Returns the stats."""
+        p = self._params(width, height, spp, max_depth, None, sample_offset, global_seed, chunk, out_sum, generic=generic, partial_mib=partial_mib)
+        p.flags |= flags
+        rec, n = _tile_list(tiles)
+        st = Stats()
+        _ck(_lib.rt1w_render_tiles_device(self._h, C.byref(p), tile, rec, n, C.c_void_p(d_ptr), C.byref(st)))
+        return _stats_dict(st)
+
     # deep: () for the first-hit entries, (max_specular, max_fuzz) for the deep ones
     def _render_aov(self, deep, width, height, spp, tile, sample_offset, global_seed, variant, strips, with_stats):
         p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
@@ -701,6 +751,24 @@ class Context:
         st = Stats()
         _ck(_lib.rt1w_accum_merge_device(self._h, width, height, *rect, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, C.c_void_p(d_tile_sums),
                                          C.c_void_p(d_aov), C.c_void_p(d_acc), C.byref(st)))
+        return _stats_dict(st)
+
+    def accum_merge_tiles(self, acc, tile_sums, aov, batch_spp, tile, tiles, keep_albedo=False, with_stats=False):
+        """One rendered batch of a LIST of square tiles into an accumulator in one launch (rt1w_accum_merge_tiles): `tile_sums`
+        [n, tile, tile, 3] as render_tiles(out_sum=True) returns them, `tiles` its list.  Returns the merged accumulator (a new array)."""
+        a, s, g = _merge_tiles_args(acc, tile_sums, aov, tile, tiles)
+        rec, n = _tile_list(tiles)
+        st = Stats()
+        _ck(_lib.rt1w_accum_merge_tiles(self._h, a.shape[1], a.shape[0], tile, rec, n, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0,
+                                        s.ctypes.data_as(_P), g.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(st)))
+        return (a, _stats_dict(st)) if with_stats else a
+
+    def accum_merge_tiles_device(self, d_acc, d_tile_sums, d_aov, width, height, tile, tiles, batch_spp, keep_albedo=False):
+        """Same on device memory (int addresses); the list itself is host memory.  Returns the stats dict."""
+        rec, n = _tile_list(tiles)
+        st = Stats()
+        _ck(_lib.rt1w_accum_merge_tiles_device(self._h, width, height, tile, rec, n, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0,
+                                               C.c_void_p(d_tile_sums), C.c_void_p(d_aov), C.c_void_p(d_acc), C.byref(st)))
         return _stats_dict(st)
 
     def accum_resolve(self, acc, batch_spp, with_stats=False):
@@ -892,6 +960,23 @@ def accum_merge_host(acc, tile_sums, aov, batch_spp, x0=0, y0=0, keep_albedo=Fal
     rc = fn(*rect, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, s.ctypes.data_as(_P), g.ctypes.data_as(_P), a.ctypes.data_as(_P))
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_accum_merge_host")
+    return a
+
+
+def accum_merge_tiles_host(acc, tile_sums, aov, batch_spp, tile, tiles, keep_albedo=False):
+    """CPU twin of Context.accum_merge_tiles (librt1w_lab.so: rt1w_lab_accum_merge_tiles_host)."""
+    fn = load_lab().rt1w_lab_accum_merge_tiles_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32] * 3 + [_P] + [C.c_uint32] * 3 + [_P, _P, _P]
+    rec, n = _tile_list(tiles)
+    s, g = (np.ascontiguousarray(x, dtype=np.float64) for x in (tile_sums, aov))
+    a = _accum_of(acc).copy()
+    if n and (s.shape != (n, tile, tile, 3) or g.shape != a.shape[:2] + (AOV_CHANNELS,)):
+        raise ValueError("tile_sums must be [n_tiles, tile, tile, 3] and aov [h, w, 8]")
+    rc = fn(a.shape[1], a.shape[0], tile, rec, n, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, s.ctypes.data_as(_P), g.ctypes.data_as(_P),
+            a.ctypes.data_as(_P))
+    if rc != 0:
+        raise Rt1wError(rc, "rt1w_lab_accum_merge_tiles_host")
     return a
 
 

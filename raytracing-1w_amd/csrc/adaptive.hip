@@ -1,5 +1,6 @@
 /* adaptive.hip -- the kernels of rt1w_accum_merge, rt1w_accum_resolve and rt1w_accum_tile_error (include/rt1w.h) over rt_adaptive.h.
  *
+ * rt1w_accum_merge_tiles is the merge over a list of square tiles in one launch.
  * A unit of its own, inside its own namespace (the pattern of denoise_var.hip), so that no other code object moves with it.  The host
  * half is in features.hip, which calls the three launchers below.
  *
@@ -39,6 +40,19 @@ __global__ __launch_bounds__(RT_AD_WG) void rt_ad_merge_kernel(uint32_t w, uint3
     const unsigned long long i = (unsigned long long)(y0 + ry) * w + (x0 + rx);
     const unsigned long long t = (unsigned long long)ry * tw + rx;
     rt_ad_merge_pixel(batch_spp, keep_albedo != 0u, sums + t * 3u, aov + i * 8u, acc + i * RT_AD_RECORD);
+}
+
+/* rt1w_accum_merge_tiles: sums[n][tile][tile][3], aov[h][w][8] -> acc[h][w][8]; (tile / 16)^2 workgroups per tile of the list, tile after
+ * tile.  A workgroup's tile follows from blockIdx alone, so its record rec[k] = {x0, y0, -, -} is read wave-uniformly. */
+__global__ __launch_bounds__(RT_AD_WG) void rt_ad_merge_tiles_kernel(uint32_t w, uint32_t h, uint32_t tile, const uint32_t* __restrict__ rec, uint32_t batch_spp,
+                                                                      uint32_t keep_albedo, const double* __restrict__ sums, const double* __restrict__ aov,
+                                                                      double* __restrict__ acc) {
+    const uint32_t bw = tile / RT_AD_BLOCK;
+    const uint32_t k = blockIdx.x / (bw * bw), b = blockIdx.x % (bw * bw);
+    const uint32_t x0 = rec[(size_t)k * 4u], y0 = rec[(size_t)k * 4u + 1u];
+    uint32_t lx, ly;
+    rt_ad_lane_xy(lx, ly);
+    rt_ad_merge_tiles_pixel(w, h, tile, x0, y0, k, (b % bw) * RT_AD_BLOCK + lx, (b / bw) * RT_AD_BLOCK + ly, batch_spp, keep_albedo != 0u, sums, aov, acc);
 }
 
 /* acc[h][w][8] -> frame[h][w][3], var[h][w], spp[h][w] */
@@ -99,6 +113,16 @@ extern "C" int rt1w_internal_accum_merge_launch(uint32_t w, uint32_t h, uint32_t
     const unsigned grid = ((tw + RT_AD_BLOCK - 1u) / RT_AD_BLOCK) * ((th + RT_AD_BLOCK - 1u) / RT_AD_BLOCK);
     launch[0] = grid; launch[1] = RT_AD_WG;
     hipLaunchKernelGGL(rt_ad_merge_kernel, dim3(grid), dim3(RT_AD_WG), 0, stream, w, x0, y0, tw, th, batch_spp, flags & RT_DN_KEEP_ALBEDO, sums, aov, acc);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+/* the list itself (alignment, frame, no tile twice) is the caller's to check (rt_adaptive_plan.h: rt_ad_tiles_check); rec is device memory */
+extern "C" int rt1w_internal_accum_merge_tiles_launch(uint32_t w, uint32_t h, uint32_t tile, const uint32_t* rec, uint32_t n, uint32_t batch_spp, uint32_t flags,
+                                                      const double* sums, const double* aov, double* acc, hipStream_t stream, unsigned launch[2]) {
+    using namespace rtad;
+    if (!rt_ad_rect_ok(w, h, 0u, 0u, 1u, 1u, batch_spp, flags) || !rt_ad_tile_ok(tile) || n < 1u || n > RT_AD_TILES_MAX) return -2;
+    const unsigned bw = tile / RT_AD_BLOCK, grid = n * bw * bw; /* <= 2^20 x 256 */
+    launch[0] = grid; launch[1] = RT_AD_WG;
+    hipLaunchKernelGGL(rt_ad_merge_tiles_kernel, dim3(grid), dim3(RT_AD_WG), 0, stream, w, h, tile, rec, batch_spp, flags & RT_DN_KEEP_ALBEDO, sums, aov, acc);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 extern "C" int rt1w_internal_accum_resolve_launch(uint32_t w, uint32_t h, uint32_t batch_spp, const double* acc, double* frame, double* var,

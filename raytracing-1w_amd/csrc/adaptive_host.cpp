@@ -4,7 +4,7 @@
 #include <cstring>
 
 #include "rt1w.h"
-#include "rt_adaptive.h"
+#include "rt_adaptive_plan.h"
 #include "walk_lab.h"
 
 extern "C" int rt1w_lab_accum_merge_host(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h, uint32_t batch_spp,
@@ -16,6 +16,17 @@ extern "C" int rt1w_lab_accum_merge_host(uint32_t width, uint32_t height, uint32
             const size_t i = (size_t)(y0 + ry) * width + (x0 + rx), t = (size_t)ry * tile_w + rx;
             rt_ad_merge_pixel(batch_spp, keep, tile_sums + t * 3, aov + i * 8, acc + i * RT_AD_RECORD);
         }
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_accum_merge_tiles_host(uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t batch_spp,
+                                               uint32_t flags, const double* tile_sums, const double* aov, double* acc) {
+    if (!tile_sums || !aov || !acc || rt_ad_tiles_check(width, height, tile, tiles, n_tiles, batch_spp, flags)) return RT1W_ERR_INVALID;
+    const bool keep = (flags & RT_DN_KEEP_ALBEDO) != 0u;
+    for (uint32_t k = 0; k < n_tiles; ++k)
+        for (uint32_t ly = 0; ly < tile; ++ly)
+            for (uint32_t lx = 0; lx < tile; ++lx)
+                rt_ad_merge_tiles_pixel(width, height, tile, tiles[k].x0, tiles[k].y0, k, lx, ly, batch_spp, keep, tile_sums, aov, acc);
     return RT1W_OK;
 }
 

@@ -6,7 +6,7 @@
  *   rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B]
  *        [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic]
  *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
- *        [--adaptive BUDGET [--max-spp N] [--target-error E]]
+ *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch]]
  * --adaptive BUDGET spends a budget of BUDGET mean samples per pixel where the frame is noisy (rt1w_render_adaptive; --spp is ignored),
  * at most --max-spp samples on one pixel, none on tiles whose error is at or below --target-error; with --denoise --variance the
  * variance-guided filter follows (first-hit guides of the pilot's samples; K and --deep-guides do not apply).
@@ -39,6 +39,7 @@ int main(int argc, char** argv) {
     bool specialise = false, generic = false, reference_stream = false, f32 = false, near_far = false, sah = false, denoise = false;
     long denoise_iterations = 0, deep_guides = -1, variance = -1; /* -1: first-hit guides; -1: the fixed-sigma filter */
     long adaptive = -1, max_spp = 0; /* -1: every pixel gets --spp samples */
+    bool one_launch = false;         /* --adaptive: every round as one launch of all its tiles (RT1W_ADAPTIVE_ONE_LAUNCH) */
     double target_error = 0.0;
     long width = -1, height = -1, spp = -1, depth = 50; /* MAX_DEPTH main.rs:801 */
     unsigned long long build_seed = 1, seed = 0;
@@ -76,10 +77,11 @@ int main(int argc, char** argv) {
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') variance = std::atol(argv[++i]);
         }
         else if (a == "--adaptive") adaptive = std::atol(next("--adaptive"));
+        else if (a == "--one-launch") one_launch = true;
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--target-error") target_error = std::atof(next("--target-error"));
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch]]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -147,6 +149,7 @@ int main(int argc, char** argv) {
         rt1w_adaptive_params ap;
         std::memset(&ap, 0, sizeof ap);
         ap.size = (uint32_t)sizeof ap; ap.budget_spp = (uint32_t)adaptive; ap.max_spp = (uint32_t)max_spp; ap.target_error = target_error;
+        if (one_launch) ap.flags |= RT1W_ADAPTIVE_ONE_LAUNCH;
         rt1w_denoise_params d;
         std::memset(&d, 0, sizeof d);
         d.iterations = denoise_iterations > 0 ? (uint32_t)denoise_iterations : 0u;

@@ -35,7 +35,14 @@ struct RtKernel {
     hipFunction_t jit = nullptr;  /* ... or the scene-specialised kernel (jit.cpp), from its module */
     bool f32 = false;             /* takes the f32 scene's views (context_f32.hip) instead of the context's */
     bool pw = false;              /* takes the pair-walk view (rt_walk_pair.h) in second place */
+    bool tiles = false;           /* tile-list form (context_tiles.hip): takes the tile list (RtTileArg) in last place */
     int grid = 0;
+};
+
+/* the tile list as the kernels of context_tiles.hip take it (rt_kernel_sorted.h: RtTileList; the same bytes, checked at first use) */
+struct RtTileArg {
+    const uint32_t* rec = nullptr; /* device: [n][4] = rt1w_tile records */
+    uint32_t side = 0, n = 0;
 };
 
 /* The f64 render kernels by walk form and variant (context.hip: g_kernels).  Every walk form is followed by its build for
@@ -96,6 +103,10 @@ struct rt1w_context {
     RtPwView pw{};
     std::string pw_why;
     RtKernel pw_k[2] = {};
+    /* rt1w_render_tiles: the tile-list forms of k64 and pw_k (context_tiles.hip), resolved at their first use, and the uploaded list */
+    RtKernel kt[RT_N_WALKS][RT_N_VARIANTS] = {};
+    RtKernel pw_kt[2] = {};
+    void* d_tiles = nullptr; size_t tiles_bytes = 0;
     /* host copies of the flat arrays the two opt-in modes convert on first use (a scene may be destroyed before its contexts) */
     std::vector<RtNode> h_nodes, h_lights; std::vector<RtMaterial> h_materials; std::vector<RtTexture> h_textures; std::vector<RtPerlin> h_perlin;
     RtKernel k32[RT_N_VARIANTS][3] = {}; /* f32 kernels by variant and rt1w_internal_f32_kernel mode: plain, reordering, pair walk */
@@ -113,6 +124,10 @@ double lane_ms(const RtLane& l); /* ms between the two events of the lane, once 
 int reserve_out(rt1w_context* c, size_t bytes); /* the context's framebuffer, grown to at least `bytes` */
 /* plan, launch on lane 0, wait, stats: what every one-shot render entry runs */
 int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, rt1w_stats* stats);
+/* rt1w_render_tiles_device without the entry's own clock: validate, upload the list, plan, launch on lane 0, wait, stats */
+/* the context's copy of a tile list (HOST memory in, device memory out: valid until the next upload), grown on demand */
+int tiles_upload(rt1w_context* c, const rt1w_tile* tiles, uint32_t n_tiles, const uint32_t** d_rec);
+int render_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* d_out, rt1w_stats* stats);
 /* the host clock of an entry, for rt1w_stats.total_ms */
 struct RtTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -39,6 +39,10 @@ extern "C" void rt1w_internal_f32_destroy(void* h);
 extern "C" const void* rt1w_internal_f32_kernel(int variant, int mode); /* mode: 0 plain, 1 reordering, 2 pair walk (render_plan) */
 extern "C" int rt1w_internal_f32_pw(void* h, unsigned stack_cap); /* 1: the scene has f32 pair-walk records and fits `stack_cap` entries */
 extern "C" const void* rt1w_internal_f32_view(void* h, int what); /* the kernels' 0 f32 RtSceneView, 1 f32 RtPwView (nullptr: none) */
+/* context_tiles.hip: the tile-list forms of the f64 kernels (rt1w_render_tiles), by walk form and variant as g_kernels below */
+extern "C" const void* rt1w_internal_tile_kernel(int walk, int variant);
+extern "C" const void* rt1w_internal_tile_pw_kernel(int which);  /* 0 pair walk, 1 pair walk + reordering */
+extern "C" unsigned rt1w_internal_tile_sizeof(int what);         /* bytes of its 0 RtSceneView, 1 RtFrame, 2 RtPwView, 3 RtTileList */
 
 #include "rt_kernels.h"
 #include "rt_walk_table.h"
@@ -236,10 +240,11 @@ void lane_destroy(RtLane& l) {
     l = RtLane();
 }
 
+#define RT_TILES_MAX (1u << 20) /* tiles of one rt1w_render_tiles list: the kernels carry a tile's index in 29 bits, the virtual tile's height is a uint32 */
 #ifndef RT_PARTIAL_BUDGET
 #define RT_PARTIAL_BUDGET (8ull << 30)
 #endif
-struct RtLaunch { RtFrame f; unsigned long long npix; unsigned long long partial_budget = RT_PARTIAL_BUDGET; int variant; RtKernel k; };
+struct RtLaunch { RtFrame f; unsigned long long npix; unsigned long long partial_budget = RT_PARTIAL_BUDGET; int variant; RtKernel k; RtTileArg tl; };
 
 /* the persistent grid of a kernel: as many workgroups as are resident at once, at least one per CU; 0, with the error set, if the
  * occupancy query failed */
@@ -404,11 +409,13 @@ int render_launch(rt1w_context* c, RtLane& l, const rt1w_render_params* p, const
     hipLaunchKernelGGL(rt_init_counters_kernel, dim3(1), dim3(1), 0, l.stream, l.d_counters, (unsigned long long)k.grid * k.block, pass ? 1u : 0u);
     double* partial = l.d_partial;
     unsigned long long* counters = l.d_counters;
-    void* args[5];
+    RtTileArg tl = L.tl;
+    void* args[6];
     int n = 0;
     args[n++] = const_cast<void*>(view);
     if (k.pw) args[n++] = const_cast<void*>(pw);
     args[n++] = &PF; args[n++] = &partial; args[n++] = &counters;
+    if (k.tiles) args[n++] = &tl; /* a pass's sample delta reaches every tile through PF.sample_offset, which the kernel adds to the tile's own */
     if (!hip_ok(k.jit ? hipModuleLaunchKernel(k.jit, (unsigned)k.grid, 1, 1, (unsigned)k.block, 1, 1, 0, l.stream, args, nullptr)
                       : hipLaunchKernel(k.fn, dim3(k.grid), dim3(k.block), args, 0, l.stream), "render kernel launch")) return RT1W_ERR_DEVICE;
     launch_resolve(l.stream, l.d_partial, d_out, L.npix, PF.n_chunks, L.f.spp, p, (pass ? 1u : 0u) | (pass + 1u < n_pass ? 2u : 0u));
@@ -512,9 +519,85 @@ int render_wavefront(rt1w_context* c, const rt1w_render_params* p, const RtLaunc
     return RT1W_OK;
 }
 
+/* the tile-list form of the kernel a plan holds (one of k64 / pw_k: the plan was made with RT1W_GENERIC), resolved at its first use */
+int tile_kernel_of(rt1w_context* c, RtKernel& k) {
+    if (rt1w_internal_tile_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_tile_sizeof(1) != sizeof(RtFrame) ||
+        rt1w_internal_tile_sizeof(2) != sizeof(RtPwView) || rt1w_internal_tile_sizeof(3) != sizeof(RtTileArg)) {
+        rt1w::set_error("tile-list kernels built against another scene layout"); return RT1W_ERR_DEVICE;
+    }
+    RtKernel* slot = nullptr;
+    RtKernel want = k;
+    want.tiles = true; want.grid = 0; want.fn = nullptr;
+    for (int i = 0; i < 2 && !slot; ++i)
+        if (c->pw_k[i].grid && c->pw_k[i].fn == k.fn) { slot = &c->pw_kt[i]; want.fn = rt1w_internal_tile_pw_kernel(i); }
+    for (int w = 0; w < RT_N_WALKS && !slot; ++w)
+        for (int v = 0; v < RT_N_VARIANTS && !slot; ++v)
+            if (c->k64[w][v].grid && c->k64[w][v].fn == k.fn) { slot = &c->kt[w][v]; want.fn = rt1w_internal_tile_kernel(w, v); }
+    if (!slot || !want.fn) { rt1w::set_error("rt1w_render_tiles: the kernel this scene renders with has no tile-list form"); return RT1W_ERR_DEVICE; }
+    const int rc = first_use(c, *slot, want);
+    if (rc < 0) return rc;
+    k = *slot;
+    return RT1W_OK;
+}
+
 } // namespace
 
 namespace rt1w {
+int tiles_upload(rt1w_context* c, const rt1w_tile* tiles, uint32_t n_tiles, const uint32_t** d_rec) {
+    static_assert(sizeof(rt1w_tile) == 16, "the kernels read a tile's record as four 32-bit words");
+    const size_t bytes = (size_t)n_tiles * sizeof(rt1w_tile);
+    if (bytes > c->tiles_bytes) {
+        if (c->d_tiles) (void)hipFree(c->d_tiles);
+        c->d_tiles = nullptr; c->tiles_bytes = 0;
+        const size_t grown = bytes < 4096 ? 4096 : bytes * 2;
+        if (!hip_ok(hipMalloc(&c->d_tiles, grown), "hipMalloc(tile list)")) return RT1W_ERR_NOMEM;
+        c->tiles_bytes = grown;
+    }
+    /* nothing of an earlier call is in flight (every entry waits for the lane), so the list may be replaced now */
+    if (!hip_ok(hipMemcpy(c->d_tiles, tiles, bytes, hipMemcpyHostToDevice), "tile list copy")) return RT1W_ERR_DEVICE;
+    *d_rec = (const uint32_t*)c->d_tiles;
+    return RT1W_OK;
+}
+
+int render_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* d_out, rt1w_stats* stats) {
+    if (!c || !p || !tiles || !d_out) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (p->width < 2 || p->height < 2) { set_error("width and height must be >= 2 (u,v divide by W-1, H-1; main.rs:968-969)"); return RT1W_ERR_INVALID; }
+    if (p->spp == 0) { set_error("spp must be > 0"); return RT1W_ERR_INVALID; }
+    if (p->precision == RT1W_PRECISION_F32) { set_error("rt1w_render_tiles: the tile-list kernels are f64 only"); return RT1W_ERR_UNSUPPORTED; }
+    if (p->precision != RT1W_PRECISION_F64) { set_error("unknown precision"); return RT1W_ERR_UNSUPPORTED; }
+    if (p->flags & ~(RT1W_OUT_SUM | RT1W_GENERIC)) { set_error("rt1w_render_tiles: flags 0, RT1W_OUT_SUM or RT1W_GENERIC only"); return RT1W_ERR_INVALID; }
+    if (p->strip_rows || p->strip_period) { set_error("rt1w_render_tiles takes no interleaved strips"); return RT1W_ERR_INVALID; }
+    if (tile < 16u || tile > 256u || tile % 16u) { set_error("rt1w_render_tiles: tile must be a multiple of 16 in 16 .. 256"); return RT1W_ERR_INVALID; }
+    if (n_tiles < 1u || n_tiles > RT_TILES_MAX) { set_error("rt1w_render_tiles: n_tiles must be 1 .. 2^20"); return RT1W_ERR_INVALID; }
+    unsigned long long inside = 0ull;
+    for (uint32_t k = 0; k < n_tiles; ++k) {
+        const rt1w_tile& t = tiles[k];
+        if (t.reserved != 0u || t.x0 % tile || t.y0 % tile || t.x0 >= p->width || t.y0 >= p->height) {
+            set_error("rt1w_render_tiles: a tile's x0 and y0 must be multiples of `tile` inside the frame, its reserved member 0"); return RT1W_ERR_INVALID;
+        }
+        if ((unsigned long long)p->sample_offset + t.sample_offset + p->spp > 0xFFFFFFFFull) { set_error("sample index overflow"); return RT1W_ERR_INVALID; }
+        inside += (unsigned long long)(p->width - t.x0 < tile ? p->width - t.x0 : tile) * (p->height - t.y0 < tile ? p->height - t.y0 : tile);
+    }
+    /* the list as ONE virtual tile of width `tile` and height n_tiles x tile, on the generic kernels (the specialised ones have no tile
+     * form; their frames are the same bits), chunked as the WHOLE frame is */
+    rt1w_render_params q = *p;
+    q.x0 = 0u; q.y0 = 0u; q.tile_w = tile; q.tile_h = n_tiles * tile;
+    q.flags |= RT1W_GENERIC;
+    if (!q.chunk) q.chunk = c->variant >= 2 ? 1u : rt1w_default_chunk(p->width, p->height, p->spp);
+    RtLaunch L;
+    int rc = render_plan(c, &q, L);
+    if (rc < 0) return rc;
+    if ((rc = tile_kernel_of(c, L.k)) < 0) return rc;
+    RtLane& l = c->lane[0];
+    if ((rc = tiles_upload(c, tiles, n_tiles, &L.tl.rec)) < 0) return rc;
+    L.tl.side = tile; L.tl.n = n_tiles;
+    if ((rc = lane_reserve_partial(l, L)) < 0) return rc;
+    if ((rc = render_launch(c, l, &q, L, d_out)) < 0) return rc;
+    if ((rc = render_finish(l, L, stats)) < 0) return rc;
+    if (stats) stats->paths = inside * p->spp; /* the pixels inside the frame: the others are not traced */
+    return RT1W_OK;
+}
+
 int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, rt1w_stats* stats) {
     /* a render this long repays the 1-8 s of the compiler: 2^35 paths where the gain is ~1.3x (scenes the generic sweep
      * handles), 2^32 where it is 1.5-2.3x (scenes the generic code hands to the stack walk).  RT1W_NO_JIT: never compile
@@ -638,7 +721,7 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
 void rt1w_context_destroy(rt1w_context* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    void* bufs[] = {c->d_nodes, c->d_lights, c->d_materials, c->d_textures, c->d_perlin, c->d_images, c->d_out, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], c->d_batches, c->d_accum};
+    void* bufs[] = {c->d_nodes, c->d_lights, c->d_materials, c->d_textures, c->d_perlin, c->d_images, c->d_out, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], c->d_batches, c->d_accum, c->d_tiles};
     if (c->wf_state && g_wf_destroy) g_wf_destroy(c->wf_state);
     for (void* b : bufs) if (b) (void)hipFree(b);
     rt1w_internal_f32_destroy(c->f32_scene);
@@ -683,6 +766,28 @@ int rt1w_render_device(rt1w_context* c, const rt1w_render_params* p, void* d_out
     rc = render_common(c, p, (double*)d_out_rgb, stats);
     if (rc == RT1W_OK && stats) stats->total_ms = timer.ms();
     return rc;
+}
+
+int rt1w_render_tiles_device(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, void* d_out, rt1w_stats* stats) {
+    if (c && !hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const int rc = render_tiles_common(c, p, tile, tiles, n_tiles, (double*)d_out, stats);
+    if (rc == RT1W_OK && stats) stats->total_ms = timer.ms();
+    return rc;
+}
+
+int rt1w_render_tiles(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out, rt1w_stats* stats) {
+    if (!c || !out) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (tile > 256u || n_tiles > RT_TILES_MAX) { rt1w::set_error("rt1w_render_tiles: tile must be a multiple of 16 in 16 .. 256, n_tiles 1 .. 2^20"); return RT1W_ERR_INVALID; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const size_t bytes = (size_t)n_tiles * tile * tile * 3 * sizeof(double);
+    int rc = reserve_out(c, bytes ? bytes : 16);
+    if (rc < 0) return rc;
+    if ((rc = render_tiles_common(c, p, tile, tiles, n_tiles, c->d_out, stats)) < 0) return rc;
+    if (!hip_ok(hipMemcpy(out, c->d_out, bytes, hipMemcpyDeviceToHost), "tile copy")) return RT1W_ERR_DEVICE;
+    if (stats) stats->total_ms = timer.ms();
+    return RT1W_OK;
 }
 
 int rt1w_render_u8(rt1w_context* c, const rt1w_render_params* p, uint8_t* out_rgb8, rt1w_stats* stats) {

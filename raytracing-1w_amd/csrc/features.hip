@@ -31,6 +31,8 @@ extern "C" unsigned rt1w_internal_denoise_var_sizeof(void); /* bytes per pixel o
 extern "C" int rt1w_internal_accum_merge_launch(uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, uint32_t batch_spp,
                                                 uint32_t flags, const double* sums, const double* aov, double* acc, hipStream_t stream,
                                                 unsigned launch[2]);
+extern "C" int rt1w_internal_accum_merge_tiles_launch(uint32_t w, uint32_t h, uint32_t tile, const uint32_t* rec, uint32_t n, uint32_t batch_spp, uint32_t flags,
+                                                      const double* sums, const double* aov, double* acc, hipStream_t stream, unsigned launch[2]);
 extern "C" int rt1w_internal_accum_resolve_launch(uint32_t w, uint32_t h, uint32_t batch_spp, const double* acc, double* frame, double* var,
                                                   double* spp, hipStream_t stream, unsigned launch[2]);
 extern "C" int rt1w_internal_accum_tile_error_launch(uint32_t w, uint32_t h, uint32_t tile, const double* acc, double* err, hipStream_t stream,
@@ -421,6 +423,20 @@ int accum_merge_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t x0, uin
     const int rc = rt1w_internal_accum_merge_launch(w, h, x0, y0, tw, th, batch_spp, flags, d_sums, d_aov, d_acc, l.stream, launch);
     return lane_finish(c, rc, launch, (uint64_t)tw * th, "accumulator merge", stats);
 }
+/* the list is checked by the caller (rt_ad_tiles_check) */
+int accum_merge_tiles_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t batch_spp, uint32_t flags,
+                             const double* d_sums, const double* d_aov, double* d_acc, rt1w_stats* stats) {
+    RtLane& l = c->lane[0];
+    const uint32_t* d_rec = nullptr;
+    int rc = tiles_upload(c, tiles, n, &d_rec);
+    if (rc < 0) return rc;
+    unsigned launch[2] = {0u, 0u};
+    (void)hipEventRecord(l.ev0, l.stream);
+    rc = rt1w_internal_accum_merge_tiles_launch(w, h, tile, d_rec, n, batch_spp, flags, d_sums, d_aov, d_acc, l.stream, launch);
+    uint64_t inside = 0;
+    for (uint32_t k = 0; k < n; ++k) inside += (uint64_t)std::min(tile, w - tiles[k].x0) * std::min(tile, h - tiles[k].y0);
+    return lane_finish(c, rc, launch, inside, "accumulator merge (tile list)", stats);
+}
 int accum_resolve_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batch_spp, const double* d_acc, double* d_frame, double* d_var, double* d_spp,
                          rt1w_stats* stats) {
     RtLane& l = c->lane[0];
@@ -463,6 +479,32 @@ int accum_merge(rt1w_context* c, uint32_t w, uint32_t h, uint32_t x0, uint32_t y
     }
     rt1w_stats st;
     if ((rc = accum_merge_common(c, w, h, x0, y0, tw, th, batch_spp, flags, d_sums, d_aov, d_acc, &st)) < 0) return rc;
+    if (host && !hip_ok(hipMemcpy(acc, d_acc, npix * RT_AD_RECORD * sizeof(double), hipMemcpyDeviceToHost), "accumulator merge: result copy")) return RT1W_ERR_DEVICE;
+    if (stats) { *stats = st; stats->total_ms = timer.ms(); }
+    return RT1W_OK;
+}
+int accum_merge_tiles(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t batch_spp, uint32_t flags,
+                      const double* sums, const double* aov, double* acc, bool host, rt1w_stats* stats) {
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (const char* why = rt_ad_tiles_check(w, h, tile, tiles, n, batch_spp, flags)) { set_error(why); return RT1W_ERR_INVALID; }
+    if (!sums || !aov || !acc) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
+    const RtTimer timer;
+    const size_t npix = (size_t)w * h, tpix = (size_t)n * tile * tile;
+    const double *d_sums = sums, *d_aov = aov;
+    double* d_acc = acc;
+    int rc;
+    if (host) {
+        if ((rc = reserve_out(c, (npix * RT1W_AOV_CHANNELS + tpix * 3) * sizeof(double))) < 0) return rc;
+        if ((rc = accum_reserve(c, npix * RT_AD_RECORD * sizeof(double))) < 0) return rc;
+        double* d_s = c->d_out + npix * RT1W_AOV_CHANNELS;
+        if (!hip_ok(hipMemcpy(c->d_out, aov, npix * RT1W_AOV_CHANNELS * sizeof(double), hipMemcpyHostToDevice), "accumulator merge: feature buffer copy")) return RT1W_ERR_DEVICE;
+        if (!hip_ok(hipMemcpy(d_s, sums, tpix * 3 * sizeof(double), hipMemcpyHostToDevice), "accumulator merge: sums copy")) return RT1W_ERR_DEVICE;
+        if (!hip_ok(hipMemcpy(c->d_accum, acc, npix * RT_AD_RECORD * sizeof(double), hipMemcpyHostToDevice), "accumulator merge: accumulator copy")) return RT1W_ERR_DEVICE;
+        d_aov = c->d_out; d_sums = d_s; d_acc = c->d_accum;
+    }
+    rt1w_stats st;
+    if ((rc = accum_merge_tiles_common(c, w, h, tile, tiles, n, batch_spp, flags, d_sums, d_aov, d_acc, &st)) < 0) return rc;
     if (host && !hip_ok(hipMemcpy(acc, d_acc, npix * RT_AD_RECORD * sizeof(double), hipMemcpyDeviceToHost), "accumulator merge: result copy")) return RT1W_ERR_DEVICE;
     if (stats) { *stats = st; stats->total_ms = timer.ms(); }
     return RT1W_OK;
@@ -532,6 +574,7 @@ int render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_ada
     if (p->strip_rows) { set_error("rt1w_render_denoised takes a contiguous tile (strip_rows must be 0): denoise the gathered frame with rt1w_denoise"); return RT1W_ERR_INVALID; }
     if (p->precision != RT1W_PRECISION_F64) { set_error("RT1W_PRECISION_F32 does not apply to rt1w_render_denoised (the filter is f64 only)"); return RT1W_ERR_INVALID; }
     if (p->x0 || p->y0 || p->tile_w != p->width || p->tile_h != p->height) { set_error("rt1w_render_adaptive takes the whole frame (x0 = y0 = 0, tile_w = width, tile_h = height)"); return RT1W_ERR_INVALID; }
+    if (plan.one_launch && (p->flags & ~RT1W_GENERIC)) { set_error("adaptive: with RT1W_ADAPTIVE_ONE_LAUNCH p->flags must be 0 or RT1W_GENERIC (rt1w_render_tiles runs the generic kernels)"); return RT1W_ERR_INVALID; }
     if ((unsigned long long)p->sample_offset + plan.max_spp > 0xFFFFFFFFull) { set_error("adaptive: sample_offset + max_spp exceeds 2^32 - 1"); return RT1W_ERR_INVALID; }
     const uint32_t W = p->width, H = p->height;
     rt1w_denoise_params dp;
@@ -546,7 +589,9 @@ int render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_ada
     const uint32_t tiles_x = (W + plan.tile - 1u) / plan.tile, tiles_y = (H + plan.tile - 1u) / plan.tile;
     const size_t ntiles = (size_t)tiles_x * tiles_y;
     if ((rc = reserve_out(c, npix * (5 + RT1W_AOV_CHANNELS) * sizeof(double))) < 0) return rc;
-    if ((rc = batches_reserve(c, npix * 3 * sizeof(double))) < 0) return rc;
+    /* one launch per round: a round's batch is whole tiles, the edge tiles' pixels beyond the frame included */
+    const size_t batch_px = plan.one_launch ? std::max(npix, ntiles * plan.tile * plan.tile) : npix;
+    if ((rc = batches_reserve(c, batch_px * 3 * sizeof(double))) < 0) return rc;
     if ((rc = accum_reserve(c, (npix * RT_AD_RECORD + ntiles) * sizeof(double))) < 0) return rc;
     double* d_frame = c->d_out;
     double* d_var = c->d_out + npix * 3;
@@ -586,6 +631,7 @@ int render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_ada
         if ((rc = batch(0u, 0u, W, H, b)) < 0) return rc;
     std::vector<uint32_t> m(ntiles, plan.pilot);
     std::vector<double> err(ntiles);
+    std::vector<rt1w_tile> list;
     uint32_t rounds = 0;
     for (;;) {
         if ((rc = accum_tile_error_common(c, W, H, plan.tile, d_acc, d_err, &sk)) < 0) return rc;
@@ -594,6 +640,19 @@ int render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_ada
         const std::vector<uint32_t> taken = rt_ad_select(plan, tiles_x, tiles_y, W, H, err.data(), m.data());
         if (taken.empty()) break;
         ++rounds;
+        if (plan.one_launch) {
+            /* RT1W_ADAPTIVE_ONE_LAUNCH: the round's tiles as one list -- one render launch, one merge */
+            list.clear();
+            for (uint32_t t : taken) list.push_back(rt1w_tile{(t % tiles_x) * plan.tile, (t / tiles_x) * plan.tile, m[t] * plan.batch_spp, 0u});
+            bp.sample_offset = p->sample_offset;
+            rt1w_stats sb;
+            memset(&sb, 0, sizeof sb);
+            if ((rc = render_tiles_common(c, &bp, plan.tile, list.data(), (uint32_t)list.size(), c->d_batches, &sb)) < 0) return rc;
+            st.paths += sb.paths; st.segments += sb.segments; st.passes += sb.passes;
+            kernel_ms += sb.kernel_ms;
+            if ((rc = accum_merge_tiles_common(c, W, H, plan.tile, list.data(), (uint32_t)list.size(), plan.batch_spp, plan.flags, c->d_batches, d_aov, d_acc, &sk)) < 0) return rc;
+            kernel_ms += sk.kernel_ms;
+        } else
         for (const RtAdRun& r : rt_ad_group(plan, tiles_x, W, H, taken, m.data()))
             if ((rc = batch(r.x0, r.y0, r.w, r.h, r.m)) < 0) return rc;
         for (uint32_t t : taken) ++m[t];
@@ -667,6 +726,14 @@ int rt1w_accum_merge(rt1w_context* c, uint32_t width, uint32_t height, uint32_t 
 int rt1w_accum_merge_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h,
                             uint32_t batch_spp, uint32_t flags, const void* d_tile_sums, const void* d_aov, void* d_acc, rt1w_stats* stats) {
     return accum_merge(c, width, height, x0, y0, tile_w, tile_h, batch_spp, flags, (const double*)d_tile_sums, (const double*)d_aov, (double*)d_acc, false, stats);
+}
+int rt1w_accum_merge_tiles(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t batch_spp,
+                           uint32_t flags, const double* tile_sums, const double* aov, double* acc, rt1w_stats* stats) {
+    return accum_merge_tiles(c, width, height, tile, tiles, n_tiles, batch_spp, flags, tile_sums, aov, acc, true, stats);
+}
+int rt1w_accum_merge_tiles_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles,
+                                  uint32_t batch_spp, uint32_t flags, const void* d_tile_sums, const void* d_aov, void* d_acc, rt1w_stats* stats) {
+    return accum_merge_tiles(c, width, height, tile, tiles, n_tiles, batch_spp, flags, (const double*)d_tile_sums, (const double*)d_aov, (double*)d_acc, false, stats);
 }
 int rt1w_accum_resolve(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc, double* frame, double* var,
                        double* spp, rt1w_stats* stats) {

@@ -68,6 +68,18 @@ RT_HD void rt_ad_merge_pixel(uint32_t batch_spp, bool keep_albedo, const double*
     acc[4] = mean_d; acc[5] = m2_d; acc[6] = mean_p; acc[7] = m2_p;
 }
 
+/* one pixel of rt1w_accum_merge_tiles: pixel (lx, ly) of tile k of the list, whose corner is (x0, y0); sums[n][tile][tile][3].  A pixel
+ * beyond the frame's edge is skipped.  The same rt_ad_merge_pixel on the same operands as rt1w_accum_merge of the clipped rectangle. */
+RT_HD void rt_ad_merge_tiles_pixel(uint32_t w, uint32_t h, uint32_t tile, uint32_t x0, uint32_t y0, uint32_t k, uint32_t lx, uint32_t ly, uint32_t batch_spp,
+                                   bool keep_albedo, const double* sums, const double* aov, double* acc) {
+    const uint32_t x = x0 + lx, y = y0 + ly;
+    if (x >= w || y >= h) return;
+    const unsigned long long i = (unsigned long long)y * w + x;
+    const unsigned long long t = ((unsigned long long)k * tile + ly) * tile + lx;
+    rt_ad_merge_pixel(batch_spp, keep_albedo, sums + t * 3u, aov + i * 8u, acc + i * RT_AD_RECORD);
+}
+#define RT_AD_TILES_MAX (1u << 20) /* tiles of one list (rt1w_render_tiles' bound) */
+
 /* one pixel of rt1w_accum_resolve: frame[3], *var, *spp */
 RT_HD void rt_ad_resolve_pixel(uint32_t batch_spp, const double* acc, double* frame, double* var, double* spp) {
     const double m = acc[3];

@@ -21,7 +21,8 @@
 
 /* rt1w_adaptive_params with the defaults filled in */
 struct RtAdPlan {
-    uint32_t tile, batch_spp, pilot, budget_spp, max_spp, flags;
+    uint32_t tile, batch_spp, pilot, budget_spp, max_spp, flags; /* flags: how the merges demodulate (RT1W_DENOISE_KEEP_ALBEDO or 0) */
+    bool one_launch;                                             /* RT1W_ADAPTIVE_ONE_LAUNCH */
     double target_error, round_share;
 };
 
@@ -46,8 +47,29 @@ inline const char* rt_ad_make_plan(const rt1w_adaptive_params* a, RtAdPlan* out)
     p.max_spp = (uint32_t)mx;
     if (!(p.target_error >= 0.0) || !rt_dn_finite(p.target_error)) return "adaptive: target_error must be finite and >= 0";
     if (!(p.round_share > 0.0) || !(p.round_share <= 1.0)) return "adaptive: round_share must be in (0, 1] (0 = default)";
-    if (p.flags & ~RT1W_DENOISE_KEEP_ALBEDO) return "adaptive: unknown flag (flags: 0 or RT1W_DENOISE_KEEP_ALBEDO)";
+    if (p.flags & ~(RT1W_DENOISE_KEEP_ALBEDO | RT1W_ADAPTIVE_ONE_LAUNCH)) return "adaptive: unknown flag (flags: RT1W_DENOISE_KEEP_ALBEDO, RT1W_ADAPTIVE_ONE_LAUNCH)";
+    p.one_launch = (p.flags & RT1W_ADAPTIVE_ONE_LAUNCH) != 0u;
+    p.flags &= ~RT1W_ADAPTIVE_ONE_LAUNCH;
     *out = p;
+    return nullptr;
+}
+
+/* the list of rt1w_accum_merge_tiles: nullptr, or why it is refused (RT1W_ERR_INVALID) */
+inline const char* rt_ad_tiles_check(uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t batch_spp, uint32_t flags) {
+    if (!rt_ad_frame_ok(w, h)) return "accumulator: width and height must be 1 .. 2^30";
+    if (!rt_ad_tile_ok(tile)) return "accumulator merge: tile must be a multiple of 16 in 16 .. 256";
+    if (batch_spp < 1u || (flags & ~RT1W_DENOISE_KEEP_ALBEDO)) return "accumulator merge: batch_spp >= 1, flags 0 or RT1W_DENOISE_KEEP_ALBEDO";
+    if (!tiles || n < 1u || n > RT_AD_TILES_MAX) return "accumulator merge: a list of 1 .. 2^20 tiles";
+    const uint32_t tiles_x = (w + tile - 1u) / tile, tiles_y = (h + tile - 1u) / tile;
+    std::vector<bool> seen((size_t)tiles_x * tiles_y, false);
+    for (uint32_t k = 0; k < n; ++k) {
+        const rt1w_tile& t = tiles[k];
+        if (t.reserved != 0u || t.x0 % tile || t.y0 % tile || t.x0 >= w || t.y0 >= h)
+            return "accumulator merge: a tile's x0 and y0 must be multiples of `tile` inside the frame, its reserved member 0";
+        const size_t id = (size_t)(t.y0 / tile) * tiles_x + t.x0 / tile;
+        if (seen[id]) return "accumulator merge: a tile is named twice (the tiles of one call are disjoint)";
+        seen[id] = true;
+    }
     return nullptr;
 }
 

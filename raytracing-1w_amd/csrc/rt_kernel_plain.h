@@ -103,7 +103,7 @@ struct LdsNodes {
 /* PW: the walk is the pair walk of rt_walk_pair.h (sphere scenes; `pw` = its records), else the one-entry-per-step walk */
 template <class Cfg, bool CACHE, bool PW = false>
 __device__ __forceinline__ void rt_render_plain_body(const RtSceneView& sc, const RtFrame& f, rt_f64* __restrict__ partial,
-                                                     unsigned long long* __restrict__ counters, const RtPwView* pwp = nullptr) {
+                                                     unsigned long long* __restrict__ counters RT_TILE_PARAM, const RtPwView* pwp = nullptr) {
     /* the sweep variants need no traversal stack (and no LDS at all) */
     typedef typename std::conditional<CACHE, uint16_t, uint32_t>::type stack_word;
     __shared__ stack_word stack_mem[(Cfg::sweep || PW) ? 1 : RT_STACK_CAP * RT_BLOCK];
@@ -143,6 +143,7 @@ __device__ __forceinline__ void rt_render_plain_body(const RtSceneView& sc, cons
     bool fresh = true; /* `item` holds an id that was not decoded yet */
     bool have = false;
     uint32_t px = 0, py = 0, chunk = 0, s = 0, s_end = 0;
+    RT_TILE_STATE
     RtV3d sum = rt_v3d(RT_R(0.0), RT_R(0.0), RT_R(0.0));
     RtPath path;
     path.alive = false;
@@ -155,7 +156,7 @@ __device__ __forceinline__ void rt_render_plain_body(const RtSceneView& sc, cons
         RT_STAMP(0);
         if (!path.alive) {
             if (have && s == s_end) {
-                rt_f64* dst = partial + ((unsigned long long)chunk * npix + (unsigned long long)py * f.tile_w + px) * 3ull;
+                rt_f64* dst = partial + ((unsigned long long)chunk * npix + RT_ITEM_PIXEL()) * 3ull;
                 dst[0] = sum.x; dst[1] = sum.y; dst[2] = sum.z;
                 have = false;
             }
@@ -175,7 +176,7 @@ __device__ __forceinline__ void rt_render_plain_body(const RtSceneView& sc, cons
                 fresh = false;
                 if (item >= n_items) break;
                 rt_item_decode(f, item, px, py, chunk);
-                if (px < f.tile_w && py < f.tile_h) {
+                if (RT_ITEM_TAKEN()) {
                     s = chunk * f.chunk;
                     s_end = s + f.chunk < f.spp ? s + f.chunk : f.spp;
                     sum = rt_v3d(RT_R(0.0), RT_R(0.0), RT_R(0.0));
@@ -183,7 +184,7 @@ __device__ __forceinline__ void rt_render_plain_body(const RtSceneView& sc, cons
                 }
             }
             if (!have) break; /* no work left: this lane retires */
-            rt_path_begin(sc, f, f.x0 + px, rt_frame_row(f, py), f.sample_offset + s, path);
+            rt_path_begin(sc, f, RT_ITEM_BEGIN_ARGS, path);
             RT_STAMP(1);
         }
 #if defined(RT_HAVE_PW)
@@ -440,7 +441,7 @@ __device__ __forceinline__ void rt_render_plain_body(const RtSceneView& sc, cons
  * record read from LDS costs an eighth of what the four divergent 16-byte lane-loads cost the vector L1, which paces this walk. */
 template <class Cfg, int CAP, int PARTS, bool PW = false, int HC = 0>
 __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const RtFrame& f, rt_f64* __restrict__ partial,
-                                                  unsigned long long* __restrict__ counters, const RtPwView* pwp = nullptr) {
+                                                  unsigned long long* __restrict__ counters RT_TILE_PARAM, const RtPwView* pwp = nullptr) {
     static_assert(!Cfg::sweep && RT_WALK_MODE == 0, "stack-walk variants only");
     static_assert(!(PW && HC > 0), "the pair walk has its own records");
     constexpr int RT_SS_PER = (RT_XCH_QW + PARTS - 1) / PARTS;
@@ -490,6 +491,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
     unsigned long long item = (unsigned long long)blockIdx.x * RT_BLOCK + threadIdx.x;
     bool fresh = true, have = false, retired = false;
     uint32_t px = 0, py = 0, chunk = 0, s = 0;
+    RT_TILE_STATE
     RtV3d sum = rt_v3d(RT_R(0.0), RT_R(0.0), RT_R(0.0));
     RtPath path;
     path.alive = false;
@@ -513,7 +515,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
         if (!walking && !path.alive && !retired) {
             const uint32_t s_end = chunk * f.chunk + f.chunk < f.spp ? chunk * f.chunk + f.chunk : f.spp;
             if (have && s == s_end) {
-                rt_f64* dst = partial + ((unsigned long long)chunk * npix + (unsigned long long)py * f.tile_w + px) * 3ull;
+                rt_f64* dst = partial + ((unsigned long long)chunk * npix + RT_ITEM_PIXEL()) * 3ull;
                 dst[0] = sum.x; dst[1] = sum.y; dst[2] = sum.z;
                 have = false;
             }
@@ -531,7 +533,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
                 fresh = false;
                 if (item >= n_items) break;
                 rt_item_decode(f, item, px, py, chunk);
-                if (px < f.tile_w && py < f.tile_h) {
+                if (RT_ITEM_TAKEN()) {
                     s = chunk * f.chunk;
                     sum = rt_v3d(RT_R(0.0), RT_R(0.0), RT_R(0.0));
                     have = true;
@@ -539,7 +541,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
             }
             if (!have) retired = true;
 #if !RT_CAM_AT_USE
-            else rt_path_begin(sc, f, f.x0 + px, rt_frame_row(f, py), f.sample_offset + s, path);
+            else rt_path_begin(sc, f, RT_ITEM_BEGIN_ARGS, path);
 #else
             else {
                 /* the camera block is read where it is used, by scalar loads from the kernel-argument segment: held across the loop its
@@ -552,7 +554,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
                 cam.horizontal = rt_v3(kc[6], kc[7], kc[8]); cam.vertical = rt_v3(kc[9], kc[10], kc[11]);
                 cam.u = rt_v3(kc[12], kc[13], kc[14]); cam.v = rt_v3(kc[15], kc[16], kc[17]); cam.w = rt_v3(kc[18], kc[19], kc[20]);
                 cam.lens_radius = kc[21]; cam.time0 = kc[22]; cam.time1 = kc[23];
-                rt_path_begin_cam(cam, f, f.x0 + px, rt_frame_row(f, py), f.sample_offset + s, path);
+                rt_path_begin_cam(cam, f, RT_ITEM_BEGIN_ARGS, path);
             }
 #endif
         }
@@ -767,7 +769,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
             st[20] = RT_PK2(path.rng.b2, path.rng.b3);
             st[21] = RT_PK2(tr.prim, tr.scope); st[22] = RT_PK2(tr.cls, path.depth_left);
             st[23] = RT_PK2(px, py); st[24] = RT_PK2(chunk, s);
-            st[25] = RT_PK2((have ? 1u : 0u) | (retired ? 2u : 0u) | (path.alive ? 4u : 0u), 0u);
+            st[25] = RT_XCH_TAIL((have ? 1u : 0u) | (retired ? 2u : 0u) | (path.alive ? 4u : 0u));
 #undef RT_PK2
 #pragma unroll
             for (int part = 0; part < PARTS; ++part) {
@@ -798,6 +800,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
                 RT_UP2(st[23], px, py); RT_UP2(st[24], chunk, s);
                 const uint32_t flags = (uint32_t)st[25];
                 have = (flags & 1u) != 0u; retired = (flags & 2u) != 0u; path.alive = (flags & 4u) != 0u;
+                RT_XCH_UNTAIL(st[25]);
 #undef RT_UP2
             }
         }

@@ -79,6 +79,62 @@ __device__ __forceinline__ uint32_t lane_prefix(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+/* ---- the tile-list form (context_tiles.hip defines RT_TILE_LIST; rt1w_render_tiles) ------------------------------------------------
+ * The frame a kernel of this form is launched with is a VIRTUAL tile of width T and height n x T: a list of n square tiles of the
+ * image, one below the other.  Work-item numbering, the partial sums [chunk][pixel][3] and the resolve kernel see that tile and nothing
+ * else.  What differs is where a virtual pixel lies in the image and which samples it draws: record k of the table gives tile k's
+ * x0, y0 and first absolute sample.  T is a multiple of 8, so an aligned run of 64 items (an 8 x 8 block) lies in one tile; the items
+ * a wave fetches later are consecutive but not aligned, so they lie in at most two tiles -- the lookup loops over the distinct tile
+ * indices of the wave (one round, seldom two), each read wave-uniformly.  It happens where an item is decoded, once per item: the
+ * lane then carries the pixel's IMAGE position in (px, py), the tile's index and its sample offset; the virtual pixel its chunk sum is
+ * stored at follows from those (x0 and y0 are multiples of T).  A pixel beyond the frame's edge is not traced: its chunk sums are
+ * written as +0.0 here.  Without RT_TILE_LIST the macros below are the statements the kernels always had. */
+#if defined(RT_TILE_LIST)
+struct RtTileList {
+    const uint32_t* rec; /* [n][4]: x0, y0, sample_offset (the tile's own: the frame's is added to it), 0 */
+    uint32_t side;    /* T */
+    uint32_t n;
+};
+__device__ __forceinline__ bool rt_tile_item(const RtFrame& f, const RtTileList& tl, rt_f64* __restrict__ partial, unsigned long long npix,
+                                             uint32_t chunk, uint32_t& px, uint32_t& py, uint32_t& tk, uint32_t& tso) {
+    typedef const __attribute__((address_space(4))) uint32_t* rec_t; /* constant address space: a uniform index is a scalar load */
+    const rec_t table = (rec_t)tl.rec;
+    const uint32_t k = py / tl.side;
+    uint32_t rx, ry, rs;
+    for (;;) {
+        /* the record of the first active lane's tile, read AHEAD of the comparison and pinned to scalar registers there: behind the
+         * comparison the compiler puts the lane's own k in k0's place, and the load becomes a vector load */
+        const uint32_t k0 = __builtin_amdgcn_readfirstlane(k);
+        uint32_t ax = table[(size_t)k0 * 4u], ay = table[(size_t)k0 * 4u + 1u], as = table[(size_t)k0 * 4u + 2u];
+        asm volatile("" : "+s"(ax), "+s"(ay), "+s"(as));
+        if (k == k0) { rx = ax; ry = ay; rs = as; break; }
+    }
+    const uint32_t ix = rx + px, iy = ry + (py - k * tl.side);
+    if (!(ix < f.width && iy < f.height)) {
+        rt_f64* dst = partial + ((unsigned long long)chunk * npix + (unsigned long long)py * f.tile_w + px) * 3ull;
+        dst[0] = RT_R(0.0); dst[1] = RT_R(0.0); dst[2] = RT_R(0.0);
+        return false;
+    }
+    px = ix; py = iy; tk = k; tso = f.sample_offset + rs;
+    return true;
+}
+#define RT_TILE_PARAM , const RtTileList& tl
+#define RT_TILE_STATE uint32_t tk = 0, tso = 0;
+#define RT_ITEM_TAKEN() rt_tile_item(f, tl, partial, npix, chunk, px, py, tk, tso)
+#define RT_ITEM_PIXEL() (((unsigned long long)tk * tl.side + py % tl.side) * tl.side + px % tl.side)
+#define RT_ITEM_BEGIN_ARGS px, py, tso + s
+#define RT_XCH_TAIL(flags) RT_PK2((flags) | (tk << 3), tso) /* tk < 2^29: the host's bound on the list */
+#define RT_XCH_UNTAIL(v) do { tk = (uint32_t)(v) >> 3; tso = (uint32_t)((v) >> 32); } while (0)
+#else
+#define RT_TILE_PARAM
+#define RT_TILE_STATE
+#define RT_ITEM_TAKEN() (px < f.tile_w && py < f.tile_h)
+#define RT_ITEM_PIXEL() ((unsigned long long)py * f.tile_w + px)
+#define RT_ITEM_BEGIN_ARGS f.x0 + px, rt_frame_row(f, py), f.sample_offset + s
+#define RT_XCH_TAIL(flags) RT_PK2((flags), 0u)
+#define RT_XCH_UNTAIL(v) do { } while (0)
+#endif
+
 /* ---- render kernel with workgroup-level reordering ------------------------------------------
  * Same per-path arithmetic as rt_render_kernel; what changes is WHICH LANE runs which path.
  * Every iteration, between the closest-hit search and the shading, the 256 paths of a workgroup
@@ -111,7 +167,7 @@ __device__ __forceinline__ uint32_t lane_prefix(unsigned long long mask) {
 #endif
 template <class Cfg>
 __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, const RtFrame& f, rt_f64* __restrict__ partial,
-                                                      unsigned long long* __restrict__ counters) {
+                                                      unsigned long long* __restrict__ counters RT_TILE_PARAM) {
     constexpr int NW = RT_SORT_BLOCK / 64;
     static_assert(Cfg::sweep, "the reordering kernel is built for the stackless variants");
     __shared__ unsigned long long xch[RT_XCH_PER * RT_SORT_BLOCK];
@@ -127,6 +183,7 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
     unsigned long long item = (unsigned long long)blockIdx.x * RT_SORT_BLOCK + threadIdx.x;
     bool fresh = true, have = false, retired = false;
     uint32_t px = 0, py = 0, chunk = 0, s = 0;
+    RT_TILE_STATE
     RtV3d sum = rt_v3d(RT_R(0.0), RT_R(0.0), RT_R(0.0));
     RtPath path;
     path.alive = false;
@@ -148,7 +205,7 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
         if (!path.alive && !retired) {
             uint32_t s_end = chunk * f.chunk + f.chunk < f.spp ? chunk * f.chunk + f.chunk : f.spp;
             if (have && s == s_end) {
-                rt_f64* dst = partial + ((unsigned long long)chunk * npix + (unsigned long long)py * f.tile_w + px) * 3ull;
+                rt_f64* dst = partial + ((unsigned long long)chunk * npix + RT_ITEM_PIXEL()) * 3ull;
                 dst[0] = sum.x; dst[1] = sum.y; dst[2] = sum.z;
                 have = false;
             }
@@ -166,14 +223,14 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
                 fresh = false;
                 if (item >= n_items) break;
                 rt_item_decode(f, item, px, py, chunk);
-                if (px < f.tile_w && py < f.tile_h) {
+                if (RT_ITEM_TAKEN()) {
                     s = chunk * f.chunk;
                     sum = rt_v3d(RT_R(0.0), RT_R(0.0), RT_R(0.0));
                     have = true;
                 }
             }
             if (!have) retired = true;
-            else rt_path_begin(sc, f, f.x0 + px, rt_frame_row(f, py), f.sample_offset + s, path);
+            else rt_path_begin(sc, f, RT_ITEM_BEGIN_ARGS, path);
         }
         RT_STAMP(1);
         /* 2. closest hit + class */
@@ -223,7 +280,7 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
             st[20] = RT_PK2(path.rng.b2, path.rng.b3);
             st[21] = RT_PK2(tr.prim, tr.scope); st[22] = RT_PK2(tr.cls, path.depth_left);
             st[23] = RT_PK2(px, py); st[24] = RT_PK2(chunk, s);
-            st[25] = RT_PK2((have ? 1u : 0u) | (retired ? 2u : 0u) | (path.alive ? 4u : 0u), 0u);
+            st[25] = RT_XCH_TAIL((have ? 1u : 0u) | (retired ? 2u : 0u) | (path.alive ? 4u : 0u));
 #undef RT_PK2
 #pragma unroll
             for (int part = 0; part < RT_XCH_PARTS; ++part) {
@@ -251,6 +308,7 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
             RT_UP2(st[23], px, py); RT_UP2(st[24], chunk, s);
             const uint32_t flags = (uint32_t)st[25];
             have = (flags & 1u) != 0u; retired = (flags & 2u) != 0u; path.alive = (flags & 4u) != 0u;
+            RT_XCH_UNTAIL(st[25]);
 #undef RT_UP2
         }
         RT_STAMP(7);

@@ -1,32 +1,41 @@
 /* rt_kernels.h -- the render kernels of librt1w.so as __global__ entry points: launch bounds, template arguments and the two small
  * kernels behind them (resolve, quantise).  Their bodies are rt_kernel_sorted.h / rt_kernel_plain.h / rt_walk_pair.h.  Kept apart from
  * context.hip so that the identity of the kernels' source text (bench.py: kernel_sources_id, what a stored PMC measurement is matched
- * against) does not move with host-side edits.  Included by context.hip only. */
+ * against) does not move with host-side edits.  Included by context.hip and, with RT_TILE_LIST defined and inside a namespace of its
+ * own, by context_tiles.hip: every render kernel then takes the tile list (rt_kernel_sorted.h) as its last argument. */
 #ifndef RT_KERNELS_H
 #define RT_KERNELS_H
 
 #include "rt_kernel_plain.h"
 
+#if defined(RT_TILE_LIST)
+#define RT_TILE_KPARAM , RtTileList tl
+#define RT_TILE_KARG , tl
+#else
+#define RT_TILE_KPARAM
+#define RT_TILE_KARG
+#endif
+
 namespace {
 
 template <class Cfg, bool CACHE = false>
 __global__ __launch_bounds__(RT_BLOCK, RT_PLAIN_WAVES(Cfg, CACHE)) void rt_render_kernel(RtSceneView sc, RtFrame f, double* __restrict__ partial,
-                                                                                  unsigned long long* __restrict__ counters) {
-    rt_render_plain_body<Cfg, CACHE>(sc, f, partial, counters);
+                                                                                  unsigned long long* __restrict__ counters RT_TILE_KPARAM) {
+    rt_render_plain_body<Cfg, CACHE>(sc, f, partial, counters RT_TILE_KARG);
 }
 
 /* sphere scenes (random_scene): the plain kernel with the pair walk of rt_walk_pair.h */
 template <class Cfg>
 __global__ __launch_bounds__(RT_BLOCK, RT_STACK_WAVES) void rt_render_kernel_pw(RtSceneView sc, RtPwView pw, RtFrame f, double* __restrict__ partial,
-                                                                           unsigned long long* __restrict__ counters) {
-    rt_render_plain_body<Cfg, false, true>(sc, f, partial, counters, &pw);
+                                                                           unsigned long long* __restrict__ counters RT_TILE_KPARAM) {
+    rt_render_plain_body<Cfg, false, true>(sc, f, partial, counters RT_TILE_KARG, &pw);
 }
 
 /* sliced stack walk + reordering of the finished paths at the end of every slice (rt_kernel_plain.h: rt_render_ss_body) */
 template <class Cfg, int CAP, int PARTS>
 __global__ __launch_bounds__(RT_BLOCK, RT_STACK_WAVES) void rt_render_kernel_ss(RtSceneView sc, RtFrame f, double* __restrict__ partial,
-                                                                           unsigned long long* __restrict__ counters) {
-    rt_render_ss_body<Cfg, CAP, PARTS>(sc, f, partial, counters);
+                                                                           unsigned long long* __restrict__ counters RT_TILE_KPARAM) {
+    rt_render_ss_body<Cfg, CAP, PARTS>(sc, f, partial, counters RT_TILE_KARG);
 }
 
 /* the same with the scene's most visited nodes in LDS (rt_walk_table.h): scenes whose walk needs at most RT_SS_HC_CAP stack entries -- the
@@ -40,10 +49,11 @@ __global__ __launch_bounds__(RT_BLOCK, RT_STACK_WAVES) void rt_render_kernel_ss(
 #endif
 template <class Cfg>
 __global__ __launch_bounds__(RT_BLOCK, RT_STACK_WAVES) void rt_render_kernel_ss_hc(RtSceneView sc, RtFrame f, double* __restrict__ partial,
-                                                                              unsigned long long* __restrict__ counters) {
-    rt_render_ss_body<Cfg, RT_SS_HC_CAP, RT_SS_HC_PARTS, false, RT_SS_HC_RECORDS>(sc, f, partial, counters);
+                                                                              unsigned long long* __restrict__ counters RT_TILE_KPARAM) {
+    rt_render_ss_body<Cfg, RT_SS_HC_CAP, RT_SS_HC_PARTS, false, RT_SS_HC_RECORDS>(sc, f, partial, counters RT_TILE_KARG);
 }
 
+#if !defined(RT_TILE_LIST) /* the walk table's count: the default build's alone */
 /* node visits of a small render, counted per node: what the context ranks the walk table by (context.hip) */
 struct RtCountingNodes {
     static constexpr bool virt = false;
@@ -74,23 +84,25 @@ __global__ void rt_visit_count_kernel(RtSceneView sc, RtFrame f, uint32_t* __res
     }
 }
 
+#endif
 /* the same for sphere scenes: the pair walk in slices + the reordering of the finished paths (RT_PW_SS_STACK, rt_kernel_plain.h) */
 #ifndef RT_SS_CAP
 #define RT_SS_CAP RT_STACK_CAP /* stack entries per lane of the stack-walk kernels that reorder (experiments: 16 for four workgroups per CU) */
 #endif
 template <class Cfg>
 __global__ __launch_bounds__(RT_BLOCK, RT_STACK_WAVES) void rt_render_kernel_pw_ss(RtSceneView sc, RtPwView pw, RtFrame f, double* __restrict__ partial,
-                                                                              unsigned long long* __restrict__ counters) {
-    rt_render_ss_body<Cfg, RT_PW_SS_STACK, RT_PW_SS_PARTS, true>(sc, f, partial, counters, &pw);
+                                                                              unsigned long long* __restrict__ counters RT_TILE_KPARAM) {
+    rt_render_ss_body<Cfg, RT_PW_SS_STACK, RT_PW_SS_PARTS, true>(sc, f, partial, counters RT_TILE_KARG, &pw);
 }
 
 /* the reordering kernel proper (rt_kernel_sorted.h) */
 template <class Cfg>
 __global__ __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES(Cfg)) void rt_render_kernel_sorted(RtSceneView sc, RtFrame f, double* __restrict__ partial,
-                                                                                       unsigned long long* __restrict__ counters) {
-    rt_render_sorted_body<Cfg>(sc, f, partial, counters);
+                                                                                       unsigned long long* __restrict__ counters RT_TILE_KPARAM) {
+    rt_render_sorted_body<Cfg>(sc, f, partial, counters RT_TILE_KARG);
 }
 
+#if !defined(RT_TILE_LIST) /* resolve and quantise serve both forms from context.hip */
 /* Sum the chunk partials of each pixel in chunk order; then Color::into_sampled
  * (color.rs:14-21) unless raw sums were asked for. */
 __global__ void rt_resolve_kernel(const double* __restrict__ partial, double* __restrict__ out,
@@ -121,6 +133,7 @@ __global__ void rt_quantize_kernel(const double* __restrict__ means, uint8_t* __
     dst[0] = (uint8_t)rt_quantize(src[0]); dst[1] = (uint8_t)rt_quantize(src[1]); dst[2] = (uint8_t)rt_quantize(src[2]);
 }
 
+#endif
 } // namespace
 
 #endif

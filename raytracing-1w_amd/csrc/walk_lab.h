@@ -56,6 +56,8 @@ int rt1w_lab_denoised_var_split(uint32_t spp, uint32_t batches, double sigma_var
  * same accumulator, the same frame / var / spp and the same tile errors from host buffers, no GPU; RT1W_ERR_INVALID as the device entries */
 int rt1w_lab_accum_merge_host(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h, uint32_t batch_spp,
                               uint32_t flags, const double* tile_sums, const double* aov, double* acc);
+int rt1w_lab_accum_merge_tiles_host(uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t batch_spp,
+                                    uint32_t flags, const double* tile_sums, const double* aov, double* acc);
 int rt1w_lab_accum_resolve_host(uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc, double* frame, double* var, double* spp);
 int rt1w_lab_tile_error_host(uint32_t width, uint32_t height, uint32_t tile, const double* acc, double* err);
 /* the two functions the filters build their weights from (rt_denoise.h), on their own: out[i] = rt_dn_falloff(x[i]) (fn 0; e may be

@@ -12,10 +12,13 @@ process per case:
   * the split of the call, from one composition of the public device entries whose own timers are summed by kind: the render launches
     (total_ms of every rt1w_render_device, kernel_ms alongside), the merge and tile-error kernels (total_ms and kernel_ms), and the
     per-round device->host copy of the tile errors (host clock around the copy).
+With `--one-launch` every case gets a second column: the call with RT1W_ADAPTIVE_ONE_LAUNCH (every round one rt1w_render_tiles_device of all
+its tiles and one rt1w_accum_merge_tiles_device), its launches, and the same split from the composition over those two entries.  `--case
+NAME:BUDGET` (repeatable; c3:16 is Cornell 600 x 600 at a budget of 16) replaces the default cases.
 Writes one JSON file (default profiles/adaptive_bench.json).  Times are wall-clock medians of a few calls on a shared machine: read them
 to two digits.
 
-usage: python3 tools/adaptive_bench.py [--out FILE] [--reps N] [--parent-root BUILT-CHECKOUT-OF-THE-PARENT]
+usage: python3 tools/adaptive_bench.py [--out FILE] [--reps N] [--parent-root BUILT-CHECKOUT-OF-THE-PARENT] [--one-launch] [--case NAME:BUDGET ...]
 """
 import argparse
 import ctypes as C
@@ -64,12 +67,12 @@ def _runs(taken, m, tx_n, W, H):
     return runs
 
 
-def child_adaptive(arm, W, H, budget, reps):
+def child_adaptive(arm, W, H, budget, reps, one=False):
     import numpy as np
     rt = _rt()
     sc = rt.Scene.reference(arm, build_seed=1)
     ctx = rt.Context(sc, 0)
-    ad = dict(budget_spp=budget)
+    ad = dict(budget_spp=budget, one_launch=True) if one else dict(budget_spp=budget)
     calls = []
     for i in range(1 + reps):
         _, spp, st = ctx.render_adaptive(W, H, adaptive=ad, with_stats=True)
@@ -87,7 +90,7 @@ def child_adaptive(arm, W, H, budget, reps):
     npix = W * H
     tx_n, ty_n = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
     chunk = sc.default_chunk(W, H, n)
-    d_aov, d_sums, d_acc, d_err = alloc(npix * 64), alloc(npix * 24), alloc(npix * 64), alloc(tx_n * ty_n * 8)
+    d_aov, d_sums, d_acc, d_err = alloc(npix * 64), alloc(max(npix, tx_n * ty_n * TILE * TILE) * 24), alloc(npix * 64), alloc(tx_n * ty_n * 8)
     assert hip.hipMemset(C.c_void_p(d_acc), 0, C.c_size_t(npix * 64)) == 0
     ctx.render_aov_device(d_aov, W, H, PILOT * n)
     part = {k: 0.0 for k in ("render_total_ms", "render_kernel_ms", "merge_total_ms", "merge_kernel_ms", "error_total_ms", "error_kernel_ms", "copy_ms")}
@@ -97,6 +100,15 @@ def child_adaptive(arm, W, H, budget, reps):
         nonlocal launches
         s = ctx.render_device(d_sums, W, H, n, tile=tuple(rect), sample_offset=mt * n, chunk=chunk, out_sum=True)
         g = ctx.accum_merge_device(d_acc, d_sums, d_aov, W, H, tuple(rect), n)
+        part["render_total_ms"] += s["total_ms"]; part["render_kernel_ms"] += s["kernel_ms"]
+        part["merge_total_ms"] += g["total_ms"]; part["merge_kernel_ms"] += g["kernel_ms"]
+        launches += 1
+
+    def batch_tiles(taken, m):
+        nonlocal launches
+        tiles = [((t % tx_n) * TILE, (t // tx_n) * TILE, int(m.flat[t]) * n) for t in taken]
+        s = ctx.render_tiles_device(d_sums, W, H, n, TILE, tiles, chunk=chunk, out_sum=True)
+        g = ctx.accum_merge_tiles_device(d_acc, d_sums, d_aov, W, H, TILE, tiles, n)
         part["render_total_ms"] += s["total_ms"]; part["render_kernel_ms"] += s["kernel_ms"]
         part["merge_total_ms"] += g["total_ms"]; part["merge_kernel_ms"] += g["kernel_ms"]
         launches += 1
@@ -115,8 +127,11 @@ def child_adaptive(arm, W, H, budget, reps):
         if not taken:
             break
         rounds += 1
-        for r in _runs(taken, m, tx_n, W, H):
-            batch(r[:4], r[4])
+        if one:
+            batch_tiles(taken, m)
+        else:
+            for r in _runs(taken, m, tx_n, W, H):
+                batch(r[:4], r[4])
         for t in taken:
             m.flat[t] += 1
     assert rounds == calls[-1]["n_chunks"] and launches <= calls[-1]["passes"], "the composition is not the call's plan"
@@ -144,15 +159,22 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "adaptive_bench.json"))
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--parent-root", default=None)
+    ap.add_argument("--one-launch", action="store_true")
+    ap.add_argument("--case", action="append", default=None)
     ap.add_argument("--child", nargs="*")
     a = ap.parse_args()
     if a.child:
         kind, arm, W, H, n, reps = a.child[0], *map(int, a.child[1:])
-        return (child_uniform if kind == "uniform" else child_adaptive)(arm, W, H, n, reps)
+        if kind == "uniform":
+            return child_uniform(arm, W, H, n, reps)
+        return child_adaptive(arm, W, H, n, reps, one=kind == "adaptive1")
+    by_name = {c[0]: c for c in CONFIGS}
+    cases = [(by_name[c.split(":")[0]], int(c.split(":")[1])) for c in a.case] if a.case else [(c, b) for c in CONFIGS for b in BUDGETS]
     rows = []
-    for name, arm, W, H in CONFIGS:
-        for budget in BUDGETS:
+    for (name, arm, W, H), budget in cases:
+        if True:
             ad = run_child(["--child", "adaptive", arm, W, H, budget, a.reps])
+            one = run_child(["--child", "adaptive1", arm, W, H, budget, a.reps]) if a.one_launch else None
             un = run_child(["--child", "uniform", arm, W, H, budget, a.reps])
             par = run_child(["--child", "uniform", arm, W, H, budget, a.reps], root=a.parent_root) if a.parent_root else None
             base = statistics.median((par or un)["total_ms"])
@@ -161,6 +183,12 @@ def main():
                    "uniform_parent_library": par, "adaptive_total_ms": call, "uniform_total_ms": base,
                    "baseline": "parent library" if par else "this library",
                    "extra_beauty_spp": (call - base) / (base / budget)}
+            if one:
+                call1 = statistics.median(one["total_ms"])
+                row.update({"adaptive_one_launch": one, "adaptive_one_launch_total_ms": call1,
+                            "extra_beauty_spp_one_launch": (call1 - base) / (base / budget)})
+                print(f"{name} budget {budget}: one launch per round {call1:.1f} ms ({one['rounds']} rounds, {one['launches']} launches, "
+                      f"{one['passes']} passes); split {one['split']}", flush=True)
             print(f"{name} budget {budget}: adaptive {call:.1f} ms ({ad['rounds']} rounds, {ad['launches']} launches), uniform {base:.1f} ms, "
                   f"+{row['extra_beauty_spp']:.1f} beauty spp; split {ad['split']}", flush=True)
             rows.append(row)
