@@ -11,7 +11,7 @@
  * adds the block's sum to the tile's: no atomics, one fixed order, the same bits as the CPU twin (adaptive_host.cpp).  The accumulator
  * record is 64 bytes per pixel, read and written by its lane as 8 doubles. */
 #include <hip/hip_runtime.h>
-
+#include "rt_feature_launch.h" /* this unit's functions as features.hip calls them: the definitions below are held to it */
 #include <stdint.h>
 #include <string.h>
 

@@ -12,7 +12,7 @@
  * Sweep variants walk with scalar node loads (RtGlobalNodes); stack variants keep their stacks in LDS columns as rt_kernel_plain.h
  * does (RT_STACK_CAP x RT_BLOCK entries).  Built for four waves per SIMD (128 VGPRs); the figures are in DESIGN.md. */
 #include <hip/hip_runtime.h>
-
+#include "rt_feature_launch.h" /* this unit's functions as features.hip calls them: the definitions below are held to it */
 #include <stdint.h>
 #include <type_traits>
 

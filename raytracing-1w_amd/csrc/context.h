@@ -1,6 +1,7 @@
 /* context.h -- the device context as the library's own units see it: context.hip (the context, the render kernels' plan and launch, the
  * render entries) and features.hip (the entries of the feature buffers and the denoiser), with the helpers of the first that the second
- * calls.  Private: nothing here is exported (-fvisibility=hidden, librt1w.map). */
+ * calls: the checks of an rt1w_render_params, the render path without an entry's clock, and dev_grow, through which every grow-on-demand
+ * device buffer of the context and its lanes grows.  Private: nothing here is exported (-fvisibility=hidden, librt1w.map). */
 #ifndef RT1W_CONTEXT_H
 #define RT1W_CONTEXT_H
 
@@ -121,6 +122,11 @@ int validate(const rt1w_context* c, const rt1w_render_params* p); /* null argume
 /* RT1W_FORCE_VARIANT: `*v` becomes the variant the flags name, if they name one (allow_v4: the order-aware V4, which exists in f64 only) */
 int forced_variant(const rt1w_context* c, uint32_t flags, bool allow_v4, int* v);
 double lane_ms(const RtLane& l); /* ms between the two events of the lane, once its stream has drained */
+/* The one way a grow-on-demand device buffer grows: (*p, *have bytes) to at least `need` bytes -- freed and allocated anew, its contents
+ * are not kept, nothing happens while it is large enough.  `what` is the text of a failed allocation ("hipMalloc(framebuffer)"), which
+ * returns RT1W_ERR_NOMEM and leaves the buffer empty.  Serves the framebuffer, a lane's partial sums, the tile list, the denoisers' buffers,
+ * the batch buffer and the accumulator buffer; the strips of rt1w_render_rows pair a device and a pinned host allocation and stay apart. */
+int dev_grow(void** p, size_t* have, size_t need, const char* what);
 int reserve_out(rt1w_context* c, size_t bytes); /* the context's framebuffer, grown to at least `bytes` */
 /* plan, launch on lane 0, wait, stats: what every one-shot render entry runs */
 int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, rt1w_stats* stats);

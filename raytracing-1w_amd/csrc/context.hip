@@ -94,6 +94,14 @@ int validate(const rt1w_context* c, const rt1w_render_params* p) {
     if (rc < 0) set_error(why);
     return rc;
 }
+int dev_grow(void** p, size_t* have, size_t need, const char* what) {
+    if (need <= *have) return RT1W_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *have = 0;
+    if (!hip_ok(hipMalloc(p, need), what)) return RT1W_ERR_NOMEM;
+    *have = need;
+    return RT1W_OK;
+}
 double lane_ms(const RtLane& l) {
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, l.ev0, l.ev1);
@@ -370,14 +378,7 @@ uint32_t chunks_per_pass(const RtLaunch& L, unsigned long long bytes = RT_PARTIA
 }
 
 int lane_reserve_partial(RtLane& l, const RtLaunch& L) {
-    size_t need = (size_t)L.npix * chunks_per_pass(L, L.partial_budget) * 3 * sizeof(double);
-    if (need > l.partial_bytes) {
-        if (l.d_partial) (void)hipFree(l.d_partial);
-        l.d_partial = nullptr; l.partial_bytes = 0;
-        if (!hip_ok(hipMalloc((void**)&l.d_partial, need), "hipMalloc(partial sums)")) return RT1W_ERR_NOMEM;
-        l.partial_bytes = need;
-    }
-    return RT1W_OK;
+    return dev_grow((void**)&l.d_partial, &l.partial_bytes, (size_t)L.npix * chunks_per_pass(L, L.partial_budget) * 3 * sizeof(double), "hipMalloc(partial sums)");
 }
 
 /* the chunk sums of `n_chunks` chunks into the pixels of `out` (rt_resolve_kernel: carry bit 0 adds to earlier passes, bit 1 keeps raw sums) */
@@ -546,13 +547,8 @@ namespace rt1w {
 int tiles_upload(rt1w_context* c, const rt1w_tile* tiles, uint32_t n_tiles, const uint32_t** d_rec) {
     static_assert(sizeof(rt1w_tile) == 16, "the kernels read a tile's record as four 32-bit words");
     const size_t bytes = (size_t)n_tiles * sizeof(rt1w_tile);
-    if (bytes > c->tiles_bytes) {
-        if (c->d_tiles) (void)hipFree(c->d_tiles);
-        c->d_tiles = nullptr; c->tiles_bytes = 0;
-        const size_t grown = bytes < 4096 ? 4096 : bytes * 2;
-        if (!hip_ok(hipMalloc(&c->d_tiles, grown), "hipMalloc(tile list)")) return RT1W_ERR_NOMEM;
-        c->tiles_bytes = grown;
-    }
+    /* a list that outgrows the buffer gets room to spare: 4096 bytes at least, otherwise twice its size */
+    if (bytes > c->tiles_bytes && dev_grow(&c->d_tiles, &c->tiles_bytes, bytes < 4096 ? 4096 : bytes * 2, "hipMalloc(tile list)") < 0) return RT1W_ERR_NOMEM;
     /* nothing of an earlier call is in flight (every entry waits for the lane), so the list may be replaced now */
     if (!hip_ok(hipMemcpy(c->d_tiles, tiles, bytes, hipMemcpyHostToDevice), "tile list copy")) return RT1W_ERR_DEVICE;
     *d_rec = (const uint32_t*)c->d_tiles;
@@ -623,14 +619,7 @@ int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, r
     return render_finish(l, L, stats);
 }
 
-int reserve_out(rt1w_context* c, size_t bytes) {
-    if (bytes <= c->out_bytes) return RT1W_OK;
-    if (c->d_out) (void)hipFree(c->d_out);
-    c->d_out = nullptr; c->out_bytes = 0;
-    if (!hip_ok(hipMalloc((void**)&c->d_out, bytes), "hipMalloc(framebuffer)")) return RT1W_ERR_NOMEM;
-    c->out_bytes = bytes;
-    return RT1W_OK;
-}
+int reserve_out(rt1w_context* c, size_t bytes) { return dev_grow((void**)&c->d_out, &c->out_bytes, bytes, "hipMalloc(framebuffer)"); }
 } // namespace rt1w
 
 extern "C" {

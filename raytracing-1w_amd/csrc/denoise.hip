@@ -16,7 +16,7 @@
  * 8 x 8 blocks, read from memory through L2.  RT_DENOISE_LDS_MASK, bit `level`, says which levels run staged; DESIGN.md section 13 has
  * the measurement behind the default. */
 #include <hip/hip_runtime.h>
-
+#include "rt_feature_launch.h" /* this unit's functions as features.hip calls them: the definitions below are held to it */
 #include <stdint.h>
 #include <string.h>
 

@@ -12,7 +12,7 @@
  * doubles as struct-of-arrays (32 000 / 46 080 B of LDS), then every tap is an LDS read.  Direct (any step): the 25 taps of a wave are
  * 25 8 x 8 blocks, read from memory through L2.  The choice by level is denoise.hip's (DESIGN.md section 13 has its measurement). */
 #include <hip/hip_runtime.h>
-
+#include "rt_feature_launch.h" /* this unit's functions as features.hip calls them: the definitions below are held to it */
 #include <stdint.h>
 #include <string.h>
 

@@ -1,0 +1,41 @@
+/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, denoise.hip, denoise_var.hip and adaptive.hip, declared once.
+ * The functions are extern "C": nothing in their names says what they take, so caller and definition both include this header and the
+ * compiler holds each definition to the declaration the caller sees.  Private (librt1w.map exports none of them).
+ * The *_launch functions enqueue on `stream`, put grid and block of the launch (of the level kernel, for the filters) into launch[0..1]
+ * and return 0, -1 launch failure, -2 parameters refused. */
+#ifndef RT1W_FEATURE_LAUNCH_H
+#define RT1W_FEATURE_LAUNCH_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+extern "C" {
+/* aov.hip: the first-hit feature buffers (rt1w_render_aov), by variant; workgroups of RT_BLOCK work-items that cover the frame's tile */
+const void* rt1w_internal_aov_kernel(int variant);
+const void* rt1w_internal_aov_deep_kernel(int variant); /* rt1w_render_aov_deep: + (max_specular, max_fuzz) before out, a segment counter after */
+unsigned rt1w_internal_aov_grid(const void* frame);
+unsigned rt1w_internal_aov_sizeof(int what);
+/* denoise.hip: the filter of rt1w_denoise; enqueues the prepare pass and the levels */
+int rt1w_internal_denoise_launch(uint32_t w, uint32_t h, uint32_t iterations, uint32_t flags, double sigma_colour, double sigma_normal,
+                                 double sigma_depth, const double* frame, const double* aov, double* out, void* col_a, void* col_b, void* guide,
+                                 hipStream_t stream, unsigned launch[2]);
+unsigned rt1w_internal_denoise_sizeof(int what); /* bytes per pixel of 0 a colour buffer, 1 the guide buffer */
+/* denoise_var.hip: the batch-variance pass and the variance-guided filter */
+int rt1w_internal_batch_variance_launch(uint32_t w, uint32_t h, uint32_t batches, uint32_t batch_spp, uint32_t flags, const double* sums,
+                                        const double* aov, double* frame, double* var, hipStream_t stream, unsigned launch[2]);
+int rt1w_internal_denoise_var_launch(uint32_t w, uint32_t h, uint32_t iterations, uint32_t flags, double sigma_normal, double sigma_depth,
+                                     double sigma_variance, const double* frame, const double* aov, const double* var, double* out, void* col_a,
+                                     void* col_b, void* guide, hipStream_t stream, unsigned launch[2]);
+unsigned rt1w_internal_denoise_var_sizeof(void); /* bytes per pixel of one of its colour buffers */
+/* adaptive.hip: the accumulator kernels */
+int rt1w_internal_accum_merge_launch(uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, uint32_t batch_spp, uint32_t flags,
+                                     const double* sums, const double* aov, double* acc, hipStream_t stream, unsigned launch[2]);
+int rt1w_internal_accum_merge_tiles_launch(uint32_t w, uint32_t h, uint32_t tile, const uint32_t* rec, uint32_t n, uint32_t batch_spp, uint32_t flags,
+                                           const double* sums, const double* aov, double* acc, hipStream_t stream, unsigned launch[2]);
+int rt1w_internal_accum_resolve_launch(uint32_t w, uint32_t h, uint32_t batch_spp, const double* acc, double* frame, double* var, double* spp,
+                                       hipStream_t stream, unsigned launch[2]);
+int rt1w_internal_accum_tile_error_launch(uint32_t w, uint32_t h, uint32_t tile, const double* acc, double* err, hipStream_t stream,
+                                          unsigned launch[2]);
+}
+
+#endif
