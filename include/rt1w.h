@@ -604,6 +604,83 @@ int rt1w_adaptive_select(const rt1w_adaptive_params* params, uint32_t n_tiles_x,
 int rt1w_render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d /* NULL: no filter */,
                          double sigma_variance, double* out_rgb, double* out_spp /* may be NULL */, rt1w_stats* stats);
 
+/* ---- adaptive sampling steered by the error that remains AFTER the filter ----
+ * rt1w_render_adaptive chooses its tiles by the variance of the unfiltered pixel mean and then, if asked, filters: the filter removes the
+ * very noise the plan spent its samples on.  Here the plan is steered by an estimate of the filtered frame's own error, the half-buffer
+ * one (Rousselle et al. 2012): the samples of every pixel are kept in two independent halves A and B, both halves go through the weights
+ * the filter computes for the whole frame, and the squared difference of the two filtered halves measures the noise that is still there.
+ * The estimate is empirical -- it does not rest on the independence assumptions of the variance v' the levels hand on -- and it is a
+ * per-pixel error map of the denoised frame, so target_error means "stop when the picture that will be looked at is this good".
+ * No render kernel is involved beyond being called, and no entry above changes.
+ *
+ * Halves.  Two accumulators acc_a, acc_b, each double[h][w][8] exactly as rt1w_accum_merge keeps it, merged with the same batch_spp = n.
+ *   Batch number b of a pixel (0-based: its samples b n .. b n + n - 1) goes into A when b is even and into B when b is odd.
+ * rt1w_halves_resolve: (acc_a, acc_b) -> frame double[h][w][3], var double[h][w], half_a, half_b double[h][w][3], spp double[h][w].
+ *   Per pixel, with m = m_A + m_B:
+ *     frame  = rt1w_resolve's rule on S_A + S_B (per channel, that one addition) with count m n; (0, 0, 0) for an empty pixel;
+ *     half_x = the same rule on S_x with count m_x n; (0, 0, 0) where m_x = 0;
+ *     spp    = m n as a double;
+ *     var    = the variance of the mean demodulated luminance over all m batches, from the two Welford states combined in this order:
+ *              delta = mean_dB - mean_dA;  M2 = (M2_dA + M2_dB) + ((delta * delta) * (double)(m_A * m_B)) / m;  var = M2 / (m (m - 1));
+ *              0 where m < 2, where either half carries RT1W_ACCUM_NO_ESTIMATE, and where the value is negative or not finite.
+ *   var is NOT bit-equal to rt1w_accum_resolve of one accumulator that received the same batches (another order of the same sums); the
+ *   two agree to 1e-12 relative where the batches' rms deviation is above 0.05 of their mean.  m_A != m_B is handled as defined.
+ *   grid = ceil(w / 16) * ceil(h / 16), block 256; batch_spp 0: RT1W_ERR_INVALID.
+ * rt1w_denoise_var_halves: rt1w_denoise_var, definition for definition, on frame, aov and var -- `out` is BIT-IDENTICAL to
+ *   rt1w_denoise_var of the same three buffers -- and in addition:
+ *     prepare   a_p = half_a / A_p and b_p = half_b / A_p per channel, with the A_p the frame is demodulated with;
+ *     levels    a'_p = sum_q w(p, q) a_q / sum_q w(p, q) over exactly the taps the colour takes (w > 0), in the colour's order, with the
+ *               weight the level computed for the frame; b likewise.  The halves never enter a weight.  A centre pixel whose luminance
+ *               is not finite passes all three values through unchanged;
+ *     finish    d = lum(a' * A_p) - lum(b' * A_p), lum = (0.2126 r + 0.7152 g) + 0.0722 b;
+ *               err_px = ((d * d) * 0.25) / (max(lum(out_p), 0) + 0.01), 0 where that is not finite.  1/4: Var((A + B) / 2) =
+ *               Var(A - B) / 4 for two independent halves of equal count.  The denominator is rt1w_accum_tile_error's: err_px is in the
+ *               units of that entry's e_p.  One squared difference is a one-degree-of-freedom estimate: read it through a tile mean.
+ *   out double[h][w][3] (may be `frame`), err_px double[h][w]; the other buffers are distinct.  The colour record of a level is 88 B per
+ *   pixel (two context buffers, grown on demand), the guide record 64 B.  stats as rt1w_denoise_var.
+ * rt1w_tile_error_map: err_px double[h][w] -> err double[ceil(h / tile)][ceil(w / tile)], the tile mean of a per-pixel map in the
+ *   summation order of rt1w_accum_tile_error (the block tree over the row-major index, then the tile's blocks in row-major order by one
+ *   lane; one workgroup per tile, no atomics).  A value that is negative or not finite counts as 0.  tile as there.
+ * All three are bit-identical to the CPU build (librt1w_lab.so: rt1w_lab_halves_resolve_host, rt1w_lab_denoise_var_halves_host,
+ * rt1w_lab_tile_error_map_host). */
+int rt1w_halves_resolve(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc_a, const double* acc_b, double* frame,
+                        double* var, double* half_a, double* half_b, double* spp, rt1w_stats* stats);
+/* same on device memory of the context's GPU; the seven buffers are distinct.  Synchronises the context's stream before returning. */
+int rt1w_halves_resolve_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batch_spp, const void* d_acc_a, const void* d_acc_b, void* d_frame,
+                               void* d_var, void* d_half_a, void* d_half_b, void* d_spp, rt1w_stats* stats);
+int rt1w_denoise_var_halves(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
+                            const double* half_b, double sigma_variance, double* out, double* err_px, rt1w_stats* stats);
+/* same on device memory of the context's GPU; d_out may equal d_frame, the other buffers are distinct */
+int rt1w_denoise_var_halves_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, const void* d_var,
+                                   const void* d_half_a, const void* d_half_b, double sigma_variance, void* d_out, void* d_err_px, rt1w_stats* stats);
+int rt1w_tile_error_map(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const double* err_px, double* err, rt1w_stats* stats);
+int rt1w_tile_error_map_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const void* d_err_px, void* d_err, rt1w_stats* stats);
+/* One call.  The unit of the plan is a PAIR of batches, one for each half: pilot_batches must be even (RT1W_ERR_INVALID otherwise) and the
+ * pilot is pilot_batches / 2 pairs.  One round's choice is rt1w_adaptive_select, unchanged, with batch_spp = 2 n, pilot_batches =
+ * max(2, pilot_batches / 2) and m = the tile's PAIR count, so its budget, max_spp, round_share and ordering rules hold as written (and
+ * what it refuses of those parameters is refused here).  RT1W_ADAPTIVE_ONE_LAUNCH is accepted and changes nothing: every round is one launch.
+ * In this order:
+ *   1. rt1w_render_aov_device over the PILOT's samples only (spp = pilot_batches * n at p->sample_offset): as in rt1w_render_adaptive these
+ *      feature buffers demodulate every merge and guide the filter -- the same stated limit: the guides have the pilot's sample count;
+ *   2. the pilot: pilot_batches whole-frame rt1w_render_device with RT1W_OUT_SUM, spp = n, sample_offset = p->sample_offset + b n, each
+ *      merged by rt1w_accum_merge_device into A (b even) or B (b odd);
+ *   3. rounds, each of: rt1w_halves_resolve_device; rt1w_denoise_var_halves_device with `d` (NULL: every default) and sigma_variance,
+ *      in place on the resolved frame; rt1w_tile_error_map_device; one device->host copy of err; the select; ONE rt1w_render_tiles_device
+ *      whose list names every taken tile twice -- first all taken tiles, in the order taken, with sample_offset = p->sample_offset +
+ *      2 j n, then all of them again with + (2 j + 1) n, j the tile's pair count -- with RT1W_OUT_SUM, spp = n; two
+ *      rt1w_accum_merge_tiles_device, the first half of the list and of the sums into A, the second into B.  chunk = p->chunk or, if that
+ *      is 0, rt1w_scene_default_chunk(scene, width, height, n) of the WHOLE frame, passed explicitly;
+ *   4. the round that takes nothing ends the loop: ITS filtered frame and error map are the result -- no further filter pass is made;
+ *   5. one device->host copy each into out_rgb[height][width][3] and, if not NULL, out_spp[height][width] and out_err[height][width].
+ * Every pixel's count is a multiple of 2 n and m_A == m_B at every estimate.  Bit-identical to composing these public entries.
+ * Because the rounds go through the tile entries, p->flags must be 0 or RT1W_GENERIC; everything rt1w_render_adaptive refuses is refused
+ * here too: all RT1W_ERR_INVALID.  stats as there: the renders' sums (paths = the samples spent, segments, passes = the pilot's launches +
+ * one per round, times its sample passes); kernel_ms every kernel of the call, every filter pass included; total_ms the whole call;
+ * n_chunks = the number of ROUNDS; grid / block of the filter's level kernel.  Buffers are the context's, grown on demand. */
+int rt1w_render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d /* NULL: defaults */,
+                                  double sigma_variance, double* out_rgb, double* out_spp /* may be NULL */, double* out_err /* may be NULL */,
+                                  rt1w_stats* stats);
+
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory
  * mapping that several single-GPU processes fill with RT1W_OUT_FRAME. */

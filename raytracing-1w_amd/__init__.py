@@ -219,6 +219,14 @@ _sig("rt1w_accum_tile_error_device", C.c_int, _P, _U, _U, _U, _P, _P, C.POINTER(
 _sig("rt1w_adaptive_select", C.c_int, C.POINTER(AdaptiveParams), _U, _U, _U, _U, _P, _P, _P, _U)
 _sig("rt1w_render_adaptive", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(DenoiseParams), C.c_double, _P, _P,
      C.POINTER(Stats))
+_sig("rt1w_halves_resolve", C.c_int, _P, _U, _U, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_halves_resolve_device", C.c_int, _P, _U, _U, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_denoise_var_halves", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, C.c_double, _P, _P, C.POINTER(Stats))
+_sig("rt1w_denoise_var_halves_device", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, C.c_double, _P, _P, C.POINTER(Stats))
+_sig("rt1w_tile_error_map", C.c_int, _P, _U, _U, _U, _P, _P, C.POINTER(Stats))
+_sig("rt1w_tile_error_map_device", C.c_int, _P, _U, _U, _U, _P, _P, C.POINTER(Stats))
+_sig("rt1w_render_adaptive_filtered", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(DenoiseParams), C.c_double, _P, _P,
+     _P, C.POINTER(Stats))
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -286,6 +294,20 @@ def _accum_of(acc):
     if a.ndim != 3 or a.shape[2] != ACCUM_RECORD:
         raise ValueError("acc must be [h, w, 8]")
     return a
+
+
+def _halves_of(frame, half_a, half_b):
+    a, b = (np.ascontiguousarray(x, dtype=np.float64) for x in (half_a, half_b))
+    if a.shape != frame.shape or b.shape != frame.shape:
+        raise ValueError("half_a and half_b must be [h, w, 3] like the frame")
+    return a, b
+
+
+def _error_map_of(err_px):
+    e = np.ascontiguousarray(err_px, dtype=np.float64)
+    if e.ndim != 2:
+        raise ValueError("err_px must be [h, w]")
+    return e
 
 
 def _merge_args(acc, tile_sums, aov, x0, y0):
@@ -816,6 +838,79 @@ class Context:
                                       spp.ctypes.data_as(_P), C.byref(st)))
         return (out, spp, _stats_dict(st)) if with_stats else (out, spp)
 
+    def halves_resolve(self, acc_a, acc_b, batch_spp, with_stats=False):
+        """(frame [h, w, 3], var [h, w], half_a [h, w, 3], half_b [h, w, 3], spp [h, w]) of two accumulators taken as the halves of one
+        frame (rt1w_halves_resolve)."""
+        a, b = _accum_of(acc_a), _accum_of(acc_b)
+        if a.shape != b.shape:
+            raise ValueError("acc_a and acc_b must have one shape")
+        hw = a.shape[:2]
+        frame, var, ha, hb, spp = np.empty(hw + (3,)), np.empty(hw), np.empty(hw + (3,)), np.empty(hw + (3,)), np.empty(hw)
+        st = Stats()
+        _ck(_lib.rt1w_halves_resolve(self._h, a.shape[1], a.shape[0], batch_spp, a.ctypes.data_as(_P), b.ctypes.data_as(_P), frame.ctypes.data_as(_P),
+                                     var.ctypes.data_as(_P), ha.ctypes.data_as(_P), hb.ctypes.data_as(_P), spp.ctypes.data_as(_P), C.byref(st)))
+        return (frame, var, ha, hb, spp, _stats_dict(st)) if with_stats else (frame, var, ha, hb, spp)
+
+    def halves_resolve_device(self, d_acc_a, d_acc_b, d_frame, d_var, d_half_a, d_half_b, d_spp, width, height, batch_spp):
+        """Same on device memory (int addresses).  Returns the stats dict."""
+        st = Stats()
+        _ck(_lib.rt1w_halves_resolve_device(self._h, width, height, batch_spp, C.c_void_p(d_acc_a), C.c_void_p(d_acc_b), C.c_void_p(d_frame),
+                                            C.c_void_p(d_var), C.c_void_p(d_half_a), C.c_void_p(d_half_b), C.c_void_p(d_spp), C.byref(st)))
+        return _stats_dict(st)
+
+    def denoise_var_halves(self, frame, aov, var, half_a, half_b, sigma_variance=0.0, with_stats=False, **kw):
+        """The variance-guided filter carrying the frame's two halves (rt1w_denoise_var_halves): (out [h, w, 3] -- the bits of denoise_var --
+        and err_px [h, w], the half-buffer error of the filtered frame).  kw as denoise_var."""
+        f, a = _frame_and_aov(frame, aov)
+        v = _variance_of(var, f)
+        ha, hb = _halves_of(f, half_a, half_b)
+        p = _denoise_params(f.shape[1], f.shape[0], **kw)
+        out, err = np.empty_like(f), np.empty(f.shape[:2])
+        st = Stats()
+        _ck(_lib.rt1w_denoise_var_halves(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), ha.ctypes.data_as(_P),
+                                         hb.ctypes.data_as(_P), sigma_variance, out.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
+        return (out, err, _stats_dict(st)) if with_stats else (out, err)
+
+    def denoise_var_halves_device(self, d_frame, d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, width, height, sigma_variance=0.0, **kw):
+        """Same on device memory (int addresses); d_out may equal d_frame.  Returns the stats dict."""
+        p = _denoise_params(width, height, **kw)
+        st = Stats()
+        _ck(_lib.rt1w_denoise_var_halves_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_var), C.c_void_p(d_half_a),
+                                                C.c_void_p(d_half_b), sigma_variance, C.c_void_p(d_out), C.c_void_p(d_err_px), C.byref(st)))
+        return _stats_dict(st)
+
+    def tile_error_map(self, err_px, tile, with_stats=False):
+        """The tile means of a per-pixel error map (rt1w_tile_error_map): float64 [ceil(h / tile), ceil(w / tile)]."""
+        e = _error_map_of(err_px)
+        tx, ty = _tiles_of(e.shape[1], e.shape[0], max(int(tile), 1))
+        err = np.empty((ty, tx))
+        st = Stats()
+        _ck(_lib.rt1w_tile_error_map(self._h, e.shape[1], e.shape[0], tile, e.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
+        return (err, _stats_dict(st)) if with_stats else err
+
+    def tile_error_map_device(self, d_err_px, d_err, width, height, tile):
+        st = Stats()
+        _ck(_lib.rt1w_tile_error_map_device(self._h, width, height, tile, C.c_void_p(d_err_px), C.c_void_p(d_err), C.byref(st)))
+        return _stats_dict(st)
+
+    def render_adaptive_filtered(self, width, height, adaptive=None, denoise=None, sigma_variance=0.0, max_depth=50, sample_offset=0, global_seed=0,
+                                 chunk=0, tile=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
+        """Adaptive sampling steered by the filtered frame's half-buffer error, in one call (rt1w_render_adaptive_filtered): (filtered frame
+        [h, w, 3], spp [h, w], err_px [h, w]).  `adaptive`: dict of the keywords of adaptive_params (pilot_batches even), None = defaults;
+        `denoise`: dict of the keywords of Context.denoise_var, None = defaults."""
+        p = self._params(width, height, 0, max_depth, tile, sample_offset, global_seed, chunk, False, kw.pop("variant", None), strips=strips, **kw)
+        p.flags |= flags
+        p.precision = precision
+        a = adaptive_params(**(adaptive or {}))
+        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
+        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
+        spp = np.empty((p.tile_h, p.tile_w), dtype=np.float64)
+        err = np.empty((p.tile_h, p.tile_w), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_adaptive_filtered(self._h, C.byref(p), C.byref(a), C.byref(d) if d is not None else None, sigma_variance,
+                                               out.ctypes.data_as(_P), spp.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
+        return (out, spp, err, _stats_dict(st)) if with_stats else (out, spp, err)
+
     def debug_aabb(self, cases):
         """cases[n, 14] = min3, max3, origin3, direction3, t_min, t_max -> (literal[n], fast[n]) from the device."""
         a = np.ascontiguousarray(cases, dtype=np.float64).reshape(-1, 14)
@@ -1004,6 +1099,55 @@ def tile_error_host(acc, tile):
     rc = fn(a.shape[1], a.shape[0], tile, a.ctypes.data_as(_P), err.ctypes.data_as(_P))
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_tile_error_host")
+    return err
+
+
+def halves_resolve_host(acc_a, acc_b, batch_spp):
+    """CPU twin of Context.halves_resolve (rt1w_lab_halves_resolve_host): (frame, var, half_a, half_b, spp)."""
+    fn = load_lab().rt1w_lab_halves_resolve_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32] * 3 + [_P] * 7
+    a, b = _accum_of(acc_a), _accum_of(acc_b)
+    if a.shape != b.shape:
+        raise ValueError("acc_a and acc_b must have one shape")
+    hw = a.shape[:2]
+    frame, var, ha, hb, spp = np.empty(hw + (3,)), np.empty(hw), np.empty(hw + (3,)), np.empty(hw + (3,)), np.empty(hw)
+    rc = fn(a.shape[1], a.shape[0], batch_spp, a.ctypes.data_as(_P), b.ctypes.data_as(_P), frame.ctypes.data_as(_P), var.ctypes.data_as(_P),
+            ha.ctypes.data_as(_P), hb.ctypes.data_as(_P), spp.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_halves_resolve_host")
+    return frame, var, ha, hb, spp
+
+
+def denoise_var_halves_host(frame, aov, var, half_a, half_b, sigma_variance=0.0, with_halves=False, **kw):
+    """CPU twin of Context.denoise_var_halves (rt1w_lab_denoise_var_halves_host): (out, err_px), what the GPU must equal bit for bit;
+    with_halves: (out, err_px, a', b'), the two filtered halves with the albedo back."""
+    fn = load_lab().rt1w_lab_denoise_var_halves_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, C.c_double, _P, _P, _P, _P]
+    f, a = _frame_and_aov(frame, aov)
+    v = _variance_of(var, f)
+    ha, hb = _halves_of(f, half_a, half_b)
+    p = _denoise_params(f.shape[1], f.shape[0], **kw)
+    out, err, fa, fb = np.empty_like(f), np.empty(f.shape[:2]), np.empty_like(f), np.empty_like(f)
+    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), ha.ctypes.data_as(_P), hb.ctypes.data_as(_P), sigma_variance,
+            out.ctypes.data_as(_P), err.ctypes.data_as(_P), fa.ctypes.data_as(_P) if with_halves else None, fb.ctypes.data_as(_P) if with_halves else None)
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_denoise_var_halves_host")
+    return (out, err, fa, fb) if with_halves else (out, err)
+
+
+def tile_error_map_host(err_px, tile):
+    """CPU twin of Context.tile_error_map (rt1w_lab_tile_error_map_host)."""
+    fn = load_lab().rt1w_lab_tile_error_map_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32] * 3 + [_P] * 2
+    e = _error_map_of(err_px)
+    tx, ty = _tiles_of(e.shape[1], e.shape[0], max(int(tile), 1))
+    err = np.empty((ty, tx))
+    rc = fn(e.shape[1], e.shape[0], tile, e.ctypes.data_as(_P), err.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_tile_error_map_host")
     return err
 
 

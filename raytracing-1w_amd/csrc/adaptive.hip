@@ -1,6 +1,9 @@
-/* adaptive.hip -- the kernels of rt1w_accum_merge, rt1w_accum_resolve and rt1w_accum_tile_error (include/rt1w.h) over rt_adaptive.h.
+/* adaptive.hip -- the kernels of rt1w_accum_merge, rt1w_accum_resolve and rt1w_accum_tile_error (include/rt1w.h) over rt_adaptive.h, and
+ * of rt1w_halves_resolve and rt1w_tile_error_map over rt_denoise_halves.h.
  *
- * rt1w_accum_merge_tiles is the merge over a list of square tiles in one launch.
+ * rt1w_accum_merge_tiles is the merge over a list of square tiles in one launch.  rt1w_halves_resolve is the resolve of two accumulators
+ * as the halves of one frame; rt1w_tile_error_map is the tile error's sum over a per-pixel map instead of the accumulator's e_p: the
+ * same kernel text with another source of the pixel's value.
  * A unit of its own, inside its own namespace (the pattern of denoise_var.hip), so that no other code object moves with it.  The host
  * half is in features.hip, which calls the three launchers below.
  *
@@ -18,6 +21,7 @@
 namespace rtad {
 #include "rt1w_num.h"
 #include "rt_adaptive.h"
+#include "rt_denoise_halves.h"
 
 #define RT_AD_WG 256
 
@@ -71,8 +75,29 @@ __global__ __launch_bounds__(RT_AD_WG) void rt_ad_resolve_kernel(uint32_t w, uin
     spp[i] = s;
 }
 
-/* acc[h][w][8] -> err[tiles_y][tiles_x]; one workgroup per tile */
-__global__ __launch_bounds__(RT_AD_WG) void rt_ad_tile_error_kernel(uint32_t w, uint32_t h, uint32_t tile, const double* __restrict__ acc,
+/* acc_a[h][w][8], acc_b[h][w][8] -> frame[h][w][3], var[h][w], half_a[h][w][3], half_b[h][w][3], spp[h][w] */
+__global__ __launch_bounds__(RT_AD_WG) void rt_ad_halves_resolve_kernel(uint32_t w, uint32_t h, uint32_t batch_spp, const double* __restrict__ acc_a,
+                                                                         const double* __restrict__ acc_b, double* __restrict__ frame, double* __restrict__ var,
+                                                                         double* __restrict__ half_a, double* __restrict__ half_b, double* __restrict__ spp) {
+    const uint32_t blocks_x = (w + RT_AD_BLOCK - 1u) / RT_AD_BLOCK;
+    uint32_t lx, ly;
+    rt_ad_lane_xy(lx, ly);
+    const uint32_t x = (blockIdx.x % blocks_x) * RT_AD_BLOCK + lx, y = (blockIdx.x / blocks_x) * RT_AD_BLOCK + ly;
+    if (x >= w || y >= h) return;
+    const unsigned long long i = (unsigned long long)y * w + x;
+    double f[3], a[3], b[3], v, s;
+    rt_dh_resolve_pixel(batch_spp, acc_a + i * RT_AD_RECORD, acc_b + i * RT_AD_RECORD, f, &v, a, b, &s);
+    frame[i * 3u] = f[0]; frame[i * 3u + 1u] = f[1]; frame[i * 3u + 2u] = f[2];
+    half_a[i * 3u] = a[0]; half_a[i * 3u + 1u] = a[1]; half_a[i * 3u + 2u] = a[2];
+    half_b[i * 3u] = b[0]; half_b[i * 3u + 1u] = b[1]; half_b[i * 3u + 2u] = b[2];
+    var[i] = v;
+    spp[i] = s;
+}
+
+/* MAP false: in = acc[h][w][8], a pixel's value its e_p; MAP true: in = err_px[h][w], the value as rt_dh_map_value takes it
+ * -> err[tiles_y][tiles_x]; one workgroup per tile */
+template <bool MAP>
+__global__ __launch_bounds__(RT_AD_WG) void rt_ad_tile_error_kernel(uint32_t w, uint32_t h, uint32_t tile, const double* __restrict__ in,
                                                                      double* __restrict__ err) {
     __shared__ double v[RT_AD_WG];
     const uint32_t tiles_x = (w + tile - 1u) / tile;
@@ -88,7 +113,11 @@ __global__ __launch_bounds__(RT_AD_WG) void rt_ad_tile_error_kernel(uint32_t w, 
             if (px0 + bx * RT_AD_BLOCK >= w) break;
             const uint32_t x = px0 + bx * RT_AD_BLOCK + lx, y = py0 + by * RT_AD_BLOCK + ly;
             double e = 0.0;
-            if (x < w && y < h) e = rt_ad_pixel_error(acc + ((unsigned long long)y * w + x) * RT_AD_RECORD);
+            if (x < w && y < h) {
+                const unsigned long long i = (unsigned long long)y * w + x;
+                if constexpr (MAP) e = rt_dh_map_value(in[i]);
+                else e = rt_ad_pixel_error(in + i * RT_AD_RECORD);
+            }
             v[ly * RT_AD_BLOCK + lx] = e;
             __syncthreads();
             for (uint32_t stride = 128u; stride >= 1u; stride >>= 1) {
@@ -134,12 +163,30 @@ extern "C" int rt1w_internal_accum_resolve_launch(uint32_t w, uint32_t h, uint32
     hipLaunchKernelGGL(rt_ad_resolve_kernel, dim3(grid), dim3(RT_AD_WG), 0, stream, w, h, batch_spp, acc, frame, var, spp);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-extern "C" int rt1w_internal_accum_tile_error_launch(uint32_t w, uint32_t h, uint32_t tile, const double* acc, double* err, hipStream_t stream,
-                                                     unsigned launch[2]) {
+extern "C" int rt1w_internal_halves_resolve_launch(uint32_t w, uint32_t h, uint32_t batch_spp, const double* acc_a, const double* acc_b, double* frame,
+                                                   double* var, double* half_a, double* half_b, double* spp, hipStream_t stream, unsigned launch[2]) {
+    using namespace rtad;
+    if (!rt_ad_frame_ok(w, h) || batch_spp == 0u) return -2;
+    const unsigned grid = ((w + RT_AD_BLOCK - 1u) / RT_AD_BLOCK) * ((h + RT_AD_BLOCK - 1u) / RT_AD_BLOCK);
+    launch[0] = grid; launch[1] = RT_AD_WG;
+    hipLaunchKernelGGL(rt_ad_halves_resolve_kernel, dim3(grid), dim3(RT_AD_WG), 0, stream, w, h, batch_spp, acc_a, acc_b, frame, var, half_a, half_b, spp);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+/* from_map 0: in = the accumulator (rt1w_accum_tile_error); 1: in = a per-pixel map (rt1w_tile_error_map) */
+static int rt_ad_tile_error_launch(uint32_t w, uint32_t h, uint32_t tile, bool from_map, const double* in, double* err, hipStream_t stream, unsigned launch[2]) {
     using namespace rtad;
     if (!rt_ad_frame_ok(w, h) || !rt_ad_tile_ok(tile)) return -2;
     const unsigned grid = ((w + tile - 1u) / tile) * ((h + tile - 1u) / tile);
     launch[0] = grid; launch[1] = RT_AD_WG;
-    hipLaunchKernelGGL(rt_ad_tile_error_kernel, dim3(grid), dim3(RT_AD_WG), 0, stream, w, h, tile, acc, err);
+    if (from_map) hipLaunchKernelGGL(rt_ad_tile_error_kernel<true>, dim3(grid), dim3(RT_AD_WG), 0, stream, w, h, tile, in, err);
+    else hipLaunchKernelGGL(rt_ad_tile_error_kernel<false>, dim3(grid), dim3(RT_AD_WG), 0, stream, w, h, tile, in, err);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int rt1w_internal_accum_tile_error_launch(uint32_t w, uint32_t h, uint32_t tile, const double* acc, double* err, hipStream_t stream,
+                                                     unsigned launch[2]) {
+    return rt_ad_tile_error_launch(w, h, tile, false, acc, err, stream, launch);
+}
+extern "C" int rt1w_internal_tile_error_map_launch(uint32_t w, uint32_t h, uint32_t tile, const double* err_px, double* err, hipStream_t stream,
+                                                   unsigned launch[2]) {
+    return rt_ad_tile_error_launch(w, h, tile, true, err_px, err, stream, launch);
 }

@@ -1,10 +1,11 @@
-/* adaptive_host.cpp -- the CPU twin of the accumulator kernels (adaptive.hip): rt_adaptive.h compiled for the host (g++,
+/* adaptive_host.cpp -- the CPU twin of the accumulator kernels (adaptive.hip): rt_adaptive.h and rt_denoise_halves.h compiled for the host (g++,
  * -ffp-contract=off like every build of the core).  Diagnostics library only (librt1w_lab.so): the expected side of the GPU tests'
  * bit-equality checks and what the CPU tier's known-answer, plan and quality tests run.  librt1w.so keeps no CPU path. */
 #include <cstring>
 
 #include "rt1w.h"
 #include "rt_adaptive_plan.h"
+#include "rt_denoise_halves.h"
 #include "walk_lab.h"
 
 extern "C" int rt1w_lab_accum_merge_host(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h, uint32_t batch_spp,
@@ -38,8 +39,10 @@ extern "C" int rt1w_lab_accum_resolve_host(uint32_t width, uint32_t height, uint
     return RT1W_OK;
 }
 
-extern "C" int rt1w_lab_tile_error_host(uint32_t width, uint32_t height, uint32_t tile, const double* acc, double* err) {
-    if (!acc || !err || !rt_ad_frame_ok(width, height) || !rt_ad_tile_ok(tile)) return RT1W_ERR_INVALID;
+namespace {
+/* the tile sum of the kernel: value(x, y) of every pixel inside the frame, the block tree, the blocks in row-major order */
+template <class Value>
+void tile_sums(uint32_t width, uint32_t height, uint32_t tile, double* err, Value value) {
     const uint32_t tiles_x = (width + tile - 1u) / tile, tiles_y = (height + tile - 1u) / tile, bw = tile / RT_AD_BLOCK;
     for (uint32_t ty = 0; ty < tiles_y; ++ty)
         for (uint32_t tx = 0; tx < tiles_x; ++tx) {
@@ -51,11 +54,32 @@ extern "C" int rt1w_lab_tile_error_host(uint32_t width, uint32_t height, uint32_
                     for (uint32_t ly = 0; ly < RT_AD_BLOCK; ++ly)
                         for (uint32_t lx = 0; lx < RT_AD_BLOCK; ++lx) {
                             const uint32_t x = px0 + bx * RT_AD_BLOCK + lx, y = py0 + by * RT_AD_BLOCK + ly;
-                            v[ly * RT_AD_BLOCK + lx] = (x < width && y < height) ? rt_ad_pixel_error(acc + ((size_t)y * width + x) * RT_AD_RECORD) : 0.0;
+                            v[ly * RT_AD_BLOCK + lx] = (x < width && y < height) ? value((size_t)y * width + x) : 0.0;
                         }
                     total = total + rt_ad_block_tree(v);
                 }
             err[(size_t)ty * tiles_x + tx] = total / (double)rt_ad_tile_pixels(width, height, tile, tx, ty);
         }
+}
+} // namespace
+
+extern "C" int rt1w_lab_tile_error_host(uint32_t width, uint32_t height, uint32_t tile, const double* acc, double* err) {
+    if (!acc || !err || !rt_ad_frame_ok(width, height) || !rt_ad_tile_ok(tile)) return RT1W_ERR_INVALID;
+    tile_sums(width, height, tile, err, [&](size_t i) { return rt_ad_pixel_error(acc + i * RT_AD_RECORD); });
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_tile_error_map_host(uint32_t width, uint32_t height, uint32_t tile, const double* err_px, double* err) {
+    if (!err_px || !err || !rt_ad_frame_ok(width, height) || !rt_ad_tile_ok(tile)) return RT1W_ERR_INVALID;
+    tile_sums(width, height, tile, err, [&](size_t i) { return rt_dh_map_value(err_px[i]); });
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_halves_resolve_host(uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc_a, const double* acc_b, double* frame,
+                                            double* var, double* half_a, double* half_b, double* spp) {
+    if (!acc_a || !acc_b || !frame || !var || !half_a || !half_b || !spp || !rt_ad_frame_ok(width, height) || batch_spp == 0u) return RT1W_ERR_INVALID;
+    const size_t n = (size_t)width * height;
+    for (size_t i = 0; i < n; ++i)
+        rt_dh_resolve_pixel(batch_spp, acc_a + i * RT_AD_RECORD, acc_b + i * RT_AD_RECORD, frame + i * 3, var + i, half_a + i * 3, half_b + i * 3, spp + i);
     return RT1W_OK;
 }

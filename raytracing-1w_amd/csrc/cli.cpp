@@ -6,10 +6,13 @@
  *   rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B]
  *        [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic]
  *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
- *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch]]
+ *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--err-out FILE]]]
  * --adaptive BUDGET spends a budget of BUDGET mean samples per pixel where the frame is noisy (rt1w_render_adaptive; --spp is ignored),
  * at most --max-spp samples on one pixel, none on tiles whose error is at or below --target-error; with --denoise --variance the
  * variance-guided filter follows (first-hit guides of the pilot's samples; K and --deep-guides do not apply).
+ * --filtered-error steers the plan by the half-buffer error of the FILTERED frame instead (rt1w_render_adaptive_filtered: the variance-guided
+ * filter runs in every round and its last frame is the image; --target-error then means the error of the picture that is printed);
+ * --err-out FILE writes the per-pixel error map of that frame as text, "width height" and then one value per pixel, top row first.
  * --denoise renders through rt1w_render_denoised: the frame, its first-hit feature buffers and the feature-guided filter in one call
  * (default 5 levels), then the PPM of the filtered frame.  --deep-guides [N] (implies --denoise) takes the guides through glass and
  * perfect mirrors instead, up to N specular bounces (default 8, at most 64): rt1w_render_denoised_deep with max_fuzz 0.
@@ -40,6 +43,8 @@ int main(int argc, char** argv) {
     long denoise_iterations = 0, deep_guides = -1, variance = -1; /* -1: first-hit guides; -1: the fixed-sigma filter */
     long adaptive = -1, max_spp = 0; /* -1: every pixel gets --spp samples */
     bool one_launch = false;         /* --adaptive: every round as one launch of all its tiles (RT1W_ADAPTIVE_ONE_LAUNCH) */
+    bool filtered_error = false;     /* --adaptive: rt1w_render_adaptive_filtered */
+    std::string err_path;
     double target_error = 0.0;
     long width = -1, height = -1, spp = -1, depth = 50; /* MAX_DEPTH main.rs:801 */
     unsigned long long build_seed = 1, seed = 0;
@@ -78,10 +83,12 @@ int main(int argc, char** argv) {
         }
         else if (a == "--adaptive") adaptive = std::atol(next("--adaptive"));
         else if (a == "--one-launch") one_launch = true;
+        else if (a == "--filtered-error") filtered_error = true;
+        else if (a == "--err-out") err_path = next("--err-out");
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--target-error") target_error = std::atof(next("--target-error"));
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--err-out FILE]]]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -144,8 +151,10 @@ int main(int argc, char** argv) {
     };
     rt1w_stats st;
     std::fprintf(stderr, "rt1w: scene arm %d, %ldx%ld, %ld spp, depth %ld\n", arm, width, height, spp, depth);
+    if (adaptive < 0 && (filtered_error || !err_path.empty())) { std::fprintf(stderr, "rt1w: --filtered-error and --err-out go with --adaptive\n"); return 2; }
+    if (!err_path.empty() && !filtered_error) { std::fprintf(stderr, "rt1w: --err-out goes with --filtered-error\n"); return 2; }
     if (adaptive >= 0) {
-        if (denoise && variance < 0) { std::fprintf(stderr, "rt1w: --adaptive filters with --denoise --variance only\n"); return 2; }
+        if (denoise && variance < 0 && !filtered_error) { std::fprintf(stderr, "rt1w: --adaptive filters with --denoise --variance only\n"); return 2; }
         rt1w_adaptive_params ap;
         std::memset(&ap, 0, sizeof ap);
         ap.size = (uint32_t)sizeof ap; ap.budget_spp = (uint32_t)adaptive; ap.max_spp = (uint32_t)max_spp; ap.target_error = target_error;
@@ -154,7 +163,18 @@ int main(int argc, char** argv) {
         std::memset(&d, 0, sizeof d);
         d.iterations = denoise_iterations > 0 ? (uint32_t)denoise_iterations : 0u;
         std::vector<double> means((size_t)width * height * 3);
-        if (rt1w_render_adaptive(ctx, &p, &ap, denoise ? &d : nullptr, 0.0, means.data(), nullptr, &st) < 0) return fail("render");
+        if (filtered_error) {
+            std::vector<double> err(err_path.empty() ? 0 : (size_t)width * height);
+            if (rt1w_render_adaptive_filtered(ctx, &p, &ap, &d, 0.0, means.data(), nullptr, err.empty() ? nullptr : err.data(), &st) < 0) return fail("render");
+            if (!err.empty()) {
+                FILE* e = std::fopen(err_path.c_str(), "w");
+                if (!e) { std::perror("rt1w: --err-out"); return 1; }
+                std::fprintf(e, "%u %u\n", p.width, p.height);
+                for (uint32_t r = 0; r < p.height; ++r)
+                    for (uint32_t i = 0; i < p.width; ++i) std::fprintf(e, "%.17g\n", err[(size_t)(p.height - 1u - r) * p.width + i]);
+                std::fclose(e);
+            }
+        } else if (rt1w_render_adaptive(ctx, &p, &ap, denoise ? &d : nullptr, 0.0, means.data(), nullptr, &st) < 0) return fail("render");
         std::fprintf(stderr, "rt1w: adaptive: %.2f samples per pixel in %u rounds, %u render launches\n", (double)st.paths / ((double)width * height), st.n_chunks, st.passes);
         for (uint32_t r = 0; r < p.height; ++r)
             if (rt1w_quantize(means.data() + (size_t)(p.height - 1u - r) * p.width * 3, (uint64_t)p.width * 3, img.data() + (size_t)r * p.width * 3) < 0) return fail("quantize");

@@ -1,4 +1,4 @@
-/* denoise_host.cpp -- the CPU twin of the filter kernels (denoise.hip, denoise_var.hip): rt_denoise.h and rt_denoise_var.h compiled for the host (g++, -ffp-contract=off
+/* denoise_host.cpp -- the CPU twin of the filter kernels (denoise.hip, denoise_var.hip, denoise_halves.hip): rt_denoise.h, rt_denoise_var.h and rt_denoise_halves.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core).  Diagnostics library only (librt1w_lab.so): the expected side of the GPU tests' bit-equality checks
  * and what the CPU tier's property and quality tests run.  librt1w.so keeps no CPU path. */
 #include <cstring>
@@ -8,6 +8,7 @@
 #include "rt1w.h"
 #include "rt_denoise.h"
 #include "rt_denoise_var.h"
+#include "rt_denoise_halves.h"
 #include "walk_lab.h"
 
 namespace {
@@ -100,6 +101,46 @@ extern "C" int rt1w_lab_denoise_var_host(const rt1w_denoise_params* p, const dou
             }
         });
         RtDvCol* t = src; src = dst; dst = t;
+    }
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_denoise_var_halves_host(const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var,
+                                                const double* half_a, const double* half_b, double sigma_variance, double* out, double* err_px,
+                                                double* filtered_a, double* filtered_b) {
+    if (!p || !frame || !aov || !var || !half_a || !half_b || !out || !err_px) return RT1W_ERR_INVALID;
+    RtDnParams P;
+    double sv;
+    if (!rt_dn_make_params(p->width, p->height, p->iterations, p->flags, 0.0, p->sigma_normal, p->sigma_depth, P) || !rt_dv_sigma(sigma_variance, sv)) return RT1W_ERR_INVALID;
+    const double sv2 = sv * sv;
+    const size_t n = (size_t)P.w * P.h;
+    std::vector<RtDhCol> a(n), b(n);
+    std::vector<RtDnGuide> g(n);
+    for_rows(P.h, [&](uint32_t y) {
+        for (uint32_t x = 0; x < P.w; ++x) {
+            const size_t i = (size_t)y * P.w + x;
+            rt_dh_prepare_pixel(P, frame + i * 3, aov + i * 8, var[i], half_a + i * 3, half_b + i * 3, a[i], g[i]);
+        }
+    });
+    RtDhCol* src = a.data();
+    RtDhCol* dst = b.data();
+    for (uint32_t level = 0; level < P.levels; ++level) {
+        const RtDhGlobalSrc s{src, g.data(), P.w};
+        const bool last = level + 1u == P.levels;
+        for_rows(P.h, [&](uint32_t y) {
+            for (uint32_t x = 0; x < P.w; ++x) {
+                const size_t i = (size_t)y * P.w + x;
+                const RtDhCol c = rt_dh_level_pixel(P, sv2, s, x, y, level);
+                if (last) {
+                    rt_dh_finish_pixel(c, g[i], out + i * 3, err_px + i);
+                    /* for the tests: the two filtered halves with the albedo back, the products rt_dh_finish_pixel takes the luminances of */
+                    if (filtered_a) { filtered_a[i * 3] = c.ar * g[i].ar; filtered_a[i * 3 + 1] = c.ag * g[i].ag; filtered_a[i * 3 + 2] = c.ab * g[i].ab; }
+                    if (filtered_b) { filtered_b[i * 3] = c.br * g[i].ar; filtered_b[i * 3 + 1] = c.bg * g[i].ag; filtered_b[i * 3 + 2] = c.bb * g[i].ab; }
+                } else
+                    dst[i] = c;
+            }
+        });
+        RtDhCol* t = src; src = dst; dst = t;
     }
     return RT1W_OK;
 }

@@ -534,6 +534,175 @@ int render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_ada
     });
 }
 
+/* ---- adaptive sampling steered by the filtered frame's half-buffer error (include/rt1w.h: rt1w_halves_resolve, rt1w_denoise_var_halves,
+ * rt1w_tile_error_map, rt1w_render_adaptive_filtered) ---- */
+int halves_resolve_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batch_spp, const double* d_acc_a, const double* d_acc_b, double* d_frame,
+                          double* d_var, double* d_half_a, double* d_half_b, double* d_spp, rt1w_stats* stats) {
+    return lane_run(c, (uint64_t)w * h, "halves resolve", stats, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_halves_resolve_launch(w, h, batch_spp, d_acc_a, d_acc_b, d_frame, d_var, d_half_a, d_half_b, d_spp, stream, launch);
+    });
+}
+int denoise_var_halves_common(rt1w_context* c, const rt1w_denoise_params* p, double sigma_variance, const double* d_frame, const double* d_aov,
+                              const double* d_var, const double* d_half_a, const double* d_half_b, double* d_out, double* d_err_px, rt1w_stats* stats) {
+    const int rc = denoise_reserve(c, (size_t)p->width * p->height, rt1w_internal_denoise_var_halves_sizeof());
+    if (rc < 0) return rc;
+    return lane_run(c, (uint64_t)p->width * p->height, "denoise", stats, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_denoise_var_halves_launch(p->width, p->height, p->iterations, p->flags, p->sigma_normal, p->sigma_depth, sigma_variance, d_frame,
+                                                       d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], stream, launch);
+    });
+}
+int tile_error_map_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const double* d_err_px, double* d_err, rt1w_stats* stats) {
+    return lane_run(c, (uint64_t)w * h, "tile error", stats, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_tile_error_map_launch(w, h, tile, d_err_px, d_err, stream, launch);
+    });
+}
+/* the two rt1w_halves_resolve entries.  Host form: the two accumulators in the accumulator buffer, the five results in the framebuffer */
+int halves_resolve(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batch_spp, const double* acc_a, const double* acc_b, double* frame, double* var,
+                   double* half_a, double* half_b, double* spp, bool host, rt1w_stats* stats) {
+    const int rc = accum_frame_validate(c, w, h);
+    if (rc < 0) return rc;
+    if (batch_spp == 0u) { set_error("halves resolve: batch_spp must be >= 1"); return RT1W_ERR_INVALID; }
+    if (!acc_a || !acc_b || !frame || !var || !half_a || !half_b || !spp) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    const size_t npix = (size_t)w * h;
+    Staged s[] = {{acc_a, nullptr, npix * RT_AD_RECORD, ACCUM_BUFFER, "halves resolve: accumulator copy", nullptr},
+                  {acc_b, nullptr, npix * RT_AD_RECORD, ACCUM_BUFFER, "halves resolve: accumulator copy", nullptr},
+                  {nullptr, frame, npix * 3, FRAMEBUFFER, nullptr, "halves resolve: frame copy"},
+                  {nullptr, var, npix, FRAMEBUFFER, nullptr, "halves resolve: variance copy"},
+                  {nullptr, half_a, npix * 3, FRAMEBUFFER, nullptr, "halves resolve: half copy"},
+                  {nullptr, half_b, npix * 3, FRAMEBUFFER, nullptr, "halves resolve: half copy"},
+                  {nullptr, spp, npix, FRAMEBUFFER, nullptr, "halves resolve: count copy"}};
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
+        return halves_resolve_common(c, w, h, batch_spp, s[0].d_in, s[1].d_in, s[2].d_out, s[3].d_out, s[4].d_out, s[5].d_out, s[6].d_out, st);
+    });
+}
+/* the two rt1w_denoise_var_halves entries: as denoise_var(), with the two halves behind the variance and the error map behind the frame */
+int denoise_var_halves(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
+                       const double* half_b, double sigma_variance, double* out, double* err_px, bool host, rt1w_stats* stats) {
+    int rc = denoise_validate(c, p);
+    if (rc < 0) return rc;
+    if ((rc = sigma_variance_validate(sigma_variance)) < 0) return rc;
+    if (!frame || !aov || !var || !half_a || !half_b || !out || !err_px) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    const size_t npix = (size_t)p->width * p->height;
+    Staged s[] = {{frame, out, npix * 3, FRAMEBUFFER, "denoise: frame copy", "denoise: result copy"},
+                  {nullptr, err_px, npix, FRAMEBUFFER, nullptr, "denoise: error map copy"},
+                  {var, nullptr, npix, FRAMEBUFFER, "denoise: variance copy", nullptr},
+                  {half_a, nullptr, npix * 3, FRAMEBUFFER, "denoise: half copy", nullptr},
+                  {half_b, nullptr, npix * 3, FRAMEBUFFER, "denoise: half copy", nullptr},
+                  {aov, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, "denoise: feature buffer copy", nullptr}};
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
+        return denoise_var_halves_common(c, p, sigma_variance, s[0].d_in, s[5].d_in, s[2].d_in, s[3].d_in, s[4].d_in, s[0].d_out, s[1].d_out, st);
+    });
+}
+int tile_error_map(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const double* err_px, double* err, bool host, rt1w_stats* stats) {
+    const int rc = accum_frame_validate(c, w, h);
+    if (rc < 0) return rc;
+    if (!rt_ad_tile_ok(tile)) { set_error("tile error: tile must be a multiple of 16 in 16 .. 256"); return RT1W_ERR_INVALID; }
+    if (!err_px || !err) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    const size_t npix = (size_t)w * h, ntiles = (size_t)((w + tile - 1u) / tile) * ((h + tile - 1u) / tile);
+    Staged s[] = {{err_px, nullptr, npix, FRAMEBUFFER, "tile error: map copy", nullptr}, {nullptr, err, ntiles, ACCUM_BUFFER, nullptr, "tile error: result copy"}};
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) { return tile_error_map_common(c, w, h, tile, s[0].d_in, s[1].d_out, st); });
+}
+/* rt1w_render_aov_device, the pilot's rt1w_render_device + rt1w_accum_merge_device into the halves in turn, then per round
+ * rt1w_halves_resolve_device, rt1w_denoise_var_halves_device, rt1w_tile_error_map_device, the plan, one rt1w_render_tiles_device and two
+ * rt1w_accum_merge_tiles_device: frame, var, spp, the error map, the feature buffers and the two halves in the framebuffer, a round's
+ * sums in the batch buffer, the two accumulators and the tile errors in the accumulator buffer */
+int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d, double sigma_variance,
+                             double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
+    int rc = sigma_variance_validate(sigma_variance);
+    if (rc < 0) return rc;
+    RtAdPlan plan, pair;
+    if (const char* why = rt_ad_make_pair_plan(a, &plan, &pair)) { set_error(why); return RT1W_ERR_INVALID; }
+    rt1w_render_params q;
+    if (p) { /* what the parameters alone decide comes before anything that needs the context */
+        if ((rc = refuse_named_flag(p->flags, true, " does not apply to rt1w_render_denoised")) < 0) return rc;
+        if (p->flags & ~RT1W_GENERIC) { set_error("rt1w_render_adaptive_filtered: p->flags must be 0 or RT1W_GENERIC (the rounds go through rt1w_render_tiles, which runs the generic kernels)"); return RT1W_ERR_INVALID; }
+        if (p->x0 || p->y0 || p->tile_w != p->width || p->tile_h != p->height) { set_error("rt1w_render_adaptive_filtered takes the whole frame (x0 = y0 = 0, tile_w = width, tile_h = height)"); return RT1W_ERR_INVALID; }
+        q = *p; q.spp = plan.batch_spp; /* p->spp is ignored: validated as one batch */
+    }
+    if ((rc = denoised_render_validate(c, p ? &q : nullptr, out_rgb)) < 0) return rc;
+    if ((unsigned long long)p->sample_offset + plan.max_spp > 0xFFFFFFFFull) { set_error("adaptive: sample_offset + max_spp exceeds 2^32 - 1"); return RT1W_ERR_INVALID; }
+    const uint32_t W = p->width, H = p->height, n = plan.batch_spp;
+    rt1w_denoise_params dp;
+    if ((rc = denoised_filter_params(c, d, W, H, &dp)) < 0) return rc;
+    const size_t npix = (size_t)W * H;
+    const uint32_t tiles_x = (W + plan.tile - 1u) / plan.tile, tiles_y = (H + plan.tile - 1u) / plan.tile;
+    const size_t ntiles = (size_t)tiles_x * tiles_y, tile_px = (size_t)plan.tile * plan.tile;
+    /* a round's batch is whole tiles, every taken tile twice, the edge tiles' pixels beyond the frame included */
+    const size_t batch_px = std::max(npix, 2 * ntiles * tile_px);
+    Staged s[] = {{nullptr, out_rgb, npix * 3, FRAMEBUFFER, nullptr, "adaptive frame copy"}, {nullptr, nullptr, npix, FRAMEBUFFER, nullptr, nullptr},
+                  {nullptr, out_spp, npix, FRAMEBUFFER, nullptr, "adaptive count copy"}, {nullptr, out_err, npix, FRAMEBUFFER, nullptr, "adaptive error map copy"},
+                  {nullptr, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, nullptr, nullptr}, {nullptr, nullptr, npix * 3, FRAMEBUFFER, nullptr, nullptr},
+                  {nullptr, nullptr, npix * 3, FRAMEBUFFER, nullptr, nullptr}, {nullptr, nullptr, batch_px * 3, BATCH_BUFFER, nullptr, nullptr},
+                  {nullptr, nullptr, npix * RT_AD_RECORD, ACCUM_BUFFER, nullptr, nullptr}, {nullptr, nullptr, npix * RT_AD_RECORD, ACCUM_BUFFER, nullptr, nullptr},
+                  {nullptr, nullptr, ntiles, ACCUM_BUFFER, nullptr, nullptr}};
+    return staged_entry(c, true, s, stats, [&](rt1w_stats* st) {
+        double *d_frame = s[0].d_out, *d_var = s[1].d_out, *d_spp = s[2].d_out, *d_err_px = s[3].d_out, *d_aov = s[4].d_out, *d_half_a = s[5].d_out,
+               *d_half_b = s[6].d_out, *d_sums = s[7].d_out, *d_acc_a = s[8].d_out, *d_acc_b = s[9].d_out, *d_err = s[10].d_out;
+        int r;
+        /* the two accumulators lie one behind the other: one clear */
+        if (!hip_ok(hipMemsetAsync(d_acc_a, 0, 2 * npix * RT_AD_RECORD * sizeof(double), c->lane[0].stream), "accumulator clear")) return RT1W_ERR_DEVICE;
+        rt1w_stats sk; /* the last kernel that is no render: its grid and block are reported; other_ms: the time of them all */
+        memset(st, 0, sizeof *st);
+        rt1w_render_params ap = *p; /* the feature buffers of the pilot's samples, by the scene's own variant */
+        ap.flags = 0u; ap.spp = plan.pilot * n;
+        if ((r = render_aov_common(c, &ap, nullptr, d_aov, &sk)) < 0) return r;
+        double other_ms = sk.kernel_ms;
+        rt1w_render_params bp = *p;
+        bp.flags |= RT1W_OUT_SUM;
+        bp.spp = n;
+        bp.chunk = p->chunk ? p->chunk : (c->variant >= 2 ? 1u : rt1w_default_chunk(W, H, n)); /* rt1w_scene_default_chunk of the whole frame */
+        for (uint32_t b = 0; b < plan.pilot; ++b) { /* the pilot: whole-frame batches, even ones into A, odd ones into B */
+            bp.sample_offset = p->sample_offset + b * n;
+            rt1w_stats sb;
+            memset(&sb, 0, sizeof sb);
+            if ((r = render_common(c, &bp, d_sums, &sb)) < 0) return r;
+            if (b == 0u) *st = sb;
+            else stats_add(st, sb);
+            if ((r = accum_merge_common(c, W, H, 0u, 0u, W, H, n, plan.flags, d_sums, d_aov, (b & 1u) ? d_acc_b : d_acc_a, &sk)) < 0) return r;
+            other_ms += sk.kernel_ms;
+        }
+        std::vector<uint32_t> m(ntiles, plan.pilot / 2u); /* pairs per tile */
+        std::vector<double> err(ntiles);
+        std::vector<rt1w_tile> list;
+        uint32_t rounds = 0;
+        for (;;) {
+            /* the estimate: every pixel holds as many batches in A as in B here; the filter runs in place on the resolved frame */
+            if ((r = halves_resolve_common(c, W, H, n, d_acc_a, d_acc_b, d_frame, d_var, d_half_a, d_half_b, d_spp, &sk)) < 0) return r;
+            other_ms += sk.kernel_ms;
+            if ((r = denoise_var_halves_common(c, &dp, sigma_variance, d_frame, d_aov, d_var, d_half_a, d_half_b, d_frame, d_err_px, &sk)) < 0) return r;
+            other_ms += sk.kernel_ms;
+            const rt1w_stats sf = sk; /* the level kernel's grid and block are the ones reported */
+            if ((r = tile_error_map_common(c, W, H, plan.tile, d_err_px, d_err, &sk)) < 0) return r;
+            other_ms += sk.kernel_ms;
+            sk = sf;
+            if (!hip_ok(hipMemcpy(err.data(), d_err, ntiles * sizeof(double), hipMemcpyDeviceToHost), "tile error copy")) return RT1W_ERR_DEVICE;
+            const std::vector<uint32_t> taken = rt_ad_select(pair, tiles_x, tiles_y, W, H, err.data(), m.data());
+            if (taken.empty()) break; /* this round's filtered frame and error map are the result */
+            ++rounds;
+            /* one render launch: every taken tile twice, first all of them with the pair's even batch (for A), then all with the odd one */
+            const uint32_t nt = (uint32_t)taken.size();
+            list.clear();
+            for (uint32_t half = 0; half < 2u; ++half)
+                for (uint32_t t : taken) list.push_back(rt1w_tile{(t % tiles_x) * plan.tile, (t / tiles_x) * plan.tile, (2u * m[t] + half) * n, 0u});
+            bp.sample_offset = p->sample_offset;
+            rt1w_stats sb;
+            memset(&sb, 0, sizeof sb);
+            if ((r = render_tiles_common(c, &bp, plan.tile, list.data(), 2u * nt, d_sums, &sb)) < 0) return r;
+            stats_add(st, sb);
+            if ((r = accum_merge_tiles_common(c, W, H, plan.tile, list.data(), nt, n, plan.flags, d_sums, d_aov, d_acc_a, &sk)) < 0) return r;
+            other_ms += sk.kernel_ms;
+            if ((r = accum_merge_tiles_common(c, W, H, plan.tile, list.data() + nt, nt, n, plan.flags, d_sums + (size_t)nt * tile_px * 3, d_aov, d_acc_b, &sk)) < 0) return r;
+            other_ms += sk.kernel_ms;
+            sk = sf;
+            for (uint32_t t : taken) ++m[t];
+        }
+        st->kernel_ms += other_ms;
+        st->chunk = bp.chunk; st->n_chunks = rounds;
+        st->grid = sk.grid; st->block = sk.block;
+        return RT1W_OK;
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -623,5 +792,33 @@ int rt1w_adaptive_select(const rt1w_adaptive_params* params, uint32_t n_tiles_x,
 int rt1w_render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d, double sigma_variance,
                          double* out_rgb, double* out_spp, rt1w_stats* stats) {
     return render_adaptive(c, p, a, d, sigma_variance, out_rgb, out_spp, stats);
+}
+int rt1w_halves_resolve(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc_a, const double* acc_b, double* frame,
+                        double* var, double* half_a, double* half_b, double* spp, rt1w_stats* stats) {
+    return halves_resolve(c, width, height, batch_spp, acc_a, acc_b, frame, var, half_a, half_b, spp, true, stats);
+}
+int rt1w_halves_resolve_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t batch_spp, const void* d_acc_a, const void* d_acc_b, void* d_frame,
+                               void* d_var, void* d_half_a, void* d_half_b, void* d_spp, rt1w_stats* stats) {
+    return halves_resolve(c, width, height, batch_spp, (const double*)d_acc_a, (const double*)d_acc_b, (double*)d_frame, (double*)d_var, (double*)d_half_a,
+                          (double*)d_half_b, (double*)d_spp, false, stats);
+}
+int rt1w_denoise_var_halves(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
+                            const double* half_b, double sigma_variance, double* out, double* err_px, rt1w_stats* stats) {
+    return denoise_var_halves(c, p, frame, aov, var, half_a, half_b, sigma_variance, out, err_px, true, stats);
+}
+int rt1w_denoise_var_halves_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, const void* d_var,
+                                   const void* d_half_a, const void* d_half_b, double sigma_variance, void* d_out, void* d_err_px, rt1w_stats* stats) {
+    return denoise_var_halves(c, p, (const double*)d_frame, (const double*)d_aov, (const double*)d_var, (const double*)d_half_a, (const double*)d_half_b,
+                              sigma_variance, (double*)d_out, (double*)d_err_px, false, stats);
+}
+int rt1w_tile_error_map(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const double* err_px, double* err, rt1w_stats* stats) {
+    return tile_error_map(c, width, height, tile, err_px, err, true, stats);
+}
+int rt1w_tile_error_map_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const void* d_err_px, void* d_err, rt1w_stats* stats) {
+    return tile_error_map(c, width, height, tile, (const double*)d_err_px, (double*)d_err, false, stats);
+}
+int rt1w_render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d,
+                                  double sigma_variance, double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
+    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, stats);
 }
 } /* extern "C" */

@@ -54,6 +54,21 @@ inline const char* rt_ad_make_plan(const rt1w_adaptive_params* a, RtAdPlan* out)
     return nullptr;
 }
 
+/* The plan of rt1w_render_adaptive_filtered, whose unit is a PAIR of batches, one for each half: *out the plan as given (its pilot even:
+ * pilot / 2 pairs), *pair what one round's choice runs on -- the same plan with batch_spp = 2 n, exactly what rt1w_adaptive_select makes
+ * of the parameters with batch_spp = 2 n and pilot_batches = max(2, pilot / 2), so that a host composing the public entries makes the one
+ * call's choices.  nullptr, or why not (RT1W_ERR_INVALID) */
+inline const char* rt_ad_make_pair_plan(const rt1w_adaptive_params* a, RtAdPlan* out, RtAdPlan* pair) {
+    if (const char* why = rt_ad_make_plan(a, out)) return why;
+    if (out->pilot % 2u) return "adaptive (filtered error): pilot_batches must be even (a pixel receives its batches in pairs, one for each half)";
+    if (out->batch_spp > 0x7FFFFFFFu) return "adaptive (filtered error): batch_spp must be below 2^31 (a pair is 2 batch_spp samples)";
+    rt1w_adaptive_params b = *a;
+    b.tile = out->tile; b.budget_spp = out->budget_spp; b.max_spp = out->max_spp;
+    b.batch_spp = 2u * out->batch_spp;
+    b.pilot_batches = std::max(2u, out->pilot / 2u);
+    return rt_ad_make_plan(&b, pair);
+}
+
 /* the list of rt1w_accum_merge_tiles: nullptr, or why it is refused (RT1W_ERR_INVALID) */
 inline const char* rt_ad_tiles_check(uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t batch_spp, uint32_t flags) {
     if (!rt_ad_frame_ok(w, h)) return "accumulator: width and height must be 1 .. 2^30";

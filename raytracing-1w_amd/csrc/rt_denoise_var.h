@@ -93,9 +93,27 @@ struct RtDvGlobalSrc {
     }
 };
 
-/* level `level` (step 2^level) of pixel (x, y): rt_dn_level_pixel but for the colour term, which every level has --
- * x_colour = 0 where l_p == l_q, else (l_p - l_q)^2 / (sigma_variance^2 (v_p + v_q)), +inf where both variances are 0 -- and for the
- * variance it hands on: v' = sum w^2 v_q / (sum w)^2 over the taps the colour takes, in their order.  sv2 = sigma_variance^2. */
+/* the weight of a tap q that is not the centre p: rt_dn_level_pixel's but for the colour term -- x_colour = 0 where l_p == l_q, else
+ * (l_p - l_q)^2 / (sigma_variance^2 (v_p + v_q)), +inf where both variances are 0.  hw = h(dx, dy); gp, gq: the two guides; pz: u_p is
+ * (0, 0, 0); sv2 = sigma_variance^2.  Shared by the level below and the level of rt_denoise_halves.h: one text for the weight. */
+RT_HD double rt_dv_tap_weight(const RtDnParams& P, double sv2, double hw, const double gp[5], bool pz, double lp, double vp, const double gq[5],
+                              double lq, double vq) {
+    const bool qz = gq[0] == 0.0 && gq[1] == 0.0 && gq[2] == 0.0;
+    double cosv = (gp[0] * gq[0] + gp[1] * gq[1]) + gp[2] * gq[2];
+    cosv = cosv > 0.0 ? (cosv < 1.0 ? cosv : 1.0) : 0.0; /* NaN: 0 */
+    const double wn = (pz && qz) ? 1.0 : rt_dn_powi(cosv, P.normal_power);
+    const bool pinf = gp[3] == RT_INF, qinf = gq[3] == RT_INF;
+    const double zmax = gp[3] > gq[3] ? gp[3] : gq[3];
+    const double xd = (gp[3] == gq[3]) ? 0.0 : ((pinf || qinf) ? RT_INF : rt_abs(gp[3] - gq[3]) / (zmax * P.sigma_depth));
+    const double dl = lp - lq;
+    const double xc = (lp == lq) ? 0.0 : (dl * dl) / (sv2 * (vp + vq)); /* x / 0 = +inf: a converged pixel keeps its value */
+    const double dv = gp[4] - gq[4];
+    const double xv = (dv * dv) * RT_DN_INV_SIGMA_COV2;
+    return (hw * wn) * rt_dn_falloff((xd + xc) + xv);
+}
+
+/* level `level` (step 2^level) of pixel (x, y): rt_dn_level_pixel but for the colour term, which every level has (rt_dv_tap_weight), and
+ * for the variance it hands on: v' = sum w^2 v_q / (sum w)^2 over the taps the colour takes, in their order.  sv2 = sigma_variance^2. */
 template <class Src>
 RT_HD RtDvCol rt_dv_level_pixel(const RtDnParams& P, double sv2, const Src& src, uint32_t x, uint32_t y, uint32_t level) {
     const RtDvCol cp = src.col(x, y);
@@ -118,18 +136,7 @@ RT_HD RtDvCol rt_dv_level_pixel(const RtDnParams& P, double sv2, const Src& src,
                 cq = src.col((uint32_t)xx, (uint32_t)yy);
                 double gq[5];
                 src.guide((uint32_t)xx, (uint32_t)yy, gq);
-                const bool qz = gq[0] == 0.0 && gq[1] == 0.0 && gq[2] == 0.0;
-                double cosv = (gp[0] * gq[0] + gp[1] * gq[1]) + gp[2] * gq[2];
-                cosv = cosv > 0.0 ? (cosv < 1.0 ? cosv : 1.0) : 0.0; /* NaN: 0 */
-                const double wn = (pz && qz) ? 1.0 : rt_dn_powi(cosv, P.normal_power);
-                const bool pinf = gp[3] == RT_INF, qinf = gq[3] == RT_INF;
-                const double zmax = gp[3] > gq[3] ? gp[3] : gq[3];
-                const double xd = (gp[3] == gq[3]) ? 0.0 : ((pinf || qinf) ? RT_INF : rt_abs(gp[3] - gq[3]) / (zmax * P.sigma_depth));
-                const double dl = cp.l - cq.l;
-                const double xc = (cp.l == cq.l) ? 0.0 : (dl * dl) / (sv2 * (cp.v + cq.v)); /* x / 0 = +inf: a converged pixel keeps its value */
-                const double dv = gp[4] - gq[4];
-                const double xv = (dv * dv) * RT_DN_INV_SIGMA_COV2;
-                w = (hw * wn) * rt_dn_falloff((xd + xc) + xv);
+                w = rt_dv_tap_weight(P, sv2, hw, gp, pz, cp.l, cp.v, gq, cq.l, cq.v);
             }
             if (w > 0.0) { /* not for 0 and not for NaN: such a tap contributes nothing, whatever its value */
                 sr += w * cq.r; sg += w * cq.g; sb += w * cq.b; sw += w;

@@ -1,4 +1,4 @@
-/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, denoise.hip, denoise_var.hip and adaptive.hip, declared once.
+/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, denoise.hip, denoise_var.hip, denoise_halves.hip and adaptive.hip, declared once.
  * The functions are extern "C": nothing in their names says what they take, so caller and definition both include this header and the
  * compiler holds each definition to the declaration the caller sees.  Private (librt1w.map exports none of them).
  * The *_launch functions enqueue on `stream`, put grid and block of the launch (of the level kernel, for the filters) into launch[0..1]
@@ -36,6 +36,17 @@ int rt1w_internal_accum_resolve_launch(uint32_t w, uint32_t h, uint32_t batch_sp
                                        hipStream_t stream, unsigned launch[2]);
 int rt1w_internal_accum_tile_error_launch(uint32_t w, uint32_t h, uint32_t tile, const double* acc, double* err, hipStream_t stream,
                                           unsigned launch[2]);
+/* adaptive.hip: two accumulators as the halves of one frame, and the tile error's sum over a per-pixel map */
+int rt1w_internal_halves_resolve_launch(uint32_t w, uint32_t h, uint32_t batch_spp, const double* acc_a, const double* acc_b, double* frame,
+                                        double* var, double* half_a, double* half_b, double* spp, hipStream_t stream, unsigned launch[2]);
+int rt1w_internal_tile_error_map_launch(uint32_t w, uint32_t h, uint32_t tile, const double* err_px, double* err, hipStream_t stream,
+                                        unsigned launch[2]);
+/* denoise_halves.hip: the variance-guided filter carrying the two halves; out and err_px of the last level */
+int rt1w_internal_denoise_var_halves_launch(uint32_t w, uint32_t h, uint32_t iterations, uint32_t flags, double sigma_normal, double sigma_depth,
+                                            double sigma_variance, const double* frame, const double* aov, const double* var, const double* half_a,
+                                            const double* half_b, double* out, double* err_px, void* col_a, void* col_b, void* guide,
+                                            hipStream_t stream, unsigned launch[2]);
+unsigned rt1w_internal_denoise_var_halves_sizeof(void); /* bytes per pixel of one of its colour buffers */
 }
 
 #endif

@@ -60,6 +60,15 @@ int rt1w_lab_accum_merge_tiles_host(uint32_t width, uint32_t height, uint32_t ti
                                     uint32_t flags, const double* tile_sums, const double* aov, double* acc);
 int rt1w_lab_accum_resolve_host(uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc, double* frame, double* var, double* spp);
 int rt1w_lab_tile_error_host(uint32_t width, uint32_t height, uint32_t tile, const double* acc, double* err);
+/* CPU twins of rt1w_halves_resolve, rt1w_denoise_var_halves and rt1w_tile_error_map (adaptive_host.cpp, denoise_host.cpp:
+ * rt_denoise_halves.h built for the host): the same buffers from host buffers, no GPU; RT1W_ERR_INVALID as the device entries.  In the
+ * filter twin `out` may be `frame` */
+int rt1w_lab_halves_resolve_host(uint32_t width, uint32_t height, uint32_t batch_spp, const double* acc_a, const double* acc_b, double* frame,
+                                 double* var, double* half_a, double* half_b, double* spp);
+int rt1w_lab_denoise_var_halves_host(const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
+                                     const double* half_b, double sigma_variance, double* out, double* err_px,
+                                     double* filtered_a /* [h][w][3], may be null: a' * A_p */, double* filtered_b /* likewise */);
+int rt1w_lab_tile_error_map_host(uint32_t width, uint32_t height, uint32_t tile, const double* err_px, double* err);
 /* the two functions the filters build their weights from (rt_denoise.h), on their own: out[i] = rt_dn_falloff(x[i]) (fn 0; e may be
  * null) or rt_dn_powi(x[i], e[i]) (fn 1).  device 0: the host build of denoise_host.cpp, no GPU; device 1: one lane per element on
  * GPU 0 (f32_exact.hip).  RT1W_ERR_INVALID for anything else, null pointers or n = 0 */

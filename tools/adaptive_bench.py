@@ -15,10 +15,17 @@ process per case:
 With `--one-launch` every case gets a second column: the call with RT1W_ADAPTIVE_ONE_LAUNCH (every round one rt1w_render_tiles_device of all
 its tiles and one rt1w_accum_merge_tiles_device), its launches, and the same split from the composition over those two entries.  `--case
 NAME:BUDGET` (repeatable; c3:16 is Cornell 600 x 600 at a budget of 16) replaces the default cases.
+With `--filtered` every case gets a third column, written to a file of its own (`--filtered-out`, default
+profiles/adaptive_filtered_bench.json): rt1w_render_adaptive_filtered (the plan steered by the filtered frame's half-buffer error) at the same
+budget, against rt1w_render_adaptive with RT1W_ADAPTIVE_ONE_LAUNCH and the variance-guided filter (this library's and, with `--parent-root`,
+the parent commit's) and against rt1w_render_denoised_var of the same mean sample count; the split of the call by kind from a composition
+of the public device entries (render launches, filter passes, resolve + tile-error kernels, merges, the err copies); and the level kernel
+of rt1w_denoise_var_halves against rt1w_denoise_var's per step, as differences of kernel_ms between `iterations` k and k - 1.
 Writes one JSON file (default profiles/adaptive_bench.json).  Times are wall-clock medians of a few calls on a shared machine: read them
 to two digits.
 
-usage: python3 tools/adaptive_bench.py [--out FILE] [--reps N] [--parent-root BUILT-CHECKOUT-OF-THE-PARENT] [--one-launch] [--case NAME:BUDGET ...]
+usage: python3 tools/adaptive_bench.py [--out FILE] [--reps N] [--parent-root BUILT-CHECKOUT-OF-THE-PARENT] [--one-launch] [--filtered [--filtered-out FILE]]
+       [--case NAME:BUDGET ...]
 """
 import argparse
 import ctypes as C
@@ -143,6 +150,102 @@ def child_adaptive(arm, W, H, budget, reps, one=False):
                                   "min_spp": float(spp.min()), "split": part}), flush=True)
 
 
+def child_filtered(arm, W, H, budget, reps):
+    """rt1w_render_adaptive_filtered: the call, its split over the public device entries, the filter per step"""
+    import numpy as np
+    rt = _rt()
+    sc = rt.Scene.reference(arm, build_seed=1)
+    ctx = rt.Context(sc, 0)
+    calls = []
+    for i in range(1 + reps):
+        _, spp, _, st = ctx.render_adaptive_filtered(W, H, adaptive=dict(budget_spp=budget), with_stats=True)
+        if i:
+            calls.append(st)
+    hip = C.CDLL("libamdhip64.so")
+
+    def alloc(nbytes):
+        p = C.c_void_p()
+        assert hip.hipMalloc(C.byref(p), C.c_size_t(nbytes)) == 0
+        return p.value
+    n = max(1, budget // BATCH_DIV)
+    pair = dict(tile=TILE, batch_spp=2 * n, pilot_batches=max(2, PILOT // 2), budget_spp=budget, max_spp=MAX_FACTOR * budget, round_share=SHARE)
+    npix = W * H
+    tx_n, ty_n = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
+    chunk = sc.default_chunk(W, H, n)
+    d_aov, d_sums, d_err = alloc(npix * 64), alloc(max(npix, 2 * tx_n * ty_n * TILE * TILE) * 24), alloc(tx_n * ty_n * 8)
+    d_acc = [alloc(npix * 64), alloc(npix * 64)]
+    d_frame, d_var, d_spp, d_epx, d_ha, d_hb = alloc(npix * 24), alloc(npix * 8), alloc(npix * 8), alloc(npix * 8), alloc(npix * 24), alloc(npix * 24)
+    for a in d_acc:
+        assert hip.hipMemset(C.c_void_p(a), 0, C.c_size_t(npix * 64)) == 0
+    ctx.render_aov_device(d_aov, W, H, PILOT * n)
+    kinds = ("render", "merge", "filter", "resolve_error")
+    part = {f"{k}_{t}": 0.0 for k in kinds for t in ("total_ms", "kernel_ms")}
+    part["copy_ms"] = 0.0
+
+    def add(kind, st):
+        part[kind + "_total_ms"] += st["total_ms"]; part[kind + "_kernel_ms"] += st["kernel_ms"]
+    for b in range(PILOT):
+        add("render", ctx.render_device(d_sums, W, H, n, sample_offset=b * n, chunk=chunk, out_sum=True))
+        add("merge", ctx.accum_merge_device(d_acc[b & 1], d_sums, d_aov, W, H, (0, 0, W, H), n))
+    m = np.full((ty_n, tx_n), PILOT // 2, dtype=np.uint32)
+    err = np.empty((ty_n, tx_n))
+    rounds = 0
+    while True:
+        add("resolve_error", ctx.halves_resolve_device(d_acc[0], d_acc[1], d_frame, d_var, d_ha, d_hb, d_spp, W, H, n))
+        add("filter", ctx.denoise_var_halves_device(d_frame, d_aov, d_var, d_ha, d_hb, d_frame, d_epx, W, H))
+        add("resolve_error", ctx.tile_error_map_device(d_epx, d_err, W, H, TILE))
+        t0 = time.perf_counter()
+        assert hip.hipMemcpy(err.ctypes.data_as(C.c_void_p), C.c_void_p(d_err), C.c_size_t(err.nbytes), 2) == 0
+        part["copy_ms"] += (time.perf_counter() - t0) * 1e3
+        taken = rt.adaptive_select(W, H, err, m, **pair)
+        if not taken:
+            break
+        rounds += 1
+        tiles = [((t % tx_n) * TILE, (t // tx_n) * TILE, (2 * int(m.flat[t]) + half) * n) for half in (0, 1) for t in taken]
+        add("render", ctx.render_tiles_device(d_sums, W, H, n, TILE, tiles, chunk=chunk, out_sum=True))
+        k = len(taken)
+        add("merge", ctx.accum_merge_tiles_device(d_acc[0], d_sums, d_aov, W, H, TILE, tiles[:k], n))
+        add("merge", ctx.accum_merge_tiles_device(d_acc[1], d_sums + k * TILE * TILE * 24, d_aov, W, H, TILE, tiles[k:], n))
+        for t in taken:
+            m.flat[t] += 1
+    assert rounds == calls[-1]["n_chunks"], "the composition is not the call's plan"
+    # the filters per step on the last round's buffers: kernel_ms(iterations k) - kernel_ms(iterations k - 1), medians of `reps`
+    d_out = alloc(npix * 24)
+    steps = {"halves": [], "var": []}
+    for name in steps:
+        prev = 0.0
+        for it in range(1, 6):
+            ms = []
+            for i in range(1 + max(reps, 3)):
+                st = (ctx.denoise_var_halves_device(d_frame, d_aov, d_var, d_ha, d_hb, d_out, d_epx, W, H, iterations=it) if name == "halves"
+                      else ctx.denoise_var_device(d_frame, d_aov, d_var, d_out, W, H, iterations=it))
+                if i:
+                    ms.append(st["kernel_ms"])
+            cur = statistics.median(ms)
+            steps[name].append(cur - prev)   # the first entry holds the prepare pass too
+            prev = cur
+    ctx.close()
+    print("ADJSON " + json.dumps({"total_ms": [c["total_ms"] for c in calls], "kernel_ms": [c["kernel_ms"] for c in calls], "rounds": rounds,
+                                  "passes": calls[-1]["passes"], "spent_spp": float(spp.mean()), "max_spp": float(spp.max()), "min_spp": float(spp.min()),
+                                  "split": part, "filter_ms_by_iterations_step": steps,
+                                  "halves_over_var_per_step": [a / b for a, b in zip(steps["halves"], steps["var"])]}), flush=True)
+
+
+def child_existing(arm, W, H, budget, reps, spp_uniform):
+    """what the new call is compared with: rt1w_render_adaptive with RT1W_ADAPTIVE_ONE_LAUNCH and the filter, and rt1w_render_denoised_var of
+    `spp_uniform` samples (a multiple of 4)"""
+    rt = _rt()
+    ctx = rt.Context(rt.Scene.reference(arm, build_seed=1), 0)
+    out = {"adaptive_one_launch_filter": [], "denoised_var": [], "lib": rt.LIB_PATH, "denoised_var_spp": spp_uniform}
+    for i in range(1 + reps):
+        _, _, st = ctx.render_adaptive(W, H, adaptive=dict(budget_spp=budget, one_launch=True), filter=True, with_stats=True)
+        _, sv = ctx.render_denoised_var(W, H, spp_uniform, with_stats=True)
+        if i:
+            out["adaptive_one_launch_filter"].append(st["total_ms"]); out["denoised_var"].append(sv["total_ms"])
+    ctx.close()
+    print("ADJSON " + json.dumps(out), flush=True)
+
+
 def run_child(args, root=None):
     env = dict(os.environ)
     if root:
@@ -161,16 +264,22 @@ def main():
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--one-launch", action="store_true")
     ap.add_argument("--case", action="append", default=None)
+    ap.add_argument("--filtered", action="store_true")
+    ap.add_argument("--filtered-out", default=os.path.join(ROOT, "profiles", "adaptive_filtered_bench.json"))
     ap.add_argument("--child", nargs="*")
     a = ap.parse_args()
     if a.child:
         kind, arm, W, H, n, reps = a.child[0], *map(int, a.child[1:])
         if kind == "uniform":
             return child_uniform(arm, W, H, n, reps)
+        if kind == "filtered":
+            return child_filtered(arm, W, H, n, reps)
+        if kind.startswith("existing"):
+            return child_existing(arm, W, H, n, reps, int(kind[8:]))
         return child_adaptive(arm, W, H, n, reps, one=kind == "adaptive1")
     by_name = {c[0]: c for c in CONFIGS}
     cases = [(by_name[c.split(":")[0]], int(c.split(":")[1])) for c in a.case] if a.case else [(c, b) for c in CONFIGS for b in BUDGETS]
-    rows = []
+    rows, frows = [], []
     for (name, arm, W, H), budget in cases:
         if True:
             ad = run_child(["--child", "adaptive", arm, W, H, budget, a.reps])
@@ -192,10 +301,27 @@ def main():
             print(f"{name} budget {budget}: adaptive {call:.1f} ms ({ad['rounds']} rounds, {ad['launches']} launches), uniform {base:.1f} ms, "
                   f"+{row['extra_beauty_spp']:.1f} beauty spp; split {ad['split']}", flush=True)
             rows.append(row)
+            if a.filtered:
+                fl = run_child(["--child", "filtered", arm, W, H, budget, a.reps])
+                spp4 = max(4, int(round(fl["spent_spp"] / 4.0)) * 4)
+                ex = run_child(["--child", f"existing{spp4}", arm, W, H, budget, a.reps])
+                exp = run_child(["--child", f"existing{spp4}", arm, W, H, budget, a.reps], root=a.parent_root) if a.parent_root else None
+                frow = {"config": name, "arm": arm, "width": W, "height": H, "budget_spp": budget, "filtered": fl, "existing_this_library": ex,
+                        "existing_parent_library": exp, "filtered_total_ms": statistics.median(fl["total_ms"]),
+                        "adaptive_one_launch_filter_total_ms": statistics.median((exp or ex)["adaptive_one_launch_filter"]),
+                        "denoised_var_total_ms": statistics.median((exp or ex)["denoised_var"]), "baseline": "parent library" if exp else "this library"}
+                print(f"{name} budget {budget}: filtered error {frow['filtered_total_ms']:.1f} ms ({fl['rounds']} rounds, {fl['passes']} passes), adaptive one launch + "
+                      f"filter {frow['adaptive_one_launch_filter_total_ms']:.1f} ms, denoised_var at {spp4} spp {frow['denoised_var_total_ms']:.1f} ms; split {fl['split']}; "
+                      f"halves / var level kernel per step {['%.2f' % x for x in fl['halves_over_var_per_step']]}", flush=True)
+                frows.append(frow)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump({"tool": "tools/adaptive_bench.py", "reps": a.reps, "rows": rows}, f, indent=1)
         f.write("\n")
+    if a.filtered:
+        with open(a.filtered_out, "w") as f:
+            json.dump({"tool": "tools/adaptive_bench.py --filtered", "reps": a.reps, "rows": frows}, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
