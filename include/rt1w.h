@@ -681,6 +681,46 @@ int rt1w_render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, 
                                   double sigma_variance, double* out_rgb, double* out_spp /* may be NULL */, double* out_err /* may be NULL */,
                                   rt1w_stats* stats);
 
+/* ---- cross-filtered half buffers: an error map that is not blind to the weights' own error ----
+ * rt1w_denoise_var_halves sends both halves through ONE set of weights, computed from the whole noisy frame: whatever error enters through
+ * the weights is common to a' and b' and cancels in their difference, so its map orders tiles but understates the filtered frame's
+ * seed-to-seed variance.  Here each half is filtered with weights whose colour term comes from the OTHER half
+ * (Rousselle et al. 2012): the two filtered halves share no weight, and no weight is computed from the value it multiplies, so a pixel
+ * no longer prefers the neighbours that share its own noise.  Like every filter here it replaces nothing of the reference, which has
+ * sample count alone (src/main.rs:939).  No entry above changes.
+ * rt1w_denoise_cross: the buffers of rt1w_denoise_var_halves.  `frame` gives no value, only its finiteness (below).
+ *   Prepare.  A_p, the guides and v_p (var, 0 where negative or not finite) as rt1w_denoise_var.  a_p = half_a / A_p, b_p = half_b / A_p per
+ *     channel; la_p, lb_p their luminances (0.2126 r + 0.7152 g) + 0.0722 b; va_p = vb_p = 2 v_p: a half of equal count has twice the
+ *     variance of the whole mean (var is the buffer rt1w_halves_resolve writes).  A weight here never sees the value it multiplies, so
+ *     what is not finite is kept out at this point: where the luminance of frame / A_p, la_p or lb_p is not finite, the first of these three
+ *     that is not stands for BOTH la_p and lb_p -- the pixel is passed through every level and no other pixel takes it, in either half.
+ *   Level i.  Step, taps, order, h, w_normal, x_depth, x_coverage and k as rt1w_denoise_var.  Two weights per tap that is not the centre:
+ *     wA(p, q), which filters A, has x_colour = 0 where lb_p == lb_q, else (lb_p - lb_q)^2 / (sigma_variance^2 * (vb_p + vb_q));
+ *     wB(p, q), which filters B, the same of la, va.  The centre tap has wA = wB = h(0, 0).
+ *       a'_p  = sum wA a_q / sum wA over the taps with wA > 0, in tap order;  la'_p = the luminance of a'_p;
+ *       va'_p = sum wA^2 va_q / (sum wA)^2 over the same taps;                 b', lb', vb' likewise with wB.
+ *     A centre whose la or lb is not finite passes its whole record through unchanged.  Every level has the colour term and
+ *     sigma_variance is not halved, as in rt1w_denoise_var.
+ *   Finish.  out = ((a' + b') * 0.5) * A_p per channel: the plain mean, which assumes m_A == m_B (rt1w_render_adaptive_cross guarantees it).
+ *     d = lum(a' * A_p) - lum(b' * A_p);  err_px = ((d * d) * 0.25) / (max(lum(out_p), 0) + 0.01), 0 where that is not finite: the units of
+ *     rt1w_denoise_var_halves's map, so rt1w_tile_error_map and the plan run on it unchanged.
+ *   `out` is NOT the bits of rt1w_denoise_var.  With half_a == half_b == frame each half's (a', la') is the bits of rt1w_denoise_var's
+ *   (c', l') of that frame with the variance 2 var, and err_px is 0.
+ *   out double[h][w][3] (may be `frame`), err_px double[h][w]; the other buffers are distinct.  The colour record of a level is 80 B per
+ *   pixel (two context buffers, grown on demand), the guide record 64 B.  Refuses what rt1w_denoise_var_halves refuses; stats as there.
+ *   Bit-identical to the CPU build (librt1w_lab.so: rt1w_lab_denoise_cross_host). */
+int rt1w_denoise_cross(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
+                       const double* half_b, double sigma_variance, double* out, double* err_px, rt1w_stats* stats);
+/* same on device memory of the context's GPU; d_out may equal d_frame, the other buffers are distinct */
+int rt1w_denoise_cross_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, const void* d_var,
+                              const void* d_half_a, const void* d_half_b, double sigma_variance, void* d_out, void* d_err_px, rt1w_stats* stats);
+/* One call: rt1w_render_adaptive_filtered, step for step, with rt1w_denoise_cross_device in place of rt1w_denoise_var_halves_device in
+ * step 3.  The same parameters, refusals (under this entry's name), buffers and stats; bit-identical to composing the public entries.
+ * An entry of its own rather than a bit of rt1w_adaptive_params.flags. */
+int rt1w_render_adaptive_cross(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d /* NULL: defaults */,
+                               double sigma_variance, double* out_rgb, double* out_spp /* may be NULL */, double* out_err /* may be NULL */,
+                               rt1w_stats* stats);
+
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory
  * mapping that several single-GPU processes fill with RT1W_OUT_FRAME. */

@@ -227,6 +227,10 @@ _sig("rt1w_tile_error_map", C.c_int, _P, _U, _U, _U, _P, _P, C.POINTER(Stats))
 _sig("rt1w_tile_error_map_device", C.c_int, _P, _U, _U, _U, _P, _P, C.POINTER(Stats))
 _sig("rt1w_render_adaptive_filtered", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(DenoiseParams), C.c_double, _P, _P,
      _P, C.POINTER(Stats))
+_sig("rt1w_denoise_cross", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, C.c_double, _P, _P, C.POINTER(Stats))
+_sig("rt1w_denoise_cross_device", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, C.c_double, _P, _P, C.POINTER(Stats))
+_sig("rt1w_render_adaptive_cross", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(DenoiseParams), C.c_double, _P, _P,
+     _P, C.POINTER(Stats))
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -861,14 +865,22 @@ class Context:
     def denoise_var_halves(self, frame, aov, var, half_a, half_b, sigma_variance=0.0, with_stats=False, **kw):
         """The variance-guided filter carrying the frame's two halves (rt1w_denoise_var_halves): (out [h, w, 3] -- the bits of denoise_var --
         and err_px [h, w], the half-buffer error of the filtered frame).  kw as denoise_var."""
+        return self._halves_filter(_lib.rt1w_denoise_var_halves, frame, aov, var, half_a, half_b, sigma_variance, with_stats, kw)
+
+    def denoise_cross(self, frame, aov, var, half_a, half_b, sigma_variance=0.0, with_stats=False, **kw):
+        """The two halves, each filtered with the other's colour term (rt1w_denoise_cross): (out [h, w, 3], the mean of the two filtered
+        halves -- NOT the bits of denoise_var -- and err_px [h, w], their squared difference as the error of that frame).  kw as denoise_var."""
+        return self._halves_filter(_lib.rt1w_denoise_cross, frame, aov, var, half_a, half_b, sigma_variance, with_stats, kw)
+
+    def _halves_filter(self, fn, frame, aov, var, half_a, half_b, sigma_variance, with_stats, kw):
         f, a = _frame_and_aov(frame, aov)
         v = _variance_of(var, f)
         ha, hb = _halves_of(f, half_a, half_b)
         p = _denoise_params(f.shape[1], f.shape[0], **kw)
         out, err = np.empty_like(f), np.empty(f.shape[:2])
         st = Stats()
-        _ck(_lib.rt1w_denoise_var_halves(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), ha.ctypes.data_as(_P),
-                                         hb.ctypes.data_as(_P), sigma_variance, out.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
+        _ck(fn(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), ha.ctypes.data_as(_P), hb.ctypes.data_as(_P),
+               sigma_variance, out.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
         return (out, err, _stats_dict(st)) if with_stats else (out, err)
 
     def denoise_var_halves_device(self, d_frame, d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, width, height, sigma_variance=0.0, **kw):
@@ -877,6 +889,14 @@ class Context:
         st = Stats()
         _ck(_lib.rt1w_denoise_var_halves_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_var), C.c_void_p(d_half_a),
                                                 C.c_void_p(d_half_b), sigma_variance, C.c_void_p(d_out), C.c_void_p(d_err_px), C.byref(st)))
+        return _stats_dict(st)
+
+    def denoise_cross_device(self, d_frame, d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, width, height, sigma_variance=0.0, **kw):
+        """Context.denoise_cross on device memory (int addresses); d_out may equal d_frame.  Returns the stats dict."""
+        p = _denoise_params(width, height, **kw)
+        st = Stats()
+        _ck(_lib.rt1w_denoise_cross_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_var), C.c_void_p(d_half_a),
+                                           C.c_void_p(d_half_b), sigma_variance, C.c_void_p(d_out), C.c_void_p(d_err_px), C.byref(st)))
         return _stats_dict(st)
 
     def tile_error_map(self, err_px, tile, with_stats=False):
@@ -898,6 +918,18 @@ class Context:
         """Adaptive sampling steered by the filtered frame's half-buffer error, in one call (rt1w_render_adaptive_filtered): (filtered frame
         [h, w, 3], spp [h, w], err_px [h, w]).  `adaptive`: dict of the keywords of adaptive_params (pilot_batches even), None = defaults;
         `denoise`: dict of the keywords of Context.denoise_var, None = defaults."""
+        return self._render_adaptive_halves(_lib.rt1w_render_adaptive_filtered, width, height, adaptive, denoise, sigma_variance, max_depth, sample_offset,
+                                            global_seed, chunk, tile, flags, strips, precision, with_stats, kw)
+
+    def render_adaptive_cross(self, width, height, adaptive=None, denoise=None, sigma_variance=0.0, max_depth=50, sample_offset=0, global_seed=0,
+                              chunk=0, tile=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
+        """render_adaptive_filtered with the cross filter (rt1w_render_adaptive_cross): every round's estimate is Context.denoise_cross, so the
+        frame is the mean of the two cross-filtered halves and err_px their squared difference.  Same arguments and results."""
+        return self._render_adaptive_halves(_lib.rt1w_render_adaptive_cross, width, height, adaptive, denoise, sigma_variance, max_depth, sample_offset,
+                                            global_seed, chunk, tile, flags, strips, precision, with_stats, kw)
+
+    def _render_adaptive_halves(self, fn, width, height, adaptive, denoise, sigma_variance, max_depth, sample_offset, global_seed, chunk, tile, flags,
+                                strips, precision, with_stats, kw):
         p = self._params(width, height, 0, max_depth, tile, sample_offset, global_seed, chunk, False, kw.pop("variant", None), strips=strips, **kw)
         p.flags |= flags
         p.precision = precision
@@ -907,8 +939,8 @@ class Context:
         spp = np.empty((p.tile_h, p.tile_w), dtype=np.float64)
         err = np.empty((p.tile_h, p.tile_w), dtype=np.float64)
         st = Stats()
-        _ck(_lib.rt1w_render_adaptive_filtered(self._h, C.byref(p), C.byref(a), C.byref(d) if d is not None else None, sigma_variance,
-                                               out.ctypes.data_as(_P), spp.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
+        _ck(fn(self._h, C.byref(p), C.byref(a), C.byref(d) if d is not None else None, sigma_variance, out.ctypes.data_as(_P), spp.ctypes.data_as(_P),
+               err.ctypes.data_as(_P), C.byref(st)))
         return (out, spp, err, _stats_dict(st)) if with_stats else (out, spp, err)
 
     def debug_aabb(self, cases):
@@ -1135,6 +1167,24 @@ def denoise_var_halves_host(frame, aov, var, half_a, half_b, sigma_variance=0.0,
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_denoise_var_halves_host")
     return (out, err, fa, fb) if with_halves else (out, err)
+
+
+def denoise_cross_host(frame, aov, var, half_a, half_b, sigma_variance=0.0, with_record=False, **kw):
+    """CPU twin of Context.denoise_cross (rt1w_lab_denoise_cross_host): (out, err_px), what the GPU must equal bit for bit; with_record:
+    (out, err_px, rec [h, w, 10]), the last level's record before the finish -- a' rgb, la', va', b' rgb, lb', vb', still demodulated."""
+    fn = load_lab().rt1w_lab_denoise_cross_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, C.c_double, _P, _P, _P]
+    f, a = _frame_and_aov(frame, aov)
+    v = _variance_of(var, f)
+    ha, hb = _halves_of(f, half_a, half_b)
+    p = _denoise_params(f.shape[1], f.shape[0], **kw)
+    out, err, rec = np.empty_like(f), np.empty(f.shape[:2]), np.empty(f.shape[:2] + (10,))
+    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), ha.ctypes.data_as(_P), hb.ctypes.data_as(_P), sigma_variance,
+            out.ctypes.data_as(_P), err.ctypes.data_as(_P), rec.ctypes.data_as(_P) if with_record else None)
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_denoise_cross_host")
+    return (out, err, rec) if with_record else (out, err)
 
 
 def tile_error_map_host(err_px, tile):

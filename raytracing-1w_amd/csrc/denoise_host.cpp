@@ -1,4 +1,4 @@
-/* denoise_host.cpp -- the CPU twin of the filter kernels (denoise.hip, denoise_var.hip, denoise_halves.hip): rt_denoise.h, rt_denoise_var.h and rt_denoise_halves.h compiled for the host (g++, -ffp-contract=off
+/* denoise_host.cpp -- the CPU twin of the filter kernels (denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip): rt_denoise.h, rt_denoise_var.h, rt_denoise_halves.h and rt_denoise_cross.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core).  Diagnostics library only (librt1w_lab.so): the expected side of the GPU tests' bit-equality checks
  * and what the CPU tier's property and quality tests run.  librt1w.so keeps no CPU path. */
 #include <cstring>
@@ -9,6 +9,7 @@
 #include "rt_denoise.h"
 #include "rt_denoise_var.h"
 #include "rt_denoise_halves.h"
+#include "rt_denoise_cross.h"
 #include "walk_lab.h"
 
 namespace {
@@ -141,6 +142,44 @@ extern "C" int rt1w_lab_denoise_var_halves_host(const rt1w_denoise_params* p, co
             }
         });
         RtDhCol* t = src; src = dst; dst = t;
+    }
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_denoise_cross_host(const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
+                                           const double* half_b, double sigma_variance, double* out, double* err_px, double* rec) {
+    if (!p || !frame || !aov || !var || !half_a || !half_b || !out || !err_px) return RT1W_ERR_INVALID;
+    RtDnParams P;
+    double sv;
+    /* sigma_colour is not used by this filter, but the entries refuse a bad one (denoise_validate): so does the twin */
+    if (!rt_dn_make_params(p->width, p->height, p->iterations, p->flags, p->sigma_colour, p->sigma_normal, p->sigma_depth, P) || !rt_dv_sigma(sigma_variance, sv)) return RT1W_ERR_INVALID;
+    const double sv2 = sv * sv;
+    const size_t n = (size_t)P.w * P.h;
+    std::vector<RtDcCol> a(n), b(n);
+    std::vector<RtDnGuide> g(n);
+    for_rows(P.h, [&](uint32_t y) {
+        for (uint32_t x = 0; x < P.w; ++x) {
+            const size_t i = (size_t)y * P.w + x;
+            rt_dc_prepare_pixel(P, frame + i * 3, aov + i * 8, var[i], half_a + i * 3, half_b + i * 3, a[i], g[i]);
+        }
+    });
+    RtDcCol* src = a.data();
+    RtDcCol* dst = b.data();
+    for (uint32_t level = 0; level < P.levels; ++level) {
+        const RtDcGlobalSrc s{src, g.data(), P.w};
+        const bool last = level + 1u == P.levels;
+        for_rows(P.h, [&](uint32_t y) {
+            for (uint32_t x = 0; x < P.w; ++x) {
+                const size_t i = (size_t)y * P.w + x;
+                const RtDcCol c = rt_dc_level_pixel(P, sv2, s, x, y, level);
+                if (last) {
+                    rt_dc_finish_pixel(c, g[i], out + i * 3, err_px + i);
+                    if (rec) memcpy(rec + i * 10, &c, sizeof c);
+                } else
+                    dst[i] = c;
+            }
+        });
+        RtDcCol* t = src; src = dst; dst = t;
     }
     return RT1W_OK;
 }

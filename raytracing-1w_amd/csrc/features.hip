@@ -1,6 +1,6 @@
 /* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_denoise*,
  * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_render_adaptive).  Host code only, built without a device pass: the kernels
- * belong to aov.hip, denoise.hip, denoise_var.hip and adaptive.hip and are reached through rt_feature_launch.h, the context and its render
+ * belong to aov.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip and adaptive.hip and are reached through rt_feature_launch.h, the context and its render
  * path belong to context.hip (context.h), so a change here rebuilds none of the code objects.
  * Every entry is its checks, in the order its callers know, then one table of its buffers (Staged) handed to staged_entry(), which does what
  * the host and the device form of an entry differ in -- growing the context's buffers, laying the call's buffers out in them, the copies
@@ -535,7 +535,7 @@ int render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_ada
 }
 
 /* ---- adaptive sampling steered by the filtered frame's half-buffer error (include/rt1w.h: rt1w_halves_resolve, rt1w_denoise_var_halves,
- * rt1w_tile_error_map, rt1w_render_adaptive_filtered) ---- */
+ * rt1w_tile_error_map, rt1w_render_adaptive_filtered; rt1w_denoise_cross, rt1w_render_adaptive_cross) ---- */
 int halves_resolve_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batch_spp, const double* d_acc_a, const double* d_acc_b, double* d_frame,
                           double* d_var, double* d_half_a, double* d_half_b, double* d_spp, rt1w_stats* stats) {
     return lane_run(c, (uint64_t)w * h, "halves resolve", stats, [&](hipStream_t stream, unsigned* launch) {
@@ -551,6 +551,19 @@ int denoise_var_halves_common(rt1w_context* c, const rt1w_denoise_params* p, dou
                                                        d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], stream, launch);
     });
 }
+/* the same for rt1w_denoise_cross: two colour buffers of 80 B per pixel */
+int denoise_cross_common(rt1w_context* c, const rt1w_denoise_params* p, double sigma_variance, const double* d_frame, const double* d_aov,
+                         const double* d_var, const double* d_half_a, const double* d_half_b, double* d_out, double* d_err_px, rt1w_stats* stats) {
+    const int rc = denoise_reserve(c, (size_t)p->width * p->height, rt1w_internal_denoise_cross_sizeof());
+    if (rc < 0) return rc;
+    return lane_run(c, (uint64_t)p->width * p->height, "denoise", stats, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_denoise_cross_launch(p->width, p->height, p->iterations, p->flags, p->sigma_normal, p->sigma_depth, sigma_variance, d_frame,
+                                                  d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], stream, launch);
+    });
+}
+/* the filter of a frame's two halves: denoise_var_halves_common or denoise_cross_common */
+typedef int (*HalvesFilter)(rt1w_context*, const rt1w_denoise_params*, double, const double*, const double*, const double*, const double*, const double*, double*,
+                            double*, rt1w_stats*);
 int tile_error_map_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const double* d_err_px, double* d_err, rt1w_stats* stats) {
     return lane_run(c, (uint64_t)w * h, "tile error", stats, [&](hipStream_t stream, unsigned* launch) {
         return rt1w_internal_tile_error_map_launch(w, h, tile, d_err_px, d_err, stream, launch);
@@ -575,9 +588,10 @@ int halves_resolve(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batch_spp, 
         return halves_resolve_common(c, w, h, batch_spp, s[0].d_in, s[1].d_in, s[2].d_out, s[3].d_out, s[4].d_out, s[5].d_out, s[6].d_out, st);
     });
 }
-/* the two rt1w_denoise_var_halves entries: as denoise_var(), with the two halves behind the variance and the error map behind the frame */
+/* the two rt1w_denoise_var_halves entries and the two rt1w_denoise_cross entries, by `filter`: as denoise_var(), with the two halves behind
+ * the variance and the error map behind the frame */
 int denoise_var_halves(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
-                       const double* half_b, double sigma_variance, double* out, double* err_px, bool host, rt1w_stats* stats) {
+                       const double* half_b, double sigma_variance, double* out, double* err_px, HalvesFilter filter, bool host, rt1w_stats* stats) {
     int rc = denoise_validate(c, p);
     if (rc < 0) return rc;
     if ((rc = sigma_variance_validate(sigma_variance)) < 0) return rc;
@@ -590,7 +604,7 @@ int denoise_var_halves(rt1w_context* c, const rt1w_denoise_params* p, const doub
                   {half_b, nullptr, npix * 3, FRAMEBUFFER, "denoise: half copy", nullptr},
                   {aov, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, "denoise: feature buffer copy", nullptr}};
     return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
-        return denoise_var_halves_common(c, p, sigma_variance, s[0].d_in, s[5].d_in, s[2].d_in, s[3].d_in, s[4].d_in, s[0].d_out, s[1].d_out, st);
+        return filter(c, p, sigma_variance, s[0].d_in, s[5].d_in, s[2].d_in, s[3].d_in, s[4].d_in, s[0].d_out, s[1].d_out, st);
     });
 }
 int tile_error_map(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const double* err_px, double* err, bool host, rt1w_stats* stats) {
@@ -605,9 +619,10 @@ int tile_error_map(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const
 /* rt1w_render_aov_device, the pilot's rt1w_render_device + rt1w_accum_merge_device into the halves in turn, then per round
  * rt1w_halves_resolve_device, rt1w_denoise_var_halves_device, rt1w_tile_error_map_device, the plan, one rt1w_render_tiles_device and two
  * rt1w_accum_merge_tiles_device: frame, var, spp, the error map, the feature buffers and the two halves in the framebuffer, a round's
- * sums in the batch buffer, the two accumulators and the tile errors in the accumulator buffer */
+ * sums in the batch buffer, the two accumulators and the tile errors in the accumulator buffer.  rt1w_render_adaptive_cross (`name`) is the same
+ * loop with rt1w_denoise_cross_device as its `filter` */
 int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d, double sigma_variance,
-                             double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
+                             double* out_rgb, double* out_spp, double* out_err, HalvesFilter filter, const char* name, rt1w_stats* stats) {
     int rc = sigma_variance_validate(sigma_variance);
     if (rc < 0) return rc;
     RtAdPlan plan, pair;
@@ -615,8 +630,8 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
     rt1w_render_params q;
     if (p) { /* what the parameters alone decide comes before anything that needs the context */
         if ((rc = refuse_named_flag(p->flags, true, " does not apply to rt1w_render_denoised")) < 0) return rc;
-        if (p->flags & ~RT1W_GENERIC) { set_error("rt1w_render_adaptive_filtered: p->flags must be 0 or RT1W_GENERIC (the rounds go through rt1w_render_tiles, which runs the generic kernels)"); return RT1W_ERR_INVALID; }
-        if (p->x0 || p->y0 || p->tile_w != p->width || p->tile_h != p->height) { set_error("rt1w_render_adaptive_filtered takes the whole frame (x0 = y0 = 0, tile_w = width, tile_h = height)"); return RT1W_ERR_INVALID; }
+        if (p->flags & ~RT1W_GENERIC) { set_error(std::string(name) + ": p->flags must be 0 or RT1W_GENERIC (the rounds go through rt1w_render_tiles, which runs the generic kernels)"); return RT1W_ERR_INVALID; }
+        if (p->x0 || p->y0 || p->tile_w != p->width || p->tile_h != p->height) { set_error(std::string(name) + " takes the whole frame (x0 = y0 = 0, tile_w = width, tile_h = height)"); return RT1W_ERR_INVALID; }
         q = *p; q.spp = plan.batch_spp; /* p->spp is ignored: validated as one batch */
     }
     if ((rc = denoised_render_validate(c, p ? &q : nullptr, out_rgb)) < 0) return rc;
@@ -669,7 +684,7 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
             /* the estimate: every pixel holds as many batches in A as in B here; the filter runs in place on the resolved frame */
             if ((r = halves_resolve_common(c, W, H, n, d_acc_a, d_acc_b, d_frame, d_var, d_half_a, d_half_b, d_spp, &sk)) < 0) return r;
             other_ms += sk.kernel_ms;
-            if ((r = denoise_var_halves_common(c, &dp, sigma_variance, d_frame, d_aov, d_var, d_half_a, d_half_b, d_frame, d_err_px, &sk)) < 0) return r;
+            if ((r = filter(c, &dp, sigma_variance, d_frame, d_aov, d_var, d_half_a, d_half_b, d_frame, d_err_px, &sk)) < 0) return r;
             other_ms += sk.kernel_ms;
             const rt1w_stats sf = sk; /* the level kernel's grid and block are the ones reported */
             if ((r = tile_error_map_common(c, W, H, plan.tile, d_err_px, d_err, &sk)) < 0) return r;
@@ -804,12 +819,12 @@ int rt1w_halves_resolve_device(rt1w_context* c, uint32_t width, uint32_t height,
 }
 int rt1w_denoise_var_halves(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
                             const double* half_b, double sigma_variance, double* out, double* err_px, rt1w_stats* stats) {
-    return denoise_var_halves(c, p, frame, aov, var, half_a, half_b, sigma_variance, out, err_px, true, stats);
+    return denoise_var_halves(c, p, frame, aov, var, half_a, half_b, sigma_variance, out, err_px, denoise_var_halves_common, true, stats);
 }
 int rt1w_denoise_var_halves_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, const void* d_var,
                                    const void* d_half_a, const void* d_half_b, double sigma_variance, void* d_out, void* d_err_px, rt1w_stats* stats) {
     return denoise_var_halves(c, p, (const double*)d_frame, (const double*)d_aov, (const double*)d_var, (const double*)d_half_a, (const double*)d_half_b,
-                              sigma_variance, (double*)d_out, (double*)d_err_px, false, stats);
+                              sigma_variance, (double*)d_out, (double*)d_err_px, denoise_var_halves_common, false, stats);
 }
 int rt1w_tile_error_map(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const double* err_px, double* err, rt1w_stats* stats) {
     return tile_error_map(c, width, height, tile, err_px, err, true, stats);
@@ -819,6 +834,19 @@ int rt1w_tile_error_map_device(rt1w_context* c, uint32_t width, uint32_t height,
 }
 int rt1w_render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d,
                                   double sigma_variance, double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
-    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, stats);
+    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_var_halves_common, "rt1w_render_adaptive_filtered", stats);
+}
+int rt1w_denoise_cross(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
+                       const double* half_b, double sigma_variance, double* out, double* err_px, rt1w_stats* stats) {
+    return denoise_var_halves(c, p, frame, aov, var, half_a, half_b, sigma_variance, out, err_px, denoise_cross_common, true, stats);
+}
+int rt1w_denoise_cross_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, const void* d_var, const void* d_half_a,
+                              const void* d_half_b, double sigma_variance, void* d_out, void* d_err_px, rt1w_stats* stats) {
+    return denoise_var_halves(c, p, (const double*)d_frame, (const double*)d_aov, (const double*)d_var, (const double*)d_half_a, (const double*)d_half_b,
+                              sigma_variance, (double*)d_out, (double*)d_err_px, denoise_cross_common, false, stats);
+}
+int rt1w_render_adaptive_cross(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d,
+                               double sigma_variance, double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
+    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_cross_common, "rt1w_render_adaptive_cross", stats);
 }
 } /* extern "C" */

@@ -1,4 +1,4 @@
-/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, denoise.hip, denoise_var.hip, denoise_halves.hip and adaptive.hip, declared once.
+/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip and adaptive.hip, declared once.
  * The functions are extern "C": nothing in their names says what they take, so caller and definition both include this header and the
  * compiler holds each definition to the declaration the caller sees.  Private (librt1w.map exports none of them).
  * The *_launch functions enqueue on `stream`, put grid and block of the launch (of the level kernel, for the filters) into launch[0..1]
@@ -47,6 +47,12 @@ int rt1w_internal_denoise_var_halves_launch(uint32_t w, uint32_t h, uint32_t ite
                                             const double* half_b, double* out, double* err_px, void* col_a, void* col_b, void* guide,
                                             hipStream_t stream, unsigned launch[2]);
 unsigned rt1w_internal_denoise_var_halves_sizeof(void); /* bytes per pixel of one of its colour buffers */
+/* denoise_cross.hip: the two halves, each filtered with the other's colour term; out and err_px of the last level */
+int rt1w_internal_denoise_cross_launch(uint32_t w, uint32_t h, uint32_t iterations, uint32_t flags, double sigma_normal, double sigma_depth,
+                                       double sigma_variance, const double* frame, const double* aov, const double* var, const double* half_a,
+                                       const double* half_b, double* out, double* err_px, void* col_a, void* col_b, void* guide,
+                                       hipStream_t stream, unsigned launch[2]);
+unsigned rt1w_internal_denoise_cross_sizeof(void); /* bytes per pixel of one of its colour buffers */
 }
 
 #endif

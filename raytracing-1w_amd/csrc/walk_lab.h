@@ -69,6 +69,10 @@ int rt1w_lab_denoise_var_halves_host(const rt1w_denoise_params* p, const double*
                                      const double* half_b, double sigma_variance, double* out, double* err_px,
                                      double* filtered_a /* [h][w][3], may be null: a' * A_p */, double* filtered_b /* likewise */);
 int rt1w_lab_tile_error_map_host(uint32_t width, uint32_t height, uint32_t tile, const double* err_px, double* err);
+/* CPU twin of rt1w_denoise_cross (denoise_host.cpp: rt_denoise_cross.h built for the host); `out` may be `frame`.  rec, for the tests: the
+ * record of the last level before the finish, still demodulated -- a' rgb, la', va', b' rgb, lb', vb' */
+int rt1w_lab_denoise_cross_host(const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
+                                const double* half_b, double sigma_variance, double* out, double* err_px, double* rec /* [h][w][10], may be null */);
 /* the two functions the filters build their weights from (rt_denoise.h), on their own: out[i] = rt_dn_falloff(x[i]) (fn 0; e may be
  * null) or rt_dn_powi(x[i], e[i]) (fn 1).  device 0: the host build of denoise_host.cpp, no GPU; device 1: one lane per element on
  * GPU 0 (f32_exact.hip).  RT1W_ERR_INVALID for anything else, null pointers or n = 0 */

@@ -21,11 +21,15 @@ budget, against rt1w_render_adaptive with RT1W_ADAPTIVE_ONE_LAUNCH and the varia
 the parent commit's) and against rt1w_render_denoised_var of the same mean sample count; the split of the call by kind from a composition
 of the public device entries (render launches, filter passes, resolve + tile-error kernels, merges, the err copies); and the level kernel
 of rt1w_denoise_var_halves against rt1w_denoise_var's per step, as differences of kernel_ms between `iterations` k and k - 1.
+With `--cross` every case gets a column of its own file (`--cross-out`, default profiles/adaptive_cross_bench.json): rt1w_render_adaptive_cross
+against rt1w_render_adaptive_filtered at the same budget in one process, and the level kernel of rt1w_denoise_cross against
+rt1w_denoise_var_halves's per step; `--cross-root LABEL=DIR` repeats it with the library of another built checkout (the staged-against-direct
+A/B: one built with EXTRA_HIPFLAGS=-DRT_DC_STAGED_LEVELS=0).  `--cross` alone runs only that column.
 Writes one JSON file (default profiles/adaptive_bench.json).  Times are wall-clock medians of a few calls on a shared machine: read them
 to two digits.
 
 usage: python3 tools/adaptive_bench.py [--out FILE] [--reps N] [--parent-root BUILT-CHECKOUT-OF-THE-PARENT] [--one-launch] [--filtered [--filtered-out FILE]]
-       [--case NAME:BUDGET ...]
+       [--cross [--cross-out FILE] [--cross-root LABEL=DIR ...]] [--case NAME:BUDGET ...]
 """
 import argparse
 import ctypes as C
@@ -231,6 +235,51 @@ def child_filtered(arm, W, H, budget, reps):
                                   "halves_over_var_per_step": [a / b for a, b in zip(steps["halves"], steps["var"])]}), flush=True)
 
 
+def child_cross(arm, W, H, budget, reps):
+    """rt1w_render_adaptive_cross against rt1w_render_adaptive_filtered at the same budget, and the level kernel of rt1w_denoise_cross against
+    rt1w_denoise_var_halves's per step (differences of kernel_ms between `iterations` k and k - 1), all in one process, on the halves the
+    pilot of the plan leaves"""
+    rt = _rt()
+    sc = rt.Scene.reference(arm, build_seed=1)
+    ctx = rt.Context(sc, 0)
+    calls = {"cross": [], "filtered": []}
+    for i in range(1 + reps):
+        for name, fn in (("cross", ctx.render_adaptive_cross), ("filtered", ctx.render_adaptive_filtered)):
+            _, spp, _, st = fn(W, H, adaptive=dict(budget_spp=budget), with_stats=True)
+            if i:
+                calls[name].append(dict(total_ms=st["total_ms"], kernel_ms=st["kernel_ms"], rounds=st["n_chunks"], spent_spp=float(spp.mean())))
+    hip = C.CDLL("libamdhip64.so")
+
+    def alloc(nbytes):
+        p = C.c_void_p()
+        assert hip.hipMalloc(C.byref(p), C.c_size_t(nbytes)) == 0
+        return p.value
+    n = max(1, budget // BATCH_DIV)
+    npix = W * H
+    d_aov, d_sums = alloc(npix * 64), alloc(npix * 24)
+    d_acc = [alloc(npix * 64), alloc(npix * 64)]
+    d_frame, d_var, d_spp, d_epx, d_ha, d_hb, d_out = (alloc(npix * k) for k in (24, 8, 8, 8, 24, 24, 24))
+    for a in d_acc:
+        assert hip.hipMemset(C.c_void_p(a), 0, C.c_size_t(npix * 64)) == 0
+    ctx.render_aov_device(d_aov, W, H, PILOT * n)
+    for b in range(PILOT):
+        ctx.render_device(d_sums, W, H, n, sample_offset=b * n, chunk=sc.default_chunk(W, H, n), out_sum=True)
+        ctx.accum_merge_device(d_acc[b & 1], d_sums, d_aov, W, H, (0, 0, W, H), n)
+    ctx.halves_resolve_device(d_acc[0], d_acc[1], d_frame, d_var, d_ha, d_hb, d_spp, W, H, n)
+    steps = {"cross": [], "halves": []}
+    for name in steps:
+        fn = ctx.denoise_cross_device if name == "cross" else ctx.denoise_var_halves_device
+        prev = 0.0
+        for it in range(1, 6):
+            ms = [fn(d_frame, d_aov, d_var, d_ha, d_hb, d_out, d_epx, W, H, iterations=it)["kernel_ms"] for _ in range(1 + max(reps, 5))][1:]
+            cur = statistics.median(ms)
+            steps[name].append(cur - prev)   # the first entry holds the prepare pass too
+            prev = cur
+    ctx.close()
+    print("ADJSON " + json.dumps({"calls": calls, "filter_ms_by_iterations_step": steps, "lib": os.path.relpath(rt.LIB_PATH, ROOT),
+                                  "cross_over_halves_per_step": [a / b for a, b in zip(steps["cross"], steps["halves"])]}), flush=True)
+
+
 def child_existing(arm, W, H, budget, reps, spp_uniform):
     """what the new call is compared with: rt1w_render_adaptive with RT1W_ADAPTIVE_ONE_LAUNCH and the filter, and rt1w_render_denoised_var of
     `spp_uniform` samples (a multiple of 4)"""
@@ -266,6 +315,10 @@ def main():
     ap.add_argument("--case", action="append", default=None)
     ap.add_argument("--filtered", action="store_true")
     ap.add_argument("--filtered-out", default=os.path.join(ROOT, "profiles", "adaptive_filtered_bench.json"))
+    ap.add_argument("--cross", action="store_true")
+    ap.add_argument("--cross-out", default=os.path.join(ROOT, "profiles", "adaptive_cross_bench.json"))
+    ap.add_argument("--cross-root", action="append", default=None,
+                    help="LABEL=BUILT-CHECKOUT: the cross column again with that checkout's library, e.g. one built with -DRT_DC_STAGED_LEVELS=0")
     ap.add_argument("--child", nargs="*")
     a = ap.parse_args()
     if a.child:
@@ -274,14 +327,28 @@ def main():
             return child_uniform(arm, W, H, n, reps)
         if kind == "filtered":
             return child_filtered(arm, W, H, n, reps)
+        if kind == "cross":
+            return child_cross(arm, W, H, n, reps)
         if kind.startswith("existing"):
             return child_existing(arm, W, H, n, reps, int(kind[8:]))
         return child_adaptive(arm, W, H, n, reps, one=kind == "adaptive1")
     by_name = {c[0]: c for c in CONFIGS}
     cases = [(by_name[c.split(":")[0]], int(c.split(":")[1])) for c in a.case] if a.case else [(c, b) for c in CONFIGS for b in BUDGETS]
-    rows, frows = [], []
+    rows, frows, crows = [], [], []
     for (name, arm, W, H), budget in cases:
-        if True:
+        if a.cross:
+            cr = {"this library": run_child(["--child", "cross", arm, W, H, budget, a.reps])}
+            for spec in a.cross_root or []:
+                label, root = spec.split("=", 1)
+                cr[label] = run_child(["--child", "cross", arm, W, H, budget, a.reps], root=root)
+            for label, c in cr.items():
+                med = {k: statistics.median(x["total_ms"] for x in v) for k, v in c["calls"].items()}
+                print(f"{name} budget {budget} [{label}]: cross {med['cross']:.1f} ms ({c['calls']['cross'][-1]['rounds']} rounds), filtered error "
+                      f"{med['filtered']:.1f} ms ({c['calls']['filtered'][-1]['rounds']} rounds); cross / halves level kernel per step "
+                      f"{['%.2f' % x for x in c['cross_over_halves_per_step']]} (ms {['%.3f' % x for x in c['filter_ms_by_iterations_step']['cross']]} / "
+                      f"{['%.3f' % x for x in c['filter_ms_by_iterations_step']['halves']]})", flush=True)
+            crows.append({"config": name, "arm": arm, "width": W, "height": H, "budget_spp": budget, "cross": cr})
+        if not a.cross or a.filtered or a.one_launch:
             ad = run_child(["--child", "adaptive", arm, W, H, budget, a.reps])
             one = run_child(["--child", "adaptive1", arm, W, H, budget, a.reps]) if a.one_launch else None
             un = run_child(["--child", "uniform", arm, W, H, budget, a.reps])
@@ -314,6 +381,13 @@ def main():
                       f"filter {frow['adaptive_one_launch_filter_total_ms']:.1f} ms, denoised_var at {spp4} spp {frow['denoised_var_total_ms']:.1f} ms; split {fl['split']}; "
                       f"halves / var level kernel per step {['%.2f' % x for x in fl['halves_over_var_per_step']]}", flush=True)
                 frows.append(frow)
+    if a.cross:
+        os.makedirs(os.path.dirname(a.cross_out), exist_ok=True)
+        with open(a.cross_out, "w") as f:
+            json.dump({"tool": "tools/adaptive_bench.py --cross", "reps": a.reps, "rows": crows}, f, indent=1)
+            f.write("\n")
+    if not rows:
+        return
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump({"tool": "tools/adaptive_bench.py", "reps": a.reps, "rows": rows}, f, indent=1)
