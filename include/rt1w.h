@@ -721,6 +721,72 @@ int rt1w_render_adaptive_cross(rt1w_context* c, const rt1w_render_params* p, con
                                double sigma_variance, double* out_rgb, double* out_spp /* may be NULL */, double* out_err /* may be NULL */,
                                rt1w_stats* stats);
 
+/* ---- full-count guides: first-hit feature SUMS of a list of tiles, and an accumulator of them ----
+ * The adaptive entries above render their feature buffers once, over the pilot's samples, and filter with them to the end: where the plan
+ * spends its samples -- geometric edges, defocus, motion blur -- a first-hit albedo, normal or depth is itself a noisy mean, and those pixels
+ * keep the pilot's guides.  What follows lets a round top up the guides of the tiles it takes in ONE launch, so that at every estimate a
+ * pixel's guides hold as many samples as its colour.  Each sample's camera ray is the one rt1w_render_aov traces (src/main.rs:964-971); like
+ * every buffer here it replaces nothing of the reference, which has sample count alone (src/main.rs:939, :957-1001).  No entry above changes.
+ * rt1w_render_aov_tiles: rt1w_render_aov for a LIST of square tiles, with the list rules of rt1w_render_tiles: `tile` a multiple of 16 in
+ *   16 .. 256, x0 and y0 multiples of it inside the p->width x p->height frame, reserved 0, n_tiles 1 .. 2^20; `tiles` is HOST memory in both
+ *   forms (uploaded into the context's tile-list buffer).  From p: width, height, spp (the same for every tile), global_seed, flags;
+ *   p->sample_offset is added to every tile's own (a sum + spp beyond 2^32 - 1: RT1W_ERR_INVALID); x0, y0, tile_w, tile_h, max_depth, chunk
+ *   and partial_mib are ignored.  Flags: 0 or RT1W_FORCE_VARIANT(v) (tests); anything else, interleaved strips or a non-zero `reserved`:
+ *   RT1W_ERR_INVALID; RT1W_PRECISION_F32: RT1W_ERR_UNSUPPORTED.  What the parameters and the list alone decide is refused before the
+ *   context is looked at.
+ *   out: double[n_tiles][tile][tile][8] of RAW SUMS in sample order, tile k's row 0 = image row y0_k:
+ *     0-2 the sum of the albedo, 3-5 of the normal, 6 of t * |d| over the samples that hit (+0.0 if none did), 7 the number of samples that hit.
+ *   A pixel beyond the frame's right or top edge is never traced and is +0.0 in all eight.
+ *   CONTRACT: for every pixel of tile k inside the frame the sums, finished as s / (double)spp in channels 0-5 and 7 and as
+ *   s7 > 0 ? s6 / s7 : +inf in channel 6, are bit-identical to rt1w_render_aov_device of the rectangle (x0_k, y0_k, min(tile, width - x0_k),
+ *   min(tile, height - y0_k)) with the same spp and seed and the tile's absolute sample offset.  The order of the list and repeats of a
+ *   tile with other offsets do not change a bit.
+ *   One lane per pixel runs its samples in order, 8 x 8 pixels per wave, 16 x 16 per workgroup, grid = n_tiles x (tile / 16)^2.
+ *   stats: paths = segments = pixels inside the frame x spp; passes 1; grid, block, variant, kernel_ms, total_ms.
+ * The guide accumulator gacc: double[h][w][9], caller-owned, 72 bytes per pixel, all zero = empty.  Values 0-7 are the sums above, value 8 is
+ *   N, the samples merged, exact as a double.
+ * rt1w_guides_merge_tiles: tile_sums double[n_tiles][tile][tile][8] as rt1w_render_aov_tiles writes them for `spp` samples, into gacc.  The
+ *   list as above, but the tiles of one call are disjoint -- a tile named twice is RT1W_ERR_INVALID, as in rt1w_accum_merge_tiles;
+ *   sample_offset is ignored; spp 0 is RT1W_ERR_INVALID.  Per pixel inside the frame: where N == 0 the eight sums are taken as they are and
+ *   N = spp; otherwise g_c = g_c + s_c for c = 0 .. 7 and N = N + spp.  One lane per pixel, 16 x 16 pixels per workgroup, grid = n_tiles x
+ *   (tile / 16)^2, no atomics.
+ * rt1w_guides_resolve: gacc -> aov double[h][w][8] in the layout of rt1w_render_aov.  N == 0 gives (0, 0, 0, 0, 0, 0, +inf, 0); otherwise
+ *   channel c of 0-5 and 7 is g_c / N and channel 6 is g7 > 0 ? g6 / g7 : +inf.  grid = ceil(w / 16) * ceil(h / 16), block 256.
+ *   After ONE merge of spp samples into an empty accumulator the resolved buffer is the bits of rt1w_render_aov_device.  After several merges
+ *   it is NOT (another association of the same sums, as rt1w_halves_resolve's var is not rt1w_accum_resolve's): the hit count and so the
+ *   coverage's numerator stay exact; the sums of a + b samples agree within (a + b) * 2^-52, relative for the non-negative ones (albedo,
+ *   distance), absolute for the normal's.
+ * All three are bit-identical to the CPU build (librt1w_lab.so: rt1w_lab_aov_tiles_host, rt1w_lab_guides_merge_tiles_host,
+ * rt1w_lab_guides_resolve_host). */
+int rt1w_render_aov_tiles(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out, rt1w_stats* stats);
+/* same, into device memory on the context's GPU; the list itself is host memory.  Synchronises the context's stream before returning. */
+int rt1w_render_aov_tiles_device(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, void* d_out,
+                                 rt1w_stats* stats);
+int rt1w_guides_merge_tiles(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t spp,
+                            const double* tile_sums, double* gacc, rt1w_stats* stats);
+int rt1w_guides_merge_tiles_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t spp,
+                                   const void* d_tile_sums, void* d_gacc, rt1w_stats* stats);
+int rt1w_guides_resolve(rt1w_context* c, uint32_t width, uint32_t height, const double* gacc, double* aov, rt1w_stats* stats);
+int rt1w_guides_resolve_device(rt1w_context* c, uint32_t width, uint32_t height, const void* d_gacc, void* d_aov, rt1w_stats* stats);
+/* One call: rt1w_render_adaptive_filtered, step for step, with the same parameters, refusals (under this entry's name), buffers and stats.
+ * It differs only here:
+ *   1. in place of rt1w_render_aov_device: rt1w_render_aov_tiles_device of EVERY tile of the frame in row-major order (spp = pilot_batches * n
+ *      at p->sample_offset, every tile's own offset 0), rt1w_guides_merge_tiles_device into a zeroed gacc, rt1w_guides_resolve_device into the
+ *      pilot feature buffer -- by the contracts above the bits rt1w_render_adaptive_filtered renders.  That buffer stays fixed and
+ *      demodulates every rt1w_accum_merge*, exactly as there, so the Welford states keep one albedo;
+ *   3. each round, after rt1w_halves_resolve_device: rt1w_guides_resolve_device into a SECOND feature buffer, which the filter and its
+ *      error map take as `aov`; after the round's rt1w_render_tiles_device: one rt1w_render_aov_tiles_device over the taken tiles, in the
+ *      order taken, once each, with sample_offset = p->sample_offset + 2 j n and spp = 2 n (the pair's samples are contiguous), then one
+ *      rt1w_guides_merge_tiles_device.
+ * At every estimate each pixel's N equals its entry in the spp map.  A stated limit: `var` is the variance of the luminance demodulated with
+ * the PILOT's albedo, while the filter demodulates the frame with the full-count albedo.  stats.passes counts trace-kernel launches only, as
+ * there; the AOV and guide kernels add to kernel_ms.  Bit-identical to composing these public entries; with budget_spp equal to the pilot's
+ * samples (no round takes a tile) out_rgb, out_spp and out_err are the bits of rt1w_render_adaptive_filtered.  An entry of its own rather
+ * than a bit of rt1w_adaptive_params.flags. */
+int rt1w_render_adaptive_guided(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d /* NULL: defaults */,
+                                double sigma_variance, double* out_rgb, double* out_spp /* may be NULL */, double* out_err /* may be NULL */,
+                                rt1w_stats* stats);
+
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory
  * mapping that several single-GPU processes fill with RT1W_OUT_FRAME. */

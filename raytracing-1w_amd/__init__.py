@@ -231,6 +231,14 @@ _sig("rt1w_denoise_cross", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P
 _sig("rt1w_denoise_cross_device", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, C.c_double, _P, _P, C.POINTER(Stats))
 _sig("rt1w_render_adaptive_cross", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(DenoiseParams), C.c_double, _P, _P,
      _P, C.POINTER(Stats))
+_sig("rt1w_render_aov_tiles", C.c_int, _P, C.POINTER(RenderParams), _U, _P, _U, _P, C.POINTER(Stats))
+_sig("rt1w_render_aov_tiles_device", C.c_int, _P, C.POINTER(RenderParams), _U, _P, _U, _P, C.POINTER(Stats))
+_sig("rt1w_guides_merge_tiles", C.c_int, _P, _U, _U, _U, _P, _U, _U, _P, _P, C.POINTER(Stats))
+_sig("rt1w_guides_merge_tiles_device", C.c_int, _P, _U, _U, _U, _P, _U, _U, _P, _P, C.POINTER(Stats))
+_sig("rt1w_guides_resolve", C.c_int, _P, _U, _U, _P, _P, C.POINTER(Stats))
+_sig("rt1w_guides_resolve_device", C.c_int, _P, _U, _U, _P, _P, C.POINTER(Stats))
+_sig("rt1w_render_adaptive_guided", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(DenoiseParams), C.c_double, _P, _P,
+     _P, C.POINTER(Stats))
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -298,6 +306,24 @@ def _accum_of(acc):
     if a.ndim != 3 or a.shape[2] != ACCUM_RECORD:
         raise ValueError("acc must be [h, w, 8]")
     return a
+
+
+GUIDES_RECORD = 9  # rt1w_guides_*: the 8 first-hit feature sums and N, the samples merged, per pixel
+
+
+def _guides_of(gacc):
+    g = np.ascontiguousarray(gacc, dtype=np.float64)
+    if g.ndim != 3 or g.shape[2] != GUIDES_RECORD:
+        raise ValueError("gacc must be [h, w, 9]")
+    return g
+
+
+def _guides_merge_args(gacc, tile_sums, tile, tiles):
+    g = _guides_of(gacc).copy()
+    s = np.ascontiguousarray(tile_sums, dtype=np.float64)
+    if len(tiles) and s.shape != (len(tiles), tile, tile, AOV_CHANNELS):
+        raise ValueError("tile_sums must be [n_tiles, tile, tile, 8]")
+    return g, s
 
 
 def _halves_of(frame, half_a, half_b):
@@ -943,6 +969,63 @@ class Context:
                err.ctypes.data_as(_P), C.byref(st)))
         return (out, spp, err, _stats_dict(st)) if with_stats else (out, spp, err)
 
+    def render_aov_tiles(self, width, height, spp, tile, tiles, sample_offset=0, global_seed=0, variant=None, flags=0, strips=None, f32=False,
+                         with_stats=False):
+        """First-hit feature SUMS of a list of square tiles in one launch (rt1w_render_aov_tiles): `tiles` = Tile objects or (x0, y0,
+        sample_offset) tuples.  Returns float64 [n, tile, tile, 8]: the sums of albedo rgb, normal xyz, t |d| over the hits and the hit count;
+        tile k's row 0 = image row y0_k, pixels beyond the frame's edge are +0.0.  with_stats: returns (array, stats dict)."""
+        p = self._params(width, height, spp, 0, None, sample_offset, global_seed, 0, False, variant, strips=strips, f32=f32)
+        p.flags |= flags
+        rec, n = _tile_list(tiles)
+        out = np.empty((n, tile, tile, AOV_CHANNELS), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_aov_tiles(self._h, C.byref(p), tile, rec, n, out.ctypes.data_as(_P), C.byref(st)))
+        return (out, _stats_dict(st)) if with_stats else out
+
+    def render_aov_tiles_device(self, d_ptr, width, height, spp, tile, tiles, sample_offset=0, global_seed=0, variant=None):
+        """Same, into device memory `d_ptr` (int address) of n * tile * tile * 8 doubles; the list itself is host memory.  Returns the stats."""
+        p = self._params(width, height, spp, 0, None, sample_offset, global_seed, 0, False, variant)
+        rec, n = _tile_list(tiles)
+        st = Stats()
+        _ck(_lib.rt1w_render_aov_tiles_device(self._h, C.byref(p), tile, rec, n, C.c_void_p(d_ptr), C.byref(st)))
+        return _stats_dict(st)
+
+    def guides_merge_tiles(self, gacc, tile_sums, spp, tile, tiles, with_stats=False):
+        """The feature sums of a list of disjoint tiles into a guide accumulator (rt1w_guides_merge_tiles): `gacc` float64 [h, w, 9] (zeros =
+        empty), `tile_sums` [n, tile, tile, 8] as render_aov_tiles returns them for `spp` samples.  Returns the merged accumulator (a new array)."""
+        g, s = _guides_merge_args(gacc, tile_sums, tile, tiles)
+        rec, n = _tile_list(tiles)
+        st = Stats()
+        _ck(_lib.rt1w_guides_merge_tiles(self._h, g.shape[1], g.shape[0], tile, rec, n, spp, s.ctypes.data_as(_P), g.ctypes.data_as(_P), C.byref(st)))
+        return (g, _stats_dict(st)) if with_stats else g
+
+    def guides_merge_tiles_device(self, d_gacc, d_tile_sums, width, height, tile, tiles, spp):
+        """Same on device memory (int addresses); the list itself is host memory.  Returns the stats dict."""
+        rec, n = _tile_list(tiles)
+        st = Stats()
+        _ck(_lib.rt1w_guides_merge_tiles_device(self._h, width, height, tile, rec, n, spp, C.c_void_p(d_tile_sums), C.c_void_p(d_gacc), C.byref(st)))
+        return _stats_dict(st)
+
+    def guides_resolve(self, gacc, with_stats=False):
+        """The feature buffers [h, w, 8] of a guide accumulator, in render_aov's layout (rt1w_guides_resolve)."""
+        g = _guides_of(gacc)
+        aov = np.empty(g.shape[:2] + (AOV_CHANNELS,))
+        st = Stats()
+        _ck(_lib.rt1w_guides_resolve(self._h, g.shape[1], g.shape[0], g.ctypes.data_as(_P), aov.ctypes.data_as(_P), C.byref(st)))
+        return (aov, _stats_dict(st)) if with_stats else aov
+
+    def guides_resolve_device(self, d_gacc, d_aov, width, height):
+        st = Stats()
+        _ck(_lib.rt1w_guides_resolve_device(self._h, width, height, C.c_void_p(d_gacc), C.c_void_p(d_aov), C.byref(st)))
+        return _stats_dict(st)
+
+    def render_adaptive_guided(self, width, height, adaptive=None, denoise=None, sigma_variance=0.0, max_depth=50, sample_offset=0, global_seed=0,
+                               chunk=0, tile=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
+        """render_adaptive_filtered with full-count guides (rt1w_render_adaptive_guided): every round tops up the first-hit feature sums of
+        the tiles it takes, and the filter is guided by all the samples a pixel holds.  Same arguments and results."""
+        return self._render_adaptive_halves(_lib.rt1w_render_adaptive_guided, width, height, adaptive, denoise, sigma_variance, max_depth, sample_offset,
+                                            global_seed, chunk, tile, flags, strips, precision, with_stats, kw)
+
     def debug_aabb(self, cases):
         """cases[n, 14] = min3, max3, origin3, direction3, t_min, t_max -> (literal[n], fast[n]) from the device."""
         a = np.ascontiguousarray(cases, dtype=np.float64).reshape(-1, 14)
@@ -1029,6 +1112,48 @@ def aov_host(scene, width, height, spp, tile=None, sample_offset=0, global_seed=
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_aov_deep_host")
     return (out, {"segments": seg.value, "lengths": lengths}) if with_stats else out
+
+
+def aov_tiles_host(scene, width, height, spp, tile, tiles, sample_offset=0, global_seed=0, variant=None, flags=0, strips=None, f32=False):
+    """CPU twin of Context.render_aov_tiles (librt1w_lab.so: rt1w_lab_aov_tiles_host, rt_aov_tiles.h built for the host): the sums
+    [n, tile, tile, 8] the GPU must equal bit for bit.  No GPU needed."""
+    fn = load_lab().rt1w_lab_aov_tiles_host
+    fn.restype = C.c_int
+    fn.argtypes = [_P, C.POINTER(RenderParams), C.c_uint32, _P, C.c_uint32, _P]
+    p = Context._params(width, height, spp, 0, None, sample_offset, global_seed, 0, False, variant, strips=strips, f32=f32)
+    p.flags |= flags
+    rec, n = _tile_list(tiles)
+    out = np.empty((n, tile, tile, AOV_CHANNELS), dtype=np.float64)
+    rc = fn(scene._h, C.byref(p), tile, rec, n, out.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_aov_tiles_host")
+    return out
+
+
+def guides_merge_tiles_host(gacc, tile_sums, spp, tile, tiles):
+    """CPU twin of Context.guides_merge_tiles (librt1w_lab.so: rt1w_lab_guides_merge_tiles_host)."""
+    fn = load_lab().rt1w_lab_guides_merge_tiles_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32] * 3 + [_P] + [C.c_uint32] * 2 + [_P, _P]
+    g, s = _guides_merge_args(gacc, tile_sums, tile, tiles)
+    rec, n = _tile_list(tiles)
+    rc = fn(g.shape[1], g.shape[0], tile, rec, n, spp, s.ctypes.data_as(_P), g.ctypes.data_as(_P))
+    if rc != 0:
+        raise Rt1wError(rc, "rt1w_lab_guides_merge_tiles_host")
+    return g
+
+
+def guides_resolve_host(gacc):
+    """CPU twin of Context.guides_resolve (rt1w_lab_guides_resolve_host): the feature buffers [h, w, 8]."""
+    fn = load_lab().rt1w_lab_guides_resolve_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32] * 2 + [_P] * 2
+    g = _guides_of(gacc)
+    aov = np.empty(g.shape[:2] + (AOV_CHANNELS,))
+    rc = fn(g.shape[1], g.shape[0], g.ctypes.data_as(_P), aov.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_guides_resolve_host")
+    return aov
 
 
 def denoise_host(frame, aov, **kw):

@@ -1,4 +1,4 @@
-/* adaptive_host.cpp -- the CPU twin of the accumulator kernels (adaptive.hip): rt_adaptive.h and rt_denoise_halves.h compiled for the host (g++,
+/* adaptive_host.cpp -- the CPU twin of the accumulator kernels (adaptive.hip, guides.hip): rt_adaptive.h, rt_denoise_halves.h and rt_guides.h compiled for the host (g++,
  * -ffp-contract=off like every build of the core).  Diagnostics library only (librt1w_lab.so): the expected side of the GPU tests'
  * bit-equality checks and what the CPU tier's known-answer, plan and quality tests run.  librt1w.so keeps no CPU path. */
 #include <cstring>
@@ -6,6 +6,7 @@
 #include "rt1w.h"
 #include "rt_adaptive_plan.h"
 #include "rt_denoise_halves.h"
+#include "rt_guides.h"
 #include "walk_lab.h"
 
 extern "C" int rt1w_lab_accum_merge_host(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w, uint32_t tile_h, uint32_t batch_spp,
@@ -81,5 +82,21 @@ extern "C" int rt1w_lab_halves_resolve_host(uint32_t width, uint32_t height, uin
     const size_t n = (size_t)width * height;
     for (size_t i = 0; i < n; ++i)
         rt_dh_resolve_pixel(batch_spp, acc_a + i * RT_AD_RECORD, acc_b + i * RT_AD_RECORD, frame + i * 3, var + i, half_a + i * 3, half_b + i * 3, spp + i);
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_guides_merge_tiles_host(uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t spp,
+                                                const double* tile_sums, double* gacc) {
+    if (!tile_sums || !gacc || rt_gd_tiles_check(width, height, tile, tiles, n_tiles, spp)) return RT1W_ERR_INVALID;
+    for (uint32_t k = 0; k < n_tiles; ++k)
+        for (uint32_t ly = 0; ly < tile; ++ly)
+            for (uint32_t lx = 0; lx < tile; ++lx) rt_gd_merge_tiles_pixel(width, height, tile, tiles[k].x0, tiles[k].y0, k, lx, ly, spp, tile_sums, gacc);
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_guides_resolve_host(uint32_t width, uint32_t height, const double* gacc, double* aov) {
+    if (!gacc || !aov || !rt_ad_frame_ok(width, height)) return RT1W_ERR_INVALID;
+    const size_t n = (size_t)width * height;
+    for (size_t i = 0; i < n; ++i) rt_gd_resolve_pixel(gacc + i * RT_GD_RECORD, aov + i * RT_GD_SUMS);
     return RT1W_OK;
 }

@@ -1,11 +1,13 @@
-/* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip): rt_aov.h and rt_aov_deep.h compiled for the host (g++, -ffp-contract=off
+/* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip, aov_tiles.hip): rt_aov.h, rt_aov_deep.h and rt_aov_tiles.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core) and run over a committed scene's flat arrays.  Diagnostics library only (librt1w_lab.so): the expected side of the GPU
  * tests' bit-equality checks and of the CPU tier's checks against the literal oracle.  librt1w.so keeps no CPU render path. */
 #include <thread>
 #include <vector>
 
 #include "render_params.h"
+#include "rt_adaptive_plan.h" /* rt_aov_tiles_check */
 #include "rt_aov_deep.h"
+#include "rt_aov_tiles.h"
 #include "walk_lab.h"
 
 namespace {
@@ -54,28 +56,42 @@ bool aov_rows_variant(int v, const RtSceneView& sc, const RtFrame& f, const AovD
     }
 }
 
+/* the kernels' view of a committed scene over its own vectors (`nodes`: with the spare record the context's node array carries) and the
+ * variant the entries run: the scene's, or the one p's RT1W_FORCE_VARIANT names.  false: that variant does not cover the scene */
+bool host_view(const rt1w_scene* s, uint32_t flags, std::vector<RtNode>& nodes, RtSceneView& sc, int& v) {
+    const uint32_t n_nodes = (uint32_t)s->flat_nodes.size();
+    v = rt_pick_variant(n_nodes, s->has_media, s->has_tex, s->has_msphere, s->scope_depth, s->walk_annotated != 0u);
+    if ((flags >> 8) & 0xFFu) {
+        v = (int)((flags >> 8) & 0xFFu) - 1;
+        if (!rt_variant_valid(v, n_nodes, s->has_media, s->has_tex, s->has_msphere, s->scope_depth)) return false;
+    }
+    nodes = s->flat_nodes;
+    nodes.push_back(RtNode{});
+    sc = rt1w::view_of(*s);
+    sc.nodes = nodes.data(); sc.lights = s->flat_lights.data(); sc.materials = s->materials.data(); sc.textures = s->textures.data();
+    sc.perlin = s->perlin.data(); sc.images = s->images.data();
+    return true;
+}
+/* at most 16 threads, at most `work` of them */
+uint32_t host_threads(uint32_t work) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    const uint32_t n = hw == 0u ? 1u : (hw > 16u ? 16u : hw);
+    return n > work ? work : n;
+}
+
 int aov_host_run(const rt1w_scene* s, const rt1w_render_params* p, const AovDeep& deep, double* out, uint64_t* segments) {
     if (!s || !p || !out || !s->committed) return RT1W_ERR_INVALID;
     if (const int rc = rt1w::params_check(p, nullptr); rc < 0) return rc; /* the entries' own check: the twin refuses what they refuse */
     if ((p->flags & ~(0xFFu << 8)) != 0u) return RT1W_ERR_INVALID;
     if (p->precision != RT1W_PRECISION_F64) return RT1W_ERR_UNSUPPORTED;
-    const uint32_t n_nodes = (uint32_t)s->flat_nodes.size();
-    int v = rt_pick_variant(n_nodes, s->has_media, s->has_tex, s->has_msphere, s->scope_depth, s->walk_annotated != 0u);
-    if ((p->flags >> 8) & 0xFFu) {
-        v = (int)((p->flags >> 8) & 0xFFu) - 1;
-        if (!rt_variant_valid(v, n_nodes, s->has_media, s->has_tex, s->has_msphere, s->scope_depth)) return RT1W_ERR_INVALID;
-    }
-    std::vector<RtNode> nodes(s->flat_nodes);
-    nodes.push_back(RtNode{}); /* the spare record the context's node array carries */
-    RtSceneView sc = rt1w::view_of(*s);
-    sc.nodes = nodes.data(); sc.lights = s->flat_lights.data(); sc.materials = s->materials.data(); sc.textures = s->textures.data();
-    sc.perlin = s->perlin.data(); sc.images = s->images.data();
+    std::vector<RtNode> nodes;
+    RtSceneView sc;
+    int v;
+    if (!host_view(s, p->flags, nodes, sc, v)) return RT1W_ERR_INVALID;
     RtFrame f = rt1w::frame_of(p);
     f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u;
     /* rows dealt round-robin over at most 16 threads: every pixel is computed whole by one thread, so the result does not depend on it */
-    unsigned hw = std::thread::hardware_concurrency();
-    uint32_t n_threads = hw == 0u ? 1u : (hw > 16u ? 16u : hw);
-    if (n_threads > f.tile_h) n_threads = f.tile_h;
+    const uint32_t n_threads = host_threads(f.tile_h);
     std::vector<char> ok(n_threads, 1);
     std::vector<uint64_t> rays(n_threads, 0u);
     std::vector<std::thread> pool;
@@ -86,7 +102,54 @@ int aov_host_run(const rt1w_scene* s, const rt1w_render_params* p, const AovDeep
     if (segments) { *segments = 0u; for (uint64_t r : rays) *segments += r; }
     return RT1W_OK;
 }
+
+/* the tiles of a list k0, k0 + step, ..: every pixel of a tile by rt_aov_tiles_pixel, as the kernel's lanes run it */
+template <class Cfg>
+bool aov_tiles(const RtSceneView& sc, const RtFrame& f, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t k0, uint32_t step, double* out) {
+    AovHostStack stk;
+    RtGlobalNodes ns{sc.nodes};
+    for (uint32_t k = k0; k < n; k += step)
+        for (uint32_t ly = 0; ly < tile; ++ly)
+            for (uint32_t lx = 0; lx < tile; ++lx) {
+                rt_aov_tiles_pixel<Cfg>(sc, ns, f, tile, k, tiles[k].x0, tiles[k].y0, tiles[k].sample_offset, lx, ly, stk, out);
+                if (stk.overflow) return false;
+            }
+    return true;
+}
+bool aov_tiles_variant(int v, const RtSceneView& sc, const RtFrame& f, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t k0, uint32_t step, double* out) {
+    switch (v) {
+        case 0: return aov_tiles<RtCfgV0>(sc, f, tile, tiles, n, k0, step, out);
+        case 1: return aov_tiles<RtCfgV1>(sc, f, tile, tiles, n, k0, step, out);
+        case 2: return aov_tiles<RtCfgV2>(sc, f, tile, tiles, n, k0, step, out);
+        case 4: return aov_tiles<RtCfgV4>(sc, f, tile, tiles, n, k0, step, out);
+        case 5: return aov_tiles<RtCfgV5>(sc, f, tile, tiles, n, k0, step, out);
+        default: return aov_tiles<RtCfgV3>(sc, f, tile, tiles, n, k0, step, out);
+    }
+}
 } // namespace
+
+extern "C" int rt1w_lab_aov_tiles_host(const rt1w_scene* s, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out) {
+    if (!s || !p || !tiles || !out || !s->committed) return RT1W_ERR_INVALID;
+    const char* why = nullptr;
+    unsigned long long inside = 0ull;
+    if (const int rc = rt_aov_tiles_check(p, tile, tiles, n_tiles, &why, &inside); rc < 0) return rc; /* the entries' own check */
+    std::vector<RtNode> nodes;
+    RtSceneView sc;
+    int v;
+    if (!host_view(s, p->flags, nodes, sc, v)) return RT1W_ERR_INVALID;
+    RtFrame f = rt1w::frame_of(p);
+    f.x0 = 0u; f.y0 = 0u; f.tile_w = tile; f.tile_h = n_tiles * tile;
+    f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u;
+    /* tiles dealt round-robin over the threads: every pixel is computed whole by one thread */
+    const uint32_t n_threads = host_threads(n_tiles);
+    std::vector<char> ok(n_threads, 1);
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back([&, t]() { ok[t] = aov_tiles_variant(v, sc, f, tile, tiles, n_tiles, t, n_threads, out) ? 1 : 0; });
+    ok[0] = aov_tiles_variant(v, sc, f, tile, tiles, n_tiles, 0u, n_threads, out) ? 1 : 0;
+    for (auto& th : pool) th.join();
+    for (char k : ok) if (!k) return RT1W_ERR_STATE; /* a traversal stack overflowed */
+    return RT1W_OK;
+}
 
 extern "C" int rt1w_lab_aov_host(const rt1w_scene* s, const rt1w_render_params* p, double* out) { return aov_host_run(s, p, AovDeep{}, out, nullptr); }
 

@@ -6,12 +6,14 @@
  *   rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B]
  *        [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic]
  *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
- *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error | --cross-filter [--err-out FILE]]]
+ *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]]]
  * --adaptive BUDGET spends a budget of BUDGET mean samples per pixel where the frame is noisy (rt1w_render_adaptive; --spp is ignored),
  * at most --max-spp samples on one pixel, none on tiles whose error is at or below --target-error; with --denoise --variance the
  * variance-guided filter follows (first-hit guides of the pilot's samples; K and --deep-guides do not apply).
  * --filtered-error steers the plan by the half-buffer error of the FILTERED frame instead (rt1w_render_adaptive_filtered: the variance-guided
  * filter runs in every round and its last frame is the image; --target-error then means the error of the picture that is printed);
+ * --full-guides (with --filtered-error) tops up the first-hit feature buffers of the tiles every round takes, so that the filter's guides hold
+ * every sample a pixel has received (rt1w_render_adaptive_guided) instead of the pilot's.
  * --cross-filter is the same plan with the cross-filtered half buffers in every round (rt1w_render_adaptive_cross: each half is filtered with
  * the other's colour term, the image is the mean of the two); it excludes --filtered-error.
  * --err-out FILE writes the per-pixel error map of that frame as text, "width height" and then one value per pixel, top row first.
@@ -47,6 +49,7 @@ int main(int argc, char** argv) {
     bool one_launch = false;         /* --adaptive: every round as one launch of all its tiles (RT1W_ADAPTIVE_ONE_LAUNCH) */
     bool filtered_error = false;     /* --adaptive: rt1w_render_adaptive_filtered */
     bool cross_filter = false;       /* --adaptive: rt1w_render_adaptive_cross */
+    bool full_guides = false;        /* --adaptive --filtered-error: rt1w_render_adaptive_guided */
     std::string err_path;
     double target_error = 0.0;
     long width = -1, height = -1, spp = -1, depth = 50; /* MAX_DEPTH main.rs:801 */
@@ -88,11 +91,12 @@ int main(int argc, char** argv) {
         else if (a == "--one-launch") one_launch = true;
         else if (a == "--filtered-error") filtered_error = true;
         else if (a == "--cross-filter") cross_filter = true;
+        else if (a == "--full-guides") full_guides = true;
         else if (a == "--err-out") err_path = next("--err-out");
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--target-error") target_error = std::atof(next("--target-error"));
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error | --cross-filter [--err-out FILE]]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]]]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -157,6 +161,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "rt1w: scene arm %d, %ldx%ld, %ld spp, depth %ld\n", arm, width, height, spp, depth);
     if (adaptive < 0 && (filtered_error || !err_path.empty())) { std::fprintf(stderr, "rt1w: --filtered-error and --err-out go with --adaptive\n"); return 2; }
     if (cross_filter && filtered_error) { std::fprintf(stderr, "rt1w: --cross-filter and --filtered-error exclude each other\n"); return 2; }
+    if (full_guides && !filtered_error) { std::fprintf(stderr, "rt1w: --full-guides goes with --adaptive B --filtered-error\n"); return 2; }
     if (adaptive < 0 && cross_filter) { std::fprintf(stderr, "rt1w: --cross-filter goes with --adaptive\n"); return 2; }
     if (!err_path.empty() && !filtered_error && !cross_filter) { std::fprintf(stderr, "rt1w: --err-out goes with --filtered-error\n"); return 2; }
     if (adaptive >= 0) {
@@ -171,7 +176,7 @@ int main(int argc, char** argv) {
         std::vector<double> means((size_t)width * height * 3);
         if (filtered_error || cross_filter) {
             std::vector<double> err(err_path.empty() ? 0 : (size_t)width * height);
-            if ((cross_filter ? rt1w_render_adaptive_cross : rt1w_render_adaptive_filtered)(ctx, &p, &ap, &d, 0.0, means.data(), nullptr, err.empty() ? nullptr : err.data(), &st) < 0) return fail("render");
+            if ((cross_filter ? rt1w_render_adaptive_cross : full_guides ? rt1w_render_adaptive_guided : rt1w_render_adaptive_filtered)(ctx, &p, &ap, &d, 0.0, means.data(), nullptr, err.empty() ? nullptr : err.data(), &st) < 0) return fail("render");
             if (!err.empty()) {
                 FILE* e = std::fopen(err_path.c_str(), "w");
                 if (!e) { std::perror("rt1w: --err-out"); return 1; }

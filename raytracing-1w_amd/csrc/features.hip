@@ -1,6 +1,6 @@
 /* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_denoise*,
- * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_render_adaptive).  Host code only, built without a device pass: the kernels
- * belong to aov.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip and adaptive.hip and are reached through rt_feature_launch.h, the context and its render
+ * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_guides_*, rt1w_render_adaptive*).  Host code only, built without a device pass: the kernels
+ * belong to aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip and adaptive.hip and are reached through rt_feature_launch.h, the context and its render
  * path belong to context.hip (context.h), so a change here rebuilds none of the code objects.
  * Every entry is its checks, in the order its callers know, then one table of its buffers (Staged) handed to staged_entry(), which does what
  * the host and the device form of an entry differ in -- growing the context's buffers, laying the call's buffers out in them, the copies
@@ -12,7 +12,8 @@
 #include "rt_feature_launch.h"
 #include "rt_aov_deep.h" /* rt_aov_deep_args_ok only */
 #include "rt_denoise_var.h" /* rt_dv_batches_ok, rt_dv_sigma, rt_dv_split only */
-#include "rt_adaptive_plan.h" /* the plan of rt1w_render_adaptive and rt1w_adaptive_select; rt_ad_*_ok of rt_adaptive.h */
+#include "rt_adaptive_plan.h" /* the plan of rt1w_render_adaptive and rt1w_adaptive_select; rt_ad_*_ok of rt_adaptive.h; the tile lists' checks */
+#include "rt_guides.h" /* RT_GD_RECORD only */
 
 using namespace rt1w;
 namespace {
@@ -616,13 +617,101 @@ int tile_error_map(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const
     Staged s[] = {{err_px, nullptr, npix, FRAMEBUFFER, "tile error: map copy", nullptr}, {nullptr, err, ntiles, ACCUM_BUFFER, nullptr, "tile error: result copy"}};
     return staged_entry(c, host, s, stats, [&](rt1w_stats* st) { return tile_error_map_common(c, w, h, tile, s[0].d_in, s[1].d_out, st); });
 }
+/* ---- first-hit feature sums of a list of tiles and the guide accumulator (include/rt1w.h: rt1w_render_aov_tiles, rt1w_guides_merge_tiles,
+ * rt1w_guides_resolve) ---- */
+/* upload the list, launch the tile-list AOV kernel of the context's (or the forced) variant into d_out, wait, fill stats.  The parameters and
+ * the list are checked by the caller (rt_aov_tiles_check), which also counts `inside`, the list's pixels inside the frame */
+int render_aov_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n, unsigned long long inside,
+                            double* d_out, rt1w_stats* stats) {
+    int variant = c->variant;
+    int rc = forced_variant(c, p->flags, true, &variant);
+    if (rc < 0) return rc;
+    RtFrame f = frame_of(p);
+    f.x0 = 0u; f.y0 = 0u; f.tile_w = tile; f.tile_h = n * tile; /* the list as one virtual tile; not read by the kernels, nor are these: */
+    f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u;
+    if (rt1w_internal_aov_tiles_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_aov_tiles_sizeof(1) != sizeof(RtFrame)) {
+        set_error("tile-list AOV kernels built against another scene layout"); return RT1W_ERR_DEVICE;
+    }
+    const void* fn = rt1w_internal_aov_tiles_kernel(variant);
+    if (!fn) { set_error("no tile-list AOV kernel of this variant"); return RT1W_ERR_DEVICE; }
+    const uint32_t* d_rec = nullptr;
+    if ((rc = tiles_upload(c, tiles, n, &d_rec)) < 0) return rc;
+    const unsigned grid = n * (tile / 16u) * (tile / 16u); /* <= 2^20 x 256 */
+    RtLane& l = c->lane[0];
+    void* args[] = {&c->view, &f, &tile, &d_rec, &d_out};
+    (void)hipEventRecord(l.ev0, l.stream);
+    if (!hip_ok(hipLaunchKernel(fn, dim3(grid), dim3(RT_BLOCK), args, 0, l.stream), "tile-list AOV kernel launch")) return RT1W_ERR_DEVICE;
+    (void)hipEventRecord(l.ev1, l.stream);
+    if (!hip_ok(hipStreamSynchronize(l.stream), "tile-list AOV kernel")) return RT1W_ERR_DEVICE;
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->paths = stats->segments = inside * p->spp; /* first hit: one camera ray per sample; pixels beyond the frame are not traced */
+        stats->kernel_ms = lane_ms(l);
+        stats->chunk = p->spp; stats->n_chunks = 1u;
+        stats->grid = grid; stats->block = RT_BLOCK;
+        stats->variant = (uint32_t)variant; stats->passes = 1u;
+    }
+    return RT1W_OK;
+}
+/* the two rt1w_render_aov_tiles entries.  What the parameters and the list alone decide comes before the context is looked at.  Host form:
+ * the sums in the framebuffer */
+int render_aov_tiles(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n, void* out, bool host, rt1w_stats* stats) {
+    if (!p || !tiles || !out) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    const char* why = nullptr;
+    unsigned long long inside = 0ull;
+    if (const int rc = rt_aov_tiles_check(p, tile, tiles, n, &why, &inside); rc < 0) { set_error(why); return rc; }
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    Staged s[] = {{nullptr, (double*)out, (size_t)n * tile * tile * RT1W_AOV_CHANNELS, FRAMEBUFFER, nullptr, "AOV tile sums copy"}};
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) { return render_aov_tiles_common(c, p, tile, tiles, n, inside, s[0].d_out, st); });
+}
+/* the list is checked by the caller (rt_gd_tiles_check) */
+int guides_merge_tiles_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t spp, const double* d_sums,
+                              double* d_gacc, rt1w_stats* stats) {
+    const uint32_t* d_rec = nullptr;
+    const int rc = tiles_upload(c, tiles, n, &d_rec);
+    if (rc < 0) return rc;
+    uint64_t inside = 0;
+    for (uint32_t k = 0; k < n; ++k) inside += (uint64_t)std::min(tile, w - tiles[k].x0) * std::min(tile, h - tiles[k].y0);
+    return lane_run(c, inside, "guides merge (tile list)", stats, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_guides_merge_tiles_launch(w, h, tile, d_rec, n, spp, d_sums, d_gacc, stream, launch);
+    });
+}
+int guides_resolve_common(rt1w_context* c, uint32_t w, uint32_t h, const double* d_gacc, double* d_aov, rt1w_stats* stats) {
+    return lane_run(c, (uint64_t)w * h, "guides resolve", stats, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_guides_resolve_launch(w, h, d_gacc, d_aov, stream, launch);
+    });
+}
+/* the two rt1w_guides_merge_tiles entries.  Host form: the sums in the framebuffer, the guide accumulator in the accumulator buffer */
+int guides_merge_tiles(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t spp, const double* sums,
+                       double* gacc, bool host, rt1w_stats* stats) {
+    if (const char* why = rt_gd_tiles_check(w, h, tile, tiles, n, spp)) { set_error(why); return RT1W_ERR_INVALID; }
+    if (!sums || !gacc) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    Staged s[] = {{sums, nullptr, (size_t)n * tile * tile * RT1W_AOV_CHANNELS, FRAMEBUFFER, "guides merge: sums copy", nullptr},
+                  {gacc, gacc, (size_t)w * h * RT_GD_RECORD, ACCUM_BUFFER, "guides merge: accumulator copy", "guides merge: result copy"}};
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) { return guides_merge_tiles_common(c, w, h, tile, tiles, n, spp, s[0].d_in, s[1].d_out, st); });
+}
+/* the two rt1w_guides_resolve entries.  Host form: the guide accumulator in the accumulator buffer, the feature buffers in the framebuffer */
+int guides_resolve(rt1w_context* c, uint32_t w, uint32_t h, const double* gacc, double* aov, bool host, rt1w_stats* stats) {
+    if (!rt_ad_frame_ok(w, h)) { set_error("guides: width and height must be 1 .. 2^30"); return RT1W_ERR_INVALID; }
+    if (!gacc || !aov) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    const size_t npix = (size_t)w * h;
+    Staged s[] = {{gacc, nullptr, npix * RT_GD_RECORD, ACCUM_BUFFER, "guides resolve: accumulator copy", nullptr},
+                  {nullptr, aov, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, nullptr, "guides resolve: feature buffer copy"}};
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) { return guides_resolve_common(c, w, h, s[0].d_in, s[1].d_out, st); });
+}
+
 /* rt1w_render_aov_device, the pilot's rt1w_render_device + rt1w_accum_merge_device into the halves in turn, then per round
  * rt1w_halves_resolve_device, rt1w_denoise_var_halves_device, rt1w_tile_error_map_device, the plan, one rt1w_render_tiles_device and two
  * rt1w_accum_merge_tiles_device: frame, var, spp, the error map, the feature buffers and the two halves in the framebuffer, a round's
  * sums in the batch buffer, the two accumulators and the tile errors in the accumulator buffer.  rt1w_render_adaptive_cross (`name`) is the same
- * loop with rt1w_denoise_cross_device as its `filter` */
+ * loop with rt1w_denoise_cross_device as its `filter`.  rt1w_render_adaptive_guided is the same loop with `guided`: the feature buffers come
+ * from a guide accumulator (behind the tile errors) that every round tops up with the first-hit sums of the tiles it takes (their sums
+ * behind the round's in the batch buffer), and the filter is guided by its resolve (a second feature buffer, last in the framebuffer);
+ * the pilot's feature buffers go on demodulating the merges */
 int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d, double sigma_variance,
-                             double* out_rgb, double* out_spp, double* out_err, HalvesFilter filter, const char* name, rt1w_stats* stats) {
+                             double* out_rgb, double* out_spp, double* out_err, HalvesFilter filter, bool guided, const char* name, rt1w_stats* stats) {
     int rc = sigma_variance_validate(sigma_variance);
     if (rc < 0) return rc;
     RtAdPlan plan, pair;
@@ -649,10 +738,15 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
                   {nullptr, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, nullptr, nullptr}, {nullptr, nullptr, npix * 3, FRAMEBUFFER, nullptr, nullptr},
                   {nullptr, nullptr, npix * 3, FRAMEBUFFER, nullptr, nullptr}, {nullptr, nullptr, batch_px * 3, BATCH_BUFFER, nullptr, nullptr},
                   {nullptr, nullptr, npix * RT_AD_RECORD, ACCUM_BUFFER, nullptr, nullptr}, {nullptr, nullptr, npix * RT_AD_RECORD, ACCUM_BUFFER, nullptr, nullptr},
-                  {nullptr, nullptr, ntiles, ACCUM_BUFFER, nullptr, nullptr}};
+                  {nullptr, nullptr, ntiles, ACCUM_BUFFER, nullptr, nullptr},
+                  /* guided only: the guide accumulator, the full-count feature buffers, the first-hit sums of a round's tiles (or of the pilot's: all) */
+                  {nullptr, nullptr, guided ? npix * RT_GD_RECORD : 0u, ACCUM_BUFFER, nullptr, nullptr},
+                  {nullptr, nullptr, guided ? npix * RT1W_AOV_CHANNELS : 0u, FRAMEBUFFER, nullptr, nullptr},
+                  {nullptr, nullptr, guided ? ntiles * tile_px * RT1W_AOV_CHANNELS : 0u, BATCH_BUFFER, nullptr, nullptr}};
     return staged_entry(c, true, s, stats, [&](rt1w_stats* st) {
         double *d_frame = s[0].d_out, *d_var = s[1].d_out, *d_spp = s[2].d_out, *d_err_px = s[3].d_out, *d_aov = s[4].d_out, *d_half_a = s[5].d_out,
                *d_half_b = s[6].d_out, *d_sums = s[7].d_out, *d_acc_a = s[8].d_out, *d_acc_b = s[9].d_out, *d_err = s[10].d_out;
+        double *d_gacc = s[11].d_out, *d_guides = guided ? s[12].d_out : d_aov, *d_aov_sums = s[13].d_out;
         int r;
         /* the two accumulators lie one behind the other: one clear */
         if (!hip_ok(hipMemsetAsync(d_acc_a, 0, 2 * npix * RT_AD_RECORD * sizeof(double), c->lane[0].stream), "accumulator clear")) return RT1W_ERR_DEVICE;
@@ -660,8 +754,26 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
         memset(st, 0, sizeof *st);
         rt1w_render_params ap = *p; /* the feature buffers of the pilot's samples, by the scene's own variant */
         ap.flags = 0u; ap.spp = plan.pilot * n;
-        if ((r = render_aov_common(c, &ap, nullptr, d_aov, &sk)) < 0) return r;
-        double other_ms = sk.kernel_ms;
+        double other_ms = 0.0;
+        std::vector<rt1w_tile> list;
+        /* guided: the first-hit sums of `list` (spp and offsets as set), merged into the guide accumulator */
+        auto guides_add = [&]() -> int {
+            unsigned long long inside = 0ull;
+            for (const rt1w_tile& t : list) inside += rt_ad_tile_pixels(W, H, plan.tile, t.x0 / plan.tile, t.y0 / plan.tile);
+            int e = render_aov_tiles_common(c, &ap, plan.tile, list.data(), (uint32_t)list.size(), inside, d_aov_sums, &sk);
+            if (e < 0) return e;
+            other_ms += sk.kernel_ms;
+            if ((e = guides_merge_tiles_common(c, W, H, plan.tile, list.data(), (uint32_t)list.size(), ap.spp, d_aov_sums, d_gacc, &sk)) < 0) return e;
+            other_ms += sk.kernel_ms;
+            return RT1W_OK;
+        };
+        if (guided) { /* every tile of the frame in row-major order, into a zeroed guide accumulator; its resolve is rt1w_render_aov_device's bits */
+            if (!hip_ok(hipMemsetAsync(d_gacc, 0, npix * RT_GD_RECORD * sizeof(double), c->lane[0].stream), "guide accumulator clear")) return RT1W_ERR_DEVICE;
+            for (uint32_t t = 0; t < ntiles; ++t) list.push_back(rt1w_tile{(t % tiles_x) * plan.tile, (t / tiles_x) * plan.tile, 0u, 0u});
+            if ((r = guides_add()) < 0) return r;
+            if ((r = guides_resolve_common(c, W, H, d_gacc, d_aov, &sk)) < 0) return r;
+        } else if ((r = render_aov_common(c, &ap, nullptr, d_aov, &sk)) < 0) return r;
+        other_ms += sk.kernel_ms;
         rt1w_render_params bp = *p;
         bp.flags |= RT1W_OUT_SUM;
         bp.spp = n;
@@ -678,13 +790,16 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
         }
         std::vector<uint32_t> m(ntiles, plan.pilot / 2u); /* pairs per tile */
         std::vector<double> err(ntiles);
-        std::vector<rt1w_tile> list;
         uint32_t rounds = 0;
         for (;;) {
             /* the estimate: every pixel holds as many batches in A as in B here; the filter runs in place on the resolved frame */
             if ((r = halves_resolve_common(c, W, H, n, d_acc_a, d_acc_b, d_frame, d_var, d_half_a, d_half_b, d_spp, &sk)) < 0) return r;
             other_ms += sk.kernel_ms;
-            if ((r = filter(c, &dp, sigma_variance, d_frame, d_aov, d_var, d_half_a, d_half_b, d_frame, d_err_px, &sk)) < 0) return r;
+            if (guided) { /* the guides of every sample the pixel holds */
+                if ((r = guides_resolve_common(c, W, H, d_gacc, d_guides, &sk)) < 0) return r;
+                other_ms += sk.kernel_ms;
+            }
+            if ((r = filter(c, &dp, sigma_variance, d_frame, d_guides, d_var, d_half_a, d_half_b, d_frame, d_err_px, &sk)) < 0) return r;
             other_ms += sk.kernel_ms;
             const rt1w_stats sf = sk; /* the level kernel's grid and block are the ones reported */
             if ((r = tile_error_map_common(c, W, H, plan.tile, d_err_px, d_err, &sk)) < 0) return r;
@@ -708,6 +823,11 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
             other_ms += sk.kernel_ms;
             if ((r = accum_merge_tiles_common(c, W, H, plan.tile, list.data() + nt, nt, n, plan.flags, d_sums + (size_t)nt * tile_px * 3, d_aov, d_acc_b, &sk)) < 0) return r;
             other_ms += sk.kernel_ms;
+            if (guided) { /* the pair's 2 n samples are contiguous: every taken tile once, in the order taken */
+                list.resize(nt);
+                ap.spp = 2u * n;
+                if ((r = guides_add()) < 0) return r;
+            }
             sk = sf;
             for (uint32_t t : taken) ++m[t];
         }
@@ -834,7 +954,7 @@ int rt1w_tile_error_map_device(rt1w_context* c, uint32_t width, uint32_t height,
 }
 int rt1w_render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d,
                                   double sigma_variance, double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
-    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_var_halves_common, "rt1w_render_adaptive_filtered", stats);
+    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_var_halves_common, false, "rt1w_render_adaptive_filtered", stats);
 }
 int rt1w_denoise_cross(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
                        const double* half_b, double sigma_variance, double* out, double* err_px, rt1w_stats* stats) {
@@ -847,6 +967,31 @@ int rt1w_denoise_cross_device(rt1w_context* c, const rt1w_denoise_params* p, con
 }
 int rt1w_render_adaptive_cross(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d,
                                double sigma_variance, double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
-    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_cross_common, "rt1w_render_adaptive_cross", stats);
+    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_cross_common, false, "rt1w_render_adaptive_cross", stats);
+}
+int rt1w_render_aov_tiles(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out, rt1w_stats* stats) {
+    return render_aov_tiles(c, p, tile, tiles, n_tiles, out, true, stats);
+}
+int rt1w_render_aov_tiles_device(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, void* d_out,
+                                 rt1w_stats* stats) {
+    return render_aov_tiles(c, p, tile, tiles, n_tiles, d_out, false, stats);
+}
+int rt1w_guides_merge_tiles(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t spp,
+                            const double* tile_sums, double* gacc, rt1w_stats* stats) {
+    return guides_merge_tiles(c, width, height, tile, tiles, n_tiles, spp, tile_sums, gacc, true, stats);
+}
+int rt1w_guides_merge_tiles_device(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t spp,
+                                   const void* d_tile_sums, void* d_gacc, rt1w_stats* stats) {
+    return guides_merge_tiles(c, width, height, tile, tiles, n_tiles, spp, (const double*)d_tile_sums, (double*)d_gacc, false, stats);
+}
+int rt1w_guides_resolve(rt1w_context* c, uint32_t width, uint32_t height, const double* gacc, double* aov, rt1w_stats* stats) {
+    return guides_resolve(c, width, height, gacc, aov, true, stats);
+}
+int rt1w_guides_resolve_device(rt1w_context* c, uint32_t width, uint32_t height, const void* d_gacc, void* d_aov, rt1w_stats* stats) {
+    return guides_resolve(c, width, height, (const double*)d_gacc, (double*)d_aov, false, stats);
+}
+int rt1w_render_adaptive_guided(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d,
+                                double sigma_variance, double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
+    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_var_halves_common, true, "rt1w_render_adaptive_guided", stats);
 }
 } /* extern "C" */

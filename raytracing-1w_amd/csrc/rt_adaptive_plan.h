@@ -69,23 +69,68 @@ inline const char* rt_ad_make_pair_plan(const rt1w_adaptive_params* a, RtAdPlan*
     return rt_ad_make_plan(&b, pair);
 }
 
+/* the records of a tile list: 0 accepted, 1 a record off the grid, outside the frame or with a non-zero reserved member, 2 (disjoint
+ * lists only) a tile named twice */
+inline int rt_ad_tile_records_check(uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, bool disjoint) {
+    const uint32_t tiles_x = (w + tile - 1u) / tile, tiles_y = (h + tile - 1u) / tile;
+    std::vector<bool> seen(disjoint ? (size_t)tiles_x * tiles_y : 0u, false);
+    for (uint32_t k = 0; k < n; ++k) {
+        const rt1w_tile& t = tiles[k];
+        if (t.reserved != 0u || t.x0 % tile || t.y0 % tile || t.x0 >= w || t.y0 >= h) return 1;
+        if (!disjoint) continue;
+        const size_t id = (size_t)(t.y0 / tile) * tiles_x + t.x0 / tile;
+        if (seen[id]) return 2;
+        seen[id] = true;
+    }
+    return 0;
+}
+
 /* the list of rt1w_accum_merge_tiles: nullptr, or why it is refused (RT1W_ERR_INVALID) */
 inline const char* rt_ad_tiles_check(uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t batch_spp, uint32_t flags) {
     if (!rt_ad_frame_ok(w, h)) return "accumulator: width and height must be 1 .. 2^30";
     if (!rt_ad_tile_ok(tile)) return "accumulator merge: tile must be a multiple of 16 in 16 .. 256";
     if (batch_spp < 1u || (flags & ~RT1W_DENOISE_KEEP_ALBEDO)) return "accumulator merge: batch_spp >= 1, flags 0 or RT1W_DENOISE_KEEP_ALBEDO";
     if (!tiles || n < 1u || n > RT_AD_TILES_MAX) return "accumulator merge: a list of 1 .. 2^20 tiles";
-    const uint32_t tiles_x = (w + tile - 1u) / tile, tiles_y = (h + tile - 1u) / tile;
-    std::vector<bool> seen((size_t)tiles_x * tiles_y, false);
-    for (uint32_t k = 0; k < n; ++k) {
-        const rt1w_tile& t = tiles[k];
-        if (t.reserved != 0u || t.x0 % tile || t.y0 % tile || t.x0 >= w || t.y0 >= h)
-            return "accumulator merge: a tile's x0 and y0 must be multiples of `tile` inside the frame, its reserved member 0";
-        const size_t id = (size_t)(t.y0 / tile) * tiles_x + t.x0 / tile;
-        if (seen[id]) return "accumulator merge: a tile is named twice (the tiles of one call are disjoint)";
-        seen[id] = true;
+    switch (rt_ad_tile_records_check(w, h, tile, tiles, n, true)) {
+        case 1: return "accumulator merge: a tile's x0 and y0 must be multiples of `tile` inside the frame, its reserved member 0";
+        case 2: return "accumulator merge: a tile is named twice (the tiles of one call are disjoint)";
     }
     return nullptr;
+}
+
+/* the list of rt1w_guides_merge_tiles: nullptr, or why it is refused (RT1W_ERR_INVALID) */
+inline const char* rt_gd_tiles_check(uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t spp) {
+    if (!rt_ad_frame_ok(w, h)) return "guides: width and height must be 1 .. 2^30";
+    if (!rt_ad_tile_ok(tile)) return "guides merge: tile must be a multiple of 16 in 16 .. 256";
+    if (spp < 1u) return "guides merge: spp must be >= 1";
+    if (!tiles || n < 1u || n > RT_AD_TILES_MAX) return "guides merge: a list of 1 .. 2^20 tiles";
+    switch (rt_ad_tile_records_check(w, h, tile, tiles, n, true)) {
+        case 1: return "guides merge: a tile's x0 and y0 must be multiples of `tile` inside the frame, its reserved member 0";
+        case 2: return "guides merge: a tile is named twice (the tiles of one call are disjoint)";
+    }
+    return nullptr;
+}
+
+/* what rt1w_render_aov_tiles refuses in its parameters and its list, in the order its callers know: RT1W_OK, or the code with *why set.
+ * A tile may be named more than once (with other offsets).  *inside: the pixels of the list that lie inside the frame */
+inline int rt_aov_tiles_check(const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n, const char** why, unsigned long long* inside) {
+    const auto refuse = [why](int rc, const char* text) { *why = text; return rc; };
+    if (p->width < 2 || p->height < 2) return refuse(RT1W_ERR_INVALID, "width and height must be >= 2 (u,v divide by W-1, H-1; main.rs:968-969)");
+    if (p->spp == 0) return refuse(RT1W_ERR_INVALID, "spp must be > 0");
+    if (p->flags & ~(0xFFu << 8)) return refuse(RT1W_ERR_INVALID, "rt1w_render_aov_tiles: flags 0 or RT1W_FORCE_VARIANT only");
+    if (p->precision == RT1W_PRECISION_F32) return refuse(RT1W_ERR_UNSUPPORTED, "rt1w_render_aov_tiles: the AOV entries are f64 only (RT1W_PRECISION_F64)");
+    if (p->precision != RT1W_PRECISION_F64) return refuse(RT1W_ERR_UNSUPPORTED, "unknown precision");
+    if (p->strip_rows || p->strip_period) return refuse(RT1W_ERR_INVALID, "rt1w_render_aov_tiles takes no interleaved strips");
+    if (!rt_ad_tile_ok(tile)) return refuse(RT1W_ERR_INVALID, "rt1w_render_aov_tiles: tile must be a multiple of 16 in 16 .. 256");
+    if (n < 1u || n > RT_AD_TILES_MAX) return refuse(RT1W_ERR_INVALID, "rt1w_render_aov_tiles: n_tiles must be 1 .. 2^20");
+    if (rt_ad_tile_records_check(p->width, p->height, tile, tiles, n, false))
+        return refuse(RT1W_ERR_INVALID, "rt1w_render_aov_tiles: a tile's x0 and y0 must be multiples of `tile` inside the frame, its reserved member 0");
+    *inside = 0ull;
+    for (uint32_t k = 0; k < n; ++k) {
+        if ((unsigned long long)p->sample_offset + tiles[k].sample_offset + p->spp > 0xFFFFFFFFull) return refuse(RT1W_ERR_INVALID, "sample index overflow");
+        *inside += rt_ad_tile_pixels(p->width, p->height, tile, tiles[k].x0 / tile, tiles[k].y0 / tile);
+    }
+    return RT1W_OK;
 }
 
 /* One round.  err and m by tile, row-major over tiles_x x tiles_y tiles of a w x h frame; the tiles taken, in the order taken */

@@ -1,4 +1,4 @@
-/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip and adaptive.hip, declared once.
+/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip and adaptive.hip, declared once.
  * The functions are extern "C": nothing in their names says what they take, so caller and definition both include this header and the
  * compiler holds each definition to the declaration the caller sees.  Private (librt1w.map exports none of them).
  * The *_launch functions enqueue on `stream`, put grid and block of the launch (of the level kernel, for the filters) into launch[0..1]
@@ -53,6 +53,14 @@ int rt1w_internal_denoise_cross_launch(uint32_t w, uint32_t h, uint32_t iteratio
                                        const double* half_b, double* out, double* err_px, void* col_a, void* col_b, void* guide,
                                        hipStream_t stream, unsigned launch[2]);
 unsigned rt1w_internal_denoise_cross_sizeof(void); /* bytes per pixel of one of its colour buffers */
+/* aov_tiles.hip: the first-hit feature sums of a list of tiles (rt1w_render_aov_tiles), by variant; n_tiles x (tile / 16)^2 workgroups of
+ * RT_BLOCK work-items on (view, frame, tile, the uploaded list, out) */
+const void* rt1w_internal_aov_tiles_kernel(int variant);
+unsigned rt1w_internal_aov_tiles_sizeof(int what);
+/* guides.hip: the guide accumulator (rt1w_guides_merge_tiles, rt1w_guides_resolve) */
+int rt1w_internal_guides_merge_tiles_launch(uint32_t w, uint32_t h, uint32_t tile, const uint32_t* rec, uint32_t n, uint32_t spp, const double* sums,
+                                            double* gacc, hipStream_t stream, unsigned launch[2]);
+int rt1w_internal_guides_resolve_launch(uint32_t w, uint32_t h, const double* gacc, double* aov, hipStream_t stream, unsigned launch[2]);
 }
 
 #endif

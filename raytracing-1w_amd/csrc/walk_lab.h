@@ -73,6 +73,13 @@ int rt1w_lab_tile_error_map_host(uint32_t width, uint32_t height, uint32_t tile,
  * record of the last level before the finish, still demodulated -- a' rgb, la', va', b' rgb, lb', vb' */
 int rt1w_lab_denoise_cross_host(const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
                                 const double* half_b, double sigma_variance, double* out, double* err_px, double* rec /* [h][w][10], may be null */);
+/* CPU twins of rt1w_render_aov_tiles (aov_host.cpp: rt_aov_tiles.h built for the host), rt1w_guides_merge_tiles and rt1w_guides_resolve
+ * (adaptive_host.cpp: rt_guides.h built for the host): the same sums[n_tiles][tile][tile][8], the same gacc[h][w][9] and aov[h][w][8], no
+ * GPU; refusals and returns as the device entries, RT1W_ERR_STATE if a traversal stack overflowed */
+int rt1w_lab_aov_tiles_host(const rt1w_scene* s, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out);
+int rt1w_lab_guides_merge_tiles_host(uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t spp,
+                                     const double* tile_sums, double* gacc);
+int rt1w_lab_guides_resolve_host(uint32_t width, uint32_t height, const double* gacc, double* aov);
 /* the two functions the filters build their weights from (rt_denoise.h), on their own: out[i] = rt_dn_falloff(x[i]) (fn 0; e may be
  * null) or rt_dn_powi(x[i], e[i]) (fn 1).  device 0: the host build of denoise_host.cpp, no GPU; device 1: one lane per element on
  * GPU 0 (f32_exact.hip).  RT1W_ERR_INVALID for anything else, null pointers or n = 0 */

@@ -25,11 +25,16 @@ With `--cross` every case gets a column of its own file (`--cross-out`, default 
 against rt1w_render_adaptive_filtered at the same budget in one process, and the level kernel of rt1w_denoise_cross against
 rt1w_denoise_var_halves's per step; `--cross-root LABEL=DIR` repeats it with the library of another built checkout (the staged-against-direct
 A/B: one built with EXTRA_HIPFLAGS=-DRT_DC_STAGED_LEVELS=0).  `--cross` alone runs only that column.
+With `--guided` every case gets a column of its own file (`--guided-out`, default profiles/adaptive_guided_bench.json): rt1w_render_adaptive_guided
+against rt1w_render_adaptive_filtered at the same budget in one process; the share of the call its guide passes take (rt1w_render_aov_tiles,
+rt1w_guides_merge_tiles, rt1w_guides_resolve), from a composition of the public device entries; and the tile-list AOV kernel over every tile
+of the frame against rt1w_render_aov_device of the whole frame at the same samples, as segments per second.  `--guided` alone runs only that
+column.
 Writes one JSON file (default profiles/adaptive_bench.json).  Times are wall-clock medians of a few calls on a shared machine: read them
 to two digits.
 
 usage: python3 tools/adaptive_bench.py [--out FILE] [--reps N] [--parent-root BUILT-CHECKOUT-OF-THE-PARENT] [--one-launch] [--filtered [--filtered-out FILE]]
-       [--cross [--cross-out FILE] [--cross-root LABEL=DIR ...]] [--case NAME:BUDGET ...]
+       [--cross [--cross-out FILE] [--cross-root LABEL=DIR ...]] [--guided [--guided-out FILE]] [--case NAME:BUDGET ...]
 """
 import argparse
 import ctypes as C
@@ -280,6 +285,96 @@ def child_cross(arm, W, H, budget, reps):
                                   "cross_over_halves_per_step": [a / b for a, b in zip(steps["cross"], steps["halves"])]}), flush=True)
 
 
+def child_guided(arm, W, H, budget, reps):
+    """rt1w_render_adaptive_guided against rt1w_render_adaptive_filtered at the same budget in one process; the guided call's split over the
+    public device entries with the guide passes as kinds of their own; the tile-list AOV kernel against rt1w_render_aov_device"""
+    import numpy as np
+    rt = _rt()
+    sc = rt.Scene.reference(arm, build_seed=1)
+    ctx = rt.Context(sc, 0)
+    calls = {"guided": [], "filtered": []}
+    for i in range(1 + reps):
+        for name, fn in (("guided", ctx.render_adaptive_guided), ("filtered", ctx.render_adaptive_filtered)):
+            _, spp, _, st = fn(W, H, adaptive=dict(budget_spp=budget), with_stats=True)
+            if i:
+                calls[name].append(dict(total_ms=st["total_ms"], kernel_ms=st["kernel_ms"], rounds=st["n_chunks"], passes=st["passes"], spent_spp=float(spp.mean())))
+    hip = C.CDLL("libamdhip64.so")
+
+    def alloc(nbytes):
+        p = C.c_void_p()
+        assert hip.hipMalloc(C.byref(p), C.c_size_t(nbytes)) == 0
+        return p.value
+    n = max(1, budget // BATCH_DIV)
+    pair = dict(tile=TILE, batch_spp=2 * n, pilot_batches=max(2, PILOT // 2), budget_spp=budget, max_spp=MAX_FACTOR * budget, round_share=SHARE)
+    npix = W * H
+    tx_n, ty_n = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
+    nt = tx_n * ty_n
+    chunk = sc.default_chunk(W, H, n)
+    d_aov, d_guides, d_sums, d_err = alloc(npix * 64), alloc(npix * 64), alloc(max(npix, 2 * nt * TILE * TILE) * 24), alloc(nt * 8)
+    d_asums, d_gacc = alloc(nt * TILE * TILE * 64), alloc(npix * 72)
+    d_acc = [alloc(npix * 64), alloc(npix * 64)]
+    d_frame, d_var, d_spp, d_epx, d_ha, d_hb = alloc(npix * 24), alloc(npix * 8), alloc(npix * 8), alloc(npix * 8), alloc(npix * 24), alloc(npix * 24)
+    for a, k in ((d_acc[0], 64), (d_acc[1], 64), (d_gacc, 72)):
+        assert hip.hipMemset(C.c_void_p(a), 0, C.c_size_t(npix * k)) == 0
+    kinds = ("render", "merge", "filter", "resolve_error", "aov_tiles", "guides_merge", "guides_resolve")
+    part = {f"{k}_{t}": 0.0 for k in kinds for t in ("total_ms", "kernel_ms")}
+    part["copy_ms"] = 0.0
+
+    def add(kind, st):
+        part[kind + "_total_ms"] += st["total_ms"]; part[kind + "_kernel_ms"] += st["kernel_ms"]
+    every = [(x, y, 0) for y in range(0, H, TILE) for x in range(0, W, TILE)]
+    add("aov_tiles", ctx.render_aov_tiles_device(d_asums, W, H, PILOT * n, TILE, every))
+    add("guides_merge", ctx.guides_merge_tiles_device(d_gacc, d_asums, W, H, TILE, every, PILOT * n))
+    add("guides_resolve", ctx.guides_resolve_device(d_gacc, d_aov, W, H))
+    for b in range(PILOT):
+        add("render", ctx.render_device(d_sums, W, H, n, sample_offset=b * n, chunk=chunk, out_sum=True))
+        add("merge", ctx.accum_merge_device(d_acc[b & 1], d_sums, d_aov, W, H, (0, 0, W, H), n))
+    m = np.full((ty_n, tx_n), PILOT // 2, dtype=np.uint32)
+    err = np.empty((ty_n, tx_n))
+    rounds = 0
+    while True:
+        add("resolve_error", ctx.halves_resolve_device(d_acc[0], d_acc[1], d_frame, d_var, d_ha, d_hb, d_spp, W, H, n))
+        add("guides_resolve", ctx.guides_resolve_device(d_gacc, d_guides, W, H))
+        add("filter", ctx.denoise_var_halves_device(d_frame, d_guides, d_var, d_ha, d_hb, d_frame, d_epx, W, H))
+        add("resolve_error", ctx.tile_error_map_device(d_epx, d_err, W, H, TILE))
+        t0 = time.perf_counter()
+        assert hip.hipMemcpy(err.ctypes.data_as(C.c_void_p), C.c_void_p(d_err), C.c_size_t(err.nbytes), 2) == 0
+        part["copy_ms"] += (time.perf_counter() - t0) * 1e3
+        taken = rt.adaptive_select(W, H, err, m, **pair)
+        if not taken:
+            break
+        rounds += 1
+        tiles = [((t % tx_n) * TILE, (t // tx_n) * TILE, (2 * int(m.flat[t]) + half) * n) for half in (0, 1) for t in taken]
+        add("render", ctx.render_tiles_device(d_sums, W, H, n, TILE, tiles, chunk=chunk, out_sum=True))
+        k = len(taken)
+        add("merge", ctx.accum_merge_tiles_device(d_acc[0], d_sums, d_aov, W, H, TILE, tiles[:k], n))
+        add("merge", ctx.accum_merge_tiles_device(d_acc[1], d_sums + k * TILE * TILE * 24, d_aov, W, H, TILE, tiles[k:], n))
+        add("aov_tiles", ctx.render_aov_tiles_device(d_asums, W, H, 2 * n, TILE, tiles[:k]))
+        add("guides_merge", ctx.guides_merge_tiles_device(d_gacc, d_asums, W, H, TILE, tiles[:k], 2 * n))
+        for t in taken:
+            m.flat[t] += 1
+    assert rounds == calls["guided"][-1]["rounds"], "the composition is not the call's plan"
+    guide_total = sum(part[k + "_total_ms"] for k in ("aov_tiles", "guides_merge", "guides_resolve"))
+    guide_kernel = sum(part[k + "_kernel_ms"] for k in ("aov_tiles", "guides_merge", "guides_resolve"))
+    all_total = sum(v for k, v in part.items() if k.endswith("_total_ms")) + part["copy_ms"]
+    all_kernel = sum(v for k, v in part.items() if k.endswith("_kernel_ms"))
+    # the tile-list AOV kernel over every tile of the frame against rt1w_render_aov_device of the whole frame, the same samples
+    spp_k = PILOT * n
+    tile_ms, rect_ms, seg = [], [], {}
+    for i in range(1 + max(reps, 5)):
+        st, sr = ctx.render_aov_tiles_device(d_asums, W, H, spp_k, TILE, every), ctx.render_aov_device(d_aov, W, H, spp_k)
+        seg = {"tiles": st["segments"], "rectangle": sr["segments"]}
+        if i:
+            tile_ms.append(st["kernel_ms"]); rect_ms.append(sr["kernel_ms"])
+    t_ms, r_ms = statistics.median(tile_ms), statistics.median(rect_ms)
+    ctx.close()
+    print("ADJSON " + json.dumps({"calls": calls, "split": part, "guide_share_of_total_ms": guide_total / all_total,
+                                  "guide_share_of_kernel_ms": guide_kernel / all_kernel, "lib": os.path.relpath(rt.LIB_PATH, ROOT),
+                                  "aov_kernel": {"spp": spp_k, "segments": seg, "tiles_kernel_ms": t_ms, "rectangle_kernel_ms": r_ms,
+                                                 "tiles_segments_per_s": seg["tiles"] / (t_ms * 1e-3), "rectangle_segments_per_s": seg["rectangle"] / (r_ms * 1e-3),
+                                                 "tiles_over_rectangle_rate": (seg["tiles"] / t_ms) / (seg["rectangle"] / r_ms)}}), flush=True)
+
+
 def child_existing(arm, W, H, budget, reps, spp_uniform):
     """what the new call is compared with: rt1w_render_adaptive with RT1W_ADAPTIVE_ONE_LAUNCH and the filter, and rt1w_render_denoised_var of
     `spp_uniform` samples (a multiple of 4)"""
@@ -319,6 +414,8 @@ def main():
     ap.add_argument("--cross-out", default=os.path.join(ROOT, "profiles", "adaptive_cross_bench.json"))
     ap.add_argument("--cross-root", action="append", default=None,
                     help="LABEL=BUILT-CHECKOUT: the cross column again with that checkout's library, e.g. one built with -DRT_DC_STAGED_LEVELS=0")
+    ap.add_argument("--guided", action="store_true")
+    ap.add_argument("--guided-out", default=os.path.join(ROOT, "profiles", "adaptive_guided_bench.json"))
     ap.add_argument("--child", nargs="*")
     a = ap.parse_args()
     if a.child:
@@ -329,12 +426,14 @@ def main():
             return child_filtered(arm, W, H, n, reps)
         if kind == "cross":
             return child_cross(arm, W, H, n, reps)
+        if kind == "guided":
+            return child_guided(arm, W, H, n, reps)
         if kind.startswith("existing"):
             return child_existing(arm, W, H, n, reps, int(kind[8:]))
         return child_adaptive(arm, W, H, n, reps, one=kind == "adaptive1")
     by_name = {c[0]: c for c in CONFIGS}
     cases = [(by_name[c.split(":")[0]], int(c.split(":")[1])) for c in a.case] if a.case else [(c, b) for c in CONFIGS for b in BUDGETS]
-    rows, frows, crows = [], [], []
+    rows, frows, crows, grows = [], [], [], []
     for (name, arm, W, H), budget in cases:
         if a.cross:
             cr = {"this library": run_child(["--child", "cross", arm, W, H, budget, a.reps])}
@@ -348,7 +447,17 @@ def main():
                       f"{['%.2f' % x for x in c['cross_over_halves_per_step']]} (ms {['%.3f' % x for x in c['filter_ms_by_iterations_step']['cross']]} / "
                       f"{['%.3f' % x for x in c['filter_ms_by_iterations_step']['halves']]})", flush=True)
             crows.append({"config": name, "arm": arm, "width": W, "height": H, "budget_spp": budget, "cross": cr})
-        if not a.cross or a.filtered or a.one_launch:
+        if a.guided:
+            g = run_child(["--child", "guided", arm, W, H, budget, a.reps])
+            med = {k: statistics.median(x["total_ms"] for x in v) for k, v in g["calls"].items()}
+            k = g["aov_kernel"]
+            print(f"{name} budget {budget}: guided {med['guided']:.1f} ms ({g['calls']['guided'][-1]['rounds']} rounds), filtered error {med['filtered']:.1f} ms "
+                  f"({g['calls']['filtered'][-1]['rounds']} rounds), ratio {med['guided'] / med['filtered']:.2f}; guide passes {100 * g['guide_share_of_total_ms']:.1f} % "
+                  f"of the call's entries ({100 * g['guide_share_of_kernel_ms']:.1f} % of kernel time); tile-list AOV kernel {k['tiles_kernel_ms']:.3f} ms against "
+                  f"{k['rectangle_kernel_ms']:.3f} ms at {k['spp']} spp: {k['tiles_over_rectangle_rate']:.2f} of its segments per second", flush=True)
+            grows.append({"config": name, "arm": arm, "width": W, "height": H, "budget_spp": budget, "guided_total_ms": med["guided"],
+                          "filtered_total_ms": med["filtered"], "guided_over_filtered": med["guided"] / med["filtered"], "guided": g})
+        if not (a.cross or a.guided) or a.filtered or a.one_launch:
             ad = run_child(["--child", "adaptive", arm, W, H, budget, a.reps])
             one = run_child(["--child", "adaptive1", arm, W, H, budget, a.reps]) if a.one_launch else None
             un = run_child(["--child", "uniform", arm, W, H, budget, a.reps])
@@ -385,6 +494,11 @@ def main():
         os.makedirs(os.path.dirname(a.cross_out), exist_ok=True)
         with open(a.cross_out, "w") as f:
             json.dump({"tool": "tools/adaptive_bench.py --cross", "reps": a.reps, "rows": crows}, f, indent=1)
+            f.write("\n")
+    if a.guided:
+        os.makedirs(os.path.dirname(a.guided_out), exist_ok=True)
+        with open(a.guided_out, "w") as f:
+            json.dump({"tool": "tools/adaptive_bench.py --guided", "reps": a.reps, "rows": grows}, f, indent=1)
             f.write("\n")
     if not rows:
         return
