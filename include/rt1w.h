@@ -120,6 +120,10 @@ int rt1w_scene_commit(rt1w_scene* s);
 int rt1w_scene_build_reference(int arm, uint64_t build_seed, double aspect_ratio,
                                const uint8_t* earth_rgb8, uint32_t earth_w, uint32_t earth_h,
                                rt1w_scene** out, uint32_t defaults[3]);
+/* The arguments rt1w_scene_build_reference hands to rt1w_scene_set_camera for `arm` (main.rs:798-800, the arms' overrides :816-936,
+ * Camera::new :941-951) besides the caller's aspect_ratio and the times 0, 1: what a host that moves a reference arm's camera
+ * (rt1w_context_set_camera) starts from.  No scene is built. */
+int rt1w_reference_camera(int arm, double look_from[3], double look_at[3], double vup[3], double* vfov_deg, double* aperture, double* focus_dist);
 
 /* OPT-IN traversal order of the BVHs.  Default RT1W_WALK_REFERENCE: every BVH node's children are visited
  * left then right exactly as `BVHNode::hit` does (src/bvh.rs:38-47) -- the walk then tests the very primitives the reference
@@ -787,6 +791,95 @@ int rt1w_render_adaptive_guided(rt1w_context* c, const rt1w_render_params* p, co
                                 double sigma_variance, double* out_rgb, double* out_spp /* may be NULL */, double* out_err /* may be NULL */,
                                 rt1w_stats* stats);
 
+/* ---- a live context's camera ----
+ * The camera is frozen into a scene at rt1w_scene_set_camera; a context copies it at creation and hands it to every kernel by value.
+ * rt1w_context_set_camera replaces that copy: the arguments, their meaning and the arithmetic (Camera::new, camera.rs:22-59: one function
+ * behind both entries) are rt1w_scene_set_camera's, and so are the refusals (a null vector, time0 >= time1: RT1W_ERR_INVALID).  Every
+ * later call on the context -- rt1w_render*, rt1w_render_aov*, the tile lists, f32 mode (its f32 copy is rounded anew), the
+ * reference-stream mode -- traces the new camera and gives, bit for bit, what a fresh context of a scene committed with these arguments
+ * gives.  Host work only: the scene object is not touched, so other contexts of the scene keep their camera; the kernel choice, the key
+ * of the scene-specialised kernel (the camera is no part of the generated source), the walk table (ranked once, by the scene's own
+ * camera) and the partial-sum buffers are unaffected.  Not to be called while a call on the context is in flight on another thread. */
+typedef struct rt1w_camera {
+    double origin[3], lower_left_corner[3], horizontal[3], vertical[3], u[3], v[3], w[3];   /* camera.rs:7-18 */
+    double lens_radius, time0, time1;
+} rt1w_camera;                          /* 192 bytes */
+int rt1w_context_set_camera(rt1w_context* c, const double look_from[3], const double look_at[3], const double vup[3], double vfov_deg,
+                            double aspect_ratio, double aperture, double focus_dist, double time0, double time1);
+/* the ten quantities the context's kernels are handed now */
+int rt1w_context_get_camera(const rt1w_context* c, rt1w_camera* out);
+
+/* ---- temporal accumulation: the previous frame's samples, reprojected ----
+ * A frame of an animation is blended with the history of the frames before it, fetched where the surface point seen in a pixel was seen
+ * in the previous frame.  Replaces nothing of the reference, which renders stills.
+ *   cur_frame double[h][w][3] means, the layout of rt1w_render;  cur_aov, prev_aov double[h][w][8], the layout of rt1w_render_aov
+ *   (first-hit buffers: the depth is t |d|, the distance along the camera ray);  cur_cam, prev_cam the cameras the two frames were
+ *   rendered with;  prev_hist double[h][w][3] and prev_len double[h][w] the outputs `hist` and `len` of the previous frame's call
+ *   (prev_len = 0 everywhere: no history, the first frame);  out: hist[h][w][3], len[h][w], frame_out[h][w][3].  The buffers are whole
+ *   images: pixel (x, y) of the buffers is pixel i = x, j = y of both cameras.  The three outputs must not overlap each other or an input:
+ *   RT1W_ERR_INVALID.
+ * Per pixel p = (x, y):
+ *   1. Demodulation.  Albedo A, value c = cur_frame / A and unit normal n_cur exactly as the prepare pass of rt1w_denoise forms them
+ *      (A = max(albedo, 0.01) per channel, 1 with RT1W_DENOISE_KEEP_ALBEDO; n_cur = (0, 0, 0) for a degenerate mean normal).  The
+ *      history is kept demodulated, so textures are not blurred by the resampling.
+ *   2. No reuse on a miss.  If the coverage of p is not > 0 or its depth z is not finite: hist = c, len = 1.
+ *   3. Reprojection point.  X = cur_cam.origin + (z / |dir|) dir,  dir = lower_left_corner + s horizontal + t vertical - origin,
+ *      s = (x + 1/2) / (w - 1), t = (y + 1/2) / (h - 1): the pixel CENTRE, the mean of the reference's jittered (i + r) / (width - 1),
+ *      r in [0, 1) (main.rs:964-971) (a buffer of one column or row, which no render makes, divides by 1).  With lens_radius > 0 this is
+ *      the ray from the lens CENTRE -- a stated approximation: the depth is a mean over rays from all over the lens, and what is out of
+ *      focus is reprojected as if it were sharp.
+ *   4. Projection.  P = X - prev_cam.origin.  If P . w_prev >= 0 (X behind the previous camera, which looks along -w) or the product is
+ *      NaN: no history.  Else X goes through prev_cam's pinhole onto its focus plane: q = D + P (D . w_prev) / (-(P . w_prev)),
+ *      D = origin - lower_left_corner, s' = q . horizontal / |horizontal|^2, t' = q . vertical / |vertical|^2, and the continuous pixel
+ *      position is fx = s' (w - 1) - 1/2, fy = t' (h - 1) - 1/2 (a pixel's centre has integer fx, fy).  Unless -1 < fx < w and
+ *      -1 < fy < h no tap lies in the image: no history.
+ *   5. Taps.  (ix, iy) = floor(fx, fy), the taps are (ix + dx, iy + dy) in the order (0,0), (1,0), (0,1), (1,1) with the bilinear
+ *      weights (dx ? fx - ix : 1 - (fx - ix)) * (dy ? fy - iy : 1 - (fy - iy)).  A tap q is VALID if it lies in the image,
+ *      prev_len_q > 0, its previous coverage > 0, |z_q - |P|| <= depth_tol |P| with z_q its previous depth,
+ *      n_q . n_cur >= normal_min with n_q the unit normal of its previous mean normal, and prev_len_q, z_q and the three values of
+ *      prev_hist_q are finite.
+ *   6. History.  h = (sum of weight * prev_hist over the valid taps, in that order) / (sum of their weights), N the same of prev_len.  If
+ *      the sum of weights is not > 0: no history.
+ *   7. Update.  With history N' = min(N, max_history - 1), hist = (N' h + c) / (N' + 1), len = N' + 1: the running mean of all frames up
+ *      to max_history, an exponential average from there on.  With no history hist = c, len = 1.
+ *   8. Output.  frame_out = hist * A per channel.
+ * Arithmetic: + - * /, sqrt, comparisons and selects in one fixed order, without FMA contraction, each output pixel whole by one lane
+ * (an 8 x 8 pixel block per wave, 2 x 2 blocks per workgroup, the cameras by value, no atomics, one launch on the context's stream):
+ * bit-identical to the CPU build of the same code (librt1w_lab.so: rt1w_lab_temporal_host).
+ * Stated limits.  The scene is taken as static: a MovingSphere's surface fails the depth test or smears.  What is seen through glass
+ * or in a mirror is reprojected with the first surface's motion.  Light that depends on the view (a Metal's reflection) lags by up to
+ * max_history frames. */
+typedef struct rt1w_temporal_params {
+    uint32_t width, height;              /* of all buffers: 1 .. 2^30 */
+    uint32_t flags;                      /* 0 or RT1W_DENOISE_KEEP_ALBEDO */
+    uint32_t max_history;                /* 0 = 32 */
+    double depth_tol;                    /* 0 = 0.05; negative or not finite: RT1W_ERR_INVALID */
+    double normal_min;                   /* 0 = 0.9; negative, NaN or > 1: RT1W_ERR_INVALID */
+} rt1w_temporal_params;                 /* 32 bytes; not one of rt1w_abi_sizeof's: bindings assert the 32 themselves */
+/* host buffers, through the context's device buffers.  stats: kernel_ms = HIP-event time of the launch, total_ms the whole call, passes 1,
+ * grid / block of the kernel, paths = pixels. */
+int rt1w_temporal_accumulate(rt1w_context* c, const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
+                             const double* prev_hist, const double* prev_len, const double* prev_aov, const rt1w_camera* prev_cam, double* hist,
+                             double* len, double* frame_out, rt1w_stats* stats);
+/* same on device memory of the context's GPU (e.g. torch tensors); the cameras are host memory.  Synchronises the context's stream before returning. */
+int rt1w_temporal_accumulate_device(rt1w_context* c, const rt1w_temporal_params* p, const void* d_cur_frame, const void* d_cur_aov,
+                                    const rt1w_camera* cur_cam, const void* d_prev_hist, const void* d_prev_len, const void* d_prev_aov,
+                                    const rt1w_camera* prev_cam, void* d_hist, void* d_len, void* d_frame_out, rt1w_stats* stats);
+/* One frame of an animation in one call: rt1w_render_device of the tile, rt1w_render_aov_device of the same tile, spp, sample_offset and
+ * global_seed, rt1w_temporal_accumulate_device against the state the context keeps from the previous call (prev_hist, prev_len, prev_aov
+ * and the camera of that call: two sets of device buffers that swap, grown on demand and freed with the context) with the context's
+ * camera at the time of the call as cur_cam, then, if `d` is given, rt1w_denoise_device of frame_out with the current feature buffers,
+ * one device->host copy into out_rgb[height][width][3].  On the first call, after rt1w_temporal_reset and after a change of width or
+ * height prev_len is 0 everywhere (and prev_cam is cur_cam).  Bit-identical to composing these public entries.  `t` may be NULL (all
+ * defaults), its width / height must be 0 or the image's; `d` NULL: no filter.  Refuses what rt1w_render_denoised refuses, and a tile
+ * that is not the whole image (the reprojection works in image coordinates): RT1W_ERR_INVALID.  stats are the render's, with the AOV,
+ * accumulation and filter kernel times added to kernel_ms; total_ms is the whole call; grid / block are the last kernel's.  The state is
+ * read and written by this entry alone: no other entry's result depends on it. */
+int rt1w_render_temporal(rt1w_context* c, const rt1w_render_params* p, const rt1w_temporal_params* t /* NULL: defaults */,
+                         const rt1w_denoise_params* d /* NULL: no filter */, double* out_rgb, rt1w_stats* stats);
+/* forget the history: the next rt1w_render_temporal is a first frame.  The buffers stay allocated. */
+int rt1w_temporal_reset(rt1w_context* c);
+
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory
  * mapping that several single-GPU processes fill with RT1W_OUT_FRAME. */
@@ -831,7 +924,8 @@ int rt1w_quantize(const double* means, uint64_t n_values, uint8_t* out);
 int64_t rt1w_format_ppm(const double* means, uint32_t width, uint32_t height, char* buf, uint64_t cap);
 
 /* sizeof of the ABI structs as this library was compiled (bindings check their own layout against it):
- * 0 rt1w_render_params, 1 rt1w_stats, 2 rt1w_scene_info, 3 rt1w_specialise_info, 4 rt1w_denoise_params; 0 for anything else */
+ * 0 rt1w_render_params, 1 rt1w_stats, 2 rt1w_scene_info, 3 rt1w_specialise_info, 4 rt1w_denoise_params, 6 rt1w_camera; 0 for anything else
+ * (5 is not given out: it stays the code that answers 0) */
 uint32_t rt1w_abi_sizeof(int what);
 
 /* ---- diagnostics ---- */

@@ -239,6 +239,43 @@ _sig("rt1w_guides_resolve", C.c_int, _P, _U, _U, _P, _P, C.POINTER(Stats))
 _sig("rt1w_guides_resolve_device", C.c_int, _P, _U, _U, _P, _P, C.POINTER(Stats))
 _sig("rt1w_render_adaptive_guided", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(DenoiseParams), C.c_double, _P, _P,
      _P, C.POINTER(Stats))
+
+
+class Camera(C.Structure):
+    """rt1w_camera: the ten quantities of camera.rs:7-18 as the kernels take them."""
+    _fields_ = [(n, _D3) for n in ("origin", "lower_left_corner", "horizontal", "vertical", "u", "v", "w")] + \
+               [(n, C.c_double) for n in ("lens_radius", "time0", "time1")]
+
+    def array(self):
+        """The 24 doubles, in the struct's order."""
+        return np.frombuffer(bytes(self), dtype=np.float64).copy()
+
+    @classmethod
+    def of(cls, cam):
+        """A Camera from a Camera or from 24 doubles."""
+        return cam if isinstance(cam, cls) else cls.from_buffer_copy(np.ascontiguousarray(cam, dtype=np.float64).reshape(24).tobytes())
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("max_history", C.c_uint32),
+                ("depth_tol", C.c_double), ("normal_min", C.c_double)]
+
+
+assert C.sizeof(TemporalParams) == 32, "rt1w_temporal_params is 32 bytes (include/rt1w.h); it is not one of rt1w_abi_sizeof's"
+
+
+def _temporal_params(width, height, keep_albedo=False, max_history=0, depth_tol=0.0, normal_min=0.0, flags=0):
+    return TemporalParams(width, height, flags | (DENOISE_KEEP_ALBEDO if keep_albedo else 0), max_history, depth_tol, normal_min)
+
+
+_CAM_ARGS = [_D3, _D3, _D3] + [C.c_double] * 6
+_sig("rt1w_reference_camera", C.c_int, C.c_int, _D3, _D3, _D3, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+_sig("rt1w_context_set_camera", C.c_int, _P, *_CAM_ARGS)
+_sig("rt1w_context_get_camera", C.c_int, _P, C.POINTER(Camera))
+_sig("rt1w_temporal_accumulate", C.c_int, _P, C.POINTER(TemporalParams), _P, _P, C.POINTER(Camera), _P, _P, _P, C.POINTER(Camera), _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_temporal_accumulate_device", C.c_int, _P, C.POINTER(TemporalParams), _P, _P, C.POINTER(Camera), _P, _P, _P, C.POINTER(Camera), _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_render_temporal", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(TemporalParams), C.POINTER(DenoiseParams), _P, C.POINTER(Stats))
+_sig("rt1w_temporal_reset", C.c_int, _P)
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -256,6 +293,8 @@ _sig("rt1w_debug_texture", C.c_int, _P, C.c_int, C.c_uint32, _P, _P, C.c_uint64)
 for _i, _t in enumerate((RenderParams, Stats, SceneInfo, SpecialiseInfo)):
     if _lib.rt1w_abi_sizeof(_i) != C.sizeof(_t):
         raise ImportError(f"librt1w.so and this binding disagree on the layout of {_t.__name__}: rebuild the library")
+if _lib.rt1w_abi_sizeof(6) != C.sizeof(Camera):
+    raise ImportError("librt1w.so and this binding disagree on the layout of Camera: rebuild the library")
 
 
 def last_error():
@@ -281,6 +320,37 @@ def _frame_and_aov(frame, aov):
     if f.ndim != 3 or f.shape[2] != 3 or a.shape != f.shape[:2] + (AOV_CHANNELS,):
         raise ValueError("frame must be [h, w, 3] and aov [h, w, 8]")
     return f, a
+
+
+def _temporal_args(cur_frame, cur_aov, prev_hist, prev_len, prev_aov):
+    f, a = _frame_and_aov(cur_frame, cur_aov)
+    h, q = _frame_and_aov(prev_hist, prev_aov)
+    n = np.ascontiguousarray(prev_len, dtype=np.float64)
+    if h.shape != f.shape or n.shape != f.shape[:2]:
+        raise ValueError("prev_hist must be [h, w, 3] and prev_len [h, w], the current frame's size")
+    return f, a, h, n, q
+
+
+def reference_camera(arm, aspect_ratio=None):
+    """The arguments Scene.reference(arm) hands to set_camera (rt1w_reference_camera), as a dict of Scene.set_camera's /
+    Context.set_camera's keywords."""
+    lf, la, up = _D3(), _D3(), _D3()
+    vfov, ap, fd = C.c_double(), C.c_double(), C.c_double()
+    _ck(_lib.rt1w_reference_camera(arm, lf, la, up, C.byref(vfov), C.byref(ap), C.byref(fd)))
+    if aspect_ratio is None:
+        aspect_ratio = 1.0 if (arm in (5, 6) or arm < 0 or arm > 6) else 16.0 / 9.0
+    return {"look_from": tuple(lf), "look_at": tuple(la), "vup": tuple(up), "vfov_deg": vfov.value, "aspect_ratio": aspect_ratio,
+            "aperture": ap.value, "focus_dist": fd.value, "time0": 0.0, "time1": 1.0}
+
+
+def orbit_camera(args, degrees):
+    """`args` (a dict as reference_camera's) with look_from turned about the vertical axis through look_at by `degrees`: the
+    turntable of the CLI's --orbit."""
+    import math
+    lf, la = args["look_from"], args["look_at"]
+    c, s = math.cos(math.radians(degrees)), math.sin(math.radians(degrees))
+    dx, dz = lf[0] - la[0], lf[2] - la[2]
+    return dict(args, look_from=(la[0] + c * dx + s * dz, lf[1], la[2] - s * dx + c * dz))
 
 
 def _sums_and_aov(sums, aov):
@@ -712,6 +782,61 @@ class Context:
         st = Stats()
         _ck(_lib.rt1w_denoise_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_out), C.byref(st)))
         return _stats_dict(st)
+
+    def set_camera(self, look_from, look_at, vup, vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1):
+        """Replace this context's camera (rt1w_context_set_camera): Scene.set_camera's arguments and arithmetic, host work only.
+        The scene and its other contexts keep theirs."""
+        _ck(_lib.rt1w_context_set_camera(self._h, _v3(look_from), _v3(look_at), _v3(vup), vfov_deg, aspect_ratio, aperture, focus_dist,
+                                         time0, time1))
+
+    def get_camera(self):
+        """The Camera the kernels of this context are handed now (rt1w_context_get_camera)."""
+        cam = Camera()
+        _ck(_lib.rt1w_context_get_camera(self._h, C.byref(cam)))
+        return cam
+
+    def temporal_accumulate(self, cur_frame, cur_aov, cur_cam, prev_hist, prev_len, prev_aov, prev_cam, with_stats=False, **kw):
+        """Temporal accumulation (rt1w_temporal_accumulate) of a float64 frame [h, w, 3] with its feature buffers [h, w, 8] against the
+        previous frame's (hist [h, w, 3], len [h, w], feature buffers); the cameras are Camera or 24 doubles.  Returns
+        (hist, len, frame_out).  kw: keep_albedo, max_history, depth_tol, normal_min (0 = default)."""
+        f, a, h, n, q = _temporal_args(cur_frame, cur_aov, prev_hist, prev_len, prev_aov)
+        p = _temporal_params(f.shape[1], f.shape[0], **kw)
+        hist, ln, out = np.empty_like(f), np.empty_like(n), np.empty_like(f)
+        st = Stats()
+        _ck(_lib.rt1w_temporal_accumulate(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(Camera.of(cur_cam)),
+                                          h.ctypes.data_as(_P), n.ctypes.data_as(_P), q.ctypes.data_as(_P), C.byref(Camera.of(prev_cam)),
+                                          hist.ctypes.data_as(_P), ln.ctypes.data_as(_P), out.ctypes.data_as(_P), C.byref(st)))
+        return (hist, ln, out, _stats_dict(st)) if with_stats else (hist, ln, out)
+
+    def temporal_accumulate_device(self, d_cur_frame, d_cur_aov, cur_cam, d_prev_hist, d_prev_len, d_prev_aov, prev_cam, d_hist, d_len,
+                                   d_frame_out, width, height, **kw):
+        """Same on device memory (int addresses, e.g. torch tensors' .data_ptr()).  Returns the stats dict."""
+        p = _temporal_params(width, height, **kw)
+        st = Stats()
+        _ck(_lib.rt1w_temporal_accumulate_device(self._h, C.byref(p), C.c_void_p(d_cur_frame), C.c_void_p(d_cur_aov), C.byref(Camera.of(cur_cam)),
+                                                 C.c_void_p(d_prev_hist), C.c_void_p(d_prev_len), C.c_void_p(d_prev_aov),
+                                                 C.byref(Camera.of(prev_cam)), C.c_void_p(d_hist), C.c_void_p(d_len), C.c_void_p(d_frame_out),
+                                                 C.byref(st)))
+        return _stats_dict(st)
+
+    def render_temporal(self, width, height, spp, max_depth=50, sample_offset=0, global_seed=0, temporal=None, denoise=None, filter=False,
+                        flags=0, with_stats=False, **kw):
+        """One frame of an animation (rt1w_render_temporal): render, feature buffers, accumulation against the state this context keeps
+        from the previous call, optionally the filter (filter=True, or `denoise`: dict of Context.denoise's keywords): float64
+        [height, width, 3].  `temporal`: dict of temporal_accumulate's keywords; other kw as Context.render's."""
+        p = self._params(width, height, spp, max_depth, kw.pop("tile", None), sample_offset, global_seed, 0, False, kw.pop("variant", None), **kw)
+        p.flags |= flags
+        t = _temporal_params(0, 0, **temporal) if temporal is not None else None
+        d = _denoise_params(0, 0, **(denoise or {})) if (filter or denoise is not None) else None
+        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_temporal(self._h, C.byref(p), C.byref(t) if t is not None else None, C.byref(d) if d is not None else None,
+                                      out.ctypes.data_as(_P), C.byref(st)))
+        return (out, _stats_dict(st)) if with_stats else out
+
+    def temporal_reset(self):
+        """Forget the history of render_temporal (rt1w_temporal_reset): the next call is a first frame."""
+        _ck(_lib.rt1w_temporal_reset(self._h))
 
     def _render_denoised(self, deep, width, height, spp, max_depth, tile, sample_offset, global_seed, denoise, flags, strips, precision, with_stats, kw):
         p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, 0, False, kw.pop("variant", None), strips=strips, **kw)
@@ -1154,6 +1279,50 @@ def guides_resolve_host(gacc):
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_guides_resolve_host")
     return aov
+
+
+def temporal_host(cur_frame, cur_aov, cur_cam, prev_hist, prev_len, prev_aov, prev_cam, with_record=False, **kw):
+    """CPU twin of Context.temporal_accumulate (librt1w_lab.so: rt1w_lab_temporal_host, the same rt_temporal.h built for the host):
+    the (hist, len, frame_out) the GPU must equal bit for bit.  No GPU needed.  with_record: also the tests' record [h, w, 8] of every
+    pixel -- fx, fy, the four taps' weights (0 where a tap is not valid), their sum, 1 / 0 history."""
+    fn = load_lab().rt1w_lab_temporal_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(TemporalParams), _P, _P, C.POINTER(Camera), _P, _P, _P, C.POINTER(Camera), _P, _P, _P, _P]
+    f, a, h, n, q = _temporal_args(cur_frame, cur_aov, prev_hist, prev_len, prev_aov)
+    p = _temporal_params(f.shape[1], f.shape[0], **kw)
+    hist, ln, out = np.empty_like(f), np.empty_like(n), np.empty_like(f)
+    rec = np.zeros(f.shape[:2] + (8,)) if with_record else None
+    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(Camera.of(cur_cam)), h.ctypes.data_as(_P), n.ctypes.data_as(_P),
+            q.ctypes.data_as(_P), C.byref(Camera.of(prev_cam)), hist.ctypes.data_as(_P), ln.ctypes.data_as(_P), out.ctypes.data_as(_P),
+            rec.ctypes.data_as(_P) if with_record else None)
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_temporal_host")
+    return (hist, ln, out, rec) if with_record else (hist, ln, out)
+
+
+def scene_set_camera_host(scene, look_from, look_at, vup, vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1):
+    """Diagnostics (librt1w_lab.so: rt1w_lab_scene_set_camera): what Context.set_camera does to a context's view, done to a COMMITTED
+    scene's own camera record, so that the CPU twins and Scene.flat -- which build their view from the scene -- render the camera a
+    live context would.  Everything made from the scene afterwards, a context too, sees a scene committed with these arguments;
+    contexts made before keep the camera they copied."""
+    fn = load_lab().rt1w_lab_scene_set_camera
+    fn.restype = C.c_int
+    fn.argtypes = [_P] + _CAM_ARGS
+    rc = fn(scene._h, _v3(look_from), _v3(look_at), _v3(vup), vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1)
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_scene_set_camera")
+
+
+def scene_camera_host(scene):
+    """The Camera of a scene's own record (librt1w_lab.so: rt1w_lab_scene_get_camera)."""
+    fn = load_lab().rt1w_lab_scene_get_camera
+    fn.restype = C.c_int
+    fn.argtypes = [_P, C.POINTER(Camera)]
+    cam = Camera()
+    rc = fn(scene._h, C.byref(cam))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_scene_get_camera")
+    return cam
 
 
 def denoise_host(frame, aov, **kw):

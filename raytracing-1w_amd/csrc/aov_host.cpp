@@ -1,6 +1,7 @@
 /* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip, aov_tiles.hip): rt_aov.h, rt_aov_deep.h and rt_aov_tiles.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core) and run over a committed scene's flat arrays.  Diagnostics library only (librt1w_lab.so): the expected side of the GPU
  * tests' bit-equality checks and of the CPU tier's checks against the literal oracle.  librt1w.so keeps no CPU render path. */
+#include <cstring>
 #include <thread>
 #include <vector>
 
@@ -159,4 +160,20 @@ extern "C" int rt1w_lab_aov_deep_host(const rt1w_scene* s, const rt1w_render_par
     AovDeep deep;
     deep.max_specular = (long)max_specular; deep.max_fuzz = max_fuzz; deep.lengths = lengths;
     return aov_host_run(s, p, deep, out, segments);
+}
+
+extern "C" int rt1w_lab_scene_set_camera(rt1w_scene* s, const double look_from[3], const double look_at[3], const double vup[3], double vfov_deg,
+                                         double aspect_ratio, double aperture, double focus_dist, double time0, double time1) {
+    if (!s || !s->committed) return RT1W_ERR_INVALID;
+    RtCamera cam;
+    const char* why = nullptr;
+    if (const int rc = rt1w::camera_make(look_from, look_at, vup, vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1, &cam, &why); rc < 0) return rc;
+    s->camera = cam;
+    return RT1W_OK;
+}
+extern "C" int rt1w_lab_scene_get_camera(const rt1w_scene* s, rt1w_camera* out) {
+    if (!s || !out || !s->has_camera) return RT1W_ERR_INVALID;
+    static_assert(sizeof(rt1w_camera) == sizeof(RtCamera), "rt1w_camera is RtCamera's layout");
+    memcpy(out, &s->camera, sizeof *out);
+    return RT1W_OK;
 }

@@ -7,6 +7,11 @@
  *        [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic]
  *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
  *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]]]
+ *        [--frames N --orbit DEG [--denoise]]
+ * --frames N --orbit DEG renders an animation of N frames through rt1w_render_temporal: before frame k look_from is turned about the
+ * vertical axis through look_at by k * DEG degrees (rt1w_context_set_camera; the scene, its upload and its kernel are frame 0's), the
+ * frame's seed is --seed + k, and the previous frames' samples are reused where their surface points are seen again; with --denoise
+ * the feature-guided filter follows.  Frame k is written to NAME_%04d.ppm, NAME being --out without its ".ppm" (default "frame").
  * --adaptive BUDGET spends a budget of BUDGET mean samples per pixel where the frame is noisy (rt1w_render_adaptive; --spp is ignored),
  * at most --max-spp samples on one pixel, none on tiles whose error is at or below --target-error; with --denoise --variance the
  * variance-guided filter follows (first-hit guides of the pilot's samples; K and --deep-guides do not apply).
@@ -28,6 +33,7 @@
  * --specialise compiles the kernel for this scene's topology now if the kernel cache has none (rt1w_context_specialise;
  * by default only a cached kernel is used, and renders of >= 2^35 paths compile on their own); --generic forbids it.
  */
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +57,8 @@ int main(int argc, char** argv) {
     bool cross_filter = false;       /* --adaptive: rt1w_render_adaptive_cross */
     bool full_guides = false;        /* --adaptive --filtered-error: rt1w_render_adaptive_guided */
     std::string err_path;
+    long frames = 0;                 /* > 0: an animation through rt1w_render_temporal */
+    double orbit = 0.0;
     double target_error = 0.0;
     long width = -1, height = -1, spp = -1, depth = 50; /* MAX_DEPTH main.rs:801 */
     unsigned long long build_seed = 1, seed = 0;
@@ -93,10 +101,12 @@ int main(int argc, char** argv) {
         else if (a == "--cross-filter") cross_filter = true;
         else if (a == "--full-guides") full_guides = true;
         else if (a == "--err-out") err_path = next("--err-out");
+        else if (a == "--frames") frames = std::atol(next("--frames"));
+        else if (a == "--orbit") orbit = std::atof(next("--orbit"));
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--target-error") target_error = std::atof(next("--target-error"));
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]]] [--frames N --orbit DEG [--denoise]]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -135,6 +145,45 @@ int main(int argc, char** argv) {
     if (generic) p.flags |= RT1W_GENERIC;
     if (reference_stream) p.flags |= RT1W_RNG_REFERENCE;
     if (f32) p.precision = RT1W_PRECISION_F32;
+    rt1w_stats st;
+    if (frames > 0) {
+        if (adaptive >= 0 || variance >= 0 || deep_guides >= 0 || reference_stream || f32) { std::fprintf(stderr, "rt1w: --frames goes with --denoise only\n"); return 2; }
+        double lf[3], la[3], up[3], vfov, aperture, focus;
+        if (rt1w_reference_camera(arm, lf, la, up, &vfov, &aperture, &focus) < 0) return fail("camera");
+        std::string name = out_path.empty() ? "frame" : out_path;
+        if (name.size() > 4 && name.compare(name.size() - 4, 4, ".ppm") == 0) name.resize(name.size() - 4);
+        rt1w_denoise_params d;
+        std::memset(&d, 0, sizeof d);
+        d.iterations = denoise_iterations > 0 ? (uint32_t)denoise_iterations : 0u;
+        std::vector<double> means((size_t)width * height * 3);
+        std::fprintf(stderr, "rt1w: scene arm %d, %ld frames of %ldx%ld, %ld spp, %g degrees per frame\n", arm, frames, width, height, spp, orbit);
+        double kernel_ms = 0.0;
+        for (long k = 0; k < frames; ++k) {
+            /* look_from about the vertical axis through look_at */
+            const double t = orbit * (double)k * 3.14159265358979323846 / 180.0, c = std::cos(t), sn = std::sin(t);
+            const double dx = lf[0] - la[0], dz = lf[2] - la[2];
+            const double from[3] = {la[0] + c * dx + sn * dz, lf[1], la[2] - sn * dx + c * dz};
+            if (rt1w_context_set_camera(ctx, from, la, up, vfov, aspect, aperture, focus, 0.0, 1.0) < 0) return fail("camera");
+            p.global_seed = (uint32_t)seed + (uint32_t)k;
+            if (rt1w_render_temporal(ctx, &p, nullptr, denoise ? &d : nullptr, means.data(), &st) < 0) return fail("render");
+            kernel_ms += st.kernel_ms;
+            const int64_t n = rt1w_format_ppm(means.data(), p.width, p.height, nullptr, 0);
+            if (n < 0) return fail("format");
+            std::vector<char> text((size_t)n + 1);
+            if (rt1w_format_ppm(means.data(), p.width, p.height, text.data(), (uint64_t)n + 1) < 0) return fail("format");
+            char file[32];
+            std::snprintf(file, sizeof file, "_%04ld.ppm", k);
+            FILE* f = std::fopen((name + file).c_str(), "w");
+            if (!f) { std::perror("rt1w: --out"); return 1; }
+            std::fwrite(text.data(), 1, (size_t)n, f);
+            std::fclose(f);
+            std::fprintf(stderr, "\rFrames remaining: %ld ", frames - 1 - k);
+        }
+        std::fprintf(stderr, "\nDone\nrt1w: %.1f ms kernels in %ld frames\n", kernel_ms, frames);
+        rt1w_context_destroy(ctx);
+        rt1w_scene_destroy(scene);
+        return 0;
+    }
     /* the reference collects the rows top-down, counting them down on stderr (main.rs:957-960,995-998), then prints them
      * (main.rs:1003-1007); here the rows are quantised on the device and written as their strips land */
     std::vector<unsigned char> img((size_t)width * height * 3);
@@ -157,7 +206,6 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "\rScanlines remaining: %u ", rows_total - rows_done);
         return 0;
     };
-    rt1w_stats st;
     std::fprintf(stderr, "rt1w: scene arm %d, %ldx%ld, %ld spp, depth %ld\n", arm, width, height, spp, depth);
     if (adaptive < 0 && (filtered_error || !err_path.empty())) { std::fprintf(stderr, "rt1w: --filtered-error and --err-out go with --adaptive\n"); return 2; }
     if (cross_filter && filtered_error) { std::fprintf(stderr, "rt1w: --cross-filter and --filtered-error exclude each other\n"); return 2; }

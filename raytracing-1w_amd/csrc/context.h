@@ -87,6 +87,11 @@ struct rt1w_context {
     void* dn_buf[3] = {nullptr, nullptr, nullptr}; size_t dn_bytes[3] = {0, 0, 0}; /* rt1w_denoise, rt1w_denoise_var: two colour buffers and the guide buffer */
     double* d_batches = nullptr; size_t batches_bytes = 0; /* rt1w_batch_variance, rt1w_render_denoised_var: the sums of the sample batches */
     double* d_accum = nullptr; size_t accum_bytes = 0; /* rt1w_accum_*, rt1w_render_adaptive: the accumulator and, behind it, the tile errors */
+    /* rt1w_render_temporal: the two sets of (hist[3], len[1], aov[8]) per pixel that swap -- tm_buf[tm_prev] is the previous frame's --,
+     * the image they hold, the camera of the previous frame; tm_valid false: no history (first call, rt1w_temporal_reset, another size) */
+    void* tm_buf[2] = {nullptr, nullptr}; size_t tm_bytes[2] = {0, 0};
+    uint32_t tm_w = 0, tm_h = 0; int tm_prev = 0; bool tm_valid = false;
+    RtCamera tm_cam{};
     RtKernel k64[RT_N_WALKS][RT_N_VARIANTS] = {}; /* g_kernels, queried at creation; the node-cache walks only with a walk table */
     bool walk_table = false; uint32_t walk_table_first = 0;
     bool sphere_media = false; /* every medium of the scene is bounded by a bare Sphere: the sphere-media walks serve */
@@ -125,7 +130,7 @@ double lane_ms(const RtLane& l); /* ms between the two events of the lane, once 
 /* The one way a grow-on-demand device buffer grows: (*p, *have bytes) to at least `need` bytes -- freed and allocated anew, its contents
  * are not kept, nothing happens while it is large enough.  `what` is the text of a failed allocation ("hipMalloc(framebuffer)"), which
  * returns RT1W_ERR_NOMEM and leaves the buffer empty.  Serves the framebuffer, a lane's partial sums, the tile list, the denoisers' buffers,
- * the batch buffer and the accumulator buffer; the strips of rt1w_render_rows pair a device and a pinned host allocation and stay apart. */
+ * the batch buffer, the accumulator buffer and the temporal state; the strips of rt1w_render_rows pair a device and a pinned host allocation and stay apart. */
 int dev_grow(void** p, size_t* have, size_t need, const char* what);
 int reserve_out(rt1w_context* c, size_t bytes); /* the context's framebuffer, grown to at least `bytes` */
 /* plan, launch on lane 0, wait, stats: what every one-shot render entry runs */

@@ -82,6 +82,12 @@ extern "C" int rt1w_internal_f32_create(const void* nodes_, uint32_t n_nodes, co
     return 0;
 }
 
+/* rt1w_context_set_camera: the camera of the f64 view `view64_`, rounded as the conversion rounds it */
+extern "C" void rt1w_internal_f32_set_camera(void* h, const void* view64_) {
+    F32Scene* s = static_cast<F32Scene*>(h);
+    if (s) rt_f32_scene::rt_f32_camera(static_cast<const ::RtSceneView*>(view64_)->camera, s->view.camera);
+}
+
 extern "C" int rt1w_internal_f32_pw(void* h, unsigned stack_cap) {
     F32Scene* s = static_cast<F32Scene*>(h);
     return (s && s->pw_ok && s->pw_stack <= stack_cap) ? 1 : 0;

@@ -1,6 +1,6 @@
 /* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_denoise*,
- * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_guides_*, rt1w_render_adaptive*).  Host code only, built without a device pass: the kernels
- * belong to aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip and adaptive.hip and are reached through rt_feature_launch.h, the context and its render
+ * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_guides_*, rt1w_render_adaptive*, rt1w_temporal_*, rt1w_render_temporal) and a live context's camera (rt1w_context_set_camera).  Host code only, built without a device pass: the kernels
+ * belong to aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip and temporal.hip and are reached through rt_feature_launch.h, the context and its render
  * path belong to context.hip (context.h), so a change here rebuilds none of the code objects.
  * Every entry is its checks, in the order its callers know, then one table of its buffers (Staged) handed to staged_entry(), which does what
  * the host and the device form of an entry differ in -- growing the context's buffers, laying the call's buffers out in them, the copies
@@ -14,6 +14,10 @@
 #include "rt_denoise_var.h" /* rt_dv_batches_ok, rt_dv_sigma, rt_dv_split only */
 #include "rt_adaptive_plan.h" /* the plan of rt1w_render_adaptive and rt1w_adaptive_select; rt_ad_*_ok of rt_adaptive.h; the tile lists' checks */
 #include "rt_guides.h" /* RT_GD_RECORD only */
+#include "rt_temporal.h" /* rt_tm_make_params only */
+
+/* context_f32.hip: the f32 scene's copy of the camera, rounded anew from the f64 view */
+extern "C" void rt1w_internal_f32_set_camera(void* h, const void* view64);
 
 using namespace rt1w;
 namespace {
@@ -838,9 +842,146 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
     });
 }
 
+/* ---- temporal accumulation (include/rt1w.h: rt1w_temporal_accumulate, rt1w_render_temporal) ---- */
+static_assert(sizeof(rt1w_camera) == sizeof(RtCamera), "rt1w_camera is RtCamera's layout");
+int temporal_validate(const rt1w_context* c, const rt1w_temporal_params* p) {
+    if (!c || !p) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (p->width == 0 || p->height == 0 || p->width > 0x40000000u || p->height > 0x40000000u) { set_error("temporal: width and height must be 1 .. 2^30"); return RT1W_ERR_INVALID; }
+    if (p->flags & ~RT1W_DENOISE_KEEP_ALBEDO) { set_error("temporal: unknown flag (flags: 0 or RT1W_DENOISE_KEEP_ALBEDO)"); return RT1W_ERR_INVALID; }
+    if (!(p->depth_tol >= 0.0) || p->depth_tol > 1.7976931348623157e308) { set_error("temporal: depth_tol must be finite and >= 0 (0 = default)"); return RT1W_ERR_INVALID; }
+    if (!(p->normal_min >= 0.0) || p->normal_min > 1.0) { set_error("temporal: normal_min must be 0 .. 1 (0 = default)"); return RT1W_ERR_INVALID; }
+    RtTmParams P;
+    if (!rt_tm_make_params(p->width, p->height, p->flags, p->max_history, p->depth_tol, p->normal_min, P)) { set_error("temporal: parameters refused"); return RT1W_ERR_INVALID; }
+    return RT1W_OK;
+}
+int temporal_common(rt1w_context* c, const rt1w_temporal_params* p, const double* d_cur_frame, const double* d_cur_aov, const void* cur_cam,
+                    const double* d_prev_hist, const double* d_prev_len, const double* d_prev_aov, const void* prev_cam, double* d_hist, double* d_len,
+                    double* d_frame_out, rt1w_stats* stats) {
+    if (rt1w_internal_temporal_sizeof() != sizeof(rt1w_camera)) { set_error("temporal kernel built against another camera layout"); return RT1W_ERR_DEVICE; }
+    return lane_run(c, (uint64_t)p->width * p->height, "temporal accumulation", stats, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_temporal_launch(p->width, p->height, p->flags, p->max_history, p->depth_tol, p->normal_min, d_cur_frame, d_cur_aov, cur_cam,
+                                             d_prev_hist, d_prev_len, d_prev_aov, prev_cam, d_hist, d_len, d_frame_out, stream, launch);
+    });
+}
+/* the two rt1w_temporal_accumulate entries.  Host form: the eight buffers one behind the other in the framebuffer */
+int temporal_accumulate(rt1w_context* c, const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
+                        const double* prev_hist, const double* prev_len, const double* prev_aov, const rt1w_camera* prev_cam, double* hist, double* len,
+                        double* frame_out, bool host, rt1w_stats* stats) {
+    const int rc = temporal_validate(c, p);
+    if (rc < 0) return rc;
+    if (!cur_frame || !cur_aov || !prev_hist || !prev_len || !prev_aov || !hist || !len || !frame_out) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!cur_cam || !prev_cam) { set_error("null camera"); return RT1W_ERR_INVALID; }
+    const size_t npix = (size_t)p->width * p->height;
+    Staged s[] = {{cur_frame, nullptr, npix * 3, FRAMEBUFFER, "temporal: frame copy", nullptr},
+                  {cur_aov, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, "temporal: feature buffer copy", nullptr},
+                  {prev_hist, nullptr, npix * 3, FRAMEBUFFER, "temporal: history copy", nullptr},
+                  {prev_len, nullptr, npix, FRAMEBUFFER, "temporal: history length copy", nullptr},
+                  {prev_aov, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, "temporal: previous feature buffer copy", nullptr},
+                  {nullptr, hist, npix * 3, FRAMEBUFFER, nullptr, "temporal: history result copy"},
+                  {nullptr, len, npix, FRAMEBUFFER, nullptr, "temporal: history length result copy"},
+                  {nullptr, frame_out, npix * 3, FRAMEBUFFER, nullptr, "temporal: frame result copy"}};
+    /* an output that overlaps another buffer of the call (the three outputs are rows 5 .. 7) */
+    for (int o = 5; o < 8; ++o)
+        for (int k = 0; k < 8; ++k) {
+            const char* a = (const char*)s[o].out;
+            const char* b = k < 5 ? (const char*)s[k].in : (const char*)s[k].out;
+            if (k != o && a < b + s[k].count * sizeof(double) && b < a + s[o].count * sizeof(double)) {
+                set_error("temporal: hist, len and frame_out must not overlap each other or an input"); return RT1W_ERR_INVALID;
+            }
+        }
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
+        return temporal_common(c, p, s[0].d_in, s[1].d_in, cur_cam, s[2].d_in, s[3].d_in, s[4].d_in, prev_cam, s[5].d_out, s[6].d_out, s[7].d_out, st);
+    });
+}
+/* rt1w_render_temporal: frame_out and the frame in the framebuffer; history, its length and the feature buffers in the context's two state sets */
+int render_temporal(rt1w_context* c, const rt1w_render_params* p, const rt1w_temporal_params* t, const rt1w_denoise_params* d, double* out_rgb, rt1w_stats* stats) {
+    int rc = denoised_render_validate(c, p, out_rgb);
+    if (rc < 0) return rc;
+    if (p->x0 != 0u || p->y0 != 0u || p->tile_w != p->width || p->tile_h != p->height) {
+        set_error("rt1w_render_temporal takes the whole image (the reprojection works in image coordinates)"); return RT1W_ERR_INVALID;
+    }
+    rt1w_temporal_params tp;
+    memset(&tp, 0, sizeof tp);
+    if (t) tp = *t;
+    if ((tp.width && tp.width != p->width) || (tp.height && tp.height != p->height)) { set_error("temporal: width / height must be 0 or the image's"); return RT1W_ERR_INVALID; }
+    tp.width = p->width; tp.height = p->height;
+    if ((rc = temporal_validate(c, &tp)) < 0) return rc;
+    rt1w_denoise_params dp;
+    if (d && (rc = denoised_filter_params(c, d, p->width, p->height, &dp)) < 0) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    Staged s[] = {{nullptr, out_rgb, npix * 3, FRAMEBUFFER, nullptr, "temporal frame copy"}, {nullptr, nullptr, npix * 3, FRAMEBUFFER, nullptr, nullptr}};
+    return staged_entry(c, true, s, stats, [&](rt1w_stats* st) {
+        double *d_out = s[0].d_out, *d_frame = s[1].d_out;
+        const size_t set_bytes = npix * (3 + 1 + RT1W_AOV_CHANNELS) * sizeof(double);
+        int r;
+        if (c->tm_w != p->width || c->tm_h != p->height) c->tm_valid = false;
+        for (int k = 0; k < 2; ++k)
+            if ((r = dev_grow(&c->tm_buf[k], &c->tm_bytes[k], set_bytes, "hipMalloc(temporal state)")) < 0) { c->tm_valid = false; return r; }
+        c->tm_w = p->width; c->tm_h = p->height;
+        const int prev = c->tm_prev, cur = 1 - prev;
+        double *ph = (double*)c->tm_buf[prev], *pl = ph + npix * 3, *pa = pl + npix;
+        double *ch = (double*)c->tm_buf[cur], *cl = ch + npix * 3, *ca = cl + npix;
+        if (!c->tm_valid) { /* no history: prev_len = 0 everywhere (all of the set is zeroed), prev_cam = cur_cam */
+            if (!hip_ok(hipMemsetAsync(ph, 0, set_bytes, c->lane[0].stream), "temporal state reset")) return RT1W_ERR_DEVICE;
+            c->tm_cam = c->view.camera;
+        }
+        memset(st, 0, sizeof *st);
+        if ((r = render_common(c, p, d_frame, st)) < 0) return r;
+        rt1w_render_params ap = *p; /* the feature buffers of the same image, samples and seed, by the scene's own variant */
+        ap.flags = 0u;
+        rt1w_stats sa, sm, sd;
+        memset(&sd, 0, sizeof sd);
+        if ((r = render_aov_common(c, &ap, nullptr, ca, &sa)) < 0) return r;
+        c->tm_valid = false; /* a failure from here on leaves no history behind */
+        if ((r = temporal_common(c, &tp, d_frame, ca, &c->view.camera, ph, pl, pa, &c->tm_cam, ch, cl, d_out, &sm)) < 0) return r;
+        c->tm_prev = cur; c->tm_cam = c->view.camera; c->tm_valid = true;
+        if (d && (r = denoise_common(c, &dp, d_out, ca, d_out, &sd)) < 0) return r;
+        st->kernel_ms = st->kernel_ms + sa.kernel_ms + sm.kernel_ms + sd.kernel_ms;
+        st->grid = d ? sd.grid : sm.grid; st->block = d ? sd.block : sm.block;
+        return RT1W_OK;
+    });
+}
+
 } // namespace
 
 extern "C" {
+int rt1w_context_set_camera(rt1w_context* c, const double look_from[3], const double look_at[3], const double vup[3], double vfov_deg,
+                            double aspect_ratio, double aperture, double focus_dist, double time0, double time1) {
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    RtCamera cam;
+    const char* why = nullptr;
+    if (camera_make(look_from, look_at, vup, vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1, &cam, &why) < 0) { set_error(why); return RT1W_ERR_INVALID; }
+    /* the view every f64 kernel takes by value -- the generic, scene-specialised, reference-stream, pair-walk and tile-list kernels and the
+     * AOV kernels all read this one copy -- and the f32 scene's rounded copy, if it has been built */
+    c->view.camera = cam;
+    rt1w_internal_f32_set_camera(c->f32_scene, &c->view);
+    return RT1W_OK;
+}
+int rt1w_context_get_camera(const rt1w_context* c, rt1w_camera* out) {
+    if (!c || !out) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    memcpy(out, &c->view.camera, sizeof *out);
+    return RT1W_OK;
+}
+int rt1w_temporal_accumulate(rt1w_context* c, const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
+                             const double* prev_hist, const double* prev_len, const double* prev_aov, const rt1w_camera* prev_cam, double* hist,
+                             double* len, double* frame_out, rt1w_stats* stats) {
+    return temporal_accumulate(c, p, cur_frame, cur_aov, cur_cam, prev_hist, prev_len, prev_aov, prev_cam, hist, len, frame_out, true, stats);
+}
+int rt1w_temporal_accumulate_device(rt1w_context* c, const rt1w_temporal_params* p, const void* d_cur_frame, const void* d_cur_aov,
+                                    const rt1w_camera* cur_cam, const void* d_prev_hist, const void* d_prev_len, const void* d_prev_aov,
+                                    const rt1w_camera* prev_cam, void* d_hist, void* d_len, void* d_frame_out, rt1w_stats* stats) {
+    return temporal_accumulate(c, p, (const double*)d_cur_frame, (const double*)d_cur_aov, cur_cam, (const double*)d_prev_hist, (const double*)d_prev_len,
+                               (const double*)d_prev_aov, prev_cam, (double*)d_hist, (double*)d_len, (double*)d_frame_out, false, stats);
+}
+int rt1w_render_temporal(rt1w_context* c, const rt1w_render_params* p, const rt1w_temporal_params* t, const rt1w_denoise_params* d, double* out_rgb,
+                         rt1w_stats* stats) {
+    return render_temporal(c, p, t, d, out_rgb, stats);
+}
+int rt1w_temporal_reset(rt1w_context* c) {
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    c->tm_valid = false;
+    return RT1W_OK;
+}
 int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_aov, rt1w_stats* stats) { return render_aov(c, p, nullptr, out_aov, true, stats); }
 int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d_out_aov, rt1w_stats* stats) { return render_aov(c, p, nullptr, d_out_aov, false, stats); }
 int rt1w_render_aov_deep(rt1w_context* c, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, double* out_aov, rt1w_stats* stats) {

@@ -68,6 +68,13 @@ struct Arrays {
     uint32_t pw_stack = 0; /* pushed right children a walk can hold at once: the depth of the inner-record tree */
 };
 
+/* the camera, every quantity rounded once: at the conversion, and again when a live context's camera is set (rt1w_context_set_camera) */
+inline void rt_f32_camera(const ::RtCamera& c, RT_F32_NS::RtCamera& o) {
+    o.origin = v3f(c.origin); o.lower_left_corner = v3f(c.lower_left_corner); o.horizontal = v3f(c.horizontal);
+    o.vertical = v3f(c.vertical); o.u = v3f(c.u); o.v = v3f(c.v); o.w = v3f(c.w);
+    o.lens_radius = (float)c.lens_radius; o.time0 = (float)c.time0; o.time1 = (float)c.time1;
+}
+
 /* `v64`: the f64 view of the scene (counts, root, camera, background; its array pointers are not read, `images` is copied as it is) */
 inline void rt_f32_convert(const ::RtNode* nodes, uint32_t n_nodes, const ::RtNode* lights, uint32_t n_lights, const ::RtMaterial* materials,
                            uint32_t n_materials, const ::RtTexture* textures, uint32_t n_textures, const ::RtPerlin* perlin, uint32_t n_perlin,
@@ -99,10 +106,7 @@ inline void rt_f32_convert(const ::RtNode* nodes, uint32_t n_nodes, const ::RtNo
     memset(&v, 0, sizeof v);
     v.images = v64.images;
     v.root = v64.root; v.n_nodes = v64.n_nodes; v.n_lights = v64.n_lights; v.n_materials = v64.n_materials; v.n_textures = v64.n_textures;
-    const ::RtCamera& c = v64.camera;
-    v.camera.origin = v3f(c.origin); v.camera.lower_left_corner = v3f(c.lower_left_corner); v.camera.horizontal = v3f(c.horizontal);
-    v.camera.vertical = v3f(c.vertical); v.camera.u = v3f(c.u); v.camera.v = v3f(c.v); v.camera.w = v3f(c.w);
-    v.camera.lens_radius = (float)c.lens_radius; v.camera.time0 = (float)c.time0; v.camera.time1 = (float)c.time1;
+    rt_f32_camera(v64.camera, v.camera);
     v.background = v3f(v64.background);
     /* pair-walk records of a sphere scene, from THIS build's node array (boxes already widened by conv_node) */
     memset(&s.pw, 0, sizeof s.pw);

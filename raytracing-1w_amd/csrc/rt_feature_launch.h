@@ -1,4 +1,4 @@
-/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip and adaptive.hip, declared once.
+/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip and temporal.hip, declared once.
  * The functions are extern "C": nothing in their names says what they take, so caller and definition both include this header and the
  * compiler holds each definition to the declaration the caller sees.  Private (librt1w.map exports none of them).
  * The *_launch functions enqueue on `stream`, put grid and block of the launch (of the level kernel, for the filters) into launch[0..1]
@@ -61,6 +61,13 @@ unsigned rt1w_internal_aov_tiles_sizeof(int what);
 int rt1w_internal_guides_merge_tiles_launch(uint32_t w, uint32_t h, uint32_t tile, const uint32_t* rec, uint32_t n, uint32_t spp, const double* sums,
                                             double* gacc, hipStream_t stream, unsigned launch[2]);
 int rt1w_internal_guides_resolve_launch(uint32_t w, uint32_t h, const double* gacc, double* aov, hipStream_t stream, unsigned launch[2]);
+/* temporal.hip: the reprojection and accumulation of rt1w_temporal_accumulate, one launch; the two cameras by address, each
+ * rt1w_internal_temporal_sizeof() bytes in the layout of rt1w_camera, copied into the kernel's arguments */
+int rt1w_internal_temporal_launch(uint32_t w, uint32_t h, uint32_t flags, uint32_t max_history, double depth_tol, double normal_min,
+                                  const double* cur_frame, const double* cur_aov, const void* cur_cam, const double* prev_hist, const double* prev_len,
+                                  const double* prev_aov, const void* prev_cam, double* hist, double* len, double* frame_out, hipStream_t stream,
+                                  unsigned launch[2]);
+unsigned rt1w_internal_temporal_sizeof(void);
 }
 
 #endif

@@ -723,26 +723,9 @@ int rt1w_scene_set_camera(rt1w_scene* s, const double look_from[3], const double
                           const double vup[3], double vfov_deg, double aspect_ratio, double aperture,
                           double focus_dist, double time0, double time1) {
     CHECK_SCENE(s);
-    if (!look_from || !look_at || !vup) { set_error("null camera vector"); return RT1W_ERR_INVALID; }
-    if (!(time0 < time1)) { set_error("camera needs time0 < time1 (gen_range panics otherwise, camera.rs:71)"); return RT1W_ERR_INVALID; }
-    /* Camera::new camera.rs:22-59 */
-    RtV3 lf = rt_v3(look_from[0], look_from[1], look_from[2]);
-    RtV3 la = rt_v3(look_at[0], look_at[1], look_at[2]);
-    RtV3 up = rt_v3(vup[0], vup[1], vup[2]);
-    double theta = vfov_deg * (RT_PI / 180.0);
-    double h = rt_tan(theta / 2.0);
-    double viewport_height = 2.0 * h;
-    double viewport_width = aspect_ratio * viewport_height;
     RtCamera c;
-    c.w = rt_normalize(lf - la);
-    c.u = rt_normalize(rt_cross(up, c.w));
-    c.v = rt_cross(c.w, c.u);
-    c.origin = lf;
-    c.horizontal = focus_dist * viewport_width * c.u;
-    c.vertical = focus_dist * viewport_height * c.v;
-    c.lower_left_corner = c.origin - c.horizontal / 2.0 - c.vertical / 2.0 - focus_dist * c.w;
-    c.lens_radius = aperture / 2.0;
-    c.time0 = time0; c.time1 = time1;
+    const char* why = nullptr;
+    if (camera_make(look_from, look_at, vup, vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1, &c, &why) < 0) { set_error(why); return RT1W_ERR_INVALID; }
     s->camera = c; s->has_camera = true;
     return RT1W_OK;
 }

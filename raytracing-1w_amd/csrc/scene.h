@@ -36,6 +36,34 @@ struct HostHittable {
 
 void set_error(const std::string& msg);
 
+/* Camera::new (camera.rs:22-59) from the arguments of rt1w_scene_set_camera: the one text behind the scene's camera
+ * (rt1w_scene_set_camera), a live context's (rt1w_context_set_camera) and the diagnostics library's.  RT1W_OK, or RT1W_ERR_INVALID
+ * with the refusal's text in *why */
+inline int camera_make(const double look_from[3], const double look_at[3], const double vup[3], double vfov_deg, double aspect_ratio,
+                       double aperture, double focus_dist, double time0, double time1, RtCamera* out, const char** why) {
+    if (!look_from || !look_at || !vup) { *why = "null camera vector"; return RT1W_ERR_INVALID; }
+    if (!(time0 < time1)) { *why = "camera needs time0 < time1 (gen_range panics otherwise, camera.rs:71)"; return RT1W_ERR_INVALID; }
+    RtV3 lf = rt_v3(look_from[0], look_from[1], look_from[2]);
+    RtV3 la = rt_v3(look_at[0], look_at[1], look_at[2]);
+    RtV3 up = rt_v3(vup[0], vup[1], vup[2]);
+    double theta = vfov_deg * (RT_PI / 180.0);
+    double h = rt_tan(theta / 2.0);
+    double viewport_height = 2.0 * h;
+    double viewport_width = aspect_ratio * viewport_height;
+    RtCamera c;
+    c.w = rt_normalize(lf - la);
+    c.u = rt_normalize(rt_cross(up, c.w));
+    c.v = rt_cross(c.w, c.u);
+    c.origin = lf;
+    c.horizontal = focus_dist * viewport_width * c.u;
+    c.vertical = focus_dist * viewport_height * c.v;
+    c.lower_left_corner = c.origin - c.horizontal / 2.0 - c.vertical / 2.0 - focus_dist * c.w;
+    c.lens_radius = aperture / 2.0;
+    c.time0 = time0; c.time1 = time1;
+    *out = c;
+    return RT1W_OK;
+}
+
 } // namespace rt1w
 
 struct rt1w_scene {

@@ -192,6 +192,21 @@ int final_scene(B& b, const uint8_t* rgb, uint32_t w, uint32_t h) {
 
 } // namespace
 
+/* the camera of a scene arm (main.rs:798-800 defaults, overridden per arm :816-936; Camera::new's other arguments :941-951) */
+extern "C" int rt1w_reference_camera(int arm, double look_from[3], double look_at[3], double vup[3], double* vfov_deg, double* aperture, double* focus_dist) {
+    if (!look_from || !look_at || !vup || !vfov_deg || !aperture || !focus_dist) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }
+    const double from_default[3] = {13.0, 2.0, 3.0}, from_light[3] = {26.0, 3.0, 6.0}, from_cornell[3] = {278.0, 278.0, -800.0}, from_final[3] = {478.0, 278.0, -600.0};
+    const bool cornell = arm == 5 || arm == 6, final_scene = arm < 0 || arm > 6;
+    const double* lf = arm == 4 ? from_light : cornell ? from_cornell : final_scene ? from_final : from_default;
+    for (int k = 0; k < 3; ++k) { look_from[k] = lf[k]; look_at[k] = 0.0; vup[k] = k == 1 ? 1.0 : 0.0; }
+    if (arm == 4) look_at[1] = 2.0;
+    if (cornell || final_scene) { look_at[0] = 278.0; look_at[1] = 278.0; }
+    *vfov_deg = (cornell || final_scene) ? 40.0 : 20.0;
+    *aperture = arm == 0 ? 0.1 : 0.0;
+    *focus_dist = 10.0;
+    return RT1W_OK;
+}
+
 extern "C" int rt1w_scene_build_reference(int arm, uint64_t build_seed, double aspect_ratio,
                                           const uint8_t* earth_rgb8, uint32_t earth_w, uint32_t earth_h,
                                           rt1w_scene** out, uint32_t defaults[3]) {
@@ -208,53 +223,42 @@ extern "C" int rt1w_scene_build_reference(int arm, uint64_t build_seed, double a
     /* main.rs:798-800 defaults, overridden per arm */
     uint32_t image_width = 400, samples_per_pixel = 100;
     double bg[3] = {0.70, 0.80, 1.00};
-    double look_from[3] = {13.0, 2.0, 3.0}, look_at[3] = {0.0, 0.0, 0.0};
-    double vfov = 20.0, aperture = 0.0;
     std::vector<int> lights;
     int null_mat = b.ck(rt1w_material_null(s)); /* main.rs:805 */
     int world = -1;
     switch (arm) {
-        case 0: samples_per_pixel = 500; world = random_scene(b); aperture = 0.1; break;        /* main.rs:816-827 */
+        case 0: samples_per_pixel = 500; world = random_scene(b); break;                      /* main.rs:816-827 */
         case 1: world = two_spheres(b); break;                                                  /* :828-836 */
         case 2: world = two_perlin_spheres(b); break;                                           /* :837-845 */
         case 3: world = earth(b, earth_rgb8, earth_w, earth_h); break;                          /* :846-854 */
         case 4:                                                                                 /* :855-866 */
             samples_per_pixel = 400; world = simple_light(b);
             bg[0] = bg[1] = bg[2] = 0.0;
-            look_from[0] = 26.0; look_from[1] = 3.0; look_from[2] = 6.0; look_at[1] = 2.0;
             break;
         case 5:                                                                                 /* :867-894 */
             image_width = 600; samples_per_pixel = 100; world = cornel_box(b);
             lights.push_back(b.xz(213.0, 343.0, 227.0, 332.0, 554.0, null_mat));
             lights.push_back(b.sphere(190.0, 90.0, 190.0, 90.0, null_mat));
             bg[0] = bg[1] = bg[2] = 0.0;
-            look_from[0] = 278.0; look_from[1] = 278.0; look_from[2] = -800.0;
-            look_at[0] = 278.0; look_at[1] = 278.0; look_at[2] = 0.0;
-            vfov = 40.0;
             break;
         case 6:                                                                                 /* :895-915 */
             image_width = 600; samples_per_pixel = 200; world = cornel_smoke(b);
             lights.push_back(b.xz(113.0, 443.0, 127.0, 432.0, 554.0, null_mat));
             bg[0] = bg[1] = bg[2] = 0.0;
-            look_from[0] = 278.0; look_from[1] = 278.0; look_from[2] = -800.0;
-            look_at[0] = 278.0; look_at[1] = 278.0; look_at[2] = 0.0;
-            vfov = 40.0;
             break;
         default:                                                                                /* :916-936 */
             image_width = 800; samples_per_pixel = 10000; world = final_scene(b, earth_rgb8, earth_w, earth_h);
             lights.push_back(b.xz(123.0, 423.0, 147.0, 412.0, 554.0, null_mat));
             bg[0] = bg[1] = bg[2] = 0.0;
-            look_from[0] = 478.0; look_from[1] = 278.0; look_from[2] = -600.0;
-            look_at[0] = 278.0; look_at[1] = 278.0; look_at[2] = 0.0;
-            vfov = 40.0;
             break;
     }
-    double vup[3] = {0.0, 1.0, 0.0};
+    double look_from[3], look_at[3], vup[3], vfov, aperture, focus_dist;
+    (void)rt1w_reference_camera(arm, look_from, look_at, vup, &vfov, &aperture, &focus_dist);
     if (b.err == RT1W_OK) b.ck(rt1w_scene_set_world(s, world));
     if (b.err == RT1W_OK) b.ck(rt1w_scene_set_lights(s, lights.data(), (uint32_t)lights.size()));
     if (b.err == RT1W_OK) b.ck(rt1w_scene_set_background(s, bg));
     /* Camera::new(look_from, look_at, vup, vfov, aspect_ratio, aperture, 10.0, 0.0, 1.0) main.rs:941-951 */
-    if (b.err == RT1W_OK) b.ck(rt1w_scene_set_camera(s, look_from, look_at, vup, vfov, aspect_ratio, aperture, 10.0, 0.0, 1.0));
+    if (b.err == RT1W_OK) b.ck(rt1w_scene_set_camera(s, look_from, look_at, vup, vfov, aspect_ratio, aperture, focus_dist, 0.0, 1.0));
     if (b.err == RT1W_OK) b.ck(rt1w_scene_commit(s));
     if (b.err != RT1W_OK) { rt1w_scene_destroy(s); return b.err; }
     if (defaults) {

@@ -80,6 +80,21 @@ int rt1w_lab_aov_tiles_host(const rt1w_scene* s, const rt1w_render_params* p, ui
 int rt1w_lab_guides_merge_tiles_host(uint32_t width, uint32_t height, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, uint32_t spp,
                                      const double* tile_sums, double* gacc);
 int rt1w_lab_guides_resolve_host(uint32_t width, uint32_t height, const double* gacc, double* aov);
+/* CPU twin of rt1w_temporal_accumulate (denoise_host.cpp: rt_temporal.h built for the host): the same hist[h][w][3], len[h][w] and
+ * frame_out[h][w][3] from host buffers, no GPU; RT1W_ERR_INVALID as the device entry (null pointers, overlapping outputs, zero sizes,
+ * unknown flags, bad tolerances).  rec, for the tests: per pixel fx, fy, the four taps' weights (0 where a tap is not valid), their sum,
+ * 1 / 0 history */
+int rt1w_lab_temporal_host(const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
+                           const double* prev_hist, const double* prev_len, const double* prev_aov, const rt1w_camera* prev_cam, double* hist,
+                           double* len, double* frame_out, double* rec /* [h][w][8], may be null */);
+/* The camera of a COMMITTED scene as the twins and rt1w_scene_copy_flat see it (aov_host.cpp).  set: what rt1w_context_set_camera does to
+ * a context's view, done to the scene's own record through the same function (csrc/scene.h: camera_make) with the same refusals -- the
+ * twins, which build their view from the scene, then render the camera a live context would.  A diagnostic: it breaks the rule that a
+ * committed scene is immutable.  Everything made from the scene afterwards -- a context too -- sees a scene committed with these
+ * arguments; contexts made before keep the camera they copied.  get: the ten quantities of the scene's record */
+int rt1w_lab_scene_set_camera(rt1w_scene* s, const double look_from[3], const double look_at[3], const double vup[3], double vfov_deg,
+                              double aspect_ratio, double aperture, double focus_dist, double time0, double time1);
+int rt1w_lab_scene_get_camera(const rt1w_scene* s, rt1w_camera* out);
 /* the two functions the filters build their weights from (rt_denoise.h), on their own: out[i] = rt_dn_falloff(x[i]) (fn 0; e may be
  * null) or rt_dn_powi(x[i], e[i]) (fn 1).  device 0: the host build of denoise_host.cpp, no GPU; device 1: one lane per element on
  * GPU 0 (f32_exact.hip).  RT1W_ERR_INVALID for anything else, null pointers or n = 0 */
