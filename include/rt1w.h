@@ -911,6 +911,10 @@ int rt1w_context_specialise(rt1w_context* c, uint32_t flags, rt1w_specialise_inf
 /* cache key of the specialised kernel of a committed scene (16 hex digits + NUL): the code object is
  * `sweep_<key>.hsaco` in the kernel cache.  No GPU needed.  RT1W_ERR_UNSUPPORTED for scenes of more than 256 nodes. */
 int rt1w_scene_kernel_key(const rt1w_scene* s, char out[24]);
+/* copy of the translation unit that is generated for a committed scene (f32 != 0: its single-precision build): the topology tables the
+ * specialised kernel is compiled around, as text.  No GPU needed.  Returns bytes written (no NUL), or the needed size if buf==NULL;
+ * RT1W_ERR_UNSUPPORTED for scenes of more than 256 nodes. */
+int64_t rt1w_scene_kernel_source(const rt1w_scene* s, int f32, char* buf, uint64_t cap);
 
 /* ---- output side (src/color.rs) ---- */
 

@@ -144,6 +144,7 @@ _sig("rt1w_context_create", C.c_int, C.c_int, _P, C.POINTER(_P))
 _sig("rt1w_context_destroy", None, _P)
 _sig("rt1w_context_specialise", C.c_int, _P, C.c_uint32, C.POINTER(SpecialiseInfo))
 _sig("rt1w_scene_kernel_key", C.c_int, _P, C.c_char * 24)
+_sig("rt1w_scene_kernel_source", C.c_int64, _P, C.c_int, _P, C.c_uint64)
 _sig("rt1w_default_chunk", C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
 _sig("rt1w_scene_default_chunk", C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32)
 _sig("rt1w_render", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(Stats))
@@ -598,6 +599,14 @@ class Scene:
         buf = (C.c_char * 24)()
         _ck(_lib.rt1w_scene_kernel_key(self._h, buf))
         return buf.value.decode()
+
+    def kernel_source(self, f32=False):
+        """The translation unit generated for this scene's specialised kernel (struct TopoJit: kind, skip, reuse), as text."""
+        n = _lib.rt1w_scene_kernel_source(self._h, int(f32), None, 0)
+        _ck(int(n))
+        buf = C.create_string_buffer(int(n) + 1)
+        _ck(int(_lib.rt1w_scene_kernel_source(self._h, int(f32), buf, int(n))))
+        return buf.raw[:int(n)].decode()
 
     def flat(self, what):
         """Bytes of one flat array (0 nodes,1 lights,2 materials,3 textures,4 perlin,5 images,6 camera+bg)."""

@@ -3,8 +3,9 @@
  * For a scene of <= RT_JIT_MAX_NODES nodes the pre-order sweep can be unrolled along the scene's own
  * tree (rt_sweep_static in rt_core.h) once the node kinds and subtree ends are compile-time constants.
  * They are only known when a scene has been committed, so the kernel is generated then: this file writes
- * a ten-line translation unit (the topology as constexpr arrays + one extern "C" kernel around
- * rt_render_sorted_body), hands it and the library's own headers (embedded at build time,
+ * a short translation unit (the topology as constexpr arrays -- node kinds, subtree ends, the slab planes
+ * a box shares with a box above it -- and one extern "C" kernel around rt_render_sorted_body), hands it
+ * and the library's own headers (embedded at build time,
  * jit_headers.inc) to hiprtc, and keeps the code object in a cache keyed by a hash of everything that
  * went into the compiler.  The arithmetic of a path is the same source as in the generic kernels; only
  * control flow is resolved earlier, so results are bit-identical (tests/test_gpu_parity.py).
@@ -172,6 +173,23 @@ bool jit_eligible(const rt1w_scene& s) {
     return s.committed && !s.flat_nodes.empty() && s.flat_nodes.size() <= RT_JIT_MAX_NODES;
 }
 
+/* Topo::reuse (rt_core.h: rt_aabb_hit_chain): the nearest BVH node above I, in I's ray space, whose plane k (0-2 min x/y/z, 3-5 max
+ * x/y/z) holds the same 8 bytes as I's (-0.0 is not +0.0), or I.  Only nodes on the way up from I are looked at -- a sibling or an
+ * earlier subtree computed its products under another lane mask -- and the way ends at the first Translate, RotateY (another ray
+ * space) or ConstantMedium (its boundary is swept on its own, from an empty chain); FlipFace leaves the ray alone.  The kernel relies
+ * on exactly this: every node named here has its frame on the chain when I is tested. */
+static uint32_t jit_slab_reuse(const std::vector<RtNode>& N, uint32_t root, uint32_t I, uint32_t k) {
+    if ((N[I].kind & RT_KIND_MASK) > RT_BVH1) return I;
+    for (uint32_t J = I; J-- > root;) {
+        if (N[J].skip <= I) continue; /* not above I */
+        const uint32_t kj = N[J].kind & RT_KIND_MASK;
+        if (kj == RT_FLIP) continue;
+        if (kj > RT_BVH1) break;
+        if (std::memcmp(&N[J].d[k], &N[I].d[k], sizeof(double)) == 0) return J;
+    }
+    return I;
+}
+
 std::string jit_source(const rt1w_scene& s, bool f32) {
     const std::vector<RtNode>& N = s.flat_nodes;
     std::string src;
@@ -198,6 +216,24 @@ std::string jit_source(const rt1w_scene& s, bool f32) {
     src += "};\n";
     src += "    static constexpr uint32_t skip[" + std::to_string(N.size()) + "] = {";
     for (size_t i = 0; i < N.size(); ++i) src += (i ? ", " : "") + std::to_string(N[i].skip) + "u";
+    src += "};\n";
+    /* which slab products a box takes from a box above it: part of the text, hence of the key -- the key depends on which bounds
+     * coincide, not on their values.
+     * Scenes with media (cornel_smoke) take whole axes only -- both planes from the same box, its swapped pair as it is.  A single
+     * product kept for a box below lives across the boundary sweeps in between: with every entry the cornel_smoke kernel went from
+     * 20 to 30 spilled VGPRs and from 60 to 68 B of scratch at four waves, with whole axes it has the resources it had without the
+     * table (profiles/slab_reuse_resources.txt) */
+    const bool whole_axes = s.has_media;
+    src += "    static constexpr uint32_t reuse[" + std::to_string(N.size()) + "][6] = {";
+    for (size_t i = 0; i < N.size(); ++i) {
+        src += i ? ", {" : "{";
+        for (uint32_t k = 0; k < 6u; ++k) {
+            uint32_t r = i >= s.flat_root ? jit_slab_reuse(N, s.flat_root, (uint32_t)i, k) : (uint32_t)i;
+            if (whole_axes && r != jit_slab_reuse(N, s.flat_root, (uint32_t)i, (k + 3u) % 6u)) r = (uint32_t)i;
+            src += (k ? ", " : "") + std::to_string(r) + "u";
+        }
+        src += "}";
+    }
     src += "};\n};\n";
     /* the features the scene actually has (code for the others is not generated, rt_flat.h RtCfg) */
     uint32_t depth = s.scope_depth < 2u ? 2u : s.scope_depth;
@@ -302,6 +338,17 @@ int jit_precompile_to(const rt1w_scene& s, const std::string& dir, JitInfo& info
 }
 
 } // namespace rt1w
+
+extern "C" int64_t rt1w_scene_kernel_source(const rt1w_scene* s, int f32, char* buf, uint64_t cap) {
+    if (!s) { rt1w::set_error("null scene"); return RT1W_ERR_INVALID; }
+    if (!s->committed) { rt1w::set_error("scene not committed"); return RT1W_ERR_STATE; }
+    if (!rt1w::jit_eligible(*s)) { rt1w::set_error("scene has more than RT_JIT_MAX_NODES nodes: no specialised kernel"); return RT1W_ERR_UNSUPPORTED; }
+    const std::string src = rt1w::jit_source(*s, f32 != 0);
+    if (!buf) return (int64_t)src.size();
+    if (cap < src.size()) { rt1w::set_error("buffer too small"); return RT1W_ERR_INVALID; }
+    std::memcpy(buf, src.data(), src.size());
+    return (int64_t)src.size();
+}
 
 extern "C" int rt1w_scene_kernel_key(const rt1w_scene* s, char out[24]) {
     if (!s || !out) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }

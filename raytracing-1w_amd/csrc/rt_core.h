@@ -39,6 +39,9 @@
 #ifndef RT_STAT_VISIT
 #define RT_STAT_VISIT(kind) ((void)0) /* hook for offline visit statistics (tools only) */
 #endif
+#ifndef RT_STAT_SLAB
+#define RT_STAT_SLAB(literal) ((void)0) /* hook of the CPU tests: which form a box test of the unrolled sweep took */
+#endif
 
 /* "does any lane of this wave want this?" -- a scalar branch on the GPU; the CPU test
  * build runs one lane at a time */
@@ -882,79 +885,144 @@ RT_HD bool rt_traverse_sweep(const RtSceneView& sc, const NS& ns, uint32_t root,
     return best_prim != RT_NONE;
 }
 
+/* Slab products a box shares with its ancestors (the unrolled sweep only).  In a median-split tree a child box keeps most of its
+ * parent's faces, and for one ray in one ray space equal bound bits give equal products `(bound - o) * inv`.  The generator (jit.cpp:
+ * jit_slab_reuse) says which: Topo::reuse[I][k] names, for plane k of BVH node I (0-2 min x/y/z, 3-5 max x/y/z), the nearest ancestor
+ * BVH node in the same ray space whose d[k] holds the same 8 bytes, or I itself.  Every box test leaves its six products and the three
+ * swapped pairs in a frame; the frames of the boxes above it are found by node index at compile time (the chain is a type), and a lane
+ * reads a frame only after it passed that box, i.e. after it filled it.  A Topo without the table reuses nothing. */
+template <class T> struct RtVoid { typedef void type; };
+template <class Topo, class = void>
+struct RtSlabReuse { static constexpr uint32_t of(uint32_t i, uint32_t) { return i; } };
+template <class Topo>
+struct RtSlabReuse<Topo, typename RtVoid<decltype(Topo::reuse)>::type> { static constexpr uint32_t of(uint32_t i, uint32_t k) { return Topo::reuse[i][k]; } };
+struct RtSlabNone {}; /* the empty chain: the root of a sweep, below a Translate / RotateY, inside a medium's boundary sweeps */
+template <uint32_t J, class Up>
+struct RtSlabFrame {
+    double p[6];         /* (d[k] - o) * inv, before the swap */
+    double lo[3], hi[3]; /* the pairs after the `inv < 0` swap */
+    const Up& up;
+    RT_HD explicit RtSlabFrame(const Up& u) : up(u) {}
+};
+template <uint32_t J, uint32_t K, class Up>
+RT_HD const auto& rt_slab_find(const RtSlabFrame<K, Up>& f) {
+    if constexpr (J == K) return f;
+    else return rt_slab_find<J>(f.up); /* no overload for RtSlabNone: a table that names a node off the chain does not compile */
+}
+/* One box test of the unrolled sweep: rt_aabb_hit (LITERAL) or rt_aabb_hit_fast<EARLY> with the products taken from the chain where the
+ * table allows it -- the same operands reach the same operations in the same order, so the same bits.  Both forms fill the frame: a
+ * descendant may run the other one. */
+template <class Topo, uint32_t I, bool LITERAL, bool EARLY, class Up>
+RT_HD bool rt_aabb_hit_chain(const double* bb, RtV3 o, RtV3 inv, double t_min, double t_max, RtSlabFrame<I, Up>& fr) {
+    bool open = true;
+#define RT_SLAB(A, ov, iv)                                                                            \
+    {                                                                                                 \
+        constexpr uint32_t j0 = RtSlabReuse<Topo>::of(I, A), j1 = RtSlabReuse<Topo>::of(I, A + 3u);   \
+        if constexpr (j0 != I && j0 == j1) { /* both planes from one box: its swapped pair as it is */ \
+            const auto& a = rt_slab_find<j0>(fr.up);                                                  \
+            fr.p[A] = a.p[A]; fr.p[A + 3] = a.p[A + 3]; fr.lo[A] = a.lo[A]; fr.hi[A] = a.hi[A];       \
+        } else {                                                                                      \
+            if constexpr (j0 != I) fr.p[A] = rt_slab_find<j0>(fr.up).p[A];                            \
+            else fr.p[A] = (bb[A] - (ov)) * (iv);                                                     \
+            if constexpr (j1 != I) fr.p[A + 3] = rt_slab_find<j1>(fr.up).p[A + 3];                    \
+            else fr.p[A + 3] = (bb[A + 3] - (ov)) * (iv);                                             \
+            double t0 = fr.p[A], t1 = fr.p[A + 3];                                                    \
+            if ((iv) < RT_R(0.0)) { double s_ = t0; t0 = t1; t1 = s_; }                               \
+            fr.lo[A] = t0; fr.hi[A] = t1;                                                             \
+        }                                                                                             \
+        if constexpr (LITERAL) {                                                                      \
+            t_min = fr.lo[A] > t_min ? fr.lo[A] : t_min;                                              \
+            t_max = fr.hi[A] < t_max ? fr.hi[A] : t_max;                                              \
+            if (t_max <= t_min) return false;                                                         \
+        } else {                                                                                      \
+            t_min = rt_vmax(fr.lo[A], t_min);                                                         \
+            t_max = rt_vmin(fr.hi[A], t_max);                                                         \
+            if (EARLY) { if (t_max <= t_min) return false; }                                          \
+            else open = open & !(t_max <= t_min);                                                     \
+        }                                                                                             \
+    }
+    RT_SLAB(0, o.x, inv.x)
+    RT_SLAB(1, o.y, inv.y)
+    RT_SLAB(2, o.z, inv.z)
+#undef RT_SLAB
+    return open;
+}
+
 /* The same sweep for a scene whose node kinds and subtree ends are known at compile time (Topo::kind[], Topo::skip[]):
  * the loop over n is unrolled into straight-line code that follows the tree -- a subtree's code is guarded by "some
  * lane of the wave is at its root", node kinds need no dispatch, the node record of step I is fetched at a constant
  * offset, and a wrapper's subtree simply runs with the inner ray while the outer one stays live.  Every lane still
- * visits exactly the nodes of the reference's walk, in its order, with the same arithmetic. */
-template <class Topo, class Cfg, bool MEDIA, uint32_t I, uint32_t END, class NS>
+ * visits exactly the nodes of the reference's walk, in its order, with the same arithmetic.
+ * No lane keeps a node index here: "the lane is at node J" is "the lane passed the box test of every BVH node above J", and after a
+ * subtree every lane that entered it stands at its end -- so `act` goes down the recursion, a BVH node's children get `act && hit`,
+ * and what follows the subtree gets `act` again.  `up` is the chain of slab frames of the BVH nodes above I in this ray space. */
+template <class Topo, class Cfg, bool MEDIA, uint32_t I, uint32_t END, class Up, class NS>
 RT_HD void rt_sweep_static(const RtSceneView& sc, const NS& ns, const RtRayOD& ray, const RtV3& inv, double time, double t_min,
-                           bool tmin_nan, RtRng& rng, uint32_t& cur, double& best_t, uint32_t& best_prim) {
+                           bool tmin_nan, RtRng& rng, const bool act, const Up& up, double& best_t, uint32_t& best_prim) {
     if constexpr (I < END) {
         constexpr uint32_t kind = Topo::kind[I] & RT_KIND_MASK;
         constexpr uint32_t skip = Topo::skip[I];
         if constexpr (kind <= RT_BVH1) {
-            if (RT_WAVE_ANY(cur == I)) {
+            if (RT_WAVE_ANY(act)) {
                 const RtNodeHot nd = ns.hot(I);
-                if (cur == I) {
-                    bool hit;
-                    if (RT_WAVE_ANY(tmin_nan || rt_isnan(best_t))) hit = rt_aabb_hit(nd.d, ray.o, inv, t_min, best_t);
-                    else hit = rt_aabb_hit_fast<Cfg::media>(nd.d, ray.o, inv, t_min, best_t);
-                    cur = hit ? I + 1u : skip;
+                RtSlabFrame<I, Up> fr(up);
+                bool hit = false;
+                if (act) {
+                    if (RT_WAVE_ANY(tmin_nan || rt_isnan(best_t))) { RT_STAT_SLAB(1); hit = rt_aabb_hit_chain<Topo, I, true, false>(nd.d, ray.o, inv, t_min, best_t, fr); }
+                    else { RT_STAT_SLAB(0); hit = rt_aabb_hit_chain<Topo, I, false, Cfg::media>(nd.d, ray.o, inv, t_min, best_t, fr); }
                 }
-                rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, cur, best_t, best_prim);
+                rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, act && hit, fr, best_t, best_prim);
             }
-            rt_sweep_static<Topo, Cfg, MEDIA, skip, END>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, cur, best_t, best_prim);
+            rt_sweep_static<Topo, Cfg, MEDIA, skip, END>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, act, up, best_t, best_prim);
         } else if constexpr (kind <= RT_YZ) {
-            if (RT_WAVE_ANY(cur == I)) {
+            if (RT_WAVE_ANY(act)) {
                 const RtNodeHot nd = ns.hot(I);
-                if (cur == I) {
+                if (act) {
                     double t;
                     bool hit;
                     if constexpr (Cfg::msphere && kind == RT_MSPHERE) hit = rt_prim_t<Cfg>(sc.nodes[I], kind, ray.o, ray.d, time, t_min, best_t, t);
                     else hit = rt_prim_hot_t(nd, kind, ray.o, ray.d, t_min, best_t, t);
                     if (hit) { best_t = t; best_prim = I; }
-                    cur = I + 1u;
                 }
             }
-            rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, END>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, cur, best_t, best_prim);
+            rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, END>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, act, up, best_t, best_prim);
         } else if constexpr (kind <= RT_FLIP) {
-            if (RT_WAVE_ANY(cur == I)) {
-                const RtNodeHot nd = ns.hot(I);
-                cur = (cur == I) ? I + 1u : cur;
+            if (RT_WAVE_ANY(act)) {
                 if constexpr (kind == RT_FLIP) {
-                    rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, cur, best_t, best_prim);
+                    rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, act, up, best_t, best_prim);
                 } else {
-                    /* Translate::hit hittable.rs:207-211 / RotateY::hit :238-251 */
+                    /* Translate::hit hittable.rs:207-211 / RotateY::hit :238-251: another ray space, the chain starts empty */
+                    const RtNodeHot nd = ns.hot(I);
                     const RtRayOD inner = rt_scope_in(nd, ray);
+                    const RtSlabNone none;
                     if constexpr (kind == RT_ROTATE_Y) {
                         const RtV3 inv_inner = rt_inv3(inner.d);
-                        rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, inner, inv_inner, time, t_min, tmin_nan, rng, cur, best_t, best_prim);
+                        rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, inner, inv_inner, time, t_min, tmin_nan, rng, act, none, best_t, best_prim);
                     } else {
-                        rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, inner, inv, time, t_min, tmin_nan, rng, cur, best_t, best_prim);
+                        rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, inner, inv, time, t_min, tmin_nan, rng, act, none, best_t, best_prim);
                     }
                 }
             }
-            rt_sweep_static<Topo, Cfg, MEDIA, skip, END>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, cur, best_t, best_prim);
+            rt_sweep_static<Topo, Cfg, MEDIA, skip, END>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, act, up, best_t, best_prim);
         } else {
-            if (RT_WAVE_ANY(cur == I)) {
-                if (cur == I) {
+            if (RT_WAVE_ANY(act)) {
+                if (act) {
                     if constexpr (MEDIA && Cfg::media && kind == RT_MEDIUM) {
-                        /* ConstantMedium::hit constant_medium.rs:58-113: the boundary is a sweep of its own subtree */
+                        /* ConstantMedium::hit constant_medium.rs:58-113: the boundary is a sweep of its own subtree, from an empty chain */
                         const RtNode& full = sc.nodes[I];
                         double t1 = RT_INF, t2 = RT_INF, t;
-                        uint32_t c1 = I + 1u, p1 = RT_NONE, c2 = I + 1u, p2 = RT_NONE;
-                        rt_sweep_static<Topo, Cfg, false, I + 1u, skip>(sc, ns, ray, inv, time, -RT_INF, false, rng, c1, t1, p1);
+                        uint32_t p1 = RT_NONE, p2 = RT_NONE;
+                        const RtSlabNone none;
+                        rt_sweep_static<Topo, Cfg, false, I + 1u, skip>(sc, ns, ray, inv, time, -RT_INF, false, rng, true, none, t1, p1);
                         if (p1 != RT_NONE) {
                             const double lo = t1 + RT_R(0.0001);
-                            rt_sweep_static<Topo, Cfg, false, I + 1u, skip>(sc, ns, ray, inv, time, lo, rt_isnan(lo), rng, c2, t2, p2);
+                            rt_sweep_static<Topo, Cfg, false, I + 1u, skip>(sc, ns, ray, inv, time, lo, rt_isnan(lo), rng, true, none, t2, p2);
                             if (p2 != RT_NONE && rt_medium_t(full, ray.d, t1, t2, t_min, best_t, rng, t)) { best_t = t; best_prim = I; }
                         }
                     }
-                    cur = skip;
                 }
             }
-            rt_sweep_static<Topo, Cfg, MEDIA, skip, END>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, cur, best_t, best_prim);
+            rt_sweep_static<Topo, Cfg, MEDIA, skip, END>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, act, up, best_t, best_prim);
         }
     }
 }
@@ -966,9 +1034,9 @@ RT_HD bool rt_closest_hit(const RtSceneView& sc, const NS& ns, const RtRay& ray,
         typedef typename Cfg::Topo Topo;
         RtRayOD w; w.o = ray.o; w.d = ray.d;
         const RtV3 inv = rt_inv3(w.d);
-        uint32_t cur = Topo::root;
+        const RtSlabNone none;
         t = t_max; prim = RT_NONE;
-        rt_sweep_static<Topo, Cfg, true, Topo::root, Topo::skip[Topo::root]>(sc, ns, w, inv, ray.time, t_min, rt_isnan(t_min), rng, cur, t, prim);
+        rt_sweep_static<Topo, Cfg, true, Topo::root, Topo::skip[Topo::root]>(sc, ns, w, inv, ray.time, t_min, rt_isnan(t_min), rng, true, none, t, prim);
         scope = prim == RT_NONE ? RT_NONE : ns.hot(prim).b; /* leaves keep their innermost wrapper in `b` */
         return prim != RT_NONE;
     } else if constexpr (Cfg::sweep) return rt_traverse_sweep<Cfg, true>(sc, ns, sc.root, ray, t_min, t_max, rng, t, prim, scope);
