@@ -5,15 +5,10 @@
  * A unit of its own, inside its own namespace (the pattern of denoise_var.hip), so that no other code object moves with it: the kernels
  * of rt1w_denoise_var stay the build they were.  The host half is in features.hip, which calls the launcher below.
  *
- * Work mapping: that of denoise_var.hip -- one lane per pixel, an 8 x 8 pixel block per wave, 2 x 2 blocks (16 x 16 pixels) per workgroup
- * of 256 lanes, every output pixel computed whole by one lane in the fixed order of rt_denoise_halves.h: no atomics, the same bits as the
- * CPU twin (denoise_host.cpp).  The colour record is 88 bytes (RtDvCol's five doubles, then the two demodulated halves), the guide record
- * denoise.hip's 64.
- *
- * Two forms of the level kernel, as there.  Staged: the workgroup copies its tile plus the 2-step halo, (16 + 4 step)^2 pixels x 16
- * doubles as struct-of-arrays (step 1: 51 200 B, step 2: 73 728 B of LDS; 160 KiB per CU hold 3 / 2 such workgroups), then every tap is
- * an LDS read.  Direct (any step): the taps are read from memory through L2.  RT_DH_STAGED_LEVELS is how many leading levels run staged
- * (0 .. 2; DESIGN.md section 17 has the measurement behind the default). */
+ * The kernels are the skeleton of rt_atrous_kernels.h over RtDhFilter: an 88-byte colour record (RtDvCol's five doubles, then the two
+ * demodulated halves), so 16 planes in the staged tile -- the record's eleven in its field order, then the guide's five (step 1:
+ * 51 200 B, step 2: 73 728 B of LDS; 160 KiB per CU hold 3 / 2 such workgroups).  RT_DH_STAGED_LEVELS is how many leading levels run
+ * staged (0 .. 2; DESIGN.md section 17 has the measurement behind the default). */
 #include <hip/hip_runtime.h>
 #include "rt_feature_launch.h" /* this unit's functions as features.hip calls them: the definitions below are held to it */
 #include <stdint.h>
@@ -26,96 +21,20 @@
 namespace rtdh {
 #include "rt1w_num.h"
 #include "rt_denoise_halves.h"
+#include "rt_atrous_kernels.h"
 
-#define RT_DH_BLOCK 256
-#define RT_DH_TILE 16u
-#define RT_DH_PLANES 16
-
-/* pixel of this lane: 8 x 8 block per wave, 2 x 2 waves per workgroup, workgroups in row order over the image */
-__device__ __forceinline__ void rt_dh_lane_pixel(uint32_t w, uint32_t& tx, uint32_t& ty, uint32_t& x, uint32_t& y) {
-    const uint32_t tiles_x = (w + RT_DH_TILE - 1u) / RT_DH_TILE;
-    tx = blockIdx.x % tiles_x; ty = blockIdx.x / tiles_x;
-    const uint32_t wv = threadIdx.x >> 6, in = threadIdx.x & 63u;
-    x = tx * RT_DH_TILE + (wv & 1u) * 8u + (in & 7u);
-    y = ty * RT_DH_TILE + (wv >> 1) * 8u + (in >> 3);
-}
-
-__global__ __launch_bounds__(RT_DH_BLOCK) void rt_dh_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
+__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dh_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
                                                                      const double* __restrict__ var, const double* __restrict__ half_a,
                                                                      const double* __restrict__ half_b, RtDhCol* __restrict__ col,
                                                                      RtDnGuide* __restrict__ guide) {
-    uint32_t tx, ty, x, y;
-    rt_dh_lane_pixel(P.w, tx, ty, x, y);
-    if (x >= P.w || y >= P.h) return;
-    const unsigned long long i = (unsigned long long)y * P.w + x;
-    RtDhCol c;
-    RtDnGuide g;
-    rt_dh_prepare_pixel(P, frame + i * 3u, aov + i * 8u, var[i], half_a + i * 3u, half_b + i * 3u, c, g);
-    col[i] = c;
-    guide[i] = g;
+    rt_at_prepare<RtDhFilter>(P, col, guide, frame, aov, var, half_a, half_b);
 }
-
-/* the staged tile: 16 planes of T x T doubles -- colour record 0 .. 4, guide 5 .. 9, halves 10 .. 15 -- origin (ox, oy) in the image; only
- * pixels inside the image are filled and only those are read */
-template <int T>
-struct RtDhLdsSrc {
-    const double* t;
-    long long ox, oy;
-    __device__ __forceinline__ int at(uint32_t x, uint32_t y) const { return (int)((long long)y - oy) * T + (int)((long long)x - ox); }
-    __device__ __forceinline__ RtDhCol col(uint32_t x, uint32_t y) const {
-        const int i = at(x, y);
-        RtDhCol c;
-        c.r = t[i]; c.g = t[T * T + i]; c.b = t[2 * T * T + i]; c.l = t[3 * T * T + i]; c.v = t[4 * T * T + i];
-        c.ar = t[10 * T * T + i]; c.ag = t[11 * T * T + i]; c.ab = t[12 * T * T + i];
-        c.br = t[13 * T * T + i]; c.bg = t[14 * T * T + i]; c.bb = t[15 * T * T + i];
-        return c;
-    }
-    __device__ __forceinline__ void guide(uint32_t x, uint32_t y, double o[5]) const {
-        const int i = at(x, y);
-        for (int k = 0; k < 5; ++k) o[k] = t[(5 + k) * T * T + i];
-    }
-};
-
-/* STEP 0: direct form, any level.  STEP 1, 2: staged form of the level whose step it is.  out != nullptr: the last level */
 template <int STEP>
-__global__ __launch_bounds__(RT_DH_BLOCK) void rt_dh_level_kernel(RtDnParams P, double sv2, uint32_t level, const RtDhCol* __restrict__ src,
+__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dh_level_kernel(RtDnParams P, double sv2, uint32_t level, const RtDhCol* __restrict__ src,
                                                                    const RtDnGuide* __restrict__ guide, RtDhCol* __restrict__ dst, double* __restrict__ out,
                                                                    double* __restrict__ err_px) {
-    uint32_t tx, ty, x, y;
-    rt_dh_lane_pixel(P.w, tx, ty, x, y);
-    const bool inside = x < P.w && y < P.h;
-    RtDhCol c;
-    if constexpr (STEP > 0) {
-        constexpr int T = (int)RT_DH_TILE + 4 * STEP;
-        __shared__ double tile[RT_DH_PLANES * T * T];
-        const long long ox = (long long)tx * RT_DH_TILE - 2 * STEP, oy = (long long)ty * RT_DH_TILE - 2 * STEP;
-        for (int i = (int)threadIdx.x; i < T * T; i += RT_DH_BLOCK) {
-            const long long gx = ox + i % T, gy = oy + i / T;
-            if (gx < 0 || gy < 0 || gx >= (long long)P.w || gy >= (long long)P.h) continue;
-            const unsigned long long q = (unsigned long long)gy * P.w + (unsigned long long)gx;
-            const RtDhCol cq = src[q];
-            const RtDnGuide* gq = guide + q;
-            tile[i] = cq.r; tile[T * T + i] = cq.g; tile[2 * T * T + i] = cq.b; tile[3 * T * T + i] = cq.l; tile[4 * T * T + i] = cq.v;
-            tile[5 * T * T + i] = gq->nx; tile[6 * T * T + i] = gq->ny; tile[7 * T * T + i] = gq->nz;
-            tile[8 * T * T + i] = gq->z; tile[9 * T * T + i] = gq->v;
-            tile[10 * T * T + i] = cq.ar; tile[11 * T * T + i] = cq.ag; tile[12 * T * T + i] = cq.ab;
-            tile[13 * T * T + i] = cq.br; tile[14 * T * T + i] = cq.bg; tile[15 * T * T + i] = cq.bb;
-        }
-        __syncthreads();
-        if (!inside) return;
-        const RtDhLdsSrc<T> s{tile, ox, oy};
-        c = rt_dh_level_pixel(P, sv2, s, x, y, level);
-    } else {
-        if (!inside) return;
-        const RtDhGlobalSrc s{src, guide, P.w};
-        c = rt_dh_level_pixel(P, sv2, s, x, y, level);
-    }
-    const unsigned long long i = (unsigned long long)y * P.w + x;
-    if (out) rt_dh_finish_pixel(c, guide[i], out + i * 3u, err_px + i);
-    else dst[i] = c;
+    rt_at_level<RtDhFilter, STEP>(P, sv2, level, src, guide, dst, out, err_px);
 }
-
-__host__ unsigned rt_dh_grid(uint32_t w, uint32_t h) { return ((w + RT_DH_TILE - 1u) / RT_DH_TILE) * ((h + RT_DH_TILE - 1u) / RT_DH_TILE); }
 } // namespace rtdh
 
 /* called by features.hip.  Enqueues the prepare pass and the levels on `stream`, one after another: frame + aov + var + half_a + half_b
@@ -131,19 +50,13 @@ extern "C" int rt1w_internal_denoise_var_halves_launch(uint32_t w, uint32_t h, u
     double sv;
     if (!rt_dn_make_params(w, h, iterations, flags, 0.0, sigma_normal, sigma_depth, P) || !rt_dv_sigma(sigma_variance, sv)) return -2;
     const double sv2 = sv * sv;
-    const unsigned grid = rt_dh_grid(P.w, P.h);
-    launch[0] = grid; launch[1] = RT_DH_BLOCK;
-    RtDhCol* src = (RtDhCol*)col_a;
-    RtDhCol* dst = (RtDhCol*)col_b;
-    const RtDnGuide* g = (const RtDnGuide*)guide;
-    hipLaunchKernelGGL(rt_dh_prepare_kernel, dim3(grid), dim3(RT_DH_BLOCK), 0, stream, P, frame, aov, var, half_a, half_b, src, (RtDnGuide*)guide);
-    for (uint32_t level = 0; level < P.levels; ++level) {
-        double* o = level + 1u == P.levels ? out : nullptr;
-        if (level == 0u && RT_DH_STAGED_LEVELS >= 1) hipLaunchKernelGGL(rt_dh_level_kernel<1>, dim3(grid), dim3(RT_DH_BLOCK), 0, stream, P, sv2, level, src, g, dst, o, err_px);
-        else if (level == 1u && RT_DH_STAGED_LEVELS >= 2) hipLaunchKernelGGL(rt_dh_level_kernel<2>, dim3(grid), dim3(RT_DH_BLOCK), 0, stream, P, sv2, level, src, g, dst, o, err_px);
-        else hipLaunchKernelGGL(rt_dh_level_kernel<0>, dim3(grid), dim3(RT_DH_BLOCK), 0, stream, P, sv2, level, src, g, dst, o, err_px);
-        RtDhCol* t = src; src = dst; dst = t;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    RtDnGuide* g = (RtDnGuide*)guide;
+    return rt_at_enqueue<RtDhCol>(
+        P, (1u << RT_DH_STAGED_LEVELS) - 1u, col_a, col_b, launch, /* the leading RT_DH_STAGED_LEVELS levels staged */
+        [&](dim3 grid, dim3 block, RtDhCol* col) { hipLaunchKernelGGL(rt_dh_prepare_kernel, grid, block, 0, stream, P, frame, aov, var, half_a, half_b, col, g); },
+        [&](int step, dim3 grid, dim3 block, uint32_t level, const RtDhCol* src, RtDhCol* dst, bool last) {
+            hipLaunchKernelGGL(step == 1 ? rt_dh_level_kernel<1> : (step == 2 ? rt_dh_level_kernel<2> : rt_dh_level_kernel<0>), grid, block, 0, stream, P,
+                               sv2, level, src, (const RtDnGuide*)g, dst, last ? out : nullptr, err_px);
+        });
 }
 extern "C" unsigned rt1w_internal_denoise_var_halves_sizeof(void) { return (unsigned)sizeof(rtdh::RtDhCol); }

@@ -25,36 +25,48 @@ void for_rows(uint32_t h, F f) {
     for (uint32_t y = 0; y < h; y += n_threads) f(y);
     for (auto& th : pool) th.join();
 }
+/* the twin of an a-trous filter F (the policies at the end of rt_denoise*.h; the kernels' skeleton over them is rt_atrous_kernels.h):
+ * prepare every pixel from the buffers `in`, run the levels with ping-pong, finish on the last, where hook(i, c, g) sees pixel i's
+ * record and guide as well.  sv2, err_px: as F takes them */
+template <class F, class Hook, class... In>
+void atrous_host(const RtDnParams& P, double sv2, double* out, double* err_px, Hook hook, In... in) {
+    typedef typename F::Col Col;
+    const size_t n = (size_t)P.w * P.h;
+    std::vector<Col> a(n), b(n);
+    std::vector<RtDnGuide> g(n);
+    for_rows(P.h, [&](uint32_t y) {
+        for (uint32_t x = 0; x < P.w; ++x) {
+            const size_t i = (size_t)y * P.w + x;
+            F::prepare(P, i, a[i], g[i], in...);
+        }
+    });
+    Col* src = a.data();
+    Col* dst = b.data();
+    for (uint32_t level = 0; level < P.levels; ++level) {
+        const RtDnGlobalSrc<Col> s{src, g.data(), P.w};
+        const bool last = level + 1u == P.levels;
+        for_rows(P.h, [&](uint32_t y) {
+            for (uint32_t x = 0; x < P.w; ++x) {
+                const size_t i = (size_t)y * P.w + x;
+                const Col c = F::level(P, sv2, s, x, y, level);
+                if (last) {
+                    F::finish(c, g[i], i, out, err_px);
+                    hook(i, c, g[i]);
+                } else
+                    dst[i] = c;
+            }
+        });
+        Col* t = src; src = dst; dst = t;
+    }
+}
+const auto no_hook = [](size_t, const auto&, const RtDnGuide&) {};
 } // namespace
 
 extern "C" int rt1w_lab_denoise_host(const rt1w_denoise_params* p, const double* frame, const double* aov, double* out) {
     if (!p || !frame || !aov || !out) return RT1W_ERR_INVALID;
     RtDnParams P;
     if (!rt_dn_make_params(p->width, p->height, p->iterations, p->flags, p->sigma_colour, p->sigma_normal, p->sigma_depth, P)) return RT1W_ERR_INVALID;
-    const size_t n = (size_t)P.w * P.h;
-    std::vector<RtDnCol> a(n), b(n);
-    std::vector<RtDnGuide> g(n);
-    for_rows(P.h, [&](uint32_t y) {
-        for (uint32_t x = 0; x < P.w; ++x) {
-            const size_t i = (size_t)y * P.w + x;
-            rt_dn_prepare_pixel(P, frame + i * 3, aov + i * 8, a[i], g[i]);
-        }
-    });
-    RtDnCol* src = a.data();
-    RtDnCol* dst = b.data();
-    for (uint32_t level = 0; level < P.levels; ++level) {
-        const RtDnGlobalSrc s{src, g.data(), P.w};
-        const bool last = level + 1u == P.levels;
-        for_rows(P.h, [&](uint32_t y) {
-            for (uint32_t x = 0; x < P.w; ++x) {
-                const size_t i = (size_t)y * P.w + x;
-                const RtDnCol c = rt_dn_level_pixel(P, s, x, y, level);
-                if (last) rt_dn_finish_pixel(c, g[i], out + i * 3);
-                else dst[i] = c;
-            }
-        });
-        RtDnCol* t = src; src = dst; dst = t;
-    }
+    atrous_host<RtDnFilter>(P, 0.0, out, nullptr, no_hook, frame, aov);
     return RT1W_OK;
 }
 
@@ -79,31 +91,7 @@ extern "C" int rt1w_lab_denoise_var_host(const rt1w_denoise_params* p, const dou
     RtDnParams P;
     double sv;
     if (!rt_dn_make_params(p->width, p->height, p->iterations, p->flags, 0.0, p->sigma_normal, p->sigma_depth, P) || !rt_dv_sigma(sigma_variance, sv)) return RT1W_ERR_INVALID;
-    const double sv2 = sv * sv;
-    const size_t n = (size_t)P.w * P.h;
-    std::vector<RtDvCol> a(n), b(n);
-    std::vector<RtDnGuide> g(n);
-    for_rows(P.h, [&](uint32_t y) {
-        for (uint32_t x = 0; x < P.w; ++x) {
-            const size_t i = (size_t)y * P.w + x;
-            rt_dv_prepare_pixel(P, frame + i * 3, aov + i * 8, var[i], a[i], g[i]);
-        }
-    });
-    RtDvCol* src = a.data();
-    RtDvCol* dst = b.data();
-    for (uint32_t level = 0; level < P.levels; ++level) {
-        const RtDvGlobalSrc s{src, g.data(), P.w};
-        const bool last = level + 1u == P.levels;
-        for_rows(P.h, [&](uint32_t y) {
-            for (uint32_t x = 0; x < P.w; ++x) {
-                const size_t i = (size_t)y * P.w + x;
-                const RtDvCol c = rt_dv_level_pixel(P, sv2, s, x, y, level);
-                if (last) rt_dv_finish_pixel(c, g[i], out + i * 3);
-                else dst[i] = c;
-            }
-        });
-        RtDvCol* t = src; src = dst; dst = t;
-    }
+    atrous_host<RtDvFilter>(P, sv * sv, out, nullptr, no_hook, frame, aov, var);
     return RT1W_OK;
 }
 
@@ -114,36 +102,11 @@ extern "C" int rt1w_lab_denoise_var_halves_host(const rt1w_denoise_params* p, co
     RtDnParams P;
     double sv;
     if (!rt_dn_make_params(p->width, p->height, p->iterations, p->flags, 0.0, p->sigma_normal, p->sigma_depth, P) || !rt_dv_sigma(sigma_variance, sv)) return RT1W_ERR_INVALID;
-    const double sv2 = sv * sv;
-    const size_t n = (size_t)P.w * P.h;
-    std::vector<RtDhCol> a(n), b(n);
-    std::vector<RtDnGuide> g(n);
-    for_rows(P.h, [&](uint32_t y) {
-        for (uint32_t x = 0; x < P.w; ++x) {
-            const size_t i = (size_t)y * P.w + x;
-            rt_dh_prepare_pixel(P, frame + i * 3, aov + i * 8, var[i], half_a + i * 3, half_b + i * 3, a[i], g[i]);
-        }
-    });
-    RtDhCol* src = a.data();
-    RtDhCol* dst = b.data();
-    for (uint32_t level = 0; level < P.levels; ++level) {
-        const RtDhGlobalSrc s{src, g.data(), P.w};
-        const bool last = level + 1u == P.levels;
-        for_rows(P.h, [&](uint32_t y) {
-            for (uint32_t x = 0; x < P.w; ++x) {
-                const size_t i = (size_t)y * P.w + x;
-                const RtDhCol c = rt_dh_level_pixel(P, sv2, s, x, y, level);
-                if (last) {
-                    rt_dh_finish_pixel(c, g[i], out + i * 3, err_px + i);
-                    /* for the tests: the two filtered halves with the albedo back, the products rt_dh_finish_pixel takes the luminances of */
-                    if (filtered_a) { filtered_a[i * 3] = c.ar * g[i].ar; filtered_a[i * 3 + 1] = c.ag * g[i].ag; filtered_a[i * 3 + 2] = c.ab * g[i].ab; }
-                    if (filtered_b) { filtered_b[i * 3] = c.br * g[i].ar; filtered_b[i * 3 + 1] = c.bg * g[i].ag; filtered_b[i * 3 + 2] = c.bb * g[i].ab; }
-                } else
-                    dst[i] = c;
-            }
-        });
-        RtDhCol* t = src; src = dst; dst = t;
-    }
+    /* for the tests: the two filtered halves with the albedo back, the products rt_dh_finish_pixel takes the luminances of */
+    atrous_host<RtDhFilter>(P, sv * sv, out, err_px, [&](size_t i, const RtDhCol& c, const RtDnGuide& g) {
+        if (filtered_a) { filtered_a[i * 3] = c.ar * g.ar; filtered_a[i * 3 + 1] = c.ag * g.ag; filtered_a[i * 3 + 2] = c.ab * g.ab; }
+        if (filtered_b) { filtered_b[i * 3] = c.br * g.ar; filtered_b[i * 3 + 1] = c.bg * g.ag; filtered_b[i * 3 + 2] = c.bb * g.ab; }
+    }, frame, aov, var, half_a, half_b);
     return RT1W_OK;
 }
 
@@ -154,34 +117,9 @@ extern "C" int rt1w_lab_denoise_cross_host(const rt1w_denoise_params* p, const d
     double sv;
     /* sigma_colour is not used by this filter, but the entries refuse a bad one (denoise_validate): so does the twin */
     if (!rt_dn_make_params(p->width, p->height, p->iterations, p->flags, p->sigma_colour, p->sigma_normal, p->sigma_depth, P) || !rt_dv_sigma(sigma_variance, sv)) return RT1W_ERR_INVALID;
-    const double sv2 = sv * sv;
-    const size_t n = (size_t)P.w * P.h;
-    std::vector<RtDcCol> a(n), b(n);
-    std::vector<RtDnGuide> g(n);
-    for_rows(P.h, [&](uint32_t y) {
-        for (uint32_t x = 0; x < P.w; ++x) {
-            const size_t i = (size_t)y * P.w + x;
-            rt_dc_prepare_pixel(P, frame + i * 3, aov + i * 8, var[i], half_a + i * 3, half_b + i * 3, a[i], g[i]);
-        }
-    });
-    RtDcCol* src = a.data();
-    RtDcCol* dst = b.data();
-    for (uint32_t level = 0; level < P.levels; ++level) {
-        const RtDcGlobalSrc s{src, g.data(), P.w};
-        const bool last = level + 1u == P.levels;
-        for_rows(P.h, [&](uint32_t y) {
-            for (uint32_t x = 0; x < P.w; ++x) {
-                const size_t i = (size_t)y * P.w + x;
-                const RtDcCol c = rt_dc_level_pixel(P, sv2, s, x, y, level);
-                if (last) {
-                    rt_dc_finish_pixel(c, g[i], out + i * 3, err_px + i);
-                    if (rec) memcpy(rec + i * 10, &c, sizeof c);
-                } else
-                    dst[i] = c;
-            }
-        });
-        RtDcCol* t = src; src = dst; dst = t;
-    }
+    atrous_host<RtDcFilter>(P, sv * sv, out, err_px, [&](size_t i, const RtDcCol& c, const RtDnGuide&) {
+        if (rec) memcpy(rec + i * 10, &c, sizeof c);
+    }, frame, aov, var, half_a, half_b);
     return RT1W_OK;
 }
 

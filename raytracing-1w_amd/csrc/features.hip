@@ -547,28 +547,23 @@ int halves_resolve_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batc
         return rt1w_internal_halves_resolve_launch(w, h, batch_spp, d_acc_a, d_acc_b, d_frame, d_var, d_half_a, d_half_b, d_spp, stream, launch);
     });
 }
-int denoise_var_halves_common(rt1w_context* c, const rt1w_denoise_params* p, double sigma_variance, const double* d_frame, const double* d_aov,
-                              const double* d_var, const double* d_half_a, const double* d_half_b, double* d_out, double* d_err_px, rt1w_stats* stats) {
-    const int rc = denoise_reserve(c, (size_t)p->width * p->height, rt1w_internal_denoise_var_halves_sizeof());
+/* the filter of a frame's two halves: the launcher of its unit and the bytes per pixel of one of that unit's colour buffers */
+struct HalvesFilter {
+    decltype(&rt1w_internal_denoise_var_halves_launch) launch;
+    unsigned (*col_sizeof)(void);
+};
+const HalvesFilter halves_filter = {rt1w_internal_denoise_var_halves_launch, rt1w_internal_denoise_var_halves_sizeof};
+const HalvesFilter cross_filter = {rt1w_internal_denoise_cross_launch, rt1w_internal_denoise_cross_sizeof};
+int denoise_halves_common(rt1w_context* c, const HalvesFilter& f, const rt1w_denoise_params* p, double sigma_variance, const double* d_frame,
+                          const double* d_aov, const double* d_var, const double* d_half_a, const double* d_half_b, double* d_out, double* d_err_px,
+                          rt1w_stats* stats) {
+    const int rc = denoise_reserve(c, (size_t)p->width * p->height, f.col_sizeof());
     if (rc < 0) return rc;
     return lane_run(c, (uint64_t)p->width * p->height, "denoise", stats, [&](hipStream_t stream, unsigned* launch) {
-        return rt1w_internal_denoise_var_halves_launch(p->width, p->height, p->iterations, p->flags, p->sigma_normal, p->sigma_depth, sigma_variance, d_frame,
-                                                       d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], stream, launch);
+        return f.launch(p->width, p->height, p->iterations, p->flags, p->sigma_normal, p->sigma_depth, sigma_variance, d_frame, d_aov, d_var, d_half_a,
+                        d_half_b, d_out, d_err_px, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], stream, launch);
     });
 }
-/* the same for rt1w_denoise_cross: two colour buffers of 80 B per pixel */
-int denoise_cross_common(rt1w_context* c, const rt1w_denoise_params* p, double sigma_variance, const double* d_frame, const double* d_aov,
-                         const double* d_var, const double* d_half_a, const double* d_half_b, double* d_out, double* d_err_px, rt1w_stats* stats) {
-    const int rc = denoise_reserve(c, (size_t)p->width * p->height, rt1w_internal_denoise_cross_sizeof());
-    if (rc < 0) return rc;
-    return lane_run(c, (uint64_t)p->width * p->height, "denoise", stats, [&](hipStream_t stream, unsigned* launch) {
-        return rt1w_internal_denoise_cross_launch(p->width, p->height, p->iterations, p->flags, p->sigma_normal, p->sigma_depth, sigma_variance, d_frame,
-                                                  d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], stream, launch);
-    });
-}
-/* the filter of a frame's two halves: denoise_var_halves_common or denoise_cross_common */
-typedef int (*HalvesFilter)(rt1w_context*, const rt1w_denoise_params*, double, const double*, const double*, const double*, const double*, const double*, double*,
-                            double*, rt1w_stats*);
 int tile_error_map_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const double* d_err_px, double* d_err, rt1w_stats* stats) {
     return lane_run(c, (uint64_t)w * h, "tile error", stats, [&](hipStream_t stream, unsigned* launch) {
         return rt1w_internal_tile_error_map_launch(w, h, tile, d_err_px, d_err, stream, launch);
@@ -596,7 +591,7 @@ int halves_resolve(rt1w_context* c, uint32_t w, uint32_t h, uint32_t batch_spp, 
 /* the two rt1w_denoise_var_halves entries and the two rt1w_denoise_cross entries, by `filter`: as denoise_var(), with the two halves behind
  * the variance and the error map behind the frame */
 int denoise_var_halves(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
-                       const double* half_b, double sigma_variance, double* out, double* err_px, HalvesFilter filter, bool host, rt1w_stats* stats) {
+                       const double* half_b, double sigma_variance, double* out, double* err_px, const HalvesFilter& filter, bool host, rt1w_stats* stats) {
     int rc = denoise_validate(c, p);
     if (rc < 0) return rc;
     if ((rc = sigma_variance_validate(sigma_variance)) < 0) return rc;
@@ -609,7 +604,7 @@ int denoise_var_halves(rt1w_context* c, const rt1w_denoise_params* p, const doub
                   {half_b, nullptr, npix * 3, FRAMEBUFFER, "denoise: half copy", nullptr},
                   {aov, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, "denoise: feature buffer copy", nullptr}};
     return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
-        return filter(c, p, sigma_variance, s[0].d_in, s[5].d_in, s[2].d_in, s[3].d_in, s[4].d_in, s[0].d_out, s[1].d_out, st);
+        return denoise_halves_common(c, filter, p, sigma_variance, s[0].d_in, s[5].d_in, s[2].d_in, s[3].d_in, s[4].d_in, s[0].d_out, s[1].d_out, st);
     });
 }
 int tile_error_map(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const double* err_px, double* err, bool host, rt1w_stats* stats) {
@@ -715,7 +710,7 @@ int guides_resolve(rt1w_context* c, uint32_t w, uint32_t h, const double* gacc, 
  * behind the round's in the batch buffer), and the filter is guided by its resolve (a second feature buffer, last in the framebuffer);
  * the pilot's feature buffers go on demodulating the merges */
 int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d, double sigma_variance,
-                             double* out_rgb, double* out_spp, double* out_err, HalvesFilter filter, bool guided, const char* name, rt1w_stats* stats) {
+                             double* out_rgb, double* out_spp, double* out_err, const HalvesFilter& filter, bool guided, const char* name, rt1w_stats* stats) {
     int rc = sigma_variance_validate(sigma_variance);
     if (rc < 0) return rc;
     RtAdPlan plan, pair;
@@ -803,7 +798,7 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
                 if ((r = guides_resolve_common(c, W, H, d_gacc, d_guides, &sk)) < 0) return r;
                 other_ms += sk.kernel_ms;
             }
-            if ((r = filter(c, &dp, sigma_variance, d_frame, d_guides, d_var, d_half_a, d_half_b, d_frame, d_err_px, &sk)) < 0) return r;
+            if ((r = denoise_halves_common(c, filter, &dp, sigma_variance, d_frame, d_guides, d_var, d_half_a, d_half_b, d_frame, d_err_px, &sk)) < 0) return r;
             other_ms += sk.kernel_ms;
             const rt1w_stats sf = sk; /* the level kernel's grid and block are the ones reported */
             if ((r = tile_error_map_common(c, W, H, plan.tile, d_err_px, d_err, &sk)) < 0) return r;
@@ -1080,12 +1075,12 @@ int rt1w_halves_resolve_device(rt1w_context* c, uint32_t width, uint32_t height,
 }
 int rt1w_denoise_var_halves(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
                             const double* half_b, double sigma_variance, double* out, double* err_px, rt1w_stats* stats) {
-    return denoise_var_halves(c, p, frame, aov, var, half_a, half_b, sigma_variance, out, err_px, denoise_var_halves_common, true, stats);
+    return denoise_var_halves(c, p, frame, aov, var, half_a, half_b, sigma_variance, out, err_px, halves_filter, true, stats);
 }
 int rt1w_denoise_var_halves_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, const void* d_var,
                                    const void* d_half_a, const void* d_half_b, double sigma_variance, void* d_out, void* d_err_px, rt1w_stats* stats) {
     return denoise_var_halves(c, p, (const double*)d_frame, (const double*)d_aov, (const double*)d_var, (const double*)d_half_a, (const double*)d_half_b,
-                              sigma_variance, (double*)d_out, (double*)d_err_px, denoise_var_halves_common, false, stats);
+                              sigma_variance, (double*)d_out, (double*)d_err_px, halves_filter, false, stats);
 }
 int rt1w_tile_error_map(rt1w_context* c, uint32_t width, uint32_t height, uint32_t tile, const double* err_px, double* err, rt1w_stats* stats) {
     return tile_error_map(c, width, height, tile, err_px, err, true, stats);
@@ -1095,20 +1090,20 @@ int rt1w_tile_error_map_device(rt1w_context* c, uint32_t width, uint32_t height,
 }
 int rt1w_render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d,
                                   double sigma_variance, double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
-    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_var_halves_common, false, "rt1w_render_adaptive_filtered", stats);
+    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, halves_filter, false, "rt1w_render_adaptive_filtered", stats);
 }
 int rt1w_denoise_cross(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, const double* var, const double* half_a,
                        const double* half_b, double sigma_variance, double* out, double* err_px, rt1w_stats* stats) {
-    return denoise_var_halves(c, p, frame, aov, var, half_a, half_b, sigma_variance, out, err_px, denoise_cross_common, true, stats);
+    return denoise_var_halves(c, p, frame, aov, var, half_a, half_b, sigma_variance, out, err_px, cross_filter, true, stats);
 }
 int rt1w_denoise_cross_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, const void* d_var, const void* d_half_a,
                               const void* d_half_b, double sigma_variance, void* d_out, void* d_err_px, rt1w_stats* stats) {
     return denoise_var_halves(c, p, (const double*)d_frame, (const double*)d_aov, (const double*)d_var, (const double*)d_half_a, (const double*)d_half_b,
-                              sigma_variance, (double*)d_out, (double*)d_err_px, denoise_cross_common, false, stats);
+                              sigma_variance, (double*)d_out, (double*)d_err_px, cross_filter, false, stats);
 }
 int rt1w_render_adaptive_cross(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d,
                                double sigma_variance, double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
-    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_cross_common, false, "rt1w_render_adaptive_cross", stats);
+    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, cross_filter, false, "rt1w_render_adaptive_cross", stats);
 }
 int rt1w_render_aov_tiles(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out, rt1w_stats* stats) {
     return render_aov_tiles(c, p, tile, tiles, n_tiles, out, true, stats);
@@ -1133,6 +1128,6 @@ int rt1w_guides_resolve_device(rt1w_context* c, uint32_t width, uint32_t height,
 }
 int rt1w_render_adaptive_guided(rt1w_context* c, const rt1w_render_params* p, const rt1w_adaptive_params* a, const rt1w_denoise_params* d,
                                 double sigma_variance, double* out_rgb, double* out_spp, double* out_err, rt1w_stats* stats) {
-    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, denoise_var_halves_common, true, "rt1w_render_adaptive_guided", stats);
+    return render_adaptive_filtered(c, p, a, d, sigma_variance, out_rgb, out_spp, out_err, halves_filter, true, "rt1w_render_adaptive_guided", stats);
 }
 } /* extern "C" */

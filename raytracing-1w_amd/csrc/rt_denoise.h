@@ -115,12 +115,14 @@ RT_HD void rt_dn_prepare_pixel(const RtDnParams& P, const double* frame, const d
 /* the B3-spline tap weights h(dy, dx) = k1(|dy|) * k1(|dx|), k1 = 3/8, 1/4, 1/16: all products are exact */
 RT_HD double rt_dn_b3(int d) { return d == 0 ? 0.375 : ((d == 1 || d == -1) ? 0.25 : 0.0625); }
 
-/* images as the level reads them: plain arrays in memory (the twin, and the kernel's direct form) */
+/* images as a level reads them: plain arrays in memory (the twin, and the kernel's direct form), for the colour record of any of the
+ * four filters (this one, rt_denoise_var.h, rt_denoise_halves.h, rt_denoise_cross.h) */
+template <class Col>
 struct RtDnGlobalSrc {
-    const RtDnCol* c;
+    const Col* c;
     const RtDnGuide* g;
     uint32_t w;
-    RT_HD RtDnCol col(uint32_t x, uint32_t y) const { return c[(unsigned long long)y * w + x]; }
+    RT_HD Col col(uint32_t x, uint32_t y) const { return c[(unsigned long long)y * w + x]; }
     RT_HD void guide(uint32_t x, uint32_t y, double o[5]) const {
         const RtDnGuide* q = g + ((unsigned long long)y * w + x);
         o[0] = q->nx; o[1] = q->ny; o[2] = q->nz; o[3] = q->z; o[4] = q->v;
@@ -181,5 +183,19 @@ RT_HD RtDnCol rt_dn_level_pixel(const RtDnParams& P, const Src& src, uint32_t x,
 RT_HD void rt_dn_finish_pixel(const RtDnCol& c, const RtDnGuide& g, double* out) {
     out[0] = c.r * g.ar; out[1] = c.g * g.ag; out[2] = c.b * g.ab;
 }
+
+/* A filter as the two skeletons see it (the kernels' in rt_atrous_kernels.h, the twin's in denoise_host.cpp): Col, the record a level
+ * reads and writes, a whole number of doubles; prepare, pixel i of the caller's input buffers to its records; level, with Src a reader
+ * like RtDnGlobalSrc<Col> and sv2 the filter's extra argument (this filter has none); finish, the last level's record of pixel i to the
+ * caller's output buffers (err_px: only the filters that have one).  Every filter header ends in its own */
+struct RtDnFilter {
+    typedef RtDnCol Col;
+    static RT_HD void prepare(const RtDnParams& P, unsigned long long i, Col& c, RtDnGuide& g, const double* frame, const double* aov) {
+        rt_dn_prepare_pixel(P, frame + i * 3u, aov + i * 8u, c, g);
+    }
+    template <class Src>
+    static RT_HD Col level(const RtDnParams& P, double, const Src& src, uint32_t x, uint32_t y, uint32_t level) { return rt_dn_level_pixel(P, src, x, y, level); }
+    static RT_HD void finish(const Col& c, const RtDnGuide& g, unsigned long long i, double* out, double*) { rt_dn_finish_pixel(c, g, out + i * 3u); }
+};
 
 #endif

@@ -40,18 +40,6 @@ RT_HD void rt_dc_prepare_pixel(const RtDnParams& P, const double* frame, const d
     c.vb = c.va;
 }
 
-/* images as the level reads them: plain arrays in memory (the twin, and the kernel's direct form) */
-struct RtDcGlobalSrc {
-    const RtDcCol* c;
-    const RtDnGuide* g;
-    uint32_t w;
-    RT_HD RtDcCol col(uint32_t x, uint32_t y) const { return c[(unsigned long long)y * w + x]; }
-    RT_HD void guide(uint32_t x, uint32_t y, double o[5]) const {
-        const RtDnGuide* q = g + ((unsigned long long)y * w + x);
-        o[0] = q->nx; o[1] = q->ny; o[2] = q->nz; o[3] = q->z; o[4] = q->v;
-    }
-};
-
 /* level `level` of pixel (x, y): rt_dv_level_pixel's taps and order, two weights per tap -- wa from (lb, vb), which filters A, and wb
  * from (la, va), which filters B -- and each half's sums over the taps its own weight takes (w > 0) */
 template <class Src>
@@ -110,5 +98,17 @@ RT_HD void rt_dc_finish_pixel(const RtDcCol& c, const RtDnGuide& g, double* out,
     const double e = ((d * d) * 0.25) / ((lo > 0.0 ? lo : 0.0) + RT_AD_ERR_FLOOR);
     *err = rt_dn_finite(e) ? e : 0.0;
 }
+
+/* the filter as the skeletons see it (rt_denoise.h: RtDnFilter) */
+struct RtDcFilter {
+    typedef RtDcCol Col;
+    static RT_HD void prepare(const RtDnParams& P, unsigned long long i, Col& c, RtDnGuide& g, const double* frame, const double* aov, const double* var,
+                              const double* half_a, const double* half_b) {
+        rt_dc_prepare_pixel(P, frame + i * 3u, aov + i * 8u, var[i], half_a + i * 3u, half_b + i * 3u, c, g);
+    }
+    template <class Src>
+    static RT_HD Col level(const RtDnParams& P, double sv2, const Src& src, uint32_t x, uint32_t y, uint32_t level) { return rt_dc_level_pixel(P, sv2, src, x, y, level); }
+    static RT_HD void finish(const Col& c, const RtDnGuide& g, unsigned long long i, double* out, double* err_px) { rt_dc_finish_pixel(c, g, out + i * 3u, err_px + i); }
+};
 
 #endif

@@ -60,18 +60,6 @@ RT_HD void rt_dh_prepare_pixel(const RtDnParams& P, const double* frame, const d
     c.bb = P.keep_albedo ? half_b[2] : half_b[2] / g.ab;
 }
 
-/* images as the level reads them: plain arrays in memory (the twin, and the kernel's direct form) */
-struct RtDhGlobalSrc {
-    const RtDhCol* c;
-    const RtDnGuide* g;
-    uint32_t w;
-    RT_HD RtDhCol col(uint32_t x, uint32_t y) const { return c[(unsigned long long)y * w + x]; }
-    RT_HD void guide(uint32_t x, uint32_t y, double o[5]) const {
-        const RtDnGuide* q = g + ((unsigned long long)y * w + x);
-        o[0] = q->nx; o[1] = q->ny; o[2] = q->nz; o[3] = q->z; o[4] = q->v;
-    }
-};
-
 /* level `level` of pixel (x, y): rt_dv_level_pixel -- the same weight, the same taps, the same additions for r, g, b, l, v -- and
  * a' = sum w a_q / sum w, b' likewise, over exactly the taps the colour takes, in the colour's order */
 template <class Src>
@@ -130,5 +118,17 @@ RT_HD void rt_dh_finish_pixel(const RtDhCol& c, const RtDnGuide& g, double* out,
 
 /* a value of rt1w_tile_error_map's per-pixel map as the tile sum takes it: negative or not finite counts as 0 */
 RT_HD double rt_dh_map_value(double e) { return (e >= 0.0 && rt_dn_finite(e)) ? e : 0.0; }
+
+/* the filter as the skeletons see it (rt_denoise.h: RtDnFilter) */
+struct RtDhFilter {
+    typedef RtDhCol Col;
+    static RT_HD void prepare(const RtDnParams& P, unsigned long long i, Col& c, RtDnGuide& g, const double* frame, const double* aov, const double* var,
+                              const double* half_a, const double* half_b) {
+        rt_dh_prepare_pixel(P, frame + i * 3u, aov + i * 8u, var[i], half_a + i * 3u, half_b + i * 3u, c, g);
+    }
+    template <class Src>
+    static RT_HD Col level(const RtDnParams& P, double sv2, const Src& src, uint32_t x, uint32_t y, uint32_t level) { return rt_dh_level_pixel(P, sv2, src, x, y, level); }
+    static RT_HD void finish(const Col& c, const RtDnGuide& g, unsigned long long i, double* out, double* err_px) { rt_dh_finish_pixel(c, g, out + i * 3u, err_px + i); }
+};
 
 #endif

@@ -81,18 +81,6 @@ RT_HD void rt_dv_prepare_pixel(const RtDnParams& P, const double* frame, const d
     c.v = (var >= 0.0 && rt_dn_finite(var)) ? var : 0.0;
 }
 
-/* images as the level reads them: plain arrays in memory (the twin, and the kernel's direct form) */
-struct RtDvGlobalSrc {
-    const RtDvCol* c;
-    const RtDnGuide* g;
-    uint32_t w;
-    RT_HD RtDvCol col(uint32_t x, uint32_t y) const { return c[(unsigned long long)y * w + x]; }
-    RT_HD void guide(uint32_t x, uint32_t y, double o[5]) const {
-        const RtDnGuide* q = g + ((unsigned long long)y * w + x);
-        o[0] = q->nx; o[1] = q->ny; o[2] = q->nz; o[3] = q->z; o[4] = q->v;
-    }
-};
-
 /* the weight of a tap q that is not the centre p: rt_dn_level_pixel's but for the colour term -- x_colour = 0 where l_p == l_q, else
  * (l_p - l_q)^2 / (sigma_variance^2 (v_p + v_q)), +inf where both variances are 0.  hw = h(dx, dy); gp, gq: the two guides; pz: u_p is
  * (0, 0, 0); sv2 = sigma_variance^2.  Shared by the level below and the level of rt_denoise_halves.h: one text for the weight. */
@@ -155,5 +143,16 @@ RT_HD RtDvCol rt_dv_level_pixel(const RtDnParams& P, double sv2, const Src& src,
 RT_HD void rt_dv_finish_pixel(const RtDvCol& c, const RtDnGuide& g, double* out) {
     out[0] = c.r * g.ar; out[1] = c.g * g.ag; out[2] = c.b * g.ab;
 }
+
+/* the filter as the skeletons see it (rt_denoise.h: RtDnFilter) */
+struct RtDvFilter {
+    typedef RtDvCol Col;
+    static RT_HD void prepare(const RtDnParams& P, unsigned long long i, Col& c, RtDnGuide& g, const double* frame, const double* aov, const double* var) {
+        rt_dv_prepare_pixel(P, frame + i * 3u, aov + i * 8u, var[i], c, g);
+    }
+    template <class Src>
+    static RT_HD Col level(const RtDnParams& P, double sv2, const Src& src, uint32_t x, uint32_t y, uint32_t level) { return rt_dv_level_pixel(P, sv2, src, x, y, level); }
+    static RT_HD void finish(const Col& c, const RtDnGuide& g, unsigned long long i, double* out, double*) { rt_dv_finish_pixel(c, g, out + i * 3u); }
+};
 
 #endif
