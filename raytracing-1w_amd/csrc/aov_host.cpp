@@ -1,6 +1,7 @@
 /* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip, aov_tiles.hip): rt_aov.h, rt_aov_deep.h and rt_aov_tiles.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core) and run over a committed scene's flat arrays.  Diagnostics library only (librt1w_lab.so): the expected side of the GPU
  * tests' bit-equality checks and of the CPU tier's checks against the literal oracle.  librt1w.so keeps no CPU render path. */
+#include <algorithm>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -46,14 +47,16 @@ bool aov_rows(const RtSceneView& sc, const RtFrame& f, const AovDeep& d, uint32_
         }
     return true;
 }
-bool aov_rows_variant(int v, const RtSceneView& sc, const RtFrame& f, const AovDeep& d, uint32_t row0, uint32_t row_step, double* out, uint64_t* rays) {
-    switch (v) { /* the variants the kernels are built for */
-        case 0: return aov_rows<RtCfgV0>(sc, f, d, row0, row_step, out, rays);
-        case 1: return aov_rows<RtCfgV1>(sc, f, d, row0, row_step, out, rays);
-        case 2: return aov_rows<RtCfgV2>(sc, f, d, row0, row_step, out, rays);
-        case 4: return aov_rows<RtCfgV4>(sc, f, d, row0, row_step, out, rays);
-        case 5: return aov_rows<RtCfgV5>(sc, f, d, row0, row_step, out, rays);
-        default: return aov_rows<RtCfgV3>(sc, f, d, row0, row_step, out, rays);
+/* run(Cfg{}) for the Cfg of variant v: the variants the kernels are built for */
+template <class Run>
+bool with_variant(int v, Run run) {
+    switch (v) {
+        case 0: return run(RtCfgV0{});
+        case 1: return run(RtCfgV1{});
+        case 2: return run(RtCfgV2{});
+        case 4: return run(RtCfgV4{});
+        case 5: return run(RtCfgV5{});
+        default: return run(RtCfgV3{});
     }
 }
 
@@ -73,11 +76,20 @@ bool host_view(const rt1w_scene* s, uint32_t flags, std::vector<RtNode>& nodes, 
     sc.perlin = s->perlin.data(); sc.images = s->images.data();
     return true;
 }
-/* at most 16 threads, at most `work` of them */
-uint32_t host_threads(uint32_t work) {
+constexpr uint32_t MAX_THREADS = 16u;
+/* `work` items dealt round-robin over at most MAX_THREADS threads: part(t, n_threads) does items t, t + n_threads, ..  Every pixel is computed whole
+ * by one thread, so the result does not depend on their number.  false: a part returned false (a traversal stack overflowed) */
+template <class Part>
+bool round_robin(uint32_t work, Part part) {
     const unsigned hw = std::thread::hardware_concurrency();
-    const uint32_t n = hw == 0u ? 1u : (hw > 16u ? 16u : hw);
-    return n > work ? work : n;
+    const uint32_t n_threads = std::max(1u, std::min({(uint32_t)hw, MAX_THREADS, work}));
+    std::vector<char> ok(n_threads, 1);
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back([&, t]() { ok[t] = part(t, n_threads) ? 1 : 0; });
+    ok[0] = part(0u, n_threads) ? 1 : 0;
+    for (auto& th : pool) th.join();
+    for (char k : ok) if (!k) return false;
+    return true;
 }
 
 int aov_host_run(const rt1w_scene* s, const rt1w_render_params* p, const AovDeep& deep, double* out, uint64_t* segments) {
@@ -91,15 +103,11 @@ int aov_host_run(const rt1w_scene* s, const rt1w_render_params* p, const AovDeep
     if (!host_view(s, p->flags, nodes, sc, v)) return RT1W_ERR_INVALID;
     RtFrame f = rt1w::frame_of(p);
     f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u;
-    /* rows dealt round-robin over at most 16 threads: every pixel is computed whole by one thread, so the result does not depend on it */
-    const uint32_t n_threads = host_threads(f.tile_h);
-    std::vector<char> ok(n_threads, 1);
-    std::vector<uint64_t> rays(n_threads, 0u);
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back([&, t]() { ok[t] = aov_rows_variant(v, sc, f, deep, t, n_threads, out, &rays[t]) ? 1 : 0; });
-    ok[0] = aov_rows_variant(v, sc, f, deep, 0u, n_threads, out, &rays[0]) ? 1 : 0;
-    for (auto& th : pool) th.join();
-    for (char k : ok) if (!k) return RT1W_ERR_STATE; /* a traversal stack overflowed */
+    uint64_t rays[MAX_THREADS] = {}; /* per thread */
+    const bool ok = round_robin(f.tile_h, [&](uint32_t t, uint32_t n_threads) { /* the tile's rows */
+        return with_variant(v, [&](auto cfg) { return aov_rows<decltype(cfg)>(sc, f, deep, t, n_threads, out, &rays[t]); });
+    });
+    if (!ok) return RT1W_ERR_STATE;
     if (segments) { *segments = 0u; for (uint64_t r : rays) *segments += r; }
     return RT1W_OK;
 }
@@ -117,23 +125,12 @@ bool aov_tiles(const RtSceneView& sc, const RtFrame& f, uint32_t tile, const rt1
             }
     return true;
 }
-bool aov_tiles_variant(int v, const RtSceneView& sc, const RtFrame& f, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t k0, uint32_t step, double* out) {
-    switch (v) {
-        case 0: return aov_tiles<RtCfgV0>(sc, f, tile, tiles, n, k0, step, out);
-        case 1: return aov_tiles<RtCfgV1>(sc, f, tile, tiles, n, k0, step, out);
-        case 2: return aov_tiles<RtCfgV2>(sc, f, tile, tiles, n, k0, step, out);
-        case 4: return aov_tiles<RtCfgV4>(sc, f, tile, tiles, n, k0, step, out);
-        case 5: return aov_tiles<RtCfgV5>(sc, f, tile, tiles, n, k0, step, out);
-        default: return aov_tiles<RtCfgV3>(sc, f, tile, tiles, n, k0, step, out);
-    }
-}
 } // namespace
 
 extern "C" int rt1w_lab_aov_tiles_host(const rt1w_scene* s, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out) {
     if (!s || !p || !tiles || !out || !s->committed) return RT1W_ERR_INVALID;
     const char* why = nullptr;
-    unsigned long long inside = 0ull;
-    if (const int rc = rt_aov_tiles_check(p, tile, tiles, n_tiles, &why, &inside); rc < 0) return rc; /* the entries' own check */
+    if (const int rc = rt_aov_tiles_check(p, tile, tiles, n_tiles, &why); rc < 0) return rc; /* the entries' own check */
     std::vector<RtNode> nodes;
     RtSceneView sc;
     int v;
@@ -141,15 +138,10 @@ extern "C" int rt1w_lab_aov_tiles_host(const rt1w_scene* s, const rt1w_render_pa
     RtFrame f = rt1w::frame_of(p);
     f.x0 = 0u; f.y0 = 0u; f.tile_w = tile; f.tile_h = n_tiles * tile;
     f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u;
-    /* tiles dealt round-robin over the threads: every pixel is computed whole by one thread */
-    const uint32_t n_threads = host_threads(n_tiles);
-    std::vector<char> ok(n_threads, 1);
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back([&, t]() { ok[t] = aov_tiles_variant(v, sc, f, tile, tiles, n_tiles, t, n_threads, out) ? 1 : 0; });
-    ok[0] = aov_tiles_variant(v, sc, f, tile, tiles, n_tiles, 0u, n_threads, out) ? 1 : 0;
-    for (auto& th : pool) th.join();
-    for (char k : ok) if (!k) return RT1W_ERR_STATE; /* a traversal stack overflowed */
-    return RT1W_OK;
+    const bool ok = round_robin(n_tiles, [&](uint32_t t, uint32_t n_threads) { /* the list's tiles */
+        return with_variant(v, [&](auto cfg) { return aov_tiles<decltype(cfg)>(sc, f, tile, tiles, n_tiles, t, n_threads, out); });
+    });
+    return ok ? RT1W_OK : RT1W_ERR_STATE;
 }
 
 extern "C" int rt1w_lab_aov_host(const rt1w_scene* s, const rt1w_render_params* p, double* out) { return aov_host_run(s, p, AovDeep{}, out, nullptr); }

@@ -21,12 +21,12 @@ namespace rtdn {
 #include "rt_denoise.h"
 #include "rt_atrous_kernels.h"
 
-__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dn_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
+__global__ __launch_bounds__(RT_PX_WG) void rt_dn_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
                                                                      RtDnCol* __restrict__ col, RtDnGuide* __restrict__ guide) {
     rt_at_prepare<RtDnFilter>(P, col, guide, frame, aov);
 }
 template <int STEP>
-__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dn_level_kernel(RtDnParams P, uint32_t level, const RtDnCol* __restrict__ src,
+__global__ __launch_bounds__(RT_PX_WG) void rt_dn_level_kernel(RtDnParams P, uint32_t level, const RtDnCol* __restrict__ src,
                                                                    const RtDnGuide* __restrict__ guide, RtDnCol* __restrict__ dst, double* __restrict__ out) {
     rt_at_level<RtDnFilter, STEP>(P, 0.0, level, src, guide, dst, out, nullptr);
 }

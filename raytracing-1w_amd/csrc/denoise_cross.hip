@@ -24,14 +24,14 @@ namespace rtdc {
 #include "rt_denoise_cross.h"
 #include "rt_atrous_kernels.h"
 
-__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dc_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
+__global__ __launch_bounds__(RT_PX_WG) void rt_dc_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
                                                                      const double* __restrict__ var, const double* __restrict__ half_a,
                                                                      const double* __restrict__ half_b, RtDcCol* __restrict__ col,
                                                                      RtDnGuide* __restrict__ guide) {
     rt_at_prepare<RtDcFilter>(P, col, guide, frame, aov, var, half_a, half_b);
 }
 template <int STEP>
-__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dc_level_kernel(RtDnParams P, double sv2, uint32_t level, const RtDcCol* __restrict__ src,
+__global__ __launch_bounds__(RT_PX_WG) void rt_dc_level_kernel(RtDnParams P, double sv2, uint32_t level, const RtDcCol* __restrict__ src,
                                                                    const RtDnGuide* __restrict__ guide, RtDcCol* __restrict__ dst, double* __restrict__ out,
                                                                    double* __restrict__ err_px) {
     rt_at_level<RtDcFilter, STEP>(P, sv2, level, src, guide, dst, out, err_px);

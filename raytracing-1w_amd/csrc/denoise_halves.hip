@@ -23,14 +23,14 @@ namespace rtdh {
 #include "rt_denoise_halves.h"
 #include "rt_atrous_kernels.h"
 
-__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dh_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
+__global__ __launch_bounds__(RT_PX_WG) void rt_dh_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
                                                                      const double* __restrict__ var, const double* __restrict__ half_a,
                                                                      const double* __restrict__ half_b, RtDhCol* __restrict__ col,
                                                                      RtDnGuide* __restrict__ guide) {
     rt_at_prepare<RtDhFilter>(P, col, guide, frame, aov, var, half_a, half_b);
 }
 template <int STEP>
-__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dh_level_kernel(RtDnParams P, double sv2, uint32_t level, const RtDhCol* __restrict__ src,
+__global__ __launch_bounds__(RT_PX_WG) void rt_dh_level_kernel(RtDnParams P, double sv2, uint32_t level, const RtDhCol* __restrict__ src,
                                                                    const RtDnGuide* __restrict__ guide, RtDhCol* __restrict__ dst, double* __restrict__ out,
                                                                    double* __restrict__ err_px) {
     rt_at_level<RtDhFilter, STEP>(P, sv2, level, src, guide, dst, out, err_px);

@@ -18,11 +18,11 @@ namespace rtdv {
 #include "rt_atrous_kernels.h"
 
 /* sums[K][h][w][3], aov[h][w][8] -> frame[h][w][3], var[h][w] */
-__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dv_variance_kernel(uint32_t w, uint32_t h, uint32_t batches, uint32_t batch_spp, uint32_t keep_albedo,
+__global__ __launch_bounds__(RT_PX_WG) void rt_dv_variance_kernel(uint32_t w, uint32_t h, uint32_t batches, uint32_t batch_spp, uint32_t keep_albedo,
                                                                       const double* __restrict__ sums, const double* __restrict__ aov,
                                                                       double* __restrict__ frame, double* __restrict__ var) {
-    uint32_t tx, ty, x, y;
-    rt_at_lane_pixel(w, tx, ty, x, y);
+    uint32_t x, y;
+    rt_px_lane_pixel(w, x, y);
     if (x >= w || y >= h) return;
     const unsigned long long i = (unsigned long long)y * w + x;
     double f[3], v;
@@ -31,13 +31,13 @@ __global__ __launch_bounds__(RT_AT_BLOCK) void rt_dv_variance_kernel(uint32_t w,
     var[i] = v;
 }
 
-__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dv_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
+__global__ __launch_bounds__(RT_PX_WG) void rt_dv_prepare_kernel(RtDnParams P, const double* __restrict__ frame, const double* __restrict__ aov,
                                                                      const double* __restrict__ var, RtDvCol* __restrict__ col,
                                                                      RtDnGuide* __restrict__ guide) {
     rt_at_prepare<RtDvFilter>(P, col, guide, frame, aov, var);
 }
 template <int STEP>
-__global__ __launch_bounds__(RT_AT_BLOCK) void rt_dv_level_kernel(RtDnParams P, double sv2, uint32_t level, const RtDvCol* __restrict__ src,
+__global__ __launch_bounds__(RT_PX_WG) void rt_dv_level_kernel(RtDnParams P, double sv2, uint32_t level, const RtDvCol* __restrict__ src,
                                                                    const RtDnGuide* __restrict__ guide, RtDvCol* __restrict__ dst, double* __restrict__ out) {
     rt_at_level<RtDvFilter, STEP>(P, sv2, level, src, guide, dst, out, nullptr);
 }
@@ -50,10 +50,7 @@ extern "C" int rt1w_internal_batch_variance_launch(uint32_t w, uint32_t h, uint3
     using namespace rtdv;
     RtDnParams P;
     if (!rt_dn_make_params(w, h, 0u, flags, 0.0, 0.0, 0.0, P) || !rt_dv_batches_ok(batches, batch_spp)) return -2;
-    const unsigned grid = rt_at_grid(w, h);
-    launch[0] = grid; launch[1] = RT_AT_BLOCK;
-    hipLaunchKernelGGL(rt_dv_variance_kernel, dim3(grid), dim3(RT_AT_BLOCK), 0, stream, w, h, batches, batch_spp, P.keep_albedo, sums, aov, frame, var);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return rt_px_launch(rt_dv_variance_kernel, rt_px_frame_grid(w, h), stream, launch, w, h, batches, batch_spp, P.keep_albedo, sums, aov, frame, var);
 }
 
 /* called by features.hip.  Enqueues the prepare pass and the levels on `stream`, one after another: frame + aov + var -> col_a, guide; the

@@ -4,7 +4,9 @@
  * path belong to context.hip (context.h), so a change here rebuilds none of the code objects.
  * Every entry is its checks, in the order its callers know, then one table of its buffers (Staged) handed to staged_entry(), which does what
  * the host and the device form of an entry differ in -- growing the context's buffers, laying the call's buffers out in them, the copies
- * in and out -- and the clock.  Every launch of a filter or accumulator kernel goes through lane_run(). */
+ * in and out -- and the clock.  Every kernel launch of this file goes through lane_run() over a typed *_launch of rt_feature_launch.h: no
+ * kernel handle, no argument array and no launch call of its own is left here.  The AOV entries add to lane_run's stats the fields it does
+ * not fill (segments, chunk, n_chunks, variant). */
 #include <cstdio>
 #include <cstring>
 
@@ -116,7 +118,7 @@ int aov_deep_validate(const AovDeep* deep) {
     set_error("max_specular must be 0 .. 64 and max_fuzz finite and >= 0");
     return RT1W_ERR_INVALID;
 }
-/* launch the AOV kernel of the context's (or the forced) variant into d_out, wait, fill stats */
+/* the AOV kernel of the context's (or the forced) variant into d_out through lane_run; of the stats what that leaves open */
 int render_aov_common(rt1w_context* c, const rt1w_render_params* p, const AovDeep* deep, double* d_out, rt1w_stats* stats) {
     int variant = c->variant;
     const int rc = forced_variant(c, p->flags, true, &variant);
@@ -127,30 +129,23 @@ int render_aov_common(rt1w_context* c, const rt1w_render_params* p, const AovDee
     if (rt1w_internal_aov_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_aov_sizeof(1) != sizeof(RtFrame)) {
         set_error("AOV kernels built against another scene layout"); return RT1W_ERR_DEVICE;
     }
-    const void* fn = deep ? rt1w_internal_aov_deep_kernel(variant) : rt1w_internal_aov_kernel(variant);
-    if (!fn) { set_error("no AOV kernel of this variant"); return RT1W_ERR_DEVICE; }
-    const unsigned grid = rt1w_internal_aov_grid(&f);
-    /* (view, frame, out), the deep kernel's (view, frame, max_specular, max_fuzz, out, rays traced): the lane's second counter, the
-     * one the render kernels count their segments in */
-    AovDeep dv = deep ? *deep : AovDeep{0u, 0.0};
+    /* the deep kernel counts the rays it traces in the lane's second counter, the one the render kernels count their segments in: zeroed
+     * before the lane's two events, read after them */
     unsigned long long* d_rays = l.d_counters + 1;
-    void* args_first[] = {&c->view, &f, &d_out};
-    void* args_deep[] = {&c->view, &f, &dv.max_specular, &dv.max_fuzz, &d_out, &d_rays};
     if (deep && !hip_ok(hipMemsetAsync(d_rays, 0, sizeof *d_rays, l.stream), "AOV counter")) return RT1W_ERR_DEVICE;
-    (void)hipEventRecord(l.ev0, l.stream);
-    if (!hip_ok(hipLaunchKernel(fn, dim3(grid), dim3(RT_BLOCK), deep ? args_deep : args_first, 0, l.stream), "AOV kernel launch")) return RT1W_ERR_DEVICE;
-    (void)hipEventRecord(l.ev1, l.stream);
-    if (deep && !hip_ok(hipMemcpyAsync(l.h_counters + 1, d_rays, sizeof *d_rays, hipMemcpyDeviceToHost, l.stream), "AOV counter copy")) return RT1W_ERR_DEVICE;
-    if (!hip_ok(hipStreamSynchronize(l.stream), "AOV kernel")) return RT1W_ERR_DEVICE;
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->paths = (uint64_t)p->tile_w * p->tile_h * p->spp;
-        stats->segments = deep ? l.h_counters[1] : stats->paths; /* first hit: one camera ray per sample */
-        stats->kernel_ms = lane_ms(l);
-        stats->chunk = p->spp; stats->n_chunks = 1u;
-        stats->grid = grid; stats->block = RT_BLOCK;
-        stats->variant = (uint32_t)variant; stats->passes = 1u;
-    }
+    rt1w_stats st;
+    const int r = lane_run(c, (uint64_t)p->tile_w * p->tile_h * p->spp, "AOV", &st, [&](hipStream_t stream, unsigned* launch) {
+        return deep ? rt1w_internal_aov_deep_launch(&c->view, &f, variant, deep->max_specular, deep->max_fuzz, d_out, d_rays, stream, launch)
+                    : rt1w_internal_aov_launch(&c->view, &f, variant, d_out, stream, launch);
+    });
+    if (r < 0) return r;
+    if (deep && !(hip_ok(hipMemcpyAsync(l.h_counters + 1, d_rays, sizeof *d_rays, hipMemcpyDeviceToHost, l.stream), "AOV counter copy") &&
+                  hip_ok(hipStreamSynchronize(l.stream), "AOV counter copy")))
+        return RT1W_ERR_DEVICE; /* on the lane's own stream: no other stream of the device is waited for */
+    st.segments = deep ? l.h_counters[1] : st.paths; /* first hit: one camera ray per sample */
+    st.chunk = p->spp; st.n_chunks = 1u;
+    st.variant = (uint32_t)variant;
+    if (stats) *stats = st;
     return RT1W_OK;
 }
 /* the four AOV entries.  `out` is device memory, or (host) host memory, filled through the context's framebuffer */
@@ -369,9 +364,7 @@ int accum_merge_tiles_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t t
     const uint32_t* d_rec = nullptr;
     const int rc = tiles_upload(c, tiles, n, &d_rec);
     if (rc < 0) return rc;
-    uint64_t inside = 0;
-    for (uint32_t k = 0; k < n; ++k) inside += (uint64_t)std::min(tile, w - tiles[k].x0) * std::min(tile, h - tiles[k].y0);
-    return lane_run(c, inside, "accumulator merge (tile list)", stats, [&](hipStream_t stream, unsigned* launch) {
+    return lane_run(c, rt_ad_list_pixels(w, h, tile, tiles, n), "accumulator merge (tile list)", stats, [&](hipStream_t stream, unsigned* launch) {
         return rt1w_internal_accum_merge_tiles_launch(w, h, tile, d_rec, n, batch_spp, flags, d_sums, d_aov, d_acc, stream, launch);
     });
 }
@@ -618,10 +611,9 @@ int tile_error_map(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const
 }
 /* ---- first-hit feature sums of a list of tiles and the guide accumulator (include/rt1w.h: rt1w_render_aov_tiles, rt1w_guides_merge_tiles,
  * rt1w_guides_resolve) ---- */
-/* upload the list, launch the tile-list AOV kernel of the context's (or the forced) variant into d_out, wait, fill stats.  The parameters and
- * the list are checked by the caller (rt_aov_tiles_check), which also counts `inside`, the list's pixels inside the frame */
-int render_aov_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n, unsigned long long inside,
-                            double* d_out, rt1w_stats* stats) {
+/* upload the list, the tile-list AOV kernel of the context's (or the forced) variant into d_out through lane_run; of the stats what that
+ * leaves open.  The parameters and the list are checked by the caller (rt_aov_tiles_check) */
+int render_aov_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n, double* d_out, rt1w_stats* stats) {
     int variant = c->variant;
     int rc = forced_variant(c, p->flags, true, &variant);
     if (rc < 0) return rc;
@@ -631,25 +623,19 @@ int render_aov_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32
     if (rt1w_internal_aov_tiles_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_aov_tiles_sizeof(1) != sizeof(RtFrame)) {
         set_error("tile-list AOV kernels built against another scene layout"); return RT1W_ERR_DEVICE;
     }
-    const void* fn = rt1w_internal_aov_tiles_kernel(variant);
-    if (!fn) { set_error("no tile-list AOV kernel of this variant"); return RT1W_ERR_DEVICE; }
     const uint32_t* d_rec = nullptr;
     if ((rc = tiles_upload(c, tiles, n, &d_rec)) < 0) return rc;
-    const unsigned grid = n * (tile / 16u) * (tile / 16u); /* <= 2^20 x 256 */
-    RtLane& l = c->lane[0];
-    void* args[] = {&c->view, &f, &tile, &d_rec, &d_out};
-    (void)hipEventRecord(l.ev0, l.stream);
-    if (!hip_ok(hipLaunchKernel(fn, dim3(grid), dim3(RT_BLOCK), args, 0, l.stream), "tile-list AOV kernel launch")) return RT1W_ERR_DEVICE;
-    (void)hipEventRecord(l.ev1, l.stream);
-    if (!hip_ok(hipStreamSynchronize(l.stream), "tile-list AOV kernel")) return RT1W_ERR_DEVICE;
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->paths = stats->segments = inside * p->spp; /* first hit: one camera ray per sample; pixels beyond the frame are not traced */
-        stats->kernel_ms = lane_ms(l);
-        stats->chunk = p->spp; stats->n_chunks = 1u;
-        stats->grid = grid; stats->block = RT_BLOCK;
-        stats->variant = (uint32_t)variant; stats->passes = 1u;
-    }
+    /* first hit: one camera ray per sample; pixels beyond the frame are not traced */
+    const uint64_t paths = rt_ad_list_pixels(p->width, p->height, tile, tiles, n) * p->spp;
+    rt1w_stats st;
+    if ((rc = lane_run(c, paths, "tile-list AOV", &st, [&](hipStream_t stream, unsigned* launch) {
+            return rt1w_internal_aov_tiles_launch(&c->view, &f, variant, tile, d_rec, n, d_out, stream, launch);
+        })) < 0)
+        return rc;
+    st.segments = st.paths;
+    st.chunk = p->spp; st.n_chunks = 1u;
+    st.variant = (uint32_t)variant;
+    if (stats) *stats = st;
     return RT1W_OK;
 }
 /* the two rt1w_render_aov_tiles entries.  What the parameters and the list alone decide comes before the context is looked at.  Host form:
@@ -657,11 +643,10 @@ int render_aov_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32
 int render_aov_tiles(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n, void* out, bool host, rt1w_stats* stats) {
     if (!p || !tiles || !out) { set_error("null argument"); return RT1W_ERR_INVALID; }
     const char* why = nullptr;
-    unsigned long long inside = 0ull;
-    if (const int rc = rt_aov_tiles_check(p, tile, tiles, n, &why, &inside); rc < 0) { set_error(why); return rc; }
+    if (const int rc = rt_aov_tiles_check(p, tile, tiles, n, &why); rc < 0) { set_error(why); return rc; }
     if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
     Staged s[] = {{nullptr, (double*)out, (size_t)n * tile * tile * RT1W_AOV_CHANNELS, FRAMEBUFFER, nullptr, "AOV tile sums copy"}};
-    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) { return render_aov_tiles_common(c, p, tile, tiles, n, inside, s[0].d_out, st); });
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) { return render_aov_tiles_common(c, p, tile, tiles, n, s[0].d_out, st); });
 }
 /* the list is checked by the caller (rt_gd_tiles_check) */
 int guides_merge_tiles_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t spp, const double* d_sums,
@@ -669,9 +654,7 @@ int guides_merge_tiles_common(rt1w_context* c, uint32_t w, uint32_t h, uint32_t 
     const uint32_t* d_rec = nullptr;
     const int rc = tiles_upload(c, tiles, n, &d_rec);
     if (rc < 0) return rc;
-    uint64_t inside = 0;
-    for (uint32_t k = 0; k < n; ++k) inside += (uint64_t)std::min(tile, w - tiles[k].x0) * std::min(tile, h - tiles[k].y0);
-    return lane_run(c, inside, "guides merge (tile list)", stats, [&](hipStream_t stream, unsigned* launch) {
+    return lane_run(c, rt_ad_list_pixels(w, h, tile, tiles, n), "guides merge (tile list)", stats, [&](hipStream_t stream, unsigned* launch) {
         return rt1w_internal_guides_merge_tiles_launch(w, h, tile, d_rec, n, spp, d_sums, d_gacc, stream, launch);
     });
 }
@@ -757,9 +740,7 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
         std::vector<rt1w_tile> list;
         /* guided: the first-hit sums of `list` (spp and offsets as set), merged into the guide accumulator */
         auto guides_add = [&]() -> int {
-            unsigned long long inside = 0ull;
-            for (const rt1w_tile& t : list) inside += rt_ad_tile_pixels(W, H, plan.tile, t.x0 / plan.tile, t.y0 / plan.tile);
-            int e = render_aov_tiles_common(c, &ap, plan.tile, list.data(), (uint32_t)list.size(), inside, d_aov_sums, &sk);
+            int e = render_aov_tiles_common(c, &ap, plan.tile, list.data(), (uint32_t)list.size(), d_aov_sums, &sk);
             if (e < 0) return e;
             other_ms += sk.kernel_ms;
             if ((e = guides_merge_tiles_common(c, W, H, plan.tile, list.data(), (uint32_t)list.size(), ap.spp, d_aov_sums, d_gacc, &sk)) < 0) return e;

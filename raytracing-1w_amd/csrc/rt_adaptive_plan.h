@@ -85,6 +85,14 @@ inline int rt_ad_tile_records_check(uint32_t w, uint32_t h, uint32_t tile, const
     return 0;
 }
 
+/* pixels of a list's tiles that lie inside the frame (the records checked: rt_ad_tile_records_check).  Each tile's rt_ad_tile_pixels, clipped
+ * with two comparisons instead of that function's divisions: lists run to 2^20 tiles */
+inline unsigned long long rt_ad_list_pixels(uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n) {
+    unsigned long long inside = 0ull;
+    for (uint32_t k = 0; k < n; ++k) inside += (unsigned long long)std::min(tile, w - tiles[k].x0) * std::min(tile, h - tiles[k].y0);
+    return inside;
+}
+
 /* the list of rt1w_accum_merge_tiles: nullptr, or why it is refused (RT1W_ERR_INVALID) */
 inline const char* rt_ad_tiles_check(uint32_t w, uint32_t h, uint32_t tile, const rt1w_tile* tiles, uint32_t n, uint32_t batch_spp, uint32_t flags) {
     if (!rt_ad_frame_ok(w, h)) return "accumulator: width and height must be 1 .. 2^30";
@@ -112,8 +120,8 @@ inline const char* rt_gd_tiles_check(uint32_t w, uint32_t h, uint32_t tile, cons
 }
 
 /* what rt1w_render_aov_tiles refuses in its parameters and its list, in the order its callers know: RT1W_OK, or the code with *why set.
- * A tile may be named more than once (with other offsets).  *inside: the pixels of the list that lie inside the frame */
-inline int rt_aov_tiles_check(const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n, const char** why, unsigned long long* inside) {
+ * A tile may be named more than once (with other offsets) */
+inline int rt_aov_tiles_check(const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n, const char** why) {
     const auto refuse = [why](int rc, const char* text) { *why = text; return rc; };
     if (p->width < 2 || p->height < 2) return refuse(RT1W_ERR_INVALID, "width and height must be >= 2 (u,v divide by W-1, H-1; main.rs:968-969)");
     if (p->spp == 0) return refuse(RT1W_ERR_INVALID, "spp must be > 0");
@@ -125,11 +133,8 @@ inline int rt_aov_tiles_check(const rt1w_render_params* p, uint32_t tile, const 
     if (n < 1u || n > RT_AD_TILES_MAX) return refuse(RT1W_ERR_INVALID, "rt1w_render_aov_tiles: n_tiles must be 1 .. 2^20");
     if (rt_ad_tile_records_check(p->width, p->height, tile, tiles, n, false))
         return refuse(RT1W_ERR_INVALID, "rt1w_render_aov_tiles: a tile's x0 and y0 must be multiples of `tile` inside the frame, its reserved member 0");
-    *inside = 0ull;
-    for (uint32_t k = 0; k < n; ++k) {
+    for (uint32_t k = 0; k < n; ++k)
         if ((unsigned long long)p->sample_offset + tiles[k].sample_offset + p->spp > 0xFFFFFFFFull) return refuse(RT1W_ERR_INVALID, "sample index overflow");
-        *inside += rt_ad_tile_pixels(p->width, p->height, tile, tiles[k].x0 / tile, tiles[k].y0 / tile);
-    }
     return RT1W_OK;
 }
 

@@ -1,5 +1,5 @@
 /* rt_atrous_kernels.h -- the one skeleton of the four a-trous filter units (denoise.hip, denoise_var.hip, denoise_halves.hip,
- * denoise_cross.hip): the work mapping, the staged tile, the bodies of the prepare and the level kernel, and the enqueue loop.  A unit
+ * denoise_cross.hip): the staged tile, the bodies of the prepare and the level kernel, and the enqueue loop.  A unit
  * includes it inside its own namespace, after its rt_denoise*.h (<hip/hip_runtime.h> and <stdint.h> before the namespace), and adds the
  * named __global__ shells over the bodies and its extern "C" launcher: the four code objects stay separate.
  *
@@ -7,7 +7,8 @@
  * CPU twin over the same four): F::Col, the colour record, sizeof(Col) / 8 doubles; F::prepare, F::level, F::finish over the per-pixel
  * functions of that header.
  *
- * Work mapping: one lane per pixel, an 8 x 8 pixel block per wave, 2 x 2 blocks (16 x 16 pixels) per workgroup of 256 lanes.  Every output
+ * Work mapping: that of rt_pixel_kernels.h, workgroups in row order over the image -- one lane per pixel, an 8 x 8 pixel block per wave,
+ * 2 x 2 blocks (16 x 16 pixels) per workgroup of 256 lanes.  Every output
  * pixel is computed whole by one lane in the fixed tap order of the filter's level_pixel: no atomics, the same bits as the twin.  The
  * prepare pass turns the caller's buffers into what the levels read: a colour record and the 64-byte guide record (RtDnGuide), both f64.
  * A level reads the colour records of the previous one and writes its own (two buffers, ping-pong); the last level writes the caller's
@@ -18,24 +19,13 @@
  * guide's normal, depth and coverage; (NC + 5) T^2 doubles -- then every tap is an LDS read.  Direct (STEP 0, any level): the 25 taps of a
  * wave are 25 8 x 8 blocks, read from memory through L2.  Which of levels 0 and 1 run staged is the launcher's mask, bit = level
  * (DESIGN.md sections 13, 17, 18 have the measurements behind the units' defaults). */
-#define RT_AT_BLOCK 256
-#define RT_AT_TILE 16u
-
-/* pixel of this lane: 8 x 8 block per wave, 2 x 2 waves per workgroup, workgroups in row order over the image */
-__device__ __forceinline__ void rt_at_lane_pixel(uint32_t w, uint32_t& tx, uint32_t& ty, uint32_t& x, uint32_t& y) {
-    const uint32_t tiles_x = (w + RT_AT_TILE - 1u) / RT_AT_TILE;
-    tx = blockIdx.x % tiles_x; ty = blockIdx.x / tiles_x;
-    const uint32_t wv = threadIdx.x >> 6, in = threadIdx.x & 63u;
-    x = tx * RT_AT_TILE + (wv & 1u) * 8u + (in & 7u);
-    y = ty * RT_AT_TILE + (wv >> 1) * 8u + (in >> 3);
-}
-__host__ inline unsigned rt_at_grid(uint32_t w, uint32_t h) { return ((w + RT_AT_TILE - 1u) / RT_AT_TILE) * ((h + RT_AT_TILE - 1u) / RT_AT_TILE); }
+#include "rt_pixel_kernels.h" /* the work mapping (rt_px_lane_pixel), its grid, RT_PX_WG, RT_PX_BLOCK */
 
 /* the body of a prepare kernel; in: the caller's buffers as F::prepare takes them */
 template <class F, class... In>
 __device__ __forceinline__ void rt_at_prepare(const RtDnParams& P, typename F::Col* col, RtDnGuide* guide, In... in) {
     uint32_t tx, ty, x, y;
-    rt_at_lane_pixel(P.w, tx, ty, x, y);
+    rt_px_lane_pixel(P.w, tx, ty, x, y);
     if (x >= P.w || y >= P.h) return;
     const unsigned long long i = (unsigned long long)y * P.w + x;
     typename F::Col c;
@@ -74,14 +64,14 @@ __device__ __forceinline__ void rt_at_level(const RtDnParams& P, double sv2, uin
                                             typename F::Col* dst, double* out, double* err_px) {
     typedef typename F::Col Col;
     uint32_t tx, ty, x, y;
-    rt_at_lane_pixel(P.w, tx, ty, x, y);
+    rt_px_lane_pixel(P.w, tx, ty, x, y);
     const bool inside = x < P.w && y < P.h;
     Col c;
     if constexpr (STEP > 0) {
-        constexpr int T = (int)RT_AT_TILE + 4 * STEP, NC = (int)(sizeof(Col) / 8);
+        constexpr int T = (int)RT_PX_BLOCK + 4 * STEP, NC = (int)(sizeof(Col) / 8);
         __shared__ double tile[(NC + 5) * T * T];
-        const long long ox = (long long)tx * RT_AT_TILE - 2 * STEP, oy = (long long)ty * RT_AT_TILE - 2 * STEP;
-        for (int i = (int)threadIdx.x; i < T * T; i += RT_AT_BLOCK) {
+        const long long ox = (long long)tx * RT_PX_BLOCK - 2 * STEP, oy = (long long)ty * RT_PX_BLOCK - 2 * STEP;
+        for (int i = (int)threadIdx.x; i < T * T; i += RT_PX_WG) {
             const long long gx = ox + i % T, gy = oy + i / T;
             if (gx < 0 || gy < 0 || gx >= (long long)P.w || gy >= (long long)P.h) continue;
             const unsigned long long q = (unsigned long long)gy * P.w + (unsigned long long)gx;
@@ -114,8 +104,8 @@ __device__ __forceinline__ void rt_at_level(const RtDnParams& P, double sv2, uin
  * grid, block of the level kernel.  0 or -1 (launch failure) */
 template <class Col, class Prepare, class Level>
 __host__ int rt_at_enqueue(const RtDnParams& P, unsigned staged, void* col_a, void* col_b, unsigned launch[2], Prepare prepare, Level level_launch) {
-    const dim3 grid(rt_at_grid(P.w, P.h)), block(RT_AT_BLOCK);
-    launch[0] = grid.x; launch[1] = RT_AT_BLOCK;
+    const dim3 grid(rt_px_frame_grid(P.w, P.h)), block(RT_PX_WG);
+    launch[0] = grid.x; launch[1] = RT_PX_WG;
     Col* src = (Col*)col_a;
     Col* dst = (Col*)col_b;
     prepare(grid, block, src);

@@ -1,8 +1,11 @@
 /* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip and temporal.hip, declared once.
  * The functions are extern "C": nothing in their names says what they take, so caller and definition both include this header and the
  * compiler holds each definition to the declaration the caller sees.  Private (librt1w.map exports none of them).
- * The *_launch functions enqueue on `stream`, put grid and block of the launch (of the level kernel, for the filters) into launch[0..1]
- * and return 0, -1 launch failure, -2 parameters refused. */
+ * Every kernel is reached through a typed *_launch: no kernel handle leaves its unit, and no argument array is built by hand.  The
+ * *_launch functions enqueue on `stream`, put grid and block of the launch (of the level kernel, for the filters) into launch[0..1]
+ * and return 0, -1 launch failure, -2 parameters refused.  What a unit's kernels take by value in a layout of the caller's (the AOV
+ * kernels' view and frame, the temporal kernel's cameras) is passed by address and copied into the unit's own type; the *_sizeof
+ * functions let the caller check that the two layouts have one size. */
 #ifndef RT1W_FEATURE_LAUNCH_H
 #define RT1W_FEATURE_LAUNCH_H
 
@@ -10,10 +13,13 @@
 #include <stdint.h>
 
 extern "C" {
-/* aov.hip: the first-hit feature buffers (rt1w_render_aov), by variant; workgroups of RT_BLOCK work-items that cover the frame's tile */
-const void* rt1w_internal_aov_kernel(int variant);
-const void* rt1w_internal_aov_deep_kernel(int variant); /* rt1w_render_aov_deep: + (max_specular, max_fuzz) before out, a segment counter after */
-unsigned rt1w_internal_aov_grid(const void* frame);
+/* aov.hip: the first-hit feature buffers (rt1w_render_aov) and the deep ones (rt1w_render_aov_deep: + max_specular, max_fuzz and a counter
+ * in device memory, zeroed by the caller, that receives the rays traced), by the kernel of `variant` over the tile of `frame`.  `view` and
+ * `frame` by address: the bytes of an RtSceneView and an RtFrame, rt1w_internal_aov_sizeof(0) and (1) of them, copied into the kernel's
+ * arguments */
+int rt1w_internal_aov_launch(const void* view, const void* frame, int variant, double* out, hipStream_t stream, unsigned launch[2]);
+int rt1w_internal_aov_deep_launch(const void* view, const void* frame, int variant, uint32_t max_specular, double max_fuzz, double* out,
+                                  unsigned long long* segments, hipStream_t stream, unsigned launch[2]);
 unsigned rt1w_internal_aov_sizeof(int what);
 /* denoise.hip: the filter of rt1w_denoise; enqueues the prepare pass and the levels */
 int rt1w_internal_denoise_launch(uint32_t w, uint32_t h, uint32_t iterations, uint32_t flags, double sigma_colour, double sigma_normal,
@@ -53,9 +59,10 @@ int rt1w_internal_denoise_cross_launch(uint32_t w, uint32_t h, uint32_t iteratio
                                        const double* half_b, double* out, double* err_px, void* col_a, void* col_b, void* guide,
                                        hipStream_t stream, unsigned launch[2]);
 unsigned rt1w_internal_denoise_cross_sizeof(void); /* bytes per pixel of one of its colour buffers */
-/* aov_tiles.hip: the first-hit feature sums of a list of tiles (rt1w_render_aov_tiles), by variant; n_tiles x (tile / 16)^2 workgroups of
- * RT_BLOCK work-items on (view, frame, tile, the uploaded list, out) */
-const void* rt1w_internal_aov_tiles_kernel(int variant);
+/* aov_tiles.hip: the first-hit feature sums of a list of tiles (rt1w_render_aov_tiles), by the kernel of `variant`; view and frame as for
+ * aov.hip, rt1w_internal_aov_tiles_sizeof(0) and (1) bytes; rec the uploaded list */
+int rt1w_internal_aov_tiles_launch(const void* view, const void* frame, int variant, uint32_t tile, const uint32_t* rec, uint32_t n, double* out,
+                                   hipStream_t stream, unsigned launch[2]);
 unsigned rt1w_internal_aov_tiles_sizeof(int what);
 /* guides.hip: the guide accumulator (rt1w_guides_merge_tiles, rt1w_guides_resolve) */
 int rt1w_internal_guides_merge_tiles_launch(uint32_t w, uint32_t h, uint32_t tile, const uint32_t* rec, uint32_t n, uint32_t spp, const double* sums,

@@ -4,8 +4,8 @@
  * none of the run-time compiler's inputs moves with it.  The host half (validation, buffers, timing, copies, the state of
  * rt1w_render_temporal) is in features.hip, which calls the launcher below.
  *
- * Work mapping: one lane per pixel, an 8 x 8 pixel block per wave, 2 x 2 blocks (16 x 16 pixels) per workgroup of 256 lanes, as the
- * denoiser has it: the reprojection of a block is a block of about the same size, so a wave's four gathers fall into few cache lines.
+ * Work mapping: that of rt_pixel_kernels.h, workgroups in row order over the image -- one lane per pixel, an 8 x 8 pixel block per wave,
+ * 2 x 2 blocks (16 x 16 pixels) per workgroup of 256 lanes, as the denoiser has it: the reprojection of a block is a block of about the same size, so a wave's four gathers fall into few cache lines.
  * Every output pixel is computed whole by one lane in the fixed tap order of rt_tm_pixel: no atomics, no LDS, the same bits as the CPU
  * twin (denoise_host.cpp).  Both cameras are kernel arguments by value (2 x 192 bytes of the kernel-argument segment, read by scalar
  * loads).  The build fails if the kernel uses scratch (Makefile: no_scratch_unit). */
@@ -18,18 +18,14 @@ namespace rttm {
 #include "rt1w_num.h"
 #include "rt_temporal.h"
 
-#define RT_TM_BLOCK 256
-#define RT_TM_TILE 16u
+#include "rt_pixel_kernels.h"
 
-__global__ __launch_bounds__(RT_TM_BLOCK) void rt_tm_accumulate_kernel(RtTmParams P, RtCamera cc, RtCamera pc, const double* __restrict__ cur_frame,
+__global__ __launch_bounds__(RT_PX_WG) void rt_tm_accumulate_kernel(RtTmParams P, RtCamera cc, RtCamera pc, const double* __restrict__ cur_frame,
                                                                         const double* __restrict__ cur_aov, const double* __restrict__ prev_hist,
                                                                         const double* __restrict__ prev_len, const double* __restrict__ prev_aov,
                                                                         double* __restrict__ hist, double* __restrict__ len, double* __restrict__ frame_out) {
-    const uint32_t tiles_x = (P.w + RT_TM_TILE - 1u) / RT_TM_TILE;
-    const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const uint32_t wv = threadIdx.x >> 6, in = threadIdx.x & 63u;
-    const uint32_t x = tx * RT_TM_TILE + (wv & 1u) * 8u + (in & 7u);
-    const uint32_t y = ty * RT_TM_TILE + (wv >> 1) * 8u + (in >> 3);
+    uint32_t x, y;
+    rt_px_lane_pixel(P.w, x, y);
     if (x >= P.w || y >= P.h) return;
     const unsigned long long i = (unsigned long long)y * P.w + x;
     rt_tm_pixel(P, cc, pc, cur_frame, cur_aov, prev_hist, prev_len, prev_aov, x, y, hist + i * 3u, len + i, frame_out + i * 3u, nullptr);
@@ -48,10 +44,7 @@ extern "C" int rt1w_internal_temporal_launch(uint32_t w, uint32_t h, uint32_t fl
     RtCamera cc, pc;
     memcpy(&cc, cur_cam, sizeof cc);
     memcpy(&pc, prev_cam, sizeof pc);
-    const unsigned grid = ((P.w + RT_TM_TILE - 1u) / RT_TM_TILE) * ((P.h + RT_TM_TILE - 1u) / RT_TM_TILE);
-    launch[0] = grid; launch[1] = RT_TM_BLOCK;
-    hipLaunchKernelGGL(rt_tm_accumulate_kernel, dim3(grid), dim3(RT_TM_BLOCK), 0, stream, P, cc, pc, cur_frame, cur_aov, prev_hist, prev_len, prev_aov,
-                       hist, len, frame_out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return rt_px_launch(rt_tm_accumulate_kernel, rt_px_frame_grid(P.w, P.h), stream, launch, P, cc, pc, cur_frame, cur_aov, prev_hist, prev_len, prev_aov,
+                        hist, len, frame_out);
 }
 extern "C" unsigned rt1w_internal_temporal_sizeof(void) { return (unsigned)sizeof(rttm::RtCamera); }
