@@ -217,6 +217,27 @@ std::string jit_source(const rt1w_scene& s, bool f32) {
     src += "    static constexpr uint32_t skip[" + std::to_string(N.size()) + "] = {";
     for (size_t i = 0; i < N.size(); ++i) src += (i ? ", " : "") + std::to_string(N[i].skip) + "u";
     src += "};\n";
+    /* the light list's shape (rt_core.h: RtLightShape): how many lights and the kind word of each, in order -- never their
+     * coordinates, which keep arriving in the light records: a scene that moves a light keeps its kernel */
+    const std::vector<RtNode>& L = s.flat_lights;
+    src += "    static constexpr uint32_t n_lights = " + std::to_string(L.size()) + "u;\n";
+    src += "    static constexpr uint32_t light_kind[" + std::to_string(L.empty() ? 1u : L.size()) + "] = {";
+    for (size_t i = 0; i < L.size(); ++i) src += (i ? ", " : "") + std::to_string(L[i].kind) + "u";
+    if (L.empty()) src += std::to_string(RT_NONE) + "u"; /* no zero-length arrays: one entry nobody reads */
+    src += "};\n";
+    /* where Lambertian materials sit (rt_core.h: RtLambertWalls): on which kinds of axis rect outside every wrapper -- their normal
+     * is one of six constant vectors and so is their shading frame -- and whether on anything else.  A FlipFace folded into the
+     * leaf (RT_LEAF_FLIPPED) changes neither the test nor the normal: such a leaf is a plain rect. */
+    bool lam_rect[3] = {false, false, false}, lam_general = false;
+    for (const RtNode& nd : N) {
+        const uint32_t k = nd.kind & RT_KIND_MASK;
+        if (k < RT_SPHERE || (k > RT_YZ && k != RT_MEDIUM) || (RT_MAT_KINDF(nd.mat) & 0xFFu) != RT_MAT_LAMBERTIAN) continue;
+        if (k >= RT_XY && k <= RT_YZ && nd.b == RT_NONE) lam_rect[k - RT_XY] = true;
+        else lam_general = true;
+    }
+    src += std::string("    static constexpr bool lambert_general = ") + (lam_general ? "true" : "false") +
+           ", lambert_xy = " + (lam_rect[0] ? "true" : "false") + ", lambert_xz = " + (lam_rect[1] ? "true" : "false") +
+           ", lambert_yz = " + (lam_rect[2] ? "true" : "false") + ";\n";
     /* which slab products a box takes from a box above it: part of the text, hence of the key -- the key depends on which bounds
      * coincide, not on their values.
      * Scenes with media (cornel_smoke) take whole axes only -- both planes from the same box, its swapped pair as it is.  A single

@@ -1193,25 +1193,27 @@ RT_HD RtV3 rt_onb_local(const RtOnb& o, RtV3 a) { return o.u * a.x + o.v * a.y +
 
 /* Hittable::pdf_value of one light: XZRect aarect.rs:119-138, Sphere sphere.rs:72-90,
  * anything else the trait default 0.0 (hittable.rs:66-68) */
+RT_HD double rt_xz_light_pdf_value(const RtNode& l, RtV3 o, RtV3 v) {
+    double t;
+    if (!rt_rect_t(l, o.y, v.y, o.x, v.x, o.z, v.z, RT_R(0.001), RT_INF, t)) return RT_R(0.0);
+    RtV3 on = rt_v3(RT_R(0.0), RT_R(1.0), RT_R(0.0));
+    RtV3 normal = (rt_dot(v, on) < RT_R(0.0)) ? on : -on;
+    double area = (l.d[1] - l.d[0]) * (l.d[3] - l.d[2]);
+    double distance_squared = t * t * rt_mag2(v);
+    double cosine = rt_abs(rt_dot(v, normal) / rt_mag(v));
+    return distance_squared / (cosine * area);
+}
+RT_HD double rt_sphere_light_pdf_value(const RtNode& l, RtV3 o, RtV3 v) {
+    double t;
+    RtV3 center = rt_v3(l.d[0], l.d[1], l.d[2]);
+    if (!rt_sphere_root(center, l.d[3], o, v, RT_R(0.001), RT_INF, t)) return RT_R(0.0);
+    double cos_theta_max = rt_sqrt(RT_R(1.0) - l.d[3] * l.d[3] / rt_mag2(center - o));
+    double solid_angle = RT_R(2.0) * RT_R(RT_PI) * (RT_R(1.0) - cos_theta_max);
+    return RT_R(1.0) / solid_angle;
+}
 RT_HD double rt_light_pdf_value(const RtNode& l, RtV3 o, RtV3 v) {
-    if (l.kind == RT_XZ) {
-        double t;
-        if (!rt_rect_t(l, o.y, v.y, o.x, v.x, o.z, v.z, RT_R(0.001), RT_INF, t)) return RT_R(0.0);
-        RtV3 on = rt_v3(RT_R(0.0), RT_R(1.0), RT_R(0.0));
-        RtV3 normal = (rt_dot(v, on) < RT_R(0.0)) ? on : -on;
-        double area = (l.d[1] - l.d[0]) * (l.d[3] - l.d[2]);
-        double distance_squared = t * t * rt_mag2(v);
-        double cosine = rt_abs(rt_dot(v, normal) / rt_mag(v));
-        return distance_squared / (cosine * area);
-    }
-    if (l.kind == RT_SPHERE) {
-        double t;
-        RtV3 center = rt_v3(l.d[0], l.d[1], l.d[2]);
-        if (!rt_sphere_root(center, l.d[3], o, v, RT_R(0.001), RT_INF, t)) return RT_R(0.0);
-        double cos_theta_max = rt_sqrt(RT_R(1.0) - l.d[3] * l.d[3] / rt_mag2(center - o));
-        double solid_angle = RT_R(2.0) * RT_R(RT_PI) * (RT_R(1.0) - cos_theta_max);
-        return RT_R(1.0) / solid_angle;
-    }
+    if (l.kind == RT_XZ) return rt_xz_light_pdf_value(l, o, v);
+    if (l.kind == RT_SPHERE) return rt_sphere_light_pdf_value(l, o, v);
     return RT_R(0.0);
 }
 /* Hittable::random of one light: aarect.rs:140-147, sphere.rs:92-99, default (1,0,0)
@@ -1236,6 +1238,83 @@ RT_HD double rt_lights_pdf_value(const RtSceneView& sc, RtV3 o, RtV3 v) {
     double sum = RT_R(0.0);
     for (uint32_t i = 0; i < sc.n_lights; ++i) sum = sum + weight * rt_light_pdf_value(sc.lights[i], o, v);
     return sum;
+}
+
+/* The light list's shape as the scene-specialised kernel knows it (jit.cpp: Topo::n_lights, Topo::light_kind -- the kind word of
+ * every sc.lights[i], in order; the records' values still come from sc.lights).  The walk over the list, the choice of a lobe and
+ * the tests for an empty list are then unrolled at compile time: every lane performs the operations of the loops above in their
+ * order, the compiler leaves out the kinds the list does not hold.  A Topo without the members (and void) leaves all of it to
+ * run time. */
+template <class Topo, class = void>
+struct RtLightShape {
+    static constexpr bool fixed = false, may_xz = true, may_sphere = true, may_default = true;
+    RT_HD static bool any(const RtSceneView& sc) { return sc.n_lights > 0u; }
+    RT_HD static uint32_t choose(const RtSceneView& sc, RtRng& rng) { return rt_gen_below(rng, sc.n_lights); }
+    RT_HD static uint32_t kind(const RtSceneView& sc, uint32_t li) { return sc.lights[li].kind; }
+    RT_HD static uint32_t index(uint32_t, uint32_t li) { return li; }
+    RT_HD static double pdf_value(const RtSceneView& sc, RtV3 o, RtV3 v) { return rt_lights_pdf_value(sc, o, v); }
+};
+/* lights of `kind` in Topo's list from entry i on, and the index of the first of them (n_lights if there is none) */
+template <class Topo>
+constexpr uint32_t rt_light_count(uint32_t kind, uint32_t i = 0u) { return i < Topo::n_lights ? (Topo::light_kind[i] == kind ? 1u : 0u) + rt_light_count<Topo>(kind, i + 1u) : 0u; }
+template <class Topo>
+constexpr uint32_t rt_light_first(uint32_t kind, uint32_t i = 0u) { return i < Topo::n_lights && Topo::light_kind[i] != kind ? rt_light_first<Topo>(kind, i + 1u) : i; }
+template <class Topo>
+struct RtLightShape<Topo, typename RtVoid<decltype(Topo::light_kind)>::type> {
+    static constexpr uint32_t n = Topo::n_lights;
+    static constexpr bool fixed = true, may_xz = rt_light_count<Topo>(RT_XZ) > 0u, may_sphere = rt_light_count<Topo>(RT_SPHERE) > 0u,
+                          may_default = rt_light_count<Topo>(RT_XZ) + rt_light_count<Topo>(RT_SPHERE) < n;
+    RT_HD static bool any(const RtSceneView&) { return n > 0u; }
+    RT_HD static uint32_t choose(const RtSceneView&, RtRng& rng) { return rt_gen_below(rng, n); }
+    template <uint32_t I = 0u>
+    RT_HD static uint32_t kind(const RtSceneView& sc, uint32_t li) {
+        if constexpr (I + 1u < n) return li == I ? Topo::light_kind[I] : kind<I + 1u>(sc, li);
+        else return Topo::light_kind[I];
+    }
+    /* the record of the chosen light of `kind`: where the list holds one light of that kind its index is a constant and the
+     * record is read once for the wave */
+    RT_HD static uint32_t index(uint32_t kind, uint32_t li) { return rt_light_count<Topo>(kind) == 1u ? rt_light_first<Topo>(kind) : li; }
+    template <uint32_t I>
+    RT_HD static double pdf_sum(const RtSceneView& sc, RtV3 o, RtV3 v, double sum) {
+        if constexpr (I < n) {
+            constexpr double weight = RT_R(1.0) / (double)n; /* the same correctly rounded quotient as at run time */
+            double value = RT_R(0.0);
+            if constexpr (Topo::light_kind[I] == RT_XZ) value = rt_xz_light_pdf_value(sc.lights[I], o, v);
+            else if constexpr (Topo::light_kind[I] == RT_SPHERE) value = rt_sphere_light_pdf_value(sc.lights[I], o, v);
+            return pdf_sum<I + 1u>(sc, o, v, sum + weight * value);
+        } else return sum;
+    }
+    RT_HD static double pdf_value(const RtSceneView& sc, RtV3 o, RtV3 v) { return pdf_sum<0u>(sc, o, v, RT_R(0.0)); }
+};
+
+/* Where Lambertian materials sit, as the scene-specialised kernel knows it (jit.cpp: Topo::lambert_xy / _xz / _yz: some XY / XZ /
+ * YZ rect outside every wrapper carries one; Topo::lambert_general: something else does).  The normal of such a rect is +-(0,0,1),
+ * +-(0,1,0) or +-(1,0,0) -- HitRecord::new's `-on`, so with the zeros' signs -- and its shading frame is rt_onb_from_w of that
+ * literal, which the compiler evaluates: six constant frames, selected by the rect's kind and the sign of the normal's own
+ * component.  The frames are not written out by hand: the signs of their zeros reach the scattered direction, 1 / d of the next
+ * segment and the slab swap. */
+template <class Topo, class = void>
+struct RtLambertWalls { static constexpr bool walls = false, general = true, xy = false, xz = false, yz = false; };
+template <class Topo>
+struct RtLambertWalls<Topo, typename RtVoid<decltype(Topo::lambert_general)>::type> {
+    static constexpr bool general = Topo::lambert_general, xy = Topo::lambert_xy, xz = Topo::lambert_xz, yz = Topo::lambert_yz, walls = xy || xz || yz;
+};
+RT_HD RtOnb rt_onb_select(bool c, const RtOnb& a, const RtOnb& b) {
+    RtOnb o;
+    o.u = rt_v3(c ? a.u.x : b.u.x, c ? a.u.y : b.u.y, c ? a.u.z : b.u.z);
+    o.v = rt_v3(c ? a.v.x : b.v.x, c ? a.v.y : b.v.y, c ? a.v.z : b.v.z);
+    o.w = rt_v3(c ? a.w.x : b.w.x, c ? a.w.y : b.w.y, c ? a.w.z : b.w.z);
+    return o;
+}
+/* the frame of an unwrapped axis rect of `kind` whose normal is n; for any other lane one of the frames, which nobody uses */
+template <class LW>
+RT_HD RtOnb rt_wall_frame(uint32_t kind, RtV3 n) {
+    const RtV3 ex = rt_v3(RT_R(1.0), RT_R(0.0), RT_R(0.0)), ey = rt_v3(RT_R(0.0), RT_R(1.0), RT_R(0.0)), ez = rt_v3(RT_R(0.0), RT_R(0.0), RT_R(1.0));
+    RtOnb o = rt_onb_from_w(ex);
+    if (LW::yz) o = rt_onb_select(n.x < RT_R(0.0), rt_onb_from_w(-ex), rt_onb_from_w(ex));
+    if (LW::xz) { RtOnb f = rt_onb_select(n.y < RT_R(0.0), rt_onb_from_w(-ey), rt_onb_from_w(ey)); o = LW::yz ? rt_onb_select(kind == RT_XZ, f, o) : f; }
+    if (LW::xy) { RtOnb f = rt_onb_select(n.z < RT_R(0.0), rt_onb_from_w(-ez), rt_onb_from_w(ez)); o = (LW::yz || LW::xz) ? rt_onb_select(kind == RT_XY, f, o) : f; }
+    return o;
 }
 
 /* ------------------------------------------------------------ materials -- */
@@ -1359,7 +1438,16 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
     if (mk == RT_MAT_LAMBERTIAN) {
         /* Lambertian::scatter material.rs:71-80 -> ScatterKind::Pdf(CosinePdf) */
         RtV3 attenuation = rt_mat_colour<Cfg>(sc, m, h.u, h.v, h.p);
-        RtOnb uvw = rt_onb_from_w(h.n);
+        typedef RtLightShape<typename Cfg::Topo> LS;
+        typedef RtLambertWalls<typename Cfg::Topo> LW;
+        /* an axis rect outside every wrapper: its frame is one of six constants (rt_wall_frame); every other path computes it */
+        const uint32_t pk = LW::walls ? sc.nodes[prim].kind & RT_KIND_MASK : (uint32_t)RT_NONE;
+        const bool wall = LW::walls && (!LW::general || (scope == RT_NONE && ((LW::xy && pk == RT_XY) || (LW::xz && pk == RT_XZ) || (LW::yz && pk == RT_YZ))));
+        RtOnb uvw = rt_wall_frame<LW>(pk, h.n);
+        if (!LW::walls || (LW::general && RT_WAVE_ANY(!wall))) {
+            RtOnb g = rt_onb_from_w(h.n);
+            uvw = rt_onb_select(wall, uvw, g);
+        }
         RtV3 dir;
         double pdf;
         /* MixturePdf::generate pdf.rs:62-68 (p0 = HittablePdf{lights}, p1 = CosinePdf), or CosinePdf alone.
@@ -1368,19 +1456,19 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
          * the three cases and only the conversion differs; cosine and sphere share one sincos. */
         uint32_t lk = RT_NONE; /* RT_NONE: cosine lobe */
         uint32_t li = 0u;
-        if (sc.n_lights > 0u) {
+        if (LS::any(sc)) {
             rt_rng_fill(p.rng);
             if (rt_take_bool(p.rng)) {
-                li = rt_gen_below(p.rng, sc.n_lights); /* choose, hittable.rs:153 */
-                lk = sc.lights[li].kind;
+                li = LS::choose(sc, p.rng); /* choose, hittable.rs:153 */
+                lk = LS::kind(sc, li);
             }
         }
-        if (lk == RT_NONE || lk == RT_XZ || lk == RT_SPHERE) {
+        if (!LS::may_default || lk == RT_NONE || lk == RT_XZ || lk == RT_SPHERE) {
             rt_rng_reserve(p.rng, rt_rng_need_2u64(p.rng));
             uint64_t q1 = rt_take_u64(p.rng);
             uint64_t q2 = rt_take_u64(p.rng);
-            if (lk == RT_XZ) {
-                const RtNode& l = sc.lights[li];
+            if (LS::may_xz && lk == RT_XZ) {
+                const RtNode& l = sc.lights[LS::index(RT_XZ, li)];
                 double x = rt_range_from_bits(q1, l.d[0], l.d[1]);
                 if (!(x < l.d[1])) { /* rounding onto `high`: the retry takes the next draw (rand 0.8 sample_single) */
                     x = rt_range_from_bits(q2, l.d[0], l.d[1]);
@@ -1396,8 +1484,8 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
                 double phi = RT_R(2.0) * RT_R(RT_PI) * r1;
                 double sn, cs;
                 rt_sincos(phi, sn, cs);
-                if (lk == RT_SPHERE) {
-                    const RtNode& l = sc.lights[li];
+                if (LS::may_sphere && lk == RT_SPHERE) {
+                    const RtNode& l = sc.lights[LS::index(RT_SPHERE, li)];
                     RtV3 direction = rt_v3(l.d[0], l.d[1], l.d[2]) - h.p;
                     double distance_squared = rt_mag2(direction);
                     RtOnb lw = rt_onb_from_w(direction);
@@ -1414,14 +1502,19 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
             dir = rt_v3(RT_R(1.0), RT_R(0.0), RT_R(0.0)); /* Hittable::random default, hittable.rs:69-71 */
         }
         double p1 = rt_max(rt_dot(rt_normalize(dir), uvw.w) / RT_R(RT_PI), RT_R(0.0)); /* CosinePdf::value pdf.rs:37-40 */
-        if (sc.n_lights > 0u) {
-            double p0 = rt_lights_pdf_value(sc, h.p, dir);
+        if (LS::any(sc)) {
+            double p0 = LS::pdf_value(sc, h.p, dir);
             pdf = RT_R(0.5) * p0 + RT_R(0.5) * p1; /* MixturePdf::value pdf.rs:58-60 */
         } else {
             pdf = p1;
         }
-        /* Lambertian::scattering_pdf material.rs:82-91 */
-        double spdf = rt_max(rt_dot(h.n, rt_normalize(dir)) / RT_R(RT_PI), RT_R(0.0));
+        /* Lambertian::scattering_pdf material.rs:82-91.  On a wall uvw.w is h.n bit for bit (an axis unit vector has magnitude exactly
+         * 1 and n * (1.0 / 1.0) is n, signed zeros included), and so this is p1, the same operations on the same operands. */
+        double spdf = p1;
+        if (!LW::walls || (LW::general && RT_WAVE_ANY(!wall))) {
+            double g = rt_max(rt_dot(h.n, rt_normalize(dir)) / RT_R(RT_PI), RT_R(0.0));
+            spdf = wall ? p1 : g;
+        }
         p.beta = rt_mul(p.beta, attenuation * spdf) / pdf;
         p.ray.o = h.p; p.ray.d = dir;
         p.ray.time = h.t; /* main.rs:86: time = hit_record.t (reference quirk Q1) */
