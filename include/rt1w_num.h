@@ -98,15 +98,31 @@ RT_HD double rt_floor(double x) { return rt_floor64(x); }
 
 struct RtPhiloxOut { uint32_t w0, w1, w2, w3; };
 
+/* a ^ b ^ c.  gfx950 has a three-input bitwise instruction (v_bitop3_b32, truth table 0x96 = odd parity) which the compiler
+ * does not select for two chained XORs; the round below has two such pairs, so the builtin takes a Philox block from 78 to
+ * 58 instructions.  Integer-exact: the same word on every target; everywhere else (host, CPU twins, other GPUs) the plain form. */
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__) && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+#define RT_HAVE_BITOP3 1
+#endif
+#endif
+RT_HD uint32_t rt_xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(RT_HAVE_BITOP3)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96u);
+#else
+    return a ^ b ^ c;
+#endif
+}
+
 RT_HD RtPhiloxOut rt_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                    uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         uint64_t p0 = (uint64_t)0xD2511F53u * c0;
         uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        uint32_t n0 = rt_xor3((uint32_t)(p1 >> 32), c1, k0);
         uint32_t n1 = (uint32_t)p1;
-        uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        uint32_t n2 = rt_xor3((uint32_t)(p0 >> 32), c3, k1);
         uint32_t n3 = (uint32_t)p0;
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
@@ -325,6 +341,22 @@ RT_HD rt_f64 rt_take_range(RtRng& r, rt_f64 low, rt_f64 high) {
         res = (v12 - 1.0) * scale + low;
     }
     return res;
+}
+/* rt_take_range(r, -1.0, 1.0) without its retry loop: the same draw, the same v12, the same (v12 - 1.0) * scale + low with
+ * scale = 1.0 - -1.0 and low = -1.0.  For these bounds the retry can never run, and every step is exact:
+ *   v12 is in [1, 2 - 2^-52] (52 random mantissa bits under the exponent of 1.0);
+ *   v12 - 1.0 is exact and in [0, 1 - 2^-52], a multiple of 2^-52;
+ *   * 2.0 is exact: a multiple of 2^-51 in [0, 2 - 2^-51];
+ *   + (-1.0) is exact: the result is a multiple of 2^-51 of magnitude <= 1, which a 53-bit significand holds.
+ * So res <= 1 - 2^-51 < high for every 64-bit word.  The compiler cannot see that through the bit operations and keeps the
+ * loop, the whole generator block of its checked draw and the loop-carried copies of the state; the unit-sphere and unit-disk
+ * samplers (csrc/rt_core.h), whose bounds are these constants, use this form.  rt_take_range keeps the retry for run-time bounds,
+ * and rt_gen_range (host, literal oracle) stays the looped statement this one is tested against (tests/test_rng_forms.py). */
+RT_HD rt_f64 rt_take_pm1(RtRng& r) {
+    const rt_f64 low = -1.0;
+    const rt_f64 scale = 1.0 - -1.0;
+    rt_f64 v12 = rt_u2d((rt_take_u64(r) >> 12) | 0x3FF0000000000000ull);
+    return (v12 - 1.0) * scale + low;
 }
 RT_HD bool rt_take_bool(RtRng& r) { return (int32_t)rt_take_u32(r) < 0; }
 

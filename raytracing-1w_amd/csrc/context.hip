@@ -75,6 +75,11 @@ __global__ void rt_debug_eval_kernel(int fn, const double* a, const double* b, d
         case 6: r = rt_log(rt_abs(y)); break;
         case 7: { RtRng g = rt_rng_pixel_sample(i, (uint32_t)rt_d2u(x), 0u); r = rt_gen_f64(g); } break;
         case 8: { RtRng g = rt_rng_pixel_sample(i, (uint32_t)rt_d2u(x), 0u); (void)rt_gen_f64(g); r = rt_gen_range(g, -1.0, 1.0); } break;
+        /* the same three draws on the stream of any 64-bit pixel seed (b's bits), and the loop-free (-1, 1) form the samplers use */
+        case 11: { RtRng g = rt_rng_pixel_sample(rt_d2u(y), (uint32_t)rt_d2u(x), 0u); r = rt_gen_f64(g); } break;
+        case 12: { RtRng g = rt_rng_pixel_sample(rt_d2u(y), (uint32_t)rt_d2u(x), 0u); (void)rt_gen_f64(g); r = rt_gen_range(g, -1.0, 1.0); } break;
+        case 13: { RtRng g = rt_rng_pixel_sample(rt_d2u(y), (uint32_t)rt_d2u(x), 0u); (void)rt_gen_f64(g);
+                   rt_rng_reserve(g, rt_rng_need_u64(g)); r = rt_take_pm1(g); } break;
         default: break;
     }
     out[i] = r;

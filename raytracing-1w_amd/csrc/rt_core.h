@@ -1132,14 +1132,15 @@ RT_HD RtV3 rt_mat_colour(const RtSceneView& sc, const RtMaterial& m, double u, d
 
 /* ------------------------------------------------------------ samplers -- */
 
-/* math.rs:6-18 */
+/* math.rs:6-18.  gen_range(-1.0..1.0) as rt_take_pm1: the same words and values as rt_take_range with those bounds, whose retry
+ * (and the generator block it holds) can never run (include/rt1w_num.h) */
 RT_HD RtV3 rt_random_in_unit_sphere(RtRng& rng) {
     for (;;) {
         rt_rng_reserve(rng, rt_rng_need_2u64(rng));
-        double x = rt_take_range(rng, -RT_R(1.0), RT_R(1.0));
-        double y = rt_take_range(rng, -RT_R(1.0), RT_R(1.0));
+        double x = rt_take_pm1(rng);
+        double y = rt_take_pm1(rng);
         rt_rng_reserve(rng, rt_rng_need_u64(rng));
-        double z = rt_take_range(rng, -RT_R(1.0), RT_R(1.0));
+        double z = rt_take_pm1(rng);
         RtV3 v = rt_v3(x, y, z);
         if (rt_mag2(v) < RT_R(1.0)) return v;
     }
@@ -1148,8 +1149,8 @@ RT_HD RtV3 rt_random_in_unit_sphere(RtRng& rng) {
 RT_HD RtV3 rt_random_in_unit_disk(RtRng& rng) {
     for (;;) {
         rt_rng_reserve(rng, rt_rng_need_2u64(rng));
-        double x = rt_take_range(rng, -RT_R(1.0), RT_R(1.0));
-        double y = rt_take_range(rng, -RT_R(1.0), RT_R(1.0));
+        double x = rt_take_pm1(rng);
+        double y = rt_take_pm1(rng);
         RtV3 p = rt_v3(x, y, RT_R(0.0));
         if (rt_mag2(p) < RT_R(1.0)) return p;
     }

@@ -45,8 +45,11 @@ template <class Cfg>
 __global__ __launch_bounds__(RT_BLOCK, RT_F32_WAVES(Cfg)) void rt_render_kernel_f32(RtSceneView sc, RtFrame f, rt_f64* __restrict__ partial, unsigned long long* __restrict__ counters) {
     rt_render_plain_body<Cfg, false>(sc, f, partial, counters);
 }
+/* the reordering kernels: 3 for both variants.  The feature-rich one needs a register or two around the 168 of that step (167 with the
+ * two-XOR Philox round, 169 with the three-input one when left to the f64 form's bound of 2 waves); held to 168 it spills nothing */
+#define RT_F32_SORT_WAVES 3
 template <class Cfg>
-__global__ __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES(Cfg)) void rt_render_kernel_sorted_f32(RtSceneView sc, RtFrame f, rt_f64* __restrict__ partial, unsigned long long* __restrict__ counters) {
+__global__ __launch_bounds__(RT_SORT_BLOCK, RT_F32_SORT_WAVES) void rt_render_kernel_sorted_f32(RtSceneView sc, RtFrame f, rt_f64* __restrict__ partial, unsigned long long* __restrict__ counters) {
     rt_render_sorted_body<Cfg>(sc, f, partial, counters);
 }
 /* the stack-walk variants with the finished paths reordered at the end of every slice (rt_kernel_plain.h: rt_render_ss_body) */
