@@ -217,6 +217,18 @@ std::string jit_source(const rt1w_scene& s, bool f32) {
     src += "    static constexpr uint32_t skip[" + std::to_string(N.size()) + "] = {";
     for (size_t i = 0; i < N.size(); ++i) src += (i ? ", " : "") + std::to_string(N[i].skip) + "u";
     src += "};\n";
+    /* what a hit needs to know about its node besides the ray (rt_core.h: RtHitShape): the wrapper above every leaf, wrapper and
+     * medium (a BVH node's `b` is its right child: RT_NONE here), and the kind word of a leaf's or medium's material with its
+     * NEEDS_UV / SOLID flags.  Indices and kinds of the topology only -- never a coordinate, never a material's values */
+    src += "    static constexpr uint32_t wrap[" + std::to_string(N.size()) + "] = {";
+    for (size_t i = 0; i < N.size(); ++i) src += (i ? ", " : "") + std::to_string((N[i].kind & RT_KIND_MASK) <= RT_BVH1 ? RT_NONE : N[i].b) + "u";
+    src += "};\n";
+    src += "    static constexpr uint32_t mat_kind[" + std::to_string(N.size()) + "] = {";
+    for (size_t i = 0; i < N.size(); ++i) {
+        const uint32_t k = N[i].kind & RT_KIND_MASK;
+        src += (i ? ", " : "") + std::to_string(((k >= RT_SPHERE && k <= RT_YZ) || k == RT_MEDIUM) ? RT_MAT_KINDF(N[i].mat) : 0u) + "u";
+    }
+    src += "};\n";
     /* the light list's shape (rt_core.h: RtLightShape): how many lights and the kind word of each, in order -- never their
      * coordinates, which keep arriving in the light records: a scene that moves a light keeps its kernel */
     const std::vector<RtNode>& L = s.flat_lights;

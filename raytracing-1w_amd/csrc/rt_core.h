@@ -213,7 +213,8 @@ RT_HD RtRayOD rt_scope_in(const NodeT& s, RtRayOD r) {
 /* the way back out: hittable.rs:215-225, :255-278, :288-291.  `inner` is the ray in
  * the wrapper's space (`moved` / `rotated_r`): both re-run HitRecord::new with it,
  * taking the child's already-forwarded normal as "outward" (reference quirk Q5). */
-RT_HD void rt_scope_out(const RtNode& s, RtRayOD inner, RtHit& h) {
+template <class NodeT>
+RT_HD void rt_scope_out(const NodeT& s, RtRayOD inner, RtHit& h) {
     if (s.kind == RT_TRANSLATE) {
         h.p = h.p + rt_v3(s.d[0], s.d[1], s.d[2]);
         bool front = rt_dot(inner.d, h.n) < RT_R(0.0);
@@ -1027,6 +1028,8 @@ RT_HD void rt_sweep_static(const RtSceneView& sc, const NS& ns, const RtRayOD& r
     }
 }
 
+template <class Topo, class = void>
+struct RtHitShape; /* below, with the static hit record */
 template <class Cfg, class Stack, class NS>
 RT_HD bool rt_closest_hit(const RtSceneView& sc, const NS& ns, const RtRay& ray, double t_min, double t_max, RtRng& rng,
                           Stack& stk, double& t, uint32_t& prim, uint32_t& scope) {
@@ -1037,7 +1040,8 @@ RT_HD bool rt_closest_hit(const RtSceneView& sc, const NS& ns, const RtRay& ray,
         const RtSlabNone none;
         t = t_max; prim = RT_NONE;
         rt_sweep_static<Topo, Cfg, true, Topo::root, Topo::skip[Topo::root]>(sc, ns, w, inv, ray.time, t_min, rt_isnan(t_min), rng, true, none, t, prim);
-        scope = prim == RT_NONE ? RT_NONE : ns.hot(prim).b; /* leaves keep their innermost wrapper in `b` */
+        if constexpr (RtHitShape<Topo>::trace || RtHitShape<Topo>::carry) scope = RtHitShape<Topo>::scope_of(prim); /* a compile-time function of the leaf: no record is read */
+        else scope = prim == RT_NONE ? RT_NONE : ns.hot(prim).b; /* leaves keep their innermost wrapper in `b` */
         return prim != RT_NONE;
     } else if constexpr (Cfg::sweep) return rt_traverse_sweep<Cfg, true>(sc, ns, sc.root, ray, t_min, t_max, rng, t, prim, scope);
     else if constexpr (RT_WALK_MODE != 0) return rt_traverse_stack_fused<Cfg, true>(sc, ns, sc.root, ray, t_min, t_max, rng, stk, t, prim, scope);
@@ -1307,14 +1311,15 @@ RT_HD RtOnb rt_onb_select(bool c, const RtOnb& a, const RtOnb& b) {
     o.w = rt_v3(c ? a.w.x : b.w.x, c ? a.w.y : b.w.y, c ? a.w.z : b.w.z);
     return o;
 }
-/* the frame of an unwrapped axis rect of `kind` whose normal is n; for any other lane one of the frames, which nobody uses */
+/* the frame of an unwrapped axis rect (an XZ one, an XY one, else a YZ one) whose normal is n; for any other lane one of the frames, which
+ * nobody uses */
 template <class LW>
-RT_HD RtOnb rt_wall_frame(uint32_t kind, RtV3 n) {
+RT_HD RtOnb rt_wall_frame(bool is_xz, bool is_xy, RtV3 n) {
     const RtV3 ex = rt_v3(RT_R(1.0), RT_R(0.0), RT_R(0.0)), ey = rt_v3(RT_R(0.0), RT_R(1.0), RT_R(0.0)), ez = rt_v3(RT_R(0.0), RT_R(0.0), RT_R(1.0));
     RtOnb o = rt_onb_from_w(ex);
     if (LW::yz) o = rt_onb_select(n.x < RT_R(0.0), rt_onb_from_w(-ex), rt_onb_from_w(ex));
-    if (LW::xz) { RtOnb f = rt_onb_select(n.y < RT_R(0.0), rt_onb_from_w(-ey), rt_onb_from_w(ey)); o = LW::yz ? rt_onb_select(kind == RT_XZ, f, o) : f; }
-    if (LW::xy) { RtOnb f = rt_onb_select(n.z < RT_R(0.0), rt_onb_from_w(-ez), rt_onb_from_w(ez)); o = (LW::yz || LW::xz) ? rt_onb_select(kind == RT_XY, f, o) : f; }
+    if (LW::xz) { RtOnb f = rt_onb_select(n.y < RT_R(0.0), rt_onb_from_w(-ey), rt_onb_from_w(ey)); o = LW::yz ? rt_onb_select(is_xz, f, o) : f; }
+    if (LW::xy) { RtOnb f = rt_onb_select(n.z < RT_R(0.0), rt_onb_from_w(-ez), rt_onb_from_w(ez)); o = (LW::yz || LW::xz) ? rt_onb_select(is_xy, f, o) : f; }
     return o;
 }
 
@@ -1382,6 +1387,260 @@ struct RtTrace {
  * (and will regenerate) the last one; other orders were measured 0.5-4 % slower */
 enum { RT_CLS_LAMBERT = 0, RT_CLS_DIELECTRIC = 1, RT_CLS_METAL = 2, RT_CLS_OTHER = 3, RT_CLS_TERMINAL = 4, RT_CLS_IDLE = 5, RT_N_CLS = 6 };
 
+/* the class of a hit on a material of kind mk */
+RT_HD constexpr uint32_t rt_class_of(uint32_t mk) {
+    return mk == RT_MAT_LAMBERTIAN ? RT_CLS_LAMBERT
+         : mk == RT_MAT_DIELECTRIC ? RT_CLS_DIELECTRIC
+         : mk == RT_MAT_METAL ? RT_CLS_METAL
+         : mk == RT_MAT_ISOTROPIC ? RT_CLS_OTHER : RT_CLS_TERMINAL;
+}
+
+/* ------------------------------------------------------ static hit record -- */
+
+/* What the scene-specialised kernel knows about the node a path hit (jit.cpp: Topo::wrap -- the wrapper above every leaf, wrapper and
+ * medium -- and Topo::mat_kind -- the kind word of a leaf's material).  In the unrolled sweep the closest leaf is one of a set the
+ * compiler knows, so its kind, its RT_LEAF_FLIPPED flag, its wrapper chain, whether its material reads (u, v) and the class its path
+ * sorts under are compile-time functions of `prim`: "is the lane's leaf one of these" replaces the node record, the walk up the chain
+ * and every dispatch on a loaded kind.  Values -- a wrapper's offset and angle, a sphere's centre -- still come from the records, read
+ * at constant indices (scalar loads).  A Topo without the members (and void) keeps rt_finish_hit.
+ * The leaves a path can hit are the leaves and media of the world outside every medium's boundary (a boundary is swept for its two
+ * roots only). */
+template <uint32_t N>
+struct RtHitTab {
+    bool leaf[N];       /* a path's closest hit can be this node */
+    uint32_t chain[N];  /* which of the distinct wrapper chains stands above it; RT_NONE outside every wrapper */
+    uint32_t s[N][3];   /* the distinct chains, outermost wrapper first (rt_chain), in the order of their first leaf */
+    uint32_t n_chains;
+};
+template <class Topo>
+constexpr RtHitTab<Topo::n> rt_hit_tab() {
+    RtHitTab<Topo::n> T{};
+    uint32_t medium_end = 0u;
+    for (uint32_t i = 0u; i < Topo::n; ++i) {
+        const uint32_t k = Topo::kind[i] & RT_KIND_MASK;
+        T.chain[i] = RT_NONE;
+        const bool hittable = i >= Topo::root && i < Topo::skip[Topo::root] && i >= medium_end && ((k >= RT_SPHERE && k <= RT_YZ) || k == RT_MEDIUM);
+        if (hittable) {
+            T.leaf[i] = true;
+            uint32_t c[3] = {RT_NONE, RT_NONE, RT_NONE};
+            for (uint32_t w = Topo::wrap[i]; w != RT_NONE; w = Topo::wrap[w]) { c[2] = c[1]; c[1] = c[0]; c[0] = w; }
+            if (c[0] != RT_NONE) {
+                uint32_t j = 0u;
+                while (j < T.n_chains && !(T.s[j][0] == c[0] && T.s[j][1] == c[1] && T.s[j][2] == c[2])) ++j;
+                if (j == T.n_chains) { T.s[j][0] = c[0]; T.s[j][1] = c[1]; T.s[j][2] = c[2]; ++T.n_chains; }
+                T.chain[i] = j;
+            }
+        }
+        if (hittable && k == RT_MEDIUM) medium_end = Topo::skip[i];
+    }
+    return T;
+}
+#ifndef RT_HIT_STATIC
+/* which parts are on (RT1W_JIT_EXTRA_OPTS=-DRT_HIT_STATIC=k builds any other mix; every mix gives the same bits).  Measured on the Cornell
+ * kernel, ms per launch at 600x600x1000 (profiles/hit_static_bench.json): none 115.6; the shipped 1 + 4: 111.6.  The class from the leaf
+ * (2) and the material word in the exchange (8) execute fewer instructions still and run slower: 1 + 2 + 4 + 8: 118.2, 1 + 4 + 8: 119.0,
+ * 1 + 2 + 8: 114.8, 2 alone 114.7 -- they stay behind the switch.
+ *   1  the static hit record (rt_finish_hit_static)
+ *   2  class and wrapper of a hit from its leaf: rt_path_trace reads no record in front of the sort
+ *   4  the Lambertian branch asks the leaf sets for "an unwrapped axis rect, and of which kind"
+ *   8  (with 1) the node's material word travels in the exchange where the wrapper did: no node record is read after it for a rect */
+#define RT_HIT_STATIC 5
+#endif
+#ifndef RT_HIT_MAX_CHAINS
+#define RT_HIT_MAX_CHAINS 8u /* distinct chains that get a block of their own; the leaves of the others walk their chain at run time */
+#endif
+/* groups of leaves: a chain's index, or */
+#define RT_HG_ANY 0xFFFFFFFEu       /* every leaf a path can hit */
+#define RT_HG_UNWRAPPED RT_NONE     /* the leaves outside every wrapper */
+#define RT_HG_WALKED 0xFFFFFFFDu    /* the leaves of the chains beyond RT_HIT_MAX_CHAINS */
+/* flags a set can ask for */
+enum { RT_HF_NONE = 0, RT_HF_FLIPPED = 1, RT_HF_UV = 2, RT_HF_CLASS = 3 /* arg: RT_CLS_* */ };
+#define RT_HK_ALL 0xFFFFFFFFu /* kinds as a mask of 1 << RT_SPHERE ... 1 << RT_MEDIUM */
+template <uint32_t I, uint32_t END, class F>
+RT_HD void rt_static_for(F&& f) {
+    if constexpr (I < END) { f(std::integral_constant<uint32_t, I>()); rt_static_for<I + 1u, END>(f); }
+}
+template <class Topo, class>
+struct RtHitShape { static constexpr bool fixed = false, record = false, trace = false, walls = false, carry = false; };
+template <class Topo>
+struct RtHitShape<Topo, typename RtVoid<decltype(Topo::wrap)>::type> {
+    static constexpr bool fixed = RT_HIT_STATIC != 0, record = (RT_HIT_STATIC & 1) != 0, trace = (RT_HIT_STATIC & 2) != 0, walls = (RT_HIT_STATIC & 4) != 0,
+                          carry = record && (RT_HIT_STATIC & 8) != 0;
+    static constexpr uint32_t n = Topo::n;
+    static constexpr RtHitTab<Topo::n> tab = rt_hit_tab<Topo>();
+    static constexpr uint32_t n_chains = tab.n_chains, n_blocks = n_chains < RT_HIT_MAX_CHAINS ? n_chains : RT_HIT_MAX_CHAINS;
+    static constexpr bool in_group(uint32_t g, uint32_t i) {
+        return tab.leaf[i] && (g == RT_HG_ANY || (g == RT_HG_WALKED ? (tab.chain[i] != RT_NONE && tab.chain[i] >= n_blocks) : tab.chain[i] == g));
+    }
+    /* the set (KINDS, FLAG, ARG, GROUP): leaves of GROUP whose kind is in KINDS and that have the flag */
+    static constexpr bool has(uint32_t kinds, uint32_t flag, uint32_t arg, uint32_t group, uint32_t i) {
+        return in_group(group, i) && ((kinds >> (Topo::kind[i] & RT_KIND_MASK)) & 1u) != 0u &&
+               (flag == RT_HF_NONE || (flag == RT_HF_FLIPPED ? (Topo::kind[i] & RT_LEAF_FLIPPED) != 0u
+                                       : flag == RT_HF_UV ? (Topo::mat_kind[i] & RT_MAT_NEEDS_UV) != 0u
+                                                          : rt_class_of(Topo::mat_kind[i] & 0xFFu) == arg));
+    }
+    static constexpr uint32_t count(uint32_t kinds, uint32_t flag, uint32_t arg, uint32_t group) {
+        uint32_t c = 0u;
+        for (uint32_t i = 0u; i < n; ++i) c += has(kinds, flag, arg, group, i) ? 1u : 0u;
+        return c;
+    }
+    /* the k-th member of the set, or of the rest of KNOWN (`other`) */
+    static constexpr uint32_t nth(uint32_t kinds, uint32_t flag, uint32_t arg, uint32_t group, uint32_t known, bool other, uint32_t k) {
+        for (uint32_t i = 0u; i < n; ++i)
+            if (in_group(known, i) && has(kinds, flag, arg, group, i) != other && k-- == 0u) return i;
+        return RT_NONE;
+    }
+    static constexpr uint64_t mask(uint32_t kinds, uint32_t flag, uint32_t arg, uint32_t group, uint32_t first, uint32_t bits) {
+        uint64_t m = 0u;
+        for (uint32_t i = 0u; i < bits && first + i < n; ++i) m |= has(kinds, flag, arg, group, first + i) ? (uint64_t)1u << i : (uint64_t)0u;
+        return m;
+    }
+    /* "is the lane's leaf in the set?", for a lane whose leaf is known to be in the group KNOWN.  A set that is empty or all of KNOWN
+     * is answered by the compiler; one or two leaves (or all but one or two) by comparing; anything else by a bit of a constant mask:
+     * one 32-bit word up to 32 nodes, one 64-bit word up to 64, and above that the non-zero 32-bit words, each behind the test for
+     * its word */
+    template <uint32_t KINDS, uint32_t FLAG, uint32_t ARG, uint32_t GROUP, uint32_t KNOWN = RT_HG_ANY>
+    RT_HD static bool in(uint32_t prim) {
+        static_assert(GROUP == KNOWN || KNOWN == RT_HG_ANY, "the set lies in the group the lane is known to be in");
+        constexpr uint32_t G = GROUP, cnt = count(KINDS, FLAG, ARG, G), tot = count(RT_HK_ALL, RT_HF_NONE, 0u, KNOWN);
+        if constexpr (cnt == 0u) return false;
+        else if constexpr (cnt == tot) return true;
+        else if constexpr (cnt <= 2u) {
+            constexpr uint32_t a = nth(KINDS, FLAG, ARG, G, KNOWN, false, 0u), b = nth(KINDS, FLAG, ARG, G, KNOWN, false, cnt - 1u);
+            return (prim == a) | (prim == b);
+        } else if constexpr (tot - cnt <= 2u) {
+            constexpr uint32_t a = nth(KINDS, FLAG, ARG, G, KNOWN, true, 0u), b = nth(KINDS, FLAG, ARG, G, KNOWN, true, tot - cnt - 1u);
+            return !((prim == a) | (prim == b));
+        } else if constexpr (n <= 32u) {
+            constexpr uint32_t m = (uint32_t)mask(KINDS, FLAG, ARG, G, 0u, 32u);
+            return ((m >> (prim & 31u)) & 1u) != 0u;
+        } else if constexpr (n <= 64u) {
+            constexpr uint64_t m = mask(KINDS, FLAG, ARG, G, 0u, 64u);
+            return ((m >> (prim & 63u)) & 1u) != 0u;
+        } else {
+            bool r = false;
+            rt_static_for<0u, (n + 31u) / 32u>([&](auto wi) {
+                constexpr uint32_t W = decltype(wi)::value, m = (uint32_t)mask(KINDS, FLAG, ARG, G, W * 32u, 32u);
+                if constexpr (m != 0u) r = r | (((prim >> 5) == W) & (((m >> (prim & 31u)) & 1u) != 0u));
+            });
+            return r;
+        }
+    }
+    /* the sort class of a hit on `prim` */
+    RT_HD static uint32_t cls(uint32_t prim) {
+        uint32_t c = RT_CLS_TERMINAL;
+        if (in<RT_HK_ALL, RT_HF_CLASS, RT_CLS_OTHER, RT_HG_ANY>(prim)) c = RT_CLS_OTHER;
+        if (in<RT_HK_ALL, RT_HF_CLASS, RT_CLS_METAL, RT_HG_ANY>(prim)) c = RT_CLS_METAL;
+        if (in<RT_HK_ALL, RT_HF_CLASS, RT_CLS_DIELECTRIC, RT_HG_ANY>(prim)) c = RT_CLS_DIELECTRIC;
+        if (in<RT_HK_ALL, RT_HF_CLASS, RT_CLS_LAMBERT, RT_HG_ANY>(prim)) c = RT_CLS_LAMBERT;
+        return c;
+    }
+    /* the innermost wrapper above `prim` (what the node keeps in `b`), for the callers of rt_closest_hit that want it */
+    RT_HD static uint32_t scope_of(uint32_t prim) {
+        uint32_t scope = RT_NONE;
+        if (prim == RT_NONE) return scope;
+        rt_static_for<0u, n_chains>([&](auto ci) {
+            constexpr uint32_t C = decltype(ci)::value;
+            constexpr uint32_t innermost = tab.s[C][2] != RT_NONE ? tab.s[C][2] : (tab.s[C][1] != RT_NONE ? tab.s[C][1] : tab.s[C][0]);
+            if (in<RT_HK_ALL, RT_HF_NONE, 0u, C>(prim)) scope = innermost;
+        });
+        return scope;
+    }
+    /* record of wrapper J, its kind word from the topology: rt_scope_in / rt_scope_out need no dispatch */
+    template <uint32_t J>
+    RT_HD static RtNodeHot wrapper(const RtSceneView& sc) {
+        constexpr uint32_t k = Topo::kind[J];
+        RtNodeHot w = RtGlobalNodes{sc.nodes}.hot(J);
+        w.kind = k;
+        return w;
+    }
+};
+
+/* rt_leaf_record for a lane whose leaf is in GROUP: the same statements on the same operands; which of them a lane runs is decided by
+ * set tests, and a record is read only where a value is needed -- a sphere's centre and radius (one scalar load where GROUP has one
+ * sphere), a moving sphere's, a rect's bounds where its texture reads (u, v) */
+template <class Cfg, uint32_t GROUP>
+RT_HD void rt_leaf_record_static(const RtSceneView& sc, RtRayOD r, double time, uint32_t prim, uint32_t mat, double t, RtHit& h) {
+    typedef RtHitShape<typename Cfg::Topo> HS;
+    constexpr uint32_t SPH = 1u << RT_SPHERE, MSPH = 1u << RT_MSPHERE, MED = 1u << RT_MEDIUM;
+    h.t = t; h.u = RT_R(0.0); h.v = RT_R(0.0); h.mat = mat;
+    h.p = rt_at(r.o, r.d, t);
+    const bool want_uv = Cfg::tex && HS::template in<RT_HK_ALL, RT_HF_UV, 0u, GROUP, GROUP>(prim);
+    if (Cfg::media && HS::template in<MED, RT_HF_NONE, 0u, GROUP, GROUP>(prim)) {
+        h.n = rt_v3(RT_R(1.0), RT_R(0.0), RT_R(0.0));
+        h.front = true;
+        return;
+    }
+    RtV3 on;
+    if (HS::template in<SPH | MSPH, RT_HF_NONE, 0u, GROUP, GROUP>(prim)) {
+        if (Cfg::msphere && HS::template in<MSPH, RT_HF_NONE, 0u, GROUP, GROUP>(prim)) {
+            const RtNode& nd = sc.nodes[prim];
+            on = (h.p - rt_msphere_center(nd, time)) / nd.e[2];
+        } else if constexpr (HS::count(Cfg::msphere ? SPH : SPH | MSPH, RT_HF_NONE, 0u, GROUP) == 1u) {
+            constexpr uint32_t J = HS::nth(Cfg::msphere ? SPH : SPH | MSPH, RT_HF_NONE, 0u, GROUP, GROUP, false, 0u);
+            const RtNodeHot nd = RtGlobalNodes{sc.nodes}.hot(J);
+            on = (h.p - rt_v3(nd.d[0], nd.d[1], nd.d[2])) / nd.d[3];
+        } else {
+            const RtNode& nd = sc.nodes[prim];
+            on = (h.p - rt_v3(nd.d[0], nd.d[1], nd.d[2])) / nd.d[3];
+        }
+        if (Cfg::tex && want_uv) rt_sphere_uv(on, h.u, h.v);
+    } else {
+        const bool is_xy = HS::template in<1u << RT_XY, RT_HF_NONE, 0u, GROUP, GROUP>(prim), is_xz = HS::template in<1u << RT_XZ, RT_HF_NONE, 0u, GROUP, GROUP>(prim);
+        on = rt_v3((is_xy | is_xz) ? RT_R(0.0) : RT_R(1.0), is_xz ? RT_R(1.0) : RT_R(0.0), is_xy ? RT_R(1.0) : RT_R(0.0));
+        if (Cfg::tex && want_uv) {
+            const RtNode& nd = sc.nodes[prim];
+            double b, c;
+            if (is_xy) { b = r.o.x + t * r.d.x; c = r.o.y + t * r.d.y; }
+            else if (is_xz) { b = r.o.x + t * r.d.x; c = r.o.z + t * r.d.z; }
+            else { b = r.o.y + t * r.d.y; c = r.o.z + t * r.d.z; }
+            h.u = (b - nd.d[0]) / (nd.d[1] - nd.d[0]);
+            h.v = (c - nd.d[2]) / (nd.d[3] - nd.d[2]);
+        }
+    }
+    /* HitRecord::new hittable.rs:30-35 */
+    bool front = rt_dot(r.d, on) < RT_R(0.0);
+    h.n = front ? on : -on;
+    h.front = HS::template in<RT_HK_ALL, RT_HF_FLIPPED, 0u, GROUP, GROUP>(prim) ? !front : front; /* FlipFace::hit hittable.rs:288-291 flips the flag only */
+}
+
+/* rt_finish_hit with the leaf sets known: the leaves outside every wrapper take their record in the world's ray; every distinct chain
+ * has one block, entered when a lane of the wave hit one of its leaves, with the wrappers' records at constant indices -- ray in,
+ * leaf record in the innermost ray, fix-ups innermost to outermost, as rt_finish_hit orders them.  Every lane performs the operations
+ * rt_finish_hit performs for it, on the same operands, in the same order.  `mat` is the node's material word.  Chains
+ * beyond RT_HIT_MAX_CHAINS are walked by rt_finish_hit itself. */
+template <class Cfg>
+RT_HD void rt_finish_hit_static(const RtSceneView& sc, const RtRay& world, uint32_t prim, uint32_t mat, double t, RtHit& h) {
+    typedef RtHitShape<typename Cfg::Topo> HS;
+    RtRayOD r0; r0.o = world.o; r0.d = world.d;
+    const bool plain = HS::template in<RT_HK_ALL, RT_HF_NONE, 0u, RT_HG_UNWRAPPED>(prim);
+    if (RT_WAVE_ANY(plain)) {
+        if (plain) rt_leaf_record_static<Cfg, RT_HG_UNWRAPPED>(sc, r0, world.time, prim, mat, t, h);
+    }
+    rt_static_for<0u, HS::n_blocks>([&](auto ci) {
+        constexpr uint32_t C = decltype(ci)::value, s0 = HS::tab.s[C][0], s1 = HS::tab.s[C][1], s2 = HS::tab.s[C][2];
+        const bool mine = HS::template in<RT_HK_ALL, RT_HF_NONE, 0u, C>(prim);
+        if (RT_WAVE_ANY(mine)) {
+            if (mine) {
+                const RtRayOD r1 = rt_scope_in(HS::template wrapper<s0>(sc), r0);
+                RtRayOD r2 = r1, r3 = r1;
+                if constexpr (s1 != RT_NONE) { r2 = rt_scope_in(HS::template wrapper<s1>(sc), r1); r3 = r2; }
+                if constexpr (s2 != RT_NONE) r3 = rt_scope_in(HS::template wrapper<s2>(sc), r2);
+                rt_leaf_record_static<Cfg, C>(sc, r3, world.time, prim, mat, t, h);
+                if constexpr (s2 != RT_NONE) rt_scope_out(HS::template wrapper<s2>(sc), r3, h);
+                if constexpr (s1 != RT_NONE) rt_scope_out(HS::template wrapper<s1>(sc), r2, h);
+                rt_scope_out(HS::template wrapper<s0>(sc), r1, h);
+            }
+        }
+    });
+    if constexpr (HS::n_chains > HS::n_blocks) {
+        const bool walked = HS::template in<RT_HK_ALL, RT_HF_NONE, 0u, RT_HG_WALKED>(prim);
+        if (RT_WAVE_ANY(walked)) {
+            if (walked) rt_finish_hit<Cfg>(sc, world, prim, sc.nodes[prim].b, t, h);
+        }
+    }
+}
+
 /* first half of one level of ray_color: depth check (main.rs:59-61) and world.hit (main.rs:62) */
 template <class Cfg, class Stack, class NS>
 RT_HD RtTrace rt_path_trace(const RtSceneView& sc, const NS& ns, RtPath& p, Stack& stk) {
@@ -1390,11 +1649,15 @@ RT_HD RtTrace rt_path_trace(const RtSceneView& sc, const NS& ns, RtPath& p, Stac
     if (p.depth_left == 0u) return tr;
     bool found = rt_closest_hit<Cfg>(sc, ns, p.ray, RT_R(0.001), RT_INF, p.rng, stk, tr.t, tr.prim, tr.scope);
     if (!found) { tr.prim = RT_NONE; return tr; }
-    uint32_t mk = RT_MAT_KINDF(ns.hot(tr.prim).mat) & 0xFFu; /* the node carries its material's kind word */
-    tr.cls = mk == RT_MAT_LAMBERTIAN ? RT_CLS_LAMBERT
-           : mk == RT_MAT_DIELECTRIC ? RT_CLS_DIELECTRIC
-           : mk == RT_MAT_METAL ? RT_CLS_METAL
-           : mk == RT_MAT_ISOTROPIC ? RT_CLS_OTHER : RT_CLS_TERMINAL;
+    if constexpr (Cfg::sweep && RtHitShape<typename Cfg::Topo>::trace) {
+        /* the class is a function of the leaf, so no load stands in front of the sort */
+        tr.cls = RtHitShape<typename Cfg::Topo>::cls(tr.prim);
+    } else {
+        uint32_t mk = RT_MAT_KINDF(ns.hot(tr.prim).mat) & 0xFFu; /* the node carries its material's kind word */
+        tr.cls = rt_class_of(mk);
+    }
+    /* the node's material word, which the second half wants for the material's index, where the wrapper was: the static hit record knows the chain */
+    if constexpr (Cfg::sweep && RtHitShape<typename Cfg::Topo>::carry) tr.scope = ns.hot(tr.prim).mat;
     return tr;
 }
 
@@ -1417,8 +1680,11 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
     }
     const double t = tr.t;
     const uint32_t prim = tr.prim, scope = tr.scope;
+    typedef RtHitShape<typename Cfg::Topo> HS;
     RtHit h;
-    rt_finish_hit<Cfg>(sc, p.ray, prim, scope, t, h);
+    if constexpr (Cfg::sweep && HS::carry) rt_finish_hit_static<Cfg>(sc, p.ray, prim, scope /* the node's material word: rt_path_trace */, t, h);
+    else if constexpr (Cfg::sweep && HS::record) rt_finish_hit_static<Cfg>(sc, p.ray, prim, sc.nodes[prim].mat, t, h);
+    else rt_finish_hit<Cfg>(sc, p.ray, prim, scope, t, h);
     RT_STAMP(3);
     const RtMaterial& m = sc.materials[RT_MAT_INDEX(h.mat)];
     uint32_t mk = RT_MAT_KINDF(h.mat) & 0xFFu;
@@ -1442,9 +1708,21 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
         typedef RtLightShape<typename Cfg::Topo> LS;
         typedef RtLambertWalls<typename Cfg::Topo> LW;
         /* an axis rect outside every wrapper: its frame is one of six constants (rt_wall_frame); every other path computes it */
-        const uint32_t pk = LW::walls ? sc.nodes[prim].kind & RT_KIND_MASK : (uint32_t)RT_NONE;
-        const bool wall = LW::walls && (!LW::general || (scope == RT_NONE && ((LW::xy && pk == RT_XY) || (LW::xz && pk == RT_XZ) || (LW::yz && pk == RT_YZ))));
-        RtOnb uvw = rt_wall_frame<LW>(pk, h.n);
+        bool wall, is_xz, is_xy;
+        if constexpr (Cfg::sweep && HS::walls) { /* which leaf it is says all three */
+            constexpr uint32_t WK = (LW::xy ? 1u << RT_XY : 0u) | (LW::xz ? 1u << RT_XZ : 0u) | (LW::yz ? 1u << RT_YZ : 0u);
+            wall = LW::walls && (!LW::general || HS::template in<WK, RT_HF_NONE, 0u, RT_HG_UNWRAPPED>(prim));
+            is_xz = HS::template in<1u << RT_XZ, RT_HF_NONE, 0u, RT_HG_ANY>(prim);
+            is_xy = HS::template in<1u << RT_XY, RT_HF_NONE, 0u, RT_HG_ANY>(prim);
+        } else {
+            const uint32_t pk = LW::walls ? sc.nodes[prim].kind & RT_KIND_MASK : (uint32_t)RT_NONE;
+            bool outside;
+            if constexpr (Cfg::sweep && HS::carry) outside = HS::template in<RT_HK_ALL, RT_HF_NONE, 0u, RT_HG_UNWRAPPED>(prim); /* `scope` carries the material word */
+            else outside = scope == RT_NONE;
+            wall = LW::walls && (!LW::general || (outside && ((LW::xy && pk == RT_XY) || (LW::xz && pk == RT_XZ) || (LW::yz && pk == RT_YZ))));
+            is_xz = pk == RT_XZ; is_xy = pk == RT_XY;
+        }
+        RtOnb uvw = rt_wall_frame<LW>(is_xz, is_xy, h.n);
         if (!LW::walls || (LW::general && RT_WAVE_ANY(!wall))) {
             RtOnb g = rt_onb_from_w(h.n);
             uvw = rt_onb_select(wall, uvw, g);

@@ -168,7 +168,9 @@ RT_HD uint32_t rt_frame_row(const RtFrame& f, uint32_t py) {
 /* `Topo_`: void, or a type with the scene's node kinds and subtree ends as compile-time arrays (rt_sweep_static) and, optionally,
  * `reuse[n][6]`: the box above it from which a BVH node takes a slab product (rt_aabb_hit_chain; absent = nothing is reused);
  * `n_lights`, `light_kind[]`: the kind word of every light, in order (RtLightShape; absent = the list is walked at run time);
- * `lambert_general`, `lambert_xy` / `_xz` / `_yz`: where Lambertian materials sit (RtLambertWalls; absent = every frame is computed) */
+ * `lambert_general`, `lambert_xy` / `_xz` / `_yz`: where Lambertian materials sit (RtLambertWalls; absent = every frame is computed);
+ * `wrap[n]`, `mat_kind[n]`: the wrapper above a node and the kind word of a leaf's material (RtHitShape; absent = the hit record reads the
+ * node and walks its chain at run time) */
 template <bool MEDIA_, bool TEX_, bool MSPHERE_, bool SWEEP_, int SCOPE_DEPTH_ = 3, class Topo_ = void, bool ORDERED_ = false>
 struct RtCfg {
     static constexpr bool ordered = ORDERED_; /* stack walk honours the opt-in near-far bits of BVH2 nodes (rt1w_scene_set_walk_order) */
