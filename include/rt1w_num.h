@@ -578,4 +578,104 @@ struct RtV3d { rt_f64 x, y, z; };
 RT_HD RtV3d rt_v3d(rt_f64 x, rt_f64 y, rt_f64 z) { RtV3d v; v.x = x; v.y = y; v.z = z; return v; }
 RT_HD RtV3d rt_v3d_add(RtV3d a, RtV3 b) { return rt_v3d(a.x + (rt_f64)b.x, a.y + (rt_f64)b.y, a.z + (rt_f64)b.z); }
 
+/* ---------------------------------- rounds of the rejection samplers, by position -- */
+/* The unit-sphere and unit-disk samplers (csrc/rt_core.h) draw candidates until one lies inside.  Their first 64-bit draw even-aligns
+ * the stream; from there a sphere round consumes exactly 6 words and a disk round exactly 4, so round r of either loop is a pure
+ * function of the stream's key and of the position the loop was entered at.  The functions below state that: where a stream stands,
+ * the candidate and the verdict of round r from there, and the generator state a lane that stops after round r is left with.  With
+ * them, lanes of a wave that have nothing to draw evaluate rounds r, r + 1, ... of a neighbour's loop at once (rt_core.h: the wave
+ * forms); the looped samplers stay the statement these are tested against (tests/test_wave_rounds.py).  Not for the reference-stream
+ * build, whose 64-bit draws do not align. */
+#if !defined(RT_RNG_REFSTREAM)
+/* the next word of the stream is word `off` (0..3) of block `blk`.  Two numbers, never a flat word index: that would wrap at 2^30 blocks */
+struct RtRngPos { uint32_t blk, off; };
+RT_HD RtRngPos rt_rng_pos(const RtRng& r) {
+    RtRngPos p;
+    p.blk = r.blk - r.bv - (r.left != 0u ? 1u : 0u); /* A's block when A holds words, else B's, else the next to generate */
+    p.off = (4u - r.left) & 3u;
+    return p;
+}
+/* where the next 64-bit draw starts (rt_take_u64's even-alignment) */
+RT_HD RtRngPos rt_rng_pos_even(const RtRng& r) {
+    RtRngPos p = rt_rng_pos(r);
+    p.off += p.off & 1u;
+    p.blk += p.off >> 2;
+    p.off &= 3u;
+    return p;
+}
+/* rt_take_pm1's statements on a 64-bit word already taken */
+RT_HD rt_f64 rt_pm1_from_bits(uint64_t q) {
+    const rt_f64 low = -1.0;
+    const rt_f64 scale = 1.0 - -1.0;
+    rt_f64 v12 = rt_u2d((q >> 12) | 0x3FF0000000000000ull);
+    return (v12 - 1.0) * scale + low;
+}
+/* One round: the candidate, the loop's own acceptance test on it, and what a stream that stops here keeps: `left` words (0 or 2) in
+ * a0, a1 -- the unconsumed tail of the round's last block -- with `blk` behind that block and B empty.  (The looped sampler may stop
+ * with a block held ahead in B instead; that changes no word anyone draws.) */
+struct RtRound { RtV3 v; uint32_t blk, left, a0, a1; bool accept; };
+#define RT_ROUND_Q(lo, hi) (((uint64_t)(hi) << 32) | (lo))
+/* rt_random_in_unit_sphere's round `round`, entered at the even position `start`: words [6 round, 6 round + 6) from there, which lie
+ * in two blocks whichever half of the first they begin in */
+RT_HD RtRound rt_sphere_round(uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2, uint32_t c3, RtRngPos start, uint32_t round) {
+    const uint32_t w = start.off + 6u * (round & 1u); /* two rounds are three blocks */
+    const uint32_t b = start.blk + 3u * (round >> 1) + (w >> 2);
+    const bool head = (w & 2u) == 0u; /* the round begins with its first block's word 0 */
+    const RtPhiloxOut A = rt_philox4x32_10(b, c1, c2, c3, k0, k1), B = rt_philox4x32_10(b + 1u, c1, c2, c3, k0, k1);
+    double x = rt_pm1_from_bits(head ? RT_ROUND_Q(A.w0, A.w1) : RT_ROUND_Q(A.w2, A.w3));
+    double y = rt_pm1_from_bits(head ? RT_ROUND_Q(A.w2, A.w3) : RT_ROUND_Q(B.w0, B.w1));
+    double z = rt_pm1_from_bits(head ? RT_ROUND_Q(B.w0, B.w1) : RT_ROUND_Q(B.w2, B.w3));
+    RtRound o;
+    o.v = rt_v3(x, y, z);
+    o.accept = rt_mag2(o.v) < RT_R(1.0);
+    o.blk = b + 2u; o.left = head ? 2u : 0u; o.a0 = B.w2; o.a1 = B.w3;
+    return o;
+}
+/* rt_random_in_unit_disk's round `round`: words [4 round, 4 round + 4); one block where the loop was entered at a block's word 0 */
+RT_HD RtRound rt_disk_round(uint32_t k0, uint32_t k1, uint32_t c1, uint32_t c2, uint32_t c3, RtRngPos start, uint32_t round) {
+    const uint32_t b = start.blk + round;
+    const bool head = start.off == 0u;
+    const RtPhiloxOut A = rt_philox4x32_10(b, c1, c2, c3, k0, k1);
+    RtPhiloxOut B = A;
+    if (!head) B = rt_philox4x32_10(b + 1u, c1, c2, c3, k0, k1);
+    double x = rt_pm1_from_bits(head ? RT_ROUND_Q(A.w0, A.w1) : RT_ROUND_Q(A.w2, A.w3));
+    double y = rt_pm1_from_bits(head ? RT_ROUND_Q(A.w2, A.w3) : RT_ROUND_Q(B.w0, B.w1));
+    RtRound o;
+    o.v = rt_v3(x, y, RT_R(0.0));
+    o.accept = rt_mag2(o.v) < RT_R(1.0);
+    o.blk = head ? b + 1u : b + 2u; o.left = head ? 0u : 2u; o.a0 = B.w2; o.a1 = B.w3;
+    return o;
+}
+#undef RT_ROUND_Q
+/* a stream that stops after the round `o` */
+RT_HD void rt_rng_after_round(RtRng& r, const RtRound& o) {
+    r.blk = o.blk; r.left = o.left; r.a0 = o.a0; r.a1 = o.a1; r.bv = 0u;
+}
+
+/* Who computes what when the K = 2^k_log2 rounds base .. base + K - 1 of each of `wanting` loops are spread over the lanes of a
+ * wave: helper j (its rank among the lanes that take part) serves loop j / K (the loops in the order of their lanes), round
+ * base + j % K.  One text for the kernels and for the tests' wave emulation. */
+/* K: as many rounds per loop as there are helpers for, a power of two (so that j / K is a shift), `cap` at the most */
+RT_HD uint32_t rt_wave_rounds_log2(uint32_t helpers, uint32_t wanting, uint32_t cap) {
+    uint32_t k = 0u;
+    while ((2u << k) <= cap && (2u << k) * wanting <= helpers) ++k;
+    return k;
+}
+struct RtWaveSlot { uint32_t loop, round; bool valid; };
+RT_HD RtWaveSlot rt_wave_slot(uint32_t j, uint32_t k_log2, uint32_t wanting, uint32_t base) {
+    RtWaveSlot s;
+    s.loop = j >> k_log2;
+    s.round = base + (j & ((1u << k_log2) - 1u));
+    s.valid = s.loop < wanting;
+    return s;
+}
+/* the helper whose round loop `loop` stops at: the first of its K that accepted (bit j of `accepted`: helper j's verdict, valid
+ * helpers only), or 64 when none did and the loop goes on from base + K */
+RT_HD uint32_t rt_wave_first(uint64_t accepted, uint32_t loop, uint32_t k_log2) {
+    const uint32_t first = loop << k_log2;
+    const uint64_t m = (accepted >> first) & ((1ull << (1u << k_log2)) - 1ull);
+    return m != 0ull ? first + (uint32_t)__builtin_ctzll(m) : 64u;
+}
+#endif /* !RT_RNG_REFSTREAM */
+
 #endif /* RT1W_NUM_H */

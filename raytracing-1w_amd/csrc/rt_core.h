@@ -1159,6 +1159,85 @@ RT_HD RtV3 rt_random_in_unit_disk(RtRng& rng) {
         if (rt_mag2(p) < RT_R(1.0)) return p;
     }
 }
+/* ---- the two rejection samplers, a wave at a time ----
+ * A wave pays every round of these loops in full while any one of its lanes is still rejecting: with 14 Metal lanes in a wave the
+ * sphere loop runs 4.6 times where a lane needs 1.9 rounds, and each round generates up to two Philox blocks for a handful of
+ * lanes.  Round r of a loop is a function of the stream's key and of where the loop was entered (include/rt1w_num.h:
+ * rt_sphere_round / rt_disk_round), so here the lanes of the wave that want nothing evaluate further rounds of the loops of those
+ * that do: K rounds of every loop in one pass, each loop stopping at its first accepted round -- the words, the values and the
+ * stream position of the looped sampler, in fewer passes.  Every lane of the wave calls the function, `want` says whether it samples.
+ *   K = the largest power of two with K <= RT_WAVE_ROUNDS_CAP and K x (lanes that want) <= 64, chosen anew for every pass; where
+ * most of the wave wants a sample K is 1 and every lane takes its own loop's next round, nothing travels.  Otherwise the lanes find
+ * each other with a ballot and mbcnt, and the key, the position and the accepted round travel by ds_permute / ds_bpermute: no LDS is
+ * allocated.  Those instructions read nothing from a lane that is switched off, so a wave that is not whole here (the last passes of
+ * a frame, where lanes have retired) keeps K = 1.  The stream is touched once, when its loop stops (rt_rng_after_round).
+ * Device code of the f64 reordering kernels only (rt_kernel_sorted.h), where a wave mostly holds one class of paths and the others
+ * are idle in these loops.  Parts (RT1W_JIT_EXTRA_OPTS=-DRT_WAVE_ROUNDS=k builds any mix of them into the kernels compiled at run
+ * time, 0 the loops; every mix gives the same bits).  Measured on the Cornell kernel, ms per launch at 600x600x1000
+ * (profiles/wave_rounds_bench.json): none 111.3; 1: 106.2; 2: 121.3; both: 115.8 -- the camera's loop is short (1.27 rounds a lane), most
+ * of a regenerating wave wants a sample, and the hand-over costs more than the passes it saves: it stays behind the switch.
+ *   1  the unit sphere of the Metal scatter (rt_path_shade_wave)      2  the unit disk of the camera ray (rt_path_begin_wave)
+ * The cap on K, with part 1: 2: 110.6; 4: 106.8; 8: 106.3; 16: 106.3. */
+#ifndef RT_WAVE_ROUNDS
+#define RT_WAVE_ROUNDS 1
+#endif
+#ifndef RT_WAVE_ROUNDS_CAP
+#define RT_WAVE_ROUNDS_CAP 8u
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_RNG_REFSTREAM) && !defined(RT_F32)
+#define RT_WAVE_ROUNDS_ON (RT_WAVE_ROUNDS)
+template <bool SPHERE>
+__device__ __forceinline__ RtV3 rt_wave_rounds(RtRng& rng, bool want) {
+    RtV3 out = rt_v3(RT_R(0.0), RT_R(0.0), RT_R(0.0));
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const bool whole = __ballot(1) == ~0ull;
+    const RtRngPos start = rt_rng_pos_even(rng);
+#define RT_FROM(l, v) ((uint32_t)__builtin_amdgcn_ds_bpermute((l), (int)(v)))
+    for (uint32_t base = 0u;;) {
+        const unsigned long long wm = __ballot(want);
+        if (wm == 0ull) break;
+        const uint32_t nw = (uint32_t)__popcll(wm);
+        const uint32_t kl = whole ? rt_wave_rounds_log2(64u, nw, RT_WAVE_ROUNDS_CAP) : 0u;
+        const uint32_t wr = __builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u));
+        /* K = 1: every lane that wants takes its own loop's round `base` */
+        uint32_t k0 = rng.k0, k1 = rng.k1, c1 = rng.c1, c2 = rng.c2, c3 = rng.c3, round = base;
+        RtRngPos from = start;
+        bool valid = want;
+        if (kl != 0u) {
+            /* lane q of `tab`: the q-th lane that wants a sample (behind those, the others: every lane is written once) */
+            const uint32_t nr = __builtin_amdgcn_mbcnt_hi((uint32_t)(~wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)~wm, 0u));
+            const uint32_t tab = (uint32_t)__builtin_amdgcn_ds_permute((int)((want ? wr : nw + nr) << 2), (int)lane);
+            const RtWaveSlot s = rt_wave_slot(lane, kl, nw, base);
+            const int src = (int)(RT_FROM((int)(s.loop << 2), tab) << 2);
+            k0 = RT_FROM(src, rng.k0); k1 = RT_FROM(src, rng.k1); c1 = RT_FROM(src, rng.c1); c2 = RT_FROM(src, rng.c2); c3 = RT_FROM(src, rng.c3);
+            from.blk = RT_FROM(src, start.blk); from.off = RT_FROM(src, start.off);
+            round = s.round; valid = s.valid;
+        }
+        RtRound o;
+        if (SPHERE) o = rt_sphere_round(k0, k1, c1, c2, c3, from, round);
+        else o = rt_disk_round(k0, k1, c1, c2, c3, from, round);
+        bool got = want && o.accept;
+        if (kl != 0u) { /* every loop stops at the first of its K rounds that accepted, and fetches it */
+            const unsigned long long accepted = __ballot(valid && o.accept);
+            const uint32_t first = rt_wave_first(accepted, want ? wr : 0u, kl);
+            got = want && first < 64u;
+            const int win = (int)((got ? first : lane) << 2);
+            const uint64_t ux = rt_d2u(o.v.x), uy = rt_d2u(o.v.y), uz = rt_d2u(o.v.z);
+            o.v.x = rt_u2d(((uint64_t)RT_FROM(win, (uint32_t)(ux >> 32)) << 32) | RT_FROM(win, (uint32_t)ux));
+            o.v.y = rt_u2d(((uint64_t)RT_FROM(win, (uint32_t)(uy >> 32)) << 32) | RT_FROM(win, (uint32_t)uy));
+            if (SPHERE) o.v.z = rt_u2d(((uint64_t)RT_FROM(win, (uint32_t)(uz >> 32)) << 32) | RT_FROM(win, (uint32_t)uz));
+            o.blk = RT_FROM(win, o.blk); o.left = RT_FROM(win, o.left); o.a0 = RT_FROM(win, o.a0); o.a1 = RT_FROM(win, o.a1);
+        }
+        if (got) { out = o.v; rt_rng_after_round(rng, o); want = false; }
+        base += 1u << kl;
+    }
+#undef RT_FROM
+    return out;
+}
+#else
+#define RT_WAVE_ROUNDS_ON 0
+#endif
+
 /* math.rs:39-49 (caller has reserved two 64-bit draws) */
 RT_HD RtV3 rt_random_cosine_direction(RtRng& rng) {
     double r1 = rt_take_f64(rng);
@@ -1368,6 +1447,32 @@ RT_HD void rt_path_begin_cam(const RtCamera& c, const RtFrame& f, uint32_t i, ui
     p.depth_left = f.max_depth;
     p.alive = true;
 }
+#if RT_WAVE_ROUNDS_ON
+/* rt_path_begin_cam for the lanes of a wave that `begin` a path, called by every lane of the wave: its statements, with the unit
+ * disk's rounds spread over the lanes that begin nothing (rt_wave_rounds) */
+__device__ __forceinline__ void rt_path_begin_wave(const RtCamera& c, const RtFrame& f, uint32_t i, uint32_t j, uint32_t sample, RtPath& p, bool begin) {
+    double u = RT_R(0.0), v = RT_R(0.0);
+    if (begin) {
+        p.rng = rt_rng_pixel_sample((uint64_t)j * f.width + i, sample, f.global_seed);
+        rt_rng_reserve(p.rng, 4u);
+        u = ((double)i + rt_take_f64(p.rng)) / (double)(f.width - 1u);
+        v = ((double)j + rt_take_f64(p.rng)) / (double)(f.height - 1u);
+    }
+    const RtV3 disk = rt_wave_rounds<false>(p.rng, begin);
+    if (begin) {
+        RtV3 rd = c.lens_radius * disk;
+        RtV3 offset = c.u * rd.x + c.v * rd.y;
+        p.ray.o = c.origin + offset;
+        p.ray.d = c.lower_left_corner + u * c.horizontal + v * c.vertical - c.origin - offset;
+        rt_rng_reserve(p.rng, rt_rng_need_u64(p.rng));
+        p.ray.time = rt_take_range(p.rng, c.time0, c.time1);
+        p.beta = rt_v3(RT_R(1.0), RT_R(1.0), RT_R(1.0));
+        p.radiance = rt_v3(RT_R(0.0), RT_R(0.0), RT_R(0.0));
+        p.depth_left = f.max_depth;
+        p.alive = true;
+    }
+}
+#endif
 
 /* ------------------------------------------------------------ integrator -- */
 
@@ -1666,8 +1771,13 @@ RT_HD RtTrace rt_path_trace(const RtSceneView& sc, const NS& ns, RtPath& p, Stac
  * beta = beta (.) W / pdf.  Every terminal adds beta (.) value -- including the zero
  * of depth exhaustion (main.rs:59-61) -- so a non-finite beta poisons the sample
  * exactly as it does through the reference's multiplications. */
-template <class Cfg>
-RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
+/* `later`: by default the Metal scatter draws its unit-sphere sample where it stands.  Given an RtSphereLater, the lane only says
+ * that it wants one, keeps the fuzz and parks the reflected direction in p.ray.d: the sample is then drawn by the whole wave behind
+ * the other materials (rt_path_shade_wave). */
+struct RtSphereNow {};
+struct RtSphereLater { bool* want; double* fuzz; };
+template <class Cfg, class Sphere = RtSphereNow>
+RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr, Sphere later = Sphere()) {
     if (p.depth_left == 0u) {
         p.radiance = p.radiance + rt_mul(p.beta, rt_v3(RT_R(0.0), RT_R(0.0), RT_R(0.0)));
         p.alive = false;
@@ -1801,7 +1911,9 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
     } else if (mk == RT_MAT_METAL) {
         /* Metal::scatter material.rs:99-111 */
         RtV3 reflected = rt_reflect(rt_normalize(p.ray.d), h.n);
-        RtV3 dir = reflected + m.d[3] * rt_random_in_unit_sphere(p.rng);
+        RtV3 dir;
+        if constexpr (std::is_same<Sphere, RtSphereLater>::value) { *later.want = true; *later.fuzz = m.d[3]; dir = reflected; }
+        else dir = reflected + m.d[3] * rt_random_in_unit_sphere(p.rng);
         p.beta = rt_mul(p.beta, rt_v3(m.d[0], m.d[1], m.d[2]));
         p.ray.o = h.p; p.ray.d = dir;
     } else if (mk == RT_MAT_DIELECTRIC) {
@@ -1833,6 +1945,23 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
     p.depth_left -= 1u;
     RT_STAMP(5);
 }
+#if RT_WAVE_ROUNDS_ON
+/* rt_path_shade for the reordering kernels, called by every lane of the region: materials exclude each other per lane, so the Metal
+ * lanes' sample can come last, behind a wave-uniform test, where the lanes of every other material -- and those whose path just ended
+ * -- take rounds of it (rt_wave_rounds) and the sample is live across no other branch.  dir = reflected + fuzz * sample, as above. */
+template <class Cfg>
+__device__ __forceinline__ void rt_path_shade_wave(const RtSceneView& sc, RtPath& p, const RtTrace& tr) {
+    bool sphere = false;
+    double fuzz = RT_R(0.0);
+    RtSphereLater later;
+    later.want = &sphere; later.fuzz = &fuzz;
+    rt_path_shade<Cfg>(sc, p, tr, later);
+    if (RT_WAVE_ANY(sphere)) {
+        const RtV3 v = rt_wave_rounds<true>(p.rng, sphere);
+        if (sphere) p.ray.d = p.ray.d + fuzz * v;
+    }
+}
+#endif
 
 /* One level of ray_color (main.rs:51-116; with no lights :118-190) */
 template <class Cfg, class Stack, class NS>

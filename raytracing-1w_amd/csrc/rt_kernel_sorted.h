@@ -202,6 +202,7 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
     for (;;) {
         RT_STAMP(6);
         /* 1. regeneration: next sample of the lane's item, or a new item */
+        bool begin = false;
         if (!path.alive && !retired) {
             uint32_t s_end = chunk * f.chunk + f.chunk < f.spp ? chunk * f.chunk + f.chunk : f.spp;
             if (have && s == s_end) {
@@ -230,8 +231,13 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
                 }
             }
             if (!have) retired = true;
+            else if (RT_WAVE_ROUNDS_ON & 2) begin = true;
             else rt_path_begin(sc, f, RT_ITEM_BEGIN_ARGS, path);
         }
+#if RT_WAVE_ROUNDS_ON & 2
+        /* every lane of the wave is here, so those that begin nothing take rounds of the lens sample (rt_core.h: rt_wave_rounds) */
+        if (RT_WAVE_ANY(begin)) rt_path_begin_wave(sc.camera, f, RT_ITEM_BEGIN_ARGS, path, begin);
+#endif
         RT_STAMP(1);
         /* 2. closest hit + class */
         RtTrace tr;
@@ -319,7 +325,11 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
 #if !RT_SORTED_CARRY_RADIANCE
             path.radiance = rt_v3(RT_R(0.0), RT_R(0.0), RT_R(0.0));
 #endif
+#if RT_WAVE_ROUNDS_ON & 1
+            rt_path_shade_wave<Cfg>(sc, path, tr);
+#else
             rt_path_shade<Cfg>(sc, path, tr);
+#endif
             if (!path.alive) {
                 sum = rt_v3d_add(sum, path.radiance); /* pixel_color += ray_color(..), main.rs:972-989 */
 #if RT_SORTED_CARRY_RADIANCE
