@@ -937,6 +937,8 @@ uint32_t rt1w_abi_sizeof(int what);
  * fn 0 a/b, 1 sqrt|a|, 2 sin a, 3 cos a, 4 acos(a/(|a|+1)), 5 atan2(a,b), 6 log|b|,
  * 7 first gen_f64 of stream (pixel=i, sample=(uint32)a_bits), 8 gen_range(-1,1) of same;
  * 11, 12 the same two of stream (pixel=b_bits, sample=(uint32)a_bits), 13 that gen_range as reserve + rt_take_pm1.
+ * 14 a/b from b's prepared divisor (rt_div_q), 15 its guards (1 divisor out of range | 2 quotient bad if used | 4 quotient too large),
+ * 16 1/b from the prepared divisor (rt_div_inv).
  * Used by the GPU tests to prove host/device bit equality. */
 int rt1w_debug_eval(rt1w_context* c, int fn, const double* a, const double* b, double* out, uint64_t n);
 /* AABB::hit (src/aabb.rs:13-32) ON THE DEVICE for n cases, in[i] = {min[3], max[3], origin[3], direction[3], t_min, t_max}:

@@ -94,6 +94,49 @@ RT_HD double rt_floor(double x) { return (double)rt_floor64((rt_f64)x); } /* exa
 RT_HD double rt_floor(double x) { return rt_floor64(x); }
 #endif
 
+/* -------------------------------------------- quotients of one divisor -- */
+
+/* `n / d` in f64 on gfx9 is eleven instructions: div_scale(d), rcp, four fma (two Newton steps: they give y ~ 1/d and depend on d
+ * only), div_scale(n), q = n * y, r = fma(-d, q, n), div_fmas(r, y, q), div_fixup (docs/LAB_NOTES.md has the listing).  Where
+ * div_scale leaves both operands alone and div_fixup passes its first operand through, the last three are plain arithmetic, so
+ * several quotients of one divisor can share y: rt_div_refine is the first half (from the seed the rcp instruction returns),
+ * rt_div_q the second, on the same values in the same order -- the same bits as `/`.  That holds for operands and results of
+ * moderate size only; the two predicates below say when, and a caller that sees one fail computes `n / d` with `/` instead
+ * (rt_core.h: the unrolled sweep).  With |d| and |t| strictly between the bounds, |n| is within 2^-601 ... 2^601: no operand is
+ * scaled (that takes |d| beyond 2^+-1022, |n| below 2^-969 or exponents 768 apart), y and q are normal, and div_fixup has no
+ * zero, infinity, NaN or overflow to patch.  `y` itself is NOT the correctly rounded 1/d and must not be replaced by it.
+ * Not for the f32 build (its divisions are not this sequence). */
+#if !defined(RT_F32)
+#define RT_DIV_LO 0x1p-300
+#define RT_DIV_HI 0x1p+300
+RT_HD double rt_div_refine(double d, double y0) {
+    double e = __builtin_fma(-d, y0, 1.0);
+    const double y1 = __builtin_fma(y0, e, y0);
+    e = __builtin_fma(-d, y1, 1.0);
+    return __builtin_fma(y1, e, y1);
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+RT_HD double rt_div_prep(double d) { return rt_div_refine(d, __builtin_amdgcn_rcp(d)); } /* v_rcp_f64: the seed the division itself starts from */
+#endif
+RT_HD bool rt_div_d_ok(double d) { const double a = __builtin_fabs(d); return (a > RT_DIV_LO) & (a < RT_DIV_HI); }
+/* 1 / d: the sequence's last steps with n = 1 (q = 1 * y is y) */
+RT_HD double rt_div_inv(double d, double y) { return __builtin_fma(__builtin_fma(-d, y, 1.0), y, y); }
+RT_HD double rt_div_q(double n, double d, double y) {
+    const double q = n * y;
+    return __builtin_fma(__builtin_fma(-d, q, n), y, q);
+}
+/* Is the quotient rt_div_q returned for a good divisor NOT to be trusted?  Too large, infinite or NaN (rt_div_q_big): always.  Zero or
+ * tiny (an exact zero's sign is not div_fixup's, and a tiny numerator is scaled): only where the caller would `use` it -- a ray that
+ * starts on the plane of a rect has n == 0 on every segment and is turned away by t_min, which the division's value fails alike
+ * (it is below 2 * RT_DIV_LO as well).  A caller that uses a quotient only if it is >= a t_min that rt_div_tmin_ok accepts need
+ * not look at the lower bound at all: for it rt_div_q_bad is rt_div_q_big.  That is the unrolled sweep's case: it calls rt_div_tmin_ok
+ * once and rt_div_q_big per quotient, never rt_div_q_bad, which is the guard in its general form -- the statement the two others are
+ * tested against (tests/test_div_shared.py: test_a_rect_need_not_look_at_the_lower_bound; rt1w_debug_eval 15 on the device). */
+RT_HD bool rt_div_q_big(double t) { return !(__builtin_fabs(t) < RT_DIV_HI); }
+RT_HD bool rt_div_q_bad(double t, bool use) { return rt_div_q_big(t) | (use & !(__builtin_fabs(t) > RT_DIV_LO)); }
+RT_HD bool rt_div_tmin_ok(double t_min) { return t_min > 2.0 * RT_DIV_LO; }
+#endif
+
 /* --------------------------------------------------------- Philox4x32-10 -- */
 
 struct RtPhiloxOut { uint32_t w0, w1, w2, w3; };

@@ -80,6 +80,14 @@ __global__ void rt_debug_eval_kernel(int fn, const double* a, const double* b, d
         case 12: { RtRng g = rt_rng_pixel_sample(rt_d2u(y), (uint32_t)rt_d2u(x), 0u); (void)rt_gen_f64(g); r = rt_gen_range(g, -1.0, 1.0); } break;
         case 13: { RtRng g = rt_rng_pixel_sample(rt_d2u(y), (uint32_t)rt_d2u(x), 0u); (void)rt_gen_f64(g);
                    rt_rng_reserve(g, rt_rng_need_u64(g)); r = rt_take_pm1(g); } break;
+#if defined(__HIP_DEVICE_COMPILE__)
+        /* quotients of one divisor (rt1w_num.h): 14 the quotient x / y from the prepared divisor, 15 what the guards say of it (1 the
+         * divisor is out of range, 2 the quotient is if it were used, 4 it is too large to be trusted at all), 16 the slab tests' 1 / y */
+        case 14: r = rt_div_q(x, y, rt_div_prep(y)); break;
+        case 15: { const double t = rt_div_q(x, y, rt_div_prep(y));
+                   r = (double)((rt_div_d_ok(y) ? 0 : 1) | (rt_div_q_bad(t, true) ? 2 : 0) | (rt_div_q_big(t) ? 4 : 0)); } break;
+        case 16: r = rt_div_inv(y, rt_div_prep(y)); break;
+#endif
         default: break;
     }
     out[i] = r;

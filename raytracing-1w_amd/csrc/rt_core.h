@@ -336,17 +336,20 @@ RT_HD void rt_finish_hit(const RtSceneView& sc, const RtRay& world, uint32_t pri
 
 /* static sphere and the three rects, from the hot half of the record (same operations as
  * rt_prim_t).  `kind` is wave-uniform in the sweep, so the axis choice is a scalar branch. */
+RT_HD bool rt_rect_hot_at(const RtNodeHot& nd, double t, bool in_t, double ob, double db, double oc, double dc, double& t_out) {
+    const double b = ob + t * db;
+    const double c = oc + t * dc;
+    const bool in_rect = !((b < nd.d[0]) | (b > nd.d[1]) | (c < nd.d[2]) | (c > nd.d[3]));
+    if (in_t & in_rect) { t_out = t; return true; }
+    return false;
+}
 RT_HD bool rt_rect_hot_t(const RtNodeHot& nd, double oa, double da, double ob, double db, double oc, double dc,
                          double t_min, double t_max, double& t_out) {
     /* both of aarect.rs' rejections as one conjunction (no exec-mask region for the second half: the wave runs it
      * anyway unless every lane fails the first); a NaN passes each comparison exactly as it does there */
     const double t = (nd.d[4] - oa) / da;
     const bool in_t = !((t < t_min) | (t > t_max));
-    const double b = ob + t * db;
-    const double c = oc + t * dc;
-    const bool in_rect = !((b < nd.d[0]) | (b > nd.d[1]) | (c < nd.d[2]) | (c > nd.d[3]));
-    if (in_t & in_rect) { t_out = t; return true; }
-    return false;
+    return rt_rect_hot_at(nd, t, in_t, ob, db, oc, dc, t_out);
 }
 RT_HD bool rt_prim_hot_t(const RtNodeHot& nd, uint32_t kind, RtV3 o, RtV3 d, double t_min, double t_max, double& t_out) {
     if (kind == RT_XY) return rt_rect_hot_t(nd, o.z, d.z, o.x, d.x, o.y, d.y, t_min, t_max, t_out);
@@ -402,6 +405,67 @@ template <class NS> RT_HD uint32_t rt_ns_wrap_id(uint32_t e, const RtNodeHot& nd
 /* ----------------------------------------------------------- traversal -- */
 
 RT_HD RtV3 rt_inv3(RtV3 d) { return rt_v3(RT_R(1.0) / d.x, RT_R(1.0) / d.y, RT_R(1.0) / d.z); }
+
+/* What the unrolled sweep knows about 1 / direction in one ray space: the three reciprocals (`inv`, a plain RtV3), or those and the
+ * prepared divisors y of include/rt1w_num.h ("quotients of one divisor") from which they were made.  A rect's t = (k - o_a) / d_a
+ * is then three instructions on y_a instead of a division, and the two Newton steps run once per axis and ray space instead of
+ * once per quotient (Cornell: 18 divisions of the sweep share 6 divisors).  Speculate, then verify: every divisor and every quotient
+ * that leaves the range where that is `/` bit for bit sets its lane in `bad`, a wave mask in scalar registers, and rt_closest_hit
+ * runs the sweep again with `/` for a wave that has one.  f64 device code of the media-free specialised units only (in a
+ * ConstantMedium's boundary sweeps t_min is -inf or NaN and a zero quotient can be accepted); everything else keeps `/`.
+ * RT_DIV_SHARED: bit 1 the prepared divisors and the reciprocals made from them, bit 2 the rects' quotients (2 alone is 3); default 3.
+ * RT1W_JIT_EXTRA_OPTS=-DRT_DIV_SHARED=0: the text without any of it.  -DRT_DIV_SHARED_FORCE_SLOW=1 (tests): every wave sweeps twice. */
+#undef RT_DIV_SHARED_ON /* (a unit may take this header twice: f64 records, then the f32 build) */
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_F32)
+#ifndef RT_DIV_SHARED
+#define RT_DIV_SHARED 3
+#endif
+#define RT_DIV_SHARED_ON (RT_DIV_SHARED)
+#else
+#define RT_DIV_SHARED_ON 0
+#endif
+#ifndef RT_DIV_SHARED_FORCE_SLOW
+#define RT_DIV_SHARED_FORCE_SLOW 0
+#endif
+template <class Inv> struct RtInvIsShared { static constexpr bool value = false; };
+RT_HD const RtV3& rt_inv_of(const RtV3& inv) { return inv; }
+RT_HD RtV3 rt_inv_again(const RtV3&, RtV3 d, bool) { return rt_inv3(d); } /* the next ray space (below a RotateY) */
+#if RT_DIV_SHARED_ON
+struct RtInvShared {
+    RtV3 inv, y;
+    uint64_t& bad;
+};
+template <> struct RtInvIsShared<RtInvShared> { static constexpr bool value = true; };
+RT_HD const RtV3& rt_inv_of(const RtInvShared& s) { return s.inv; }
+/* `act`: the lanes whose ray this is (the others' directions are whatever they hold and must not send the wave to the slow sweep) */
+RT_HD RtInvShared rt_inv3_shared(RtV3 d, bool act, uint64_t& bad) {
+    const RtV3 y = rt_v3(rt_div_prep(d.x), rt_div_prep(d.y), rt_div_prep(d.z));
+    bad |= __builtin_amdgcn_ballot_w64(act & !(rt_div_d_ok(d.x) & rt_div_d_ok(d.y) & rt_div_d_ok(d.z)));
+    return RtInvShared{rt_v3(rt_div_inv(d.x, y.x), rt_div_inv(d.y, y.y), rt_div_inv(d.z, y.z)), y, bad};
+}
+/* a scene without a rect has no quotient to share with the box tests' reciprocals: its unit keeps one sweep, with `/` */
+template <class Topo>
+constexpr bool rt_topo_has_rect() {
+    for (uint32_t i = 0; i < sizeof(Topo::kind) / sizeof(Topo::kind[0]); ++i)
+        if ((Topo::kind[i] & RT_KIND_MASK) >= RT_XY && (Topo::kind[i] & RT_KIND_MASK) <= RT_YZ) return true;
+    return false;
+}
+RT_HD RtInvShared rt_inv_again(const RtInvShared& s, RtV3 d, bool act) { return rt_inv3_shared(d, act, s.bad); }
+/* rt_rect_hot_t with the quotient from the prepared divisor of its axis.  Every lane of the wave computes, `act` says whose verdict
+ * counts: the range test is then one compare straight into the wave mask (taken under `if (act)` it would be a per-lane value that
+ * has to be collected again), and a lane that is elsewhere in the tree tests its own, real ray -- at worst a sweep too many.
+ * rt_closest_hit has made sure of t_min (rt_div_tmin_ok), so a quotient that passes it is above the lower bound as well. */
+RT_HD bool rt_rect_hot_t(const RtNodeHot& nd, uint32_t kind, RtV3 o, RtV3 d, const RtInvShared& s, bool act, double t_min, double t_max, double& t_out) {
+    const double oa = kind == RT_XY ? o.z : (kind == RT_XZ ? o.y : o.x), da = kind == RT_XY ? d.z : (kind == RT_XZ ? d.y : d.x);
+    const double ya = kind == RT_XY ? s.y.z : (kind == RT_XZ ? s.y.y : s.y.x);
+    const double t = rt_div_q(nd.d[4] - oa, da, ya);
+    s.bad |= __builtin_amdgcn_ballot_w64(rt_div_q_big(t));
+    const bool in_t = act & !((t < t_min) | (t > t_max));
+    if (kind == RT_XY) return rt_rect_hot_at(nd, t, in_t, o.x, d.x, o.y, d.y, t_out);
+    if (kind == RT_XZ) return rt_rect_hot_at(nd, t, in_t, o.x, d.x, o.z, d.z, t_out);
+    return rt_rect_hot_at(nd, t, in_t, o.y, d.y, o.z, d.z, t_out);
+}
+#endif
 
 /* ConstantMedium::hit constant_medium.rs:58-113, given the two boundary roots t1, t2 */
 RT_HD bool rt_medium_t(double neg_inv_density, RtV3 d, double t1, double t2, double t_min, double t_max, RtRng& rng,
@@ -957,8 +1021,8 @@ RT_HD bool rt_aabb_hit_chain(const double* bb, RtV3 o, RtV3 inv, double t_min, d
  * No lane keeps a node index here: "the lane is at node J" is "the lane passed the box test of every BVH node above J", and after a
  * subtree every lane that entered it stands at its end -- so `act` goes down the recursion, a BVH node's children get `act && hit`,
  * and what follows the subtree gets `act` again.  `up` is the chain of slab frames of the BVH nodes above I in this ray space. */
-template <class Topo, class Cfg, bool MEDIA, uint32_t I, uint32_t END, class Up, class NS>
-RT_HD void rt_sweep_static(const RtSceneView& sc, const NS& ns, const RtRayOD& ray, const RtV3& inv, double time, double t_min,
+template <class Topo, class Cfg, bool MEDIA, uint32_t I, uint32_t END, class Up, class NS, class Inv>
+RT_HD void rt_sweep_static(const RtSceneView& sc, const NS& ns, const RtRayOD& ray, const Inv& inv, double time, double t_min,
                            bool tmin_nan, RtRng& rng, const bool act, const Up& up, double& best_t, uint32_t& best_prim) {
     if constexpr (I < END) {
         constexpr uint32_t kind = Topo::kind[I] & RT_KIND_MASK;
@@ -969,8 +1033,8 @@ RT_HD void rt_sweep_static(const RtSceneView& sc, const NS& ns, const RtRayOD& r
                 RtSlabFrame<I, Up> fr(up);
                 bool hit = false;
                 if (act) {
-                    if (RT_WAVE_ANY(tmin_nan || rt_isnan(best_t))) { RT_STAT_SLAB(1); hit = rt_aabb_hit_chain<Topo, I, true, false>(nd.d, ray.o, inv, t_min, best_t, fr); }
-                    else { RT_STAT_SLAB(0); hit = rt_aabb_hit_chain<Topo, I, false, Cfg::media>(nd.d, ray.o, inv, t_min, best_t, fr); }
+                    if (RT_WAVE_ANY(tmin_nan || rt_isnan(best_t))) { RT_STAT_SLAB(1); hit = rt_aabb_hit_chain<Topo, I, true, false>(nd.d, ray.o, rt_inv_of(inv), t_min, best_t, fr); }
+                    else { RT_STAT_SLAB(0); hit = rt_aabb_hit_chain<Topo, I, false, Cfg::media>(nd.d, ray.o, rt_inv_of(inv), t_min, best_t, fr); }
                 }
                 rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, ray, inv, time, t_min, tmin_nan, rng, act && hit, fr, best_t, best_prim);
             }
@@ -978,7 +1042,10 @@ RT_HD void rt_sweep_static(const RtSceneView& sc, const NS& ns, const RtRayOD& r
         } else if constexpr (kind <= RT_YZ) {
             if (RT_WAVE_ANY(act)) {
                 const RtNodeHot nd = ns.hot(I);
-                if (act) {
+                if constexpr (RtInvIsShared<Inv>::value && (RT_DIV_SHARED_ON & 2) != 0 && kind >= RT_XY) {
+                    double t;
+                    if (rt_rect_hot_t(nd, kind, ray.o, ray.d, inv, act, t_min, best_t, t)) { best_t = t; best_prim = I; }
+                } else if (act) {
                     double t;
                     bool hit;
                     if constexpr (Cfg::msphere && kind == RT_MSPHERE) hit = rt_prim_t<Cfg>(sc.nodes[I], kind, ray.o, ray.d, time, t_min, best_t, t);
@@ -997,7 +1064,7 @@ RT_HD void rt_sweep_static(const RtSceneView& sc, const NS& ns, const RtRayOD& r
                     const RtRayOD inner = rt_scope_in(nd, ray);
                     const RtSlabNone none;
                     if constexpr (kind == RT_ROTATE_Y) {
-                        const RtV3 inv_inner = rt_inv3(inner.d);
+                        const Inv inv_inner = rt_inv_again(inv, inner.d, act);
                         rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, inner, inv_inner, time, t_min, tmin_nan, rng, act, none, best_t, best_prim);
                     } else {
                         rt_sweep_static<Topo, Cfg, MEDIA, I + 1u, skip>(sc, ns, inner, inv, time, t_min, tmin_nan, rng, act, none, best_t, best_prim);
@@ -1036,10 +1103,30 @@ RT_HD bool rt_closest_hit(const RtSceneView& sc, const NS& ns, const RtRay& ray,
     if constexpr (Cfg::sweep && !std::is_void<typename Cfg::Topo>::value) {
         typedef typename Cfg::Topo Topo;
         RtRayOD w; w.o = ray.o; w.d = ray.d;
-        const RtV3 inv = rt_inv3(w.d);
         const RtSlabNone none;
         t = t_max; prim = RT_NONE;
-        rt_sweep_static<Topo, Cfg, true, Topo::root, Topo::skip[Topo::root]>(sc, ns, w, inv, ray.time, t_min, rt_isnan(t_min), rng, true, none, t, prim);
+#if RT_DIV_SHARED_ON
+        if constexpr (!Cfg::media && rt_topo_has_rect<Topo>()) {
+            /* a tiny quotient is trusted to fail t_min as the division's would: not with a t_min down there (or NaN) */
+            uint64_t bad = __builtin_amdgcn_ballot_w64(!rt_div_tmin_ok(t_min));
+#if RT_DIV_SHARED_FORCE_SLOW
+            { uint64_t all = ~0ull; asm volatile("" : "+s"(all)); bad |= all; } /* opaque: the first sweep stays, the second always runs */
+#endif
+            const RtInvShared shared = rt_inv3_shared(w.d, true, bad);
+            rt_sweep_static<Topo, Cfg, true, Topo::root, Topo::skip[Topo::root]>(sc, ns, w, shared, ray.time, t_min, rt_isnan(t_min), rng, true, none, t, prim);
+            if (bad != 0ull) { /* some lane left the range: the whole wave once more, with `/` (a lane that was good gets its bits again) */
+                RT_STAMP(2); /* diagnostic builds: the first sweep is traversal as ever, the second is bucket 14 (tools/stamps.py --jit) */
+                const RtV3 inv = rt_inv3(w.d);
+                t = t_max; prim = RT_NONE;
+                rt_sweep_static<Topo, Cfg, true, Topo::root, Topo::skip[Topo::root]>(sc, ns, w, inv, ray.time, t_min, rt_isnan(t_min), rng, true, none, t, prim);
+                RT_STAMP(14);
+            }
+        } else
+#endif
+        {
+            const RtV3 inv = rt_inv3(w.d);
+            rt_sweep_static<Topo, Cfg, true, Topo::root, Topo::skip[Topo::root]>(sc, ns, w, inv, ray.time, t_min, rt_isnan(t_min), rng, true, none, t, prim);
+        }
         if constexpr (RtHitShape<Topo>::trace || RtHitShape<Topo>::carry) scope = RtHitShape<Topo>::scope_of(prim); /* a compile-time function of the leaf: no record is read */
         else scope = prim == RT_NONE ? RT_NONE : ns.hot(prim).b; /* leaves keep their innermost wrapper in `b` */
         return prim != RT_NONE;
