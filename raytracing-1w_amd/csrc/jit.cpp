@@ -4,7 +4,7 @@
  * tree (rt_sweep_static in rt_core.h) once the node kinds and subtree ends are compile-time constants.
  * They are only known when a scene has been committed, so the kernel is generated then: this file writes
  * a short translation unit (the topology as constexpr arrays -- node kinds, subtree ends, the slab planes
- * a box shares with a box above it -- and one extern "C" kernel around rt_render_sorted_body), hands it
+ * a box shares with a box above it, the box a hit is verified against where the sweep runs without box tests -- and one extern "C" kernel around rt_render_sorted_body), hands it
  * and the library's own headers (embedded at build time,
  * jit_headers.inc) to hiprtc, and keeps the code object in a cache keyed by a hash of everything that
  * went into the compiler.  The arithmetic of a path is the same source as in the generic kernels; only
@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "jit_headers.inc"
+#include "rt_box_free.h"
 
 namespace rt1w {
 
@@ -229,6 +230,10 @@ std::string jit_source(const rt1w_scene& s, bool f32) {
         src += (i ? ", " : "") + std::to_string(((k >= RT_SPHERE && k <= RT_YZ) || k == RT_MEDIUM) ? RT_MAT_KINDF(N[i].mat) : 0u) + "u";
     }
     src += "};\n";
+    /* the box-free sweep (rt_core.h: rt_sweep_free): the box every leaf's hit is verified against in each ray space of its wrapper
+     * chain, and whether the unit sweeps that way at all -- no medium, a rect, nested boxes, few enough nodes (rt_box_free.h).  Both
+     * precisions declare them; the f32 build keeps its boxes */
+    src += box_free_members(N.data(), (uint32_t)N.size(), s.flat_root);
     /* the light list's shape (rt_core.h: RtLightShape): how many lights and the kind word of each, in order -- never their
      * coordinates, which keep arriving in the light records: a scene that moves a light keeps its kernel */
     const std::vector<RtNode>& L = s.flat_lights;

@@ -1095,6 +1095,216 @@ RT_HD void rt_sweep_static(const RtSceneView& sc, const NS& ns, const RtRayOD& r
     }
 }
 
+/* The unrolled sweep without box tests (RT_BOX_FREE; DESIGN.md "Sweep without boxes").  Since the rects' quotients come from one
+ * prepared divisor per axis, every lane computes every rect whatever `act` says, and in a scene of a dozen leaves nearly every wave
+ * has a lane in every subtree: the box tests gate verdicts, they save no work.  So: speculate, then verify, with the machinery of
+ * the shared divisors (a wave mask `bad`, and the parent's own sweep once more for a wave that has a lane in it).
+ *   rt_sweep_free: a BVH node tests nothing; every lane visits every leaf in the reference's order, leaf tests and wrapper entries
+ *     statement for statement.  It ends on the smallest candidate t, among equal ones on the last in sweep order.
+ *   rt_box_free_verify: in every ray space on the way to that leaf, the INNERMOST box above it (Topo::vbox) must pass the reference's
+ *     own test with t_max = T, the closest candidate among the leaves BEFORE it in sweep order (or the caller's t_max): what the running
+ *     t_max was when the hit was accepted.  The reference's t_max at any box on the way is a minimum over some of those leaves, hence at
+ *     or above T.  The boxes of one space are nested bit for bit and `(bound - o) * inv` is monotone in the bound, so every box above
+ *     passed as well, each at its own, larger t_max: the reference reached the leaf and accepted it.  (Not the final t itself: a box face
+ *     in the plane of the rect that is hit -- the top of a rotated box and its own world box -- would tie with it on half of the rays.)
+ *   Anything the argument does not cover -- a NaN candidate or product, a divisor out of range (inv is then finite and non-zero
+ *     in every ray space) -- sets the lane's bit.
+ * The world space is verified after the sweep; the space below a Translate / RotateY where its subtree ends, on the inner ray the sweep
+ * holds there, for the lanes whose closest hit so far lies in the subtree (for a lane that ends elsewhere a verdict too many).
+ * Which units: f64, scene-specialised, no media, a rect, and Topo::box_free (jit.cpp: nested boxes, at most 64 nodes).  On the device
+ * by default where the divisors are shared; RT1W_JIT_EXTRA_OPTS=-DRT_BOX_FREE=0 is the text without it.  A host build takes it with
+ * -DRT_BOX_FREE=1: a wave of one lane, the mask a bool, quotients by `/`. */
+#undef RT_BOX_FREE_ON /* (a unit may take this header twice: f64 records, then the f32 build) */
+#if defined(RT_F32)
+#define RT_BOX_FREE_ON 0
+#elif defined(__HIP_DEVICE_COMPILE__)
+#ifndef RT_BOX_FREE
+#define RT_BOX_FREE 1
+#endif
+#define RT_BOX_FREE_ON ((RT_BOX_FREE) != 0 && (RT_DIV_SHARED_ON) == 3)
+#elif defined(RT_BOX_FREE)
+#define RT_BOX_FREE_ON ((RT_BOX_FREE) != 0)
+#else
+#define RT_BOX_FREE_ON 0
+#endif
+#ifndef RT1W_WAVE_MASK
+#define RT1W_WAVE_MASK
+/* the lanes of the wave for which `p` holds: a scalar register pair on the GPU, the one lane's own answer on the host */
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef uint64_t RtWaveMask;
+RT_HD RtWaveMask rt_wave_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+#else
+typedef bool RtWaveMask;
+RT_HD RtWaveMask rt_wave_mask(bool p) { return p; }
+#endif
+#endif
+template <class Topo, class = void>
+struct RtBoxFreeTopo { static constexpr bool value = false; };
+template <class Topo>
+struct RtBoxFreeTopo<Topo, typename RtVoid<decltype(Topo::vbox)>::type> { static constexpr bool value = Topo::box_free; };
+#if RT_BOX_FREE_ON
+/* the common entry of the leaves [LO, HI) in column D of Topo::vbox, RT_NONE if they have none, RT_VBOX_MIXED if they differ */
+#define RT_VBOX_MIXED 0xFFFFFFFEu
+template <class Topo, uint32_t D, uint32_t LO, uint32_t HI>
+constexpr uint32_t rt_vbox_common() {
+    uint32_t c = RT_NONE;
+    bool first = true;
+    for (uint32_t i = LO; i < HI; ++i) {
+        const uint32_t k = Topo::kind[i] & RT_KIND_MASK, v = Topo::vbox[i][D];
+        if (k < RT_SPHERE || k > RT_YZ) continue;
+        if (!first && c != v) return RT_VBOX_MIXED;
+        c = v; first = false;
+    }
+    return c;
+}
+/* AABB::hit aabb.rs:13-32 as rt_aabb_hit_fast has it, for a t_min and t_max that are no NaN; a NaN product fails */
+RT_HD bool rt_box_free_test(const double* bb, RtV3 o, RtV3 inv, double t_min, double t_max) {
+    bool ok = true;
+#define RT_SLAB(minv, maxv, ov, iv)                                 \
+    {                                                               \
+        double t0 = ((minv) - (ov)) * (iv);                         \
+        double t1 = ((maxv) - (ov)) * (iv);                         \
+        if ((iv) < RT_R(0.0)) { double s_ = t0; t0 = t1; t1 = s_; } \
+        ok = ok & (t0 <= t1);                                       \
+        t_min = rt_vmax(t0, t_min);                                 \
+        t_max = rt_vmin(t1, t_max);                                 \
+        ok = ok & (t_max > t_min);                                  \
+    }
+    RT_SLAB(bb[0], bb[3], o.x, inv.x)
+    RT_SLAB(bb[1], bb[4], o.y, inv.y)
+    RT_SLAB(bb[2], bb[5], o.z, inv.z)
+#undef RT_SLAB
+    return ok;
+}
+/* What a lane keeps as its closest leaf while it sweeps: the leaf's index in bits 0-7 and its row of Topo::vbox behind it, a byte per
+ * ray space (0xFF: none; the fourth space of a three-wrapper chain is read from the table) -- a constant per leaf, so accepting a hit
+ * is the one move it always was and the verification starts from a register, not from a table in memory.  RT_NONE is RT_NONE. */
+template <class Topo>
+constexpr uint32_t rt_vbox_word(uint32_t i) {
+    static_assert(Topo::n <= 127u, "a node index is a byte here, and the sign-extended 0xFF is RT_NONE");
+    uint32_t w = i;
+    for (uint32_t s = 0u; s < 3u; ++s) w |= (Topo::vbox[i][s] == RT_NONE ? 0xFFu : Topo::vbox[i][s]) << (8u + 8u * s);
+    return w;
+}
+RT_HD uint32_t rt_vbox_word_leaf(uint32_t word) { return (uint32_t)(int32_t)(int8_t)(word & 0xFFu); }
+/* ray space D, entered for the leaves [LO, HI): a lane whose closest hit `word` is one of them verifies its box there.  The bounds
+ * differ per lane, so they are data: six doubles of the node array (a few dozen records, cache-resident) by vector loads; where the
+ * leaves share one box the index is a constant and the loads are scalar */
+template <class Topo, uint32_t D, uint32_t LO, uint32_t HI>
+RT_HD void rt_box_free_verify(const RtSceneView& sc, const RtRayOD& r, RtV3 inv, double t_min, double t, uint32_t word, RtWaveMask& bad) {
+    constexpr uint32_t common = rt_vbox_common<Topo, D, LO, HI>();
+    if constexpr (common != RT_NONE) {
+        const bool mine = D == 0u ? word != RT_NONE : ((word & 0xFFu) - LO) < (HI - LO);
+        if (RT_WAVE_ANY(mine)) {
+            if constexpr (common != RT_VBOX_MIXED) {
+                bad |= rt_wave_mask(mine & !rt_box_free_test(sc.nodes[common].d, r.o, inv, t_min, t));
+            } else {
+                uint32_t vb;
+                if constexpr (D < 3u) vb = (word >> (8u + 8u * D)) & 0xFFu;
+                else { vb = Topo::vbox[mine ? (word & 0xFFu) : LO][D]; vb = vb == RT_NONE ? 0xFFu : vb; }
+                const bool need = mine & (vb != 0xFFu);
+                bad |= rt_wave_mask(need & !rt_box_free_test(sc.nodes[need ? vb : LO].d, r.o, inv, t_min, t));
+            }
+        }
+    }
+}
+/* 1 / direction of a ray space and the range check on its divisors: with the prepared divisors where they are shared, else by `/` */
+RT_HD RtV3 rt_inv_free(RtV3 d, RtWaveMask& bad) {
+    bad |= rt_wave_mask(!(rt_div_d_ok(d.x) & rt_div_d_ok(d.y) & rt_div_d_ok(d.z)));
+    return rt_inv3(d);
+}
+RT_HD RtV3 rt_inv_free_again(const RtV3&, RtV3 d, RtWaveMask& bad) { return rt_inv_free(d, bad); }
+#if RT_DIV_SHARED_ON
+RT_HD RtInvShared rt_inv_free_again(const RtInvShared& s, RtV3 d, RtWaveMask&) { return rt_inv3_shared(d, true, s.bad); }
+#endif
+/* How far ahead of the leaf being tested the records of later leaves may be fetched.  The sweep is straight-line code, and left alone
+ * the scheduler starts every leaf's scalar loads at the top: a dozen records are some 130 SGPRs, most of them spilled to VGPR lanes and
+ * read back one v_readlane at a time.  So leaf I takes its record at index I + z, where z is a zero the compiler cannot see through and
+ * that is not there before the verdict of the leaf RT_BOX_FREE_AHEAD nodes earlier is: the loads run that far ahead and no further. */
+#ifndef RT_BOX_FREE_AHEAD
+#define RT_BOX_FREE_AHEAD 3
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && RT_BOX_FREE_AHEAD > 0
+struct RtSweepAhead { uint32_t tok[RT_BOX_FREE_AHEAD]; };
+template <uint32_t I>
+RT_HD uint32_t rt_sweep_ahead_index(const RtSweepAhead& a) {
+    uint32_t z;
+    asm("s_and_b32 %0, %1, 0" : "=s"(z) : "s"(a.tok[I % RT_BOX_FREE_AHEAD]) : "scc");
+    return I + z;
+}
+template <uint32_t I>
+RT_HD void rt_sweep_ahead_done(RtSweepAhead& a, bool hit) { a.tok[I % RT_BOX_FREE_AHEAD] = (uint32_t)rt_wave_mask(hit); }
+#else
+struct RtSweepAhead {};
+template <uint32_t I> RT_HD uint32_t rt_sweep_ahead_index(const RtSweepAhead&) { return I; }
+template <uint32_t I> RT_HD void rt_sweep_ahead_done(RtSweepAhead&, bool) {}
+#endif
+template <class Topo, class Cfg, uint32_t D, uint32_t I, uint32_t END, class NS, class Inv>
+RT_HD void rt_sweep_free(const RtSceneView& sc, const NS& ns, const RtRayOD& ray, const Inv& inv, double time, double t_min,
+                         RtWaveMask& bad, double& best_t, double& prev_t, uint32_t& best_word, RtSweepAhead& ahead) {
+    if constexpr (I < END) {
+        constexpr uint32_t kind = Topo::kind[I] & RT_KIND_MASK;
+        constexpr uint32_t skip = Topo::skip[I];
+        if constexpr (kind <= RT_BVH1 || kind == RT_FLIP) {
+            /* pre-order: the subtree is what follows */
+            rt_sweep_free<Topo, Cfg, D, I + 1u, END>(sc, ns, ray, inv, time, t_min, bad, best_t, prev_t, best_word, ahead);
+        } else if constexpr (kind <= RT_YZ) {
+            const RtNodeHot nd = ns.hot(rt_sweep_ahead_index<I>(ahead));
+            double t;
+            bool hit;
+#if RT_DIV_SHARED_ON
+            if constexpr (RtInvIsShared<Inv>::value && kind >= RT_XY) hit = rt_rect_hot_t(nd, kind, ray.o, ray.d, inv, true, t_min, best_t, t); /* (a NaN quotient is `big`) */
+            else
+#endif
+            {
+                if constexpr (Cfg::msphere && kind == RT_MSPHERE) hit = rt_prim_t<Cfg>(sc.nodes[I], kind, ray.o, ray.d, time, t_min, best_t, t);
+                else hit = rt_prim_hot_t(nd, kind, ray.o, ray.d, t_min, best_t, t);
+                bad |= rt_wave_mask(hit && rt_isnan(t)); /* accepted as the reference accepts it, and every later leaf after it: not verifiable */
+            }
+            if (hit) { prev_t = best_t; best_t = t; best_word = rt_vbox_word<Topo>(I); }
+            rt_sweep_ahead_done<I>(ahead, hit);
+            rt_sweep_free<Topo, Cfg, D, I + 1u, END>(sc, ns, ray, inv, time, t_min, bad, best_t, prev_t, best_word, ahead);
+        } else if constexpr (kind <= RT_ROTATE_Y) {
+            /* Translate::hit hittable.rs:207-211 / RotateY::hit :238-251: another ray space */
+            const RtNodeHot nd = ns.hot(I);
+            const RtRayOD inner = rt_scope_in(nd, ray);
+            if constexpr (kind == RT_ROTATE_Y) {
+                const Inv inv_inner = rt_inv_free_again(inv, inner.d, bad);
+                rt_sweep_free<Topo, Cfg, D + 1u, I + 1u, skip>(sc, ns, inner, inv_inner, time, t_min, bad, best_t, prev_t, best_word, ahead);
+                rt_box_free_verify<Topo, D + 1u, I + 1u, skip>(sc, inner, rt_inv_of(inv_inner), t_min, prev_t, best_word, bad);
+            } else {
+                rt_sweep_free<Topo, Cfg, D + 1u, I + 1u, skip>(sc, ns, inner, inv, time, t_min, bad, best_t, prev_t, best_word, ahead);
+                rt_box_free_verify<Topo, D + 1u, I + 1u, skip>(sc, inner, rt_inv_of(inv), t_min, prev_t, best_word, bad);
+            }
+            rt_sweep_free<Topo, Cfg, D, skip, END>(sc, ns, ray, inv, time, t_min, bad, best_t, prev_t, best_word, ahead);
+        } else {
+            static_assert(kind <= RT_ROTATE_Y, "a unit with a medium keeps its boxes");
+        }
+    }
+}
+/* the speculative closest hit and the lanes that must not trust theirs (rt_closest_hit; tests/test_box_free.py reads both) */
+template <class Cfg, class NS>
+RT_HD RtWaveMask rt_closest_hit_free(const RtSceneView& sc, const NS& ns, const RtRayOD& w, double time, double t_min, double t_max,
+                                     double& t, uint32_t& prim) {
+    typedef typename Cfg::Topo Topo;
+    /* a tiny quotient is trusted to fail t_min as the division's would: not with a t_min down there (or NaN) */
+    RtWaveMask bad = rt_wave_mask(!rt_div_tmin_ok(t_min) | rt_isnan(t_max)); /* (nor with a NaN for t_max: nothing is "at or above" it) */
+    t = t_max;
+#if RT_DIV_SHARED_ON
+    const RtInvShared inv = rt_inv3_shared(w.d, true, bad);
+#else
+    const RtV3 inv = rt_inv_free(w.d, bad);
+#endif
+    uint32_t word = RT_NONE;
+    RtSweepAhead ahead = {};
+    double prev = t_max; /* the closest candidate of the leaves before the one that holds the hit: what the boxes are verified against */
+    rt_sweep_free<Topo, Cfg, 0u, Topo::root, Topo::skip[Topo::root]>(sc, ns, w, inv, time, t_min, bad, t, prev, word, ahead);
+    rt_box_free_verify<Topo, 0u, Topo::root, Topo::skip[Topo::root]>(sc, w, rt_inv_of(inv), t_min, prev, word, bad);
+    prim = rt_vbox_word_leaf(word);
+    return bad;
+}
+#endif
+
 template <class Topo, class = void>
 struct RtHitShape; /* below, with the static hit record */
 template <class Cfg, class Stack, class NS>
@@ -1105,6 +1315,25 @@ RT_HD bool rt_closest_hit(const RtSceneView& sc, const NS& ns, const RtRay& ray,
         RtRayOD w; w.o = ray.o; w.d = ray.d;
         const RtSlabNone none;
         t = t_max; prim = RT_NONE;
+#if RT_BOX_FREE_ON
+        if constexpr (!Cfg::media && RtBoxFreeTopo<Topo>::value) {
+            RtWaveMask bad = rt_closest_hit_free<Cfg>(sc, ns, w, ray.time, t_min, t_max, t, prim);
+#if RT_DIV_SHARED_FORCE_SLOW
+#if defined(__HIP_DEVICE_COMPILE__)
+            { uint64_t all = ~0ull; asm volatile("" : "+s"(all)); bad |= all; } /* opaque: the first sweep stays, the second always runs */
+#else
+            bad = true;
+#endif
+#endif
+            if (bad != 0) { /* some lane could not be verified: the whole wave once more, with boxes and `/` */
+                RT_STAMP(2);
+                const RtV3 inv = rt_inv3(w.d);
+                t = t_max; prim = RT_NONE;
+                rt_sweep_static<Topo, Cfg, true, Topo::root, Topo::skip[Topo::root]>(sc, ns, w, inv, ray.time, t_min, rt_isnan(t_min), rng, true, none, t, prim);
+                RT_STAMP(14);
+            }
+        } else
+#endif
 #if RT_DIV_SHARED_ON
         if constexpr (!Cfg::media && rt_topo_has_rect<Topo>()) {
             /* a tiny quotient is trusted to fail t_min as the division's would: not with a t_min down there (or NaN) */

@@ -170,7 +170,9 @@ RT_HD uint32_t rt_frame_row(const RtFrame& f, uint32_t py) {
  * `n_lights`, `light_kind[]`: the kind word of every light, in order (RtLightShape; absent = the list is walked at run time);
  * `lambert_general`, `lambert_xy` / `_xz` / `_yz`: where Lambertian materials sit (RtLambertWalls; absent = every frame is computed);
  * `wrap[n]`, `mat_kind[n]`: the wrapper above a node and the kind word of a leaf's material (RtHitShape; absent = the hit record reads the
- * node and walks its chain at run time) */
+ * node and walks its chain at run time);
+ * `vbox[n][4]`, `box_free`: the box a leaf's hit is verified against in each ray space of its chain, and whether the unit sweeps without
+ * box tests (rt_sweep_free; absent or false = every box is tested) */
 template <bool MEDIA_, bool TEX_, bool MSPHERE_, bool SWEEP_, int SCOPE_DEPTH_ = 3, class Topo_ = void, bool ORDERED_ = false>
 struct RtCfg {
     static constexpr bool ordered = ORDERED_; /* stack walk honours the opt-in near-far bits of BVH2 nodes (rt1w_scene_set_walk_order) */
