@@ -1230,6 +1230,117 @@ int orc_render(const orc_scene* o, uint32_t width, uint32_t height, uint32_t x0,
     return orc_render_checkpoints(o, width, height, x0, y0, tw, th, spp, sample_offset, max_depth, global_seed, out_sum, threads,
                                   &spp, 1, out, segments_out);
 }
+/* ---- feature buffers (include/rt1w.h: rt1w_render_aov, rt1w_render_aov_deep, rt1w_render_aov_tiles), stated on the class surface above ----
+ * TEST SUPPORT with no counterpart in the reference, which has no feature buffers; what it states is the header's text read against the
+ * reference lines the header cites.  Per (pixel, sample) the stream and the camera ray are those of orc_render_checkpoints, so sample k
+ * here is beauty sample k.  The chain: world->hit(ray, 0.001, inf) (main.rs:62); a miss ends it.  A hit on a Dielectric, or on a Metal
+ * whose fuzz <= max_fuzz -- decided by the material's dynamic type -- is followed while fewer than max_specular bounces have been
+ * followed: the material's own scatter() with the live generator (material.rs:99-111, :133-160), beta *= attenuation, on along
+ * `specular`.  Any other hit ends it.  max_specular = 0 is the first-hit buffer.
+ * At the end of the chain: albedo = beta (.) [Lambertian, Isotropic: albedo->value(u, v, p) (material.rs:71-80, constant_medium.rs:37-50);
+ * Metal: albedo; Dielectric: (1, 1, 1); DiffuseLight: emitted() (material.rs:163-178); (): 0 (material.rs:68); a miss: the background];
+ * normal = HitRecord.normal as hit() left it ((0, 0, 0) on a miss); depth = the sum of t * |d| over the chain's hits; coverage 1 / 0.
+ * out[th][tw][8]: sums in sample order; 0-5 and 7 divided by spp, 6 (summed over the samples whose last ray hit) divided by their number,
+ * +inf if there is none.  out_sum: the raw sums, 6 is +0.0 if no sample hit, 7 the number of samples whose last ray hit
+ * (rt1w_render_aov_tiles).  counts[4] (may be NULL): samples whose chain ended 0 on a hit that is not followed (not specular), 1 on a
+ * miss, 2 on a specular surface because max_specular bounces had been followed; 0 + 1 + 2 = tw * th * spp; 3: those of 0 that ended
+ * on a ConstantMedium's Isotropic.  segments_out (may be NULL): the rays traced.
+ * The reference-stream build returns -1: the product refuses RT1W_RNG_REFERENCE for these entries. */
+int orc_aov(const orc_scene* o, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, uint32_t spp,
+            uint32_t sample_offset, uint32_t global_seed, uint32_t max_specular, double max_fuzz, int out_sum, int threads, double* out,
+            uint64_t* counts, uint64_t* segments_out) {
+#if ORC_STREAM_PER_PIXEL
+    (void)o; (void)width; (void)height; (void)x0; (void)y0; (void)tw; (void)th; (void)spp; (void)sample_offset; (void)global_seed;
+    (void)max_specular; (void)max_fuzz; (void)out_sum; (void)threads; (void)out; (void)counts; (void)segments_out;
+    return -1;
+#else
+    if (!o || !out || width < 2 || height < 2 || spp == 0) return -1;
+    const Scene& s = o->s;
+    if (threads < 1) threads = 1;
+    std::atomic<uint32_t> next_row(0);
+    std::atomic<uint64_t> seg_total(0), n_end[4];
+    for (auto& n : n_end) n = 0;
+    auto worker = [&]() {
+        uint64_t rays = 0, ended[4] = {0, 0, 0, 0};
+        for (;;) {
+            uint32_t r = next_row.fetch_add(1);
+            if (r >= th) break;
+            uint32_t j = y0 + r;
+            for (uint32_t c = 0; c < tw; ++c) {
+                uint32_t i = x0 + c;
+                V3 albedo_sum = rt_v3(0.0, 0.0, 0.0), normal_sum = rt_v3(0.0, 0.0, 0.0);
+                Float depth_sum = 0.0;
+                uint32_t hits = 0;
+                for (uint32_t k = 0; k < spp; ++k) {
+                    MyRng rng = orc_rng_pixel((uint64_t)j * width + i, sample_offset + k, global_seed); /* main.rs:964 */
+                    Float u = ((Float)i + rt_gen_f64(rng)) / (Float)(width - 1);
+                    Float v = ((Float)j + rt_gen_f64(rng)) / (Float)(height - 1);
+                    Ray ray = s.camera.get_ray(u, v, rng);
+                    V3 beta = rt_v3(1.0, 1.0, 1.0);
+                    Float depth = 0.0;
+                    uint32_t followed = 0;
+                    for (;;) {
+                        rays++;
+                        HitRecord rec;
+                        if (!s.world->hit(ray, 0.001, RT_INF, rng, rec)) {
+                            albedo_sum = albedo_sum + rt_mul(beta, s.background);
+                            ended[1]++;
+                            break;
+                        }
+                        depth = depth + rec.t * rt_mag(ray.direction);
+                        const Material* m = rec.material;
+                        const Metal* metal = dynamic_cast<const Metal*>(m);
+                        const bool dielectric = dynamic_cast<const Dielectric*>(m) != nullptr;
+                        const bool specular = dielectric || (metal && metal->fuzz <= max_fuzz);
+                        if (specular && followed < max_specular) {
+                            Scatter sc;
+                            m->scatter(ray, rec, rng, sc);
+                            beta = rt_mul(beta, sc.attenuation);
+                            ray = sc.specular;
+                            ++followed;
+                            continue;
+                        }
+                        V3 value = rt_v3(0.0, 0.0, 0.0); /* impl Material for () */
+                        if (const Lambertian* l = dynamic_cast<const Lambertian*>(m)) value = l->albedo->value(rec.u, rec.v, rec.position);
+                        else if (const Isotropic* iso = dynamic_cast<const Isotropic*>(m)) value = iso->albedo->value(rec.u, rec.v, rec.position);
+                        else if (metal) value = metal->albedo;
+                        else if (dielectric) value = rt_v3(1.0, 1.0, 1.0);
+                        else if (dynamic_cast<const DiffuseLight*>(m)) value = m->emitted(ray, rec, rec.u, rec.v, rec.position);
+                        albedo_sum = albedo_sum + rt_mul(beta, value);
+                        normal_sum = normal_sum + rec.normal;
+                        depth_sum = depth_sum + depth;
+                        hits++;
+                        if (specular) ended[2]++;
+                        else { ended[0]++; if (dynamic_cast<const Isotropic*>(m)) ended[3]++; }
+                        break;
+                    }
+                }
+                double* dst = out + ((size_t)r * tw + c) * 8;
+                const Float n = (Float)spp;
+                if (out_sum) {
+                    dst[0] = albedo_sum.x; dst[1] = albedo_sum.y; dst[2] = albedo_sum.z;
+                    dst[3] = normal_sum.x; dst[4] = normal_sum.y; dst[5] = normal_sum.z;
+                    dst[6] = depth_sum; dst[7] = (Float)hits;
+                } else {
+                    dst[0] = albedo_sum.x / n; dst[1] = albedo_sum.y / n; dst[2] = albedo_sum.z / n;
+                    dst[3] = normal_sum.x / n; dst[4] = normal_sum.y / n; dst[5] = normal_sum.z / n;
+                    dst[6] = hits ? depth_sum / (Float)hits : RT_INF;
+                    dst[7] = (Float)hits / n;
+                }
+            }
+        }
+        seg_total += rays;
+        for (int e = 0; e < 4; ++e) n_end[e] += ended[e];
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < threads; ++t) pool.emplace_back(worker);
+    worker();
+    for (auto& t : pool) t.join();
+    if (segments_out) *segments_out = seg_total.load();
+    if (counts) for (int e = 0; e < 4; ++e) counts[e] = n_end[e].load();
+    return 0;
+#endif
+}
 /* 1 = this library was built with -DORC_REFSTREAM (ChaCha12 per-pixel stream + libm) */
 int orc_is_refstream(void) { return ORC_STREAM_PER_PIXEL; }
 

@@ -35,6 +35,8 @@ for _L in (A, REF):
     _L.orc_render_checkpoints.argtypes = [_P] + [C.c_uint32] * 10 + [C.c_int, C.c_int, _P, C.c_uint32, _P, C.POINTER(C.c_uint64)]
     _L.orc_quantize.argtypes = [_P, C.c_uint64, _P]
     _L.orc_is_refstream.restype = C.c_int
+    _L.orc_aov.restype = C.c_int
+    _L.orc_aov.argtypes = [_P] + [C.c_uint32] * 10 + [C.c_double, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_uint64)]
 # the same restatement with `type Float = f32` (main.rs:1; oracle/oracle_f32.cpp): `double` parameters are `float` in this library
 F32 = C.CDLL(os.path.join(ORACLE_DIR, "liborc_f32.so"))
 F32.orc_scene_build.restype = _P
@@ -137,6 +139,24 @@ class OracleScene:
                                              threads, cp, len(checkpoints), out.ctypes.data_as(_P), C.byref(seg))
         assert rc == 0
         return out, {"segments": seg.value, "paths": tw * th * checkpoints[-1]}
+
+    def aov(self, width, height, spp, tile=None, sample_offset=0, global_seed=0, max_specular=0, max_fuzz=0.0, out_sum=False, threads=None):
+        """The literal statement of the feature buffers (oracle.cpp: orc_aov): float64 [tile_h, tile_w, 8] in the layout of
+        rt1w_render_aov; max_specular = 0 is the first-hit buffer, otherwise the deep one; out_sum: the raw sums of
+        rt1w_render_aov_tiles.  Second value: {"segments": rays traced, "paths", "counts": samples whose chain ended [on a hit that
+        is not followed, on a miss, cut at max_specular while still specular, (of the first) on a medium's Isotropic]}.  f64 library
+        only; the reference-stream build refuses (-1), as the product refuses that flag for these entries."""
+        assert not getattr(self, "f32", False), "the feature buffers are stated for the f64 library only"
+        x0, y0, tw, th = tile if tile is not None else (0, 0, width, height)
+        out = np.empty((th, tw, 8), dtype=np.float64)
+        seg = C.c_uint64()
+        counts = (C.c_uint64 * 4)()
+        threads = threads or min(16, os.cpu_count() or 1)
+        rc = self.lib.orc_aov(self._h, width, height, x0, y0, tw, th, spp, sample_offset, global_seed, max_specular, max_fuzz,
+                              1 if out_sum else 0, threads, out.ctypes.data_as(_P), counts, C.byref(seg))
+        if rc != 0:
+            raise RuntimeError(f"orc_aov refused ({rc})")
+        return out, {"segments": seg.value, "paths": tw * th * spp, "counts": [int(c) for c in counts]}
 
     def apply_topology(self, topo, merge_nested=True):
         """Rebuild every BVH of this oracle scene over its own leaves with the trees of `topo` (the product's opt-in SAH build,
