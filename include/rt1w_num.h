@@ -721,4 +721,26 @@ RT_HD uint32_t rt_wave_first(uint64_t accepted, uint32_t loop, uint32_t k_log2) 
 }
 #endif /* !RT_RNG_REFSTREAM */
 
+/* The class bases of the reordering kernels' sort (csrc/rt_kernel_sorted.h).  The count of class c in wave w is held at slot
+ * c * nw + w, so the slots before it are exactly what sorts below it: every lower class, and its own class in the lower waves.  A wave
+ * holds slot i in lane i (what the lanes behind the last slot hold reaches no slot's sum) and gets "the counts before my slot" for all of them from one exclusive prefix
+ * sum across its lanes; a path of class c in wave w then takes its base from lane rt_sort_slot(c, w, nw).  One text for the kernels and
+ * for the tests' wave emulation: W supplies the moves between lanes, T is one value per lane.
+ *   w.row_shr<S>(x)   lane l takes x of lane l - S where that lies in l's row of 16 lanes, else 0
+ *   w.row_bcast15(x)  the lanes of rows 1 and 3 take x of the last lane of the row before theirs, the others 0
+ *   w.row_bcast31(x)  the lanes of rows 2 and 3 take x of lane 31, the others 0 */
+RT_HD uint32_t rt_sort_slot(uint32_t cls, uint32_t wave, uint32_t nw) { return cls * nw + wave; }
+template <uint32_t N, class W, class T>
+RT_HD T rt_sort_scan(const W& w, const T& held) {
+    static_assert(N <= 64u, "one slot to a lane");
+    T x = held;
+    x = x + w.template row_shr<1u>(x); /* inclusive sums within a row */
+    x = x + w.template row_shr<2u>(x);
+    x = x + w.template row_shr<4u>(x);
+    x = x + w.template row_shr<8u>(x);
+    if (N > 16u) x = x + w.row_bcast15(x); /* rows 1 and 3 over their pair of rows */
+    if (N > 32u) x = x + w.row_bcast31(x); /* the upper pair over the whole wave */
+    return x - held;
+}
+
 #endif /* RT1W_NUM_H */

@@ -210,6 +210,31 @@ RT_HD RtRayOD rt_scope_in(const NodeT& s, RtRayOD r) {
     }
     return r;
 }
+/* the same for a wrapper whose kind the caller knows at compile time (the sweeps unrolled along a scene's own tree): the statements of
+ * that kind and nothing else -- the record's kind word is not read, no arm is chosen at run time, the ray stays in its registers.
+ * RT_SCOPE_STATIC 0 is the dispatch on the record (RT1W_JIT_EXTRA_OPTS=-DRT_SCOPE_STATIC=0: the A/B). */
+#ifndef RT_SCOPE_STATIC
+#define RT_SCOPE_STATIC 1
+#endif
+template <uint32_t KIND, class NodeT>
+RT_HD RtRayOD rt_scope_in_k(const NodeT& s, RtRayOD r) {
+#if RT_SCOPE_STATIC
+    static_assert(KIND == RT_TRANSLATE || KIND == RT_ROTATE_Y, "a wrapper that moves the ray");
+    if constexpr (KIND == RT_TRANSLATE) {
+        r.o = r.o - rt_v3(s.d[0], s.d[1], s.d[2]);
+    } else {
+        double sn = s.d[0], cs = s.d[1];
+        RtV3 o = r.o, d = r.d;
+        r.o.x = cs * o.x - sn * o.z;
+        r.o.z = sn * o.x + cs * o.z;
+        r.d.x = cs * d.x - sn * d.z;
+        r.d.z = sn * d.x + cs * d.z;
+    }
+    return r;
+#else
+    return rt_scope_in(s, r);
+#endif
+}
 /* the way back out: hittable.rs:215-225, :255-278, :288-291.  `inner` is the ray in
  * the wrapper's space (`moved` / `rotated_r`): both re-run HitRecord::new with it,
  * taking the child's already-forwarded normal as "outward" (reference quirk Q5). */
@@ -1061,7 +1086,7 @@ RT_HD void rt_sweep_static(const RtSceneView& sc, const NS& ns, const RtRayOD& r
                 } else {
                     /* Translate::hit hittable.rs:207-211 / RotateY::hit :238-251: another ray space, the chain starts empty */
                     const RtNodeHot nd = ns.hot(I);
-                    const RtRayOD inner = rt_scope_in(nd, ray);
+                    const RtRayOD inner = rt_scope_in_k<kind>(nd, ray);
                     const RtSlabNone none;
                     if constexpr (kind == RT_ROTATE_Y) {
                         const Inv inv_inner = rt_inv_again(inv, inner.d, act);
@@ -1232,12 +1257,24 @@ RT_HD uint32_t rt_sweep_ahead_index(const RtSweepAhead& a) {
     asm("s_and_b32 %0, %1, 0" : "=s"(z) : "s"(a.tok[I % RT_BOX_FREE_AHEAD]) : "scc");
     return I + z;
 }
+/* The token of a leaf's verdict.  The wave mask of `hit` is a mask the compiler has to rebuild: `hit` is an `and` of compares, so its
+ * ballot is a 0 / 1 per lane (v_cndmask) compared with 0 again, two vector instructions a leaf.  RT_AHEAD_WORD 1 takes the first lane's
+ * closest-hit word after the leaf has been accepted or not instead: as late as the verdict, one v_readfirstlane.  (0: the mask; the A/B.) */
+#ifndef RT_AHEAD_WORD
+#define RT_AHEAD_WORD 0
+#endif
 template <uint32_t I>
-RT_HD void rt_sweep_ahead_done(RtSweepAhead& a, bool hit) { a.tok[I % RT_BOX_FREE_AHEAD] = (uint32_t)rt_wave_mask(hit); }
+RT_HD void rt_sweep_ahead_done(RtSweepAhead& a, bool hit, uint32_t word) {
+#if RT_AHEAD_WORD
+    a.tok[I % RT_BOX_FREE_AHEAD] = __builtin_amdgcn_readfirstlane(word);
+#else
+    a.tok[I % RT_BOX_FREE_AHEAD] = (uint32_t)rt_wave_mask(hit);
+#endif
+}
 #else
 struct RtSweepAhead {};
 template <uint32_t I> RT_HD uint32_t rt_sweep_ahead_index(const RtSweepAhead&) { return I; }
-template <uint32_t I> RT_HD void rt_sweep_ahead_done(RtSweepAhead&, bool) {}
+template <uint32_t I> RT_HD void rt_sweep_ahead_done(RtSweepAhead&, bool, uint32_t) {}
 #endif
 template <class Topo, class Cfg, uint32_t D, uint32_t I, uint32_t END, class NS, class Inv>
 RT_HD void rt_sweep_free(const RtSceneView& sc, const NS& ns, const RtRayOD& ray, const Inv& inv, double time, double t_min,
@@ -1262,12 +1299,12 @@ RT_HD void rt_sweep_free(const RtSceneView& sc, const NS& ns, const RtRayOD& ray
                 bad |= rt_wave_mask(hit && rt_isnan(t)); /* accepted as the reference accepts it, and every later leaf after it: not verifiable */
             }
             if (hit) { prev_t = best_t; best_t = t; best_word = rt_vbox_word<Topo>(I); }
-            rt_sweep_ahead_done<I>(ahead, hit);
+            rt_sweep_ahead_done<I>(ahead, hit, best_word);
             rt_sweep_free<Topo, Cfg, D, I + 1u, END>(sc, ns, ray, inv, time, t_min, bad, best_t, prev_t, best_word, ahead);
         } else if constexpr (kind <= RT_ROTATE_Y) {
             /* Translate::hit hittable.rs:207-211 / RotateY::hit :238-251: another ray space */
             const RtNodeHot nd = ns.hot(I);
-            const RtRayOD inner = rt_scope_in(nd, ray);
+            const RtRayOD inner = rt_scope_in_k<kind>(nd, ray);
             if constexpr (kind == RT_ROTATE_Y) {
                 const Inv inv_inner = rt_inv_free_again(inv, inner.d, bad);
                 rt_sweep_free<Topo, Cfg, D + 1u, I + 1u, skip>(sc, ns, inner, inv_inner, time, t_min, bad, best_t, prev_t, best_word, ahead);

@@ -150,6 +150,24 @@ __device__ __forceinline__ bool rt_tile_item(const RtFrame& f, const RtTileList&
 #ifndef RT_SORTED_CARRY_RADIANCE
 #define RT_SORTED_CARRY_RADIANCE 0 /* A/B (RT1W_JIT_EXTRA_OPTS=-DRT_SORTED_CARRY_RADIANCE=1): round 3's form, the zero radiance carried across the loop */
 #endif
+/* Where a path goes in the sort: its rank within its wave's lanes of its class plus the class base -- the paths of the lower classes and of
+ * its own class in the lower waves.  The bases are one exclusive prefix sum over the RT_N_CLS x NW counts, the same for the whole workgroup.
+ * RT_SORT_SCAN 1: the table is [class][wave], every wave loads it one count to a lane, scans it across its lanes (include/rt1w_num.h:
+ * rt_sort_scan over the moves below) and every lane fetches its base from the lane that holds it.  0: every lane reads every count and
+ * sums the ones below its own (RT1W_JIT_EXTRA_OPTS=-DRT_SORT_SCAN=0: the A/B).  2: the scan, and a wave's six counts stored by lane 0 in
+ * one region behind the ballots instead of one region a class. */
+#ifndef RT_SORT_SCAN
+#define RT_SORT_SCAN 1
+#endif
+#if RT_SORT_SCAN
+/* the moves of rt_sort_scan on a wave of 64: DPP row shifts and row broadcasts; a lane without a source, or outside the row mask, takes 0.
+ * They read registers of other lanes, so every lane of the wave must be active where they run. */
+struct RtWaveDpp {
+    template <uint32_t S> __device__ __forceinline__ uint32_t row_shr(uint32_t x) const { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x110 + (int)S, 0xf, 0xf, false); }
+    __device__ __forceinline__ uint32_t row_bcast15(uint32_t x) const { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false); }
+    __device__ __forceinline__ uint32_t row_bcast31(uint32_t x) const { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false); }
+};
+#endif
 #define RT_XCH_QW 26 /* qwords of per-path state exchanged */
 #ifndef RT_XCH_PARTS
 #define RT_XCH_PARTS 1 /* rounds the exchange is done in (LDS per workgroup = ceil(26 / parts) qwords x paths) */
@@ -171,7 +189,13 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
     constexpr int NW = RT_SORT_BLOCK / 64;
     static_assert(Cfg::sweep, "the reordering kernel is built for the stackless variants");
     __shared__ unsigned long long xch[RT_XCH_PER * RT_SORT_BLOCK];
+#if RT_SORT_SCAN
+    constexpr uint32_t NV = (uint32_t)NW * RT_N_CLS;
+    static_assert(NV <= 64u && RT_CLS_IDLE == RT_N_CLS - 1, "one count to a lane, the idle class last");
+    __shared__ uint32_t cnt[NV]; /* [class][wave]: rt_sort_slot */
+#else
     __shared__ uint32_t cnt[NW][RT_N_CLS];
+#endif
     LdsStack stk;
     stk.base = nullptr;
     stk.sp = 0;
@@ -179,7 +203,11 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
 
     const unsigned long long n_items = rt_item_count(f);
     const unsigned long long npix = (unsigned long long)f.tile_w * f.tile_h;
+#if RT_SORT_SCAN
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); /* (a scalar: it is only added to addresses) */
+#else
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#endif
     unsigned long long item = (unsigned long long)blockIdx.x * RT_SORT_BLOCK + threadIdx.x;
     bool fresh = true, have = false, retired = false;
     uint32_t px = 0, py = 0, chunk = 0, s = 0;
@@ -249,15 +277,43 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
         RT_STAMP(2);
         /* 3. sort the workgroup's paths by class */
         uint32_t my_rank = 0;
+#if RT_SORT_SCAN >= 2
+        uint32_t n_cls[RT_N_CLS]; /* (scalars: the wave's six counts go out together, from one lane in one region) */
 #pragma unroll
         for (uint32_t c = 0; c < RT_N_CLS; ++c) {
             unsigned long long m = __ballot(tr.cls == c);
             if (tr.cls == c) my_rank = lane_prefix(m);
-            if (lane == 0u) cnt[wave][c] = (uint32_t)__popcll(m);
+            n_cls[c] = (uint32_t)__popcll(m);
         }
+        if (lane == 0u) {
+#pragma unroll
+            for (uint32_t c = 0; c < RT_N_CLS; ++c) cnt[rt_sort_slot(c, wave, (uint32_t)NW)] = n_cls[c];
+        }
+#else
+#pragma unroll
+        for (uint32_t c = 0; c < RT_N_CLS; ++c) {
+            unsigned long long m = __ballot(tr.cls == c);
+            if (tr.cls == c) my_rank = lane_prefix(m);
+#if RT_SORT_SCAN
+            if (lane == 0u) cnt[rt_sort_slot(c, wave, (uint32_t)NW)] = (uint32_t)__popcll(m);
+#else
+            if (lane == 0u) cnt[wave][c] = (uint32_t)__popcll(m);
+#endif
+        }
+#endif
         RT_STAMP(8);
         __syncthreads();
         RT_STAMP(9);
+#if RT_SORT_SCAN
+        /* Not inside any divergent region: a retired lane keeps looping until the whole workgroup breaks below, so all 64 lanes of
+         * the wave are active here, which the scan's moves and the fetch need. */
+        const uint32_t held = cnt[lane < NV ? lane : NV - 1u]; /* (a lane without a slot: any count will do, nothing looks at its sum) */
+        const uint32_t below = rt_sort_scan<NV>(RtWaveDpp(), held); /* lane i: the counts of the slots before i */
+        const uint32_t idle_total = (uint32_t)__builtin_amdgcn_readlane((int)(below + held), (int)NV - 1) -
+                                    (uint32_t)__builtin_amdgcn_readlane((int)below, (int)rt_sort_slot(RT_CLS_IDLE, 0u, (uint32_t)NW));
+        if (idle_total == RT_SORT_BLOCK) break; /* every path of the workgroup is done (uniform) */
+        const uint32_t dest = my_rank + (uint32_t)__builtin_amdgcn_ds_bpermute((int)(rt_sort_slot(tr.cls, wave, (uint32_t)NW) << 2), (int)below);
+#else
         uint32_t dest = my_rank, idle_total = 0;
 #pragma unroll
         for (uint32_t c = 0; c < RT_N_CLS; ++c) {
@@ -269,6 +325,7 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
             }
         }
         if (idle_total == RT_SORT_BLOCK) break; /* every path of the workgroup is done (uniform) */
+#endif
         {
             /* the path state as 26 qwords (compile-time indices only: these stay registers), handed over in RT_XCH_PARTS rounds
              * through an exchange buffer of ceil(26 / parts) qwords per slot */
