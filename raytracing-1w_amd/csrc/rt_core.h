@@ -158,6 +158,48 @@ RT_HD bool rt_sphere_root(RtV3 center, double radius, RtV3 o, RtV3 d, double t_m
     root_out = root;
     return true;
 }
+/* rt_sphere_root for a caller that holds oc2 = |center - o|^2 already (rt_sphere_cone): its statements, with that value for |o - center|^2.
+ * The two are the same bits: x - y and y - x are each other's negation in round-to-nearest, a square does not see the sign, and the
+ * three squares are added in the same order (tests/test_light_cone.py compares them on 10^5 random pairs and the specials). */
+RT_HD bool rt_sphere_root_oc2(RtV3 center, double radius, double oc2, RtV3 o, RtV3 d, double t_min, double t_max, double& root_out) {
+    RtV3 oc = o - center;
+    double a = rt_mag2(d);
+    double half_b = rt_dot(oc, d);
+    double c = oc2 - radius * radius;
+    double discriminant = half_b * half_b - a * c;
+    if (discriminant < RT_R(0.0)) return false;
+    double sqrtd = rt_sqrt(discriminant);
+    double root = (-half_b - sqrtd) / a;
+    if (root < t_min || t_max < root) {
+        root = (-half_b + sqrtd) / a;
+        if (root < t_min || t_max < root) return false;
+    }
+    root_out = root;
+    return true;
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+/* rt_sphere_root for a leaf of the box-free sweep that hands out a token besides its verdict (rt_sweep_free, RT_AHEAD_WORD 2): its
+ * statements, and in `tok` the low word of the wave mask of ONE compare they make anyway -- a compare writes its mask to a scalar
+ * register pair, so taking it costs no instruction.  The sphere's: the discriminant's sign, its last compare outside the divergent
+ * part (the roots are tested by the lanes that have some). */
+__device__ __forceinline__ bool rt_sphere_root_tok(RtV3 center, double radius, RtV3 o, RtV3 d, double t_min, double t_max, double& root_out, uint32_t& tok) {
+    RtV3 oc = o - center;
+    double a = rt_mag2(d);
+    double half_b = rt_dot(oc, d);
+    double c = rt_mag2(oc) - radius * radius;
+    double discriminant = half_b * half_b - a * c;
+    tok = (uint32_t)__builtin_amdgcn_ballot_w64(discriminant < RT_R(0.0));
+    if (discriminant < RT_R(0.0)) return false;
+    double sqrtd = rt_sqrt(discriminant);
+    double root = (-half_b - sqrtd) / a;
+    if (root < t_min || t_max < root) {
+        root = (-half_b + sqrtd) / a;
+        if (root < t_min || t_max < root) return false;
+    }
+    root_out = root;
+    return true;
+}
+#endif
 /* MovingSphere::center moving_sphere.rs:23-26 */
 RT_HD RtV3 rt_msphere_center(const RtNode& nd, double time) {
     RtV3 c0 = rt_v3(nd.d[0], nd.d[1], nd.d[2]), c1 = rt_v3(nd.d[3], nd.d[4], nd.d[5]);
@@ -489,6 +531,26 @@ RT_HD bool rt_rect_hot_t(const RtNodeHot& nd, uint32_t kind, RtV3 o, RtV3 d, con
     if (kind == RT_XY) return rt_rect_hot_at(nd, t, in_t, o.x, d.x, o.y, d.y, t_out);
     if (kind == RT_XZ) return rt_rect_hot_at(nd, t, in_t, o.x, d.x, o.z, d.z, t_out);
     return rt_rect_hot_at(nd, t, in_t, o.y, d.y, o.z, d.z, t_out);
+}
+/* the same with a token for the box-free sweep (rt_sphere_root_tok): the mask of the rect's last compare, `c > nd.d[3]`, said once more
+ * behind the conjunction it is part of -- one value, one instruction */
+__device__ __forceinline__ bool rt_rect_hot_at_tok(const RtNodeHot& nd, double t, bool in_t, double ob, double db, double oc, double dc, double& t_out, uint32_t& tok) {
+    const double b = ob + t * db;
+    const double c = oc + t * dc;
+    const bool in_rect = !((b < nd.d[0]) | (b > nd.d[1]) | (c < nd.d[2]) | (c > nd.d[3]));
+    tok = (uint32_t)__builtin_amdgcn_ballot_w64(c > nd.d[3]);
+    if (in_t & in_rect) { t_out = t; return true; }
+    return false;
+}
+__device__ __forceinline__ bool rt_rect_hot_t_tok(const RtNodeHot& nd, uint32_t kind, RtV3 o, RtV3 d, const RtInvShared& s, bool act, double t_min, double t_max, double& t_out, uint32_t& tok) {
+    const double oa = kind == RT_XY ? o.z : (kind == RT_XZ ? o.y : o.x), da = kind == RT_XY ? d.z : (kind == RT_XZ ? d.y : d.x);
+    const double ya = kind == RT_XY ? s.y.z : (kind == RT_XZ ? s.y.y : s.y.x);
+    const double t = rt_div_q(nd.d[4] - oa, da, ya);
+    s.bad |= __builtin_amdgcn_ballot_w64(rt_div_q_big(t));
+    const bool in_t = act & !((t < t_min) | (t > t_max));
+    if (kind == RT_XY) return rt_rect_hot_at_tok(nd, t, in_t, o.x, d.x, o.y, d.y, t_out, tok);
+    if (kind == RT_XZ) return rt_rect_hot_at_tok(nd, t, in_t, o.x, d.x, o.z, d.z, t_out, tok);
+    return rt_rect_hot_at_tok(nd, t, in_t, o.y, d.y, o.z, d.z, t_out, tok);
 }
 #endif
 
@@ -1259,13 +1321,18 @@ RT_HD uint32_t rt_sweep_ahead_index(const RtSweepAhead& a) {
 }
 /* The token of a leaf's verdict.  The wave mask of `hit` is a mask the compiler has to rebuild: `hit` is an `and` of compares, so its
  * ballot is a 0 / 1 per lane (v_cndmask) compared with 0 again, two vector instructions a leaf.  RT_AHEAD_WORD 1 takes the first lane's
- * closest-hit word after the leaf has been accepted or not instead: as late as the verdict, one v_readfirstlane.  (0: the mask; the A/B.) */
+ * closest-hit word after the leaf has been accepted or not instead: as late as the verdict, one v_readfirstlane -- and twice the scalar
+ * spills (docs/LAB_NOTES.md).  RT_AHEAD_WORD 2 takes the low word of the wave mask of one compare `hit` is made of, which the compare
+ * has written to scalar registers anyway (rt_rect_hot_t_tok, rt_sphere_root_tok: a rect's last bound test, a sphere's discriminant
+ * test): no instruction at all, the same spills, ten pairs fewer in the Cornell unit -- and +0.45 % measured, 2.5 times the spread
+ * where the project asks for four, so it is not the default either.  The token only has to exist no sooner than the leaf's
+ * arithmetic; its value is and-ed with 0.  (0, the default: the mask of `hit`.) */
 #ifndef RT_AHEAD_WORD
 #define RT_AHEAD_WORD 0
 #endif
 template <uint32_t I>
 RT_HD void rt_sweep_ahead_done(RtSweepAhead& a, bool hit, uint32_t word) {
-#if RT_AHEAD_WORD
+#if RT_AHEAD_WORD == 1
     a.tok[I % RT_BOX_FREE_AHEAD] = __builtin_amdgcn_readfirstlane(word);
 #else
     a.tok[I % RT_BOX_FREE_AHEAD] = (uint32_t)rt_wave_mask(hit);
@@ -1275,6 +1342,12 @@ RT_HD void rt_sweep_ahead_done(RtSweepAhead& a, bool hit, uint32_t word) {
 struct RtSweepAhead {};
 template <uint32_t I> RT_HD uint32_t rt_sweep_ahead_index(const RtSweepAhead&) { return I; }
 template <uint32_t I> RT_HD void rt_sweep_ahead_done(RtSweepAhead&, bool, uint32_t) {}
+#endif
+#undef RT_AHEAD_TOKEN_ON
+#if defined(__HIP_DEVICE_COMPILE__) && RT_BOX_FREE_AHEAD > 0 && RT_AHEAD_WORD == 2
+#define RT_AHEAD_TOKEN_ON 1
+#else
+#define RT_AHEAD_TOKEN_ON 0
 #endif
 template <class Topo, class Cfg, uint32_t D, uint32_t I, uint32_t END, class NS, class Inv>
 RT_HD void rt_sweep_free(const RtSceneView& sc, const NS& ns, const RtRayOD& ray, const Inv& inv, double time, double t_min,
@@ -1289,17 +1362,30 @@ RT_HD void rt_sweep_free(const RtSceneView& sc, const NS& ns, const RtRayOD& ray
             const RtNodeHot nd = ns.hot(rt_sweep_ahead_index<I>(ahead));
             double t;
             bool hit;
-#if RT_DIV_SHARED_ON
-            if constexpr (RtInvIsShared<Inv>::value && kind >= RT_XY) hit = rt_rect_hot_t(nd, kind, ray.o, ray.d, inv, true, t_min, best_t, t); /* (a NaN quotient is `big`) */
-            else
+#if RT_AHEAD_TOKEN_ON
+            /* the kinds whose test hands the token out itself (RT_AHEAD_WORD 2); every other leaf's is the mask of its verdict */
+            if constexpr (RtInvIsShared<Inv>::value && kind >= RT_XY) {
+                hit = rt_rect_hot_t_tok(nd, kind, ray.o, ray.d, inv, true, t_min, best_t, t, ahead.tok[I % RT_BOX_FREE_AHEAD]);
+                if (hit) { prev_t = best_t; best_t = t; best_word = rt_vbox_word<Topo>(I); }
+            } else if constexpr (kind == RT_SPHERE) {
+                hit = rt_sphere_root_tok(rt_v3(nd.d[0], nd.d[1], nd.d[2]), nd.d[3], ray.o, ray.d, t_min, best_t, t, ahead.tok[I % RT_BOX_FREE_AHEAD]); /* rt_prim_hot_t's call */
+                bad |= rt_wave_mask(hit && rt_isnan(t));
+                if (hit) { prev_t = best_t; best_t = t; best_word = rt_vbox_word<Topo>(I); }
+            } else
 #endif
             {
-                if constexpr (Cfg::msphere && kind == RT_MSPHERE) hit = rt_prim_t<Cfg>(sc.nodes[I], kind, ray.o, ray.d, time, t_min, best_t, t);
-                else hit = rt_prim_hot_t(nd, kind, ray.o, ray.d, t_min, best_t, t);
-                bad |= rt_wave_mask(hit && rt_isnan(t)); /* accepted as the reference accepts it, and every later leaf after it: not verifiable */
+#if RT_DIV_SHARED_ON
+                if constexpr (RtInvIsShared<Inv>::value && kind >= RT_XY) hit = rt_rect_hot_t(nd, kind, ray.o, ray.d, inv, true, t_min, best_t, t); /* (a NaN quotient is `big`) */
+                else
+#endif
+                {
+                    if constexpr (Cfg::msphere && kind == RT_MSPHERE) hit = rt_prim_t<Cfg>(sc.nodes[I], kind, ray.o, ray.d, time, t_min, best_t, t);
+                    else hit = rt_prim_hot_t(nd, kind, ray.o, ray.d, t_min, best_t, t);
+                    bad |= rt_wave_mask(hit && rt_isnan(t)); /* accepted as the reference accepts it, and every later leaf after it: not verifiable */
+                }
+                if (hit) { prev_t = best_t; best_t = t; best_word = rt_vbox_word<Topo>(I); }
+                rt_sweep_ahead_done<I>(ahead, hit, best_word);
             }
-            if (hit) { prev_t = best_t; best_t = t; best_word = rt_vbox_word<Topo>(I); }
-            rt_sweep_ahead_done<I>(ahead, hit, best_word);
             rt_sweep_free<Topo, Cfg, D, I + 1u, END>(sc, ns, ray, inv, time, t_min, bad, best_t, prev_t, best_word, ahead);
         } else if constexpr (kind <= RT_ROTATE_Y) {
             /* Translate::hit hittable.rs:207-211 / RotateY::hit :238-251: another ray space */
@@ -1648,6 +1734,37 @@ RT_HD double rt_sphere_light_pdf_value(const RtNode& l, RtV3 o, RtV3 v) {
     double solid_angle = RT_R(2.0) * RT_R(RT_PI) * (RT_R(1.0) - cos_theta_max);
     return RT_R(1.0) / solid_angle;
 }
+/* What the sphere light's sampling lobe (rt_random_to_sphere's caller, sphere.rs:92-99) and its pdf (above, sphere.rs:72-90) both compute
+ * from the light and the shaded point o alone: the direction to the centre, its squared length, and the cosine of the cone the sphere
+ * fills -- the statements of the two, in their order.  A Lambertian bounce under a light list with one sphere in it (RtLightShape:
+ * `cone`) evaluates this once for both; in the kernel the two copies sat in different divergent regions and both ran for nearly every wave.
+ * RT_LIGHT_CONE 0 (RT1W_JIT_EXTRA_OPTS=-DRT_LIGHT_CONE=0) is the text without it.  f64 builds with the library's own stream only. */
+#ifndef RT_LIGHT_CONE
+#define RT_LIGHT_CONE 1
+#endif
+#undef RT_LIGHT_CONE_ON
+#if defined(RT_F32) || defined(RT_RNG_REFSTREAM)
+#define RT_LIGHT_CONE_ON 0
+#else
+#define RT_LIGHT_CONE_ON ((RT_LIGHT_CONE) != 0)
+#endif
+struct RtSphereCone { RtV3 direction; double distance_squared, cos_theta_max; };
+struct RtNoCone {};
+RT_HD RtSphereCone rt_sphere_cone(const RtNode& l, RtV3 o) {
+    RtSphereCone k;
+    k.direction = rt_v3(l.d[0], l.d[1], l.d[2]) - o;
+    k.distance_squared = rt_mag2(k.direction);
+    k.cos_theta_max = rt_sqrt(RT_R(1.0) - l.d[3] * l.d[3] / k.distance_squared);
+    return k;
+}
+/* rt_sphere_light_pdf_value with the cone of (l, o) at hand */
+RT_HD double rt_sphere_light_pdf_value(const RtNode& l, const RtSphereCone& k, RtV3 o, RtV3 v) {
+    double t;
+    RtV3 center = rt_v3(l.d[0], l.d[1], l.d[2]);
+    if (!rt_sphere_root_oc2(center, l.d[3], k.distance_squared, o, v, RT_R(0.001), RT_INF, t)) return RT_R(0.0);
+    double solid_angle = RT_R(2.0) * RT_R(RT_PI) * (RT_R(1.0) - k.cos_theta_max);
+    return RT_R(1.0) / solid_angle;
+}
 RT_HD double rt_light_pdf_value(const RtNode& l, RtV3 o, RtV3 v) {
     if (l.kind == RT_XZ) return rt_xz_light_pdf_value(l, o, v);
     if (l.kind == RT_SPHERE) return rt_sphere_light_pdf_value(l, o, v);
@@ -1684,7 +1801,7 @@ RT_HD double rt_lights_pdf_value(const RtSceneView& sc, RtV3 o, RtV3 v) {
  * run time. */
 template <class Topo, class = void>
 struct RtLightShape {
-    static constexpr bool fixed = false, may_xz = true, may_sphere = true, may_default = true;
+    static constexpr bool fixed = false, may_xz = true, may_sphere = true, may_default = true, cone = false;
     RT_HD static bool any(const RtSceneView& sc) { return sc.n_lights > 0u; }
     RT_HD static uint32_t choose(const RtSceneView& sc, RtRng& rng) { return rt_gen_below(rng, sc.n_lights); }
     RT_HD static uint32_t kind(const RtSceneView& sc, uint32_t li) { return sc.lights[li].kind; }
@@ -1700,7 +1817,8 @@ template <class Topo>
 struct RtLightShape<Topo, typename RtVoid<decltype(Topo::light_kind)>::type> {
     static constexpr uint32_t n = Topo::n_lights;
     static constexpr bool fixed = true, may_xz = rt_light_count<Topo>(RT_XZ) > 0u, may_sphere = rt_light_count<Topo>(RT_SPHERE) > 0u,
-                          may_default = rt_light_count<Topo>(RT_XZ) + rt_light_count<Topo>(RT_SPHERE) < n;
+                          may_default = rt_light_count<Topo>(RT_XZ) + rt_light_count<Topo>(RT_SPHERE) < n,
+                          cone = RT_LIGHT_CONE_ON && rt_light_count<Topo>(RT_SPHERE) == 1u; /* exactly one sphere light: one cone per shaded point (rt_sphere_cone) */
     RT_HD static bool any(const RtSceneView&) { return n > 0u; }
     RT_HD static uint32_t choose(const RtSceneView&, RtRng& rng) { return rt_gen_below(rng, n); }
     template <uint32_t I = 0u>
@@ -1722,6 +1840,18 @@ struct RtLightShape<Topo, typename RtVoid<decltype(Topo::light_kind)>::type> {
         } else return sum;
     }
     RT_HD static double pdf_value(const RtSceneView& sc, RtV3 o, RtV3 v) { return pdf_sum<0u>(sc, o, v, RT_R(0.0)); }
+    /* the same sum where the one sphere light's cone at o is at hand (`cone`) */
+    template <uint32_t I>
+    RT_HD static double pdf_sum(const RtSceneView& sc, const RtSphereCone& k, RtV3 o, RtV3 v, double sum) {
+        if constexpr (I < n) {
+            constexpr double weight = RT_R(1.0) / (double)n;
+            double value = RT_R(0.0);
+            if constexpr (Topo::light_kind[I] == RT_XZ) value = rt_xz_light_pdf_value(sc.lights[I], o, v);
+            else if constexpr (Topo::light_kind[I] == RT_SPHERE) value = rt_sphere_light_pdf_value(sc.lights[I], k, o, v);
+            return pdf_sum<I + 1u>(sc, k, o, v, sum + weight * value);
+        } else return sum;
+    }
+    RT_HD static double pdf_value(const RtSceneView& sc, const RtSphereCone& k, RtV3 o, RtV3 v) { return pdf_sum<0u>(sc, k, o, v, RT_R(0.0)); }
 };
 
 /* Where Lambertian materials sit, as the scene-specialised kernel knows it (jit.cpp: Topo::lambert_xy / _xz / _yz: some XY / XZ /
@@ -2205,6 +2335,9 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr, Sp
                 lk = LS::kind(sc, li);
             }
         }
+        /* the one sphere light's cone at h.p, for the lobe and for the pdf below: every Lambertian lane, whichever lobe it drew */
+        typename std::conditional<LS::cone, RtSphereCone, RtNoCone>::type cone;
+        if constexpr (LS::cone) cone = rt_sphere_cone(sc.lights[LS::index(RT_SPHERE, 0u)], h.p);
         if (!LS::may_default || lk == RT_NONE || lk == RT_XZ || lk == RT_SPHERE) {
             rt_rng_reserve(p.rng, rt_rng_need_2u64(p.rng));
             uint64_t q1 = rt_take_u64(p.rng);
@@ -2227,13 +2360,20 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr, Sp
                 double sn, cs;
                 rt_sincos(phi, sn, cs);
                 if (LS::may_sphere && lk == RT_SPHERE) {
-                    const RtNode& l = sc.lights[LS::index(RT_SPHERE, li)];
-                    RtV3 direction = rt_v3(l.d[0], l.d[1], l.d[2]) - h.p;
-                    double distance_squared = rt_mag2(direction);
-                    RtOnb lw = rt_onb_from_w(direction);
-                    double z = RT_R(1.0) + r2 * (rt_sqrt(RT_R(1.0) - l.d[3] * l.d[3] / distance_squared) - RT_R(1.0));
-                    double q = rt_sqrt(RT_R(1.0) - z * z);
-                    dir = rt_onb_local(lw, rt_v3(cs * q, sn * q, z));
+                    if constexpr (LS::cone) {
+                        RtOnb lw = rt_onb_from_w(cone.direction);
+                        double z = RT_R(1.0) + r2 * (cone.cos_theta_max - RT_R(1.0));
+                        double q = rt_sqrt(RT_R(1.0) - z * z);
+                        dir = rt_onb_local(lw, rt_v3(cs * q, sn * q, z));
+                    } else {
+                        const RtNode& l = sc.lights[LS::index(RT_SPHERE, li)];
+                        RtV3 direction = rt_v3(l.d[0], l.d[1], l.d[2]) - h.p;
+                        double distance_squared = rt_mag2(direction);
+                        RtOnb lw = rt_onb_from_w(direction);
+                        double z = RT_R(1.0) + r2 * (rt_sqrt(RT_R(1.0) - l.d[3] * l.d[3] / distance_squared) - RT_R(1.0));
+                        double q = rt_sqrt(RT_R(1.0) - z * z);
+                        dir = rt_onb_local(lw, rt_v3(cs * q, sn * q, z));
+                    }
                 } else {
                     double z = rt_sqrt(RT_R(1.0) - r2);
                     double sr2 = rt_sqrt(r2);
@@ -2245,7 +2385,9 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr, Sp
         }
         double p1 = rt_max(rt_dot(rt_normalize(dir), uvw.w) / RT_R(RT_PI), RT_R(0.0)); /* CosinePdf::value pdf.rs:37-40 */
         if (LS::any(sc)) {
-            double p0 = LS::pdf_value(sc, h.p, dir);
+            double p0;
+            if constexpr (LS::cone) p0 = LS::pdf_value(sc, cone, h.p, dir);
+            else p0 = LS::pdf_value(sc, h.p, dir);
             pdf = RT_R(0.5) * p0 + RT_R(0.5) * p1; /* MixturePdf::value pdf.rs:58-60 */
         } else {
             pdf = p1;
