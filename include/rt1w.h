@@ -211,6 +211,7 @@ void rt1w_context_destroy(rt1w_context* c);
 #define RT1W_CLASSIC_WALK 128u /* tests/ablation: sphere scenes (random_scene) walk their BVH with the pair walk of csrc/rt_walk_pair.h by default (box work and leaf work in separate phases, inner boxes in f32 rounded outward, every sphere gated by its group's own f64 box at the reference's moment: the same frames bit for bit, stats.sorted bit 7 says it ran); this flag keeps the one-entry-per-step walk.  Likewise scenes whose every ConstantMedium is bounded by a bare Sphere (final_scene) run stack-walk kernels built without the general boundary walks (rt_flat.h: RtCfgSphereMedia; stats.sorted bit 8); this flag keeps the general kernels */
 #define RT1W_PROBE_COHERENT 0x40000000u /* MEASUREMENT ONLY -- the frame written is NOT the image: every wave's 64 lanes trace the SAME path (one pixel of every 8x8 block, each 64 times), so the kernel runs without divergence and its instruction count per traced segment (rocprofv3 SQ_INSTS_VALU x 64 / stats.segments) is what ONE path needs in this kernel's code: the `necessary` side of bench.py's `roofline.valu` (tools/bench_pmc.sh).  Replaces nothing of the reference: a property of this implementation's measurement */
 #define RT1W_NO_NODE_CACHE 0x10000u /* tests/ablation: big scenes' stack-walk kernels keep the most visited node records in LDS (csrc/rt_walk_table.h: ranked by a visit count at context creation; stats.sorted bit 10 says the cache ran; same frames bit for bit); this flag keeps the kernels that read every record from memory */
+#define RT1W_TILES_SPECIALISED 0x40000u /* rt1w_render_tiles[_device] and the adaptive entries whose rounds go through them: run the tile-list form of the scene-specialised kernel where the context can load one from a kernel cache (the build's, or the user's after rt1w_context_specialise with RT1W_SPECIALISE_TILES), the generic tile-list kernel otherwise -- the same bits either way, a tile render never compiles, stats.sorted bit 2 says which ran.  Excludes RT1W_GENERIC.  The rectangle entries ignore the bit */
 #define RT1W_UNSORTED 2u  /* tests/ablation: use the plain persistent kernel (no workgroup-level path reordering: neither the reordering kernel of the small scenes nor, for sphere-media scenes such as final_scene, the reordering of the finished paths at the end of every slice of the stack walk, stats.sorted bit 9) */
 #define RT1W_FORCE_VARIANT(v) ((((uint32_t)(v)) + 1u) << 8) /* tests: force kernel variant v (must be valid for the scene) */
 
@@ -273,11 +274,15 @@ typedef struct rt1w_tile { uint32_t x0, y0, sample_offset, reserved; } rt1w_tile
  * CONTRACT: tile k's pixels inside the frame are bit-identical to rt1w_render_device of the rectangle (x0_k, y0_k, min(tile, width - x0_k),
  * min(tile, height - y0_k)) with the same spp and seed, the tile's absolute sample offset and the same chunk passed explicitly.  The order
  * of the list, repeats of a tile with other offsets and partial_mib do not change a bit.
- * Flags: 0, RT1W_OUT_SUM, RT1W_GENERIC (a no-op: the tile entries always run the generic kernels -- the scene-specialised ones have no
- * tile form and render the same bits); any other flag, interleaved strips or a non-zero `reserved`: RT1W_ERR_INVALID;
- * RT1W_PRECISION_F32: RT1W_ERR_UNSUPPORTED.
+ * Flags: 0, RT1W_OUT_SUM, RT1W_GENERIC (a no-op: without RT1W_TILES_SPECIALISED the tile entries run the generic kernels, which render
+ * the same bits as the scene-specialised ones), RT1W_TILES_SPECIALISED (alongside RT1W_OUT_SUM or alone: the tile-list form of the
+ * scene-specialised kernel if the context can load one from a kernel cache -- looked up at the first such call, never compiled here --
+ * and the generic tile-list kernel otherwise, without an error; the contract above holds unchanged; with RT1W_GENERIC:
+ * RT1W_ERR_INVALID); any other flag, interleaved strips or a non-zero `reserved`: RT1W_ERR_INVALID; RT1W_PRECISION_F32:
+ * RT1W_ERR_UNSUPPORTED.
  * stats: paths = pixels inside the frame x spp; segments = rays traced (the sum over the per-rectangle renders); passes = launches of the
- * trace kernel; variant / sorted / grid / block / chunk / n_chunks as rt1w_render with RT1W_GENERIC. */
+ * trace kernel; variant / sorted / grid / block / chunk / n_chunks as rt1w_render with RT1W_GENERIC, or, where the specialised tile-list
+ * kernel ran (sorted bit 2), that kernel's sorted bits, grid and block. */
 int rt1w_render_tiles(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out, rt1w_stats* stats);
 int rt1w_render_tiles_device(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, void* d_out, rt1w_stats* stats);
 
@@ -573,8 +578,10 @@ int rt1w_accum_merge_tiles_device(rt1w_context* c, uint32_t width, uint32_t heig
  *   One launch per round.  With RT1W_ADAPTIVE_ONE_LAUNCH in `flags` every ROUND is instead one rt1w_render_tiles_device of all its taken
  *            tiles (each with sample_offset = m * batch_spp, RT1W_OUT_SUM, the same spp and chunk) and one rt1w_accum_merge_tiles_device;
  *            the pilot stays whole-frame.  Frame, spp map, paths, segments and n_chunks are the bits of the call without the flag;
- *            passes falls to the pilot's launches + one per round (times its sample passes).  The tile entries run the generic
- *            kernels, so p->flags must then be 0 or RT1W_GENERIC.  rt1w_adaptive_select accepts the flag and ignores it. */
+ *            passes falls to the pilot's launches + one per round (times its sample passes).  p->flags must then be 0, RT1W_GENERIC
+ *            or RT1W_TILES_SPECIALISED: the flags go to the renders as they are, the pilot's rectangle renders ignore the last and the
+ *            rounds' tile lists run the tile-list form of the scene-specialised kernel with it (the generic kernels without: the same
+ *            bits).  rt1w_adaptive_select accepts the flag and ignores it. */
 #define RT1W_ADAPTIVE_ONE_LAUNCH 0x100u
 typedef struct rt1w_adaptive_params {
     uint32_t size;           /* sizeof(rt1w_adaptive_params) */
@@ -677,7 +684,8 @@ int rt1w_tile_error_map_device(rt1w_context* c, uint32_t width, uint32_t height,
  *   4. the round that takes nothing ends the loop: ITS filtered frame and error map are the result -- no further filter pass is made;
  *   5. one device->host copy each into out_rgb[height][width][3] and, if not NULL, out_spp[height][width] and out_err[height][width].
  * Every pixel's count is a multiple of 2 n and m_A == m_B at every estimate.  Bit-identical to composing these public entries.
- * Because the rounds go through the tile entries, p->flags must be 0 or RT1W_GENERIC; everything rt1w_render_adaptive refuses is refused
+ * Because the rounds go through the tile entries, p->flags must be 0, RT1W_GENERIC or RT1W_TILES_SPECIALISED (the rounds on the tile-list
+ * form of the scene-specialised kernel: the same bits); everything rt1w_render_adaptive refuses is refused
  * here too: all RT1W_ERR_INVALID.  stats as there: the renders' sums (paths = the samples spent, segments, passes = the pilot's launches +
  * one per round, times its sample passes); kernel_ms every kernel of the call, every filter pass included; total_ms the whole call;
  * n_chunks = the number of ROUNDS; grid / block of the filter's level kernel.  Buffers are the context's, grown on demand. */
@@ -900,6 +908,7 @@ int rt1w_host_unregister(void* p);
  * generic kernels: RT1W_ERR_UNSUPPORTED.  RT1W_GENERIC in rt1w_render_params.flags selects the generic kernel for one
  * render. */
 #define RT1W_SPECIALISE_CACHED_ONLY 1u /* do not run the compiler: RT1W_ERR_STATE on a cache miss */
+#define RT1W_SPECIALISE_TILES 2u /* after the f64 kernel (and the optional f32 one) load the kernel's tile-list form too (RT1W_TILES_SPECIALISED), compiling it unless RT1W_SPECIALISE_CACHED_ONLY is set; its failure is the call's error.  The info describes the rectangle kernel as without the flag; compile_ms includes the tile form's compile */
 typedef struct rt1w_specialise_info {
     char key[24];        /* cache key: hash of the generated source, the library's embedded headers and the compiler options */
     uint32_t active;     /* 1: renders on this context now use the specialised kernel */
@@ -915,6 +924,12 @@ int rt1w_scene_kernel_key(const rt1w_scene* s, char out[24]);
  * specialised kernel is compiled around, as text.  No GPU needed.  Returns bytes written (no NUL), or the needed size if buf==NULL;
  * RT1W_ERR_UNSUPPORTED for scenes of more than 256 nodes. */
 int64_t rt1w_scene_kernel_source(const rt1w_scene* s, int f32, char* buf, uint64_t cap);
+/* the same two for the kernel's TILE-LIST FORM (f64 only; RT1W_TILES_SPECIALISED): the same tables around a kernel that takes the tile
+ * table of rt1w_render_tiles as its last argument -- the list stands in for the row hand-out of src/main.rs:957-963, a tile's record
+ * saying where its pixels lie in the image.  Another text, so another key and another `sweep_<key>.hsaco`.  No GPU needed; the
+ * refusals of the two above. */
+int rt1w_scene_kernel_key_tiles(const rt1w_scene* s, char out[24]);
+int64_t rt1w_scene_kernel_source_tiles(const rt1w_scene* s, char* buf, uint64_t cap);
 
 /* ---- output side (src/color.rs) ---- */
 

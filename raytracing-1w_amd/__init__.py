@@ -54,6 +54,8 @@ NO_NODE_CACHE = 0x10000  # big scenes: the stack-walk kernels without the most v
 CLASSIC_WALK = 128  # sphere scenes: the one-entry-per-step walk instead of the pair walk (rt_walk_pair.h)
 WAVEFRONT = 16  # big scenes: path state queued in HBM, trace / shade kernels per bounce
 SPECIALISE_CACHED_ONLY = 1
+SPECIALISE_TILES = 2  # rt1w_context_specialise: load (or compile) the kernel's tile-list form too
+TILES_SPECIALISED = 0x40000  # tile entries and the adaptive entries' rounds: the tile-list form of the scene-specialised kernel where a kernel cache has one
 AOV_CHANNELS = 8  # rt1w_render_aov: albedo rgb, normal xyz, depth, coverage per pixel
 DENOISE_KEEP_ALBEDO = 1  # rt1w_denoise: no albedo demodulation
 ADAPTIVE_ONE_LAUNCH = 0x100  # rt1w_adaptive_params.flags: every round is one rt1w_render_tiles launch and one rt1w_accum_merge_tiles
@@ -145,6 +147,8 @@ _sig("rt1w_context_destroy", None, _P)
 _sig("rt1w_context_specialise", C.c_int, _P, C.c_uint32, C.POINTER(SpecialiseInfo))
 _sig("rt1w_scene_kernel_key", C.c_int, _P, C.c_char * 24)
 _sig("rt1w_scene_kernel_source", C.c_int64, _P, C.c_int, _P, C.c_uint64)
+_sig("rt1w_scene_kernel_key_tiles", C.c_int, _P, C.c_char * 24)
+_sig("rt1w_scene_kernel_source_tiles", C.c_int64, _P, _P, C.c_uint64)
 _sig("rt1w_default_chunk", C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
 _sig("rt1w_scene_default_chunk", C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32)
 _sig("rt1w_render", C.c_int, _P, C.POINTER(RenderParams), _P, C.POINTER(Stats))
@@ -594,18 +598,24 @@ class Scene:
         _ck(_lib.rt1w_scene_get_info(self._h, C.byref(i)))
         return {n: getattr(i, n) for n, _ in SceneInfo._fields_}
 
-    def kernel_key(self):
-        """Cache key of this scene's specialised kernel (sweep_<key>.hsaco); raises ERR_UNSUPPORTED for big scenes."""
+    def kernel_key(self, tiles=False):
+        """Cache key of this scene's specialised kernel (sweep_<key>.hsaco); raises ERR_UNSUPPORTED for big scenes.
+        tiles: the key of the kernel's tile-list form (rt1w_scene_kernel_key_tiles)."""
         buf = (C.c_char * 24)()
-        _ck(_lib.rt1w_scene_kernel_key(self._h, buf))
+        _ck((_lib.rt1w_scene_kernel_key_tiles if tiles else _lib.rt1w_scene_kernel_key)(self._h, buf))
         return buf.value.decode()
 
-    def kernel_source(self, f32=False):
-        """The translation unit generated for this scene's specialised kernel (struct TopoJit: kind, skip, reuse), as text."""
-        n = _lib.rt1w_scene_kernel_source(self._h, int(f32), None, 0)
+    def kernel_source(self, f32=False, tiles=False):
+        """The translation unit generated for this scene's specialised kernel (struct TopoJit: kind, skip, reuse), as text.
+        tiles: the unit of the kernel's tile-list form (rt1w_scene_kernel_source_tiles; f64 only)."""
+        if tiles and f32:
+            raise ValueError("the tile-list form of the specialised kernel is f64 only")
+        ask = (lambda buf, cap: _lib.rt1w_scene_kernel_source_tiles(self._h, buf, cap)) if tiles else \
+              (lambda buf, cap: _lib.rt1w_scene_kernel_source(self._h, int(f32), buf, cap))
+        n = ask(None, 0)
         _ck(int(n))
         buf = C.create_string_buffer(int(n) + 1)
-        _ck(int(_lib.rt1w_scene_kernel_source(self._h, int(f32), buf, int(n))))
+        _ck(int(ask(buf, int(n))))
         return buf.raw[:int(n)].decode()
 
     def flat(self, what):
@@ -644,12 +654,13 @@ class Context:
         sr, sp = strips if strips is not None else (0, 0)
         return RenderParams(width, height, x0, y0, tw, th, spp, sample_offset, max_depth, global_seed, chunk, flags, sr, sp, 1 if f32 else 0, int(partial_mib))
 
-    def specialise(self, cached_only=False):
+    def specialise(self, cached_only=False, tiles=False):
         """Load (from the kernel cache) or compile (hiprtc, 3-5 s) the kernel specialised for this scene's topology
         (rt1w_context_specialise).  Returns the info dict; raises Rt1wError for scenes of more than 256 nodes
-        (ERR_UNSUPPORTED) or, with cached_only, on a cache miss (ERR_STATE)."""
+        (ERR_UNSUPPORTED) or, with cached_only, on a cache miss (ERR_STATE).  tiles: the kernel's tile-list form too
+        (RT1W_SPECIALISE_TILES: what render_tiles(specialised=True) runs)."""
         info = SpecialiseInfo()
-        _ck(_lib.rt1w_context_specialise(self._h, SPECIALISE_CACHED_ONLY if cached_only else 0, C.byref(info)))
+        _ck(_lib.rt1w_context_specialise(self._h, (SPECIALISE_CACHED_ONLY if cached_only else 0) | (SPECIALISE_TILES if tiles else 0), C.byref(info)))
         return {"key": info.key.decode(), "active": bool(info.active), "from_cache": bool(info.from_cache),
                 "compile_ms": info.compile_ms, "grid": info.grid, "vgprs": info.vgprs}
 
@@ -716,12 +727,13 @@ class Context:
         return _stats_dict(st)
 
     def render_tiles(self, width, height, spp, tile, tiles, max_depth=50, sample_offset=0, global_seed=0, chunk=0, out_sum=False, generic=False,
-                     partial_mib=0, flags=0, strips=None, f32=False):
+                     partial_mib=0, flags=0, strips=None, f32=False, specialised=False):
         """A list of square tiles of side `tile` in one launch (rt1w_render_tiles): `tiles` = Tile objects or (x0, y0, sample_offset)
-        tuples.  Returns (float64 [n, tile, tile, 3], stats); tile k's row 0 = image row y0_k, pixels beyond the frame's edge are +0.0."""
+        tuples.  Returns (float64 [n, tile, tile, 3], stats); tile k's row 0 = image row y0_k, pixels beyond the frame's edge are +0.0.
+        specialised: RT1W_TILES_SPECIALISED -- the tile-list form of the scene-specialised kernel where a kernel cache has one."""
         p = self._params(width, height, spp, max_depth, None, sample_offset, global_seed, chunk, out_sum, generic=generic, partial_mib=partial_mib,
                          strips=strips, f32=f32)
-        p.flags |= flags
+        p.flags |= flags | (TILES_SPECIALISED if specialised else 0)
         rec, n = _tile_list(tiles)
         out = np.empty((n, tile, tile, 3), dtype=np.float64)
         st = Stats()
@@ -729,10 +741,10 @@ class Context:
         return out, _stats_dict(st)
 
     def render_tiles_device(self, d_ptr, width, height, spp, tile, tiles, max_depth=50, sample_offset=0, global_seed=0, chunk=0, out_sum=False,
-                            generic=False, partial_mib=0, flags=0):
+                            generic=False, partial_mib=0, flags=0, specialised=False):
         """Same, into device memory `d_ptr` (int address) of n * tile * tile * 3 doubles; the list itself is host memory.  Returns the stats."""
         p = self._params(width, height, spp, max_depth, None, sample_offset, global_seed, chunk, out_sum, generic=generic, partial_mib=partial_mib)
-        p.flags |= flags
+        p.flags |= flags | (TILES_SPECIALISED if specialised else 0)
         rec, n = _tile_list(tiles)
         st = Stats()
         _ck(_lib.rt1w_render_tiles_device(self._h, C.byref(p), tile, rec, n, C.c_void_p(d_ptr), C.byref(st)))

@@ -6,7 +6,7 @@
  *   rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B]
  *        [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic]
  *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
- *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]]]
+ *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]]
  *        [--frames N --orbit DEG [--denoise]]
  * --frames N --orbit DEG renders an animation of N frames through rt1w_render_temporal: before frame k look_from is turned about the
  * vertical axis through look_at by k * DEG degrees (rt1w_context_set_camera; the scene, its upload and its kernel are frame 0's), the
@@ -21,6 +21,8 @@
  * every sample a pixel has received (rt1w_render_adaptive_guided) instead of the pilot's.
  * --cross-filter is the same plan with the cross-filtered half buffers in every round (rt1w_render_adaptive_cross: each half is filtered with
  * the other's colour term, the image is the mean of the two); it excludes --filtered-error.
+ * --specialised-tiles (with --adaptive B and one of --one-launch, --filtered-error, --cross-filter) runs the rounds' tile lists on the
+ * tile-list form of the scene-specialised kernel where the kernel cache has one (RT1W_TILES_SPECIALISED; the same frame, bit for bit).
  * --err-out FILE writes the per-pixel error map of that frame as text, "width height" and then one value per pixel, top row first.
  * --denoise renders through rt1w_render_denoised: the frame, its first-hit feature buffers and the feature-guided filter in one call
  * (default 5 levels), then the PPM of the filtered frame.  --deep-guides [N] (implies --denoise) takes the guides through glass and
@@ -56,6 +58,7 @@ int main(int argc, char** argv) {
     bool filtered_error = false;     /* --adaptive: rt1w_render_adaptive_filtered */
     bool cross_filter = false;       /* --adaptive: rt1w_render_adaptive_cross */
     bool full_guides = false;        /* --adaptive --filtered-error: rt1w_render_adaptive_guided */
+    bool specialised_tiles = false;  /* --adaptive with rounds through the tile entries: RT1W_TILES_SPECIALISED */
     std::string err_path;
     long frames = 0;                 /* > 0: an animation through rt1w_render_temporal */
     double orbit = 0.0;
@@ -100,13 +103,14 @@ int main(int argc, char** argv) {
         else if (a == "--filtered-error") filtered_error = true;
         else if (a == "--cross-filter") cross_filter = true;
         else if (a == "--full-guides") full_guides = true;
+        else if (a == "--specialised-tiles") specialised_tiles = true;
         else if (a == "--err-out") err_path = next("--err-out");
         else if (a == "--frames") frames = std::atol(next("--frames"));
         else if (a == "--orbit") orbit = std::atof(next("--orbit"));
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--target-error") target_error = std::atof(next("--target-error"));
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]]] [--frames N --orbit DEG [--denoise]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]] [--frames N --orbit DEG [--denoise]]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -143,6 +147,12 @@ int main(int argc, char** argv) {
     p.width = (uint32_t)width; p.height = (uint32_t)height; p.tile_w = p.width; p.tile_h = p.height;
     p.spp = (uint32_t)spp; p.max_depth = (uint32_t)depth; p.global_seed = (uint32_t)seed;
     if (generic) p.flags |= RT1W_GENERIC;
+    if (specialised_tiles) {
+        if (adaptive < 0 || !(one_launch || filtered_error || cross_filter) || generic) {
+            std::fprintf(stderr, "rt1w: --specialised-tiles goes with --adaptive B and --one-launch, --filtered-error or --cross-filter, without --generic\n"); return 2;
+        }
+        p.flags |= RT1W_TILES_SPECIALISED;
+    }
     if (reference_stream) p.flags |= RT1W_RNG_REFERENCE;
     if (f32) p.precision = RT1W_PRECISION_F32;
     rt1w_stats st;

@@ -57,8 +57,8 @@ enum RtWalkForm {
     RT_N_WALKS
 };
 
-/* a scene-specialised kernel (jit.cpp) of one precision.  The first five members say how loading it differs between the two
- * (load_specialised) */
+/* a scene-specialised kernel (jit.cpp) in one of its forms: f64, f32, and the f64 tile-list form.  The first six members say how
+ * loading it differs between them (load_specialised) */
 struct RtJitSlot {
     const char* what;          /* for error texts */
     bool f32;                  /* the f32 build of the kernel */
@@ -66,6 +66,7 @@ struct RtJitSlot {
     bool block_from_bounds;    /* f64: the workgroup size is the kernel's launch bound = its sort domain (experiments build it for 512) */
     bool sticky;               /* f32: honours RT1W_NO_JIT, renders look at the caches once per context, a failure is remembered with
                                 * its reason (rt1w_context_specialise reports it) */
+    bool tiles = false;        /* the tile-list form: takes the tile list in last place, whose size is checked against the unit's own */
     std::string src, key;      /* generated source (empty: scene not eligible), cache key */
     hipModule_t mod = nullptr;
     RtKernel k{};              /* k.jit != nullptr once loaded */
@@ -119,6 +120,9 @@ struct rt1w_context {
     RtKernel k32x[RT_N_VARIANTS][3] = {}; /* the same slots for the kernels a registered rt1w_f32_kernel_fn hands out (rt1w_internal.h) */
     RtJitSlot jit{"specialised kernel", false, true, true, false};
     RtJitSlot jit32{"f32 specialised kernel", true, false, false, true}; /* loaded only where `jit` is */
+    /* the tile-list form (rt1w_render_tiles with RT1W_TILES_SPECIALISED): from the caches at the first tile render that asks for it, or
+     * from the compiler in rt1w_context_specialise with RT1W_SPECIALISE_TILES; `tried`: the caches have been looked at and had none */
+    RtJitSlot jit_tiles{"tile-list specialised kernel", false, true, true, false, true};
 };
 
 namespace rt1w {

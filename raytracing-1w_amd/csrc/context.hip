@@ -483,8 +483,18 @@ int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::Ji
         if (!(ok = hip_ok(hipModuleLoadData(&s.mod, code.data()), ("hipModuleLoadData(" + what + ")").c_str()))) s.mod = nullptr;
     }
     RtKernel k{RT_SORT_BLOCK, RT_BIT_SORTED | RT_BIT_JIT | (s.f32 ? RT_BIT_F32 : 0u), nullptr, nullptr, s.f32};
+    k.tiles = s.tiles;
     int max_threads = 0;
     ok = ok && hip_ok(hipModuleGetFunction(&k.jit, s.mod, "rt_jit_sorted"), ("hipModuleGetFunction(" + what + ")").c_str());
+    if (ok && s.tiles) {
+        /* the unit's own RtTileList against the bytes render_launch will pass, as tile_kernel_of checks the built-in forms */
+        hipDeviceptr_t dptr = nullptr;
+        size_t bytes = 0;
+        unsigned int theirs = 0u;
+        ok = hip_ok(hipModuleGetGlobal(&dptr, &bytes, s.mod, "rt_jit_tile_list_bytes"), ("hipModuleGetGlobal(" + what + ")").c_str()) &&
+             bytes == sizeof theirs && hip_ok(hipMemcpy(&theirs, dptr, sizeof theirs, hipMemcpyDeviceToHost), ("hipMemcpy(" + what + ")").c_str());
+        if (ok && theirs != (unsigned int)sizeof(RtTileArg)) { rt1w::set_error(what + " built against another tile-list layout"); ok = false; }
+    }
     if (ok && s.block_from_bounds && hipFuncGetAttribute(&max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, k.jit) == hipSuccess &&
         (max_threads == 512 || max_threads == 128)) k.block = max_threads;
     if (ok) ok = (k.grid = kernel_grid(c, k)) > 0;
@@ -533,6 +543,20 @@ int render_wavefront(rt1w_context* c, const rt1w_render_params* p, const RtLaunc
     return RT1W_OK;
 }
 
+/* RT1W_TILES_SPECIALISED: whether the context has the tile-list form of its scene-specialised kernel, looking in the kernel caches the
+ * first time it is asked (the lazy load of jit32: context creation pays no third module load, a render never compiles).  A miss is
+ * remembered and is no error -- the generic tile form runs; rt1w_context_specialise with RT1W_SPECIALISE_TILES loads it later */
+bool specialised_tiles(rt1w_context* c) {
+    RtJitSlot& s = c->jit_tiles;
+    if (s.k.jit) return true;
+    if (s.tried || s.src.empty()) return false;
+    s.tried = true;
+    rt1w::JitInfo info;
+    if (load_specialised(c, s, false, info) == RT1W_OK) return true;
+    (void)hipGetLastError(); /* a cached object the driver refused is a miss like any other: nothing of it is left for the next launch check */
+    return false;
+}
+
 /* the tile-list form of the kernel a plan holds (one of k64 / pw_k: the plan was made with RT1W_GENERIC), resolved at its first use */
 int tile_kernel_of(rt1w_context* c, RtKernel& k) {
     if (rt1w_internal_tile_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_tile_sizeof(1) != sizeof(RtFrame) ||
@@ -574,7 +598,8 @@ int render_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32_t t
     if (p->spp == 0) { set_error("spp must be > 0"); return RT1W_ERR_INVALID; }
     if (p->precision == RT1W_PRECISION_F32) { set_error("rt1w_render_tiles: the tile-list kernels are f64 only"); return RT1W_ERR_UNSUPPORTED; }
     if (p->precision != RT1W_PRECISION_F64) { set_error("unknown precision"); return RT1W_ERR_UNSUPPORTED; }
-    if (p->flags & ~(RT1W_OUT_SUM | RT1W_GENERIC)) { set_error("rt1w_render_tiles: flags 0, RT1W_OUT_SUM or RT1W_GENERIC only"); return RT1W_ERR_INVALID; }
+    if (p->flags & ~(RT1W_OUT_SUM | RT1W_GENERIC | RT1W_TILES_SPECIALISED)) { set_error("rt1w_render_tiles: flags 0, RT1W_OUT_SUM or RT1W_GENERIC only"); return RT1W_ERR_INVALID; }
+    if ((p->flags & RT1W_TILES_SPECIALISED) && (p->flags & RT1W_GENERIC)) { set_error("rt1w_render_tiles: RT1W_TILES_SPECIALISED and RT1W_GENERIC exclude each other"); return RT1W_ERR_INVALID; }
     if (p->strip_rows || p->strip_period) { set_error("rt1w_render_tiles takes no interleaved strips"); return RT1W_ERR_INVALID; }
     if (tile < 16u || tile > 256u || tile % 16u) { set_error("rt1w_render_tiles: tile must be a multiple of 16 in 16 .. 256"); return RT1W_ERR_INVALID; }
     if (n_tiles < 1u || n_tiles > RT_TILES_MAX) { set_error("rt1w_render_tiles: n_tiles must be 1 .. 2^20"); return RT1W_ERR_INVALID; }
@@ -587,16 +612,18 @@ int render_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32_t t
         if ((unsigned long long)p->sample_offset + t.sample_offset + p->spp > 0xFFFFFFFFull) { set_error("sample index overflow"); return RT1W_ERR_INVALID; }
         inside += (unsigned long long)(p->width - t.x0 < tile ? p->width - t.x0 : tile) * (p->height - t.y0 < tile ? p->height - t.y0 : tile);
     }
-    /* the list as ONE virtual tile of width `tile` and height n_tiles x tile, on the generic kernels (the specialised ones have no tile
-     * form; their frames are the same bits), chunked as the WHOLE frame is */
+    /* the list as ONE virtual tile of width `tile` and height n_tiles x tile, chunked as the WHOLE frame is.  The plan is the one of a
+     * render with RT1W_GENERIC, whose kernel has a tile-list form in context_tiles.hip; with RT1W_TILES_SPECIALISED the tile-list form
+     * of the scene-specialised kernel takes its place where a kernel cache has one (the same bits; never compiled here) */
     rt1w_render_params q = *p;
     q.x0 = 0u; q.y0 = 0u; q.tile_w = tile; q.tile_h = n_tiles * tile;
-    q.flags |= RT1W_GENERIC;
+    q.flags = (q.flags & ~RT1W_TILES_SPECIALISED) | RT1W_GENERIC;
     if (!q.chunk) q.chunk = c->variant >= 2 ? 1u : rt1w_default_chunk(p->width, p->height, p->spp);
     RtLaunch L;
     int rc = render_plan(c, &q, L);
     if (rc < 0) return rc;
-    if ((rc = tile_kernel_of(c, L.k)) < 0) return rc;
+    if ((p->flags & RT1W_TILES_SPECIALISED) && specialised_tiles(c)) L.k = c->jit_tiles.k;
+    else if ((rc = tile_kernel_of(c, L.k)) < 0) return rc;
     RtLane& l = c->lane[0];
     if ((rc = tiles_upload(c, tiles, n_tiles, &L.tl.rec)) < 0) return rc;
     L.tl.side = tile; L.tl.n = n_tiles;
@@ -713,6 +740,7 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
     if (rt1w::jit_eligible(*s)) {
         c->jit.src = rt1w::jit_source(*s);
         c->jit32.src = rt1w::jit_source(*s, true);
+        c->jit_tiles.src = rt1w::jit_source(*s, false, true); /* loaded at the first tile render that asks for it (specialised_tiles) */
         rt1w::JitInfo info;
         (void)load_specialised(c, c->jit, false, info); /* a cache hit is used from the first render on; a miss costs nothing */
     }
@@ -733,6 +761,7 @@ void rt1w_context_destroy(rt1w_context* c) {
     lane_destroy(c->lane[1]);
     if (c->jit.mod) (void)hipModuleUnload(c->jit.mod);
     if (c->jit32.mod) (void)hipModuleUnload(c->jit32.mod);
+    if (c->jit_tiles.mod) (void)hipModuleUnload(c->jit_tiles.mod);
     if (c->ev_first) (void)hipEventDestroy(c->ev_first);
     delete c;
 }
@@ -746,6 +775,11 @@ int rt1w_context_specialise(rt1w_context* c, uint32_t flags, rt1w_specialise_inf
     if (rc == RT1W_OK && c->jit.k.jit) { /* optional: a failure leaves f32 renders on the generic kernels */
         rt1w::JitInfo info32;
         (void)load_specialised(c, c->jit32, !(flags & RT1W_SPECIALISE_CACHED_ONLY), info32);
+    }
+    if (rc == RT1W_OK && (flags & RT1W_SPECIALISE_TILES)) { /* asked for: its failure is the call's */
+        rt1w::JitInfo info_t;
+        rc = load_specialised(c, c->jit_tiles, !(flags & RT1W_SPECIALISE_CACHED_ONLY), info_t);
+        info.compile_ms += info_t.compile_ms;
     }
     if (out) {
         memset(out, 0, sizeof *out);

@@ -10,7 +10,9 @@
  *
  * Built: the kernels render_plan reaches with flags 0 on a context without a scene-specialised kernel -- the reordering kernels of V0 and
  * V1, the stack walks that reorder the finished paths (with and without the node cache, with and without the sphere-media build), the
- * pair walks of sphere scenes, and the plain kernel V4 falls back to.  The scene-specialised kernels have no tile form. */
+ * pair walks of sphere scenes, and the plain kernel V4 falls back to.  The tile-list form of a scene-specialised kernel is generated and
+ * compiled like its rectangle form (jit.cpp: jit_source with `tiles`, the two switches below ahead of its includes) and is no part of
+ * this unit. */
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>

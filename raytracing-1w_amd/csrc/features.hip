@@ -94,13 +94,17 @@ const struct { uint32_t bit; const char* name; bool denoised; } g_flags[] = {
     {RT1W_OUT_SUM, "RT1W_OUT_SUM", true}, {RT1W_UNSORTED, "RT1W_UNSORTED", false}, {RT1W_LDS_NODES, "RT1W_LDS_NODES", false},
     {RT1W_GENERIC, "RT1W_GENERIC", false}, {RT1W_WAVEFRONT, "RT1W_WAVEFRONT", false}, {RT1W_OUT_FRAME, "RT1W_OUT_FRAME", true},
     {RT1W_RNG_REFERENCE, "RT1W_RNG_REFERENCE", true}, {RT1W_CLASSIC_WALK, "RT1W_CLASSIC_WALK", false},
-    {RT1W_NO_NODE_CACHE, "RT1W_NO_NODE_CACHE", false}, {RT1W_PROBE_COHERENT, "RT1W_PROBE_COHERENT", true}};
+    {RT1W_NO_NODE_CACHE, "RT1W_NO_NODE_CACHE", false}, {RT1W_PROBE_COHERENT, "RT1W_PROBE_COHERENT", true},
+    {RT1W_TILES_SPECIALISED, "RT1W_TILES_SPECIALISED", false}};
 /* refuses the first flag of `flags` that has a name (denoised_only: and that rt1w_render_denoised refuses), as "<name><tail>" */
 int refuse_named_flag(uint32_t flags, bool denoised_only, const char* tail) {
     for (const auto& k : g_flags)
         if ((flags & k.bit) && (k.denoised || !denoised_only)) { set_error(std::string(k.name) + tail); return RT1W_ERR_INVALID; }
     return RT1W_OK;
 }
+/* the p->flags of an adaptive entry whose rounds go through the tile entries: 0, RT1W_GENERIC, or RT1W_TILES_SPECIALISED (the rounds on
+ * the tile-list form of the scene-specialised kernel; the pilot's rectangle renders ignore the bit) */
+bool tile_round_flags_ok(uint32_t flags) { return flags == 0u || flags == RT1W_GENERIC || flags == RT1W_TILES_SPECIALISED; }
 /* the one flag the AOV entries take besides RT1W_FORCE_VARIANT: everything else is named and refused */
 int aov_check_flags(uint32_t flags) {
     const uint32_t bad = flags & ~(0xFFu << 8);
@@ -447,7 +451,7 @@ int render_adaptive(rt1w_context* c, const rt1w_render_params* p, const rt1w_ada
     if (p) { q = *p; q.spp = plan.batch_spp; } /* p->spp is ignored: validated as one batch */
     if ((rc = denoised_render_validate(c, p ? &q : nullptr, out_rgb)) < 0) return rc;
     if (p->x0 || p->y0 || p->tile_w != p->width || p->tile_h != p->height) { set_error("rt1w_render_adaptive takes the whole frame (x0 = y0 = 0, tile_w = width, tile_h = height)"); return RT1W_ERR_INVALID; }
-    if (plan.one_launch && (p->flags & ~RT1W_GENERIC)) { set_error("adaptive: with RT1W_ADAPTIVE_ONE_LAUNCH p->flags must be 0 or RT1W_GENERIC (rt1w_render_tiles runs the generic kernels)"); return RT1W_ERR_INVALID; }
+    if (plan.one_launch && !tile_round_flags_ok(p->flags)) { set_error("adaptive: with RT1W_ADAPTIVE_ONE_LAUNCH p->flags must be 0 or RT1W_GENERIC (rt1w_render_tiles runs the generic kernels)"); return RT1W_ERR_INVALID; }
     if ((unsigned long long)p->sample_offset + plan.max_spp > 0xFFFFFFFFull) { set_error("adaptive: sample_offset + max_spp exceeds 2^32 - 1"); return RT1W_ERR_INVALID; }
     const uint32_t W = p->width, H = p->height;
     rt1w_denoise_params dp;
@@ -701,7 +705,7 @@ int render_adaptive_filtered(rt1w_context* c, const rt1w_render_params* p, const
     rt1w_render_params q;
     if (p) { /* what the parameters alone decide comes before anything that needs the context */
         if ((rc = refuse_named_flag(p->flags, true, " does not apply to rt1w_render_denoised")) < 0) return rc;
-        if (p->flags & ~RT1W_GENERIC) { set_error(std::string(name) + ": p->flags must be 0 or RT1W_GENERIC (the rounds go through rt1w_render_tiles, which runs the generic kernels)"); return RT1W_ERR_INVALID; }
+        if (!tile_round_flags_ok(p->flags)) { set_error(std::string(name) + ": p->flags must be 0 or RT1W_GENERIC (the rounds go through rt1w_render_tiles, which runs the generic kernels)"); return RT1W_ERR_INVALID; }
         if (p->x0 || p->y0 || p->tile_w != p->width || p->tile_h != p->height) { set_error(std::string(name) + " takes the whole frame (x0 = y0 = 0, tile_w = width, tile_h = height)"); return RT1W_ERR_INVALID; }
         q = *p; q.spp = plan.batch_spp; /* p->spp is ignored: validated as one batch */
     }

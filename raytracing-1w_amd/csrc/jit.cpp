@@ -9,6 +9,8 @@
  * jit_headers.inc) to hiprtc, and keeps the code object in a cache keyed by a hash of everything that
  * went into the compiler.  The arithmetic of a path is the same source as in the generic kernels; only
  * control flow is resolved earlier, so results are bit-identical (tests/test_gpu_parity.py).
+ * The unit has three forms: f64, its RT_F32 build, and the f64 TILE-LIST FORM (rt1w_render_tiles with RT1W_TILES_SPECIALISED) -- the same
+ * tables and configuration under RT_TILE_LIST, the kernel taking the tile table last.  Another text is another key and another cache file.
  *
  * libhiprtc is opened with dlopen: the library has no link-time dependency on it, and a host without
  * it simply keeps the generic kernels.
@@ -191,10 +193,13 @@ static uint32_t jit_slab_reuse(const std::vector<RtNode>& N, uint32_t root, uint
     return I;
 }
 
-std::string jit_source(const rt1w_scene& s, bool f32) {
+std::string jit_source(const rt1w_scene& s, bool f32, bool tiles) {
     const std::vector<RtNode>& N = s.flat_nodes;
     std::string src;
     src += "/* generated by librt1w (jit.cpp) for one scene topology */\n";
+    /* the tile-list form (rt1w_render_tiles; f64 only): context_tiles.hip's two switches ahead of everything, the same tables, the same
+     * configuration and the same wave / exchange-parts choice below, and a kernel that takes the tile table in last place */
+    if (tiles && !f32) src += "#define RT_TILE_LIST 1\n#define RT_NO_PROBE 1\n";
     if (f32) /* the single-precision build of the same kernel: context_f32.hip's switch, here for the run-time compiler */
         src += "#include <stdint.h>\n#include <type_traits>\ntypedef double rt_f64;\n#define RT_F32 1\n#define double float\n";
     else {
@@ -277,9 +282,16 @@ std::string jit_source(const rt1w_scene& s, bool f32) {
     uint32_t depth = s.scope_depth < 2u ? 2u : s.scope_depth;
     src += std::string("typedef RtCfg<") + (s.has_media ? "true" : "false") + ", " + (s.has_tex ? "true" : "false") + ", " +
            (s.has_msphere ? "true" : "false") + ", true, " + std::to_string(depth) + ", TopoJit> CfgJit;\n";
-    src += "extern \"C\" __global__ __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES(CfgJit)) void rt_jit_sorted(\n"
-           "    RtSceneView sc, RtFrame f, rt_f64* __restrict__ partial, unsigned long long* __restrict__ counters) {\n"
-           "    rt_render_sorted_body<CfgJit>(sc, f, partial, counters);\n}\n";
+    if (tiles && !f32)
+        src += "extern \"C\" __global__ __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES(CfgJit)) void rt_jit_sorted(\n"
+               "    RtSceneView sc, RtFrame f, rt_f64* __restrict__ partial, unsigned long long* __restrict__ counters, RtTileList tl) {\n"
+               "    rt_render_sorted_body<CfgJit>(sc, f, partial, counters, tl);\n}\n"
+               /* what the host checks its own record of the list against before the first launch (context.h: RtTileArg) */
+               "extern \"C\" __device__ unsigned int rt_jit_tile_list_bytes = (unsigned int)sizeof(RtTileList);\n";
+    else
+        src += "extern \"C\" __global__ __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES(CfgJit)) void rt_jit_sorted(\n"
+               "    RtSceneView sc, RtFrame f, rt_f64* __restrict__ partial, unsigned long long* __restrict__ counters) {\n"
+               "    rt_render_sorted_body<CfgJit>(sc, f, partial, counters);\n}\n";
     return src;
 }
 
@@ -353,10 +365,10 @@ int jit_get_code(const std::string& src, bool allow_compile, std::vector<char>& 
     return RT1W_OK;
 }
 
-int jit_precompile_to(const rt1w_scene& s, const std::string& dir, JitInfo& info, bool f32) {
+int jit_precompile_to(const rt1w_scene& s, const std::string& dir, JitInfo& info, bool f32, bool tiles) {
     info = JitInfo();
     if (!jit_eligible(s)) { info.message = "scene is not eligible"; return RT1W_ERR_UNSUPPORTED; }
-    const std::string src = jit_source(s, f32);
+    const std::string src = jit_source(s, f32, tiles);
     info.key = jit_key(src);
     const std::string path = dir + "/sweep_" + info.key + ".hsaco";
     std::vector<char> code;
@@ -377,21 +389,27 @@ int jit_precompile_to(const rt1w_scene& s, const std::string& dir, JitInfo& info
 
 } // namespace rt1w
 
-extern "C" int64_t rt1w_scene_kernel_source(const rt1w_scene* s, int f32, char* buf, uint64_t cap) {
+/* the text of one form of the generated unit: the refusals and the copy the two source entries share */
+static int64_t kernel_source_of(const rt1w_scene* s, bool f32, bool tiles, char* buf, uint64_t cap) {
     if (!s) { rt1w::set_error("null scene"); return RT1W_ERR_INVALID; }
     if (!s->committed) { rt1w::set_error("scene not committed"); return RT1W_ERR_STATE; }
     if (!rt1w::jit_eligible(*s)) { rt1w::set_error("scene has more than RT_JIT_MAX_NODES nodes: no specialised kernel"); return RT1W_ERR_UNSUPPORTED; }
-    const std::string src = rt1w::jit_source(*s, f32 != 0);
+    const std::string src = rt1w::jit_source(*s, f32, tiles);
     if (!buf) return (int64_t)src.size();
     if (cap < src.size()) { rt1w::set_error("buffer too small"); return RT1W_ERR_INVALID; }
     std::memcpy(buf, src.data(), src.size());
     return (int64_t)src.size();
 }
 
-extern "C" int rt1w_scene_kernel_key(const rt1w_scene* s, char out[24]) {
+extern "C" int64_t rt1w_scene_kernel_source(const rt1w_scene* s, int f32, char* buf, uint64_t cap) { return kernel_source_of(s, f32 != 0, false, buf, cap); }
+extern "C" int64_t rt1w_scene_kernel_source_tiles(const rt1w_scene* s, char* buf, uint64_t cap) { return kernel_source_of(s, false, true, buf, cap); }
+
+static int kernel_key_of(const rt1w_scene* s, bool tiles, char out[24]) {
     if (!s || !out) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }
     if (!s->committed) { rt1w::set_error("scene not committed"); return RT1W_ERR_STATE; }
     if (!rt1w::jit_eligible(*s)) { rt1w::set_error("scene has more than RT_JIT_MAX_NODES nodes: no specialised kernel"); return RT1W_ERR_UNSUPPORTED; }
-    std::snprintf(out, 24, "%s", rt1w::jit_key(rt1w::jit_source(*s)).c_str());
+    std::snprintf(out, 24, "%s", rt1w::jit_key(rt1w::jit_source(*s, false, tiles)).c_str());
     return RT1W_OK;
 }
+extern "C" int rt1w_scene_kernel_key(const rt1w_scene* s, char out[24]) { return kernel_key_of(s, false, out); }
+extern "C" int rt1w_scene_kernel_key_tiles(const rt1w_scene* s, char out[24]) { return kernel_key_of(s, true, out); }

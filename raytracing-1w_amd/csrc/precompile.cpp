@@ -1,5 +1,5 @@
 /* rt1w_precompile -- build step: compiles the topology-specialised kernels of the reference's own scene
- * arms (src/main.rs:815-936, build_seed as given) into <package>/kernels, so that the scenes everybody
+ * arms (src/main.rs:815-936, build_seed as given), each with its tile-list form, into <package>/kernels, so that the scenes everybody
  * renders never meet the run-time compiler.  No GPU needed (hiprtc cross-compiles for gfx950).
  *   rt1w_precompile <out_dir> [build_seed ...]
  */
@@ -34,6 +34,13 @@ int main(int argc, char** argv) {
                 else keep.insert(info.path.substr(info.path.rfind('/') + 1));
                 if (rc >= 0) std::printf("arm %d seed %llu: %zu nodes -> %s (%s, %.1f s)\n", arm, seed, s->flat_nodes.size(), info.path.c_str(),
                                  info.from_cache ? "present" : "compiled", info.compile_ms / 1e3);
+                { /* every arm's tile-list form (rt1w_render_tiles with RT1W_TILES_SPECIALISED: the rounds of the adaptive entries) */
+                    rt1w::JitInfo it;
+                    int rt = rt1w::jit_precompile_to(*s, dir, it, false, true);
+                    if (rt < 0) { std::fprintf(stderr, "arm %d seed %llu (tiles): %s\n", arm, seed, it.message.c_str()); ++failures; }
+                    else { keep.insert(it.path.substr(it.path.rfind('/') + 1));
+                           std::printf("arm %d seed %llu tiles: -> %s (%s, %.1f s)\n", arm, seed, it.path.c_str(), it.from_cache ? "present" : "compiled", it.compile_ms / 1e3); }
+                }
                 if (arm == 5 || arm == 6) { /* the Cornell arms also in single precision (RT1W_PRECISION_F32) */
                     rt1w::JitInfo i32;
                     int r32 = rt1w::jit_precompile_to(*s, dir, i32, true);
