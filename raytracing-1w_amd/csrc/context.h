@@ -1,7 +1,8 @@
 /* context.h -- the device context as the library's own units see it: context.hip (the context, the render kernels' plan and launch, the
  * render entries) and features.hip (the entries of the feature buffers and the denoiser), with the helpers of the first that the second
  * calls: the checks of an rt1w_render_params, the render path without an entry's clock, and dev_grow, through which every grow-on-demand
- * device buffer of the context and its lanes grows.  Private: nothing here is exported (-fvisibility=hidden, librt1w.map). */
+ * device buffer of the context and its lanes grows.  The scene-specialised kernel is kept by form (jit.h: JitForm) in RtJitSlot jit[], state
+ * only: loader, policy table and render-time lookup are context.hip's.  Private: nothing here is exported (-fvisibility=hidden, librt1w.map). */
 #ifndef RT1W_CONTEXT_H
 #define RT1W_CONTEXT_H
 
@@ -34,10 +35,15 @@ struct RtKernel {
     uint32_t bits;
     const void* fn = nullptr;     /* a __global__ of this library (context.hip, context_ref.hip, context_f32.hip) ... */
     hipFunction_t jit = nullptr;  /* ... or the scene-specialised kernel (jit.cpp), from its module */
-    bool f32 = false;             /* takes the f32 scene's views (context_f32.hip) instead of the context's */
-    bool pw = false;              /* takes the pair-walk view (rt_walk_pair.h) in second place */
-    bool tiles = false;           /* tile-list form (context_tiles.hip): takes the tile list (RtTileArg) in last place */
+    bool pw = false,              /* takes the pair-walk view (rt_walk_pair.h) in second place */
+         f32 = false,             /* takes the f32 scene's views (context_f32.hip) instead of the context's */
+         tiles = false;           /* tile-list form (context_tiles.hip): takes the tile list (RtTileArg) in last place */
     int grid = 0;
+    /* the makers: RtKernel::of(block, bits, fn).with_pw() -- a call site names the arguments its kernel takes */
+    static RtKernel of(int block, uint32_t bits, const void* fn = nullptr) { RtKernel k; k.block = block; k.bits = bits; k.fn = fn; return k; }
+    RtKernel with_pw(bool on = true) const { RtKernel k = *this; k.pw = on; return k; }
+    RtKernel with_f32(bool on = true) const { RtKernel k = *this; k.f32 = on; return k; }
+    RtKernel with_tiles(bool on = true) const { RtKernel k = *this; k.tiles = on; return k; }
 };
 
 /* the tile list as the kernels of context_tiles.hip take it (rt_kernel_sorted.h: RtTileList; the same bytes, checked at first use) */
@@ -57,23 +63,16 @@ enum RtWalkForm {
     RT_N_WALKS
 };
 
-/* a scene-specialised kernel (jit.cpp) in one of its forms: f64, f32, and the f64 tile-list form.  The first six members say how
- * loading it differs between them (load_specialised) */
+/* a scene-specialised kernel (jit.cpp) in one of its forms (jit.h: JitForm): what the context knows of it.  State only -- how loading
+ * differs between the forms is one table beside the loader (context.hip: g_jit_forms, load_specialised) */
 struct RtJitSlot {
-    const char* what;          /* for error texts */
-    bool f32;                  /* the f32 build of the kernel */
-    bool recompile_refused;    /* f64: compile once more when the driver refuses a cached object */
-    bool block_from_bounds;    /* f64: the workgroup size is the kernel's launch bound = its sort domain (experiments build it for 512) */
-    bool sticky;               /* f32: honours RT1W_NO_JIT, renders look at the caches once per context, a failure is remembered with
-                                * its reason (rt1w_context_specialise reports it) */
-    bool tiles = false;        /* the tile-list form: takes the tile list in last place, whose size is checked against the unit's own */
     std::string src, key;      /* generated source (empty: scene not eligible), cache key */
     hipModule_t mod = nullptr;
     RtKernel k{};              /* k.jit != nullptr once loaded */
     uint32_t vgprs = 0;
-    bool tried = false;
-    bool failed = false;       /* f64: a compile was tried and failed, renders do not try again (render_common); f32: see `sticky` */
-    std::string error;
+    bool consulted = false;    /* a render has looked in the kernel caches for it (specialised_lookup: once per context and form) */
+    bool failed = false;       /* a compile or load failed and is not repeated: by a long render (render_common), of an optional form (load_specialised) */
+    std::string error;         /* ... and why */
 };
 
 struct rt1w_context {
@@ -103,7 +102,7 @@ struct rt1w_context {
     uint32_t stack_need = 0;
     RtKernel ref[4] = {}; /* reference-stream kernels by rt1w_internal_ref_kernel mode: sweep, stack walk, reordering V0, reordering every-feature */
     void* f32_scene = nullptr;   /* context_f32.hip: f32 copies of the scene arrays, built at the first f32 render */
-    bool f32_tried = false;
+    bool tried_f32_scene = false;
     /* pair walk (rt_walk_pair.h): records of an eligible scene (sphere-only, variant 5); its kernels, plain and reordering (grid 0: the
      * scene is not eligible) */
     void* d_pw_inner = nullptr; void* d_pw_groups = nullptr;
@@ -118,11 +117,9 @@ struct rt1w_context {
     std::vector<RtNode> h_nodes, h_lights; std::vector<RtMaterial> h_materials; std::vector<RtTexture> h_textures; std::vector<RtPerlin> h_perlin;
     RtKernel k32[RT_N_VARIANTS][3] = {}; /* f32 kernels by variant and rt1w_internal_f32_kernel mode: plain, reordering, pair walk */
     RtKernel k32x[RT_N_VARIANTS][3] = {}; /* the same slots for the kernels a registered rt1w_f32_kernel_fn hands out (rt1w_internal.h) */
-    RtJitSlot jit{"specialised kernel", false, true, true, false};
-    RtJitSlot jit32{"f32 specialised kernel", true, false, false, true}; /* loaded only where `jit` is */
-    /* the tile-list form (rt1w_render_tiles with RT1W_TILES_SPECIALISED): from the caches at the first tile render that asks for it, or
-     * from the compiler in rt1w_context_specialise with RT1W_SPECIALISE_TILES; `tried`: the caches have been looked at and had none */
-    RtJitSlot jit_tiles{"tile-list specialised kernel", false, true, true, false, true};
+    /* the scene-specialised kernel by form: JIT_F64 from the caches at creation, the other two at the first render that asks for them
+     * (specialised_lookup: JIT_F32 only beside JIT_F64, JIT_TILES with RT1W_TILES_SPECIALISED); from the compiler in rt1w_context_specialise */
+    RtJitSlot jit[3]; /* JIT_N_FORMS: context.hip checks it (features.hip, which never looks at a slot, does not see jit.h) */
 };
 
 namespace rt1w {

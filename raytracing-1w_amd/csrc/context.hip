@@ -212,8 +212,8 @@ bool build_walk_table(rt1w_context* c, const std::vector<RtNode>& nodes, uint32_
 /* RT1W_PRECISION_F32: the f32 copies of the scene arrays, at the first f32 render */
 int ensure_f32_scene(rt1w_context* c) {
     if (c->f32_scene) return RT1W_OK;
-    if (c->f32_tried) { rt1w::set_error("could not build the single-precision scene arrays"); return RT1W_ERR_DEVICE; }
-    c->f32_tried = true;
+    if (c->tried_f32_scene) { rt1w::set_error("could not build the single-precision scene arrays"); return RT1W_ERR_DEVICE; }
+    c->tried_f32_scene = true;
     if (rt1w_internal_f32_create(c->h_nodes.data(), (uint32_t)c->h_nodes.size(), c->h_lights.data(), (uint32_t)c->h_lights.size(),
                                  c->h_materials.data(), (uint32_t)c->h_materials.size(), c->h_textures.data(), (uint32_t)c->h_textures.size(),
                                  c->h_perlin.data(), (uint32_t)c->h_perlin.size(), &c->view, &c->f32_scene) != 0) {
@@ -265,7 +265,9 @@ void lane_destroy(RtLane& l) {
 #ifndef RT_PARTIAL_BUDGET
 #define RT_PARTIAL_BUDGET (8ull << 30)
 #endif
-struct RtLaunch { RtFrame f; unsigned long long npix; unsigned long long partial_budget = RT_PARTIAL_BUDGET; int variant; RtKernel k; RtTileArg tl; };
+/* where a plan's kernel sits in the context: k64[i][v], pw_k[i], or neither; its tile-list form has the same index (tile_kernel_of) */
+struct RtKernelAt { enum Table { NOWHERE, K64, PW } table = NOWHERE; int i = 0, v = 0; };
+struct RtLaunch { RtFrame f; unsigned long long npix; unsigned long long partial_budget = RT_PARTIAL_BUDGET; int variant; RtKernel k; RtKernelAt at; RtTileArg tl; };
 
 /* the persistent grid of a kernel: as many workgroups as are resident at once, at least one per CU; 0, with the error set, if the
  * occupancy query failed */
@@ -292,7 +294,7 @@ uint32_t default_chunk(const rt1w_context* c, const rt1w_render_params* p) {
     return (c->variant >= 2 && !(p->flags & RT1W_WAVEFRONT)) ? 1u : rt1w_default_chunk(p->tile_w, p->tile_h, p->spp);
 }
 
-int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::JitInfo& info);
+const RtKernel* specialised_lookup(rt1w_context* c, JitForm form);
 
 /* the f32 kernel of (variant, mode): the product's own (context_f32.hip), unless librt1w_lab.so has registered a function that hands
  * out another build of the same kernel (rt1w_internal.h: rt1w_f32_kernel_fn; f32_exact.hip).  While that function answers, the
@@ -312,9 +314,9 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
     f.n_chunks = (f.spp + f.chunk - 1u) / f.chunk;
     L.npix = (unsigned long long)f.tile_w * f.tile_h;
     L.partial_budget = p->partial_mib ? ((unsigned long long)p->partial_mib << 20) : RT_PARTIAL_BUDGET;
+    L.at = RtKernelAt();
     const uint32_t fl = p->flags;
     const bool forced = ((fl >> 8) & 0xFFu) != 0u;
-    rt1w::JitInfo info;
     int rc;
     if (p->precision == RT1W_PRECISION_F32) {
         if (fl & (RT1W_RNG_REFERENCE | RT1W_WAVEFRONT | RT1W_LDS_NODES)) { rt1w::set_error("RT1W_PRECISION_F32 has the default kernels only"); return RT1W_ERR_INVALID; }
@@ -325,10 +327,8 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
         (void)f32_kernel_of(L.variant, 1, own); /* own: the product's kernels serve, the scene-specialised one among them */
         /* a context that runs a scene-specialised kernel in f64 uses the f32 build of that kernel too -- from the kernel
          * caches only: renders never compile (rt1w_context_specialise does, for both precisions) */
-        if (!(fl & (RT1W_GENERIC | RT1W_UNSORTED)) && !forced && c->jit.k.jit && own && load_specialised(c, c->jit32, false, info) == RT1W_OK) {
-            L.k = c->jit32.k;
-            return RT1W_OK;
-        }
+        if (!(fl & (RT1W_GENERIC | RT1W_UNSORTED)) && !forced && c->jit[JIT_F64].k.jit && own)
+            if (const RtKernel* k = specialised_lookup(c, JIT_F32)) { L.k = *k; return RT1W_OK; }
         /* mode 1: the reordering kernel of the sweep variants, the slice-end reordering of the stack walks; 2: sphere scenes' pair walk
          * (rt_walk_pair.h) in this precision too -- in the kernel that reorders the finished paths */
         const int v = L.variant;
@@ -337,7 +337,7 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
         const uint32_t bits = RT_BIT_F32 | (mode == 2 ? RT_BIT_PW | RT_BIT_SS : mode == 1 ? (v >= 2 ? RT_BIT_SS : RT_BIT_SORTED) : 0u);
         const void* fn = f32_kernel_of(v, mode, own);
         RtKernel& slot = own ? c->k32[v][mode] : c->k32x[v][mode];
-        if ((rc = first_use(c, slot, RtKernel{mode ? RT_SORT_BLOCK : RT_BLOCK, bits, fn, nullptr, true, mode == 2})) < 0) return rc;
+        if ((rc = first_use(c, slot, RtKernel::of(mode ? RT_SORT_BLOCK : RT_BLOCK, bits, fn).with_f32().with_pw(mode == 2))) < 0) return rc;
         L.k = slot;
         return RT1W_OK;
     }
@@ -352,17 +352,18 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
         if (!c->ref[mode].grid && (rt1w_internal_ref_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_ref_sizeof(1) != sizeof(RtFrame))) {
             rt1w::set_error("reference-stream kernels built against another scene layout"); return RT1W_ERR_DEVICE;
         }
-        if ((rc = first_use(c, c->ref[mode], RtKernel{mode >= 2 ? RT_SORT_BLOCK : RT_BLOCK, RT_BIT_REF | (mode >= 2 ? RT_BIT_SORTED : 0u), rt1w_internal_ref_kernel(mode)})) < 0) return rc;
+        if ((rc = first_use(c, c->ref[mode], RtKernel::of(mode >= 2 ? RT_SORT_BLOCK : RT_BLOCK, RT_BIT_REF | (mode >= 2 ? RT_BIT_SORTED : 0u), rt1w_internal_ref_kernel(mode)))) < 0) return rc;
         L.k = c->ref[mode];
         return RT1W_OK;
     }
     L.variant = c->variant;
     if ((rc = forced_variant(c, fl, true, &L.variant)) < 0) return rc;
     const int v = L.variant;
-    if (c->jit.k.jit && !(fl & (RT1W_GENERIC | RT1W_UNSORTED | RT1W_LDS_NODES)) && !forced) { L.k = c->jit.k; return RT1W_OK; }
+    if (c->jit[JIT_F64].k.jit && !(fl & (RT1W_GENERIC | RT1W_UNSORTED | RT1W_LDS_NODES)) && !forced) { L.k = c->jit[JIT_F64].k; return RT1W_OK; }
     /* sphere scenes: the pair walk (same frames, bit for bit), unless the caller asks for the one-entry-per-step walk */
     if (c->pw_k[0].grid && v == 5 && !(fl & (RT1W_CLASSIC_WALK | RT1W_LDS_NODES | RT1W_WAVEFRONT))) {
-        L.k = c->pw_k[c->pw_k[1].grid && !(fl & RT1W_UNSORTED) ? 1 : 0];
+        L.at.table = RtKernelAt::PW; L.at.i = c->pw_k[1].grid && !(fl & RT1W_UNSORTED) ? 1 : 0;
+        L.k = c->pw_k[L.at.i];
         return RT1W_OK;
     }
     auto built = [&](int w) { return c->k64[w][v].grid > 0; };
@@ -375,6 +376,7 @@ int render_plan(rt1w_context* c, const rt1w_render_params* p, RtLaunch& L) {
         if (built(RT_WALK_SS + sm) && !(fl & RT1W_UNSORTED))
             w = (built(RT_WALK_SS_HC + sm) && !(fl & RT1W_NO_NODE_CACHE)) ? RT_WALK_SS_HC + sm : RT_WALK_SS + sm;
     }
+    L.at.table = RtKernelAt::K64; L.at.i = w; L.at.v = v;
     L.k = c->k64[w][v];
     return RT1W_OK;
 }
@@ -455,38 +457,52 @@ int render_finish(RtLane& l, const RtLaunch& L, rt1w_stats* stats) {
     return RT1W_OK;
 }
 
-/* load the specialised kernel of this context's scene in the precision of `s`: from the caches, or (allow_compile) from the compiler */
-int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::JitInfo& info) {
+/* How loading the scene-specialised kernel differs between its forms (jit.h: JitForm); load_specialised is the only reader.  There is
+ * no column for "a cached object the driver refuses is compiled once more": that is `!optional`, since compiling again repeats a failure */
+struct RtJitPolicy {
+    const char* what;        /* the prefix of the form's error texts */
+    bool views_f32;          /* takes the f32 scene's views: the RT_F32 build reads the f32 copies of the scene arrays */
+    bool tile_list;          /* takes the tile list in last place: only this form's text has an RtTileList, whose sizeof is checked */
+    bool block_from_bounds;  /* workgroup size = launch bound = sort domain: experiments build the f64 text for 512 or 128; f32 runs at RT_SORT_BLOCK like its twins */
+    bool optional;           /* a by-product of the f64 form nobody asks for by name: honours RT1W_NO_JIT, a failed compile or load is remembered, not repeated */
+};
+static_assert(sizeof(rt1w_context::jit) / sizeof(RtJitSlot) == JIT_N_FORMS, "one slot per form");
+static constexpr RtJitPolicy g_jit_forms[JIT_N_FORMS] = {
+    /*              what                            views_f32 tile_list block_from_bounds optional */
+    /* JIT_F64   */ {"specialised kernel",           false,    false,    true,             false},
+    /* JIT_F32   */ {"f32 specialised kernel",       true,     false,    false,            true},
+    /* JIT_TILES */ {"tile-list specialised kernel", false,    true,     true,             false},
+};
+
+/* load one form of the specialised kernel of this context's scene: from the caches, or (allow_compile) from the compiler */
+int load_specialised(rt1w_context* c, JitForm form, bool allow_compile, rt1w::JitInfo& info) {
+    const RtJitPolicy& P = g_jit_forms[form];
+    RtJitSlot& s = c->jit[form];
     if (s.k.jit) { info = rt1w::JitInfo(); info.key = s.key; info.from_cache = true; return RT1W_OK; }
     if (s.src.empty()) { rt1w::set_error("scene has more than RT_JIT_MAX_NODES nodes: no specialised kernel"); return RT1W_ERR_UNSUPPORTED; }
-    const std::string what = s.what;
-    if (s.sticky) {
-        if (s.tried && !allow_compile) return RT1W_ERR_STATE;
-        if (s.failed) { rt1w::set_error(what + ": " + s.error); return RT1W_ERR_DEVICE; }
-        s.tried = true;
-    }
+    const std::string what = P.what;
+    if (P.optional && s.failed) { rt1w::set_error(what + ": " + s.error); return RT1W_ERR_DEVICE; }
     std::vector<char> code;
-    int rc = rt1w::jit_get_code(s.src, allow_compile && !(s.sticky && getenv("RT1W_NO_JIT")), code, info);
+    int rc = rt1w::jit_get_code(s.src, allow_compile && !(P.optional && getenv("RT1W_NO_JIT")), code, info);
     s.key = info.key;
     if (rc < 0) {
         rt1w::set_error(what + ": " + info.message);
-        if (s.sticky && allow_compile) { s.failed = true; s.error = info.message; }
+        if (P.optional && allow_compile) { s.failed = true; s.error = info.message; }
         return rc;
     }
     bool ok = hip_ok(hipModuleLoadData(&s.mod, code.data()), ("hipModuleLoadData(" + what + ")").c_str());
     if (!ok) s.mod = nullptr;
-    if (!ok && info.from_cache && s.recompile_refused) {
+    if (!ok && info.from_cache && !P.optional) {
         /* a cached object the driver refuses (truncated, foreign toolchain): forget it and, if allowed, compile afresh */
         rt1w::jit_invalidate(info);
         if (!allow_compile) return RT1W_ERR_DEVICE;
         if ((rc = rt1w::jit_get_code(s.src, true, code, info, true)) < 0) { rt1w::set_error(what + ": " + info.message); return rc; }
         if (!(ok = hip_ok(hipModuleLoadData(&s.mod, code.data()), ("hipModuleLoadData(" + what + ")").c_str()))) s.mod = nullptr;
     }
-    RtKernel k{RT_SORT_BLOCK, RT_BIT_SORTED | RT_BIT_JIT | (s.f32 ? RT_BIT_F32 : 0u), nullptr, nullptr, s.f32};
-    k.tiles = s.tiles;
+    RtKernel k = RtKernel::of(RT_SORT_BLOCK, RT_BIT_SORTED | RT_BIT_JIT | (P.views_f32 ? RT_BIT_F32 : 0u)).with_f32(P.views_f32).with_tiles(P.tile_list);
     int max_threads = 0;
     ok = ok && hip_ok(hipModuleGetFunction(&k.jit, s.mod, "rt_jit_sorted"), ("hipModuleGetFunction(" + what + ")").c_str());
-    if (ok && s.tiles) {
+    if (ok && P.tile_list) {
         /* the unit's own RtTileList against the bytes render_launch will pass, as tile_kernel_of checks the built-in forms */
         hipDeviceptr_t dptr = nullptr;
         size_t bytes = 0;
@@ -495,13 +511,13 @@ int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::Ji
              bytes == sizeof theirs && hip_ok(hipMemcpy(&theirs, dptr, sizeof theirs, hipMemcpyDeviceToHost), ("hipMemcpy(" + what + ")").c_str());
         if (ok && theirs != (unsigned int)sizeof(RtTileArg)) { rt1w::set_error(what + " built against another tile-list layout"); ok = false; }
     }
-    if (ok && s.block_from_bounds && hipFuncGetAttribute(&max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, k.jit) == hipSuccess &&
+    if (ok && P.block_from_bounds && hipFuncGetAttribute(&max_threads, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, k.jit) == hipSuccess &&
         (max_threads == 512 || max_threads == 128)) k.block = max_threads;
     if (ok) ok = (k.grid = kernel_grid(c, k)) > 0;
     if (!ok) {
         if (s.mod) (void)hipModuleUnload(s.mod);
         s.mod = nullptr;
-        if (s.sticky) {
+        if (P.optional) {
             if (info.from_cache) rt1w::jit_invalidate(info);
             s.failed = true; s.error = rt1w_last_error();
         }
@@ -511,6 +527,19 @@ int load_specialised(rt1w_context* c, RtJitSlot& s, bool allow_compile, rt1w::Ji
     if (hipFuncGetAttribute(&vg, HIP_FUNC_ATTRIBUTE_NUM_REGS, k.jit) == hipSuccess) s.vgprs = (uint32_t)vg;
     s.k = k;
     return RT1W_OK;
+}
+
+/* What a render may do about a form: the loaded kernel, or one look into the kernel caches per context and form, never the compiler.  A miss
+ * is remembered and is no error: nullptr, a generic kernel runs, no HIP error of a refused object is left for the next launch check */
+const RtKernel* specialised_lookup(rt1w_context* c, JitForm form) {
+    RtJitSlot& s = c->jit[form];
+    if (s.k.jit) return &s.k;
+    if (s.consulted || s.src.empty()) return nullptr;
+    s.consulted = true;
+    rt1w::JitInfo info;
+    if (load_specialised(c, form, false, info) == RT1W_OK) return &s.k;
+    (void)hipGetLastError();
+    return nullptr;
 }
 
 /* ---- wavefront form: lives in librt1w_lab.so (wavefront.hip), which registers itself here when it is loaded ---- */
@@ -543,38 +572,20 @@ int render_wavefront(rt1w_context* c, const rt1w_render_params* p, const RtLaunc
     return RT1W_OK;
 }
 
-/* RT1W_TILES_SPECIALISED: whether the context has the tile-list form of its scene-specialised kernel, looking in the kernel caches the
- * first time it is asked (the lazy load of jit32: context creation pays no third module load, a render never compiles).  A miss is
- * remembered and is no error -- the generic tile form runs; rt1w_context_specialise with RT1W_SPECIALISE_TILES loads it later */
-bool specialised_tiles(rt1w_context* c) {
-    RtJitSlot& s = c->jit_tiles;
-    if (s.k.jit) return true;
-    if (s.tried || s.src.empty()) return false;
-    s.tried = true;
-    rt1w::JitInfo info;
-    if (load_specialised(c, s, false, info) == RT1W_OK) return true;
-    (void)hipGetLastError(); /* a cached object the driver refused is a miss like any other: nothing of it is left for the next launch check */
-    return false;
-}
-
-/* the tile-list form of the kernel a plan holds (one of k64 / pw_k: the plan was made with RT1W_GENERIC), resolved at its first use */
-int tile_kernel_of(rt1w_context* c, RtKernel& k) {
+/* the tile-list form of the kernel a plan holds (from k64 / pw_k: the plan was made with RT1W_GENERIC), resolved at its first use */
+int tile_kernel_of(rt1w_context* c, RtLaunch& L) {
     if (rt1w_internal_tile_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_tile_sizeof(1) != sizeof(RtFrame) ||
         rt1w_internal_tile_sizeof(2) != sizeof(RtPwView) || rt1w_internal_tile_sizeof(3) != sizeof(RtTileArg)) {
         rt1w::set_error("tile-list kernels built against another scene layout"); return RT1W_ERR_DEVICE;
     }
-    RtKernel* slot = nullptr;
-    RtKernel want = k;
-    want.tiles = true; want.grid = 0; want.fn = nullptr;
-    for (int i = 0; i < 2 && !slot; ++i)
-        if (c->pw_k[i].grid && c->pw_k[i].fn == k.fn) { slot = &c->pw_kt[i]; want.fn = rt1w_internal_tile_pw_kernel(i); }
-    for (int w = 0; w < RT_N_WALKS && !slot; ++w)
-        for (int v = 0; v < RT_N_VARIANTS && !slot; ++v)
-            if (c->k64[w][v].grid && c->k64[w][v].fn == k.fn) { slot = &c->kt[w][v]; want.fn = rt1w_internal_tile_kernel(w, v); }
+    const RtKernelAt& at = L.at;
+    RtKernel* const slot = at.table == RtKernelAt::PW ? &c->pw_kt[at.i] : at.table == RtKernelAt::K64 ? &c->kt[at.i][at.v] : nullptr;
+    RtKernel want = L.k.with_tiles(); want.grid = 0;
+    want.fn = at.table == RtKernelAt::PW ? rt1w_internal_tile_pw_kernel(at.i) : at.table == RtKernelAt::K64 ? rt1w_internal_tile_kernel(at.i, at.v) : nullptr;
     if (!slot || !want.fn) { rt1w::set_error("rt1w_render_tiles: the kernel this scene renders with has no tile-list form"); return RT1W_ERR_DEVICE; }
     const int rc = first_use(c, *slot, want);
     if (rc < 0) return rc;
-    k = *slot;
+    L.k = *slot;
     return RT1W_OK;
 }
 
@@ -622,8 +633,9 @@ int render_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32_t t
     RtLaunch L;
     int rc = render_plan(c, &q, L);
     if (rc < 0) return rc;
-    if ((p->flags & RT1W_TILES_SPECIALISED) && specialised_tiles(c)) L.k = c->jit_tiles.k;
-    else if ((rc = tile_kernel_of(c, L.k)) < 0) return rc;
+    const RtKernel* spec = (p->flags & RT1W_TILES_SPECIALISED) ? specialised_lookup(c, JIT_TILES) : nullptr;
+    if (spec) L.k = *spec;
+    else if ((rc = tile_kernel_of(c, L)) < 0) return rc;
     RtLane& l = c->lane[0];
     if ((rc = tiles_upload(c, tiles, n_tiles, &L.tl.rec)) < 0) return rc;
     L.tl.side = tile; L.tl.n = n_tiles;
@@ -638,11 +650,11 @@ int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, r
     /* a render this long repays the 1-8 s of the compiler: 2^35 paths where the gain is ~1.3x (scenes the generic sweep
      * handles), 2^32 where it is 1.5-2.3x (scenes the generic code hands to the stack walk).  RT1W_NO_JIT: never compile
      * behind the caller's back */
-    if (!c->jit.k.jit && !c->jit.failed && !c->jit.src.empty() && !(p->flags & (RT1W_GENERIC | RT1W_UNSORTED)) &&
+    if (!c->jit[JIT_F64].k.jit && !c->jit[JIT_F64].failed && !c->jit[JIT_F64].src.empty() && !(p->flags & (RT1W_GENERIC | RT1W_UNSORTED)) &&
         (unsigned long long)p->tile_w * p->tile_h * p->spp >= (c->n_nodes <= RT_SWEEP_MAX_NODES ? (1ull << 35) : (1ull << 32)) &&
         !getenv("RT1W_NO_JIT")) {
         rt1w::JitInfo info;
-        if (load_specialised(c, c->jit, true, info) < 0) c->jit.failed = true;
+        if (load_specialised(c, JIT_F64, true, info) < 0) c->jit[JIT_F64].failed = true;
     }
     RtLaunch L;
     int rc = render_plan(c, p, L);
@@ -715,7 +727,7 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
         for (int v = 0; v < RT_N_VARIANTS; ++v) {
             if (!g_kernels[w][v] || ((w == RT_WALK_SS_HC || w == RT_WALK_SS_HC_SPHERE_MEDIA) && !c->walk_table)) continue;
             RtKernel& k = c->k64[w][v];
-            k = RtKernel{g_walks[w].block, g_walks[w].bits, reinterpret_cast<const void*>(g_kernels[w][v])};
+            k = RtKernel::of(g_walks[w].block, g_walks[w].bits, reinterpret_cast<const void*>(g_kernels[w][v]));
             if (!(k.grid = kernel_grid(c, k))) { rt1w_context_destroy(c); return RT1W_ERR_DEVICE; }
         }
     if (c->variant == 5 && s->stack_need + 1u <= (uint32_t)RT_PW_STACK) {
@@ -724,8 +736,8 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
         std::vector<RtPwInner> pin; std::vector<RtPwGroup> pgr;
         if (rt_pw_build(s->flat_nodes, s->flat_root, pin, pgr, c->pw, c->pw_why)) {
             const int n_pw = s->stack_need + 1u <= (uint32_t)RT_PW_SS_STACK ? 2 : 1;
-            c->pw_k[0] = RtKernel{RT_BLOCK, RT_BIT_PW, reinterpret_cast<const void*>(rt_render_kernel_pw<RtCfgV5>), nullptr, false, true};
-            c->pw_k[1] = RtKernel{RT_BLOCK, RT_BIT_PW | RT_BIT_SS, reinterpret_cast<const void*>(rt_render_kernel_pw_ss<RtCfgV5>), nullptr, false, true};
+            c->pw_k[0] = RtKernel::of(RT_BLOCK, RT_BIT_PW, reinterpret_cast<const void*>(rt_render_kernel_pw<RtCfgV5>)).with_pw();
+            c->pw_k[1] = RtKernel::of(RT_BLOCK, RT_BIT_PW | RT_BIT_SS, reinterpret_cast<const void*>(rt_render_kernel_pw_ss<RtCfgV5>)).with_pw();
             if (!upload(&c->d_pw_inner, pin.data(), pin.size() * sizeof(RtPwInner)) || !upload(&c->d_pw_groups, pgr.data(), pgr.size() * sizeof(RtPwGroup))) {
                 rt1w_context_destroy(c); return RT1W_ERR_DEVICE;
             }
@@ -738,11 +750,9 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
      * ensure_f32_scene; the wavefront form's in librt1w_lab.so */
     c->h_nodes = s->flat_nodes; c->h_lights = s->flat_lights; c->h_materials = s->materials; c->h_textures = s->textures; c->h_perlin = s->perlin;
     if (rt1w::jit_eligible(*s)) {
-        c->jit.src = rt1w::jit_source(*s);
-        c->jit32.src = rt1w::jit_source(*s, true);
-        c->jit_tiles.src = rt1w::jit_source(*s, false, true); /* loaded at the first tile render that asks for it (specialised_tiles) */
+        for (int form = 0; form < JIT_N_FORMS; ++form) c->jit[form].src = rt1w::jit_source(*s, (JitForm)form);
         rt1w::JitInfo info;
-        (void)load_specialised(c, c->jit, false, info); /* a cache hit is used from the first render on; a miss costs nothing */
+        (void)load_specialised(c, JIT_F64, false, info); /* a cache hit is used from the first render on, a miss costs nothing; the other forms: specialised_lookup */
     }
     *out = c;
     return RT1W_OK;
@@ -759,9 +769,7 @@ void rt1w_context_destroy(rt1w_context* c) {
     if (c->d_pw_groups) (void)hipFree(c->d_pw_groups);
     lane_destroy(c->lane[0]);
     lane_destroy(c->lane[1]);
-    if (c->jit.mod) (void)hipModuleUnload(c->jit.mod);
-    if (c->jit32.mod) (void)hipModuleUnload(c->jit32.mod);
-    if (c->jit_tiles.mod) (void)hipModuleUnload(c->jit_tiles.mod);
+    for (RtJitSlot& j : c->jit) if (j.mod) (void)hipModuleUnload(j.mod);
     if (c->ev_first) (void)hipEventDestroy(c->ev_first);
     delete c;
 }
@@ -769,25 +777,26 @@ void rt1w_context_destroy(rt1w_context* c) {
 int rt1w_context_specialise(rt1w_context* c, uint32_t flags, rt1w_specialise_info* out) {
     if (!c) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
-    rt1w::JitInfo info;
-    const bool had = c->jit.k.jit != nullptr;
-    int rc = load_specialised(c, c->jit, !(flags & RT1W_SPECIALISE_CACHED_ONLY), info);
-    if (rc == RT1W_OK && c->jit.k.jit) { /* optional: a failure leaves f32 renders on the generic kernels */
-        rt1w::JitInfo info32;
-        (void)load_specialised(c, c->jit32, !(flags & RT1W_SPECIALISE_CACHED_ONLY), info32);
-    }
-    if (rc == RT1W_OK && (flags & RT1W_SPECIALISE_TILES)) { /* asked for: its failure is the call's */
-        rt1w::JitInfo info_t;
-        rc = load_specialised(c, c->jit_tiles, !(flags & RT1W_SPECIALISE_CACHED_ONLY), info_t);
-        info.compile_ms += info_t.compile_ms;
+    const RtJitSlot& j64 = c->jit[JIT_F64];
+    const bool had = j64.k.jit != nullptr;
+    rt1w::JitInfo info; /* the f64 form's, with the compile time of the tile-list form */
+    int rc = RT1W_OK;
+    for (int form = 0; form < JIT_N_FORMS && rc == RT1W_OK; ++form) {
+        /* f64: required.  f32: only beside a loaded f64 kernel, its failure is not the call's.  Tiles: when asked for, its failure is the call's */
+        if (form == JIT_F32 ? !j64.k.jit : form == JIT_TILES && !(flags & RT1W_SPECIALISE_TILES)) continue;
+        rt1w::JitInfo fi;
+        const int r = load_specialised(c, (JitForm)form, !(flags & RT1W_SPECIALISE_CACHED_ONLY), fi);
+        if (form == JIT_F32) continue;
+        rc = r;
+        if (form == JIT_F64) info = fi; else info.compile_ms += fi.compile_ms;
     }
     if (out) {
         memset(out, 0, sizeof *out);
-        snprintf(out->key, sizeof out->key, "%s", c->jit.key.c_str());
-        out->active = c->jit.k.jit ? 1u : 0u;
+        snprintf(out->key, sizeof out->key, "%s", j64.key.c_str());
+        out->active = j64.k.jit ? 1u : 0u;
         out->from_cache = (had || info.from_cache) ? 1u : 0u;
         out->compile_ms = info.compile_ms;
-        out->grid = (uint32_t)c->jit.k.grid; out->vgprs = c->jit.vgprs;
+        out->grid = (uint32_t)j64.k.grid; out->vgprs = j64.vgprs;
     }
     return rc;
 }
@@ -1082,10 +1091,10 @@ int rt1w_debug_stamps(rt1w_context* c, uint64_t out[16], int reset) {
     }
 #endif
     /* a scene-specialised kernel compiled with RT1W_JIT_STAMPS=1 in the environment carries its own counters */
-    if (c->jit.mod) {
+    if (c->jit[JIT_F64].mod) {
         hipDeviceptr_t dptr = nullptr;
         size_t bytes = 0;
-        if (hipModuleGetGlobal(&dptr, &bytes, c->jit.mod, "g_stamp_total") == hipSuccess && bytes == 16 * sizeof(unsigned long long)) {
+        if (hipModuleGetGlobal(&dptr, &bytes, c->jit[JIT_F64].mod, "g_stamp_total") == hipSuccess && bytes == 16 * sizeof(unsigned long long)) {
             unsigned long long h[16];
             (void)hipMemcpy(h, dptr, sizeof h, hipMemcpyDeviceToHost);
             for (int i = 0; i < 16; ++i) out[i] += h[i];

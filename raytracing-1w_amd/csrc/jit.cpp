@@ -9,8 +9,9 @@
  * jit_headers.inc) to hiprtc, and keeps the code object in a cache keyed by a hash of everything that
  * went into the compiler.  The arithmetic of a path is the same source as in the generic kernels; only
  * control flow is resolved earlier, so results are bit-identical (tests/test_gpu_parity.py).
- * The unit has three forms: f64, its RT_F32 build, and the f64 TILE-LIST FORM (rt1w_render_tiles with RT1W_TILES_SPECIALISED) -- the same
- * tables and configuration under RT_TILE_LIST, the kernel taking the tile table last.  Another text is another key and another cache file.
+ * The unit has three forms (jit.h: JitForm): f64, its RT_F32 build, and the f64 TILE-LIST FORM (rt1w_render_tiles with
+ * RT1W_TILES_SPECIALISED) -- the same tables and configuration under RT_TILE_LIST, the kernel taking the tile table last.  Another text is
+ * another key and another cache file.  jit_get_code finds a text's code object (install cache, user cache, compiler), jit_precompile_to fills the install cache.
  *
  * libhiprtc is opened with dlopen: the library has no link-time dependency on it, and a host without
  * it simply keeps the generic kernels.
@@ -193,14 +194,14 @@ static uint32_t jit_slab_reuse(const std::vector<RtNode>& N, uint32_t root, uint
     return I;
 }
 
-std::string jit_source(const rt1w_scene& s, bool f32, bool tiles) {
+std::string jit_source(const rt1w_scene& s, JitForm form) {
     const std::vector<RtNode>& N = s.flat_nodes;
     std::string src;
     src += "/* generated by librt1w (jit.cpp) for one scene topology */\n";
     /* the tile-list form (rt1w_render_tiles; f64 only): context_tiles.hip's two switches ahead of everything, the same tables, the same
      * configuration and the same wave / exchange-parts choice below, and a kernel that takes the tile table in last place */
-    if (tiles && !f32) src += "#define RT_TILE_LIST 1\n#define RT_NO_PROBE 1\n";
-    if (f32) /* the single-precision build of the same kernel: context_f32.hip's switch, here for the run-time compiler */
+    if (form == JIT_TILES) src += "#define RT_TILE_LIST 1\n#define RT_NO_PROBE 1\n";
+    if (form == JIT_F32) /* the single-precision build of the same kernel: context_f32.hip's switch, here for the run-time compiler */
         src += "#include <stdint.h>\n#include <type_traits>\ntypedef double rt_f64;\n#define RT_F32 1\n#define double float\n";
     else {
         /* Four waves per SIMD (128 VGPRs) and the exchange in two rounds (27 KB of LDS per workgroup, four workgroups per CU) for the
@@ -217,24 +218,22 @@ std::string jit_source(const rt1w_scene& s, bool f32, bool tiles) {
     src += "#include \"rt_kernel_sorted.h\"\n";
     src += "struct TopoJit {\n";
     src += "    static constexpr uint32_t n = " + std::to_string(N.size()) + "u, root = " + std::to_string(s.flat_root) + "u;\n";
-    src += "    static constexpr uint32_t kind[" + std::to_string(N.size()) + "] = {";
-    for (size_t i = 0; i < N.size(); ++i) src += (i ? ", " : "") + std::to_string(N[i].kind) + "u";
-    src += "};\n";
-    src += "    static constexpr uint32_t skip[" + std::to_string(N.size()) + "] = {";
-    for (size_t i = 0; i < N.size(); ++i) src += (i ? ", " : "") + std::to_string(N[i].skip) + "u";
-    src += "};\n";
+    /* one row of the topology's tables: `n` words, the i-th from value(i) */
+    auto row = [&src](const char* name, size_t n, auto value) {
+        src += std::string("    static constexpr uint32_t ") + name + "[" + std::to_string(n) + "] = {";
+        for (size_t i = 0; i < n; ++i) src += (i ? ", " : "") + std::to_string((uint32_t)value(i)) + "u";
+        src += "};\n";
+    };
+    row("kind", N.size(), [&](size_t i) { return N[i].kind; });
+    row("skip", N.size(), [&](size_t i) { return N[i].skip; });
     /* what a hit needs to know about its node besides the ray (rt_core.h: RtHitShape): the wrapper above every leaf, wrapper and
      * medium (a BVH node's `b` is its right child: RT_NONE here), and the kind word of a leaf's or medium's material with its
      * NEEDS_UV / SOLID flags.  Indices and kinds of the topology only -- never a coordinate, never a material's values */
-    src += "    static constexpr uint32_t wrap[" + std::to_string(N.size()) + "] = {";
-    for (size_t i = 0; i < N.size(); ++i) src += (i ? ", " : "") + std::to_string((N[i].kind & RT_KIND_MASK) <= RT_BVH1 ? RT_NONE : N[i].b) + "u";
-    src += "};\n";
-    src += "    static constexpr uint32_t mat_kind[" + std::to_string(N.size()) + "] = {";
-    for (size_t i = 0; i < N.size(); ++i) {
+    row("wrap", N.size(), [&](size_t i) { return (N[i].kind & RT_KIND_MASK) <= RT_BVH1 ? RT_NONE : N[i].b; });
+    row("mat_kind", N.size(), [&](size_t i) {
         const uint32_t k = N[i].kind & RT_KIND_MASK;
-        src += (i ? ", " : "") + std::to_string(((k >= RT_SPHERE && k <= RT_YZ) || k == RT_MEDIUM) ? RT_MAT_KINDF(N[i].mat) : 0u) + "u";
-    }
-    src += "};\n";
+        return ((k >= RT_SPHERE && k <= RT_YZ) || k == RT_MEDIUM) ? RT_MAT_KINDF(N[i].mat) : 0u;
+    });
     /* the box-free sweep (rt_core.h: rt_sweep_free): the box every leaf's hit is verified against in each ray space of its wrapper
      * chain, and whether the unit sweeps that way at all -- no medium, a rect, nested boxes, few enough nodes (rt_box_free.h).  Both
      * precisions declare them; the f32 build keeps its boxes */
@@ -243,10 +242,7 @@ std::string jit_source(const rt1w_scene& s, bool f32, bool tiles) {
      * coordinates, which keep arriving in the light records: a scene that moves a light keeps its kernel */
     const std::vector<RtNode>& L = s.flat_lights;
     src += "    static constexpr uint32_t n_lights = " + std::to_string(L.size()) + "u;\n";
-    src += "    static constexpr uint32_t light_kind[" + std::to_string(L.empty() ? 1u : L.size()) + "] = {";
-    for (size_t i = 0; i < L.size(); ++i) src += (i ? ", " : "") + std::to_string(L[i].kind) + "u";
-    if (L.empty()) src += std::to_string(RT_NONE) + "u"; /* no zero-length arrays: one entry nobody reads */
-    src += "};\n";
+    row("light_kind", L.empty() ? 1u : L.size(), [&](size_t i) { return L.empty() ? RT_NONE : L[i].kind; }); /* no zero-length arrays: one entry nobody reads */
     /* where Lambertian materials sit (rt_core.h: RtLambertWalls): on which kinds of axis rect outside every wrapper -- their normal
      * is one of six constant vectors and so is their shading frame -- and whether on anything else.  A FlipFace folded into the
      * leaf (RT_LEAF_FLIPPED) changes neither the test nor the normal: such a leaf is a plain rect. */
@@ -282,16 +278,12 @@ std::string jit_source(const rt1w_scene& s, bool f32, bool tiles) {
     uint32_t depth = s.scope_depth < 2u ? 2u : s.scope_depth;
     src += std::string("typedef RtCfg<") + (s.has_media ? "true" : "false") + ", " + (s.has_tex ? "true" : "false") + ", " +
            (s.has_msphere ? "true" : "false") + ", true, " + std::to_string(depth) + ", TopoJit> CfgJit;\n";
-    if (tiles && !f32)
-        src += "extern \"C\" __global__ __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES(CfgJit)) void rt_jit_sorted(\n"
-               "    RtSceneView sc, RtFrame f, rt_f64* __restrict__ partial, unsigned long long* __restrict__ counters, RtTileList tl) {\n"
-               "    rt_render_sorted_body<CfgJit>(sc, f, partial, counters, tl);\n}\n"
-               /* what the host checks its own record of the list against before the first launch (context.h: RtTileArg) */
-               "extern \"C\" __device__ unsigned int rt_jit_tile_list_bytes = (unsigned int)sizeof(RtTileList);\n";
-    else
-        src += "extern \"C\" __global__ __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES(CfgJit)) void rt_jit_sorted(\n"
-               "    RtSceneView sc, RtFrame f, rt_f64* __restrict__ partial, unsigned long long* __restrict__ counters) {\n"
-               "    rt_render_sorted_body<CfgJit>(sc, f, partial, counters);\n}\n";
+    const bool tl = form == JIT_TILES; /* the tile table: the kernel's last parameter, the body's last argument */
+    src += std::string("extern \"C\" __global__ __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES(CfgJit)) void rt_jit_sorted(\n"
+                       "    RtSceneView sc, RtFrame f, rt_f64* __restrict__ partial, unsigned long long* __restrict__ counters") +
+           (tl ? ", RtTileList tl" : "") + ") {\n    rt_render_sorted_body<CfgJit>(sc, f, partial, counters" + (tl ? ", tl" : "") + ");\n}\n";
+    if (tl) /* what the host checks its own record of the list against before the first launch (context.h: RtTileArg) */
+        src += "extern \"C\" __device__ unsigned int rt_jit_tile_list_bytes = (unsigned int)sizeof(RtTileList);\n";
     return src;
 }
 
@@ -339,6 +331,20 @@ void jit_invalidate(const JitInfo& info) {
     if (!info.path.empty() && !u.empty() && info.path.compare(0, u.size(), u) == 0) std::remove(info.path.c_str());
 }
 
+/* the compiler with the clock running: info.compile_ms, info.message on failure; the code goes to dir + name (info.path, if it could be written) */
+static int compile_into(const std::string& src, const std::string& dir, const std::string& name, std::vector<char>& code, JitInfo& info) {
+    auto t0 = std::chrono::steady_clock::now();
+    std::string log;
+    int rc = jit_compile(src, code, log);
+    info.compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc < 0) { info.message = log; return rc; }
+    if (!dir.empty()) {
+        mkdirs(dir);
+        if (write_file_atomic(dir + name, code)) info.path = dir + name;
+    }
+    return RT1W_OK;
+}
+
 int jit_get_code(const std::string& src, bool allow_compile, std::vector<char>& code, JitInfo& info, bool ignore_cache) {
     info = JitInfo();
     if (src.empty()) { info.message = "scene is not eligible (more than RT_JIT_MAX_NODES nodes)"; return RT1W_ERR_UNSUPPORTED; }
@@ -353,34 +359,20 @@ int jit_get_code(const std::string& src, bool allow_compile, std::vector<char>& 
     const std::string uname = "/sweep_" + info.key + "-" + user_cache_tag() + ".hsaco";
     if (!user.empty() && !ignore_cache && read_file(user + uname, code)) { info.from_cache = true; info.path = user + uname; return RT1W_OK; }
     if (!allow_compile) { info.message = "no cached kernel for this topology"; return RT1W_ERR_STATE; }
-    auto t0 = std::chrono::steady_clock::now();
-    std::string log;
-    int rc = jit_compile(src, code, log);
-    info.compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (rc < 0) { info.message = log; return rc; }
-    if (!user.empty()) {
-        mkdirs(user);
-        if (write_file_atomic(user + uname, code)) info.path = user + uname;
-    }
-    return RT1W_OK;
+    return compile_into(src, user, uname, code, info); /* a user cache that cannot be written is no error: the kernel serves this context */
 }
 
-int jit_precompile_to(const rt1w_scene& s, const std::string& dir, JitInfo& info, bool f32, bool tiles) {
+int jit_precompile_to(const rt1w_scene& s, const std::string& dir, JitInfo& info, JitForm form) {
     info = JitInfo();
     if (!jit_eligible(s)) { info.message = "scene is not eligible"; return RT1W_ERR_UNSUPPORTED; }
-    const std::string src = jit_source(s, f32, tiles);
+    const std::string src = jit_source(s, form);
     info.key = jit_key(src);
-    const std::string path = dir + "/sweep_" + info.key + ".hsaco";
+    const std::string name = "/sweep_" + info.key + ".hsaco";
     std::vector<char> code;
-    if (read_file(path, code)) { info.from_cache = true; info.path = path; return RT1W_OK; }
-    auto t0 = std::chrono::steady_clock::now();
-    std::string log;
-    int rc = jit_compile(src, code, log);
-    info.compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (rc < 0) { info.message = log; return rc; }
-    mkdirs(dir);
-    if (!write_file_atomic(path, code)) { info.message = "cannot write " + path; return RT1W_ERR_STATE; }
-    info.path = path;
+    if (read_file(dir + name, code)) { info.from_cache = true; info.path = dir + name; return RT1W_OK; }
+    const int rc = compile_into(src, dir, name, code, info);
+    if (rc < 0) return rc;
+    if (info.path.empty()) { info.message = "cannot write " + dir + name; return RT1W_ERR_STATE; }
     /* which compiler made the directory's kernels: for the record only, no lookup reads it */
     const std::string note = compiler_id() + "\n";
     (void)write_file_atomic(dir + "/COMPILER", std::vector<char>(note.begin(), note.end()));
@@ -389,27 +381,31 @@ int jit_precompile_to(const rt1w_scene& s, const std::string& dir, JitInfo& info
 
 } // namespace rt1w
 
-/* the text of one form of the generated unit: the refusals and the copy the two source entries share */
-static int64_t kernel_source_of(const rt1w_scene* s, bool f32, bool tiles, char* buf, uint64_t cap) {
-    if (!s) { rt1w::set_error("null scene"); return RT1W_ERR_INVALID; }
+/* what the source and key entries refuse alike: a missing argument (in the entry's own words), a scene that is not committed or not eligible */
+static int kernel_refused(const rt1w_scene* s, bool args, const char* null_text) {
+    if (!s || !args) { rt1w::set_error(null_text); return RT1W_ERR_INVALID; }
     if (!s->committed) { rt1w::set_error("scene not committed"); return RT1W_ERR_STATE; }
     if (!rt1w::jit_eligible(*s)) { rt1w::set_error("scene has more than RT_JIT_MAX_NODES nodes: no specialised kernel"); return RT1W_ERR_UNSUPPORTED; }
-    const std::string src = rt1w::jit_source(*s, f32, tiles);
+    return RT1W_OK;
+}
+
+/* the text of one form of the generated unit: the copy the two source entries share */
+static int64_t kernel_source_of(const rt1w_scene* s, rt1w::JitForm form, char* buf, uint64_t cap) {
+    if (const int rc = kernel_refused(s, true, "null scene")) return rc;
+    const std::string src = rt1w::jit_source(*s, form);
     if (!buf) return (int64_t)src.size();
     if (cap < src.size()) { rt1w::set_error("buffer too small"); return RT1W_ERR_INVALID; }
     std::memcpy(buf, src.data(), src.size());
     return (int64_t)src.size();
 }
 
-extern "C" int64_t rt1w_scene_kernel_source(const rt1w_scene* s, int f32, char* buf, uint64_t cap) { return kernel_source_of(s, f32 != 0, false, buf, cap); }
-extern "C" int64_t rt1w_scene_kernel_source_tiles(const rt1w_scene* s, char* buf, uint64_t cap) { return kernel_source_of(s, false, true, buf, cap); }
+extern "C" int64_t rt1w_scene_kernel_source(const rt1w_scene* s, int f32, char* buf, uint64_t cap) { return kernel_source_of(s, f32 ? rt1w::JIT_F32 : rt1w::JIT_F64, buf, cap); }
+extern "C" int64_t rt1w_scene_kernel_source_tiles(const rt1w_scene* s, char* buf, uint64_t cap) { return kernel_source_of(s, rt1w::JIT_TILES, buf, cap); }
 
-static int kernel_key_of(const rt1w_scene* s, bool tiles, char out[24]) {
-    if (!s || !out) { rt1w::set_error("null argument"); return RT1W_ERR_INVALID; }
-    if (!s->committed) { rt1w::set_error("scene not committed"); return RT1W_ERR_STATE; }
-    if (!rt1w::jit_eligible(*s)) { rt1w::set_error("scene has more than RT_JIT_MAX_NODES nodes: no specialised kernel"); return RT1W_ERR_UNSUPPORTED; }
-    std::snprintf(out, 24, "%s", rt1w::jit_key(rt1w::jit_source(*s, false, tiles)).c_str());
+static int kernel_key_of(const rt1w_scene* s, rt1w::JitForm form, char out[24]) {
+    if (const int rc = kernel_refused(s, out != nullptr, "null argument")) return rc;
+    std::snprintf(out, 24, "%s", rt1w::jit_key(rt1w::jit_source(*s, form)).c_str());
     return RT1W_OK;
 }
-extern "C" int rt1w_scene_kernel_key(const rt1w_scene* s, char out[24]) { return kernel_key_of(s, false, out); }
-extern "C" int rt1w_scene_kernel_key_tiles(const rt1w_scene* s, char out[24]) { return kernel_key_of(s, true, out); }
+extern "C" int rt1w_scene_kernel_key(const rt1w_scene* s, char out[24]) { return kernel_key_of(s, rt1w::JIT_F64, out); }
+extern "C" int rt1w_scene_kernel_key_tiles(const rt1w_scene* s, char out[24]) { return kernel_key_of(s, rt1w::JIT_TILES, out); }

@@ -12,6 +12,11 @@
 
 #include "jit.h"
 
+/* which arms get which form: f64 and its tile-list form (rt1w_render_tiles with RT1W_TILES_SPECIALISED: the rounds of the adaptive
+ * entries) for every eligible arm, single precision (RT1W_PRECISION_F32) for the Cornell arms */
+static bool builds(int form, int arm) { return form != rt1w::JIT_F32 || arm == 5 || arm == 6; }
+static const char* const labels[rt1w::JIT_N_FORMS] = {"", " f32", " tiles"}; /* behind the seed in the progress lines (tools/resources_ab.py reads them) */
+
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: rt1w_precompile <out_dir> [build_seed ...]\n"); return 2; }
     const std::string dir = argv[1];
@@ -27,27 +32,15 @@ int main(int argc, char** argv) {
             if (rt1w_scene_build_reference(arm, seed, aspect, dummy_earth, 2, 2, &s, defaults) < 0) {
                 std::fprintf(stderr, "arm %d: %s\n", arm, rt1w_last_error()); ++failures; continue;
             }
-            if (rt1w::jit_eligible(*s)) {
+            for (int form = 0; form < rt1w::JIT_N_FORMS; ++form) {
+                if (!rt1w::jit_eligible(*s) || !builds(form, arm)) continue;
                 rt1w::JitInfo info;
-                int rc = rt1w::jit_precompile_to(*s, dir, info);
-                if (rc < 0) { std::fprintf(stderr, "arm %d seed %llu: %s\n", arm, seed, info.message.c_str()); ++failures; }
-                else keep.insert(info.path.substr(info.path.rfind('/') + 1));
-                if (rc >= 0) std::printf("arm %d seed %llu: %zu nodes -> %s (%s, %.1f s)\n", arm, seed, s->flat_nodes.size(), info.path.c_str(),
-                                 info.from_cache ? "present" : "compiled", info.compile_ms / 1e3);
-                { /* every arm's tile-list form (rt1w_render_tiles with RT1W_TILES_SPECIALISED: the rounds of the adaptive entries) */
-                    rt1w::JitInfo it;
-                    int rt = rt1w::jit_precompile_to(*s, dir, it, false, true);
-                    if (rt < 0) { std::fprintf(stderr, "arm %d seed %llu (tiles): %s\n", arm, seed, it.message.c_str()); ++failures; }
-                    else { keep.insert(it.path.substr(it.path.rfind('/') + 1));
-                           std::printf("arm %d seed %llu tiles: -> %s (%s, %.1f s)\n", arm, seed, it.path.c_str(), it.from_cache ? "present" : "compiled", it.compile_ms / 1e3); }
+                if (rt1w::jit_precompile_to(*s, dir, info, (rt1w::JitForm)form) < 0) {
+                    std::fprintf(stderr, "arm %d seed %llu%s: %s\n", arm, seed, labels[form], info.message.c_str()); ++failures; continue;
                 }
-                if (arm == 5 || arm == 6) { /* the Cornell arms also in single precision (RT1W_PRECISION_F32) */
-                    rt1w::JitInfo i32;
-                    int r32 = rt1w::jit_precompile_to(*s, dir, i32, true);
-                    if (r32 < 0) { std::fprintf(stderr, "arm %d seed %llu (f32): %s\n", arm, seed, i32.message.c_str()); ++failures; }
-                    else { keep.insert(i32.path.substr(i32.path.rfind('/') + 1));
-                           std::printf("arm %d seed %llu f32: -> %s (%s, %.1f s)\n", arm, seed, i32.path.c_str(), i32.from_cache ? "present" : "compiled", i32.compile_ms / 1e3); }
-                }
+                keep.insert(info.path.substr(info.path.rfind('/') + 1));
+                std::printf("arm %d seed %llu%s: %zu nodes -> %s (%s, %.1f s)\n", arm, seed, labels[form], s->flat_nodes.size(), info.path.c_str(),
+                            info.from_cache ? "present" : "compiled", info.compile_ms / 1e3);
             }
             rt1w_scene_destroy(s);
         }

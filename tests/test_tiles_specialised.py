@@ -1,4 +1,4 @@
-"""The tile-list form of the scene-specialised kernels, host side (csrc/jit.cpp: jit_source with `tiles`; include/rt1w.h:
+"""The tile-list form of the scene-specialised kernels, host side (csrc/jit.cpp: jit_source of JIT_TILES; include/rt1w.h:
 rt1w_scene_kernel_key_tiles, rt1w_scene_kernel_source_tiles): the generated text, its key, the code objects the build leaves in
 <package>/kernels and the refusals.  No GPU."""
 import os
