@@ -885,8 +885,72 @@ int rt1w_temporal_accumulate_device(rt1w_context* c, const rt1w_temporal_params*
  * read and written by this entry alone: no other entry's result depends on it. */
 int rt1w_render_temporal(rt1w_context* c, const rt1w_render_params* p, const rt1w_temporal_params* t /* NULL: defaults */,
                          const rt1w_denoise_params* d /* NULL: no filter */, double* out_rgb, rt1w_stats* stats);
-/* forget the history: the next rt1w_render_temporal is a first frame.  The buffers stay allocated. */
+/* forget the history: the next rt1w_render_temporal -- and the next rt1w_render_temporal_var, whose state is its own -- is a first frame.
+ * The buffers stay allocated. */
 int rt1w_temporal_reset(rt1w_context* c);
+
+/* ---- temporal second moments: a variance for the filter from the history ----
+ * An animation carries a variance estimate for free: the spread of a pixel's values from frame to frame is the variance of its
+ * accumulated mean (Schied et al. 2017, SVGF).  One more history channel, the running mean of the squared demodulated luminance, and one
+ * small pass turn the history into the `var` buffer rt1w_denoise_var takes -- one render launch per frame instead of rt1w_batch_variance's
+ * K.  Replaces nothing of the reference, which renders stills.  No entry above changes; the parameters are rt1w_temporal_params and
+ * rt1w_denoise_params.
+ * rt1w_temporal_moments: the arguments of rt1w_temporal_accumulate, with prev_m2 double[h][w] after prev_hist (the output `m2` of the
+ *   previous frame's call) and the output m2 double[h][w] after hist.  Steps 1-8 are rt1w_temporal_accumulate's, word for word: hist, len
+ *   and frame_out are ITS BITS on the same inputs.  In addition, with l = the luminance (0.2126 r + 0.7152 g) + 0.0722 b of the
+ *   demodulated current value c of step 1:
+ *     no history:    m2 = l * l;
+ *     with history:  m2 = (N' * (sum of weight * prev_m2 over the valid taps of step 5, in that order, / the sum of their weights) + l * l)
+ *                         / (N' + 1), with the N' of step 7.
+ *   prev_m2 is no part of a tap's validity (the tap set stays the accumulate entry's) and an invalid tap's prev_m2 is never read into a
+ *   product: with prev_len = 0 everywhere prev_m2 may hold anything.  A valid tap whose prev_m2 is not finite gives an m2 that is not
+ *   finite, which rt1w_temporal_variance answers with "no estimate".  The four outputs must not overlap each other or an input:
+ *   RT1W_ERR_INVALID.  Refusals, stats and work mapping as rt1w_temporal_accumulate; 256 bytes per pixel against its 240.
+ * rt1w_temporal_variance: hist double[h][w][3], m2 and len double[h][w] as rt1w_temporal_moments wrote them, aov double[h][w][8] the
+ *   CURRENT frame's feature buffers -> var double[h][w], the buffer rt1w_denoise_var takes: the variance of the mean demodulated
+ *   luminance.  Per pixel p, with l1 = lum(hist_p) -- the luminance is linear, so this is the running mean of l up to rounding, and no
+ *   first-moment channel is kept:
+ *     Temporal estimate, where len_p >= RT1W_TEMPORAL_MIN_LEN (4: a constant as in SVGF, not a parameter):
+ *       var = max(m2_p - l1 * l1, 0) / (len_p - 1).
+ *     Spatial estimate, where len_p < 4.  The taps are q = p + (dx, dy), dx, dy = -3 .. 3, inside the image, in row order (dy outer).  The
+ *       guides are the prepare pass's of rt1w_denoise: unit normal, depth, coverage.  The centre tap has weight 1; every other tap has the
+ *       guide-only weight of the variance filter, w_normal * k(x_depth + x_coverage) with rt1w_denoise's defaults (normal power 32,
+ *       sigma_depth 0.1).  A tap is taken if w > 0 and lum(hist_q) and m2_q are finite.  S0 = sum w, S1 = sum w * lum(hist_q),
+ *       S2 = sum w * m2_q;  M1 = S1 / S0, M2 = S2 / S0;  var = max(M2 - M1 * M1, 0) / len_p.
+ *     var = 0 ("no usable estimate", rt1w_batch_variance's rule) where l1, m2_p or len_p is not finite, where len_p < 1, and where the
+ *       result is negative or not finite.
+ *   var must not overlap an input, width and height are 1 .. 2^30: RT1W_ERR_INVALID.  One lane per pixel in the work mapping of
+ *   rt1w_temporal_accumulate, no atomics, no LDS: a lane of a short history walks the 49 taps through global memory, every other lane
+ *   reads its own 104 bytes.  stats as rt1w_temporal_accumulate.
+ *   A stated limit: the first frame of an animation has no history, so its variance is the spatial estimate alone, which takes the
+ *   frame's own texture under the window for noise (DESIGN.md section 21 has the measurement).
+ * Both are bit-identical to the CPU build of the same code (librt1w_lab.so: rt1w_lab_temporal_moments_host,
+ * rt1w_lab_temporal_variance_host). */
+#define RT1W_TEMPORAL_MIN_LEN 4
+int rt1w_temporal_moments(rt1w_context* c, const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
+                          const double* prev_hist, const double* prev_m2, const double* prev_len, const double* prev_aov, const rt1w_camera* prev_cam,
+                          double* hist, double* m2, double* len, double* frame_out, rt1w_stats* stats);
+/* same on device memory of the context's GPU; the cameras are host memory.  Synchronises the context's stream before returning. */
+int rt1w_temporal_moments_device(rt1w_context* c, const rt1w_temporal_params* p, const void* d_cur_frame, const void* d_cur_aov, const rt1w_camera* cur_cam,
+                                 const void* d_prev_hist, const void* d_prev_m2, const void* d_prev_len, const void* d_prev_aov,
+                                 const rt1w_camera* prev_cam, void* d_hist, void* d_m2, void* d_len, void* d_frame_out, rt1w_stats* stats);
+int rt1w_temporal_variance(rt1w_context* c, uint32_t width, uint32_t height, const double* hist, const double* m2, const double* len, const double* aov,
+                           double* var, rt1w_stats* stats);
+int rt1w_temporal_variance_device(rt1w_context* c, uint32_t width, uint32_t height, const void* d_hist, const void* d_m2, const void* d_len,
+                                  const void* d_aov, void* d_var, rt1w_stats* stats);
+/* One frame of an animation, filtered with the history's own variance, in one call.  In this order: rt1w_render_device of the whole image,
+ * rt1w_render_aov_device of the same spp, sample_offset and global_seed, rt1w_temporal_moments_device against a state of this entry's
+ * own (two swapping sets of hist, m2, len and feature buffers, grown on demand and freed with the context; zeroed on the first call,
+ * after rt1w_temporal_reset and after a change of size -- never rt1w_render_temporal's state, so the two entries may be interleaved),
+ * rt1w_temporal_variance_device of the new history with the current feature buffers, rt1w_denoise_var_device of frame_out with the
+ * current feature buffers, that var, `d` (NULL: every default) and sigma_variance, one device->host copy into
+ * out_rgb[height][width][3].  Bit-identical to composing these public entries.  The filter is always on: without it the call would be
+ * rt1w_render_temporal.  Refuses what rt1w_render_temporal refuses, sigma_variance as rt1w_denoise_var does, and a `t` and a `d` that
+ * disagree on RT1W_DENOISE_KEEP_ALBEDO (var is in the units of t's demodulation): RT1W_ERR_INVALID; sigma_variance and that disagreement
+ * are decided before the context is looked at.  stats as rt1w_render_temporal, every kernel of the call in kernel_ms, grid / block of the
+ * filter's level kernel. */
+int rt1w_render_temporal_var(rt1w_context* c, const rt1w_render_params* p, const rt1w_temporal_params* t /* NULL: defaults */,
+                             const rt1w_denoise_params* d /* NULL: defaults */, double sigma_variance, double* out_rgb, rt1w_stats* stats);
 
 /* Page-locked host memory for output frames (hipHostMalloc / hipHostRegister): device->host copies into it run at full
  * PCIe rate and asynchronously.  rt1w_host_register pins memory the caller already owns, e.g. a POSIX shared-memory

@@ -281,6 +281,11 @@ _sig("rt1w_temporal_accumulate", C.c_int, _P, C.POINTER(TemporalParams), _P, _P,
 _sig("rt1w_temporal_accumulate_device", C.c_int, _P, C.POINTER(TemporalParams), _P, _P, C.POINTER(Camera), _P, _P, _P, C.POINTER(Camera), _P, _P, _P, C.POINTER(Stats))
 _sig("rt1w_render_temporal", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(TemporalParams), C.POINTER(DenoiseParams), _P, C.POINTER(Stats))
 _sig("rt1w_temporal_reset", C.c_int, _P)
+_sig("rt1w_temporal_moments", C.c_int, _P, C.POINTER(TemporalParams), _P, _P, C.POINTER(Camera), _P, _P, _P, _P, C.POINTER(Camera), _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_temporal_moments_device", C.c_int, _P, C.POINTER(TemporalParams), _P, _P, C.POINTER(Camera), _P, _P, _P, _P, C.POINTER(Camera), _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_temporal_variance", C.c_int, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_temporal_variance_device", C.c_int, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_render_temporal_var", C.c_int, _P, C.POINTER(RenderParams), C.POINTER(TemporalParams), C.POINTER(DenoiseParams), C.c_double, _P, C.POINTER(Stats))
 _sig("rt1w_abi_sizeof", C.c_uint32, C.c_int)
 _sig("rt1w_host_alloc", C.c_int, C.c_uint64, C.POINTER(_P))
 _sig("rt1w_host_free", C.c_int, _P)
@@ -334,6 +339,22 @@ def _temporal_args(cur_frame, cur_aov, prev_hist, prev_len, prev_aov):
     if h.shape != f.shape or n.shape != f.shape[:2]:
         raise ValueError("prev_hist must be [h, w, 3] and prev_len [h, w], the current frame's size")
     return f, a, h, n, q
+
+
+def _moments_args(cur_frame, cur_aov, prev_hist, prev_m2, prev_len, prev_aov):
+    f, a, h, n, q = _temporal_args(cur_frame, cur_aov, prev_hist, prev_len, prev_aov)
+    m = np.ascontiguousarray(prev_m2, dtype=np.float64)
+    if m.shape != f.shape[:2]:
+        raise ValueError("prev_m2 must be [h, w], the current frame's size")
+    return f, a, h, m, n, q
+
+
+def _variance_args(hist, m2, length, aov):
+    h, a = _frame_and_aov(hist, aov)
+    m, n = (np.ascontiguousarray(x, dtype=np.float64) for x in (m2, length))
+    if m.shape != h.shape[:2] or n.shape != h.shape[:2]:
+        raise ValueError("m2 and len must be [h, w], the history's size")
+    return h, m, n, a
 
 
 def reference_camera(arm, aspect_ratio=None):
@@ -855,8 +876,64 @@ class Context:
                                       out.ctypes.data_as(_P), C.byref(st)))
         return (out, _stats_dict(st)) if with_stats else out
 
+    def temporal_moments(self, cur_frame, cur_aov, cur_cam, prev_hist, prev_m2, prev_len, prev_aov, prev_cam, with_stats=False, **kw):
+        """temporal_accumulate with the second-moment channel (rt1w_temporal_moments): prev_m2 [h, w] goes in after prev_hist, and
+        (hist, m2, len, frame_out) come back; hist, len and frame_out are temporal_accumulate's bits.  kw as temporal_accumulate's."""
+        f, a, h, m, n, q = _moments_args(cur_frame, cur_aov, prev_hist, prev_m2, prev_len, prev_aov)
+        p = _temporal_params(f.shape[1], f.shape[0], **kw)
+        hist, m2, ln, out = np.empty_like(f), np.empty_like(n), np.empty_like(n), np.empty_like(f)
+        st = Stats()
+        _ck(_lib.rt1w_temporal_moments(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(Camera.of(cur_cam)),
+                                       h.ctypes.data_as(_P), m.ctypes.data_as(_P), n.ctypes.data_as(_P), q.ctypes.data_as(_P),
+                                       C.byref(Camera.of(prev_cam)), hist.ctypes.data_as(_P), m2.ctypes.data_as(_P), ln.ctypes.data_as(_P),
+                                       out.ctypes.data_as(_P), C.byref(st)))
+        return (hist, m2, ln, out, _stats_dict(st)) if with_stats else (hist, m2, ln, out)
+
+    def temporal_moments_device(self, d_cur_frame, d_cur_aov, cur_cam, d_prev_hist, d_prev_m2, d_prev_len, d_prev_aov, prev_cam, d_hist, d_m2,
+                                d_len, d_frame_out, width, height, **kw):
+        """Same on device memory (int addresses, e.g. torch tensors' .data_ptr()).  Returns the stats dict."""
+        p = _temporal_params(width, height, **kw)
+        st = Stats()
+        _ck(_lib.rt1w_temporal_moments_device(self._h, C.byref(p), C.c_void_p(d_cur_frame), C.c_void_p(d_cur_aov), C.byref(Camera.of(cur_cam)),
+                                              C.c_void_p(d_prev_hist), C.c_void_p(d_prev_m2), C.c_void_p(d_prev_len), C.c_void_p(d_prev_aov),
+                                              C.byref(Camera.of(prev_cam)), C.c_void_p(d_hist), C.c_void_p(d_m2), C.c_void_p(d_len),
+                                              C.c_void_p(d_frame_out), C.byref(st)))
+        return _stats_dict(st)
+
+    def temporal_variance(self, hist, m2, length, aov, with_stats=False):
+        """The variance buffer of denoise_var from a history (rt1w_temporal_variance): hist [h, w, 3], m2 and len [h, w] as
+        temporal_moments returned them, aov the CURRENT frame's feature buffers: var [h, w]."""
+        h, m, n, a = _variance_args(hist, m2, length, aov)
+        var = np.empty_like(m)
+        st = Stats()
+        _ck(_lib.rt1w_temporal_variance(self._h, h.shape[1], h.shape[0], h.ctypes.data_as(_P), m.ctypes.data_as(_P), n.ctypes.data_as(_P),
+                                        a.ctypes.data_as(_P), var.ctypes.data_as(_P), C.byref(st)))
+        return (var, _stats_dict(st)) if with_stats else var
+
+    def temporal_variance_device(self, d_hist, d_m2, d_len, d_aov, d_var, width, height):
+        """Same on device memory (int addresses).  Returns the stats dict."""
+        st = Stats()
+        _ck(_lib.rt1w_temporal_variance_device(self._h, width, height, C.c_void_p(d_hist), C.c_void_p(d_m2), C.c_void_p(d_len), C.c_void_p(d_aov),
+                                               C.c_void_p(d_var), C.byref(st)))
+        return _stats_dict(st)
+
+    def render_temporal_var(self, width, height, spp, max_depth=50, sample_offset=0, global_seed=0, temporal=None, denoise=None,
+                            sigma_variance=0.0, flags=0, with_stats=False, **kw):
+        """One frame of an animation filtered with the history's own variance (rt1w_render_temporal_var): render, feature buffers,
+        temporal_moments against a state of this entry's own, temporal_variance, denoise_var: float64 [height, width, 3].  `temporal`:
+        dict of temporal_accumulate's keywords, `denoise`: dict of Context.denoise's; other kw as Context.render's."""
+        p = self._params(width, height, spp, max_depth, kw.pop("tile", None), sample_offset, global_seed, 0, False, kw.pop("variant", None), **kw)
+        p.flags |= flags
+        t = _temporal_params(0, 0, **temporal) if temporal is not None else None
+        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
+        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
+        st = Stats()
+        _ck(_lib.rt1w_render_temporal_var(self._h, C.byref(p), C.byref(t) if t is not None else None, C.byref(d) if d is not None else None,
+                                          sigma_variance, out.ctypes.data_as(_P), C.byref(st)))
+        return (out, _stats_dict(st)) if with_stats else out
+
     def temporal_reset(self):
-        """Forget the history of render_temporal (rt1w_temporal_reset): the next call is a first frame."""
+        """Forget the history of render_temporal and of render_temporal_var (rt1w_temporal_reset): the next call is a first frame."""
         _ck(_lib.rt1w_temporal_reset(self._h))
 
     def _render_denoised(self, deep, width, height, spp, max_depth, tile, sample_offset, global_seed, denoise, flags, strips, precision, with_stats, kw):
@@ -1319,6 +1396,38 @@ def temporal_host(cur_frame, cur_aov, cur_cam, prev_hist, prev_len, prev_aov, pr
     if rc < 0:
         raise Rt1wError(rc, "rt1w_lab_temporal_host")
     return (hist, ln, out, rec) if with_record else (hist, ln, out)
+
+
+def temporal_moments_host(cur_frame, cur_aov, cur_cam, prev_hist, prev_m2, prev_len, prev_aov, prev_cam, with_record=False, **kw):
+    """CPU twin of Context.temporal_moments (librt1w_lab.so: rt1w_lab_temporal_moments_host): the (hist, m2, len, frame_out) the GPU must
+    equal bit for bit.  No GPU needed.  with_record: also temporal_host's record [h, w, 8]."""
+    fn = load_lab().rt1w_lab_temporal_moments_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(TemporalParams), _P, _P, C.POINTER(Camera), _P, _P, _P, _P, C.POINTER(Camera), _P, _P, _P, _P, _P]
+    f, a, h, m, n, q = _moments_args(cur_frame, cur_aov, prev_hist, prev_m2, prev_len, prev_aov)
+    p = _temporal_params(f.shape[1], f.shape[0], **kw)
+    hist, m2, ln, out = np.empty_like(f), np.empty_like(n), np.empty_like(n), np.empty_like(f)
+    rec = np.zeros(f.shape[:2] + (8,)) if with_record else None
+    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(Camera.of(cur_cam)), h.ctypes.data_as(_P), m.ctypes.data_as(_P),
+            n.ctypes.data_as(_P), q.ctypes.data_as(_P), C.byref(Camera.of(prev_cam)), hist.ctypes.data_as(_P), m2.ctypes.data_as(_P),
+            ln.ctypes.data_as(_P), out.ctypes.data_as(_P), rec.ctypes.data_as(_P) if with_record else None)
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_temporal_moments_host")
+    return (hist, m2, ln, out, rec) if with_record else (hist, m2, ln, out)
+
+
+def temporal_variance_host(hist, m2, length, aov):
+    """CPU twin of Context.temporal_variance (librt1w_lab.so: rt1w_lab_temporal_variance_host): the var [h, w] the GPU must equal bit
+    for bit.  No GPU needed."""
+    fn = load_lab().rt1w_lab_temporal_variance_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]
+    h, m, n, a = _variance_args(hist, m2, length, aov)
+    var = np.empty_like(m)
+    rc = fn(h.shape[1], h.shape[0], h.ctypes.data_as(_P), m.ctypes.data_as(_P), n.ctypes.data_as(_P), a.ctypes.data_as(_P), var.ctypes.data_as(_P))
+    if rc < 0:
+        raise Rt1wError(rc, "rt1w_lab_temporal_variance_host")
+    return var
 
 
 def scene_set_camera_host(scene, look_from, look_at, vup, vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1):

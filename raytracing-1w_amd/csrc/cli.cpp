@@ -7,11 +7,12 @@
  *        [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic]
  *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
  *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]]
- *        [--frames N --orbit DEG [--denoise]]
+ *        [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]]
  * --frames N --orbit DEG renders an animation of N frames through rt1w_render_temporal: before frame k look_from is turned about the
  * vertical axis through look_at by k * DEG degrees (rt1w_context_set_camera; the scene, its upload and its kernel are frame 0's), the
  * frame's seed is --seed + k, and the previous frames' samples are reused where their surface points are seen again; with --denoise
- * the feature-guided filter follows.  Frame k is written to NAME_%04d.ppm, NAME being --out without its ".ppm" (default "frame").
+ * the feature-guided filter follows; with --denoise --temporal-variance [SIGMA] the frames go through rt1w_render_temporal_var instead: the
+ * variance-guided filter, steered by the variance the history itself carries (SIGMA: sigma_variance, default 3).  Frame k is written to NAME_%04d.ppm, NAME being --out without its ".ppm" (default "frame").
  * --adaptive BUDGET spends a budget of BUDGET mean samples per pixel where the frame is noisy (rt1w_render_adaptive; --spp is ignored),
  * at most --max-spp samples on one pixel, none on tiles whose error is at or below --target-error; with --denoise --variance the
  * variance-guided filter follows (first-hit guides of the pilot's samples; K and --deep-guides do not apply).
@@ -62,6 +63,7 @@ int main(int argc, char** argv) {
     std::string err_path;
     long frames = 0;                 /* > 0: an animation through rt1w_render_temporal */
     double orbit = 0.0;
+    double temporal_variance = -1.0; /* >= 0: the frames through rt1w_render_temporal_var with this sigma_variance (0 = default) */
     double target_error = 0.0;
     long width = -1, height = -1, spp = -1, depth = 50; /* MAX_DEPTH main.rs:801 */
     unsigned long long build_seed = 1, seed = 0;
@@ -106,11 +108,15 @@ int main(int argc, char** argv) {
         else if (a == "--specialised-tiles") specialised_tiles = true;
         else if (a == "--err-out") err_path = next("--err-out");
         else if (a == "--frames") frames = std::atol(next("--frames"));
+        else if (a == "--temporal-variance") {
+            temporal_variance = 0.0;
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) temporal_variance = std::atof(argv[++i]);
+        }
         else if (a == "--orbit") orbit = std::atof(next("--orbit"));
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--target-error") target_error = std::atof(next("--target-error"));
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]] [--frames N --orbit DEG [--denoise]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]] [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -156,6 +162,7 @@ int main(int argc, char** argv) {
     if (reference_stream) p.flags |= RT1W_RNG_REFERENCE;
     if (f32) p.precision = RT1W_PRECISION_F32;
     rt1w_stats st;
+    if (temporal_variance >= 0.0 && (frames <= 0 || !denoise)) { std::fprintf(stderr, "rt1w: --temporal-variance goes with --frames N --denoise\n"); return 2; }
     if (frames > 0) {
         if (adaptive >= 0 || variance >= 0 || deep_guides >= 0 || reference_stream || f32) { std::fprintf(stderr, "rt1w: --frames goes with --denoise only\n"); return 2; }
         double lf[3], la[3], up[3], vfov, aperture, focus;
@@ -175,7 +182,8 @@ int main(int argc, char** argv) {
             const double from[3] = {la[0] + c * dx + sn * dz, lf[1], la[2] - sn * dx + c * dz};
             if (rt1w_context_set_camera(ctx, from, la, up, vfov, aspect, aperture, focus, 0.0, 1.0) < 0) return fail("camera");
             p.global_seed = (uint32_t)seed + (uint32_t)k;
-            if (rt1w_render_temporal(ctx, &p, nullptr, denoise ? &d : nullptr, means.data(), &st) < 0) return fail("render");
+            if ((temporal_variance >= 0.0 ? rt1w_render_temporal_var(ctx, &p, nullptr, &d, temporal_variance, means.data(), &st)
+                                          : rt1w_render_temporal(ctx, &p, nullptr, denoise ? &d : nullptr, means.data(), &st)) < 0) return fail("render");
             kernel_ms += st.kernel_ms;
             const int64_t n = rt1w_format_ppm(means.data(), p.width, p.height, nullptr, 0);
             if (n < 0) return fail("format");

@@ -92,6 +92,10 @@ struct rt1w_context {
     void* tm_buf[2] = {nullptr, nullptr}; size_t tm_bytes[2] = {0, 0};
     uint32_t tm_w = 0, tm_h = 0; int tm_prev = 0; bool tm_valid = false;
     RtCamera tm_cam{};
+    /* rt1w_render_temporal_var: a state of its own, the same scheme -- two sets of (hist[3], m2[1], len[1], aov[8]) per pixel that swap */
+    void* tv_buf[2] = {nullptr, nullptr}; size_t tv_bytes[2] = {0, 0};
+    uint32_t tv_w = 0, tv_h = 0; int tv_prev = 0; bool tv_valid = false;
+    RtCamera tv_cam{};
     RtKernel k64[RT_N_WALKS][RT_N_VARIANTS] = {}; /* g_kernels, queried at creation; the node-cache walks only with a walk table */
     bool walk_table = false; uint32_t walk_table_first = 0;
     bool sphere_media = false; /* every medium of the scene is bounded by a bare Sphere: the sphere-media walks serve */

@@ -761,7 +761,7 @@ int rt1w_context_create(int device_id, const rt1w_scene* s, rt1w_context** out) 
 void rt1w_context_destroy(rt1w_context* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    void* bufs[] = {c->d_nodes, c->d_lights, c->d_materials, c->d_textures, c->d_perlin, c->d_images, c->d_out, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], c->d_batches, c->d_accum, c->d_tiles, c->tm_buf[0], c->tm_buf[1]};
+    void* bufs[] = {c->d_nodes, c->d_lights, c->d_materials, c->d_textures, c->d_perlin, c->d_images, c->d_out, c->dn_buf[0], c->dn_buf[1], c->dn_buf[2], c->d_batches, c->d_accum, c->d_tiles, c->tm_buf[0], c->tm_buf[1], c->tv_buf[0], c->tv_buf[1]};
     if (c->wf_state && g_wf_destroy) g_wf_destroy(c->wf_state);
     for (void* b : bufs) if (b) (void)hipFree(b);
     rt1w_internal_f32_destroy(c->f32_scene);

@@ -1,4 +1,4 @@
-/* denoise_host.cpp -- the CPU twin of the filter kernels (denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip) and of temporal accumulation (temporal.hip): rt_denoise.h, rt_denoise_var.h, rt_denoise_halves.h, rt_denoise_cross.h and rt_temporal.h compiled for the host (g++, -ffp-contract=off
+/* denoise_host.cpp -- the CPU twin of the filter kernels (denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip) and of temporal accumulation and its variance (temporal.hip, temporal_var.hip): rt_denoise.h, rt_denoise_var.h, rt_denoise_halves.h, rt_denoise_cross.h, rt_temporal.h and rt_temporal_var.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core).  Diagnostics library only (librt1w_lab.so): the expected side of the GPU tests' bit-equality checks
  * and what the CPU tier's property and quality tests run.  librt1w.so keeps no CPU path. */
 #include <cstring>
@@ -11,6 +11,7 @@
 #include "rt_denoise_halves.h"
 #include "rt_denoise_cross.h"
 #include "rt_temporal.h"
+#include "rt_temporal_var.h"
 #include "walk_lab.h"
 
 namespace {
@@ -143,9 +144,50 @@ extern "C" int rt1w_lab_temporal_host(const rt1w_temporal_params* p, const doubl
     for_rows(P.h, [&](uint32_t y) {
         for (uint32_t x = 0; x < P.w; ++x) {
             const size_t i = (size_t)y * P.w + x;
-            rt_tm_pixel(P, cc, pc, cur_frame, cur_aov, prev_hist, prev_len, prev_aov, x, y, hist + i * 3, len + i, frame_out + i * 3,
+            rt_tm_pixel(P, cc, pc, cur_frame, cur_aov, prev_hist, prev_len, prev_aov, nullptr, x, y, hist + i * 3, len + i, frame_out + i * 3,
+                        nullptr, rec ? rec + i * RT_TM_REC : nullptr);
+        }
+    });
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_temporal_moments_host(const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
+                                              const double* prev_hist, const double* prev_m2, const double* prev_len, const double* prev_aov,
+                                              const rt1w_camera* prev_cam, double* hist, double* m2, double* len, double* frame_out, double* rec) {
+    if (!p || !cur_frame || !cur_aov || !cur_cam || !prev_hist || !prev_m2 || !prev_len || !prev_aov || !prev_cam || !hist || !m2 || !len || !frame_out)
+        return RT1W_ERR_INVALID;
+    RtTmParams P;
+    if (!rt_tm_make_params(p->width, p->height, p->flags, p->max_history, p->depth_tol, p->normal_min, P)) return RT1W_ERR_INVALID;
+    const size_t n = (size_t)P.w * P.h;
+    /* the entries' own check: an output that overlaps another buffer of the call */
+    const struct { const double* p; size_t count; } b[10] = {{cur_frame, n * 3}, {cur_aov, n * 8}, {prev_hist, n * 3}, {prev_m2, n}, {prev_len, n},
+                                                             {prev_aov, n * 8}, {hist, n * 3}, {m2, n}, {len, n}, {frame_out, n * 3}};
+    for (int o = 6; o < 10; ++o)
+        for (int k = 0; k < 10; ++k)
+            if (k != o && (const char*)b[o].p < (const char*)(b[k].p + b[k].count) && (const char*)b[k].p < (const char*)(b[o].p + b[o].count)) return RT1W_ERR_INVALID;
+    RtCamera cc, pc;
+    memcpy(&cc, cur_cam, sizeof cc);
+    memcpy(&pc, prev_cam, sizeof pc);
+    for_rows(P.h, [&](uint32_t y) {
+        for (uint32_t x = 0; x < P.w; ++x) {
+            const size_t i = (size_t)y * P.w + x;
+            rt_tm_pixel(P, cc, pc, cur_frame, cur_aov, prev_hist, prev_len, prev_aov, prev_m2, x, y, hist + i * 3, len + i, frame_out + i * 3, m2 + i,
                         rec ? rec + i * RT_TM_REC : nullptr);
         }
+    });
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_temporal_variance_host(uint32_t width, uint32_t height, const double* hist, const double* m2, const double* len, const double* aov,
+                                               double* var) {
+    RtDnParams P;
+    if (!hist || !m2 || !len || !aov || !var || !rt_tv_make_params(width, height, P)) return RT1W_ERR_INVALID;
+    const size_t n = (size_t)P.w * P.h;
+    const struct { const double* p; size_t count; } b[4] = {{hist, n * 3}, {m2, n}, {len, n}, {aov, n * 8}};
+    for (int k = 0; k < 4; ++k)
+        if ((const char*)var < (const char*)(b[k].p + b[k].count) && (const char*)b[k].p < (const char*)(var + n)) return RT1W_ERR_INVALID;
+    for_rows(P.h, [&](uint32_t y) {
+        for (uint32_t x = 0; x < P.w; ++x) var[(size_t)y * P.w + x] = rt_tv_pixel(P, hist, m2, len, aov, x, y);
     });
     return RT1W_OK;
 }

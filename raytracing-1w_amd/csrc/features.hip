@@ -1,6 +1,6 @@
 /* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_denoise*,
- * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_guides_*, rt1w_render_adaptive*, rt1w_temporal_*, rt1w_render_temporal) and a live context's camera (rt1w_context_set_camera).  Host code only, built without a device pass: the kernels
- * belong to aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip and temporal.hip and are reached through rt_feature_launch.h, the context and its render
+ * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_guides_*, rt1w_render_adaptive*, rt1w_temporal_*, rt1w_render_temporal*) and a live context's camera (rt1w_context_set_camera).  Host code only, built without a device pass: the kernels
+ * belong to aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip, temporal.hip and temporal_var.hip and are reached through rt_feature_launch.h, the context and its render
  * path belong to context.hip (context.h), so a change here rebuilds none of the code objects.
  * Every entry is its checks, in the order its callers know, then one table of its buffers (Staged) handed to staged_entry(), which does what
  * the host and the device form of an entry differ in -- growing the context's buffers, laying the call's buffers out in them, the copies
@@ -843,6 +843,16 @@ int temporal_common(rt1w_context* c, const rt1w_temporal_params* p, const double
                                              d_prev_hist, d_prev_len, d_prev_aov, prev_cam, d_hist, d_len, d_frame_out, stream, launch);
     });
 }
+/* true: output row `o` of an entry's table overlaps another row of it (the caller's buffers: an input's `in`, an output's `out`) */
+template <size_t N>
+bool staged_output_overlaps(const Staged (&s)[N], size_t o) {
+    const char* a = (const char*)s[o].out;
+    for (size_t k = 0; k < N; ++k) {
+        const char* b = s[k].out ? (const char*)s[k].out : (const char*)s[k].in;
+        if (k != o && a < b + s[k].count * sizeof(double) && b < a + s[o].count * sizeof(double)) return true;
+    }
+    return false;
+}
 /* the two rt1w_temporal_accumulate entries.  Host form: the eight buffers one behind the other in the framebuffer */
 int temporal_accumulate(rt1w_context* c, const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
                         const double* prev_hist, const double* prev_len, const double* prev_aov, const rt1w_camera* prev_cam, double* hist, double* len,
@@ -860,15 +870,8 @@ int temporal_accumulate(rt1w_context* c, const rt1w_temporal_params* p, const do
                   {nullptr, hist, npix * 3, FRAMEBUFFER, nullptr, "temporal: history result copy"},
                   {nullptr, len, npix, FRAMEBUFFER, nullptr, "temporal: history length result copy"},
                   {nullptr, frame_out, npix * 3, FRAMEBUFFER, nullptr, "temporal: frame result copy"}};
-    /* an output that overlaps another buffer of the call (the three outputs are rows 5 .. 7) */
-    for (int o = 5; o < 8; ++o)
-        for (int k = 0; k < 8; ++k) {
-            const char* a = (const char*)s[o].out;
-            const char* b = k < 5 ? (const char*)s[k].in : (const char*)s[k].out;
-            if (k != o && a < b + s[k].count * sizeof(double) && b < a + s[o].count * sizeof(double)) {
-                set_error("temporal: hist, len and frame_out must not overlap each other or an input"); return RT1W_ERR_INVALID;
-            }
-        }
+    for (size_t o = 5; o < 8; ++o) /* the three outputs */
+        if (staged_output_overlaps(s, o)) { set_error("temporal: hist, len and frame_out must not overlap each other or an input"); return RT1W_ERR_INVALID; }
     return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
         return temporal_common(c, p, s[0].d_in, s[1].d_in, cur_cam, s[2].d_in, s[3].d_in, s[4].d_in, prev_cam, s[5].d_out, s[6].d_out, s[7].d_out, st);
     });
@@ -922,6 +925,122 @@ int render_temporal(rt1w_context* c, const rt1w_render_params* p, const rt1w_tem
     });
 }
 
+/* ---- the variance of a temporal history (include/rt1w.h: rt1w_temporal_moments, rt1w_temporal_variance, rt1w_render_temporal_var) ---- */
+int temporal_moments_common(rt1w_context* c, const rt1w_temporal_params* p, const double* d_cur_frame, const double* d_cur_aov, const void* cur_cam,
+                            const double* d_prev_hist, const double* d_prev_m2, const double* d_prev_len, const double* d_prev_aov, const void* prev_cam,
+                            double* d_hist, double* d_m2, double* d_len, double* d_frame_out, rt1w_stats* stats) {
+    if (rt1w_internal_temporal_var_sizeof() != sizeof(rt1w_camera)) { set_error("temporal kernel built against another camera layout"); return RT1W_ERR_DEVICE; }
+    return lane_run(c, (uint64_t)p->width * p->height, "temporal moments", stats, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_temporal_moments_launch(p->width, p->height, p->flags, p->max_history, p->depth_tol, p->normal_min, d_cur_frame, d_cur_aov,
+                                                     cur_cam, d_prev_hist, d_prev_m2, d_prev_len, d_prev_aov, prev_cam, d_hist, d_m2, d_len, d_frame_out,
+                                                     stream, launch);
+    });
+}
+int temporal_variance_common(rt1w_context* c, uint32_t w, uint32_t h, const double* d_hist, const double* d_m2, const double* d_len, const double* d_aov,
+                             double* d_var, rt1w_stats* stats) {
+    return lane_run(c, (uint64_t)w * h, "temporal variance", stats, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_temporal_variance_launch(w, h, d_hist, d_m2, d_len, d_aov, d_var, stream, launch);
+    });
+}
+/* the two rt1w_temporal_moments entries.  Host form: the ten buffers one behind the other in the framebuffer */
+int temporal_moments(rt1w_context* c, const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
+                     const double* prev_hist, const double* prev_m2, const double* prev_len, const double* prev_aov, const rt1w_camera* prev_cam,
+                     double* hist, double* m2, double* len, double* frame_out, bool host, rt1w_stats* stats) {
+    const int rc = temporal_validate(c, p);
+    if (rc < 0) return rc;
+    if (!cur_frame || !cur_aov || !prev_hist || !prev_m2 || !prev_len || !prev_aov || !hist || !m2 || !len || !frame_out) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    if (!cur_cam || !prev_cam) { set_error("null camera"); return RT1W_ERR_INVALID; }
+    const size_t npix = (size_t)p->width * p->height;
+    Staged s[] = {{cur_frame, nullptr, npix * 3, FRAMEBUFFER, "temporal: frame copy", nullptr},
+                  {cur_aov, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, "temporal: feature buffer copy", nullptr},
+                  {prev_hist, nullptr, npix * 3, FRAMEBUFFER, "temporal: history copy", nullptr},
+                  {prev_m2, nullptr, npix, FRAMEBUFFER, "temporal: second moment copy", nullptr},
+                  {prev_len, nullptr, npix, FRAMEBUFFER, "temporal: history length copy", nullptr},
+                  {prev_aov, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, "temporal: previous feature buffer copy", nullptr},
+                  {nullptr, hist, npix * 3, FRAMEBUFFER, nullptr, "temporal: history result copy"},
+                  {nullptr, m2, npix, FRAMEBUFFER, nullptr, "temporal: second moment result copy"},
+                  {nullptr, len, npix, FRAMEBUFFER, nullptr, "temporal: history length result copy"},
+                  {nullptr, frame_out, npix * 3, FRAMEBUFFER, nullptr, "temporal: frame result copy"}};
+    for (size_t o = 6; o < 10; ++o) /* the four outputs */
+        if (staged_output_overlaps(s, o)) { set_error("temporal: hist, m2, len and frame_out must not overlap each other or an input"); return RT1W_ERR_INVALID; }
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
+        return temporal_moments_common(c, p, s[0].d_in, s[1].d_in, cur_cam, s[2].d_in, s[3].d_in, s[4].d_in, s[5].d_in, prev_cam, s[6].d_out, s[7].d_out,
+                                       s[8].d_out, s[9].d_out, st);
+    });
+}
+/* the two rt1w_temporal_variance entries.  Host form: the five buffers one behind the other in the framebuffer */
+int temporal_variance(rt1w_context* c, uint32_t w, uint32_t h, const double* hist, const double* m2, const double* len, const double* aov, double* var,
+                      bool host, rt1w_stats* stats) {
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (w == 0 || h == 0 || w > 0x40000000u || h > 0x40000000u) { set_error("temporal variance: width and height must be 1 .. 2^30"); return RT1W_ERR_INVALID; }
+    if (!hist || !m2 || !len || !aov || !var) { set_error("null buffer"); return RT1W_ERR_INVALID; }
+    const size_t npix = (size_t)w * h;
+    Staged s[] = {{hist, nullptr, npix * 3, FRAMEBUFFER, "temporal variance: history copy", nullptr},
+                  {m2, nullptr, npix, FRAMEBUFFER, "temporal variance: second moment copy", nullptr},
+                  {len, nullptr, npix, FRAMEBUFFER, "temporal variance: history length copy", nullptr},
+                  {aov, nullptr, npix * RT1W_AOV_CHANNELS, FRAMEBUFFER, "temporal variance: feature buffer copy", nullptr},
+                  {nullptr, var, npix, FRAMEBUFFER, nullptr, "temporal variance: result copy"}};
+    if (staged_output_overlaps(s, 4)) { set_error("temporal variance: var must not overlap an input"); return RT1W_ERR_INVALID; }
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) { return temporal_variance_common(c, w, h, s[0].d_in, s[1].d_in, s[2].d_in, s[3].d_in, s[4].d_out, st); });
+}
+/* rt1w_render_temporal_var: frame_out, the frame and var in the framebuffer; history, second moment, length and the feature buffers in the
+ * context's two state sets of this entry */
+int render_temporal_var(rt1w_context* c, const rt1w_render_params* p, const rt1w_temporal_params* t, const rt1w_denoise_params* d, double sigma_variance,
+                        double* out_rgb, rt1w_stats* stats) {
+    /* what the parameters alone decide, before the context is looked at */
+    int rc = sigma_variance_validate(sigma_variance);
+    if (rc < 0) return rc;
+    if (((t ? t->flags : 0u) ^ (d ? d->flags : 0u)) & RT1W_DENOISE_KEEP_ALBEDO) {
+        set_error("rt1w_render_temporal_var: the temporal and the denoise parameters must agree on RT1W_DENOISE_KEEP_ALBEDO (the variance is in the units of the history's demodulation)");
+        return RT1W_ERR_INVALID;
+    }
+    if ((rc = denoised_render_validate(c, p, out_rgb)) < 0) return rc;
+    if (p->x0 != 0u || p->y0 != 0u || p->tile_w != p->width || p->tile_h != p->height) {
+        set_error("rt1w_render_temporal_var takes the whole image (the reprojection works in image coordinates)"); return RT1W_ERR_INVALID;
+    }
+    rt1w_temporal_params tp;
+    memset(&tp, 0, sizeof tp);
+    if (t) tp = *t;
+    if ((tp.width && tp.width != p->width) || (tp.height && tp.height != p->height)) { set_error("temporal: width / height must be 0 or the image's"); return RT1W_ERR_INVALID; }
+    tp.width = p->width; tp.height = p->height;
+    if ((rc = temporal_validate(c, &tp)) < 0) return rc;
+    rt1w_denoise_params dp;
+    if ((rc = denoised_filter_params(c, d, p->width, p->height, &dp)) < 0) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    Staged s[] = {{nullptr, out_rgb, npix * 3, FRAMEBUFFER, nullptr, "temporal frame copy"}, {nullptr, nullptr, npix * 3, FRAMEBUFFER, nullptr, nullptr},
+                  {nullptr, nullptr, npix, FRAMEBUFFER, nullptr, nullptr}};
+    return staged_entry(c, true, s, stats, [&](rt1w_stats* st) {
+        double *d_out = s[0].d_out, *d_frame = s[1].d_out, *d_var = s[2].d_out;
+        const size_t set_bytes = npix * (3 + 1 + 1 + RT1W_AOV_CHANNELS) * sizeof(double);
+        int r;
+        if (c->tv_w != p->width || c->tv_h != p->height) c->tv_valid = false;
+        for (int k = 0; k < 2; ++k)
+            if ((r = dev_grow(&c->tv_buf[k], &c->tv_bytes[k], set_bytes, "hipMalloc(temporal variance state)")) < 0) { c->tv_valid = false; return r; }
+        c->tv_w = p->width; c->tv_h = p->height;
+        const int prev = c->tv_prev, cur = 1 - prev;
+        double *ph = (double*)c->tv_buf[prev], *pm = ph + npix * 3, *pl = pm + npix, *pa = pl + npix;
+        double *ch = (double*)c->tv_buf[cur], *cm = ch + npix * 3, *cl = cm + npix, *ca = cl + npix;
+        if (!c->tv_valid) { /* no history: prev_len = 0 everywhere (all of the set is zeroed), prev_cam = cur_cam */
+            if (!hip_ok(hipMemsetAsync(ph, 0, set_bytes, c->lane[0].stream), "temporal variance state reset")) return RT1W_ERR_DEVICE;
+            c->tv_cam = c->view.camera;
+        }
+        memset(st, 0, sizeof *st);
+        if ((r = render_common(c, p, d_frame, st)) < 0) return r;
+        rt1w_render_params ap = *p; /* the feature buffers of the same image, samples and seed, by the scene's own variant */
+        ap.flags = 0u;
+        rt1w_stats sa, sm, sv, sd;
+        if ((r = render_aov_common(c, &ap, nullptr, ca, &sa)) < 0) return r;
+        c->tv_valid = false; /* a failure from here on leaves no history behind */
+        if ((r = temporal_moments_common(c, &tp, d_frame, ca, &c->view.camera, ph, pm, pl, pa, &c->tv_cam, ch, cm, cl, d_out, &sm)) < 0) return r;
+        c->tv_prev = cur; c->tv_cam = c->view.camera; c->tv_valid = true;
+        if ((r = temporal_variance_common(c, p->width, p->height, ch, cm, cl, ca, d_var, &sv)) < 0) return r;
+        if ((r = denoise_var_common(c, &dp, sigma_variance, d_out, ca, d_var, d_out, &sd)) < 0) return r;
+        st->kernel_ms = st->kernel_ms + sa.kernel_ms + sm.kernel_ms + sv.kernel_ms + sd.kernel_ms;
+        st->grid = sd.grid; st->block = sd.block;
+        return RT1W_OK;
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -960,7 +1079,33 @@ int rt1w_render_temporal(rt1w_context* c, const rt1w_render_params* p, const rt1
 int rt1w_temporal_reset(rt1w_context* c) {
     if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
     c->tm_valid = false;
+    c->tv_valid = false;
     return RT1W_OK;
+}
+int rt1w_temporal_moments(rt1w_context* c, const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
+                          const double* prev_hist, const double* prev_m2, const double* prev_len, const double* prev_aov, const rt1w_camera* prev_cam,
+                          double* hist, double* m2, double* len, double* frame_out, rt1w_stats* stats) {
+    return temporal_moments(c, p, cur_frame, cur_aov, cur_cam, prev_hist, prev_m2, prev_len, prev_aov, prev_cam, hist, m2, len, frame_out, true, stats);
+}
+int rt1w_temporal_moments_device(rt1w_context* c, const rt1w_temporal_params* p, const void* d_cur_frame, const void* d_cur_aov, const rt1w_camera* cur_cam,
+                                 const void* d_prev_hist, const void* d_prev_m2, const void* d_prev_len, const void* d_prev_aov,
+                                 const rt1w_camera* prev_cam, void* d_hist, void* d_m2, void* d_len, void* d_frame_out, rt1w_stats* stats) {
+    return temporal_moments(c, p, (const double*)d_cur_frame, (const double*)d_cur_aov, cur_cam, (const double*)d_prev_hist, (const double*)d_prev_m2,
+                            (const double*)d_prev_len, (const double*)d_prev_aov, prev_cam, (double*)d_hist, (double*)d_m2, (double*)d_len,
+                            (double*)d_frame_out, false, stats);
+}
+int rt1w_temporal_variance(rt1w_context* c, uint32_t width, uint32_t height, const double* hist, const double* m2, const double* len, const double* aov,
+                           double* var, rt1w_stats* stats) {
+    return temporal_variance(c, width, height, hist, m2, len, aov, var, true, stats);
+}
+int rt1w_temporal_variance_device(rt1w_context* c, uint32_t width, uint32_t height, const void* d_hist, const void* d_m2, const void* d_len,
+                                  const void* d_aov, void* d_var, rt1w_stats* stats) {
+    return temporal_variance(c, width, height, (const double*)d_hist, (const double*)d_m2, (const double*)d_len, (const double*)d_aov, (double*)d_var, false,
+                             stats);
+}
+int rt1w_render_temporal_var(rt1w_context* c, const rt1w_render_params* p, const rt1w_temporal_params* t, const rt1w_denoise_params* d,
+                             double sigma_variance, double* out_rgb, rt1w_stats* stats) {
+    return render_temporal_var(c, p, t, d, sigma_variance, out_rgb, stats);
 }
 int rt1w_render_aov(rt1w_context* c, const rt1w_render_params* p, double* out_aov, rt1w_stats* stats) { return render_aov(c, p, nullptr, out_aov, true, stats); }
 int rt1w_render_aov_device(rt1w_context* c, const rt1w_render_params* p, void* d_out_aov, rt1w_stats* stats) { return render_aov(c, p, nullptr, d_out_aov, false, stats); }

@@ -1,4 +1,4 @@
-/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip and temporal.hip, declared once.
+/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip, temporal.hip and temporal_var.hip, declared once.
  * The functions are extern "C": nothing in their names says what they take, so caller and definition both include this header and the
  * compiler holds each definition to the declaration the caller sees.  Private (librt1w.map exports none of them).
  * Every kernel is reached through a typed *_launch: no kernel handle leaves its unit, and no argument array is built by hand.  The
@@ -75,6 +75,16 @@ int rt1w_internal_temporal_launch(uint32_t w, uint32_t h, uint32_t flags, uint32
                                   const double* prev_aov, const void* prev_cam, double* hist, double* len, double* frame_out, hipStream_t stream,
                                   unsigned launch[2]);
 unsigned rt1w_internal_temporal_sizeof(void);
+/* temporal_var.hip: that launch with the second-moment channel beside the history (rt1w_temporal_moments), and the pass that turns
+ * history, second moment and length into the variance buffer of rt1w_denoise_var (rt1w_temporal_variance); the cameras as above,
+ * rt1w_internal_temporal_var_sizeof() bytes each */
+int rt1w_internal_temporal_moments_launch(uint32_t w, uint32_t h, uint32_t flags, uint32_t max_history, double depth_tol, double normal_min,
+                                          const double* cur_frame, const double* cur_aov, const void* cur_cam, const double* prev_hist,
+                                          const double* prev_m2, const double* prev_len, const double* prev_aov, const void* prev_cam, double* hist,
+                                          double* m2, double* len, double* frame_out, hipStream_t stream, unsigned launch[2]);
+int rt1w_internal_temporal_variance_launch(uint32_t w, uint32_t h, const double* hist, const double* m2, const double* len, const double* aov,
+                                           double* var, hipStream_t stream, unsigned launch[2]);
+unsigned rt1w_internal_temporal_var_sizeof(void);
 }
 
 #endif

@@ -1,7 +1,7 @@
 /* rt_temporal.h -- temporal accumulation (rt1w_temporal_accumulate, include/rt1w.h has the definition): the current frame's pixel is
  * reprojected through its first-hit depth into the previous frame, whose demodulated history is gathered with four bilinear taps that
- * pass a depth and a normal test, and blended with the current value.  Compiled by the kernel (temporal.hip) and by the CPU twin of the
- * diagnostics library (denoise_host.cpp), from this one text.
+ * pass a depth and a normal test, and blended with the current value.  Compiled by the kernels (temporal.hip, and temporal_var.hip for
+ * rt1w_temporal_moments) and by the CPU twin of the diagnostics library (denoise_host.cpp), from this one text.
  *
  * Everything is + - * /, rt_sqrt, comparisons, selects and integer <-> double conversions in one fixed order (built with
  * -ffp-contract=off like every build of the core): the two builds give the same bits.  No libm, no intrinsic.  Nothing here is reached
@@ -46,17 +46,20 @@ RT_HD void rt_tm_prepare(uint32_t keep_albedo, const double* frame, const double
     rt_dn_prepare_pixel(D, frame, aov, c, g);
 }
 
-/* pixel (x, y) of a w x h image: hist[3], len[1] and frame_out[3] of that pixel; rec: RT_TM_REC doubles, or null */
+/* pixel (x, y) of a w x h image: hist[3], len[1] and frame_out[3] of that pixel; rec: RT_TM_REC doubles, or null.
+ * prev_m2, m2: null for rt1w_temporal_accumulate (its kernel passes null constants: the branches fold away).  For rt1w_temporal_moments
+ * the whole previous image of second moments and this pixel's m2[1]: the running mean of the squared demodulated luminance, gathered
+ * over the very taps of the history, read only where a tap is valid */
 RT_HD void rt_tm_pixel(const RtTmParams& P, const RtCamera& cc, const RtCamera& pc, const double* cur_frame, const double* cur_aov,
-                       const double* prev_hist, const double* prev_len, const double* prev_aov, uint32_t x, uint32_t y, double* hist,
-                       double* len, double* frame_out, double* rec) {
+                       const double* prev_hist, const double* prev_len, const double* prev_aov, const double* prev_m2, uint32_t x, uint32_t y,
+                       double* hist, double* len, double* frame_out, double* m2, double* rec) {
     const unsigned long long i = (unsigned long long)y * P.w + x;
     RtDnCol c;
     RtDnGuide g;
     rt_tm_prepare(P.keep_albedo, cur_frame + i * 3u, cur_aov + i * 8u, c, g);
     /* the divisors of main.rs:968-969; an image of one column or row (which no render makes) has its centre at 1/2 */
     const double w1 = (double)(P.w > 1u ? P.w - 1u : 1u), h1 = (double)(P.h > 1u ? P.h - 1u : 1u);
-    double hr = 0.0, hg = 0.0, hb = 0.0, hn = 0.0, sw = 0.0, fx = 0.0, fy = 0.0;
+    double hr = 0.0, hg = 0.0, hb = 0.0, hn = 0.0, hm = 0.0, sw = 0.0, fx = 0.0, fy = 0.0;
     double tw[4] = {0.0, 0.0, 0.0, 0.0};
     bool history = false;
     if (g.v > 0.0 && rt_dn_finite(g.z)) { /* a hit with a depth: NaN coverage is no hit */
@@ -96,6 +99,7 @@ RT_HD void rt_tm_pixel(const RtTmParams& P, const RtCamera& cc, const RtCamera& 
                     const double w = ((k4 & 1) ? wx : 1.0 - wx) * ((k4 >> 1) ? wy : 1.0 - wy);
                     tw[k4] = w;
                     hr += w * cq.r; hg += w * cq.g; hb += w * cq.b; hn += w * n; sw += w;
+                    if (prev_m2) hm += w * prev_m2[j];
                 }
                 history = sw > 0.0;
             }
@@ -110,6 +114,9 @@ RT_HD void rt_tm_pixel(const RtTmParams& P, const RtCamera& cc, const RtCamera& 
         o1 = (Nc * (hg / sw) + c.g) / (Nc + 1.0);
         o2 = (Nc * (hb / sw) + c.b) / (Nc + 1.0);
         on = Nc + 1.0;
+        if (m2) m2[0] = (Nc * (hm / sw) + c.l * c.l) / (Nc + 1.0);
+    } else if (m2) {
+        m2[0] = c.l * c.l;
     }
     hist[0] = o0; hist[1] = o1; hist[2] = o2;
     len[0] = on;

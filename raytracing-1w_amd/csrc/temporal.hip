@@ -28,7 +28,7 @@ __global__ __launch_bounds__(RT_PX_WG) void rt_tm_accumulate_kernel(RtTmParams P
     rt_px_lane_pixel(P.w, x, y);
     if (x >= P.w || y >= P.h) return;
     const unsigned long long i = (unsigned long long)y * P.w + x;
-    rt_tm_pixel(P, cc, pc, cur_frame, cur_aov, prev_hist, prev_len, prev_aov, x, y, hist + i * 3u, len + i, frame_out + i * 3u, nullptr);
+    rt_tm_pixel(P, cc, pc, cur_frame, cur_aov, prev_hist, prev_len, prev_aov, nullptr, x, y, hist + i * 3u, len + i, frame_out + i * 3u, nullptr, nullptr);
 }
 } // namespace rttm
 

@@ -87,6 +87,13 @@ int rt1w_lab_guides_resolve_host(uint32_t width, uint32_t height, const double* 
 int rt1w_lab_temporal_host(const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
                            const double* prev_hist, const double* prev_len, const double* prev_aov, const rt1w_camera* prev_cam, double* hist,
                            double* len, double* frame_out, double* rec /* [h][w][8], may be null */);
+/* CPU twins of rt1w_temporal_moments and rt1w_temporal_variance (denoise_host.cpp: rt_temporal.h and rt_temporal_var.h built for the host),
+ * no GPU; RT1W_ERR_INVALID as the device entries.  rec as above */
+int rt1w_lab_temporal_moments_host(const rt1w_temporal_params* p, const double* cur_frame, const double* cur_aov, const rt1w_camera* cur_cam,
+                                   const double* prev_hist, const double* prev_m2, const double* prev_len, const double* prev_aov,
+                                   const rt1w_camera* prev_cam, double* hist, double* m2, double* len, double* frame_out,
+                                   double* rec /* [h][w][8], may be null */);
+int rt1w_lab_temporal_variance_host(uint32_t width, uint32_t height, const double* hist, const double* m2, const double* len, const double* aov, double* var);
 /* The camera of a COMMITTED scene as the twins and rt1w_scene_copy_flat see it (aov_host.cpp).  set: what rt1w_context_set_camera does to
  * a context's view, done to the scene's own record through the same function (csrc/scene.h: camera_make) with the same refusals -- the
  * twins, which build their view from the scene, then render the camera a live context would.  A diagnostic: it breaks the rule that a
