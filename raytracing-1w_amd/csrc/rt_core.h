@@ -1748,6 +1748,13 @@ RT_HD double rt_sphere_light_pdf_value(const RtNode& l, RtV3 o, RtV3 v) {
 #else
 #define RT_LIGHT_CONE_ON ((RT_LIGHT_CONE) != 0)
 #endif
+/* Where the cone is (`cone`), the cosine lobe and the sphere lobe build their direction alike: a square root, and a frame applied to
+ * (cos * q, sin * q, z).  A wave that holds lanes of both -- nearly every Lambertian one -- ran the two copies one after the other;
+ * with RT_LOBE_SHARED each lobe leaves its frame, its z and its radicand (r2, or 1 - z * z), and one sqrt and one rt_onb_local serve
+ * both: per lane the operations and operands of before.  RT1W_JIT_EXTRA_OPTS=-DRT_LOBE_SHARED=0 is the text with the two copies. */
+#ifndef RT_LOBE_SHARED
+#define RT_LOBE_SHARED 1
+#endif
 struct RtSphereCone { RtV3 direction; double distance_squared, cos_theta_max; };
 struct RtNoCone {};
 RT_HD RtSphereCone rt_sphere_cone(const RtNode& l, RtV3 o) {
@@ -1756,6 +1763,22 @@ RT_HD RtSphereCone rt_sphere_cone(const RtNode& l, RtV3 o) {
     k.distance_squared = rt_mag2(k.direction);
     k.cos_theta_max = rt_sqrt(RT_R(1.0) - l.d[3] * l.d[3] / k.distance_squared);
     return k;
+}
+/* RT_LOBE_SHARED: the scattered direction of a lane that drew the one sphere light's lobe (`sphere`) or the cosine lobe about `uvw`,
+ * from r2 and the sine and cosine of 2 pi r1.  Each lobe hands over its frame, its z and its radicand; the square root and the
+ * frame's product stand once.  The sphere lobe: sphere.rs:92-99 -> math.rs:51-65; the cosine lobe: math.rs:39-49. */
+RT_HD RtV3 rt_lobe_dir_shared(bool sphere, const RtOnb& uvw, const RtSphereCone& cone, double r2, double sn, double cs) {
+    RtOnb fr = uvw;
+    double z, rad = r2;
+    if (sphere) {
+        fr = rt_onb_from_w(cone.direction);
+        z = RT_R(1.0) + r2 * (cone.cos_theta_max - RT_R(1.0));
+        rad = RT_R(1.0) - z * z;
+    } else {
+        z = rt_sqrt(RT_R(1.0) - r2);
+    }
+    const double q = rt_sqrt(rad);
+    return rt_onb_local(fr, rt_v3(cs * q, sn * q, z));
 }
 /* rt_sphere_light_pdf_value with the cone of (l, o) at hand */
 RT_HD double rt_sphere_light_pdf_value(const RtNode& l, const RtSphereCone& k, RtV3 o, RtV3 v) {
@@ -1894,11 +1917,24 @@ RT_HD RtV3 rt_refract(RtV3 uv, RtV3 n, double etai_over_etat) {               /*
     RtV3 r_out_parallel = -rt_sqrt(rt_abs(RT_R(1.0) - rt_mag2(r_out_perp))) * n;
     return r_out_perp + r_out_parallel;
 }
-RT_HD double rt_reflectance(double cosine, double ref_idx) {                  /* material.rs:121-125 */
-    double r0 = (RT_R(1.0) - ref_idx) / (RT_R(1.0) + ref_idx);
-    r0 = r0 * r0;
+RT_HD double rt_reflectance_r0(double cosine, double r0) {                    /* material.rs:124: the statement behind r0 */
     return r0 + (RT_R(1.0) - r0) * rt_pow5(RT_R(1.0) - cosine);
 }
+RT_HD double rt_reflectance(double cosine, double ref_idx) {                  /* material.rs:121-125 */
+    return rt_reflectance_r0(cosine, rt_schlick_r0(ref_idx));
+}
+/* A Dielectric's refraction ratios and their r0 are the material's alone: the record carries them (rt_flat.h: rt_material_derive) and a
+ * bounce selects by the face instead of dividing twice per lane.  RT1W_JIT_EXTRA_OPTS=-DRT_MAT_DERIVED=0: the text that computes them.
+ * f64 records only (the f32 build's records are conversions, and the conversion of a quotient is not the quotient of conversions). */
+#ifndef RT_MAT_DERIVED
+#define RT_MAT_DERIVED 1
+#endif
+#undef RT_MAT_DERIVED_ON /* (a unit may take this header twice: f64 records, then the f32 build) */
+#if defined(RT_F32)
+#define RT_MAT_DERIVED_ON false
+#else
+#define RT_MAT_DERIVED_ON ((RT_MAT_DERIVED) != 0)
+#endif
 
 /* --------------------------------------------------------------- camera -- */
 
@@ -2144,6 +2180,45 @@ struct RtHitShape<Topo, typename RtVoid<decltype(Topo::wrap)>::type> {
     }
 };
 
+/* A sphere's outward normal, (p - c) / r, is three divisions by one divisor: with the divisor prepared once (rt1w_num.h: rt_div_prep)
+ * the three quotients are rt_div_q's, 5 + 9 instructions for 33.  The guards are the header's: the divisor's range, and every quotient's
+ * as one that is used (a zero or tiny component would take div_fixup's sign and div_scale's scaling, which rt_div_q does not
+ * reproduce).  rt_div_q3 is the three quotients and `bad`, whether a guard failed; a wave with a failing lane divides with `/`
+ * (rt_sphere_normal; diagnostic builds charge that to bucket 15).  The static hit record's Sphere case, f64 device code only.
+ * NOT SHIPPED: exact (tests/test_glass_terms.py, test_glass_terms_gpu.py), but on the Cornell kernel it gains 0.2-0.4 %, one parent
+ * spread where the bar is four, alone and on top of the two other parts (docs/LAB_NOTES.md section 5; profiles/glass_terms_bench.json):
+ * the guards cost eight compares of the nineteen instructions saved, and the fallback's text is 24 more static VALU.  The default is the
+ * text with the three divisions; RT1W_JIT_EXTRA_OPTS=-DRT_NORMAL_SHARED=1 builds the part. */
+#ifndef RT_NORMAL_SHARED
+#define RT_NORMAL_SHARED 0
+#endif
+#undef RT_NORMAL_SHARED_ON /* (a unit may take this header twice: f64 records, then the f32 build) */
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_F32)
+#define RT_NORMAL_SHARED_ON ((RT_NORMAL_SHARED) != 0)
+#else
+#define RT_NORMAL_SHARED_ON 0
+#endif
+#if !defined(RT_F32)
+RT_HD RtV3 rt_div_q3(RtV3 n, double d, double y, bool& bad) {
+    const RtV3 q = rt_v3(rt_div_q(n.x, d, y), rt_div_q(n.y, d, y), rt_div_q(n.z, d, y));
+    bad = !rt_div_d_ok(d) | rt_div_q_bad(q.x, true) | rt_div_q_bad(q.y, true) | rt_div_q_bad(q.z, true);
+    return q;
+}
+#endif
+RT_HD RtV3 rt_sphere_normal(RtV3 n, double r) {
+#if RT_NORMAL_SHARED_ON
+    bool bad;
+    RtV3 on = rt_div_q3(n, r, rt_div_prep(r), bad);
+    if (RT_WAVE_ANY(bad)) {
+        on = n / r;
+        RT_STAMP(15);
+    }
+    return on;
+#else
+    return n / r;
+#endif
+}
+
 /* rt_leaf_record for a lane whose leaf is in GROUP: the same statements on the same operands; which of them a lane runs is decided by
  * set tests, and a record is read only where a value is needed -- a sphere's centre and radius (one scalar load where GROUP has one
  * sphere), a moving sphere's, a rect's bounds where its texture reads (u, v) */
@@ -2167,10 +2242,10 @@ RT_HD void rt_leaf_record_static(const RtSceneView& sc, RtRayOD r, double time, 
         } else if constexpr (HS::count(Cfg::msphere ? SPH : SPH | MSPH, RT_HF_NONE, 0u, GROUP) == 1u) {
             constexpr uint32_t J = HS::nth(Cfg::msphere ? SPH : SPH | MSPH, RT_HF_NONE, 0u, GROUP, GROUP, false, 0u);
             const RtNodeHot nd = RtGlobalNodes{sc.nodes}.hot(J);
-            on = (h.p - rt_v3(nd.d[0], nd.d[1], nd.d[2])) / nd.d[3];
+            on = rt_sphere_normal(h.p - rt_v3(nd.d[0], nd.d[1], nd.d[2]), nd.d[3]);
         } else {
             const RtNode& nd = sc.nodes[prim];
-            on = (h.p - rt_v3(nd.d[0], nd.d[1], nd.d[2])) / nd.d[3];
+            on = rt_sphere_normal(h.p - rt_v3(nd.d[0], nd.d[1], nd.d[2]), nd.d[3]);
         }
         if (Cfg::tex && want_uv) rt_sphere_uv(on, h.u, h.v);
     } else {
@@ -2359,7 +2434,9 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr, Sp
                 double phi = RT_R(2.0) * RT_R(RT_PI) * r1;
                 double sn, cs;
                 rt_sincos(phi, sn, cs);
-                if (LS::may_sphere && lk == RT_SPHERE) {
+                if constexpr (LS::cone && (RT_LOBE_SHARED) != 0) {
+                    dir = rt_lobe_dir_shared(lk == RT_SPHERE, uvw, cone, r2, sn, cs);
+                } else if (LS::may_sphere && lk == RT_SPHERE) {
                     if constexpr (LS::cone) {
                         RtOnb lw = rt_onb_from_w(cone.direction);
                         double z = RT_R(1.0) + r2 * (cone.cos_theta_max - RT_R(1.0));
@@ -2413,13 +2490,15 @@ RT_HD void rt_path_shade(const RtSceneView& sc, RtPath& p, const RtTrace& tr, Sp
         p.ray.o = h.p; p.ray.d = dir;
     } else if (mk == RT_MAT_DIELECTRIC) {
         /* Dielectric::scatter material.rs:133-160 */
-        double refraction_ratio = h.front ? RT_R(1.0) / m.d[0] : m.d[0];
+        double refraction_ratio, r0 = RT_R(0.0);
+        if constexpr (RT_MAT_DERIVED_ON) { refraction_ratio = h.front ? m.d[1] : m.d[0]; r0 = h.front ? m.d[2] : m.d[3]; }
+        else refraction_ratio = h.front ? RT_R(1.0) / m.d[0] : m.d[0];
         RtV3 unit_direction = rt_normalize(p.ray.d);
         double cos_theta = rt_min(rt_dot(-unit_direction, h.n), RT_R(1.0));
         double sin_theta = rt_sqrt(RT_R(1.0) - cos_theta * cos_theta);
         bool cannot_refract = refraction_ratio * sin_theta > RT_R(1.0);
         RtV3 dir;
-        if (cannot_refract || rt_reflectance(cos_theta, refraction_ratio) > rt_gen_f64(p.rng)) /* checked draw: rarely-run site */
+        if (cannot_refract || (RT_MAT_DERIVED_ON ? rt_reflectance_r0(cos_theta, r0) : rt_reflectance(cos_theta, refraction_ratio)) > rt_gen_f64(p.rng)) /* checked draw: rarely-run site */
             dir = rt_reflect(unit_direction, h.n);
         else
             dir = rt_refract(unit_direction, h.n, refraction_ratio);

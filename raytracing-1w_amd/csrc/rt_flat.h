@@ -69,7 +69,7 @@ enum {
     RT_MAT_NULL = 0,         /* impl Material for ()      src/material.rs:68 */
     RT_MAT_LAMBERTIAN = 1,   /* src/material.rs:70-92   tex */
     RT_MAT_METAL = 2,        /* src/material.rs:98-112  d[0..2]=albedo d[3]=fuzz */
-    RT_MAT_DIELECTRIC = 3,   /* src/material.rs:132-161 d[0]=ir */
+    RT_MAT_DIELECTRIC = 3,   /* src/material.rs:132-161 d[0]=ir; d[1..3] what a bounce derives from ir alone (rt_material_derive) */
     RT_MAT_DIFFUSE_LIGHT = 4,/* src/material.rs:163-182 tex */
     RT_MAT_ISOTROPIC = 5     /* src/constant_medium.rs:31-51 tex */
 };
@@ -86,6 +86,22 @@ struct RtMaterial {
     uint32_t tex;
     uint32_t pad0, pad1;
 }; /* 48 bytes */
+/* Schlick's r0 of a refraction ratio: the first two statements of reflectance (material.rs:121-125; rt_core.h: rt_reflectance) */
+RT_HD double rt_schlick_r0(double ref_idx) {
+    double r0 = (RT_R(1.0) - ref_idx) / (RT_R(1.0) + ref_idx);
+    return r0 * r0;
+}
+/* What a Dielectric bounce computes from `ir` alone, written where the record is (scene.cpp: add_material, the one writer of material
+ * records): d[1] = 1 / ir, the refraction ratio on a front face; d[2], d[3] = r0 of the front face's ratio (d[1]) and of the back
+ * face's (ir).  Division and multiplication are correctly rounded on the host and on the device and neither side contracts, so these
+ * are the bits the kernel would compute (tests/test_glass_terms.py).  The f64 kernels read them (rt_core.h: RT_MAT_DERIVED); the
+ * f32 build converts records to float and float(1 / ir) is not 1.0f / float(ir), so it computes from d[0] as ever. */
+inline void rt_material_derive(RtMaterial& m) {
+    if ((m.kind & 0xFFu) != RT_MAT_DIELECTRIC) return;
+    m.d[1] = RT_R(1.0) / m.d[0];
+    m.d[2] = rt_schlick_r0(m.d[1]);
+    m.d[3] = rt_schlick_r0(m.d[0]);
+}
 
 /* texture kinds: every `impl Texture` used by a scene */
 enum {

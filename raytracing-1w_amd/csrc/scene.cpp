@@ -442,6 +442,7 @@ static int add_material(rt1w_scene* s, uint32_t kind, uint32_t tex, double d0, d
     RtMaterial m;
     std::memset(&m, 0, sizeof m);
     m.kind = kind; m.tex = tex; m.d[0] = d0; m.d[1] = d1; m.d[2] = d2; m.d[3] = d3;
+    rt_material_derive(m); /* a Dielectric's d[1..3], from d[0]; the only other statement that writes a record (commit, below) touches textured kinds alone */
     s->materials.push_back(m);
     return (int)s->materials.size() - 1;
 }
