@@ -12,6 +12,12 @@ The package name has a hyphen (mandated layout), so import it with::
 
 Method names follow the reference's constructors (src/sphere.rs, src/aarect.rs,
 src/material.rs, src/texture.rs, src/bvh.rs, src/camera.rs of hatoo/raytracing-1w).
+
+How an entry is bound: its prototype stands once, in the ``_sig`` table (librt1w.so) or in ``_LAB_SIGS`` (the CPU twins of
+librt1w_lab.so); ``_call`` / ``_call_lab`` turn arrays and structs into pointers, make the call and check its code; and an entry
+that has a twin has one ``_*_prep`` function that normalises its inputs, checks their shapes and allocates its outputs.
+``Context.X`` and ``X_host`` are that preparation handed to ``Context._entry`` or ``_twin``, ``Context.X_device`` is the same
+argument list with the caller's addresses in it.
 """
 import ctypes as C
 import os
@@ -29,16 +35,6 @@ if not os.path.exists(LIB_PATH):
 
 _lib = C.CDLL(LIB_PATH)
 _lab = None
-
-
-def load_lab():
-    """Load the diagnostics library librt1w_lab.so (the trace-only harness and the wavefront form: measured opt-ins that are not in the
-    product library).  Loading it registers the wavefront form with librt1w.so; RT1W_WAVEFRONT renders need it."""
-    global _lab
-    if _lab is None:
-        _lab = C.CDLL(os.path.join(os.path.dirname(LIB_PATH), "librt1w_lab.so"))
-    return _lab
-
 
 OK = 0
 ERR_INVALID, ERR_UNSUPPORTED, ERR_DEVICE, ERR_NOMEM, ERR_STATE, ERR_CANCELLED = -1, -2, -3, -4, -5, -6
@@ -59,6 +55,11 @@ TILES_SPECIALISED = 0x40000  # tile entries and the adaptive entries' rounds: th
 AOV_CHANNELS = 8  # rt1w_render_aov: albedo rgb, normal xyz, depth, coverage per pixel
 DENOISE_KEEP_ALBEDO = 1  # rt1w_denoise: no albedo demodulation
 ADAPTIVE_ONE_LAUNCH = 0x100  # rt1w_adaptive_params.flags: every round is one rt1w_render_tiles launch and one rt1w_accum_merge_tiles
+
+# Context._params: the keywords that are one bit of rt1w_render_params.flags each
+_RENDER_FLAGS = {"out_sum": OUT_SUM, "out_frame": OUT_FRAME, "reference_stream": RNG_REFERENCE, "unsorted": UNSORTED, "lds_nodes": LDS_NODES,
+                 "generic": GENERIC, "wavefront": WAVEFRONT, "classic_walk": CLASSIC_WALK, "no_node_cache": NO_NODE_CACHE,
+                 "probe_coherent": PROBE_COHERENT}
 
 
 class Rt1wError(RuntimeError):
@@ -168,8 +169,12 @@ class DenoiseParams(C.Structure):
                 ("sigma_colour", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
 
 
+def _keep(keep_albedo):
+    return DENOISE_KEEP_ALBEDO if keep_albedo else 0
+
+
 def _denoise_params(width, height, iterations=0, keep_albedo=False, sigma_colour=0.0, sigma_normal=0.0, sigma_depth=0.0, flags=0):
-    return DenoiseParams(width, height, iterations, flags | (DENOISE_KEEP_ALBEDO if keep_albedo else 0), sigma_colour, sigma_normal, sigma_depth)
+    return DenoiseParams(width, height, iterations, flags | _keep(keep_albedo), sigma_colour, sigma_normal, sigma_depth)
 
 
 _sig("rt1w_denoise", C.c_int, _P, C.POINTER(DenoiseParams), _P, _P, _P, C.POINTER(Stats))
@@ -193,7 +198,7 @@ class AdaptiveParams(C.Structure):
 def adaptive_params(tile=0, batch_spp=0, pilot_batches=0, budget_spp=0, max_spp=0, target_error=0.0, round_share=0.0, keep_albedo=False, flags=0,
                     size=None, one_launch=False):
     return AdaptiveParams(C.sizeof(AdaptiveParams) if size is None else size, tile, batch_spp, pilot_batches, budget_spp, max_spp, target_error,
-                          round_share, flags | (DENOISE_KEEP_ALBEDO if keep_albedo else 0) | (ADAPTIVE_ONE_LAUNCH if one_launch else 0))
+                          round_share, flags | _keep(keep_albedo) | (ADAPTIVE_ONE_LAUNCH if one_launch else 0))
 
 
 class Tile(C.Structure):
@@ -270,7 +275,7 @@ assert C.sizeof(TemporalParams) == 32, "rt1w_temporal_params is 32 bytes (includ
 
 
 def _temporal_params(width, height, keep_albedo=False, max_history=0, depth_tol=0.0, normal_min=0.0, flags=0):
-    return TemporalParams(width, height, flags | (DENOISE_KEEP_ALBEDO if keep_albedo else 0), max_history, depth_tol, normal_min)
+    return TemporalParams(width, height, flags | _keep(keep_albedo), max_history, depth_tol, normal_min)
 
 
 _CAM_ARGS = [_D3, _D3, _D3] + [C.c_double] * 6
@@ -307,6 +312,51 @@ if _lib.rt1w_abi_sizeof(6) != C.sizeof(Camera):
     raise ImportError("librt1w.so and this binding disagree on the layout of Camera: rebuild the library")
 
 
+# The functions of librt1w_lab.so this binding calls (csrc/walk_lab.h), name -> argtypes; every one returns int.  load_lab applies it.
+_I, _F, _N = C.c_int, C.c_double, C.c_uint64
+_PR, _PD, _PT, _PC = C.POINTER(RenderParams), C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(Camera)
+_LAB_SIGS = {
+    "rt1w_lab_aov_host": [_P, _PR, _P],
+    "rt1w_lab_aov_deep_host": [_P, _PR, _U, _F, _P, C.POINTER(_N), _P],
+    "rt1w_lab_aov_tiles_host": [_P, _PR, _U, _P, _U, _P],
+    "rt1w_lab_denoise_host": [_PD, _P, _P, _P],
+    "rt1w_lab_batch_variance_host": [_U] * 5 + [_P] * 4,
+    "rt1w_lab_denoise_var_host": [_PD, _P, _P, _P, _F, _P],
+    "rt1w_lab_accum_merge_host": [_U] * 8 + [_P] * 3,
+    "rt1w_lab_accum_merge_tiles_host": [_U] * 3 + [_P] + [_U] * 3 + [_P] * 3,
+    "rt1w_lab_accum_resolve_host": [_U] * 3 + [_P] * 4,
+    "rt1w_lab_tile_error_host": [_U] * 3 + [_P] * 2,
+    "rt1w_lab_halves_resolve_host": [_U] * 3 + [_P] * 7,
+    "rt1w_lab_denoise_var_halves_host": [_PD] + [_P] * 5 + [_F] + [_P] * 4,
+    "rt1w_lab_tile_error_map_host": [_U] * 3 + [_P] * 2,
+    "rt1w_lab_denoise_cross_host": [_PD] + [_P] * 5 + [_F] + [_P] * 3,
+    "rt1w_lab_guides_merge_tiles_host": [_U] * 3 + [_P] + [_U] * 2 + [_P] * 2,
+    "rt1w_lab_guides_resolve_host": [_U] * 2 + [_P] * 2,
+    "rt1w_lab_temporal_host": [_PT, _P, _P, _PC, _P, _P, _P, _PC, _P, _P, _P, _P],
+    "rt1w_lab_temporal_moments_host": [_PT, _P, _P, _PC, _P, _P, _P, _P, _PC, _P, _P, _P, _P, _P],
+    "rt1w_lab_temporal_variance_host": [_U] * 2 + [_P] * 5,
+    "rt1w_lab_scene_set_camera": [_P] + _CAM_ARGS,
+    "rt1w_lab_scene_get_camera": [_P, _PC],
+    "rt1w_lab_denoise_elementary": [_I, _I, _P, _P, _N, _P],
+    "rt1w_lab_f32_exact": [_I],
+    "rt1w_lab_f32_elementary": [_I, _I, _P, _P, _N, _P],
+}
+
+
+def load_lab():
+    """Load the diagnostics library librt1w_lab.so (the trace-only harness and the wavefront form: measured opt-ins that are not in the
+    product library).  Loading it registers the wavefront form with librt1w.so; RT1W_WAVEFRONT renders need it."""
+    global _lab
+    if _lab is None:
+        lab = C.CDLL(os.path.join(os.path.dirname(LIB_PATH), "librt1w_lab.so"))
+        for name, argtypes in _LAB_SIGS.items():
+            fn = getattr(lab, name)
+            fn.restype = C.c_int
+            fn.argtypes = argtypes
+        _lab = lab
+    return _lab
+
+
 def last_error():
     return _lib.rt1w_last_error().decode()
 
@@ -321,40 +371,228 @@ def _ck(rc):
     return rc
 
 
+def _ck_lab(rc, name):
+    """The twins do not set rt1w_last_error: the error names the function."""
+    if rc < 0:
+        raise Rt1wError(rc, name)
+    return rc
+
+
 def _stats_dict(st):
     return {n: getattr(st, n) for n, _ in Stats._fields_}
 
 
+def _c_args(args):
+    """Arguments as a C function takes them: an ndarray is its data pointer, a Structure a reference to it; None, numbers (device
+    addresses among them), handles and ctypes arrays pass as they are.  The pointers are explicit, so the call is valid under the
+    prototypes of the tables and under all-void* ones."""
+    return [a.ctypes.data_as(_P) if isinstance(a, np.ndarray) else C.byref(a) if isinstance(a, C.Structure) else a for a in args]
+
+
+def _call(fn, *args, stats=True):
+    """One call of librt1w.so, checked.  stats: `fn` takes an rt1w_stats* last; it is appended and comes back as a dict.  Else the
+    function's (non-negative) return value."""
+    if not stats:
+        return _ck(fn(*_c_args(args)))
+    st = Stats()
+    _ck(fn(*_c_args(args), C.byref(st)))
+    return _stats_dict(st)
+
+
+def _call_lab(name, *args):
+    """One call of librt1w_lab.so's function `name`, checked."""
+    return _ck_lab(getattr(load_lab(), name)(*_c_args(args)), name)
+
+
+def _twin(name, prep, *extra):
+    """A CPU twin: `prep` = (arguments, results) of the entry's _*_prep, `extra` the twin's optional outputs.  Returns the results."""
+    args, out = prep
+    _call_lab(name, *args, *extra)
+    return out
+
+
+def _ret(out, stats, with_stats):
+    """`out` (an array or a tuple of arrays), with the stats dict after it if asked for"""
+    if not with_stats:
+        return out
+    return out + (stats,) if isinstance(out, tuple) else (out, stats)
+
+
+def _f64(*arrays):
+    return [np.ascontiguousarray(x, dtype=np.float64) for x in arrays]
+
+
 def _frame_and_aov(frame, aov):
-    f, a = (np.ascontiguousarray(x, dtype=np.float64) for x in (frame, aov))
+    f, a = _f64(frame, aov)
     if f.ndim != 3 or f.shape[2] != 3 or a.shape != f.shape[:2] + (AOV_CHANNELS,):
         raise ValueError("frame must be [h, w, 3] and aov [h, w, 8]")
     return f, a
 
 
-def _temporal_args(cur_frame, cur_aov, prev_hist, prev_len, prev_aov):
+def _variance_of(var, frame):
+    v, = _f64(var)
+    if v.shape != frame.shape[:2]:
+        raise ValueError("var must be [h, w]")
+    return v
+
+
+ACCUM_RECORD = 8  # rt1w_accum_*: S rgb, m, mean_d, M2_d, mean_p, M2_p per pixel
+ACCUM_NO_ESTIMATE = -1.0
+
+
+def _accum_of(acc):
+    a, = _f64(acc)
+    if a.ndim != 3 or a.shape[2] != ACCUM_RECORD:
+        raise ValueError("acc must be [h, w, 8]")
+    return a
+
+
+GUIDES_RECORD = 9  # rt1w_guides_*: the 8 first-hit feature sums and N, the samples merged, per pixel
+
+
+def _guides_of(gacc):
+    g, = _f64(gacc)
+    if g.ndim != 3 or g.shape[2] != GUIDES_RECORD:
+        raise ValueError("gacc must be [h, w, 9]")
+    return g
+
+
+def _error_map_of(err_px):
+    e, = _f64(err_px)
+    if e.ndim != 2:
+        raise ValueError("err_px must be [h, w]")
+    return e
+
+
+# The preparation of every entry that has a CPU twin, written once for Context.X and X_host: inputs as contiguous float64, their shapes
+# checked, the outputs allocated.  Each returns (the C arguments after the context and before the stats, what the entry returns).
+
+def _aov_prep(deep, width, height, spp, tile, sample_offset, global_seed, variant, strips):
+    """deep: () for the first-hit entries, (max_specular, max_fuzz) for the deep ones"""
+    p = Context._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant=variant, strips=strips)
+    out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
+    return (p, *deep, out), out
+
+
+def _aov_tiles_prep(width, height, spp, tile, tiles, sample_offset, global_seed, variant, flags, strips, f32):
+    p = Context._params(width, height, spp, 0, None, sample_offset, global_seed, 0, False, variant=variant, strips=strips, f32=f32, flags=flags)
+    rec, n = _tile_list(tiles)
+    out = np.empty((n, tile, tile, AOV_CHANNELS), dtype=np.float64)
+    return (p, tile, rec, n, out), out
+
+
+def _denoise_prep(frame, aov, kw):
+    f, a = _frame_and_aov(frame, aov)
+    out = np.empty_like(f)
+    return (_denoise_params(f.shape[1], f.shape[0], **kw), f, a, out), out
+
+
+def _batch_variance_prep(sums, aov, batch_spp, keep_albedo):
+    s, a = _f64(sums, aov)
+    if s.ndim != 4 or s.shape[3] != 3 or a.shape != s.shape[1:3] + (AOV_CHANNELS,):
+        raise ValueError("sums must be [batches, h, w, 3] and aov [h, w, 8]")
+    frame, var = np.empty(s.shape[1:], dtype=np.float64), np.empty(s.shape[1:3], dtype=np.float64)
+    return (s.shape[2], s.shape[1], s.shape[0], batch_spp, _keep(keep_albedo), s, a, frame, var), (frame, var)
+
+
+def _denoise_var_prep(frame, aov, var, sigma_variance, kw):
+    f, a = _frame_and_aov(frame, aov)
+    v = _variance_of(var, f)
+    out = np.empty_like(f)
+    return (_denoise_params(f.shape[1], f.shape[0], **kw), f, a, v, sigma_variance, out), out
+
+
+def _halves_filter_prep(frame, aov, var, half_a, half_b, sigma_variance, kw):
+    """denoise_var_halves and denoise_cross"""
+    f, a = _frame_and_aov(frame, aov)
+    v = _variance_of(var, f)
+    ha, hb = _f64(half_a, half_b)
+    if ha.shape != f.shape or hb.shape != f.shape:
+        raise ValueError("half_a and half_b must be [h, w, 3] like the frame")
+    out, err = np.empty_like(f), np.empty(f.shape[:2])
+    return (_denoise_params(f.shape[1], f.shape[0], **kw), f, a, v, ha, hb, sigma_variance, out, err), (out, err)
+
+
+def _merge_prep(acc, tile_sums, aov, batch_spp, x0, y0, keep_albedo):
+    a = _accum_of(acc).copy()
+    s, g = _f64(tile_sums, aov)
+    if s.ndim != 3 or s.shape[2] != 3 or g.shape != a.shape[:2] + (AOV_CHANNELS,):
+        raise ValueError("tile_sums must be [tile_h, tile_w, 3] and aov [h, w, 8]")
+    return (a.shape[1], a.shape[0], x0, y0, s.shape[1], s.shape[0], batch_spp, _keep(keep_albedo), s, g, a), a
+
+
+def _merge_tiles_prep(acc, tile_sums, aov, batch_spp, tile, tiles, keep_albedo):
+    """An empty list skips the shape check, as in _guides_merge_prep: the library's own refusal is what the caller sees."""
+    a = _accum_of(acc).copy()
+    s, g = _f64(tile_sums, aov)
+    rec, n = _tile_list(tiles)
+    if n and (s.shape != (n, tile, tile, 3) or g.shape != a.shape[:2] + (AOV_CHANNELS,)):
+        raise ValueError("tile_sums must be [n_tiles, tile, tile, 3] and aov [h, w, 8]")
+    return (a.shape[1], a.shape[0], tile, rec, n, batch_spp, _keep(keep_albedo), s, g, a), a
+
+
+def _accum_resolve_prep(acc, batch_spp):
+    a = _accum_of(acc)
+    hw = a.shape[:2]
+    out = np.empty(hw + (3,)), np.empty(hw), np.empty(hw)
+    return (a.shape[1], a.shape[0], batch_spp, a, *out), out
+
+
+def _halves_resolve_prep(acc_a, acc_b, batch_spp):
+    a, b = _accum_of(acc_a), _accum_of(acc_b)
+    if a.shape != b.shape:
+        raise ValueError("acc_a and acc_b must have one shape")
+    hw = a.shape[:2]
+    out = np.empty(hw + (3,)), np.empty(hw), np.empty(hw + (3,)), np.empty(hw + (3,)), np.empty(hw)
+    return (a.shape[1], a.shape[0], batch_spp, a, b, *out), out
+
+
+def _tile_error_prep(px, tile):
+    """accum_tile_error (px = _accum_of(acc)) and tile_error_map (px = _error_map_of(err_px)).  The output is sized for a tile of at
+    least 1; the library is handed `tile` itself and refuses 0."""
+    h, w = px.shape[:2]
+    t = max(int(tile), 1)
+    err = np.empty(((h + t - 1) // t, (w + t - 1) // t))
+    return (w, h, tile, px, err), err
+
+
+def _guides_merge_prep(gacc, tile_sums, spp, tile, tiles):
+    g = _guides_of(gacc).copy()
+    s, = _f64(tile_sums)
+    rec, n = _tile_list(tiles)
+    if n and s.shape != (n, tile, tile, AOV_CHANNELS):
+        raise ValueError("tile_sums must be [n_tiles, tile, tile, 8]")
+    return (g.shape[1], g.shape[0], tile, rec, n, spp, s, g), g
+
+
+def _guides_resolve_prep(gacc):
+    g = _guides_of(gacc)
+    aov = np.empty(g.shape[:2] + (AOV_CHANNELS,))
+    return (g.shape[1], g.shape[0], g, aov), aov
+
+
+def _temporal_prep(cur_frame, cur_aov, cur_cam, prev_hist, prev_m2, prev_len, prev_aov, prev_cam, kw):
+    """temporal_accumulate (prev_m2 None) and temporal_moments: the second-moment channel goes in after prev_hist and comes back after hist"""
     f, a = _frame_and_aov(cur_frame, cur_aov)
     h, q = _frame_and_aov(prev_hist, prev_aov)
-    n = np.ascontiguousarray(prev_len, dtype=np.float64)
+    n, = _f64(prev_len)
     if h.shape != f.shape or n.shape != f.shape[:2]:
         raise ValueError("prev_hist must be [h, w, 3] and prev_len [h, w], the current frame's size")
-    return f, a, h, n, q
-
-
-def _moments_args(cur_frame, cur_aov, prev_hist, prev_m2, prev_len, prev_aov):
-    f, a, h, n, q = _temporal_args(cur_frame, cur_aov, prev_hist, prev_len, prev_aov)
-    m = np.ascontiguousarray(prev_m2, dtype=np.float64)
-    if m.shape != f.shape[:2]:
+    m = () if prev_m2 is None else tuple(_f64(prev_m2))
+    if m and m[0].shape != f.shape[:2]:
         raise ValueError("prev_m2 must be [h, w], the current frame's size")
-    return f, a, h, m, n, q
+    p = _temporal_params(f.shape[1], f.shape[0], **kw)
+    out = (np.empty_like(f),) + tuple(np.empty_like(n) for _ in m) + (np.empty_like(n), np.empty_like(f))
+    return (p, f, a, Camera.of(cur_cam), h, *m, n, q, Camera.of(prev_cam), *out), out
 
 
-def _variance_args(hist, m2, length, aov):
+def _temporal_variance_prep(hist, m2, length, aov):
     h, a = _frame_and_aov(hist, aov)
-    m, n = (np.ascontiguousarray(x, dtype=np.float64) for x in (m2, length))
+    m, n = _f64(m2, length)
     if m.shape != h.shape[:2] or n.shape != h.shape[:2]:
         raise ValueError("m2 and len must be [h, w], the history's size")
-    return h, m, n, a
+    var = np.empty_like(m)
+    return (h.shape[1], h.shape[0], h, m, n, a, var), var
 
 
 def reference_camera(arm, aspect_ratio=None):
@@ -377,83 +615,6 @@ def orbit_camera(args, degrees):
     c, s = math.cos(math.radians(degrees)), math.sin(math.radians(degrees))
     dx, dz = lf[0] - la[0], lf[2] - la[2]
     return dict(args, look_from=(la[0] + c * dx + s * dz, lf[1], la[2] - s * dx + c * dz))
-
-
-def _sums_and_aov(sums, aov):
-    s, a = (np.ascontiguousarray(x, dtype=np.float64) for x in (sums, aov))
-    if s.ndim != 4 or s.shape[3] != 3 or a.shape != s.shape[1:3] + (AOV_CHANNELS,):
-        raise ValueError("sums must be [batches, h, w, 3] and aov [h, w, 8]")
-    return s, a
-
-
-def _variance_of(var, frame):
-    v = np.ascontiguousarray(var, dtype=np.float64)
-    if v.shape != frame.shape[:2]:
-        raise ValueError("var must be [h, w]")
-    return v
-
-
-ACCUM_RECORD = 8  # rt1w_accum_*: S rgb, m, mean_d, M2_d, mean_p, M2_p per pixel
-ACCUM_NO_ESTIMATE = -1.0
-
-
-def _accum_of(acc):
-    a = np.ascontiguousarray(acc, dtype=np.float64)
-    if a.ndim != 3 or a.shape[2] != ACCUM_RECORD:
-        raise ValueError("acc must be [h, w, 8]")
-    return a
-
-
-GUIDES_RECORD = 9  # rt1w_guides_*: the 8 first-hit feature sums and N, the samples merged, per pixel
-
-
-def _guides_of(gacc):
-    g = np.ascontiguousarray(gacc, dtype=np.float64)
-    if g.ndim != 3 or g.shape[2] != GUIDES_RECORD:
-        raise ValueError("gacc must be [h, w, 9]")
-    return g
-
-
-def _guides_merge_args(gacc, tile_sums, tile, tiles):
-    g = _guides_of(gacc).copy()
-    s = np.ascontiguousarray(tile_sums, dtype=np.float64)
-    if len(tiles) and s.shape != (len(tiles), tile, tile, AOV_CHANNELS):
-        raise ValueError("tile_sums must be [n_tiles, tile, tile, 8]")
-    return g, s
-
-
-def _halves_of(frame, half_a, half_b):
-    a, b = (np.ascontiguousarray(x, dtype=np.float64) for x in (half_a, half_b))
-    if a.shape != frame.shape or b.shape != frame.shape:
-        raise ValueError("half_a and half_b must be [h, w, 3] like the frame")
-    return a, b
-
-
-def _error_map_of(err_px):
-    e = np.ascontiguousarray(err_px, dtype=np.float64)
-    if e.ndim != 2:
-        raise ValueError("err_px must be [h, w]")
-    return e
-
-
-def _merge_args(acc, tile_sums, aov, x0, y0):
-    a = _accum_of(acc).copy()
-    s, g = (np.ascontiguousarray(x, dtype=np.float64) for x in (tile_sums, aov))
-    if s.ndim != 3 or s.shape[2] != 3 or g.shape != a.shape[:2] + (AOV_CHANNELS,):
-        raise ValueError("tile_sums must be [tile_h, tile_w, 3] and aov [h, w, 8]")
-    return a, s, g, (a.shape[1], a.shape[0], x0, y0, s.shape[1], s.shape[0])
-
-
-def _merge_tiles_args(acc, tile_sums, aov, tile, tiles):
-    a = _accum_of(acc).copy()
-    s, g = (np.ascontiguousarray(x, dtype=np.float64) for x in (tile_sums, aov))
-    if s.shape != (len(tiles), tile, tile, 3) or g.shape != a.shape[:2] + (AOV_CHANNELS,):
-        raise ValueError("tile_sums must be [n_tiles, tile, tile, 3] and aov [h, w, 8]")
-    return a, s, g
-
-
-def _tiles_of(width, height, tile):
-    return (width + tile - 1) // tile, (height + tile - 1) // tile
 
 
 def _v3(v):
@@ -666,14 +827,36 @@ class Context:
     __del__ = close
 
     @staticmethod
-    def _params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, variant=None, unsorted=False, lds_nodes=False, generic=False, wavefront=False,
-                strips=None, out_frame=False, reference_stream=False, f32=False, classic_walk=False, probe_coherent=False, partial_mib=0, no_node_cache=False):
-        x0, y0, tw, th = tile if tile is not None else (0, 0, width, height)
-        if wavefront:
+    def _params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, *, variant=None, strips=None, f32=False,
+                partial_mib=0, flags=0, **switches):
+        """rt1w_render_params.  switches: the keywords of _RENDER_FLAGS (out_sum is one of them); flags: raw RT1W_* bits on top."""
+        if switches.keys() - _RENDER_FLAGS.keys():
+            raise TypeError(f"_params() got an unexpected keyword argument {sorted(switches.keys() - _RENDER_FLAGS.keys())[0]!r}")
+        if switches.get("wavefront"):
             load_lab()
-        flags = (OUT_SUM if out_sum else 0) | (OUT_FRAME if out_frame else 0) | (RNG_REFERENCE if reference_stream else 0) | (UNSORTED if unsorted else 0) | (LDS_NODES if lds_nodes else 0) | (GENERIC if generic else 0) | (WAVEFRONT if wavefront else 0) | (CLASSIC_WALK if classic_walk else 0) | (NO_NODE_CACHE if no_node_cache else 0) | (PROBE_COHERENT if probe_coherent else 0) | (((variant + 1) << 8) if variant is not None else 0)
+        for name, on in dict(switches, out_sum=out_sum).items():
+            flags |= _RENDER_FLAGS[name] if on else 0
+        if variant is not None:
+            flags |= (variant + 1) << 8
+        x0, y0, tw, th = tile if tile is not None else (0, 0, width, height)
         sr, sp = strips if strips is not None else (0, 0)
         return RenderParams(width, height, x0, y0, tw, th, spp, sample_offset, max_depth, global_seed, chunk, flags, sr, sp, 1 if f32 else 0, int(partial_mib))
+
+    def _composite(self, width, height, spp, max_depth, sample_offset, global_seed, chunk, flags, denoise, kw, filter=False, precision=None):
+        """(p, d, out) of the entries that render and filter in one call.  kw: Context.render's keywords, `tile` among them; flags: raw
+        RT1W_* render flags; denoise: dict of the filter's keywords -- without one d is None (the defaults), unless `filter` asks for
+        the filter; precision: rt1w_render_params.precision, None = what kw's f32 says."""
+        p = self._params(width, height, spp, max_depth, kw.pop("tile", None), sample_offset, global_seed, chunk, False, flags=flags, **kw)
+        if precision is not None:
+            p.precision = precision
+        d = _denoise_params(0, 0, **(denoise or {})) if (filter or denoise is not None) else None
+        return p, d, np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
+
+    def _entry(self, fn, prep, with_stats):
+        """A feature entry on host arrays: `prep` = (arguments, results) of the entry's _*_prep.  Returns the results, with the stats
+        dict after them if asked for."""
+        args, out = prep
+        return _ret(out, _call(fn, self._h, *args), with_stats)
 
     def specialise(self, cached_only=False, tiles=False):
         """Load (from the kernel cache) or compile (hiprtc, 3-5 s) the kernel specialised for this scene's topology
@@ -681,7 +864,7 @@ class Context:
         (ERR_UNSUPPORTED) or, with cached_only, on a cache miss (ERR_STATE).  tiles: the kernel's tile-list form too
         (RT1W_SPECIALISE_TILES: what render_tiles(specialised=True) runs)."""
         info = SpecialiseInfo()
-        _ck(_lib.rt1w_context_specialise(self._h, (SPECIALISE_CACHED_ONLY if cached_only else 0) | (SPECIALISE_TILES if tiles else 0), C.byref(info)))
+        _call(_lib.rt1w_context_specialise, self._h, (SPECIALISE_CACHED_ONLY if cached_only else 0) | (SPECIALISE_TILES if tiles else 0), info, stats=False)
         return {"key": info.key.decode(), "active": bool(info.active), "from_cache": bool(info.from_cache),
                 "compile_ms": info.compile_ms, "grid": info.grid, "vgprs": info.vgprs}
 
@@ -699,8 +882,10 @@ class Context:
         strips=(strip_rows, strip_period): row-interleaved tile (tile row r = image row y0 + r//strip_rows*strip_period +
         r%strip_rows).  out: caller's array for the packed tile (e.g. pinned_empty).  frame: caller's WHOLE image
         [height, width, 3]; the tile's pixels are written at their image positions (RT1W_OUT_FRAME) and `frame` is returned."""
-        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, variant, unsorted, lds_nodes, generic, wavefront,
-                         strips, frame is not None, reference_stream, f32, classic_walk, probe_coherent, partial_mib, no_node_cache)
+        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, variant=variant, unsorted=unsorted,
+                         lds_nodes=lds_nodes, generic=generic, wavefront=wavefront, strips=strips, out_frame=frame is not None,
+                         reference_stream=reference_stream, f32=f32, classic_walk=classic_walk, probe_coherent=probe_coherent,
+                         partial_mib=partial_mib, no_node_cache=no_node_cache)
         if frame is not None:
             assert frame.dtype == np.float64 and frame.shape == (height, width, 3) and frame.flags.c_contiguous
             out = frame
@@ -708,9 +893,7 @@ class Context:
             out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
         else:
             assert out.dtype == np.float64 and out.shape == (p.tile_h, p.tile_w, 3) and out.flags.c_contiguous
-        st = Stats()
-        _ck(_lib.rt1w_render(self._h, C.byref(p), out.ctypes.data_as(_P), C.byref(st)))
-        return out, _stats_dict(st)
+        return out, _call(_lib.rt1w_render, self._h, p, out)
 
     def render_u8(self, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, chunk=0, reference_stream=False,
                   partial_mib=0):
@@ -718,9 +901,7 @@ class Context:
         p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, False, reference_stream=reference_stream,
                          partial_mib=partial_mib)
         out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.uint8)
-        st = Stats()
-        _ck(_lib.rt1w_render_u8(self._h, C.byref(p), out.ctypes.data_as(_P), C.byref(st)))
-        return out, _stats_dict(st)
+        return out, _call(_lib.rt1w_render_u8, self._h, p, out)
 
     def render_rows(self, width, height, spp, strip_rows=0, u8=False, progress=None, max_depth=50, tile=None,
                     sample_offset=0, global_seed=0, chunk=0, out_sum=False, out=None, no_node_cache=False, partial_mib=0, f32=False, generic=False):
@@ -732,20 +913,15 @@ class Context:
         if out is None:
             out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.uint8 if u8 else np.float64)
         assert out.flags.c_contiguous and out.shape == (p.tile_h, p.tile_w, 3) and out.dtype == (np.uint8 if u8 else np.float64)
-        st = Stats()
         cb = PROGRESS_FN((lambda user, done, total: 1 if progress(done, total) else 0) if progress else 0)
-        _ck(_lib.rt1w_render_rows(self._h, C.byref(p), strip_rows, ROWS_U8 if u8 else ROWS_F64, out.ctypes.data_as(_P), cb,
-                                  None, C.byref(st)))
-        return out, _stats_dict(st)
+        return out, _call(_lib.rt1w_render_rows, self._h, p, strip_rows, ROWS_U8 if u8 else ROWS_F64, out, cb, None)
 
     def render_device(self, d_ptr, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, chunk=0,
                       out_sum=False, variant=None, unsorted=False, generic=False, strips=None, f32=False, partial_mib=0):
         """Same, into device memory `d_ptr` (int address, e.g. torch tensor .data_ptr()); packed tile rows."""
-        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, variant, unsorted, False, generic,
-                         False, strips, f32=f32, partial_mib=partial_mib)
-        st = Stats()
-        _ck(_lib.rt1w_render_device(self._h, C.byref(p), C.c_void_p(d_ptr), C.byref(st)))
-        return _stats_dict(st)
+        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, out_sum, variant=variant, unsorted=unsorted,
+                         generic=generic, strips=strips, f32=f32, partial_mib=partial_mib)
+        return _call(_lib.rt1w_render_device, self._h, p, d_ptr)
 
     def render_tiles(self, width, height, spp, tile, tiles, max_depth=50, sample_offset=0, global_seed=0, chunk=0, out_sum=False, generic=False,
                      partial_mib=0, flags=0, strips=None, f32=False, specialised=False):
@@ -753,414 +929,242 @@ class Context:
         tuples.  Returns (float64 [n, tile, tile, 3], stats); tile k's row 0 = image row y0_k, pixels beyond the frame's edge are +0.0.
         specialised: RT1W_TILES_SPECIALISED -- the tile-list form of the scene-specialised kernel where a kernel cache has one."""
         p = self._params(width, height, spp, max_depth, None, sample_offset, global_seed, chunk, out_sum, generic=generic, partial_mib=partial_mib,
-                         strips=strips, f32=f32)
-        p.flags |= flags | (TILES_SPECIALISED if specialised else 0)
+                         strips=strips, f32=f32, flags=flags | (TILES_SPECIALISED if specialised else 0))
         rec, n = _tile_list(tiles)
         out = np.empty((n, tile, tile, 3), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_tiles(self._h, C.byref(p), tile, rec, n, out.ctypes.data_as(_P), C.byref(st)))
-        return out, _stats_dict(st)
+        return out, _call(_lib.rt1w_render_tiles, self._h, p, tile, rec, n, out)
 
     def render_tiles_device(self, d_ptr, width, height, spp, tile, tiles, max_depth=50, sample_offset=0, global_seed=0, chunk=0, out_sum=False,
                             generic=False, partial_mib=0, flags=0, specialised=False):
         """Same, into device memory `d_ptr` (int address) of n * tile * tile * 3 doubles; the list itself is host memory.  Returns the stats."""
-        p = self._params(width, height, spp, max_depth, None, sample_offset, global_seed, chunk, out_sum, generic=generic, partial_mib=partial_mib)
-        p.flags |= flags | (TILES_SPECIALISED if specialised else 0)
-        rec, n = _tile_list(tiles)
-        st = Stats()
-        _ck(_lib.rt1w_render_tiles_device(self._h, C.byref(p), tile, rec, n, C.c_void_p(d_ptr), C.byref(st)))
-        return _stats_dict(st)
-
-    # deep: () for the first-hit entries, (max_specular, max_fuzz) for the deep ones
-    def _render_aov(self, deep, width, height, spp, tile, sample_offset, global_seed, variant, strips, with_stats):
-        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
-        out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
-        st = Stats()
-        _ck((_lib.rt1w_render_aov_deep if deep else _lib.rt1w_render_aov)(self._h, C.byref(p), *deep, out.ctypes.data_as(_P), C.byref(st)))
-        return (out, _stats_dict(st)) if with_stats else out
-
-    def _render_aov_device(self, deep, d_ptr, width, height, spp, tile, sample_offset, global_seed, variant, strips):
-        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
-        st = Stats()
-        _ck((_lib.rt1w_render_aov_deep_device if deep else _lib.rt1w_render_aov_device)(self._h, C.byref(p), *deep, C.c_void_p(d_ptr), C.byref(st)))
-        return _stats_dict(st)
+        p = self._params(width, height, spp, max_depth, None, sample_offset, global_seed, chunk, out_sum, generic=generic, partial_mib=partial_mib,
+                         flags=flags | (TILES_SPECIALISED if specialised else 0))
+        return _call(_lib.rt1w_render_tiles_device, self._h, p, tile, *_tile_list(tiles), d_ptr)
 
     def render_aov(self, width, height, spp, tile=None, sample_offset=0, global_seed=0, variant=None, strips=None, with_stats=False):
         """First-hit feature buffers of the tile (rt1w_render_aov): float64 [tile_h, tile_w, 8] = albedo rgb, normal xyz, depth,
         coverage, row 0 = reference row j = y0 (include/rt1w.h has the semantics).  with_stats: returns (array, stats dict)."""
-        return self._render_aov((), width, height, spp, tile, sample_offset, global_seed, variant, strips, with_stats)
+        return self._entry(_lib.rt1w_render_aov, _aov_prep((), width, height, spp, tile, sample_offset, global_seed, variant, strips), with_stats)
 
     def render_aov_device(self, d_ptr, width, height, spp, tile=None, sample_offset=0, global_seed=0, variant=None, strips=None):
         """Same, into device memory `d_ptr` (int address of tile_h * tile_w * 8 float64, e.g. a torch tensor's .data_ptr());
         returns the stats dict."""
-        return self._render_aov_device((), d_ptr, width, height, spp, tile, sample_offset, global_seed, variant, strips)
+        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant=variant, strips=strips)
+        return _call(_lib.rt1w_render_aov_device, self._h, p, d_ptr)
 
     def render_aov_deep(self, width, height, spp, max_specular=8, max_fuzz=0.0, tile=None, sample_offset=0, global_seed=0, variant=None,
                         strips=None, with_stats=False):
         """Deep feature buffers of the tile (rt1w_render_aov_deep): the 8 channels of render_aov at the first vertex of each sample's
         path that is neither a Dielectric nor a Metal of fuzz <= max_fuzz, after at most max_specular bounces.  stats["segments"] is
         the number of rays traced."""
-        return self._render_aov((max_specular, max_fuzz), width, height, spp, tile, sample_offset, global_seed, variant, strips, with_stats)
+        return self._entry(_lib.rt1w_render_aov_deep,
+                           _aov_prep((max_specular, max_fuzz), width, height, spp, tile, sample_offset, global_seed, variant, strips), with_stats)
 
     def render_aov_deep_device(self, d_ptr, width, height, spp, max_specular=8, max_fuzz=0.0, tile=None, sample_offset=0, global_seed=0,
                                variant=None, strips=None):
         """Same, into device memory `d_ptr` (int address of tile_h * tile_w * 8 float64); returns the stats dict."""
-        return self._render_aov_device((max_specular, max_fuzz), d_ptr, width, height, spp, tile, sample_offset, global_seed, variant, strips)
+        p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant=variant, strips=strips)
+        return _call(_lib.rt1w_render_aov_deep_device, self._h, p, max_specular, max_fuzz, d_ptr)
 
     def denoise(self, frame, aov, with_stats=False, **kw):
         """Feature-guided filter (rt1w_denoise) of a float64 frame [h, w, 3] with its feature buffers [h, w, 8] (render_aov): the
         denoised [h, w, 3].  kw: iterations, keep_albedo, sigma_colour, sigma_normal, sigma_depth (0 = default)."""
-        f, a = _frame_and_aov(frame, aov)
-        p = _denoise_params(f.shape[1], f.shape[0], **kw)
-        out = np.empty_like(f)
-        st = Stats()
-        _ck(_lib.rt1w_denoise(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), out.ctypes.data_as(_P), C.byref(st)))
-        return (out, _stats_dict(st)) if with_stats else out
+        return self._entry(_lib.rt1w_denoise, _denoise_prep(frame, aov, kw), with_stats)
 
     def denoise_device(self, d_frame, d_aov, d_out, width, height, **kw):
         """Same on device memory (int addresses of height * width * 3 / 8 / 3 float64, e.g. torch tensors' .data_ptr()); d_out may
         equal d_frame.  Returns the stats dict."""
-        p = _denoise_params(width, height, **kw)
-        st = Stats()
-        _ck(_lib.rt1w_denoise_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_out), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_denoise_device, self._h, _denoise_params(width, height, **kw), d_frame, d_aov, d_out)
 
     def set_camera(self, look_from, look_at, vup, vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1):
         """Replace this context's camera (rt1w_context_set_camera): Scene.set_camera's arguments and arithmetic, host work only.
         The scene and its other contexts keep theirs."""
-        _ck(_lib.rt1w_context_set_camera(self._h, _v3(look_from), _v3(look_at), _v3(vup), vfov_deg, aspect_ratio, aperture, focus_dist,
-                                         time0, time1))
+        _call(_lib.rt1w_context_set_camera, self._h, _v3(look_from), _v3(look_at), _v3(vup), vfov_deg, aspect_ratio, aperture, focus_dist,
+              time0, time1, stats=False)
 
     def get_camera(self):
         """The Camera the kernels of this context are handed now (rt1w_context_get_camera)."""
         cam = Camera()
-        _ck(_lib.rt1w_context_get_camera(self._h, C.byref(cam)))
+        _call(_lib.rt1w_context_get_camera, self._h, cam, stats=False)
         return cam
 
     def temporal_accumulate(self, cur_frame, cur_aov, cur_cam, prev_hist, prev_len, prev_aov, prev_cam, with_stats=False, **kw):
         """Temporal accumulation (rt1w_temporal_accumulate) of a float64 frame [h, w, 3] with its feature buffers [h, w, 8] against the
         previous frame's (hist [h, w, 3], len [h, w], feature buffers); the cameras are Camera or 24 doubles.  Returns
         (hist, len, frame_out).  kw: keep_albedo, max_history, depth_tol, normal_min (0 = default)."""
-        f, a, h, n, q = _temporal_args(cur_frame, cur_aov, prev_hist, prev_len, prev_aov)
-        p = _temporal_params(f.shape[1], f.shape[0], **kw)
-        hist, ln, out = np.empty_like(f), np.empty_like(n), np.empty_like(f)
-        st = Stats()
-        _ck(_lib.rt1w_temporal_accumulate(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(Camera.of(cur_cam)),
-                                          h.ctypes.data_as(_P), n.ctypes.data_as(_P), q.ctypes.data_as(_P), C.byref(Camera.of(prev_cam)),
-                                          hist.ctypes.data_as(_P), ln.ctypes.data_as(_P), out.ctypes.data_as(_P), C.byref(st)))
-        return (hist, ln, out, _stats_dict(st)) if with_stats else (hist, ln, out)
+        return self._entry(_lib.rt1w_temporal_accumulate, _temporal_prep(cur_frame, cur_aov, cur_cam, prev_hist, None, prev_len, prev_aov, prev_cam, kw),
+                           with_stats)
 
     def temporal_accumulate_device(self, d_cur_frame, d_cur_aov, cur_cam, d_prev_hist, d_prev_len, d_prev_aov, prev_cam, d_hist, d_len,
                                    d_frame_out, width, height, **kw):
         """Same on device memory (int addresses, e.g. torch tensors' .data_ptr()).  Returns the stats dict."""
-        p = _temporal_params(width, height, **kw)
-        st = Stats()
-        _ck(_lib.rt1w_temporal_accumulate_device(self._h, C.byref(p), C.c_void_p(d_cur_frame), C.c_void_p(d_cur_aov), C.byref(Camera.of(cur_cam)),
-                                                 C.c_void_p(d_prev_hist), C.c_void_p(d_prev_len), C.c_void_p(d_prev_aov),
-                                                 C.byref(Camera.of(prev_cam)), C.c_void_p(d_hist), C.c_void_p(d_len), C.c_void_p(d_frame_out),
-                                                 C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_temporal_accumulate_device, self._h, _temporal_params(width, height, **kw), d_cur_frame, d_cur_aov, Camera.of(cur_cam),
+                     d_prev_hist, d_prev_len, d_prev_aov, Camera.of(prev_cam), d_hist, d_len, d_frame_out)
 
     def render_temporal(self, width, height, spp, max_depth=50, sample_offset=0, global_seed=0, temporal=None, denoise=None, filter=False,
                         flags=0, with_stats=False, **kw):
         """One frame of an animation (rt1w_render_temporal): render, feature buffers, accumulation against the state this context keeps
         from the previous call, optionally the filter (filter=True, or `denoise`: dict of Context.denoise's keywords): float64
         [height, width, 3].  `temporal`: dict of temporal_accumulate's keywords; other kw as Context.render's."""
-        p = self._params(width, height, spp, max_depth, kw.pop("tile", None), sample_offset, global_seed, 0, False, kw.pop("variant", None), **kw)
-        p.flags |= flags
+        p, d, out = self._composite(width, height, spp, max_depth, sample_offset, global_seed, 0, flags, denoise, kw, filter=filter)
         t = _temporal_params(0, 0, **temporal) if temporal is not None else None
-        d = _denoise_params(0, 0, **(denoise or {})) if (filter or denoise is not None) else None
-        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_temporal(self._h, C.byref(p), C.byref(t) if t is not None else None, C.byref(d) if d is not None else None,
-                                      out.ctypes.data_as(_P), C.byref(st)))
-        return (out, _stats_dict(st)) if with_stats else out
+        return _ret(out, _call(_lib.rt1w_render_temporal, self._h, p, t, d, out), with_stats)
 
     def temporal_moments(self, cur_frame, cur_aov, cur_cam, prev_hist, prev_m2, prev_len, prev_aov, prev_cam, with_stats=False, **kw):
         """temporal_accumulate with the second-moment channel (rt1w_temporal_moments): prev_m2 [h, w] goes in after prev_hist, and
         (hist, m2, len, frame_out) come back; hist, len and frame_out are temporal_accumulate's bits.  kw as temporal_accumulate's."""
-        f, a, h, m, n, q = _moments_args(cur_frame, cur_aov, prev_hist, prev_m2, prev_len, prev_aov)
-        p = _temporal_params(f.shape[1], f.shape[0], **kw)
-        hist, m2, ln, out = np.empty_like(f), np.empty_like(n), np.empty_like(n), np.empty_like(f)
-        st = Stats()
-        _ck(_lib.rt1w_temporal_moments(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(Camera.of(cur_cam)),
-                                       h.ctypes.data_as(_P), m.ctypes.data_as(_P), n.ctypes.data_as(_P), q.ctypes.data_as(_P),
-                                       C.byref(Camera.of(prev_cam)), hist.ctypes.data_as(_P), m2.ctypes.data_as(_P), ln.ctypes.data_as(_P),
-                                       out.ctypes.data_as(_P), C.byref(st)))
-        return (hist, m2, ln, out, _stats_dict(st)) if with_stats else (hist, m2, ln, out)
+        return self._entry(_lib.rt1w_temporal_moments, _temporal_prep(cur_frame, cur_aov, cur_cam, prev_hist, prev_m2, prev_len, prev_aov, prev_cam, kw),
+                           with_stats)
 
     def temporal_moments_device(self, d_cur_frame, d_cur_aov, cur_cam, d_prev_hist, d_prev_m2, d_prev_len, d_prev_aov, prev_cam, d_hist, d_m2,
                                 d_len, d_frame_out, width, height, **kw):
         """Same on device memory (int addresses, e.g. torch tensors' .data_ptr()).  Returns the stats dict."""
-        p = _temporal_params(width, height, **kw)
-        st = Stats()
-        _ck(_lib.rt1w_temporal_moments_device(self._h, C.byref(p), C.c_void_p(d_cur_frame), C.c_void_p(d_cur_aov), C.byref(Camera.of(cur_cam)),
-                                              C.c_void_p(d_prev_hist), C.c_void_p(d_prev_m2), C.c_void_p(d_prev_len), C.c_void_p(d_prev_aov),
-                                              C.byref(Camera.of(prev_cam)), C.c_void_p(d_hist), C.c_void_p(d_m2), C.c_void_p(d_len),
-                                              C.c_void_p(d_frame_out), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_temporal_moments_device, self._h, _temporal_params(width, height, **kw), d_cur_frame, d_cur_aov, Camera.of(cur_cam),
+                     d_prev_hist, d_prev_m2, d_prev_len, d_prev_aov, Camera.of(prev_cam), d_hist, d_m2, d_len, d_frame_out)
 
     def temporal_variance(self, hist, m2, length, aov, with_stats=False):
         """The variance buffer of denoise_var from a history (rt1w_temporal_variance): hist [h, w, 3], m2 and len [h, w] as
         temporal_moments returned them, aov the CURRENT frame's feature buffers: var [h, w]."""
-        h, m, n, a = _variance_args(hist, m2, length, aov)
-        var = np.empty_like(m)
-        st = Stats()
-        _ck(_lib.rt1w_temporal_variance(self._h, h.shape[1], h.shape[0], h.ctypes.data_as(_P), m.ctypes.data_as(_P), n.ctypes.data_as(_P),
-                                        a.ctypes.data_as(_P), var.ctypes.data_as(_P), C.byref(st)))
-        return (var, _stats_dict(st)) if with_stats else var
+        return self._entry(_lib.rt1w_temporal_variance, _temporal_variance_prep(hist, m2, length, aov), with_stats)
 
     def temporal_variance_device(self, d_hist, d_m2, d_len, d_aov, d_var, width, height):
         """Same on device memory (int addresses).  Returns the stats dict."""
-        st = Stats()
-        _ck(_lib.rt1w_temporal_variance_device(self._h, width, height, C.c_void_p(d_hist), C.c_void_p(d_m2), C.c_void_p(d_len), C.c_void_p(d_aov),
-                                               C.c_void_p(d_var), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_temporal_variance_device, self._h, width, height, d_hist, d_m2, d_len, d_aov, d_var)
 
     def render_temporal_var(self, width, height, spp, max_depth=50, sample_offset=0, global_seed=0, temporal=None, denoise=None,
                             sigma_variance=0.0, flags=0, with_stats=False, **kw):
         """One frame of an animation filtered with the history's own variance (rt1w_render_temporal_var): render, feature buffers,
         temporal_moments against a state of this entry's own, temporal_variance, denoise_var: float64 [height, width, 3].  `temporal`:
         dict of temporal_accumulate's keywords, `denoise`: dict of Context.denoise's; other kw as Context.render's."""
-        p = self._params(width, height, spp, max_depth, kw.pop("tile", None), sample_offset, global_seed, 0, False, kw.pop("variant", None), **kw)
-        p.flags |= flags
+        p, d, out = self._composite(width, height, spp, max_depth, sample_offset, global_seed, 0, flags, denoise, kw)
         t = _temporal_params(0, 0, **temporal) if temporal is not None else None
-        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
-        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_temporal_var(self._h, C.byref(p), C.byref(t) if t is not None else None, C.byref(d) if d is not None else None,
-                                          sigma_variance, out.ctypes.data_as(_P), C.byref(st)))
-        return (out, _stats_dict(st)) if with_stats else out
+        return _ret(out, _call(_lib.rt1w_render_temporal_var, self._h, p, t, d, sigma_variance, out), with_stats)
 
     def temporal_reset(self):
         """Forget the history of render_temporal and of render_temporal_var (rt1w_temporal_reset): the next call is a first frame."""
         _ck(_lib.rt1w_temporal_reset(self._h))
 
-    def _render_denoised(self, deep, width, height, spp, max_depth, tile, sample_offset, global_seed, denoise, flags, strips, precision, with_stats, kw):
-        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, 0, False, kw.pop("variant", None), strips=strips, **kw)
-        p.flags |= flags
-        p.precision = precision
-        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
-        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
-        st = Stats()
-        _ck((_lib.rt1w_render_denoised_deep if deep else _lib.rt1w_render_denoised)(self._h, C.byref(p), C.byref(d) if d is not None else None, *deep, out.ctypes.data_as(_P), C.byref(st)))
-        return (out, _stats_dict(st)) if with_stats else out
-
     def render_denoised(self, width, height, spp, max_depth=50, tile=None, sample_offset=0, global_seed=0, denoise=None, flags=0,
                         strips=None, precision=0, with_stats=False, **kw):
         """Render, feature buffers and filter in one call (rt1w_render_denoised): float64 [tile_h, tile_w, 3].  `denoise`: dict of
         the keywords of Context.denoise, None = defaults; `flags`: raw RT1W_* render flags; other kw as Context.render's."""
-        return self._render_denoised((), width, height, spp, max_depth, tile, sample_offset, global_seed, denoise, flags, strips, precision, with_stats, kw)
+        p, d, out = self._composite(width, height, spp, max_depth, sample_offset, global_seed, 0, flags, denoise, dict(kw, tile=tile, strips=strips),
+                                    precision=precision)
+        return _ret(out, _call(_lib.rt1w_render_denoised, self._h, p, d, out), with_stats)
 
     def render_denoised_deep(self, width, height, spp, max_specular=8, max_fuzz=0.0, max_depth=50, tile=None, sample_offset=0, global_seed=0,
                              denoise=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
         """render_denoised with the deep feature buffers (rt1w_render_denoised_deep) in place of the first-hit ones."""
-        return self._render_denoised((max_specular, max_fuzz), width, height, spp, max_depth, tile, sample_offset, global_seed, denoise, flags, strips, precision, with_stats, kw)
+        p, d, out = self._composite(width, height, spp, max_depth, sample_offset, global_seed, 0, flags, denoise, dict(kw, tile=tile, strips=strips),
+                                    precision=precision)
+        return _ret(out, _call(_lib.rt1w_render_denoised_deep, self._h, p, d, max_specular, max_fuzz, out), with_stats)
 
     def batch_variance(self, sums, aov, batch_spp, keep_albedo=False, with_stats=False):
         """Frame and variance from K sample batches (rt1w_batch_variance): `sums` float64 [K, h, w, 3], the raw sums of K renders with
         out_sum=True, spp=batch_spp and sample_offset = k * batch_spp; `aov` [h, w, 8].  Returns (frame [h, w, 3], var [h, w]): the mean
         over all K * batch_spp samples and the variance of the mean demodulated luminance."""
-        s, a = _sums_and_aov(sums, aov)
-        frame = np.empty(s.shape[1:], dtype=np.float64)
-        var = np.empty(s.shape[1:3], dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_batch_variance(self._h, s.shape[2], s.shape[1], s.shape[0], batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0,
-                                     s.ctypes.data_as(_P), a.ctypes.data_as(_P), frame.ctypes.data_as(_P), var.ctypes.data_as(_P), C.byref(st)))
-        return (frame, var, _stats_dict(st)) if with_stats else (frame, var)
+        return self._entry(_lib.rt1w_batch_variance, _batch_variance_prep(sums, aov, batch_spp, keep_albedo), with_stats)
 
     def batch_variance_device(self, d_sums, d_aov, d_frame, d_var, width, height, batches, batch_spp, keep_albedo=False):
         """Same on device memory (int addresses of batches * height * width * 3, height * width * 8 / 3 / 1 float64).  Returns the stats dict."""
-        st = Stats()
-        _ck(_lib.rt1w_batch_variance_device(self._h, width, height, batches, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0,
-                                            C.c_void_p(d_sums), C.c_void_p(d_aov), C.c_void_p(d_frame), C.c_void_p(d_var), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_batch_variance_device, self._h, width, height, batches, batch_spp, _keep(keep_albedo), d_sums, d_aov, d_frame, d_var)
 
     def denoise_var(self, frame, aov, var, sigma_variance=0.0, with_stats=False, **kw):
         """Variance-guided filter (rt1w_denoise_var) of a float64 frame [h, w, 3] with its feature buffers [h, w, 8] and the variance
         [h, w] of batch_variance: the denoised [h, w, 3].  kw: iterations, keep_albedo, sigma_normal, sigma_depth (0 = default)."""
-        f, a = _frame_and_aov(frame, aov)
-        v = _variance_of(var, f)
-        p = _denoise_params(f.shape[1], f.shape[0], **kw)
-        out = np.empty_like(f)
-        st = Stats()
-        _ck(_lib.rt1w_denoise_var(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), sigma_variance,
-                                  out.ctypes.data_as(_P), C.byref(st)))
-        return (out, _stats_dict(st)) if with_stats else out
+        return self._entry(_lib.rt1w_denoise_var, _denoise_var_prep(frame, aov, var, sigma_variance, kw), with_stats)
 
     def denoise_var_device(self, d_frame, d_aov, d_var, d_out, width, height, sigma_variance=0.0, **kw):
         """Same on device memory (int addresses of height * width * 3 / 8 / 1 / 3 float64); d_out may equal d_frame.  Returns the stats dict."""
-        p = _denoise_params(width, height, **kw)
-        st = Stats()
-        _ck(_lib.rt1w_denoise_var_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_var), sigma_variance,
-                                         C.c_void_p(d_out), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_denoise_var_device, self._h, _denoise_params(width, height, **kw), d_frame, d_aov, d_var, sigma_variance, d_out)
 
     def render_denoised_var(self, width, height, spp, batches=0, sigma_variance=0.0, max_specular=0, max_fuzz=0.0, max_depth=50, tile=None,
                             sample_offset=0, global_seed=0, chunk=0, denoise=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
         """Batches, feature buffers, batch variance and the variance-guided filter in one call (rt1w_render_denoised_var): float64
         [tile_h, tile_w, 3].  `spp` must be a multiple of `batches` (0 = 4); max_specular > 0 takes the deep feature buffers; other
         arguments as render_denoised."""
-        p = self._params(width, height, spp, max_depth, tile, sample_offset, global_seed, chunk, False, kw.pop("variant", None), strips=strips, **kw)
-        p.flags |= flags
-        p.precision = precision
-        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
-        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_denoised_var(self._h, C.byref(p), C.byref(d) if d is not None else None, batches, sigma_variance, max_specular, max_fuzz,
-                                          out.ctypes.data_as(_P), C.byref(st)))
-        return (out, _stats_dict(st)) if with_stats else out
+        p, d, out = self._composite(width, height, spp, max_depth, sample_offset, global_seed, chunk, flags, denoise, dict(kw, tile=tile, strips=strips),
+                                    precision=precision)
+        return _ret(out, _call(_lib.rt1w_render_denoised_var, self._h, p, d, batches, sigma_variance, max_specular, max_fuzz, out), with_stats)
 
     def accum_merge(self, acc, tile_sums, aov, batch_spp, x0=0, y0=0, keep_albedo=False, with_stats=False):
         """One rendered batch of a rectangle into an accumulator (rt1w_accum_merge): `acc` float64 [h, w, 8] (zeros = empty), `tile_sums`
         [tile_h, tile_w, 3] the raw sums of a render with out_sum=True, spp=batch_spp of the rectangle at (x0, y0), `aov` [h, w, 8] of the
         whole frame.  Returns the merged accumulator (a new array)."""
-        a, s, g, rect = _merge_args(acc, tile_sums, aov, x0, y0)
-        st = Stats()
-        _ck(_lib.rt1w_accum_merge(self._h, *rect, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, s.ctypes.data_as(_P), g.ctypes.data_as(_P),
-                                  a.ctypes.data_as(_P), C.byref(st)))
-        return (a, _stats_dict(st)) if with_stats else a
+        return self._entry(_lib.rt1w_accum_merge, _merge_prep(acc, tile_sums, aov, batch_spp, x0, y0, keep_albedo), with_stats)
 
     def accum_merge_device(self, d_acc, d_tile_sums, d_aov, width, height, rect, batch_spp, keep_albedo=False):
         """Same on device memory (int addresses); rect = (x0, y0, tile_w, tile_h).  Returns the stats dict."""
-        st = Stats()
-        _ck(_lib.rt1w_accum_merge_device(self._h, width, height, *rect, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, C.c_void_p(d_tile_sums),
-                                         C.c_void_p(d_aov), C.c_void_p(d_acc), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_accum_merge_device, self._h, width, height, *rect, batch_spp, _keep(keep_albedo), d_tile_sums, d_aov, d_acc)
 
     def accum_merge_tiles(self, acc, tile_sums, aov, batch_spp, tile, tiles, keep_albedo=False, with_stats=False):
         """One rendered batch of a LIST of square tiles into an accumulator in one launch (rt1w_accum_merge_tiles): `tile_sums`
         [n, tile, tile, 3] as render_tiles(out_sum=True) returns them, `tiles` its list.  Returns the merged accumulator (a new array)."""
-        a, s, g = _merge_tiles_args(acc, tile_sums, aov, tile, tiles)
-        rec, n = _tile_list(tiles)
-        st = Stats()
-        _ck(_lib.rt1w_accum_merge_tiles(self._h, a.shape[1], a.shape[0], tile, rec, n, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0,
-                                        s.ctypes.data_as(_P), g.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(st)))
-        return (a, _stats_dict(st)) if with_stats else a
+        return self._entry(_lib.rt1w_accum_merge_tiles, _merge_tiles_prep(acc, tile_sums, aov, batch_spp, tile, tiles, keep_albedo), with_stats)
 
     def accum_merge_tiles_device(self, d_acc, d_tile_sums, d_aov, width, height, tile, tiles, batch_spp, keep_albedo=False):
         """Same on device memory (int addresses); the list itself is host memory.  Returns the stats dict."""
-        rec, n = _tile_list(tiles)
-        st = Stats()
-        _ck(_lib.rt1w_accum_merge_tiles_device(self._h, width, height, tile, rec, n, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0,
-                                               C.c_void_p(d_tile_sums), C.c_void_p(d_aov), C.c_void_p(d_acc), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_accum_merge_tiles_device, self._h, width, height, tile, *_tile_list(tiles), batch_spp, _keep(keep_albedo), d_tile_sums,
+                     d_aov, d_acc)
 
     def accum_resolve(self, acc, batch_spp, with_stats=False):
         """(frame [h, w, 3], var [h, w], spp [h, w]) of an accumulator (rt1w_accum_resolve)."""
-        a = _accum_of(acc)
-        frame, var, spp = np.empty(a.shape[:2] + (3,)), np.empty(a.shape[:2]), np.empty(a.shape[:2])
-        st = Stats()
-        _ck(_lib.rt1w_accum_resolve(self._h, a.shape[1], a.shape[0], batch_spp, a.ctypes.data_as(_P), frame.ctypes.data_as(_P), var.ctypes.data_as(_P),
-                                    spp.ctypes.data_as(_P), C.byref(st)))
-        return (frame, var, spp, _stats_dict(st)) if with_stats else (frame, var, spp)
+        return self._entry(_lib.rt1w_accum_resolve, _accum_resolve_prep(acc, batch_spp), with_stats)
 
     def accum_resolve_device(self, d_acc, d_frame, d_var, d_spp, width, height, batch_spp):
-        st = Stats()
-        _ck(_lib.rt1w_accum_resolve_device(self._h, width, height, batch_spp, C.c_void_p(d_acc), C.c_void_p(d_frame), C.c_void_p(d_var),
-                                           C.c_void_p(d_spp), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_accum_resolve_device, self._h, width, height, batch_spp, d_acc, d_frame, d_var, d_spp)
 
     def accum_tile_error(self, acc, tile, with_stats=False):
         """The error of every tile of an accumulator (rt1w_accum_tile_error): float64 [ceil(h / tile), ceil(w / tile)]."""
-        a = _accum_of(acc)
-        tx, ty = _tiles_of(a.shape[1], a.shape[0], max(int(tile), 1))
-        err = np.empty((ty, tx))
-        st = Stats()
-        _ck(_lib.rt1w_accum_tile_error(self._h, a.shape[1], a.shape[0], tile, a.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
-        return (err, _stats_dict(st)) if with_stats else err
+        return self._entry(_lib.rt1w_accum_tile_error, _tile_error_prep(_accum_of(acc), tile), with_stats)
 
     def accum_tile_error_device(self, d_acc, d_err, width, height, tile):
-        st = Stats()
-        _ck(_lib.rt1w_accum_tile_error_device(self._h, width, height, tile, C.c_void_p(d_acc), C.c_void_p(d_err), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_accum_tile_error_device, self._h, width, height, tile, d_acc, d_err)
 
     def render_adaptive(self, width, height, adaptive=None, denoise=None, filter=False, sigma_variance=0.0, max_depth=50, sample_offset=0,
                         global_seed=0, chunk=0, tile=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
         """Adaptive sampling in one call (rt1w_render_adaptive): (frame [h, w, 3], spp [h, w]).  `adaptive`: dict of the keywords of
         adaptive_params, None = defaults; `filter` or a `denoise` dict (keywords of Context.denoise_var) adds the variance-guided filter."""
-        p = self._params(width, height, 0, max_depth, tile, sample_offset, global_seed, chunk, False, kw.pop("variant", None), strips=strips, **kw)
-        p.flags |= flags
-        p.precision = precision
-        a = adaptive_params(**(adaptive or {}))
-        d = _denoise_params(0, 0, **(denoise or {})) if (filter or denoise is not None) else None
-        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
-        spp = np.empty((p.tile_h, p.tile_w), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_adaptive(self._h, C.byref(p), C.byref(a), C.byref(d) if d is not None else None, sigma_variance, out.ctypes.data_as(_P),
-                                      spp.ctypes.data_as(_P), C.byref(st)))
-        return (out, spp, _stats_dict(st)) if with_stats else (out, spp)
+        p, d, out = self._composite(width, height, 0, max_depth, sample_offset, global_seed, chunk, flags, denoise, dict(kw, tile=tile, strips=strips),
+                                    filter=filter, precision=precision)
+        spp = np.empty(out.shape[:2], dtype=np.float64)
+        return _ret((out, spp), _call(_lib.rt1w_render_adaptive, self._h, p, adaptive_params(**(adaptive or {})), d, sigma_variance, out, spp), with_stats)
 
     def halves_resolve(self, acc_a, acc_b, batch_spp, with_stats=False):
         """(frame [h, w, 3], var [h, w], half_a [h, w, 3], half_b [h, w, 3], spp [h, w]) of two accumulators taken as the halves of one
         frame (rt1w_halves_resolve)."""
-        a, b = _accum_of(acc_a), _accum_of(acc_b)
-        if a.shape != b.shape:
-            raise ValueError("acc_a and acc_b must have one shape")
-        hw = a.shape[:2]
-        frame, var, ha, hb, spp = np.empty(hw + (3,)), np.empty(hw), np.empty(hw + (3,)), np.empty(hw + (3,)), np.empty(hw)
-        st = Stats()
-        _ck(_lib.rt1w_halves_resolve(self._h, a.shape[1], a.shape[0], batch_spp, a.ctypes.data_as(_P), b.ctypes.data_as(_P), frame.ctypes.data_as(_P),
-                                     var.ctypes.data_as(_P), ha.ctypes.data_as(_P), hb.ctypes.data_as(_P), spp.ctypes.data_as(_P), C.byref(st)))
-        return (frame, var, ha, hb, spp, _stats_dict(st)) if with_stats else (frame, var, ha, hb, spp)
+        return self._entry(_lib.rt1w_halves_resolve, _halves_resolve_prep(acc_a, acc_b, batch_spp), with_stats)
 
     def halves_resolve_device(self, d_acc_a, d_acc_b, d_frame, d_var, d_half_a, d_half_b, d_spp, width, height, batch_spp):
         """Same on device memory (int addresses).  Returns the stats dict."""
-        st = Stats()
-        _ck(_lib.rt1w_halves_resolve_device(self._h, width, height, batch_spp, C.c_void_p(d_acc_a), C.c_void_p(d_acc_b), C.c_void_p(d_frame),
-                                            C.c_void_p(d_var), C.c_void_p(d_half_a), C.c_void_p(d_half_b), C.c_void_p(d_spp), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_halves_resolve_device, self._h, width, height, batch_spp, d_acc_a, d_acc_b, d_frame, d_var, d_half_a, d_half_b, d_spp)
 
     def denoise_var_halves(self, frame, aov, var, half_a, half_b, sigma_variance=0.0, with_stats=False, **kw):
         """The variance-guided filter carrying the frame's two halves (rt1w_denoise_var_halves): (out [h, w, 3] -- the bits of denoise_var --
         and err_px [h, w], the half-buffer error of the filtered frame).  kw as denoise_var."""
-        return self._halves_filter(_lib.rt1w_denoise_var_halves, frame, aov, var, half_a, half_b, sigma_variance, with_stats, kw)
+        return self._entry(_lib.rt1w_denoise_var_halves, _halves_filter_prep(frame, aov, var, half_a, half_b, sigma_variance, kw), with_stats)
 
     def denoise_cross(self, frame, aov, var, half_a, half_b, sigma_variance=0.0, with_stats=False, **kw):
         """The two halves, each filtered with the other's colour term (rt1w_denoise_cross): (out [h, w, 3], the mean of the two filtered
         halves -- NOT the bits of denoise_var -- and err_px [h, w], their squared difference as the error of that frame).  kw as denoise_var."""
-        return self._halves_filter(_lib.rt1w_denoise_cross, frame, aov, var, half_a, half_b, sigma_variance, with_stats, kw)
-
-    def _halves_filter(self, fn, frame, aov, var, half_a, half_b, sigma_variance, with_stats, kw):
-        f, a = _frame_and_aov(frame, aov)
-        v = _variance_of(var, f)
-        ha, hb = _halves_of(f, half_a, half_b)
-        p = _denoise_params(f.shape[1], f.shape[0], **kw)
-        out, err = np.empty_like(f), np.empty(f.shape[:2])
-        st = Stats()
-        _ck(fn(self._h, C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), ha.ctypes.data_as(_P), hb.ctypes.data_as(_P),
-               sigma_variance, out.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
-        return (out, err, _stats_dict(st)) if with_stats else (out, err)
+        return self._entry(_lib.rt1w_denoise_cross, _halves_filter_prep(frame, aov, var, half_a, half_b, sigma_variance, kw), with_stats)
 
     def denoise_var_halves_device(self, d_frame, d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, width, height, sigma_variance=0.0, **kw):
         """Same on device memory (int addresses); d_out may equal d_frame.  Returns the stats dict."""
-        p = _denoise_params(width, height, **kw)
-        st = Stats()
-        _ck(_lib.rt1w_denoise_var_halves_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_var), C.c_void_p(d_half_a),
-                                                C.c_void_p(d_half_b), sigma_variance, C.c_void_p(d_out), C.c_void_p(d_err_px), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_denoise_var_halves_device, self._h, _denoise_params(width, height, **kw), d_frame, d_aov, d_var, d_half_a, d_half_b,
+                     sigma_variance, d_out, d_err_px)
 
     def denoise_cross_device(self, d_frame, d_aov, d_var, d_half_a, d_half_b, d_out, d_err_px, width, height, sigma_variance=0.0, **kw):
         """Context.denoise_cross on device memory (int addresses); d_out may equal d_frame.  Returns the stats dict."""
-        p = _denoise_params(width, height, **kw)
-        st = Stats()
-        _ck(_lib.rt1w_denoise_cross_device(self._h, C.byref(p), C.c_void_p(d_frame), C.c_void_p(d_aov), C.c_void_p(d_var), C.c_void_p(d_half_a),
-                                           C.c_void_p(d_half_b), sigma_variance, C.c_void_p(d_out), C.c_void_p(d_err_px), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_denoise_cross_device, self._h, _denoise_params(width, height, **kw), d_frame, d_aov, d_var, d_half_a, d_half_b,
+                     sigma_variance, d_out, d_err_px)
 
     def tile_error_map(self, err_px, tile, with_stats=False):
         """The tile means of a per-pixel error map (rt1w_tile_error_map): float64 [ceil(h / tile), ceil(w / tile)]."""
-        e = _error_map_of(err_px)
-        tx, ty = _tiles_of(e.shape[1], e.shape[0], max(int(tile), 1))
-        err = np.empty((ty, tx))
-        st = Stats()
-        _ck(_lib.rt1w_tile_error_map(self._h, e.shape[1], e.shape[0], tile, e.ctypes.data_as(_P), err.ctypes.data_as(_P), C.byref(st)))
-        return (err, _stats_dict(st)) if with_stats else err
+        return self._entry(_lib.rt1w_tile_error_map, _tile_error_prep(_error_map_of(err_px), tile), with_stats)
 
     def tile_error_map_device(self, d_err_px, d_err, width, height, tile):
-        st = Stats()
-        _ck(_lib.rt1w_tile_error_map_device(self._h, width, height, tile, C.c_void_p(d_err_px), C.c_void_p(d_err), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_tile_error_map_device, self._h, width, height, tile, d_err_px, d_err)
 
     def render_adaptive_filtered(self, width, height, adaptive=None, denoise=None, sigma_variance=0.0, max_depth=50, sample_offset=0, global_seed=0,
                                  chunk=0, tile=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
@@ -1179,68 +1183,39 @@ class Context:
 
     def _render_adaptive_halves(self, fn, width, height, adaptive, denoise, sigma_variance, max_depth, sample_offset, global_seed, chunk, tile, flags,
                                 strips, precision, with_stats, kw):
-        p = self._params(width, height, 0, max_depth, tile, sample_offset, global_seed, chunk, False, kw.pop("variant", None), strips=strips, **kw)
-        p.flags |= flags
-        p.precision = precision
-        a = adaptive_params(**(adaptive or {}))
-        d = _denoise_params(0, 0, **denoise) if denoise is not None else None
-        out = np.empty((p.tile_h, p.tile_w, 3), dtype=np.float64)
-        spp = np.empty((p.tile_h, p.tile_w), dtype=np.float64)
-        err = np.empty((p.tile_h, p.tile_w), dtype=np.float64)
-        st = Stats()
-        _ck(fn(self._h, C.byref(p), C.byref(a), C.byref(d) if d is not None else None, sigma_variance, out.ctypes.data_as(_P), spp.ctypes.data_as(_P),
-               err.ctypes.data_as(_P), C.byref(st)))
-        return (out, spp, err, _stats_dict(st)) if with_stats else (out, spp, err)
+        p, d, out = self._composite(width, height, 0, max_depth, sample_offset, global_seed, chunk, flags, denoise, dict(kw, tile=tile, strips=strips),
+                                    precision=precision)
+        spp, err = np.empty(out.shape[:2], dtype=np.float64), np.empty(out.shape[:2], dtype=np.float64)
+        return _ret((out, spp, err), _call(fn, self._h, p, adaptive_params(**(adaptive or {})), d, sigma_variance, out, spp, err), with_stats)
 
     def render_aov_tiles(self, width, height, spp, tile, tiles, sample_offset=0, global_seed=0, variant=None, flags=0, strips=None, f32=False,
                          with_stats=False):
         """First-hit feature SUMS of a list of square tiles in one launch (rt1w_render_aov_tiles): `tiles` = Tile objects or (x0, y0,
         sample_offset) tuples.  Returns float64 [n, tile, tile, 8]: the sums of albedo rgb, normal xyz, t |d| over the hits and the hit count;
         tile k's row 0 = image row y0_k, pixels beyond the frame's edge are +0.0.  with_stats: returns (array, stats dict)."""
-        p = self._params(width, height, spp, 0, None, sample_offset, global_seed, 0, False, variant, strips=strips, f32=f32)
-        p.flags |= flags
-        rec, n = _tile_list(tiles)
-        out = np.empty((n, tile, tile, AOV_CHANNELS), dtype=np.float64)
-        st = Stats()
-        _ck(_lib.rt1w_render_aov_tiles(self._h, C.byref(p), tile, rec, n, out.ctypes.data_as(_P), C.byref(st)))
-        return (out, _stats_dict(st)) if with_stats else out
+        return self._entry(_lib.rt1w_render_aov_tiles,
+                           _aov_tiles_prep(width, height, spp, tile, tiles, sample_offset, global_seed, variant, flags, strips, f32), with_stats)
 
     def render_aov_tiles_device(self, d_ptr, width, height, spp, tile, tiles, sample_offset=0, global_seed=0, variant=None):
         """Same, into device memory `d_ptr` (int address) of n * tile * tile * 8 doubles; the list itself is host memory.  Returns the stats."""
-        p = self._params(width, height, spp, 0, None, sample_offset, global_seed, 0, False, variant)
-        rec, n = _tile_list(tiles)
-        st = Stats()
-        _ck(_lib.rt1w_render_aov_tiles_device(self._h, C.byref(p), tile, rec, n, C.c_void_p(d_ptr), C.byref(st)))
-        return _stats_dict(st)
+        p = self._params(width, height, spp, 0, None, sample_offset, global_seed, 0, False, variant=variant)
+        return _call(_lib.rt1w_render_aov_tiles_device, self._h, p, tile, *_tile_list(tiles), d_ptr)
 
     def guides_merge_tiles(self, gacc, tile_sums, spp, tile, tiles, with_stats=False):
         """The feature sums of a list of disjoint tiles into a guide accumulator (rt1w_guides_merge_tiles): `gacc` float64 [h, w, 9] (zeros =
         empty), `tile_sums` [n, tile, tile, 8] as render_aov_tiles returns them for `spp` samples.  Returns the merged accumulator (a new array)."""
-        g, s = _guides_merge_args(gacc, tile_sums, tile, tiles)
-        rec, n = _tile_list(tiles)
-        st = Stats()
-        _ck(_lib.rt1w_guides_merge_tiles(self._h, g.shape[1], g.shape[0], tile, rec, n, spp, s.ctypes.data_as(_P), g.ctypes.data_as(_P), C.byref(st)))
-        return (g, _stats_dict(st)) if with_stats else g
+        return self._entry(_lib.rt1w_guides_merge_tiles, _guides_merge_prep(gacc, tile_sums, spp, tile, tiles), with_stats)
 
     def guides_merge_tiles_device(self, d_gacc, d_tile_sums, width, height, tile, tiles, spp):
         """Same on device memory (int addresses); the list itself is host memory.  Returns the stats dict."""
-        rec, n = _tile_list(tiles)
-        st = Stats()
-        _ck(_lib.rt1w_guides_merge_tiles_device(self._h, width, height, tile, rec, n, spp, C.c_void_p(d_tile_sums), C.c_void_p(d_gacc), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_guides_merge_tiles_device, self._h, width, height, tile, *_tile_list(tiles), spp, d_tile_sums, d_gacc)
 
     def guides_resolve(self, gacc, with_stats=False):
         """The feature buffers [h, w, 8] of a guide accumulator, in render_aov's layout (rt1w_guides_resolve)."""
-        g = _guides_of(gacc)
-        aov = np.empty(g.shape[:2] + (AOV_CHANNELS,))
-        st = Stats()
-        _ck(_lib.rt1w_guides_resolve(self._h, g.shape[1], g.shape[0], g.ctypes.data_as(_P), aov.ctypes.data_as(_P), C.byref(st)))
-        return (aov, _stats_dict(st)) if with_stats else aov
+        return self._entry(_lib.rt1w_guides_resolve, _guides_resolve_prep(gacc), with_stats)
 
     def guides_resolve_device(self, d_gacc, d_aov, width, height):
-        st = Stats()
-        _ck(_lib.rt1w_guides_resolve_device(self._h, width, height, C.c_void_p(d_gacc), C.c_void_p(d_aov), C.byref(st)))
-        return _stats_dict(st)
+        return _call(_lib.rt1w_guides_resolve_device, self._h, width, height, d_gacc, d_aov)
 
     def render_adaptive_guided(self, width, height, adaptive=None, denoise=None, sigma_variance=0.0, max_depth=50, sample_offset=0, global_seed=0,
                                chunk=0, tile=None, flags=0, strips=None, precision=0, with_stats=False, **kw):
@@ -1315,119 +1290,59 @@ def aov_host(scene, width, height, spp, tile=None, sample_offset=0, global_seed=
     """CPU twin of Context.render_aov (librt1w_lab.so: rt1w_lab_aov_host, the same rt_aov.h built for the host): the array the GPU
     must equal bit for bit.  No GPU needed.  max_specular not None: the twin of Context.render_aov_deep (rt1w_lab_aov_deep_host,
     rt_aov_deep.h); with_stats then returns (array, {"segments": rays traced, "lengths": uint8 [tile_h, tile_w, spp] rays per sample})."""
-    lab = load_lab()
-    p = Context._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant, strips=strips)
-    out = np.empty((p.tile_h, p.tile_w, AOV_CHANNELS), dtype=np.float64)
+    args, out = _aov_prep(() if max_specular is None else (max_specular, max_fuzz), width, height, spp, tile, sample_offset, global_seed, variant, strips)
     if max_specular is None:
-        f = lab.rt1w_lab_aov_host
-        f.restype = C.c_int
-        f.argtypes = [_P, C.POINTER(RenderParams), _P]
-        rc = f(scene._h, C.byref(p), out.ctypes.data_as(_P))
-        if rc < 0:
-            raise Rt1wError(rc, "rt1w_lab_aov_host")
-        return (out, {"segments": p.tile_w * p.tile_h * spp}) if with_stats else out
-    f = lab.rt1w_lab_aov_deep_host
-    f.restype = C.c_int
-    f.argtypes = [_P, C.POINTER(RenderParams), C.c_uint32, C.c_double, _P, C.POINTER(C.c_uint64), _P]
+        _call_lab("rt1w_lab_aov_host", scene._h, *args)
+        return (out, {"segments": out.shape[0] * out.shape[1] * spp}) if with_stats else out
     seg = C.c_uint64()
-    lengths = np.zeros((p.tile_h, p.tile_w, spp), dtype=np.uint8) if with_stats else None
-    rc = f(scene._h, C.byref(p), max_specular, max_fuzz, out.ctypes.data_as(_P), C.byref(seg), lengths.ctypes.data_as(_P) if with_stats else None)
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_aov_deep_host")
+    lengths = np.zeros(out.shape[:2] + (spp,), dtype=np.uint8) if with_stats else None
+    _call_lab("rt1w_lab_aov_deep_host", scene._h, *args, C.byref(seg), lengths)
     return (out, {"segments": seg.value, "lengths": lengths}) if with_stats else out
 
 
 def aov_tiles_host(scene, width, height, spp, tile, tiles, sample_offset=0, global_seed=0, variant=None, flags=0, strips=None, f32=False):
     """CPU twin of Context.render_aov_tiles (librt1w_lab.so: rt1w_lab_aov_tiles_host, rt_aov_tiles.h built for the host): the sums
     [n, tile, tile, 8] the GPU must equal bit for bit.  No GPU needed."""
-    fn = load_lab().rt1w_lab_aov_tiles_host
-    fn.restype = C.c_int
-    fn.argtypes = [_P, C.POINTER(RenderParams), C.c_uint32, _P, C.c_uint32, _P]
-    p = Context._params(width, height, spp, 0, None, sample_offset, global_seed, 0, False, variant, strips=strips, f32=f32)
-    p.flags |= flags
-    rec, n = _tile_list(tiles)
-    out = np.empty((n, tile, tile, AOV_CHANNELS), dtype=np.float64)
-    rc = fn(scene._h, C.byref(p), tile, rec, n, out.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_aov_tiles_host")
+    args, out = _aov_tiles_prep(width, height, spp, tile, tiles, sample_offset, global_seed, variant, flags, strips, f32)
+    _call_lab("rt1w_lab_aov_tiles_host", scene._h, *args)
     return out
 
 
 def guides_merge_tiles_host(gacc, tile_sums, spp, tile, tiles):
     """CPU twin of Context.guides_merge_tiles (librt1w_lab.so: rt1w_lab_guides_merge_tiles_host)."""
-    fn = load_lab().rt1w_lab_guides_merge_tiles_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32] * 3 + [_P] + [C.c_uint32] * 2 + [_P, _P]
-    g, s = _guides_merge_args(gacc, tile_sums, tile, tiles)
-    rec, n = _tile_list(tiles)
-    rc = fn(g.shape[1], g.shape[0], tile, rec, n, spp, s.ctypes.data_as(_P), g.ctypes.data_as(_P))
-    if rc != 0:
-        raise Rt1wError(rc, "rt1w_lab_guides_merge_tiles_host")
-    return g
+    return _twin("rt1w_lab_guides_merge_tiles_host", _guides_merge_prep(gacc, tile_sums, spp, tile, tiles))
 
 
 def guides_resolve_host(gacc):
     """CPU twin of Context.guides_resolve (rt1w_lab_guides_resolve_host): the feature buffers [h, w, 8]."""
-    fn = load_lab().rt1w_lab_guides_resolve_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32] * 2 + [_P] * 2
-    g = _guides_of(gacc)
-    aov = np.empty(g.shape[:2] + (AOV_CHANNELS,))
-    rc = fn(g.shape[1], g.shape[0], g.ctypes.data_as(_P), aov.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_guides_resolve_host")
-    return aov
+    return _twin("rt1w_lab_guides_resolve_host", _guides_resolve_prep(gacc))
 
 
 def temporal_host(cur_frame, cur_aov, cur_cam, prev_hist, prev_len, prev_aov, prev_cam, with_record=False, **kw):
     """CPU twin of Context.temporal_accumulate (librt1w_lab.so: rt1w_lab_temporal_host, the same rt_temporal.h built for the host):
     the (hist, len, frame_out) the GPU must equal bit for bit.  No GPU needed.  with_record: also the tests' record [h, w, 8] of every
     pixel -- fx, fy, the four taps' weights (0 where a tap is not valid), their sum, 1 / 0 history."""
-    fn = load_lab().rt1w_lab_temporal_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(TemporalParams), _P, _P, C.POINTER(Camera), _P, _P, _P, C.POINTER(Camera), _P, _P, _P, _P]
-    f, a, h, n, q = _temporal_args(cur_frame, cur_aov, prev_hist, prev_len, prev_aov)
-    p = _temporal_params(f.shape[1], f.shape[0], **kw)
-    hist, ln, out = np.empty_like(f), np.empty_like(n), np.empty_like(f)
-    rec = np.zeros(f.shape[:2] + (8,)) if with_record else None
-    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(Camera.of(cur_cam)), h.ctypes.data_as(_P), n.ctypes.data_as(_P),
-            q.ctypes.data_as(_P), C.byref(Camera.of(prev_cam)), hist.ctypes.data_as(_P), ln.ctypes.data_as(_P), out.ctypes.data_as(_P),
-            rec.ctypes.data_as(_P) if with_record else None)
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_temporal_host")
-    return (hist, ln, out, rec) if with_record else (hist, ln, out)
+    return _temporal_twin("rt1w_lab_temporal_host", _temporal_prep(cur_frame, cur_aov, cur_cam, prev_hist, None, prev_len, prev_aov, prev_cam, kw),
+                          with_record)
 
 
 def temporal_moments_host(cur_frame, cur_aov, cur_cam, prev_hist, prev_m2, prev_len, prev_aov, prev_cam, with_record=False, **kw):
     """CPU twin of Context.temporal_moments (librt1w_lab.so: rt1w_lab_temporal_moments_host): the (hist, m2, len, frame_out) the GPU must
     equal bit for bit.  No GPU needed.  with_record: also temporal_host's record [h, w, 8]."""
-    fn = load_lab().rt1w_lab_temporal_moments_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(TemporalParams), _P, _P, C.POINTER(Camera), _P, _P, _P, _P, C.POINTER(Camera), _P, _P, _P, _P, _P]
-    f, a, h, m, n, q = _moments_args(cur_frame, cur_aov, prev_hist, prev_m2, prev_len, prev_aov)
-    p = _temporal_params(f.shape[1], f.shape[0], **kw)
-    hist, m2, ln, out = np.empty_like(f), np.empty_like(n), np.empty_like(n), np.empty_like(f)
-    rec = np.zeros(f.shape[:2] + (8,)) if with_record else None
-    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), C.byref(Camera.of(cur_cam)), h.ctypes.data_as(_P), m.ctypes.data_as(_P),
-            n.ctypes.data_as(_P), q.ctypes.data_as(_P), C.byref(Camera.of(prev_cam)), hist.ctypes.data_as(_P), m2.ctypes.data_as(_P),
-            ln.ctypes.data_as(_P), out.ctypes.data_as(_P), rec.ctypes.data_as(_P) if with_record else None)
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_temporal_moments_host")
-    return (hist, m2, ln, out, rec) if with_record else (hist, m2, ln, out)
+    return _temporal_twin("rt1w_lab_temporal_moments_host",
+                          _temporal_prep(cur_frame, cur_aov, cur_cam, prev_hist, prev_m2, prev_len, prev_aov, prev_cam, kw), with_record)
+
+
+def _temporal_twin(name, prep, with_record):
+    rec = np.zeros(prep[1][0].shape[:2] + (8,)) if with_record else None
+    out = _twin(name, prep, rec)
+    return out + (rec,) if with_record else out
 
 
 def temporal_variance_host(hist, m2, length, aov):
     """CPU twin of Context.temporal_variance (librt1w_lab.so: rt1w_lab_temporal_variance_host): the var [h, w] the GPU must equal bit
     for bit.  No GPU needed."""
-    fn = load_lab().rt1w_lab_temporal_variance_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]
-    h, m, n, a = _variance_args(hist, m2, length, aov)
-    var = np.empty_like(m)
-    rc = fn(h.shape[1], h.shape[0], h.ctypes.data_as(_P), m.ctypes.data_as(_P), n.ctypes.data_as(_P), a.ctypes.data_as(_P), var.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_temporal_variance_host")
-    return var
+    return _twin("rt1w_lab_temporal_variance_host", _temporal_variance_prep(hist, m2, length, aov))
 
 
 def scene_set_camera_host(scene, look_from, look_at, vup, vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1):
@@ -1435,194 +1350,79 @@ def scene_set_camera_host(scene, look_from, look_at, vup, vfov_deg, aspect_ratio
     scene's own camera record, so that the CPU twins and Scene.flat -- which build their view from the scene -- render the camera a
     live context would.  Everything made from the scene afterwards, a context too, sees a scene committed with these arguments;
     contexts made before keep the camera they copied."""
-    fn = load_lab().rt1w_lab_scene_set_camera
-    fn.restype = C.c_int
-    fn.argtypes = [_P] + _CAM_ARGS
-    rc = fn(scene._h, _v3(look_from), _v3(look_at), _v3(vup), vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1)
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_scene_set_camera")
+    _call_lab("rt1w_lab_scene_set_camera", scene._h, _v3(look_from), _v3(look_at), _v3(vup), vfov_deg, aspect_ratio, aperture, focus_dist, time0, time1)
 
 
 def scene_camera_host(scene):
     """The Camera of a scene's own record (librt1w_lab.so: rt1w_lab_scene_get_camera)."""
-    fn = load_lab().rt1w_lab_scene_get_camera
-    fn.restype = C.c_int
-    fn.argtypes = [_P, C.POINTER(Camera)]
     cam = Camera()
-    rc = fn(scene._h, C.byref(cam))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_scene_get_camera")
+    _call_lab("rt1w_lab_scene_get_camera", scene._h, cam)
     return cam
 
 
 def denoise_host(frame, aov, **kw):
     """CPU twin of Context.denoise (librt1w_lab.so: rt1w_lab_denoise_host, the same rt_denoise.h built for the host): the array the
     GPU must equal bit for bit.  No GPU needed."""
-    lab = load_lab()
-    fn = lab.rt1w_lab_denoise_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(DenoiseParams), _P, _P, _P]
-    f, a = _frame_and_aov(frame, aov)
-    p = _denoise_params(f.shape[1], f.shape[0], **kw)
-    out = np.empty_like(f)
-    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), out.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_denoise_host")
-    return out
+    return _twin("rt1w_lab_denoise_host", _denoise_prep(frame, aov, kw))
 
 
 def batch_variance_host(sums, aov, batch_spp, keep_albedo=False):
     """CPU twin of Context.batch_variance (librt1w_lab.so: rt1w_lab_batch_variance_host, rt_denoise_var.h built for the host): the
     (frame, var) the GPU must equal bit for bit.  No GPU needed."""
-    fn = load_lab().rt1w_lab_batch_variance_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P]
-    s, a = _sums_and_aov(sums, aov)
-    frame = np.empty(s.shape[1:], dtype=np.float64)
-    var = np.empty(s.shape[1:3], dtype=np.float64)
-    rc = fn(s.shape[2], s.shape[1], s.shape[0], batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, s.ctypes.data_as(_P), a.ctypes.data_as(_P),
-            frame.ctypes.data_as(_P), var.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_batch_variance_host")
-    return frame, var
+    return _twin("rt1w_lab_batch_variance_host", _batch_variance_prep(sums, aov, batch_spp, keep_albedo))
 
 
 def denoise_var_host(frame, aov, var, sigma_variance=0.0, **kw):
     """CPU twin of Context.denoise_var (librt1w_lab.so: rt1w_lab_denoise_var_host): the array the GPU must equal bit for bit."""
-    fn = load_lab().rt1w_lab_denoise_var_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(DenoiseParams), _P, _P, _P, C.c_double, _P]
-    f, a = _frame_and_aov(frame, aov)
-    v = _variance_of(var, f)
-    p = _denoise_params(f.shape[1], f.shape[0], **kw)
-    out = np.empty_like(f)
-    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), sigma_variance, out.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_denoise_var_host")
-    return out
+    return _twin("rt1w_lab_denoise_var_host", _denoise_var_prep(frame, aov, var, sigma_variance, kw))
 
 
 def accum_merge_host(acc, tile_sums, aov, batch_spp, x0=0, y0=0, keep_albedo=False):
     """CPU twin of Context.accum_merge (librt1w_lab.so: rt1w_lab_accum_merge_host): the accumulator the GPU must equal bit for bit."""
-    fn = load_lab().rt1w_lab_accum_merge_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32] * 8 + [_P, _P, _P]
-    a, s, g, rect = _merge_args(acc, tile_sums, aov, x0, y0)
-    rc = fn(*rect, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, s.ctypes.data_as(_P), g.ctypes.data_as(_P), a.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_accum_merge_host")
-    return a
+    return _twin("rt1w_lab_accum_merge_host", _merge_prep(acc, tile_sums, aov, batch_spp, x0, y0, keep_albedo))
 
 
 def accum_merge_tiles_host(acc, tile_sums, aov, batch_spp, tile, tiles, keep_albedo=False):
     """CPU twin of Context.accum_merge_tiles (librt1w_lab.so: rt1w_lab_accum_merge_tiles_host)."""
-    fn = load_lab().rt1w_lab_accum_merge_tiles_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32] * 3 + [_P] + [C.c_uint32] * 3 + [_P, _P, _P]
-    rec, n = _tile_list(tiles)
-    s, g = (np.ascontiguousarray(x, dtype=np.float64) for x in (tile_sums, aov))
-    a = _accum_of(acc).copy()
-    if n and (s.shape != (n, tile, tile, 3) or g.shape != a.shape[:2] + (AOV_CHANNELS,)):
-        raise ValueError("tile_sums must be [n_tiles, tile, tile, 3] and aov [h, w, 8]")
-    rc = fn(a.shape[1], a.shape[0], tile, rec, n, batch_spp, DENOISE_KEEP_ALBEDO if keep_albedo else 0, s.ctypes.data_as(_P), g.ctypes.data_as(_P),
-            a.ctypes.data_as(_P))
-    if rc != 0:
-        raise Rt1wError(rc, "rt1w_lab_accum_merge_tiles_host")
-    return a
+    return _twin("rt1w_lab_accum_merge_tiles_host", _merge_tiles_prep(acc, tile_sums, aov, batch_spp, tile, tiles, keep_albedo))
 
 
 def accum_resolve_host(acc, batch_spp):
     """CPU twin of Context.accum_resolve (rt1w_lab_accum_resolve_host): (frame, var, spp)."""
-    fn = load_lab().rt1w_lab_accum_resolve_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32] * 3 + [_P] * 4
-    a = _accum_of(acc)
-    frame, var, spp = np.empty(a.shape[:2] + (3,)), np.empty(a.shape[:2]), np.empty(a.shape[:2])
-    rc = fn(a.shape[1], a.shape[0], batch_spp, a.ctypes.data_as(_P), frame.ctypes.data_as(_P), var.ctypes.data_as(_P), spp.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_accum_resolve_host")
-    return frame, var, spp
+    return _twin("rt1w_lab_accum_resolve_host", _accum_resolve_prep(acc, batch_spp))
 
 
 def tile_error_host(acc, tile):
     """CPU twin of Context.accum_tile_error (rt1w_lab_tile_error_host)."""
-    fn = load_lab().rt1w_lab_tile_error_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32] * 3 + [_P] * 2
-    a = _accum_of(acc)
-    tx, ty = _tiles_of(a.shape[1], a.shape[0], max(int(tile), 1))
-    err = np.empty((ty, tx))
-    rc = fn(a.shape[1], a.shape[0], tile, a.ctypes.data_as(_P), err.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_tile_error_host")
-    return err
+    return _twin("rt1w_lab_tile_error_host", _tile_error_prep(_accum_of(acc), tile))
 
 
 def halves_resolve_host(acc_a, acc_b, batch_spp):
     """CPU twin of Context.halves_resolve (rt1w_lab_halves_resolve_host): (frame, var, half_a, half_b, spp)."""
-    fn = load_lab().rt1w_lab_halves_resolve_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32] * 3 + [_P] * 7
-    a, b = _accum_of(acc_a), _accum_of(acc_b)
-    if a.shape != b.shape:
-        raise ValueError("acc_a and acc_b must have one shape")
-    hw = a.shape[:2]
-    frame, var, ha, hb, spp = np.empty(hw + (3,)), np.empty(hw), np.empty(hw + (3,)), np.empty(hw + (3,)), np.empty(hw)
-    rc = fn(a.shape[1], a.shape[0], batch_spp, a.ctypes.data_as(_P), b.ctypes.data_as(_P), frame.ctypes.data_as(_P), var.ctypes.data_as(_P),
-            ha.ctypes.data_as(_P), hb.ctypes.data_as(_P), spp.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_halves_resolve_host")
-    return frame, var, ha, hb, spp
+    return _twin("rt1w_lab_halves_resolve_host", _halves_resolve_prep(acc_a, acc_b, batch_spp))
 
 
 def denoise_var_halves_host(frame, aov, var, half_a, half_b, sigma_variance=0.0, with_halves=False, **kw):
     """CPU twin of Context.denoise_var_halves (rt1w_lab_denoise_var_halves_host): (out, err_px), what the GPU must equal bit for bit;
     with_halves: (out, err_px, a', b'), the two filtered halves with the albedo back."""
-    fn = load_lab().rt1w_lab_denoise_var_halves_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, C.c_double, _P, _P, _P, _P]
-    f, a = _frame_and_aov(frame, aov)
-    v = _variance_of(var, f)
-    ha, hb = _halves_of(f, half_a, half_b)
-    p = _denoise_params(f.shape[1], f.shape[0], **kw)
-    out, err, fa, fb = np.empty_like(f), np.empty(f.shape[:2]), np.empty_like(f), np.empty_like(f)
-    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), ha.ctypes.data_as(_P), hb.ctypes.data_as(_P), sigma_variance,
-            out.ctypes.data_as(_P), err.ctypes.data_as(_P), fa.ctypes.data_as(_P) if with_halves else None, fb.ctypes.data_as(_P) if with_halves else None)
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_denoise_var_halves_host")
-    return (out, err, fa, fb) if with_halves else (out, err)
+    prep = _halves_filter_prep(frame, aov, var, half_a, half_b, sigma_variance, kw)
+    halves = (np.empty_like(prep[1][0]), np.empty_like(prep[1][0])) if with_halves else (None, None)
+    out = _twin("rt1w_lab_denoise_var_halves_host", prep, *halves)
+    return out + halves if with_halves else out
 
 
 def denoise_cross_host(frame, aov, var, half_a, half_b, sigma_variance=0.0, with_record=False, **kw):
     """CPU twin of Context.denoise_cross (rt1w_lab_denoise_cross_host): (out, err_px), what the GPU must equal bit for bit; with_record:
     (out, err_px, rec [h, w, 10]), the last level's record before the finish -- a' rgb, la', va', b' rgb, lb', vb', still demodulated."""
-    fn = load_lab().rt1w_lab_denoise_cross_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, C.c_double, _P, _P, _P]
-    f, a = _frame_and_aov(frame, aov)
-    v = _variance_of(var, f)
-    ha, hb = _halves_of(f, half_a, half_b)
-    p = _denoise_params(f.shape[1], f.shape[0], **kw)
-    out, err, rec = np.empty_like(f), np.empty(f.shape[:2]), np.empty(f.shape[:2] + (10,))
-    rc = fn(C.byref(p), f.ctypes.data_as(_P), a.ctypes.data_as(_P), v.ctypes.data_as(_P), ha.ctypes.data_as(_P), hb.ctypes.data_as(_P), sigma_variance,
-            out.ctypes.data_as(_P), err.ctypes.data_as(_P), rec.ctypes.data_as(_P) if with_record else None)
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_denoise_cross_host")
-    return (out, err, rec) if with_record else (out, err)
+    prep = _halves_filter_prep(frame, aov, var, half_a, half_b, sigma_variance, kw)
+    rec = np.empty(prep[1][0].shape[:2] + (10,)) if with_record else None
+    out = _twin("rt1w_lab_denoise_cross_host", prep, rec)
+    return out + (rec,) if with_record else out
 
 
 def tile_error_map_host(err_px, tile):
     """CPU twin of Context.tile_error_map (rt1w_lab_tile_error_map_host)."""
-    fn = load_lab().rt1w_lab_tile_error_map_host
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_uint32] * 3 + [_P] * 2
-    e = _error_map_of(err_px)
-    tx, ty = _tiles_of(e.shape[1], e.shape[0], max(int(tile), 1))
-    err = np.empty((ty, tx))
-    rc = fn(e.shape[1], e.shape[0], tile, e.ctypes.data_as(_P), err.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_tile_error_map_host")
-    return err
+    return _twin("rt1w_lab_tile_error_map_host", _tile_error_prep(_error_map_of(err_px), tile))
 
 
 def adaptive_select(width, height, err, m_per_tile, **adaptive):
@@ -1634,8 +1434,7 @@ def adaptive_select(width, height, err, m_per_tile, **adaptive):
     if e.ndim != 2 or m.shape != e.shape:
         raise ValueError("err and m_per_tile must be [tiles_y, tiles_x]")
     out = np.zeros(max(e.size, 1), dtype=np.uint32)
-    n = _ck(_lib.rt1w_adaptive_select(C.byref(a), e.shape[1], e.shape[0], width, height, e.ctypes.data_as(_P), m.ctypes.data_as(_P),
-                                      out.ctypes.data_as(_P), e.size))
+    n = _call(_lib.rt1w_adaptive_select, a, e.shape[1], e.shape[0], width, height, e, m, out, e.size, stats=False)
     return [int(t) for t in out[:n]]
 
 
@@ -1659,16 +1458,11 @@ F32_ELEMENTARY = ("sin", "cos", "atan2", "acos", "log")
 def f32_elementary(name, x, y=None, device=0):
     """Diagnostics (librt1w_lab.so: rt1w_lab_f32_elementary): the device's single-precision function `name` of F32_ELEMENTARY over
     float32 arrays, as the product's f32 kernels call it (atan2: of (x, y) = atan2f(x, y))."""
-    fn = load_lab().rt1w_lab_f32_elementary
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_int, C.c_int, _P, _P, C.c_uint64, _P]
     x = np.ascontiguousarray(x, dtype=np.float32)
     y = np.ascontiguousarray(y if y is not None else np.zeros_like(x), dtype=np.float32)
     assert x.shape == y.shape and x.ndim == 1 and x.size > 0
     out = np.empty_like(x)
-    rc = fn(device, F32_ELEMENTARY.index(name), x.ctypes.data_as(_P), y.ctypes.data_as(_P), x.size, out.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_f32_elementary")
+    _call_lab("rt1w_lab_f32_elementary", device, F32_ELEMENTARY.index(name), x, y, x.size, out)
     return out
 
 
@@ -1679,32 +1473,26 @@ def denoise_elementary(name, x, e=None, device=0):
     """Diagnostics (librt1w_lab.so: rt1w_lab_denoise_elementary): the function `name` of DENOISE_ELEMENTARY of csrc/rt_denoise.h over a
     float64 array -- rt_dn_falloff(x), or rt_dn_powi(x, e) with uint32 exponents e.  device 0: the host build (no GPU); 1: a kernel on
     GPU 0."""
-    fn = load_lab().rt1w_lab_denoise_elementary
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_int, C.c_int, _P, _P, C.c_uint64, _P]
     x = np.ascontiguousarray(x, dtype=np.float64)
     assert x.ndim == 1 and x.size > 0
     if e is not None:
         e = np.ascontiguousarray(np.broadcast_to(np.asarray(e, dtype=np.uint32), x.shape))
     out = np.empty_like(x)
-    rc = fn(device, DENOISE_ELEMENTARY.index(name), x.ctypes.data_as(_P), e.ctypes.data_as(_P) if e is not None else None, x.size,
-            out.ctypes.data_as(_P))
-    if rc < 0:
-        raise Rt1wError(rc, "rt1w_lab_denoise_elementary")
+    _call_lab("rt1w_lab_denoise_elementary", device, DENOISE_ELEMENTARY.index(name), x, e, x.size, out)
     return out
 
 
 def resolve(sums, spp):
     s = np.ascontiguousarray(sums, dtype=np.float64)
     out = np.empty_like(s)
-    _ck(_lib.rt1w_resolve(s.ctypes.data_as(_P), s.size // 3, spp, out.ctypes.data_as(_P)))
+    _call(_lib.rt1w_resolve, s, s.size // 3, spp, out, stats=False)
     return out
 
 
 def quantize(means):
     m = np.ascontiguousarray(means, dtype=np.float64)
     out = np.empty(m.shape, dtype=np.uint8)
-    _ck(_lib.rt1w_quantize(m.ctypes.data_as(_P), m.size, out.ctypes.data_as(_P)))
+    _call(_lib.rt1w_quantize, m, m.size, out, stats=False)
     return out
 
 
@@ -1712,8 +1500,7 @@ def format_ppm(means):
     """P3 text exactly as the reference prints it (src/main.rs:953,1003-1007); means[j, i, 3], row 0 = j = 0."""
     m = np.ascontiguousarray(means, dtype=np.float64)
     h, w = m.shape[:2]
-    n = int(_lib.rt1w_format_ppm(m.ctypes.data_as(_P), w, h, None, 0))
-    _ck(n)
+    n = _call(_lib.rt1w_format_ppm, m, w, h, None, 0, stats=False)
     buf = C.create_string_buffer(n + 1)
-    _ck(int(_lib.rt1w_format_ppm(m.ctypes.data_as(_P), w, h, buf, n + 1)))
+    _call(_lib.rt1w_format_ppm, m, w, h, buf, n + 1, stats=False)
     return buf.raw[:n].decode()

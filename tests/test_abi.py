@@ -40,6 +40,21 @@ def test_library_exports_nothing_else(rt):
     assert "rt1w_lab_trace" in lab_syms and "rt1w_lab_" not in out
 
 
+def test_lab_prototype_table_matches_the_header(rt):
+    """The binding declares the rt1w_lab_* functions it calls once, in its _LAB_SIGS table: csrc/walk_lab.h declares every one of them
+    with as many parameters as the table gives it argtypes, and the binding names no rt1w_lab_* function the table lacks.  The table
+    is read, not the live function objects: other tests re-type those."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "raytracing-1w_amd", "csrc", "walk_lab.h")).read(), flags=re.S)
+    assert len(rt._LAB_SIGS) >= 24
+    for name, argtypes in rt._LAB_SIGS.items():
+        assert "int " + name + "(" in hdr, f"{name} is not declared in csrc/walk_lab.h"
+        decl = hdr[hdr.index("int " + name + "("):]
+        assert decl[:decl.index(";")].count(",") + 1 == len(argtypes), name
+    src = open(os.path.join(ROOT, "raytracing-1w_amd", "__init__.py")).read()
+    called = set(re.findall(r"\"(rt1w_lab_[a-z0-9_]+)\"", src)) | set(re.findall(r"\.(rt1w_lab_[a-z0-9_]+)\(", src))
+    assert called == set(rt._LAB_SIGS), called ^ set(rt._LAB_SIGS)
+
+
 def test_integration_rust_block_declares_every_entry_of_the_header():
     """INTEGRATION.md section 2 claims to mirror include/rt1w.h one to one: the `extern "C"` block must name exactly the
     functions the header declares, and its #[repr(C)] structs must have the header's fields in the header's order."""
