@@ -338,9 +338,30 @@ RT_HD uint64_t rt_take_u64(RtRng& r) {
 RT_HD uint32_t rt_next_u32(RtRng& r) { rt_rng_reserve(r, 1u); return rt_take_u32(r); }
 RT_HD uint64_t rt_next_u64(RtRng& r) { rt_rng_reserve(r, rt_rng_need_u64(r)); return rt_take_u64(r); }
 
+/* The draw contract of the single-precision builds (RT_F32: `double` is float there).  rand's floats are half-open: `gen::<f32>()` is in
+ * [0, 1) and `gen_range(low..high)` in [low, high) AS FLOATS.  These builds keep the 64-bit draws (one u64 per draw: the f32 and f64
+ * frames consume the same words and share their paths; rand's own 24-bit shape would take one u32) and round them where they are
+ * assigned, so the half-open end has to be restored after that rounding:
+ *   unit draw   k 2^-53 rounds to 1.0f for every k >= 2^53 - 2^28 (2^28 of the 2^53 values: the tie at 1 - 2^-25 goes to the even 1.0f).
+ *               RT_UNIT caps the 64-bit value at 1 - 2^-24, the largest float below 1: what it returns rounds to the float nearest the
+ *               draw, except that 1.0f becomes 1 - 2^-24.  Only draws in [1 - 2^-25, 1) change.  With r2 = 1.0f the cosine lobe's
+ *               direction lies in the surface and its pdf and scattering pdf are both 0: 0 / 0, a NaN pixel (csrc/rt_core.h).
+ *   range draw  the retry compares with `high` after rounding: `res` is the working precision (`double`), as its callers keep it.
+ *               rt_range_from_bits and rt_take_pm1 have no retry of their own: their callers compare what they assigned
+ *               (rt_core.h: the rect light), or reject a candidate with a coordinate of 1.0f by its length (the unit sphere and disk).
+ * In the f64 builds RT_UNIT(x) is (x) and `double res` is the rt_f64 it was: the same statements (tests/test_f32_draws.py). */
+#undef RT_UNIT /* a translation unit that compiles this header twice (f64, then f32: csrc/rt_f32_kernels.h) gets each build its own */
+#if defined(RT_F32)
+#define RT_UNIT_MAX_F32 0.999999940395355224609375 /* 1 - 2^-24 */
+RT_HD rt_f64 rt_unit_f32(rt_f64 x) { return x < RT_UNIT_MAX_F32 ? x : RT_UNIT_MAX_F32; }
+#define RT_UNIT(x) rt_unit_f32(x)
+#else
+#define RT_UNIT(x) (x)
+#endif
+
 /* rand 0.8 `rng.gen::<f64>()`: 53 random bits scaled into [0,1). */
 RT_HD rt_f64 rt_gen_f64(RtRng& r) {
-    return (rt_f64)(rt_next_u64(r) >> 11) * (1.0 / 9007199254740992.0);
+    return RT_UNIT((rt_f64)(rt_next_u64(r) >> 11) * (1.0 / 9007199254740992.0));
 }
 /* rand 0.8 `rng.gen_range(low..high)` for f64 (UniformFloat::sample_single):
  * 52 mantissa bits -> [1,2) -> minus 1 -> *scale + low, retry if >= high. */
@@ -348,7 +369,7 @@ RT_HD rt_f64 rt_gen_range(RtRng& r, rt_f64 low, rt_f64 high) {
     rt_f64 scale = high - low;
     for (;;) {
         rt_f64 v12 = rt_u2d((rt_next_u64(r) >> 12) | 0x3FF0000000000000ull);
-        rt_f64 res = (v12 - 1.0) * scale + low;
+        double res = (v12 - 1.0) * scale + low;
         if (res < high) return res;
     }
 }
@@ -367,18 +388,18 @@ RT_HD uint32_t rt_gen_below(RtRng& r, uint32_t n) {
 }
 
 /* conversions of one 64-bit draw (rand 0.8 Standard f64 / UniformFloat) */
-RT_HD rt_f64 rt_f64_from_bits(uint64_t q) { return (rt_f64)(q >> 11) * (1.0 / 9007199254740992.0); }
+RT_HD rt_f64 rt_f64_from_bits(uint64_t q) { return RT_UNIT((rt_f64)(q >> 11) * (1.0 / 9007199254740992.0)); }
 RT_HD rt_f64 rt_range_from_bits(uint64_t q, rt_f64 low, rt_f64 high) {
     rt_f64 scale = high - low;
     rt_f64 v12 = rt_u2d((q >> 12) | 0x3FF0000000000000ull);
     return (v12 - 1.0) * scale + low;
 }
 /* ---- the same shapes over reserved words (device core; see rt_rng_reserve) ---- */
-RT_HD rt_f64 rt_take_f64(RtRng& r) { return (rt_f64)(rt_take_u64(r) >> 11) * (1.0 / 9007199254740992.0); }
+RT_HD rt_f64 rt_take_f64(RtRng& r) { return RT_UNIT((rt_f64)(rt_take_u64(r) >> 11) * (1.0 / 9007199254740992.0)); }
 RT_HD rt_f64 rt_take_range(RtRng& r, rt_f64 low, rt_f64 high) {
     rt_f64 scale = high - low;
     rt_f64 v12 = rt_u2d((rt_take_u64(r) >> 12) | 0x3FF0000000000000ull);
-    rt_f64 res = (v12 - 1.0) * scale + low;
+    double res = (v12 - 1.0) * scale + low; /* the working precision: the f32 build compares what its caller will hold */
     while (!(res < high)) { /* rounding pushed the value onto `high`: draw again (checked) */
         v12 = rt_u2d((rt_next_u64(r) >> 12) | 0x3FF0000000000000ull);
         res = (v12 - 1.0) * scale + low;

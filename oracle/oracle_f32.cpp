@@ -5,9 +5,13 @@
  * statistical by nature.  How the switch is thrown: every `double` of oracle.cpp and include/rt1w_num.h becomes `float` (the same
  * preprocessor switch the device build uses, RT_F32), so every vector, ray, hit record, box, camera, colour and pdf of the restatement
  * is f32.  What stays 64-bit, stated so that nobody mistakes this for a bit-level model of a Rust f32 build:
- *   - generator word -> number conversions: the f64 draw of rand 0.8's shapes (rt_gen_f64, rt_gen_range), rounded to f32 where it is
- *     assigned -- exactly what context_f32.hip does (rand's own f32 shapes, 24-bit draws from ONE u32, would consume the word stream
- *     differently and the f32 frame would stop sharing its paths with the f64 frame);
+ *   - generator word -> number conversions: the f64 draw of rand 0.8's shapes (rt_gen_f64, rt_gen_range) from ONE u64, under the draw
+ *     contract of the f32 builds (include/rt1w_num.h): a unit draw is the float nearest k 2^-53, except that 1.0f becomes 1 - 2^-24;
+ *     a range draw is compared with `high` after it is rounded to float and drawn again when it reached it.  That is rand's RANGE
+ *     contract -- gen::<f32>() in [0, 1), gen_range(low..high) in [low, high), as floats -- with the product's WORD CONSUMPTION, not
+ *     rand's 24-bit shape: rand's own f32 draws take one u32 each, which would consume the word stream differently, and the f32 frame
+ *     would stop sharing its paths with the f64 frame.  The rule is the header's, so this oracle and context_f32.hip follow it together;
+ *     what holds it to something that is not the project's is tests/test_f32_draws.py (Python integers and numpy on the expected side);
  *   - the internals of sin / cos / tan / acos / atan2 / ln (include/rt1w_num.h, spelled rt_f64), rounded once;
  *   - untyped literals are C++ doubles: a subexpression that contains one is evaluated in f64 and rounded on assignment (a single
  *     + - * / of f32 operands evaluated in f64 and rounded is the correctly rounded f32 result; longer chains can differ in the last

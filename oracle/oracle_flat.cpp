@@ -324,8 +324,8 @@ extern "C" int orcflat_walk_table_check(const void* nodes_, uint32_t n_nodes, ui
 
 #if !defined(RT_RNG_REFSTREAM)
 /* Every consumer of a uniform draw in the core, fed ONE chosen draw: the generator's buffer is loaded so that each 64-bit take returns
- * `bits` (all ones: the largest draw, 1 - 2^-53, which the f32 build rounds to 1.0f -- a value rand's own f32 shapes never return;
- * 0: the smallest).  out[12], in 64 bits whatever the build: 0-2 rt_random_cosine_direction, 3-5 rt_random_to_sphere(0.5, 4),
+ * `bits` (all ones: the largest draw, 1 - 2^-53, which would round to 1.0f -- a value rand's own f32 shapes never return -- and which
+ * the f32 build's draw contract, include/rt1w_num.h, makes 1 - 2^-24; 0: the smallest).  out[12], in 64 bits whatever the build: 0-2 rt_random_cosine_direction, 3-5 rt_random_to_sphere(0.5, 4),
  * 6 the light rectangle's coordinate in [213, 343), 7 the free flight -100 ln(r), 8 the draw as the Schlick test compares it,
  * 9-10 rt_random_in_unit_disk (first try from `bits`, further tries from the stream), 11 the shutter time in [0, 1) */
 extern "C" void orcflat_draw_probe(uint64_t bits, rt_f64* out) {

@@ -340,6 +340,7 @@ _LAB_SIGS = {
     "rt1w_lab_denoise_elementary": [_I, _I, _P, _P, _N, _P],
     "rt1w_lab_f32_exact": [_I],
     "rt1w_lab_f32_elementary": [_I, _I, _P, _P, _N, _P],
+    "rt1w_lab_f32_draws": [_I, _I, _P, C.c_float, C.c_float, _N, _P],
 }
 
 
@@ -1463,6 +1464,22 @@ def f32_elementary(name, x, y=None, device=0):
     assert x.shape == y.shape and x.ndim == 1 and x.size > 0
     out = np.empty_like(x)
     _call_lab("rt1w_lab_f32_elementary", device, F32_ELEMENTARY.index(name), x, y, x.size, out)
+    return out
+
+
+F32_DRAWS = ("unit", "range_single", "take_range", "take_unit", "gen_unit", "gen_range", "pm1")
+
+
+def f32_draws(name, words, lo=0.0, hi=1.0, device=0):
+    """Diagnostics (librt1w_lab.so: rt1w_lab_f32_draws): the single-precision builds' conversion `name` of F32_DRAWS of 64-bit generator
+    words into float32 -- "unit": the unit draw; "range_single": the range draw [lo, hi) with one take and no retry; "take_range" /
+    "gen_range": the retrying range draws over a stream of the word and then the word 0 (so a rejected word comes back as lo);
+    "take_unit" / "gen_unit": the unit draw's other two spellings; "pm1": the samplers' (-1, 1).  device 0: the host build (no GPU);
+    1: one lane per word on GPU 0."""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    assert w.ndim == 1 and w.size > 0
+    out = np.empty(w.shape, dtype=np.float32)
+    _call_lab("rt1w_lab_f32_draws", device, F32_DRAWS.index(name), w, lo, hi, w.size, out)
     return out
 
 

@@ -24,6 +24,13 @@
 #error "f32_exact.hip is built with -DRT_F32_ELEMENTARY_F64"
 #endif
 
+/* the draw layer of this build's rt1w_num.h on given words (rt_f32_draws.h), for the host and for the device */
+namespace rtf32x {
+#define double float
+#include "rt_f32_draws.h"
+#undef double
+} // namespace rtf32x
+
 namespace {
 
 bool g_exact_on = false;
@@ -51,6 +58,12 @@ __global__ void f32_elementary_kernel(int fn, const float* __restrict__ x, const
         }
         out[i] = r;
     }
+}
+
+/* the f32 build's word -> number conversions (include/rt1w_num.h under RT_F32), one word per lane */
+__global__ void f32_draws_kernel(int fn, const unsigned long long* __restrict__ words, float lo, float hi, unsigned long long n, float* __restrict__ out) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x)
+        out[i] = rtf32x::rt_f32_draw(fn, words[i], lo, hi);
 }
 
 /* the two functions the filter kernels build their weights from (rt_denoise.h), one argument per lane: what the device makes of the
@@ -106,5 +119,35 @@ extern "C" int rt1w_lab_f32_elementary(int device, int fn, const float* x, const
     if (dy) (void)hipFree(dy);
     if (dout) (void)hipFree(dout);
     if (!ok) { rt1w_internal_set_error("rt1w_lab_f32_elementary: device error"); return RT1W_ERR_DEVICE; }
+    return RT1W_OK;
+}
+
+/* device 0: this translation unit's host pass over the same text; device 1: one lane per word on GPU 0.  The range selectors loop until
+ * a draw is below `hi`, so bounds that no draw can satisfy are refused here, before anything runs */
+extern "C" int rt1w_lab_f32_draws(int device, int fn, const uint64_t* words, float lo, float hi, uint64_t n, float* out) {
+    const bool ranged = fn == 1 || fn == 2 || fn == 5;
+    if ((device != 0 && device != 1) || fn < 0 || fn >= RT_F32_DRAW_FNS || !words || !out || n == 0u ||
+        (ranged && !(lo < hi && hi - lo < __builtin_huge_valf() && lo > -__builtin_huge_valf()))) {
+        rt1w_internal_set_error("rt1w_lab_f32_draws: bad argument");
+        return RT1W_ERR_INVALID;
+    }
+    if (device == 0) {
+        for (uint64_t i = 0; i < n; ++i) out[i] = rtf32x::rt_f32_draw(fn, words[i], lo, hi);
+        return RT1W_OK;
+    }
+    unsigned long long* dw = nullptr;
+    float* dout = nullptr;
+    const size_t wbytes = (size_t)n * sizeof(uint64_t), obytes = (size_t)n * sizeof(float);
+    bool ok = hipSetDevice(0) == hipSuccess && hipMalloc((void**)&dw, wbytes) == hipSuccess && hipMalloc((void**)&dout, obytes) == hipSuccess &&
+              hipMemcpy(dw, words, wbytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        const unsigned int block = 256;
+        const unsigned long long want = (n + block - 1u) / block;
+        hipLaunchKernelGGL(f32_draws_kernel, dim3((unsigned int)(want < 4096ull ? want : 4096ull)), dim3(block), 0, 0, fn, dw, lo, hi, (unsigned long long)n, dout);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, obytes, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (dw) (void)hipFree(dw);
+    if (dout) (void)hipFree(dout);
+    if (!ok) { rt1w_internal_set_error("rt1w_lab_f32_draws: device error"); return RT1W_ERR_DEVICE; }
     return RT1W_OK;
 }

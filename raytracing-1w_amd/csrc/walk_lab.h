@@ -113,6 +113,13 @@ int rt1w_lab_denoise_elementary(int device, int fn, const double* x, const uint3
  * product's f32 kernels call it -- fn 0 sinf(x), 1 cosf(x), 2 atan2f(x, y), 3 acosf(x), 4 logf(x) */
 int rt1w_lab_f32_exact(int on);
 int rt1w_lab_f32_elementary(int device, int fn, const float* x, const float* y, uint64_t n, float* out);
+/* the draw layer of the f32 builds (include/rt1w_num.h under RT_F32) on given 64-bit words: out[i] = what the f32 core holds after
+ * assigning the draw of words[i] to its float.  fn (rt_f32_draws.h): 0 the unit draw rt_f64_from_bits, 1 the range draw
+ * rt_range_from_bits(lo, hi) with one take and no retry, 2 rt_take_range(lo, hi) over a stream of words[i] then the word 0 (= the
+ * single take where the retry accepts it, lo where it rejects), 3 rt_take_f64, 4 rt_gen_f64, 5 rt_gen_range as 2, 6 rt_pm1_from_bits.
+ * device 0: the host build, no GPU; device 1: one lane per word on GPU 0.  RT1W_ERR_INVALID for anything else, null pointers, n = 0 or,
+ * for the range selectors, bounds that are not finite with lo < hi */
+int rt1w_lab_f32_draws(int device, int fn, const uint64_t* words, float lo, float hi, uint64_t n, float* out);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

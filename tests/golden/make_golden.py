@@ -6,7 +6,8 @@
     that match a scene arm of master (one_weekend.png is the book-1 scene: gradient sky, no checker, no motion blur);
 (2) golden framebuffers of the literal CPU oracle (oracle/oracle.cpp) for small
     configurations of every scene arm, incl. BASELINE config C1 (Cornell 200x200x64);
-(3) block means of the same oracle built with `type Float = f32` (oracle/oracle_f32.cpp) -- `make_golden.py f32` makes only these.
+(3) block means of the same oracle built with `type Float = f32` (oracle/oracle_f32.cpp) -- `make_golden.py f32` makes only these;
+(4) `make_golden.py census [frame ...]` only: the census of non-finite samples of the single-precision frames (f32_nonfinite_census.json).
 The reference (Rust) cannot be run here, so (2) are oracle outputs, not reference
 outputs; (1) is the reference's.
 """
@@ -119,9 +120,95 @@ def f32_frames():
     with open(os.path.join(HERE, 'oracle_f32_blocks.json'), 'w') as f:
         json.dump({"build_seed": 1, "global_seed": 0, "source": "oracle/oracle_f32.cpp (liborc_f32.so)", "cases": out}, f, indent=1)
 
+CENSUS_FRAMES = {  # name: (arm, W, H, spp, aspect) -- Cornell at the size of test_f32_mode_matches_the_f64_frame_statistically,
+    "cornell_600x600x256": (5, 600, 600, 256, None),          # the others at the sizes of F32_CASES (+ the smoke box at final_scene's)
+    "random_scene_300x200x64": (0, 300, 200, 64, 1.5),
+    "cornell_smoke_200x200x64": (6, 200, 200, 64, None),
+    "final_scene_200x200x64": (7, 200, 200, 64, None),
+}
+
+def _f32_only_zero(f32_img, f64_img):
+    """[row, col] of the pixels whose three channels are zero in the f32 frame and not in the f64 frame: the NaN scrub's trace."""
+    return [[int(r), int(c)] for r, c in np.argwhere((f32_img == 0).all(axis=2) & ~(f64_img == 0).all(axis=2))]
+
+def _brief(pixels):
+    """a list of pixels as the census keeps it: its length, and the pixels themselves while they are few (a dark frame has thousands)"""
+    return {"count": len(pixels), "pixels": pixels if len(pixels) <= 16 else None}
+
+def census_frame(name, scene, lit, arm, W, H, spp, aspect=None, twin_lib=None, literal_frame=True):
+    """One frame of the census: the f32 twin against the f64 core, every f32-only zero pixel taken apart into single samples (1x1 tiles,
+    raw sums), each non-finite sample into the first max_depth at which it is non-finite, and the literal f32 oracle asked about the
+    same sample.  A pixel none of whose samples is non-finite is black for another reason: it goes to `finite_zero_pixels` once its
+    raw sum over all samples is seen to be exactly zero."""
+    kw = dict(lib=twin_lib) if twin_lib is not None else {}
+    a, sa = orc.flat_render(scene, W, H, spp)
+    b, sb = orc.flat_f32_render(scene, W, H, spp, **kw)
+    assert np.isfinite(b).all() and np.isfinite(a).all()
+    pixels = _f32_only_zero(b, a)
+    print(name, "twin f32-only zero pixels:", len(pixels), "f64-only:", len(_f32_only_zero(a, b)), "segments", sb["segments"], flush=True)
+    entries, finite_zero = [], []
+    for row, col in pixels:
+        tile = (col, row, 1, 1)
+        one = lambda s, depth=50, n=1: orc.flat_f32_render(scene, W, H, n, max_depth=depth, tile=tile, sample_offset=s, out_sum=True, threads=1, **kw)
+        found = False
+        for s in range(spp):
+            raw, st = one(s)
+            if np.isfinite(raw).all():
+                continue
+            found = True
+            first = next(d for d in range(1, 51) if not np.isfinite(one(s, d)[0]).all())
+            l, _ = lit.render(W, H, 1, tile=tile, sample_offset=s, out_sum=True, threads=1)
+            entries.append({"pixel": [row, col], "sample": s, "bounce": first, "segments": st["segments"], "raw_sum": [repr(float(v)) for v in raw[0, 0]],
+                            "literal_too": bool(not np.isfinite(l).all())})
+            print("  ", entries[-1], flush=True)
+        if not found:
+            assert (one(0, n=spp)[0] == 0).all(), (row, col)   # every sample is finite: so is their sum, and the pixel is zero because the sum is
+            finite_zero.append([row, col])
+    rec = {"arm": arm, "W": W, "H": H, "spp": spp, "aspect": aspect, "twin_segments": sb["segments"], "twin_zero_pixels": len(pixels),
+           "f64_only_zero_pixels": len(_f32_only_zero(a, b)), "entries": entries, "finite_zero_pixels": _brief(finite_zero)}
+    if literal_frame:
+        l, sl = lit.render(W, H, spp)
+        lo, _ = orc.OracleScene(arm, build_seed=1, aspect_ratio=aspect).render(W, H, spp)
+        rec["literal_zero_pixels"] = _brief(_f32_only_zero(l, lo))
+        print(name, "literal f32-only zero pixels:", rec["literal_zero_pixels"]["count"], flush=True)
+    return rec
+
+def census(only=None):
+    """(4) `make_golden.py census`: every non-finite sample of four single-precision frames (CENSUS_FRAMES), CPU only.  Writes
+    f32_nonfinite_census.json.  An entry's `cause`, `decision`, `shade_origin` and `shade_direction` (the ray of the bounce that went
+    non-finite) and a frame's `notes` are filled in by hand after reading and tracing the code; they are carried over from the file that
+    is already there (matched by frame, pixel and sample), as are the top-level keys this mode does not write."""
+    path = os.path.join(HERE, 'f32_nonfinite_census.json')
+    old = json.load(open(path)) if os.path.exists(path) else {"frames": {}}
+    rt = orc.rt()
+    frames = dict(old.get("frames", {}))
+    for name, (arm, W, H, spp, aspect) in CENSUS_FRAMES.items():
+        if only and name not in only:
+            continue
+        scene = rt.Scene.reference(arm, build_seed=1, aspect_ratio=aspect)
+        lit = orc.OracleScene(arm, build_seed=1, aspect_ratio=aspect, f32=True)
+        rec = census_frame(name, scene, lit, arm, W, H, spp, aspect)
+        was = old.get("frames", {}).get(name, {})
+        said = {(tuple(e["pixel"]), e["sample"]): e for e in was.get("entries", [])}
+        for e in rec["entries"]:   # what was filled in by hand stays with its sample
+            prev = said.get((tuple(e["pixel"]), e["sample"]), {})
+            e.update({k: prev.get(k, "") for k in ("shade_origin", "shade_direction", "cause", "decision")})
+        rec["notes"] = was.get("notes", {})
+        frames[name] = rec
+    out = {k: v for k, v in old.items() if k != "frames"}
+    out.update({"build_seed": 1, "global_seed": 0, "source": "oracle/oracle_flat_f32.cpp against oracle/oracle_flat.cpp; literal_too: oracle/oracle_f32.cpp",
+                "pixel": "[row, col] of the returned array (row 0 = the frame's y0)", "frames": frames})
+    c = frames.get("cornell_600x600x256")
+    if c and "literal_zero_pixels" in c:   # the bound of test_f32_mode_matches_the_f64_frame_statistically comes from here
+        out["cornell_literal_zero_pixel_count"] = c["literal_zero_pixels"]["count"]
+    with open(path, 'w') as f:
+        json.dump(out, f, indent=1)
+
 def main():
     if sys.argv[1:] == ["f32"]:
         return f32_frames()
+    if sys.argv[1:2] == ["census"]:
+        return census(sys.argv[2:])
     f32_frames()
     with open(os.path.join(HERE, 'cornell_png_blocks.json'), 'w') as f:
         json.dump(png_blocks(), f, indent=1)

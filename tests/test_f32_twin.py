@@ -221,22 +221,27 @@ def draw_probe(lib, bits):
 
 
 def test_draws_that_round_to_one_stay_in_range(rt):
-    """A 53-bit draw r < 1 of the generator, rounded to f32 where the core assigns it, can be 1.0f (r >= 1 - 2^-25), which rand's own
-    `gen::<f32>()` never returns; the smallest draw is 0 in both precisions.  Every consumer of a uniform draw -- the cosine
-    direction, random_to_sphere, the light rectangle's point, the free flight -ln(r) / density, the Schlick comparison, the lens disk
-    and the shutter time -- is fed the largest draw (all mantissa bits set) and 0 through the f32 twin (orcflat_draw_probe).  Each
-    result must be finite wherever the f64 core's is, and lie inside what the f64 core returns for that draw and its three
-    neighbours, widened by 4 f32 roundings (4 * 2^-24 * max(1, |value|): the draw's own rounding, 2 pi r, and the function's).  The
-    free flight of the draw 0 is +inf in both cores, as the reference's ln(0) makes it: the medium is left without scattering."""
+    """A 53-bit draw r < 1 of the generator would round to 1.0f where the f32 core assigns it (r >= 1 - 2^-25), which rand's own
+    `gen::<f32>()` never returns; the draw contract of the f32 builds (include/rt1w_num.h, tests/test_f32_draws.py) makes it 1 - 2^-24
+    instead, and a range draw that rounds onto `high` is drawn again.  The smallest draw is 0 in both precisions.  Every consumer of a
+    uniform draw -- the cosine direction, random_to_sphere, the light rectangle's point, the free flight -ln(r) / density, the Schlick
+    comparison, the lens disk and the shutter time -- is fed the largest draw (all mantissa bits set) and 0 through the f32 twin
+    (orcflat_draw_probe).  Each result must be finite wherever the f64 core's is, and lie inside what the f64 core returns for the
+    64-bit draws the f32 draw may stand for -- the contract keeps it within 2^-24 of the 64-bit draw, so for the largest: that draw, its
+    three neighbours, 1 - 2^-24 and 1 - 2^-23; for 0: the draw and its three neighbours -- widened by 4 f32 roundings (4 * 2^-24 *
+    max(1, |value|): 2 pi r and the function's).  The free flight of the draw 0 is +inf in both cores, as the reference's ln(0) makes
+    it: the medium is left without scattering.  The lens disk and the shutter time reject the largest draw and draw on from the
+    stream: finite, inside the disk, and in [0, 1) as floats."""
     f32, f64 = orc.flat_f32_lib(), orc.B
     names = ("cos.x", "cos.y", "cos.z", "sph.x", "sph.y", "sph.z", "light", "flight", "draw", "lens.x", "lens.y", "time")
     top = (1 << 64) - 1
     step = 1 << 11
-    for label, around in (("largest", [top - k * step for k in range(4)]), ("smallest", [k * step for k in range(4)])):
+    stands_for = [top - k * step for k in range(4)] + [((1 << 53) - (1 << 29)) << 11, ((1 << 53) - (1 << 30)) << 11]
+    for label, around in (("largest", stands_for), ("smallest", [k * step for k in range(4)])):
         got = draw_probe(f32, around[0])
         ref = np.array([draw_probe(f64, b) for b in around])
         for i, name in enumerate(names):
-            if name.startswith("lens"):        # the rejection loop draws on from the stream: only finite and inside the disk
+            if name.startswith("lens") or (name == "time" and label == "largest"):   # the rejection draws on from the stream
                 assert np.isfinite(got[i]) and abs(got[i]) < 1.0, (label, name, got[i])
                 continue
             if not np.isfinite(ref[0, i]):
@@ -246,7 +251,10 @@ def test_draws_that_round_to_one_stay_in_range(rt):
             fin = ref[:, i][np.isfinite(ref[:, i])]
             tol = 4 * 2.0 ** -24 * max(1.0, float(np.abs(fin).max()))
             assert fin.min() - tol <= got[i] <= fin.max() + tol, (label, name, got[i], fin.min(), fin.max())
-        assert 0.0 <= got[8] <= 1.0 and 0.0 <= got[11] <= 1.0 and 213.0 <= got[6] <= 343.0, (label, got)
+        # the unit draw and the shutter time are half-open as floats; the light's coordinate is shown before its caller's retry (rt_core.h)
+        assert 0.0 <= got[8] < 1.0 and 0.0 <= got[11] < 1.0 and 213.0 <= got[6] <= 343.0, (label, got)
+        assert got[8] == np.float32(got[8]) and got[11] == np.float32(got[11])
+    assert draw_probe(f32, top)[8] == 1.0 - 2.0 ** -24 and draw_probe(f32, top)[2] == 2.0 ** -12   # the cosine lobe leaves the surface: z = sqrt(1 - r2)
 
 
 # ------------------------------------------------------------------------------------------------------------------- GPU tier

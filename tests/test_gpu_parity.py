@@ -652,8 +652,11 @@ def test_f32_mode_matches_the_f64_frame_statistically(rt, gpu_ctx_factory):
     """RT1W_PRECISION_F32 (the reference's `type Float = f32`, main.rs:1): same scene, same streams, f32
     arithmetic.  Parity is statistical: at 600x600x256 spp the 8-bit 100x100-block means of the f32 and f64 frames agree
     within 1/255 (measured 0.65) and the global channel means within 0.1/255 (the two frames share their random numbers, so most paths
-    are the same paths and the difference is far below the Monte-Carlo noise of either); no NaN pixel, and at most a handful of pixels zeroed by the reference's NaN
-    scrub that the f64 frame does not have (measured 8 of 360 000); and explicitly at the reference's thin spots: the k = 555 walls, whose BVH boxes are
+    are the same paths and the difference is far below the Monte-Carlo noise of either); no NaN pixel, and no more pixels that are black in f32 only than
+    twice the literal f32 oracle's own count for this frame (5, so 10: tests/golden/f32_nonfinite_census.json, which accounts for each -- a
+    diffuse hit at the very height of the light's plane, the reference's own 0 / 0, and one pixel on a mirror's edge that no NaN touches;
+    measured on the MI355X: 7 -- the twin's 6 and [417, 254], where the product's path leaves the twin's at its first sinf / cosf and goes
+    non-finite a bounce later; 10 before the draw contract of include/rt1w_num.h); and explicitly at the reference's thin spots: the k = 555 walls, whose BVH boxes are
     0.0001 thick (aarect.rs:74-79) = 1.6 f32 ulps -- the rows and columns next to the walls show no holes (their means
     stay within 2 % of the f64 frame's) -- and t_min = 0.001 (main.rs:62): no acne, i.e. the floor's mean is unchanged."""
     ctx = gpu_ctx_factory(rt.Scene.reference(5, build_seed=1))
@@ -669,7 +672,13 @@ def test_f32_mode_matches_the_f64_frame_statistically(rt, gpu_ctx_factory):
     assert np.abs(qa.mean(axis=(0, 1)) - qb.mean(axis=(0, 1))).max() < 0.1
     blocks = (qa - qb).reshape(6, 100, 6, 100, 3).mean(axis=(1, 3))
     assert np.abs(blocks).max() < 1.0, np.abs(blocks).max()          # measured 0.65
-    assert int(((b == 0).all(axis=2) & ~(a == 0).all(axis=2)).sum()) <= 40   # NaN-scrubbed pixels (color.rs:16-18): measured 8 of 360 000
+    # pixels that are black in f32 only (color.rs:16-18 scrubs a NaN sum to zero): the literal f32 oracle's own count for this frame,
+    # computed on the CPU and stored with the census, allowed twice (paths the five single-precision functions send elsewhere), 2 at the least
+    census = json.load(open(os.path.join(HERE, "golden", "f32_nonfinite_census.json")))
+    allowed = max(2, 2 * census["cornell_literal_zero_pixel_count"])
+    black = np.argwhere((b == 0).all(axis=2) & ~(a == 0).all(axis=2))
+    print(f"\nf32-only black pixels: {len(black)} (allowed {allowed}): {black.tolist()}")
+    assert len(black) <= allowed, black.tolist()
     for sl in (np.s_[:, 5:25], np.s_[:, -25:-5], np.s_[5:25, :], np.s_[-25:-5, :]):      # next to the four walls in the picture
         ra, rb = a[sl].mean(), b[sl].mean()
         assert abs(rb / ra - 1.0) < 0.03, (ra, rb)
