@@ -382,6 +382,52 @@ int rt1w_render_aov_deep(rt1w_context* c, const rt1w_render_params* p, uint32_t 
 int rt1w_render_aov_deep_device(rt1w_context* c, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, void* d_out_aov,
                                 rt1w_stats* stats);
 
+/* ---- ray queries: Hittable::hit of the scene's world for a list of the caller's own rays ----
+ * For every ray r of 0 .. n - 1: world.hit(ray, t_min, t_max, rng) -> Option<HitRecord> (hittable.rs:63-64, HitRecord hittable.rs:10-18),
+ * exactly as the first segment of a beauty path does it (main.rs:62, bvh.rs:25-50) but with the caller's ray and bounds: the walk is
+ * the scene variant's own, in the reference's order; ties between equal t and the time a MovingSphere is evaluated at are those of the
+ * render kernels.  The direction is NOT normalised: t is in units of it, p = origin + t * direction (ray.rs:12-14).
+ *   rays  double[n][9] = origin xyz, direction xyz, time (Ray, ray.rs:5), t_min, t_max (the two bounds of `hit`).
+ *   out   double[n][12]:
+ *           0     hit 1, miss 0
+ *           1     t
+ *           2-4   p: the hit point in world space (a Translate / RotateY above the leaf moves it back as hittable.rs:215-225, :255-278 do)
+ *           5-7   normal in world space, against the ray (hittable.rs:30-35); a ConstantMedium's is (1, 0, 0) (constant_medium.rs:101)
+ *           8, 9  u, v of the leaf (sphere.rs:50-62, aarect.rs:58-71) WHERE THE HIT MATERIAL'S TEXTURE READS THEM -- an image texture
+ *                 (texture.rs:67-89) somewhere in its texture tree --, else 0: the kernels do not compute what no texture looks at
+ *           10    front_face 1 or 0; a FlipFace flips this flag only, not the normal (hittable.rs:288-291)
+ *           11    index of the hit material in the scene's material table: the id the rt1w_material_* constructor returned.  The
+ *                 Isotropic of a ConstantMedium (constant_medium.rs:22-28) has no constructor of its own: it takes the next free id at
+ *                 the moment rt1w_hittable_constant_medium is called, so ids handed out later skip it
+ *   out_node  (may be NULL) uint32[n]: the pre-order index of the hit leaf's record in the flattened node array, the array
+ *             rt1w_scene_copy_flat(.., 0, ..) exports (a ConstantMedium's own record for a hit inside it).
+ *   A miss writes 0 into all 12 slots and 0xFFFFFFFF as the node.
+ * Media: ConstantMedium::hit draws (constant_medium.rs:58-113, the free flight of :85).  Ray r draws from the Philox stream of
+ * (pixel seed first_stream + r, sample `sample`, `global_seed`) -- the stream a render gives that pixel's sample -- starting at the
+ * stream's FIRST word (a render's sample has drawn its camera ray before).  A list split into two calls, the second with first_stream
+ * advanced by the rays of the first, therefore gives the same records, bit for bit.  A scene without media draws nothing.
+ * ONE DEVIATION from the literal hit(): a ray with a non-finite value (an infinity or a NaN) among origin, direction and time, or with
+ * a NaN for t_min or t_max, is answered as a miss before any walk.  A t_max of +inf is allowed, and everything finite is literal: a
+ * zero direction, denormals, t_min > t_max.
+ * RT1W_ERR_INVALID: a null context, params, rays or out; n = 0 or n > 2^32 - 1; global_seed >= 2^32 (the streams take 32 bits of it);
+ * flags other than 0 or RT1W_FORCE_VARIANT(v) with a v that covers the scene (tests); out or out_node overlapping rays or each other.
+ * stats: paths = segments = n, kernel_ms (HIP events), total_ms, grid, block, variant.  One lane per ray, 64 consecutive rays per wave;
+ * the list is not reordered.  Bit-identical to the CPU build of the same code (librt1w_lab.so: rt1w_lab_hit_host).  None of the render
+ * kernels is involved. */
+typedef struct rt1w_hit_params {
+    uint64_t n;            /* rays */
+    uint64_t first_stream; /* ray r draws from the stream of pixel seed first_stream + r */
+    uint64_t global_seed;  /* as rt1w_render_params.global_seed; below 2^32 */
+    uint32_t sample;       /* the stream's sample index */
+    uint32_t flags;        /* 0 or RT1W_FORCE_VARIANT(v) */
+} rt1w_hit_params; /* 32 bytes */
+/* host memory in and out (through the context's device framebuffer, grown on demand and freed with the context) */
+int rt1w_hit(rt1w_context* c, const rt1w_hit_params* params, const double* rays, double* out, uint32_t* out_node /* may be NULL */, rt1w_stats* stats);
+/* same, on device memory of the context's GPU (e.g. torch tensors): d_rays double[n][9], d_out double[n][12], d_out_node uint32[n] or
+ * NULL; no host copy.  Synchronises the context's stream before returning. */
+int rt1w_hit_device(rt1w_context* c, const rt1w_hit_params* params, const void* d_rays, void* d_out, void* d_out_node /* may be NULL */,
+                    rt1w_stats* stats);
+
 /* ---- feature-guided denoiser: the consumer of the feature buffers above ----
  * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) over an image and its first-hit feature buffers.
  * Replaces nothing of the reference, which reaches a clean image by sample count alone (10 000 spp for final_scene, src/main.rs:939).

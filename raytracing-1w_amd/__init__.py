@@ -278,6 +278,18 @@ def _temporal_params(width, height, keep_albedo=False, max_history=0, depth_tol=
     return TemporalParams(width, height, flags | _keep(keep_albedo), max_history, depth_tol, normal_min)
 
 
+class HitParams(C.Structure):
+    """rt1w_hit_params: n rays; ray r draws from the stream of pixel seed first_stream + r, sample `sample`, `global_seed`."""
+    _fields_ = [("n", C.c_uint64), ("first_stream", C.c_uint64), ("global_seed", C.c_uint64), ("sample", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(HitParams) == 32, "rt1w_hit_params is 32 bytes (include/rt1w.h); it is not one of rt1w_abi_sizeof's"
+HIT_RAY = 9  # rt1w_hit: origin xyz, direction xyz, time, t_min, t_max per ray
+HIT_RECORD = 12  # rt1w_hit: hit, t, p xyz, normal xyz, u, v, front_face, material id per ray
+HIT_NO_NODE = 0xFFFFFFFF  # the node index of a miss
+_sig("rt1w_hit", C.c_int, _P, C.POINTER(HitParams), _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_hit_device", C.c_int, _P, C.POINTER(HitParams), _P, _P, _P, C.POINTER(Stats))
+
 _CAM_ARGS = [_D3, _D3, _D3] + [C.c_double] * 6
 _sig("rt1w_reference_camera", C.c_int, C.c_int, _D3, _D3, _D3, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("rt1w_context_set_camera", C.c_int, _P, *_CAM_ARGS)
@@ -319,6 +331,8 @@ _LAB_SIGS = {
     "rt1w_lab_aov_host": [_P, _PR, _P],
     "rt1w_lab_aov_deep_host": [_P, _PR, _U, _F, _P, C.POINTER(_N), _P],
     "rt1w_lab_aov_tiles_host": [_P, _PR, _U, _P, _U, _P],
+    "rt1w_lab_hit_host": [_P, C.POINTER(HitParams), _P, _P, _P],
+    "rt1w_lab_camera_rays_host": [_P, _PR, _P],
     "rt1w_lab_denoise_host": [_PD, _P, _P, _P],
     "rt1w_lab_batch_variance_host": [_U] * 5 + [_P] * 4,
     "rt1w_lab_denoise_var_host": [_PD, _P, _P, _P, _F, _P],
@@ -480,6 +494,22 @@ def _aov_tiles_prep(width, height, spp, tile, tiles, sample_offset, global_seed,
     rec, n = _tile_list(tiles)
     out = np.empty((n, tile, tile, AOV_CHANNELS), dtype=np.float64)
     return (p, tile, rec, n, out), out
+
+
+def _hit_params(n, first_stream=0, sample=0, global_seed=0, variant=None, flags=0):
+    return HitParams(n, first_stream, global_seed, sample, flags | (0 if variant is None else (variant + 1) << 8))
+
+
+def _hit_prep(rays, t_min, t_max, first_stream, sample, global_seed, variant):
+    """rays [n, 9], or [n, 7] = origin, direction, time with t_min and t_max filled in for every ray"""
+    r, = _f64(rays)
+    if r.ndim != 2 or r.shape[1] not in (7, HIT_RAY):
+        raise ValueError("rays must be [n, 7] (origin, direction, time) or [n, 9] (+ t_min, t_max)")
+    if r.shape[1] == 7:
+        r = np.concatenate([r, np.full((r.shape[0], 1), t_min, dtype=np.float64), np.full((r.shape[0], 1), t_max, dtype=np.float64)], axis=1)
+    out = np.empty((r.shape[0], HIT_RECORD), dtype=np.float64)
+    node = np.empty(r.shape[0], dtype=np.uint32)
+    return (_hit_params(r.shape[0], first_stream, sample, global_seed, variant), r, out, node), (out, node)
 
 
 def _denoise_prep(frame, aov, kw):
@@ -967,6 +997,18 @@ class Context:
         p = self._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, variant=variant, strips=strips)
         return _call(_lib.rt1w_render_aov_deep_device, self._h, p, max_specular, max_fuzz, d_ptr)
 
+    def hit(self, rays, t_min=0.001, t_max=float("inf"), first_stream=0, sample=0, global_seed=0, variant=None, with_stats=False):
+        """Ray queries (rt1w_hit): Hittable::hit of the scene's world for the caller's rays [n, 9] = origin, direction, time, t_min,
+        t_max -- or [n, 7] with `t_min` and `t_max` filled in.  Returns (records float64 [n, 12] = hit, t, p xyz, normal xyz, u, v,
+        front_face, material id; nodes uint32 [n] = the hit leaf's index in Scene.flat(0), HIT_NO_NODE on a miss).  A medium's draws of
+        ray r come from the stream of pixel seed first_stream + r (include/rt1w.h has the semantics)."""
+        return self._entry(_lib.rt1w_hit, _hit_prep(rays, t_min, t_max, first_stream, sample, global_seed, variant), with_stats)
+
+    def hit_device(self, d_rays, d_out, d_node, n, first_stream=0, sample=0, global_seed=0, variant=None):
+        """Same on device memory (int addresses, e.g. torch tensors' .data_ptr()): d_rays n * 9 float64 with the bounds in, d_out n * 12
+        float64, d_node n uint32 or None; returns the stats dict."""
+        return _call(_lib.rt1w_hit_device, self._h, _hit_params(n, first_stream, sample, global_seed, variant), d_rays, d_out, d_node)
+
     def denoise(self, frame, aov, with_stats=False, **kw):
         """Feature-guided filter (rt1w_denoise) of a float64 frame [h, w, 3] with its feature buffers [h, w, 8] (render_aov): the
         denoised [h, w, 3].  kw: iterations, keep_albedo, sigma_colour, sigma_normal, sigma_depth (0 = default)."""
@@ -1307,6 +1349,21 @@ def aov_tiles_host(scene, width, height, spp, tile, tiles, sample_offset=0, glob
     args, out = _aov_tiles_prep(width, height, spp, tile, tiles, sample_offset, global_seed, variant, flags, strips, f32)
     _call_lab("rt1w_lab_aov_tiles_host", scene._h, *args)
     return out
+
+
+def hit_host(scene, rays, t_min=0.001, t_max=float("inf"), first_stream=0, sample=0, global_seed=0, variant=None):
+    """CPU twin of Context.hit (librt1w_lab.so: rt1w_lab_hit_host, the same rt_hit.h built for the host): the (records, nodes) the GPU
+    must equal bit for bit.  No GPU needed."""
+    args, out = _hit_prep(rays, t_min, t_max, first_stream, sample, global_seed, variant)
+    return _twin("rt1w_lab_hit_host", ((scene._h, *args), out))
+
+
+def camera_rays_host(scene, width, height, spp, tile=None, sample_offset=0, global_seed=0, strips=None):
+    """The camera rays of a tile (librt1w_lab.so: rt1w_lab_camera_rays_host): float64 [tile_h, tile_w, spp, 8] = origin, direction, time,
+    1 of the ray every sample's path and feature buffers begin with.  No GPU needed."""
+    p = Context._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, strips=strips)
+    out = np.empty((p.tile_h, p.tile_w, spp, 8), dtype=np.float64)
+    return _twin("rt1w_lab_camera_rays_host", ((scene._h, p, out), out))
 
 
 def guides_merge_tiles_host(gacc, tile_sums, spp, tile, tiles):

@@ -1,4 +1,4 @@
-/* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip, aov_tiles.hip): rt_aov.h, rt_aov_deep.h and rt_aov_tiles.h compiled for the host (g++, -ffp-contract=off
+/* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip, aov_tiles.hip) and of the ray-query kernels (hit.hip): rt_aov.h, rt_aov_deep.h, rt_aov_tiles.h and rt_hit.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core) and run over a committed scene's flat arrays.  Diagnostics library only (librt1w_lab.so): the expected side of the GPU
  * tests' bit-equality checks and of the CPU tier's checks against the literal oracle.  librt1w.so keeps no CPU render path. */
 #include <algorithm>
@@ -10,6 +10,7 @@
 #include "rt_adaptive_plan.h" /* rt_aov_tiles_check */
 #include "rt_aov_deep.h"
 #include "rt_aov_tiles.h"
+#include "rt_hit.h"
 #include "walk_lab.h"
 
 namespace {
@@ -125,7 +126,60 @@ bool aov_tiles(const RtSceneView& sc, const RtFrame& f, uint32_t tile, const rt1
             }
     return true;
 }
+
+/* rays k0, k0 + step, .. of a query list by rt_hit_ray, as the kernel's lanes run them */
+template <class Cfg>
+bool hit_rays(const RtSceneView& sc, const RtHitParams& hp, uint64_t k0, uint64_t step, const double* rays, double* out, uint32_t* out_node) {
+    AovHostStack stk;
+    RtGlobalNodes ns{sc.nodes};
+    for (uint64_t r = k0; r < hp.n; r += step) {
+        uint32_t node;
+        rt_hit_ray<Cfg>(sc, ns, rays + r * RT_HIT_RAY, r, hp, stk, out + r * RT_HIT_RECORD, node);
+        if (stk.overflow) return false;
+        if (out_node) out_node[r] = node;
+    }
+    return true;
+}
 } // namespace
+
+extern "C" int rt1w_lab_hit_host(const rt1w_scene* s, const rt1w_hit_params* p, const double* rays, double* out, uint32_t* out_node) {
+    static_assert(sizeof(rt1w_hit_params) == sizeof(RtHitParams), "rt1w_hit_params is RtHitParams' layout");
+    if (!s || !p || !rays || !out || !s->committed) return RT1W_ERR_INVALID;
+    RtHitParams hp;
+    memcpy(&hp, p, sizeof hp);
+    if (rt_hit_refusal(hp, rays, out, out_node)) return RT1W_ERR_INVALID; /* the entries' own check */
+    std::vector<RtNode> nodes;
+    RtSceneView sc;
+    int v;
+    if (!host_view(s, p->flags, nodes, sc, v)) return RT1W_ERR_INVALID;
+    const bool ok = round_robin((uint32_t)hp.n, [&](uint32_t t, uint32_t n_threads) { /* the list's rays */
+        return with_variant(v, [&](auto cfg) { return hit_rays<decltype(cfg)>(sc, hp, t, n_threads, rays, out, out_node); });
+    });
+    return ok ? RT1W_OK : RT1W_ERR_STATE;
+}
+
+extern "C" int rt1w_lab_camera_rays_host(const rt1w_scene* s, const rt1w_render_params* p, double* out) {
+    if (!s || !p || !out || !s->committed) return RT1W_ERR_INVALID;
+    if (const int rc = rt1w::params_check(p, nullptr); rc < 0) return rc;
+    if (p->precision != RT1W_PRECISION_F64) return RT1W_ERR_UNSUPPORTED;
+    std::vector<RtNode> nodes;
+    RtSceneView sc;
+    int v;
+    if (!host_view(s, 0u, nodes, sc, v)) return RT1W_ERR_INVALID;
+    RtFrame f = rt1w::frame_of(p);
+    f.max_depth = 1u; f.chunk = p->spp; f.n_chunks = 1u;
+    double* o = out;
+    for (uint32_t py = 0; py < f.tile_h; ++py)
+        for (uint32_t px = 0; px < f.tile_w; ++px)
+            for (uint32_t k = 0; k < f.spp; ++k, o += 8) {
+                RtPath path;
+                rt_path_begin(sc, f, f.x0 + px, rt_frame_row(f, py), f.sample_offset + k, path); /* what rt_aov_sample and the render kernels begin with */
+                o[0] = path.ray.o.x; o[1] = path.ray.o.y; o[2] = path.ray.o.z;
+                o[3] = path.ray.d.x; o[4] = path.ray.d.y; o[5] = path.ray.d.z;
+                o[6] = path.ray.time; o[7] = 1.0; /* valid, as in rt1w_lab_dump_rays */
+            }
+    return RT1W_OK;
+}
 
 extern "C" int rt1w_lab_aov_tiles_host(const rt1w_scene* s, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* out) {
     if (!s || !p || !tiles || !out || !s->committed) return RT1W_ERR_INVALID;

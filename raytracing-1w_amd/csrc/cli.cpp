@@ -8,6 +8,11 @@
  *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
  *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]]
  *        [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]]
+ *        [--pick I J]
+ * --pick I J renders nothing: it prints the hit record (rt1w_hit) of the ray through the CENTRE of pixel (I, J), J counting the
+ * reference's rows j (0 = bottom row, main.rs:957): origin = the camera's lens centre, direction = lower_left_corner + s horizontal +
+ * t vertical - origin with s = (I + 1/2) / (width - 1), t = (J + 1/2) / (height - 1) (rt1w_context_get_camera; the s, t of
+ * rt1w_temporal_accumulate step 3), time = the shutter's opening, bounds 0.001 and inf (main.rs:62).
  * --frames N --orbit DEG renders an animation of N frames through rt1w_render_temporal: before frame k look_from is turned about the
  * vertical axis through look_at by k * DEG degrees (rt1w_context_set_camera; the scene, its upload and its kernel are frame 0's), the
  * frame's seed is --seed + k, and the previous frames' samples are reused where their surface points are seen again; with --denoise
@@ -61,6 +66,7 @@ int main(int argc, char** argv) {
     bool full_guides = false;        /* --adaptive --filtered-error: rt1w_render_adaptive_guided */
     bool specialised_tiles = false;  /* --adaptive with rounds through the tile entries: RT1W_TILES_SPECIALISED */
     std::string err_path;
+    long pick_i = -1, pick_j = -1;   /* >= 0: --pick, the record under a pixel instead of a render */
     long frames = 0;                 /* > 0: an animation through rt1w_render_temporal */
     double orbit = 0.0;
     double temporal_variance = -1.0; /* >= 0: the frames through rt1w_render_temporal_var with this sigma_variance (0 = default) */
@@ -108,6 +114,7 @@ int main(int argc, char** argv) {
         else if (a == "--specialised-tiles") specialised_tiles = true;
         else if (a == "--err-out") err_path = next("--err-out");
         else if (a == "--frames") frames = std::atol(next("--frames"));
+        else if (a == "--pick") { pick_i = std::atol(next("--pick I")); pick_j = std::atol(next("--pick J")); }
         else if (a == "--temporal-variance") {
             temporal_variance = 0.0;
             if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) temporal_variance = std::atof(argv[++i]);
@@ -116,7 +123,7 @@ int main(int argc, char** argv) {
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--target-error") target_error = std::atof(next("--target-error"));
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]] [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]] [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]] [--pick I J]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -147,6 +154,32 @@ int main(int argc, char** argv) {
         rt1w_specialise_info si;
         if (rt1w_context_specialise(ctx, 0, &si) < 0) std::fprintf(stderr, "rt1w: not specialised: %s\n", rt1w_last_error());
         else std::fprintf(stderr, "rt1w: kernel %s (%s, %.1f s in the compiler)\n", si.key, si.from_cache ? "from the kernel cache" : "compiled", si.compile_ms / 1e3);
+    }
+    if (pick_i >= 0 || pick_j >= 0) {
+        if (pick_i < 0 || pick_j < 0 || pick_i >= width || pick_j >= height) { std::fprintf(stderr, "rt1w: --pick I J: a pixel of the %ldx%ld frame\n", width, height); return 2; }
+        rt1w_camera cam;
+        if (rt1w_context_get_camera(ctx, &cam) < 0) return fail("camera");
+        const double s = ((double)pick_i + 0.5) / (double)(width > 1 ? width - 1 : 1), t = ((double)pick_j + 0.5) / (double)(height > 1 ? height - 1 : 1);
+        double ray[9], rec[12];
+        for (int k = 0; k < 3; ++k) {
+            ray[k] = cam.origin[k];
+            ray[3 + k] = cam.lower_left_corner[k] + s * cam.horizontal[k] + t * cam.vertical[k] - cam.origin[k];
+        }
+        ray[6] = cam.time0; ray[7] = 0.001; ray[8] = HUGE_VAL;
+        rt1w_hit_params hp;
+        std::memset(&hp, 0, sizeof hp);
+        hp.n = 1u; hp.first_stream = (uint64_t)pick_j * (uint64_t)width + (uint64_t)pick_i; hp.global_seed = (uint32_t)seed;
+        uint32_t node;
+        rt1w_stats hs;
+        if (rt1w_hit(ctx, &hp, ray, rec, &node, &hs) < 0) return fail("pick");
+        std::printf("pixel %ld %ld\norigin %.17g %.17g %.17g\ndirection %.17g %.17g %.17g\n", pick_i, pick_j, ray[0], ray[1], ray[2], ray[3], ray[4], ray[5]);
+        if (rec[0] == 0.0) std::printf("miss\n");
+        else
+            std::printf("hit\nt %.17g\np %.17g %.17g %.17g\nnormal %.17g %.17g %.17g\nu %.17g\nv %.17g\nfront_face %d\nmaterial %u\nnode %u\n", rec[1], rec[2],
+                        rec[3], rec[4], rec[5], rec[6], rec[7], rec[8], rec[9], (int)rec[10], (unsigned)rec[11], node);
+        rt1w_context_destroy(ctx);
+        rt1w_scene_destroy(scene);
+        return 0;
     }
     rt1w_render_params p;
     std::memset(&p, 0, sizeof p);

@@ -1,6 +1,6 @@
-/* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_denoise*,
+/* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_hit*, rt1w_denoise*,
  * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_guides_*, rt1w_render_adaptive*, rt1w_temporal_*, rt1w_render_temporal*) and a live context's camera (rt1w_context_set_camera).  Host code only, built without a device pass: the kernels
- * belong to aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip, temporal.hip and temporal_var.hip and are reached through rt_feature_launch.h, the context and its render
+ * belong to aov.hip, hit.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip, temporal.hip and temporal_var.hip and are reached through rt_feature_launch.h, the context and its render
  * path belong to context.hip (context.h), so a change here rebuilds none of the code objects.
  * Every entry is its checks, in the order its callers know, then one table of its buffers (Staged) handed to staged_entry(), which does what
  * the host and the device form of an entry differ in -- growing the context's buffers, laying the call's buffers out in them, the copies
@@ -13,6 +13,7 @@
 #include "context.h"
 #include "rt_feature_launch.h"
 #include "rt_aov_deep.h" /* rt_aov_deep_args_ok only */
+#include "rt_hit.h" /* RtHitParams, rt_hit_refusal only */
 #include "rt_denoise_var.h" /* rt_dv_batches_ok, rt_dv_sigma, rt_dv_split only */
 #include "rt_adaptive_plan.h" /* the plan of rt1w_render_adaptive and rt1w_adaptive_select; rt_ad_*_ok of rt_adaptive.h; the tile lists' checks */
 #include "rt_guides.h" /* RT_GD_RECORD only */
@@ -162,6 +163,47 @@ int render_aov(rt1w_context* c, const rt1w_render_params* p, const AovDeep* deep
     if (p->precision != RT1W_PRECISION_F64) { set_error("the AOV entries are f64 only (RT1W_PRECISION_F64)"); return RT1W_ERR_UNSUPPORTED; }
     Staged s[] = {{nullptr, (double*)out, (size_t)p->tile_w * p->tile_h * RT1W_AOV_CHANNELS, FRAMEBUFFER, nullptr, "AOV copy"}};
     return staged_entry(c, host, s, stats, [&](rt1w_stats* st) { return render_aov_common(c, p, deep, s[0].d_out, st); });
+}
+
+/* ---- ray queries (include/rt1w.h: rt1w_hit) ---- */
+static_assert(sizeof(rt1w_hit_params) == sizeof(RtHitParams), "rt1w_hit_params is RtHitParams' layout");
+/* the query kernel of the context's (or the forced) variant over device buffers through lane_run; of the stats what that leaves open */
+int hit_common(rt1w_context* c, const rt1w_hit_params* p, int variant, const double* d_rays, double* d_out, uint32_t* d_node, rt1w_stats* stats) {
+    if (rt1w_internal_hit_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_hit_sizeof(1) != sizeof(rt1w_hit_params)) {
+        set_error("ray-query kernels built against another scene layout"); return RT1W_ERR_DEVICE;
+    }
+    rt1w_stats st;
+    const int r = lane_run(c, p->n, "ray query", &st, [&](hipStream_t stream, unsigned* launch) {
+        return rt1w_internal_hit_launch(&c->view, p, variant, d_rays, d_out, d_node, stream, launch);
+    });
+    if (r < 0) return r;
+    st.segments = st.paths; /* one ray each */
+    st.chunk = 1u; st.n_chunks = 1u;
+    st.variant = (uint32_t)variant;
+    if (stats) *stats = st;
+    return RT1W_OK;
+}
+/* the two query entries.  The buffers are device memory, or (host) host memory, passed through the context's framebuffer */
+int hit(rt1w_context* c, const rt1w_hit_params* p, const void* rays, void* out, void* out_node, bool host, rt1w_stats* stats) {
+    if (!c || !p || !rays || !out) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    RtHitParams hp;
+    memcpy(&hp, p, sizeof hp);
+    if (const char* why = rt_hit_refusal(hp, rays, out, out_node)) { set_error(why); return RT1W_ERR_INVALID; }
+    int variant = c->variant;
+    const int rc = forced_variant(c, p->flags, true, &variant);
+    if (rc < 0) return rc;
+    const uint64_t node_bytes = p->n * sizeof(uint32_t);
+    /* the node indices are 4 bytes each: staged as room of whole doubles, copied out here in their own size */
+    Staged s[] = {{(const double*)rays, nullptr, (size_t)p->n * 9u, FRAMEBUFFER, "ray copy", nullptr},
+                  {nullptr, (double*)out, (size_t)p->n * 12u, FRAMEBUFFER, nullptr, "hit record copy"},
+                  {nullptr, nullptr, host && out_node ? (size_t)((p->n + 1u) / 2u) : 0u, FRAMEBUFFER, nullptr, nullptr}};
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
+        uint32_t* d_node = host ? (out_node ? (uint32_t*)s[2].d_out : nullptr) : (uint32_t*)out_node;
+        const int r = hit_common(c, p, variant, s[0].d_in, s[1].d_out, d_node, st);
+        if (r < 0) return r;
+        if (host && out_node && !hip_ok(hipMemcpy(out_node, d_node, node_bytes, hipMemcpyDeviceToHost), "node index copy")) return (int)RT1W_ERR_DEVICE;
+        return (int)RT1W_OK;
+    });
 }
 
 /* ---- feature-guided denoiser (include/rt1w.h: rt1w_denoise) ---- */
@@ -1117,6 +1159,8 @@ int rt1w_render_aov_deep_device(rt1w_context* c, const rt1w_render_params* p, ui
     const AovDeep deep{max_specular, max_fuzz};
     return render_aov(c, p, &deep, d_out_aov, false, stats);
 }
+int rt1w_hit(rt1w_context* c, const rt1w_hit_params* p, const double* rays, double* out, uint32_t* out_node, rt1w_stats* stats) { return hit(c, p, rays, out, out_node, true, stats); }
+int rt1w_hit_device(rt1w_context* c, const rt1w_hit_params* p, const void* d_rays, void* d_out, void* d_out_node, rt1w_stats* stats) { return hit(c, p, d_rays, d_out, d_out_node, false, stats); }
 int rt1w_denoise(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, double* out, rt1w_stats* stats) { return denoise(c, p, frame, aov, out, true, stats); }
 int rt1w_denoise_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, void* d_out, rt1w_stats* stats) {
     return denoise(c, p, (const double*)d_frame, (const double*)d_aov, (double*)d_out, false, stats);

@@ -1,4 +1,4 @@
-/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip, temporal.hip and temporal_var.hip, declared once.
+/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip, temporal.hip, temporal_var.hip and hit.hip, declared once.
  * The functions are extern "C": nothing in their names says what they take, so caller and definition both include this header and the
  * compiler holds each definition to the declaration the caller sees.  Private (librt1w.map exports none of them).
  * Every kernel is reached through a typed *_launch: no kernel handle leaves its unit, and no argument array is built by hand.  The
@@ -85,6 +85,12 @@ int rt1w_internal_temporal_moments_launch(uint32_t w, uint32_t h, uint32_t flags
 int rt1w_internal_temporal_variance_launch(uint32_t w, uint32_t h, const double* hist, const double* m2, const double* len, const double* aov,
                                            double* var, hipStream_t stream, unsigned launch[2]);
 unsigned rt1w_internal_temporal_var_sizeof(void);
+/* hit.hip: the ray queries (rt1w_hit): the kernel of `variant` over the params->n rays of `rays` into out (and out_node unless null), all device
+ * memory.  `view` and `params` by address: the bytes of an RtSceneView and an rt1w_hit_params, rt1w_internal_hit_sizeof(0) and (1) of
+ * them, copied into the kernel's arguments; rt1w_internal_hit_sizeof(2): 1 if the unit was built with the staged ray I/O */
+int rt1w_internal_hit_launch(const void* view, const void* params, int variant, const double* rays, double* out, uint32_t* out_node,
+                             hipStream_t stream, unsigned launch[2]);
+unsigned rt1w_internal_hit_sizeof(int what);
 }
 
 #endif

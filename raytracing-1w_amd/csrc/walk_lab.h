@@ -40,6 +40,15 @@ int rt1w_lab_aov_host(const rt1w_scene* s, const rt1w_render_params* p, double* 
 int rt1w_lab_aov_deep_host(const rt1w_scene* s, const rt1w_render_params* p, uint32_t max_specular, double max_fuzz, double* out,
                            uint64_t* segments, uint8_t* lengths);
 
+/* CPU twin of rt1w_hit (aov_host.cpp: rt_hit.h built for the host): the same out[n][12] and out_node[n] (may be null) for a committed
+ * scene, same variant choice (or p->flags' RT1W_FORCE_VARIANT), no GPU.  RT1W_OK, RT1W_ERR_INVALID as the device entry (null pointers,
+ * n, global_seed, flags, overlapping buffers), RT1W_ERR_STATE if a traversal stack overflowed */
+int rt1w_lab_hit_host(const rt1w_scene* s, const rt1w_hit_params* p, const double* rays, double* out, uint32_t* out_node);
+/* the camera rays of a tile: out[tile_h][tile_w][spp][8] = {origin, direction, time, 1} of the ray rt_path_begin gives sample
+ * sample_offset + k of the pixel -- the ray rt1w_render and rt1w_render_aov trace first (main.rs:964-971, camera.rs:61-73).  No GPU;
+ * refusals of rt1w_lab_aov_host */
+int rt1w_lab_camera_rays_host(const rt1w_scene* s, const rt1w_render_params* p, double* out);
+
 /* CPU twin of rt1w_denoise (denoise_host.cpp: rt_denoise.h built for the host): the same double[h][w][3] from host buffers, no GPU.
  * RT1W_OK, or RT1W_ERR_INVALID as the device entry (null pointers, zero sizes, iterations > 8, unknown flags, bad sigmas) */
 int rt1w_lab_denoise_host(const rt1w_denoise_params* p, const double* frame, const double* aov, double* out);
