@@ -1,7 +1,6 @@
 """Shared by test_box_free.py (CPU) and test_box_free_gpu.py: the scenes whose specialised unit sweeps without box tests (rt_core.h:
 rt_sweep_free), what their generated unit declares about it (Topo::vbox, Topo::box_free), and the same answered by an independent walk
 of the flat nodes."""
-import os
 import re
 
 import numpy as np
@@ -121,22 +120,3 @@ def world_bounds(nodes, root):
         d = nodes['d'][root]
         return d[:3].copy(), d[3:6].copy()
     return np.array([-1.0, -1.0, -1.0]), np.array([4.0, 4.0, 4.0])
-
-
-def specialised(ctx_factory, sc, cache, opts):
-    """a context whose scene-specialised kernel is built with `opts` (RT1W_JIT_EXTRA_OPTS is part of a kernel's key)"""
-    keys = ("RT1W_KERNEL_CACHE", "RT1W_JIT_EXTRA_OPTS")
-    old = {k: os.environ.get(k) for k in keys}
-    os.environ["RT1W_KERNEL_CACHE"] = cache
-    os.environ.pop("RT1W_JIT_EXTRA_OPTS", None)
-    if opts:
-        os.environ["RT1W_JIT_EXTRA_OPTS"] = opts
-    try:
-        ctx = ctx_factory(sc)
-        assert ctx.specialise()["active"]
-        return ctx
-    finally:
-        for k in keys:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]

@@ -17,15 +17,6 @@ def root_of(sc):
     return int(np.frombuffer(sc.flat(6).tobytes()[-8:-4], dtype='<u4')[0])
 
 
-def topo_text(sc, name):
-    """`struct TopoJit { ... };` of the generated unit, renamed"""
-    src = sc.kernel_source()
-    body = src[src.index("struct TopoJit {"):]
-    body = body[:body.index("};\n};\n") + len("};\n};\n")]
-    assert "reuse[" in body
-    return body.replace("struct TopoJit", "struct " + name)
-
-
 def reuse_table(sc):
     src = sc.kernel_source()
     m = re.search(r"reuse\[(\d+)\]\[6\] = \{(.*)\};", src)

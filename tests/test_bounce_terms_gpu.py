@@ -3,12 +3,11 @@ of a compare the leaf makes anyway (RT_AHEAD_WORD 2) in the scene-specialised ke
 
 Frames: the kernel as shipped = the same kernel with each switch at its other setting alone (the cone out is the text before both)
 = with both parts in = the generic kernel = the CPU build of the core, byte for byte, segment counts equal."""
-import os
-
 import numpy as np
 import pytest
 
 import bounce_scenes as Bn
+import core_builds as CB
 import orc
 
 pytestmark = pytest.mark.gpu
@@ -20,25 +19,6 @@ SCENES = {f.__name__: f for f in (Bn.cornell, Bn.cornel_smoke, Bn.sphere_only, B
 BUILDS = (None, "-DRT_LIGHT_CONE=0", "-DRT_AHEAD_WORD=2", "-DRT_AHEAD_WORD=2 -DRT_LIGHT_CONE=0")
 
 
-def _specialised(ctx_factory, sc, cache, opts):
-    """a context whose scene-specialised kernel is built with `opts` (RT1W_JIT_EXTRA_OPTS is part of a kernel's key)"""
-    keys = ("RT1W_KERNEL_CACHE", "RT1W_JIT_EXTRA_OPTS")
-    old = {k: os.environ.get(k) for k in keys}
-    os.environ["RT1W_KERNEL_CACHE"] = cache
-    os.environ.pop("RT1W_JIT_EXTRA_OPTS", None)
-    if opts:
-        os.environ["RT1W_JIT_EXTRA_OPTS"] = opts
-    try:
-        ctx = ctx_factory(sc)
-        assert ctx.specialise()["active"]
-        return ctx
-    finally:
-        for k in keys:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
 @pytest.fixture(scope="module")
 def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     """name -> (scene, [a context per build]); built once per scene"""
@@ -48,7 +28,7 @@ def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     def get(name):
         if name not in made:
             sc = SCENES[name](rt)
-            made[name] = (sc, [_specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS])
+            made[name] = (sc, [CB.specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS])
         return made[name]
 
     return get

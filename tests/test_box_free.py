@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import box_free_scenes as B
+import core_builds as CB
 import hit_scenes as H
 import orc
 import slab_scenes as S
@@ -32,23 +33,19 @@ def cases(rt):
 
 
 def _gxx(work, out, *extra):
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-pthread", "-Wno-unknown-pragmas",
-           "-I" + os.path.join(orc.ROOT, "include"), "-I" + os.path.join(orc.ROOT, "raytracing-1w_amd", "csrc"), "-I" + str(work),
-           *extra, os.path.join(orc.ROOT, "tests", "box_free_driver.cpp"), "-o", str(out)]
-    subprocess.check_call(cmd)
+    subprocess.check_call(CB.command(out, os.path.join(orc.ROOT, "tests", "box_free_driver.cpp"), *extra, level="-O2", work=work))
     return out
 
 
 @pytest.fixture(scope="module")
 def driver(cases, tmp_path_factory):
     work = tmp_path_factory.mktemp("box_free")
+    CB.claim_tag("box_free")
     hdr, sw = [], []
     for k, (name, sc) in enumerate(cases.items()):
-        info = sc.info()
-        assert not info["has_media"]
-        hdr.append(S.topo_text(sc, f"Topo{k}") + f"typedef RtCfg<false, {'true' if info['has_textures'] else 'false'}, "
-                   f"{'true' if info['has_moving'] else 'false'}, true, {max(2, info['scope_depth'])}, Topo{k}> CfgB{k};\n")
-        sw.append(f"case {k}: trace<CfgB{k}>(sc, rays, lo, hi, o); break;")
+        assert not sc.info()["has_media"]
+        hdr.append(CB.unit_text(sc, CB.topo_text(sc, "Topo"), "box_free", k))
+        sw.append(f"case {k}: trace<Cfg_box_free_{k}>(sc, rays, lo, hi, o); break;")
     (work / "bf_topo.h").write_text("".join(hdr) + "#define BF_CASES " + " ".join(sw) + "\n")
     lib = C.CDLL(str(_gxx(work, work / "libbox_free.so", "-DRT_BOX_FREE=1", '-DBF_TOPO_H="bf_topo.h"', "-shared")))
     lib.bf_trace.restype = C.c_int
@@ -313,20 +310,17 @@ def test_a_bound_one_ulp_outside_its_parent_is_refused(cases, tmp_path):
     assert tried >= 6
 
 
-def test_frames_of_the_box_free_core_equal_the_generic_core(cases, tmp_path):
+@pytest.fixture(scope="module")
+def frames_lib(cases, tmp_path_factory):
+    """the flat core built around the same Topos with -DRT_BOX_FREE=1; built once, as its tag is given out once"""
+    assert not any(sc.info()["has_media"] for sc in cases.values())
+    return CB.static_lib(tmp_path_factory.mktemp("box_free_frames"), "box_free_frames",
+                         [(name, sc, CB.topo_text(sc, "Topo")) for name, sc in cases.items()], ("-DRT_BOX_FREE=1",))
+
+
+def test_frames_of_the_box_free_core_equal_the_generic_core(cases, frames_lib):
     """whole paths: the flat core built around the same Topos with -DRT_BOX_FREE=1 renders the generic core's frames, bit for bit"""
-    hdr, sw = [], []
-    for k, (name, sc) in enumerate(cases.items()):
-        info = sc.info()
-        hdr.append(S.topo_text(sc, f"Topo{k}") + f"typedef RtCfg<false, {'true' if info['has_textures'] else 'false'}, "
-                   f"{'true' if info['has_moving'] else 'false'}, true, {max(2, info['scope_depth'])}, Topo{k}> CfgS{k};\n")
-        sw.append(f"case {100 + k}: run_path<CfgS{k}>(sc, f, px, py, s, stk, sum, segs, path); break;")
-    (tmp_path / "topo_gen.h").write_text("".join(hdr) + f"#define ORC_N_STATIC {len(cases)}\n#define ORC_STATIC_CASES " + " ".join(sw) + "\n")
-    so = tmp_path / "liborc_flat_box_free.so"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-pthread", "-Wno-unknown-pragmas", "-DRT_BOX_FREE=1",
-                           "-I" + os.path.join(orc.ROOT, "include"), "-I" + os.path.join(orc.ROOT, "raytracing-1w_amd", "csrc"), "-I" + str(tmp_path),
-                           "-DRT_RNG_CHECK", '-DORC_STATIC_TOPO_H="topo_gen.h"', "-shared", os.path.join(orc.ROOT, "oracle", "oracle_flat.cpp"), "-o", str(so)])
-    lib = orc.declare_flat(C.CDLL(str(so)))
+    lib = frames_lib
     for k, (name, sc) in enumerate(cases.items()):
         shape = (48, 48, 6) if name == "cornell" else (28, 20, 4)
         a, sa = orc.flat_render(sc, *shape, chunk=3)

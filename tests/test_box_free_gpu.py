@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import box_free_scenes as B
+import core_builds as CB
 import orc
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     def get(name):
         if name not in made:
             sc = scenes[name]
-            made[name] = (sc,) + tuple(B.specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS)
+            made[name] = (sc,) + tuple(CB.specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS)
         return made[name]
 
     return get

@@ -10,13 +10,11 @@ to that size, both signs.  The real seed is tested on the GPU (test_div_shared_g
 Condition, not a statistic: for every pair whose guards pass, the model's quotient is `n / d` bit for bit and the model's 1/d is
 `1.0 / d` bit for bit; every pair with a zero, infinite, NaN, denormal or out-of-range operand or result raises a guard."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import orc
+import core_builds as CB
 
 SHIM = r"""
 #include "rt1w_num.h"
@@ -57,12 +55,7 @@ def _p(a):
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    work = tmp_path_factory.mktemp("div_shared")
-    (work / "shim.cpp").write_text(SHIM)
-    so = work / "libdiv_shared.so"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(orc.ROOT, "include"), "-shared", str(work / "shim.cpp"), "-o", str(so)])
-    L = C.CDLL(str(so))
+    L = CB.shim_lib(tmp_path_factory.mktemp("div_shared"), "div_shared", SHIM)
     L.ds_lo.restype = L.ds_hi.restype = C.c_double
     return L
 

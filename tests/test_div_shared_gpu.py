@@ -7,11 +7,10 @@ guards pass has the division's bits; every zero, infinity, NaN, denormal and out
 
 Part two, frames: the scene-specialised kernel as shipped = the same kernel built with -DRT_DIV_SHARED=0 (`/` everywhere) = built
 with -DRT_DIV_SHARED_FORCE_SLOW=1 (every wave runs the second sweep) = the generic kernel = the CPU build of the core, byte for byte."""
-import os
-
 import numpy as np
 import pytest
 
+import core_builds as CB
 import hit_scenes as H
 import orc
 import slab_scenes as S
@@ -95,25 +94,6 @@ SCENES = {f.__name__: f for f in (cornell,) + tuple(H.HAND_BUILT) + (S.nan_best_
 BUILDS = (None, "-DRT_DIV_SHARED=0", "-DRT_DIV_SHARED_FORCE_SLOW=1")
 
 
-def _specialised(ctx_factory, sc, cache, opts):
-    """a context whose scene-specialised kernel is built with `opts` (RT1W_JIT_EXTRA_OPTS is part of a kernel's key)"""
-    keys = ("RT1W_KERNEL_CACHE", "RT1W_JIT_EXTRA_OPTS")
-    old = {k: os.environ.get(k) for k in keys}
-    os.environ["RT1W_KERNEL_CACHE"] = cache
-    os.environ.pop("RT1W_JIT_EXTRA_OPTS", None)
-    if opts:
-        os.environ["RT1W_JIT_EXTRA_OPTS"] = opts
-    try:
-        ctx = ctx_factory(sc)
-        assert ctx.specialise()["active"]
-        return ctx
-    finally:
-        for k in keys:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
 @pytest.fixture(scope="module")
 def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     """name -> (scene, context with the kernel as shipped, with `/` everywhere, with the second sweep forced); built once per scene"""
@@ -123,7 +103,7 @@ def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     def get(name):
         if name not in made:
             sc = SCENES[name](rt)
-            made[name] = (sc,) + tuple(_specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS)
+            made[name] = (sc,) + tuple(CB.specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS)
         return made[name]
 
     return get

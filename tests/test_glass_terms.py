@@ -9,15 +9,13 @@ C  one direction build for the cosine lobe and the sphere lobe (rt_lobe_dir_shar
 
 Condition, not a statistic: equal in every bit (a NaN where the other has a NaN), segment counts equal."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import core_builds as CB
 import glass_scenes as G
 import orc
-import slab_scenes as S
 
 IRS = [1.5, 1.0, 0.5, 1.0 / 3.0, 2.4, 1.7976931348623157e308, 5e-324]
 
@@ -118,12 +116,7 @@ def _same_bits(a, b):
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    work = tmp_path_factory.mktemp("glass_terms_shim")
-    (work / "shim.cpp").write_text(SHIM)
-    so = work / "libglass_terms.so"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I" + os.path.join(orc.ROOT, "include"),
-                           "-I" + os.path.join(orc.ROOT, "raytracing-1w_amd", "csrc"), "-shared", str(work / "shim.cpp"), "-o", str(so)])
-    L = C.CDLL(str(so))
+    L = CB.shim_lib(tmp_path_factory.mktemp("glass_terms_shim"), "glass_terms", SHIM, csrc=True)
     L.gt_lo.restype = L.gt_hi.restype = C.c_double
     return L
 
@@ -200,32 +193,19 @@ def cases(rt):
 BUILDS = ([], [G.OFF["A"]], [G.OFF["C"]], G.ALL_OFF.split())
 
 
-def _build(work, cases, extra):
-    work.mkdir()
-    hdr, sw = [], []
-    for k, (_, sc) in enumerate(cases):
-        info = sc.info()
-        shared = "true" if G.OFF["C"] not in extra else "false"
-        hdr.append(S.topo_text(sc, f"Topo{k}") + f"typedef RtCfg<{'true' if info['has_media'] else 'false'}, {'true' if info['has_textures'] else 'false'}, "
-                   f"{'true' if info['has_moving'] else 'false'}, true, {max(2, info['scope_depth'])}, Topo{k}> CfgS{k};\n"
-                   f"static_assert(RtLightShape<Topo{k}>::cone, \"one sphere light: the unit builds the lobes' part\");\n"
-                   f"static_assert(((RT_LOBE_SHARED) != 0) == {shared} && (RT_MAT_DERIVED_ON) == {'true' if G.OFF['A'] not in extra else 'false'}, \"the switches reach the core\");\n")
-        sw.append(f"case {100 + k}: run_path<CfgS{k}>(sc, f, px, py, s, stk, sum, segs, path); break;")
-    (work / "topo_gen.h").write_text("".join(hdr) + f"#define ORC_N_STATIC {len(cases)}\n#define ORC_STATIC_CASES " + " ".join(sw) + "\n")
-    so = work / "liborc_flat_glass.so"
-    cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-pthread", "-Wno-unknown-pragmas",
-           "-I" + os.path.join(orc.ROOT, "include"), "-I" + os.path.join(orc.ROOT, "raytracing-1w_amd", "csrc"), "-I" + str(work),
-           "-DRT_RNG_CHECK", '-DORC_STATIC_TOPO_H="topo_gen.h"'] + extra + ["-shared", os.path.join(orc.ROOT, "oracle", "oracle_flat.cpp"), "-o", str(so)]
-    return subprocess.Popen(cmd), so
+def _command(work, cases, tag, extra):
+    shared, derived = ("true" if G.OFF[part] not in extra else "false" for part in "CA")
+    census = lambda k, name, sc: (f"static_assert(RtLightShape<Topo_{tag}_{k}>::cone, \"one sphere light: the unit builds the lobes' part\");\n"
+                                  f"static_assert(((RT_LOBE_SHARED) != 0) == {shared} && (RT_MAT_DERIVED_ON) == {derived}, \"the switches reach the core\");\n")
+    return CB.static_command(work, tag, [(name, sc, CB.topo_text(sc, "Topo")) for name, sc in cases], extra, per_unit=census)
 
 
 @pytest.fixture(scope="module")
 def libs(cases, tmp_path_factory):
     work = tmp_path_factory.mktemp("glass_terms")
-    builds = [_build(work / f"b{k}", cases, extra) for k, extra in enumerate(BUILDS)]
-    for p, _ in builds:
-        assert p.wait() == 0
-    return [orc.declare_flat(C.CDLL(str(so))) for _, so in builds]
+    builds = [_command(work / f"b{k}", cases, f"glass_terms_b{k}", extra) for k, extra in enumerate(BUILDS)]
+    CB.build_all([cmd for _, cmd in builds])
+    return [orc.declare_flat(C.CDLL(so)) for so, _ in builds]
 
 
 @pytest.mark.parametrize("W,H,chunk", G.FRAMES, ids=lambda v: str(v))

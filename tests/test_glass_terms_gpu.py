@@ -4,11 +4,10 @@ run-time-compiled units, on the GPU, where the real wave masks and the real reci
 Frames: the kernel as shipped = each part alone = all three = none (the text before the change) = the generic kernel = the CPU build of
 the core, byte for byte, segment counts equal; one single-precision render (that build takes none of the parts) and the stack-walk
 kernel on glass (arm 0, which reads the same records)."""
-import os
-
 import numpy as np
 import pytest
 
+import core_builds as CB
 import glass_scenes as G
 import orc
 
@@ -27,25 +26,6 @@ def _opts(parts):
 BUILDS = (None, _opts("A"), _opts("B"), _opts("C"), _opts("ABC"), _opts(""))
 
 
-def _specialised(ctx_factory, sc, cache, opts):
-    """a context whose scene-specialised kernel is built with `opts` (RT1W_JIT_EXTRA_OPTS is part of a kernel's key)"""
-    keys = ("RT1W_KERNEL_CACHE", "RT1W_JIT_EXTRA_OPTS")
-    old = {k: os.environ.get(k) for k in keys}
-    os.environ["RT1W_KERNEL_CACHE"] = cache
-    os.environ.pop("RT1W_JIT_EXTRA_OPTS", None)
-    if opts:
-        os.environ["RT1W_JIT_EXTRA_OPTS"] = opts
-    try:
-        ctx = ctx_factory(sc)
-        assert ctx.specialise()["active"]
-        return ctx
-    finally:
-        for k in keys:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
 @pytest.fixture(scope="module")
 def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     """name -> (scene, [a context per build]); built once per scene"""
@@ -55,7 +35,7 @@ def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     def get(name):
         if name not in made:
             sc = SCENES[name](rt)
-            made[name] = (sc, [_specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS])
+            made[name] = (sc, [CB.specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS])
         return made[name]
 
     return get

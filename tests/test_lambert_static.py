@@ -1,13 +1,10 @@
 """Static lights and wall frames in the Lambertian shading of the scene-specialised kernels (rt_core.h: RtLightShape, RtLambertWalls,
 rt_wall_frame): the flat core built on the CPU around the library's own generated Topo (Scene.kernel_source) against the generic
 core, bit for bit, and what the generated text declares."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import core_builds as CB
 import lambert_scenes as L
 import orc
 import slab_scenes as S
@@ -31,21 +28,9 @@ def cases(rt):
 def static_lib(cases, tmp_path_factory):
     work = tmp_path_factory.mktemp("lambert_static")
     by_name = dict(cases)
-    topos = [(name, sc, S.topo_text(sc, f"Topo{k}")) for k, (name, sc) in enumerate(cases)]
-    topos += [(name + "_stripped", by_name[name], L.strip_new_members(S.topo_text(by_name[name], f"Topo{len(cases) + j}"))) for j, name in enumerate(STRIPPED)]
-    hdr, sw = [], []
-    for k, (name, sc, topo) in enumerate(topos):
-        info = sc.info()
-        hdr.append(topo + f"typedef RtCfg<{'true' if info['has_media'] else 'false'}, {'true' if info['has_textures'] else 'false'}, "
-                   f"{'true' if info['has_moving'] else 'false'}, true, {max(2, info['scope_depth'])}, Topo{k}> CfgS{k};\n")
-        sw.append(f"case {100 + k}: run_path<CfgS{k}>(sc, f, px, py, s, stk, sum, segs, path); break;")
-    (work / "topo_gen.h").write_text("".join(hdr) + f"#define ORC_N_STATIC {len(topos)}\n#define ORC_STATIC_CASES " + " ".join(sw) + "\n")
-    so = work / "liborc_flat_lambert.so"
-    cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-pthread", "-Wno-unknown-pragmas",
-           "-I" + os.path.join(orc.ROOT, "include"), "-I" + os.path.join(orc.ROOT, "raytracing-1w_amd", "csrc"), "-I" + str(work),
-           "-DRT_RNG_CHECK", '-DORC_STATIC_TOPO_H="topo_gen.h"', "-shared", os.path.join(orc.ROOT, "oracle", "oracle_flat.cpp"), "-o", str(so)]
-    subprocess.check_call(cmd)
-    return orc.declare_flat(C.CDLL(str(so))), [(name, sc) for name, sc, _ in topos]
+    topos = [(name, sc, CB.topo_text(sc, "Topo")) for name, sc in cases]
+    topos += [(name + "_stripped", by_name[name], L.strip_new_members(CB.topo_text(by_name[name], "Topo"))) for name in STRIPPED]
+    return CB.static_lib(work, "lambert_static", topos), [(name, sc) for name, sc, _ in topos]
 
 
 @pytest.fixture(scope="module")
@@ -53,7 +38,7 @@ def generic_frames(cases):
     """the generic core's frame and statistics of every scene, rendered once"""
     out = {}
     for name, sc in cases:
-        W, H, spp = (48, 48, 6) if "cornel" in name else (28, 20, 4)
+        W, H, spp = CB.small_frame(name)
         out[name] = (W, H, spp) + orc.flat_render(sc, W, H, spp, chunk=3)
     return out
 

@@ -6,15 +6,13 @@ and the part's own functions against the ones they stand for on random operands.
 Condition, not a statistic: every frame equal in every bit (a NaN where the other has a NaN), the segment counts equal, every pair
 of squared distances and every pdf value equal in every bit."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bounce_scenes as Bn
+import core_builds as CB
 import orc
-import slab_scenes as S
 
 
 @pytest.fixture(scope="module")
@@ -22,20 +20,10 @@ def cases(rt):
     return [(f.__name__, f(rt)) for f in Bn.SCENES]
 
 
-def _build(work, cases, name, extra):
-    hdr, sw = [], []
-    for k, (_, sc) in enumerate(cases):
-        info = sc.info()
-        hdr.append(S.topo_text(sc, f"Topo{k}") + f"typedef RtCfg<{'true' if info['has_media'] else 'false'}, {'true' if info['has_textures'] else 'false'}, "
-                   f"{'true' if info['has_moving'] else 'false'}, true, {max(2, info['scope_depth'])}, Topo{k}> CfgS{k};\n"
-                   f"static_assert(RtLightShape<Topo{k}>::cone == {'true' if Bn.ELIGIBLE[cases[k][0]] and not extra else 'false'}, \"which units build the part\");\n")
-        sw.append(f"case {100 + k}: run_path<CfgS{k}>(sc, f, px, py, s, stk, sum, segs, path); break;")
-    (work / "topo_gen.h").write_text("".join(hdr) + f"#define ORC_N_STATIC {len(cases)}\n#define ORC_STATIC_CASES " + " ".join(sw) + "\n")
-    so = work / name
-    cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-pthread", "-Wno-unknown-pragmas",
-           "-I" + os.path.join(orc.ROOT, "include"), "-I" + os.path.join(orc.ROOT, "raytracing-1w_amd", "csrc"), "-I" + str(work),
-           "-DRT_RNG_CHECK", '-DORC_STATIC_TOPO_H="topo_gen.h"'] + extra + ["-shared", os.path.join(orc.ROOT, "oracle", "oracle_flat.cpp"), "-o", str(so)]
-    return subprocess.Popen(cmd), so
+def _command(work, cases, tag, extra):
+    census = lambda k, name, sc: (f"static_assert(RtLightShape<Topo_{tag}_{k}>::cone == {'true' if Bn.ELIGIBLE[name] and not extra else 'false'}, "
+                                  "\"which units build the part\");\n")
+    return CB.static_command(work, tag, [(name, sc, CB.topo_text(sc, "Topo")) for name, sc in cases], extra, per_unit=census)
 
 
 @pytest.fixture(scope="module")
@@ -43,12 +31,9 @@ def libs(cases, tmp_path_factory):
     """(the core with the cone, the core built with -DRT_LIGHT_CONE=0): the static_assert in each unit's text is the census -- which
     Topo builds the part is checked by the compiler, in both builds"""
     work = tmp_path_factory.mktemp("light_cone")
-    (work / "on").mkdir()
-    (work / "off").mkdir()
-    builds = [_build(work / "on", cases, "liborc_flat_cone.so", []), _build(work / "off", cases, "liborc_flat_nocone.so", ["-DRT_LIGHT_CONE=0"])]
-    for p, _ in builds:
-        assert p.wait() == 0
-    return tuple(orc.declare_flat(C.CDLL(str(so))) for _, so in builds)
+    builds = [_command(work / "on", cases, "light_cone_on", []), _command(work / "off", cases, "light_cone_off", ["-DRT_LIGHT_CONE=0"])]
+    CB.build_all([cmd for _, cmd in builds])
+    return tuple(orc.declare_flat(C.CDLL(so)) for so, _ in builds)
 
 
 def test_the_generated_units_say_which_build_the_part(cases):
@@ -109,12 +94,7 @@ void lc_pdf(const double* o, const double* c, const double* r, const double* v, 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    work = tmp_path_factory.mktemp("light_cone_shim")
-    (work / "shim.cpp").write_text(SHIM)
-    so = work / "liblight_cone.so"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I" + os.path.join(orc.ROOT, "include"),
-                           "-I" + os.path.join(orc.ROOT, "raytracing-1w_amd", "csrc"), "-shared", str(work / "shim.cpp"), "-o", str(so)])
-    return C.CDLL(str(so))
+    return CB.shim_lib(tmp_path_factory.mktemp("light_cone_shim"), "light_cone", SHIM, csrc=True)
 
 
 def _p(a):

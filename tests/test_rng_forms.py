@@ -2,13 +2,11 @@
 samplers without rand 0.8's retry loop, against rt_take_range(r, -1.0, 1.0), which keeps the loop -- bits and generator state; and
 rt_xor3's plain form, the one every target but gfx950 compiles.  The header is built with g++ as the CPU twins build it."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import orc
+import core_builds as CB
 
 SHIM = r"""
 #include "rt1w_num.h"
@@ -63,12 +61,7 @@ def _p(a):
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    work = tmp_path_factory.mktemp("rng_forms")
-    (work / "shim.cpp").write_text(SHIM)
-    so = work / "librng_forms.so"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(orc.ROOT, "include"), "-shared", str(work / "shim.cpp"), "-o", str(so)])
-    return C.CDLL(str(so))
+    return CB.shim_lib(tmp_path_factory.mktemp("rng_forms"), "rng_forms", SHIM)
 
 
 def _words(lib, w):

@@ -2,12 +2,11 @@
 generates, checked against the flat scene in plain Python, and the unrolled sweep built on the CPU around the library's own
 table (Scene.kernel_source) against the generic sweep, bit for bit."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import core_builds as CB
 import orc
 import slab_scenes as S
 from dual import random_scene_pair
@@ -32,26 +31,13 @@ def cases(rt):
 @pytest.fixture(scope="module")
 def static_lib(cases, tmp_path_factory):
     work = tmp_path_factory.mktemp("slab_reuse")
-    hdr = ["std::atomic<unsigned long long> orc_slab_forms[2];\n"
-           'extern "C" unsigned long long orc_slab_form_count(int literal) { return orc_slab_forms[literal].exchange(0); }\n']
-    sw = []
-    for k, (name, sc) in enumerate(cases):
-        info = sc.info()
-        hdr.append(S.topo_text(sc, f"Topo{k}") +
-                   f"typedef RtCfg<{'true' if info['has_media'] else 'false'}, {'true' if info['has_textures'] else 'false'}, "
-                   f"{'true' if info['has_moving'] else 'false'}, true, {max(2, info['scope_depth'])}, Topo{k}> CfgS{k};\n")
-        sw.append(f"case {100 + k}: run_path<CfgS{k}>(sc, f, px, py, s, stk, sum, segs, path); break;")
-    (work / "topo_gen.h").write_text("".join(hdr) + f"#define ORC_N_STATIC {len(cases)}\n#define ORC_STATIC_CASES " + " ".join(sw) + "\n")
+    counters = ("std::atomic<unsigned long long> orc_slab_forms[2];\n"
+                'extern "C" unsigned long long orc_slab_form_count(int literal) { return orc_slab_forms[literal].exchange(0); }\n')
     # which form each box test of the unrolled sweep took (RT_STAT_SLAB, rt_core.h), counted for the whole library
     (work / "slab_stat.h").write_text("#include <atomic>\nextern std::atomic<unsigned long long> orc_slab_forms[2];\n"
                                       "#define RT_STAT_SLAB(literal) ((void)orc_slab_forms[literal].fetch_add(1, std::memory_order_relaxed))\n")
-    so = work / "liborc_flat_slab.so"
-    cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-pthread", "-Wno-unknown-pragmas",
-           "-I" + os.path.join(orc.ROOT, "include"), "-I" + os.path.join(orc.ROOT, "raytracing-1w_amd", "csrc"), "-I" + str(work),
-           "-include", "slab_stat.h", "-DRT_RNG_CHECK", '-DORC_STATIC_TOPO_H="topo_gen.h"', "-shared",
-           os.path.join(orc.ROOT, "oracle", "oracle_flat.cpp"), "-o", str(so)]
-    subprocess.check_call(cmd)
-    lib = orc.declare_flat(C.CDLL(str(so)))
+    lib = CB.static_lib(work, "slab_reuse", [(name, sc, CB.topo_text(sc, "Topo")) for name, sc in cases], ("-include", "slab_stat.h"),
+                        prologue=counters)
     lib.orc_slab_form_count.restype = C.c_ulonglong
     lib.orc_slab_form_count.argtypes = [C.c_int]
     return lib
@@ -114,7 +100,7 @@ def test_unrolled_sweep_with_the_table_equals_generic_sweep(cases, static_lib):
     assert lib.orcflat_n_static() == len(cases)
     lib.orc_slab_form_count(0), lib.orc_slab_form_count(1)
     for k, (name, sc) in enumerate(cases):
-        W, H, spp = (48, 48, 6) if "cornel" in name else (28, 20, 4)
+        W, H, spp = CB.small_frame(name)
         a, sa = orc.flat_render(sc, W, H, spp, chunk=3)
         b, sb = orc.flat_render(sc, W, H, spp, chunk=3, variant=100 + k, lib=lib)
         fast, literal = lib.orc_slab_form_count(0), lib.orc_slab_form_count(1)

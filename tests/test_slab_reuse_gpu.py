@@ -1,9 +1,8 @@
 """The scene-specialised kernels with slab products taken from the boxes above (Topo::reuse, rt_aabb_hit_chain) on the GPU:
 the same bits as the generic kernels and as the CPU build of the core.  The table itself is checked in test_slab_reuse.py."""
-import numpy as np
 import pytest
 
-import orc
+import core_builds as CB
 import slab_scenes as S
 
 pytestmark = pytest.mark.gpu
@@ -13,35 +12,16 @@ pytestmark = pytest.mark.gpu
 def test_reference_arms_specialised_generic_and_cpu_core_agree(rt, gpu_ctx_factory, arm, W, H, spp):
     sc = rt.Scene.reference(arm, build_seed=1)
     assert S.counts(S.reuse_table(sc))[0] > 0
-    ctx = gpu_ctx_factory(sc)
-    assert ctx.specialised(), "no precompiled kernel found next to the library"
-    a, sa = ctx.render(W, H, spp)
-    b, sb = ctx.render(W, H, spp, generic=True)
-    f, sf = orc.flat_render(sc, W, H, spp, chunk=sa["chunk"])
-    assert (sa["sorted"] & 4) and not (sb["sorted"] & 4)
-    assert sa["segments"] == sb["segments"] == sf["segments"]
-    assert np.array_equal(a, b, equal_nan=True) and np.array_equal(a, f, equal_nan=True)
+    CB.agree_specialised_generic_core(gpu_ctx_factory(sc), sc, W, H, spp)
 
 
 @pytest.mark.parametrize("build", S.HAND_BUILT, ids=lambda f: f.__name__)
 def test_hand_built_scenes_compiled_at_run_time(rt, gpu_ctx_factory, tmp_path, monkeypatch, build):
     monkeypatch.setenv("RT1W_KERNEL_CACHE", str(tmp_path / "kcache"))
     sc = build(rt)
-    ctx = gpu_ctx_factory(sc)
-    b, sb = ctx.render(32, 32, 4)
-    assert not (sb["sorted"] & 4)
-    info = ctx.specialise()
-    assert info["active"] and not info["from_cache"]
-    a, sa = ctx.render(32, 32, 4)
-    f, sf = orc.flat_render(sc, 32, 32, 4, chunk=sa["chunk"])
-    assert (sa["sorted"] & 4) and sa["segments"] == sb["segments"] == sf["segments"]
-    assert np.array_equal(a, b, equal_nan=True) and np.array_equal(a, f, equal_nan=True)
+    CB.agree_compiled_at_run_time(gpu_ctx_factory(sc), sc)
 
 
 def test_f32_specialised_cornell_equals_f32_generic(rt, gpu_ctx_factory):
     sc = rt.Scene.reference(5, build_seed=1)
-    ctx = gpu_ctx_factory(sc)
-    a, sa = ctx.render(64, 64, 8, f32=True)
-    b, sb = ctx.render(64, 64, 8, f32=True, generic=True)
-    assert (sa["sorted"] & 4) and not (sb["sorted"] & 4)
-    assert sa["segments"] == sb["segments"] and np.array_equal(a, b, equal_nan=True)
+    CB.agree_f32_specialised_generic(gpu_ctx_factory(sc))

@@ -5,13 +5,11 @@ them (what the DPP row shifts and row broadcasts of the device do) and follows t
 lane, the scan, the fetch from the lane that holds the base, the idle total from the scan's last class.  The header is built with g++ as
 the CPU twins build it."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import orc
+import core_builds as CB
 
 N_CLS, IDLE = 6, 5   # csrc/rt_core.h: RT_N_CLS, RT_CLS_IDLE
 
@@ -105,12 +103,7 @@ extern "C" uint32_t sort_many(uint32_t nw, uint64_t n, const uint8_t* cls, uint3
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    work = tmp_path_factory.mktemp("sort_scan")
-    (work / "shim.cpp").write_text(SHIM)
-    so = work / "libsort_scan.so"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(orc.ROOT, "include"), "-shared", str(work / "shim.cpp"), "-o", str(so)])
-    lib = C.CDLL(str(so))
+    lib = CB.shim_lib(tmp_path_factory.mktemp("sort_scan"), "sort_scan", SHIM)
     lib.sort_many.restype = C.c_uint32
     return lib
 

@@ -7,7 +7,7 @@ test_sort_scan.py."""
 import numpy as np
 import pytest
 
-import box_free_scenes as B
+import core_builds as CB
 import hit_scenes as H
 import orc
 import test_wave_rounds_gpu as WR
@@ -47,7 +47,7 @@ def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     def get(name):
         if name not in made:
             sc = SCENES[name](rt)
-            made[name] = (sc,) + tuple(B.specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS)
+            made[name] = (sc,) + tuple(CB.specialised(gpu_ctx_factory, sc, cache, o) for o in BUILDS)
         return made[name]
 
     return get

@@ -13,12 +13,11 @@ build here; RT_DIV_SHARED is device text only and its switch changes nothing in 
 import ctypes as C
 import json
 import os
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
+import core_builds as CB
 import orc
 import spec_graphs as G
 from test_random_scenes import RTOL, close
@@ -46,13 +45,6 @@ def censuses(corpus):
     return {name: G.census(prod) for name, (_, prod, _) in corpus.items()}
 
 
-def topo_text(sc, name, f32=False):
-    """`struct TopoJit { ... };` of the generated unit (of either precision), renamed"""
-    src = sc.kernel_source(f32=f32)
-    body = src[src.index("struct TopoJit {"):]
-    return body[:body.index("};\n};\n") + len("};\n};\n")].replace("struct TopoJit", "struct " + name)
-
-
 def f32_names(censuses):
     """8 graphs of each source for the f32 twin: four that sweep without boxes in f64 and four that do not, the first of the lists, none
     of the large ones"""
@@ -65,24 +57,8 @@ def f32_names(censuses):
 
 
 def _command(work, tag, scenes, flags, f32):
-    """writes <tag>/topo_gen.h for `scenes` (variant 100 + k) and returns the compiler's command line for lib<tag>.so"""
-    d = work / tag
-    d.mkdir()
-    hdr, sw = [], []
-    for k, sc in enumerate(scenes):
-        info = sc.info()
-        # type names of this library alone: a static member of a template over a Topo is one object per NAME in the whole process,
-        # however many libraries define it, and these libraries are all loaded into one
-        topo, cfg = f"Topo_{tag}_{k}", f"Cfg_{tag}_{k}"
-        hdr.append(topo_text(sc, topo, f32) + f"typedef RtCfg<{'true' if info['has_media'] else 'false'}, {'true' if info['has_textures'] else 'false'}, "
-                   f"{'true' if info['has_moving'] else 'false'}, true, {max(2, info['scope_depth'])}, {topo}> {cfg};\n")
-        sw.append(f"case {100 + k}: run_path<{cfg}>(sc, f, px, py, s, stk, sum, segs, path); break;")
-    (d / "topo_gen.h").write_text("".join(hdr) + f"#define ORC_N_STATIC {len(scenes)}\n#define ORC_STATIC_CASES " + " ".join(sw) + "\n")
-    so = d / f"lib{tag}.so"
-    return so, ["g++", "-O1", *flags, "-std=c++17", "-fPIC", "-ffp-contract=off", "-pthread", "-Wno-unknown-pragmas",
-                "-I" + os.path.join(orc.ROOT, "include"), "-I" + os.path.join(orc.ROOT, "raytracing-1w_amd", "csrc"), "-I" + str(d),
-                "-DRT_RNG_CHECK", '-DORC_STATIC_TOPO_H="topo_gen.h"', "-shared",
-                os.path.join(orc.ROOT, "oracle", "oracle_flat_f32.cpp" if f32 else "oracle_flat.cpp"), "-o", str(so)]
+    """writes <tag>/topo_gen.h for `scenes` (variant 100 + k) and returns the library's path and the compiler's command line"""
+    return CB.static_command(work / tag, "fuzz_" + tag, [(None, sc, CB.topo_text(sc, "Topo", f32)) for sc in scenes], flags, f32)
 
 
 @pytest.fixture(scope="module")
@@ -104,8 +80,7 @@ def libs(corpus, censuses, tmp_path_factory):
     batch = f32_names(censuses)
     jobs.append(("f32", batch) + _command(work, "f32", [corpus[n][1] for n in batch], (), True))
     t0 = time.time()
-    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
-        list(pool.map(lambda j: subprocess.check_call(j[3]), jobs))
+    CB.build_all([j[3] for j in jobs])
     print(f"spec_fuzz: {len(jobs)} host libraries in {time.time() - t0:.0f} s")
     out = {}
     for build, batch, so, _ in jobs:
@@ -204,7 +179,7 @@ def test_f32_specialised_twin_equals_f32_generic_twin(corpus, censuses, libs):
     assert len(names) == 2 * N_F32 and sum(censuses[n]["box_free"] for n in names) >= N_F32 // 2
     for name in names:
         _, prod, _ = corpus[name]
-        assert topo_text(prod, "T", f32=True) == topo_text(prod, "T"), name   # both precisions declare the same members
+        assert CB.topo_text(prod, "T", f32=True) == CB.topo_text(prod, "T"), name   # both precisions declare the same members
         lib, variant = libs[("f32", name)]
         for depth in DEPTHS:
             a, sa = orc.flat_f32_render(prod, W, HGT, SPP, max_depth=depth, chunk=CHUNK)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import box_free_scenes as BF
+import core_builds as CB
 import orc
 import spec_graphs as G
 
@@ -72,7 +73,7 @@ def test_box_free_builds_have_the_shipped_bits(gpu_ctx_factory, tmp_path, name):
     shipped = {}
     keys = set()
     for opts in (None, "-DRT_BOX_FREE=0", "-DRT_DIV_SHARED_FORCE_SLOW=1"):
-        ctx = BF.specialised(gpu_ctx_factory, prod, str(tmp_path), opts)
+        ctx = CB.specialised(gpu_ctx_factory, prod, str(tmp_path), opts)
         try:
             keys.add(ctx.specialise()["key"])
             for W, H, spp, chunk in FRAMES:

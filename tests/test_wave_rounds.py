@@ -3,13 +3,11 @@ rt_sphere_round, rt_disk_round, rt_rng_after_round) against the looped samplers 
 a wave (rt_wave_rounds_log2, rt_wave_slot, rt_wave_first) in an emulation of 64 lanes that runs the very functions the kernels run.
 The header is built with g++ as the CPU twins build it; the two loops are the text of csrc/rt_core.h's samplers."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import orc
+import core_builds as CB
 
 SHIM = r"""
 #include "rt1w_num.h"
@@ -141,12 +139,7 @@ def _p(a):
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    work = tmp_path_factory.mktemp("wave_rounds")
-    (work / "shim.cpp").write_text(SHIM)
-    so = work / "libwave_rounds.so"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(orc.ROOT, "include"), "-shared", str(work / "shim.cpp"), "-o", str(so)])
-    lib = C.CDLL(str(so))
+    lib = CB.shim_lib(tmp_path_factory.mktemp("wave_rounds"), "wave_rounds", SHIM)
     lib.wr_wave.restype = C.c_uint32
     lib.wr_k_log2.restype = C.c_uint32
     return lib

@@ -3,11 +3,10 @@ which ships, and the camera's unit disk, which stays behind the switch) on the G
 scene-specialised and generic, give the frames of the CPU build of the core, which keeps the loops, and of the same specialised kernel
 built with -DRT_WAVE_ROUNDS=0 (the loops) and -DRT_WAVE_ROUNDS=3 (both parts), bit for bit.  The arithmetic and the assignment of
 rounds to lanes are checked on the CPU in test_wave_rounds.py."""
-import os
-
 import numpy as np
 import pytest
 
+import core_builds as CB
 import lambert_scenes as L
 import orc
 
@@ -53,25 +52,6 @@ def open_lens(rt):
 SCENES = {f.__name__: f for f in (cornell, metal_enclosure, metal_marble, open_lens)}
 
 
-def _specialised(ctx_factory, sc, cache, opts):
-    """a context whose scene-specialised kernel is built with `opts` (RT1W_JIT_EXTRA_OPTS is part of a kernel's key)"""
-    keys = ("RT1W_KERNEL_CACHE", "RT1W_JIT_EXTRA_OPTS")
-    old = {k: os.environ.get(k) for k in keys}
-    os.environ["RT1W_KERNEL_CACHE"] = cache
-    os.environ.pop("RT1W_JIT_EXTRA_OPTS", None)
-    if opts:
-        os.environ["RT1W_JIT_EXTRA_OPTS"] = opts
-    try:
-        ctx = ctx_factory(sc)
-        assert ctx.specialise()["active"]
-        return ctx
-    finally:
-        for k in keys:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
 @pytest.fixture(scope="module")
 def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     """name -> (scene, context with the kernel as shipped, with the loops, with both parts of the form); built once per scene"""
@@ -81,7 +61,7 @@ def kernels(rt, gpu_ctx_factory, tmp_path_factory):
     def get(name):
         if name not in made:
             sc = SCENES[name](rt)
-            made[name] = (sc,) + tuple(_specialised(gpu_ctx_factory, sc, cache, o) for o in (None, "-DRT_WAVE_ROUNDS=0", "-DRT_WAVE_ROUNDS=3"))
+            made[name] = (sc,) + tuple(CB.specialised(gpu_ctx_factory, sc, cache, o) for o in (None, "-DRT_WAVE_ROUNDS=0", "-DRT_WAVE_ROUNDS=3"))
         return made[name]
 
     return get
