@@ -428,6 +428,56 @@ int rt1w_hit(rt1w_context* c, const rt1w_hit_params* params, const double* rays,
 int rt1w_hit_device(rt1w_context* c, const rt1w_hit_params* params, const void* d_rays, void* d_out, void* d_out_node /* may be NULL */,
                     rt1w_stats* stats);
 
+/* ---- radiance queries: ray_color for a list of the caller's own rays ----
+ * For every ray r of 0 .. n - 1 and every sample k of 0 .. spp - 1: ray_color(ray, background, world, lights, max_depth, rng) (main.rs:51-116;
+ * a scene without lights :118-190) -- the other half of the reference's sample loop (main.rs:964-989), which rt1w_render reaches through
+ * Camera::get_ray (camera.rs:61-73) alone.  The rays run through the kernels rt1w_render runs with RT1W_GENERIC -- the reordering
+ * kernel of small scenes, the sliced stack walk with the node cache and slice-end reordering, the pair walk of sphere scenes -- built
+ * once more with the ray's record where the camera was: traversal, shading, draw order and sums are the render's text.
+ *   rays  double[n][stride] = origin xyz, direction xyz, time (Ray, ray.rs:5); the record's other doubles are not read (stride 9 takes
+ *         rt1w_hit's records as they are).  The direction is used as given; the bounds are ray_color's own, 0.001 and +inf (main.rs:62).
+ *   start_word  (may be NULL: all 0) uint32[n], see below.
+ *   out   double[n][3]: with RT1W_OUT_SUM the raw sum over the ray's samples, else Color::into_sampled(sum, spp) (color.rs:14-21, the NaN
+ *         scrub included).  The sums are made exactly as rt1w_render makes a pixel's: per work item of `chunk` samples in sample order,
+ *         then the items in order.
+ * Streams.  Sample k of ray r draws from the Philox stream of (pixel seed first_stream + r, sample sample_offset + k, global_seed) -- the
+ * stream a render gives that pixel's sample (main.rs:964) -- starting at word start_word[r] of it: word index = 4 * block + word in block,
+ * the RtRngPos of include/rt1w_num.h as one number (rt_rng_at puts a stream there).  The same start_word[r] serves each of the ray's
+ * samples.  Two consequences:
+ *   - a list split into two calls, the second with first_stream advanced by the first call's ray count, gives the same values bit for bit;
+ *   - given the camera ray of pixel (i, j), sample s, and the position that ray's stream has after Camera::get_ray (camera.rs:61-73), with
+ *     first_stream + r = j * width + i and sample_offset = s, the entry returns that sample of rt1w_render, bit for bit.
+ * ONE DEVIATION from the literal ray_color, the one rt1w_hit has: a ray with a non-finite value (an infinity or a NaN) among origin,
+ * direction and time is not traced; each of its samples is a miss -- the background (main.rs:64-66), or 0 at max_depth 0 (main.rs:59-61).
+ * Everything finite is literal: a zero direction, denormals, huge values.
+ * RT1W_ERR_INVALID: a null context, params, rays or out; n = 0 or n > 2^32 - 1; spp = 0; sample_offset + spp > 2^32 - 1; global_seed >=
+ * 2^32; stride 1 .. 6; any flag but RT1W_OUT_SUM and RT1W_GENERIC (RT1W_RNG_REFERENCE included: the reference stream has no positions);
+ * reserved != 0; out overlapping rays or start_word.  f64 only: the block has no precision member.
+ * stats: paths = n * spp; segments = rays traced (a ray that is not traced counts none); passes, variant, sorted, grid, block, chunk and
+ * n_chunks as rt1w_render's with RT1W_GENERIC on a frame of n x 1 pixels.  A context that holds a scene-specialised kernel runs the
+ * generic ray-list kernel: the same bits, `sorted` says what ran.  Bit-identical to the CPU build of the same code (librt1w_lab.so:
+ * rt1w_lab_ray_color_host). */
+typedef struct rt1w_ray_color_params {
+    uint64_t n;             /* rays, 1 .. 2^32 - 1 */
+    uint64_t first_stream;  /* ray r draws from the streams of pixel seed first_stream + r */
+    uint64_t global_seed;   /* as rt1w_render_params.global_seed; below 2^32 */
+    uint32_t spp;           /* samples per ray: streams (first_stream + r, sample_offset + k), k = 0 .. spp - 1 */
+    uint32_t sample_offset;
+    uint32_t max_depth;     /* the `depth` argument of ray_color; 0 gives 0 (main.rs:59-61) */
+    uint32_t chunk;         /* samples per work item, 0 = rt1w_scene_default_chunk(scene, (uint32_t)n, 1, spp) */
+    uint32_t stride;        /* doubles from one ray record to the next, >= 7; 0 = 7 */
+    uint32_t flags;         /* 0, RT1W_OUT_SUM, RT1W_GENERIC (a no-op: the generic kernels run anyway) */
+    uint32_t partial_mib;   /* as rt1w_render_params.partial_mib: the budget of the chunk partial sums, 0 = default */
+    uint32_t reserved;      /* 0 */
+} rt1w_ray_color_params; /* 56 bytes; rt1w_abi_sizeof(8) */
+/* host memory in and out (through the context's device buffers, grown on demand and freed with the context); ray_color, main.rs:51-116 */
+int rt1w_ray_color(rt1w_context* c, const rt1w_ray_color_params* params, const double* rays, const uint32_t* start_word /* may be NULL */,
+                   double* out, rt1w_stats* stats);
+/* same, on device memory of the context's GPU (e.g. torch tensors): d_rays double[n][stride], d_start_word uint32[n] or NULL, d_out
+ * double[n][3]; no host copy.  Synchronises the context's stream before returning.  ray_color, main.rs:51-116 */
+int rt1w_ray_color_device(rt1w_context* c, const rt1w_ray_color_params* params, const void* d_rays, const void* d_start_word /* may be NULL */,
+                          void* d_out, rt1w_stats* stats);
+
 /* ---- feature-guided denoiser: the consumer of the feature buffers above ----
  * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) over an image and its first-hit feature buffers.
  * Replaces nothing of the reference, which reaches a clean image by sample count alone (10 000 spp for final_scene, src/main.rs:939).
@@ -1053,8 +1103,8 @@ int rt1w_quantize(const double* means, uint64_t n_values, uint8_t* out);
 int64_t rt1w_format_ppm(const double* means, uint32_t width, uint32_t height, char* buf, uint64_t cap);
 
 /* sizeof of the ABI structs as this library was compiled (bindings check their own layout against it):
- * 0 rt1w_render_params, 1 rt1w_stats, 2 rt1w_scene_info, 3 rt1w_specialise_info, 4 rt1w_denoise_params, 6 rt1w_camera; 0 for anything else
- * (5 is not given out: it stays the code that answers 0) */
+ * 0 rt1w_render_params, 1 rt1w_stats, 2 rt1w_scene_info, 3 rt1w_specialise_info, 4 rt1w_denoise_params, 6 rt1w_camera,
+ * 8 rt1w_ray_color_params; 0 for anything else (5 and 7 are not given out: they stay codes that answer 0) */
 uint32_t rt1w_abi_sizeof(int what);
 
 /* ---- diagnostics ---- */

@@ -659,6 +659,24 @@ RT_HD RtRngPos rt_rng_pos(const RtRng& r) {
     p.off = (4u - r.left) & 3u;
     return p;
 }
+/* The way back: the stream `r` (fresh from rt_rng_make: its key and counter words) standing at word `word` = 4 * blk + off, one number
+ * where a caller hands a position over (rt1w_ray_color's start_word: the first 2^32 words of a stream).  It draws the words a stream that
+ * got there by drawing draws: A holds the tail of block word / 4 from word % 4 on, B is empty (a stream that drew its way may hold a
+ * block ahead in B instead; that changes no word anyone draws). */
+RT_HD RtRng rt_rng_at(RtRng r, uint32_t word) {
+    const uint32_t off = word & 3u;
+    r.blk = word >> 2; r.left = 0u; r.bv = 0u;
+    if (off != 0u) {
+        rt_rng_gen_b(r);
+        r.a0 = off == 1u ? r.b1 : (off == 2u ? r.b2 : r.b3);
+        r.a1 = off == 1u ? r.b2 : r.b3;
+        r.a2 = r.b3; r.a3 = r.b3;
+        r.left = 4u - off; r.bv = 0u;
+    }
+    return r;
+}
+/* rt_rng_pos as that one number (a stream within its first 2^30 blocks) */
+RT_HD uint32_t rt_rng_word(const RtRng& r) { const RtRngPos p = rt_rng_pos(r); return p.blk * 4u + p.off; }
 /* where the next 64-bit draw starts (rt_take_u64's even-alignment) */
 RT_HD RtRngPos rt_rng_pos_even(const RtRng& r) {
     RtRngPos p = rt_rng_pos(r);

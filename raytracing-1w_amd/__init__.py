@@ -290,6 +290,19 @@ HIT_NO_NODE = 0xFFFFFFFF  # the node index of a miss
 _sig("rt1w_hit", C.c_int, _P, C.POINTER(HitParams), _P, _P, _P, C.POINTER(Stats))
 _sig("rt1w_hit_device", C.c_int, _P, C.POINTER(HitParams), _P, _P, _P, C.POINTER(Stats))
 
+
+class RayColorParams(C.Structure):
+    """rt1w_ray_color_params: n rays, spp samples each; sample k of ray r draws from the stream of pixel seed first_stream + r, sample
+    sample_offset + k, `global_seed`."""
+    _fields_ = [("n", C.c_uint64), ("first_stream", C.c_uint64), ("global_seed", C.c_uint64), ("spp", C.c_uint32), ("sample_offset", C.c_uint32),
+                ("max_depth", C.c_uint32), ("chunk", C.c_uint32), ("stride", C.c_uint32), ("flags", C.c_uint32), ("partial_mib", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+RAY_RECORD = 7  # rt1w_ray_color: origin xyz, direction xyz, time per ray; a record may be longer (its stride)
+_sig("rt1w_ray_color", C.c_int, _P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_ray_color_device", C.c_int, _P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(Stats))
+
 _CAM_ARGS = [_D3, _D3, _D3] + [C.c_double] * 6
 _sig("rt1w_reference_camera", C.c_int, C.c_int, _D3, _D3, _D3, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("rt1w_context_set_camera", C.c_int, _P, *_CAM_ARGS)
@@ -322,6 +335,8 @@ for _i, _t in enumerate((RenderParams, Stats, SceneInfo, SpecialiseInfo)):
         raise ImportError(f"librt1w.so and this binding disagree on the layout of {_t.__name__}: rebuild the library")
 if _lib.rt1w_abi_sizeof(6) != C.sizeof(Camera):
     raise ImportError("librt1w.so and this binding disagree on the layout of Camera: rebuild the library")
+if _lib.rt1w_abi_sizeof(8) != C.sizeof(RayColorParams) or C.sizeof(RayColorParams) != 56:
+    raise ImportError("librt1w.so and this binding disagree on the layout of RayColorParams: rebuild the library")
 
 
 # The functions of librt1w_lab.so this binding calls (csrc/walk_lab.h), name -> argtypes; every one returns int.  load_lab applies it.
@@ -333,6 +348,8 @@ _LAB_SIGS = {
     "rt1w_lab_aov_tiles_host": [_P, _PR, _U, _P, _U, _P],
     "rt1w_lab_hit_host": [_P, C.POINTER(HitParams), _P, _P, _P],
     "rt1w_lab_camera_rays_host": [_P, _PR, _P],
+    "rt1w_lab_camera_rays_pos_host": [_P, _PR, _P, _P],
+    "rt1w_lab_ray_color_host": [_P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(_N)],
     "rt1w_lab_denoise_host": [_PD, _P, _P, _P],
     "rt1w_lab_batch_variance_host": [_U] * 5 + [_P] * 4,
     "rt1w_lab_denoise_var_host": [_PD, _P, _P, _P, _F, _P],
@@ -387,7 +404,7 @@ def _ck(rc):
 
 
 def _ck_lab(rc, name):
-    """The twins do not set rt1w_last_error: the error names the function."""
+    """Most twins do not set rt1w_last_error: the error names the function."""
     if rc < 0:
         raise Rt1wError(rc, name)
     return rc
@@ -414,15 +431,16 @@ def _call(fn, *args, stats=True):
     return _stats_dict(st)
 
 
-def _call_lab(name, *args):
-    """One call of librt1w_lab.so's function `name`, checked."""
-    return _ck_lab(getattr(load_lab(), name)(*_c_args(args)), name)
+def _call_lab(name, *args, says_why=False):
+    """One call of librt1w_lab.so's function `name`, checked.  says_why: the function sets rt1w_last_error when it refuses."""
+    rc = getattr(load_lab(), name)(*_c_args(args))
+    return _ck(rc) if says_why else _ck_lab(rc, name)
 
 
-def _twin(name, prep, *extra):
+def _twin(name, prep, *extra, says_why=False):
     """A CPU twin: `prep` = (arguments, results) of the entry's _*_prep, `extra` the twin's optional outputs.  Returns the results."""
     args, out = prep
-    _call_lab(name, *args, *extra)
+    _call_lab(name, *args, *extra, says_why=says_why)
     return out
 
 
@@ -510,6 +528,26 @@ def _hit_prep(rays, t_min, t_max, first_stream, sample, global_seed, variant):
     out = np.empty((r.shape[0], HIT_RECORD), dtype=np.float64)
     node = np.empty(r.shape[0], dtype=np.uint32)
     return (_hit_params(r.shape[0], first_stream, sample, global_seed, variant), r, out, node), (out, node)
+
+
+def _ray_color_params(n, spp=1, sample_offset=0, max_depth=50, first_stream=0, global_seed=0, chunk=0, stride=0, out_sum=False, generic=False,
+                      partial_mib=0, flags=0, f32=False):
+    if f32:  # the parameter block has no precision member: the refusal include/rt1w.h states for single precision is the binding's
+        raise Rt1wError(ERR_UNSUPPORTED, "ray_color: the ray-list kernels are f64 only")
+    flags |= (_RENDER_FLAGS["out_sum"] if out_sum else 0) | (_RENDER_FLAGS["generic"] if generic else 0)
+    return RayColorParams(n, first_stream, global_seed, spp, sample_offset, max_depth, chunk, stride, flags, int(partial_mib), 0)
+
+
+def _ray_color_prep(rays, start_word, kw):
+    """rays [n, stride >= 7] = origin, direction, time, .. (the record's other doubles are not read); start_word None or uint32 [n]"""
+    r, = _f64(rays)
+    if r.ndim != 2 or r.shape[1] < RAY_RECORD:
+        raise ValueError("rays must be [n, 7] (origin, direction, time) or wider ([n, 9]: rt1w_hit's records)")
+    sw = None if start_word is None else np.ascontiguousarray(start_word, dtype=np.uint32)
+    if sw is not None and sw.shape != (r.shape[0],):
+        raise ValueError("start_word must be [n]")
+    out = np.empty((r.shape[0], 3), dtype=np.float64)
+    return (_ray_color_params(r.shape[0], stride=r.shape[1], **kw), r, sw, out), out
 
 
 def _denoise_prep(frame, aov, kw):
@@ -1004,6 +1042,21 @@ class Context:
         ray r come from the stream of pixel seed first_stream + r (include/rt1w.h has the semantics)."""
         return self._entry(_lib.rt1w_hit, _hit_prep(rays, t_min, t_max, first_stream, sample, global_seed, variant), with_stats)
 
+    def ray_color(self, rays, start_word=None, with_stats=False, **kw):
+        """Radiance queries (rt1w_ray_color): ray_color of the scene for the caller's rays [n, 7] = origin, direction, time (or wider
+        records, e.g. [n, 9] as hit() takes them) through the render kernels' ray-list form.  Returns float64 [n, 3]: the mean of spp
+        samples per ray, or with out_sum their raw sum.  kw: spp=1, sample_offset=0, max_depth=50, first_stream=0, global_seed=0, chunk=0,
+        out_sum, generic, partial_mib; f32=True is refused with ERR_UNSUPPORTED (the ray-list kernels are f64 only; rt1w_ray_color_params
+        has no precision member, so this refusal is the binding's).  Sample k of ray r draws from the stream of pixel seed first_stream + r, sample sample_offset + k,
+        from word start_word[r] on (None: word 0; include/rt1w.h has the semantics)."""
+        return self._entry(_lib.rt1w_ray_color, _ray_color_prep(rays, start_word, kw), with_stats)
+
+    def ray_color_device(self, d_rays, d_out, n, d_start_word=None, stride=RAY_RECORD, **kw):
+        """Same on device memory of the context's GPU (int addresses, e.g. torch tensors' .data_ptr()): d_rays n * stride float64, d_out
+        n * 3 float64, d_start_word None or n uint32; no host copy.  kw as ray_color's (f32=True: ERR_UNSUPPORTED, the binding's own
+        refusal).  Returns the stats dict."""
+        return _call(_lib.rt1w_ray_color_device, self._h, _ray_color_params(n, stride=stride, **kw), d_rays, d_start_word, d_out)
+
     def hit_device(self, d_rays, d_out, d_node, n, first_stream=0, sample=0, global_seed=0, variant=None):
         """Same on device memory (int addresses, e.g. torch tensors' .data_ptr()): d_rays n * 9 float64 with the bounds in, d_out n * 12
         float64, d_node n uint32 or None; returns the stats dict."""
@@ -1364,6 +1417,25 @@ def camera_rays_host(scene, width, height, spp, tile=None, sample_offset=0, glob
     p = Context._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, strips=strips)
     out = np.empty((p.tile_h, p.tile_w, spp, 8), dtype=np.float64)
     return _twin("rt1w_lab_camera_rays_host", ((scene._h, p, out), out))
+
+
+def camera_rays_pos_host(scene, width, height, spp, tile=None, sample_offset=0, global_seed=0, strips=None):
+    """camera_rays_host's rays and, per ray, uint32 [tile_h, tile_w, spp]: the word its sample's stream stands at behind the camera's
+    draws (librt1w_lab.so: rt1w_lab_camera_rays_pos_host) -- the start_word with which ray_color continues that sample of a render."""
+    p = Context._params(width, height, spp, 0, tile, sample_offset, global_seed, 0, False, strips=strips)
+    out = np.empty((p.tile_h, p.tile_w, spp, 8), dtype=np.float64)
+    word = np.empty((p.tile_h, p.tile_w, spp), dtype=np.uint32)
+    return _twin("rt1w_lab_camera_rays_pos_host", ((scene._h, p, out, word), (out, word)))
+
+
+def ray_color_host(scene, rays, start_word=None, with_stats=False, **kw):
+    """CPU twin of Context.ray_color (librt1w_lab.so: rt1w_lab_ray_color_host, rt_ray_list.h and rt_core.h built for the host): the
+    array the GPU must equal bit for bit; with_stats: (array, {"segments": rays traced}).  No GPU needed.  This twin says why it
+    refuses a call, as the entries do."""
+    args, out = _ray_color_prep(rays, start_word, kw)
+    seg = C.c_uint64()
+    _twin("rt1w_lab_ray_color_host", ((scene._h, *args), out), C.byref(seg), says_why=True)
+    return (out, {"segments": seg.value}) if with_stats else out
 
 
 def guides_merge_tiles_host(gacc, tile_sums, spp, tile, tiles):

@@ -1,4 +1,4 @@
-/* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip, aov_tiles.hip) and of the ray-query kernels (hit.hip): rt_aov.h, rt_aov_deep.h, rt_aov_tiles.h and rt_hit.h compiled for the host (g++, -ffp-contract=off
+/* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip, aov_tiles.hip) and of the ray-query kernels (hit.hip) and the ray-list form of the render kernels (context_rays.hip): rt_aov.h, rt_aov_deep.h, rt_aov_tiles.h and rt_hit.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core) and run over a committed scene's flat arrays.  Diagnostics library only (librt1w_lab.so): the expected side of the GPU
  * tests' bit-equality checks and of the CPU tier's checks against the literal oracle.  librt1w.so keeps no CPU render path. */
 #include <algorithm>
@@ -7,10 +7,12 @@
 #include <vector>
 
 #include "render_params.h"
+#include "rt1w_internal.h" /* rt1w_internal_set_error: the twin of rt1w_ray_color says why it refuses, as the entries do */
 #include "rt_adaptive_plan.h" /* rt_aov_tiles_check */
 #include "rt_aov_deep.h"
 #include "rt_aov_tiles.h"
 #include "rt_hit.h"
+#include "rt_ray_list.h"
 #include "walk_lab.h"
 
 namespace {
@@ -140,7 +142,68 @@ bool hit_rays(const RtSceneView& sc, const RtHitParams& hp, uint64_t k0, uint64_
     }
     return true;
 }
+
+/* rays k0, k0 + step, .. of a radiance list, as the ray-list kernels run them (rt_kernel_sorted.h with RT_RAY_LIST): per ray, per work item
+ * of f.chunk samples, per sample rt_ray_begin and rt_path_step until the path ends; the items' sums added in order (rt_resolve_kernel) */
+template <class Cfg>
+bool ray_color_rays(const RtSceneView& sc, const RtFrame& f, const RtRayList& rl, bool out_sum, uint64_t k0, uint64_t step, double* out, uint64_t* segments) {
+    AovHostStack stk;
+    RtGlobalNodes ns{sc.nodes};
+    for (uint64_t r = k0; r < rl.n; r += step) {
+        const bool traced = rt_ray_traced(rl.rays + r * (uint64_t)rl.stride);
+        RtV3 total = rt_v3(0.0, 0.0, 0.0);
+        for (uint32_t chunk = 0; chunk < f.n_chunks; ++chunk) {
+            const uint32_t s0 = chunk * f.chunk, s_end = s0 + f.chunk < f.spp ? s0 + f.chunk : f.spp;
+            RtV3d sum = rt_v3d(0.0, 0.0, 0.0);
+            if (!traced) sum = rt_ray_untraced_sum(sc, f.max_depth, s_end - s0);
+            else
+                for (uint32_t s = s0; s < s_end; ++s) {
+                    RtPath path;
+                    rt_ray_begin(rl, f.global_seed, f.max_depth, r, f.sample_offset + s, path);
+                    while (path.alive) {
+                        *segments += path.depth_left != 0u ? 1u : 0u;
+                        rt_path_step<Cfg>(sc, ns, path, stk);
+                        if (stk.overflow) return false;
+                    }
+                    sum = rt_v3d_add(sum, path.radiance);
+                }
+            total = total + rt_v3(sum.x, sum.y, sum.z);
+        }
+        if (!out_sum) total = rt_into_sampled(total, f.spp);
+        out[r * 3u] = total.x; out[r * 3u + 1u] = total.y; out[r * 3u + 2u] = total.z;
+    }
+    return true;
+}
 } // namespace
+
+extern "C" int rt1w_lab_ray_color_host(const rt1w_scene* s, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out,
+                                       uint64_t* segments) {
+    static_assert(sizeof(rt1w_ray_color_params) == sizeof(RtRayColorParams), "rt1w_ray_color_params is RtRayColorParams' layout");
+    if (!s || !s->committed) { rt1w_internal_set_error("null or uncommitted scene"); return RT1W_ERR_INVALID; }
+    if (const char* why = rt_ray_color_refusal((const RtRayColorParams*)p, rays, start_word, out, RT1W_OUT_SUM, RT1W_GENERIC)) { /* the entries' own check */
+        rt1w_internal_set_error(why); return RT1W_ERR_INVALID;
+    }
+    std::vector<RtNode> nodes;
+    RtSceneView sc;
+    int v;
+    if (!host_view(s, 0u, nodes, sc, v)) return RT1W_ERR_INVALID;
+    RtFrame f{};
+    f.width = f.tile_w = (uint32_t)p->n; f.height = f.tile_h = 1u;
+    f.spp = p->spp; f.sample_offset = p->sample_offset; f.max_depth = p->max_depth; f.global_seed = (uint32_t)p->global_seed;
+    f.chunk = p->chunk ? p->chunk : rt1w_scene_default_chunk(s, (uint32_t)p->n, 1u, p->spp);
+    if (f.chunk > f.spp) f.chunk = f.spp;
+    f.n_chunks = (f.spp + f.chunk - 1u) / f.chunk;
+    RtRayList rl;
+    rl.rays = rays; rl.start_word = start_word; rl.n = p->n; rl.first_stream = p->first_stream;
+    rl.stride = p->stride ? p->stride : (uint32_t)RT_RAY_RECORD; rl.pad = 0u;
+    uint64_t segs[MAX_THREADS] = {}; /* per thread */
+    const bool ok = round_robin((uint32_t)p->n, [&](uint32_t t, uint32_t n_threads) { /* the list's rays */
+        return with_variant(v, [&](auto cfg) { return ray_color_rays<decltype(cfg)>(sc, f, rl, (p->flags & RT1W_OUT_SUM) != 0u, t, n_threads, out, &segs[t]); });
+    });
+    if (!ok) return RT1W_ERR_STATE;
+    if (segments) { *segments = 0u; for (uint64_t k : segs) *segments += k; }
+    return RT1W_OK;
+}
 
 extern "C" int rt1w_lab_hit_host(const rt1w_scene* s, const rt1w_hit_params* p, const double* rays, double* out, uint32_t* out_node) {
     static_assert(sizeof(rt1w_hit_params) == sizeof(RtHitParams), "rt1w_hit_params is RtHitParams' layout");
@@ -158,7 +221,10 @@ extern "C" int rt1w_lab_hit_host(const rt1w_scene* s, const rt1w_hit_params* p, 
     return ok ? RT1W_OK : RT1W_ERR_STATE;
 }
 
-extern "C" int rt1w_lab_camera_rays_host(const rt1w_scene* s, const rt1w_render_params* p, double* out) {
+extern "C" int rt1w_lab_camera_rays_pos_host(const rt1w_scene* s, const rt1w_render_params* p, double* out, uint32_t* out_word);
+extern "C" int rt1w_lab_camera_rays_host(const rt1w_scene* s, const rt1w_render_params* p, double* out) { return rt1w_lab_camera_rays_pos_host(s, p, out, nullptr); }
+
+extern "C" int rt1w_lab_camera_rays_pos_host(const rt1w_scene* s, const rt1w_render_params* p, double* out, uint32_t* out_word) {
     if (!s || !p || !out || !s->committed) return RT1W_ERR_INVALID;
     if (const int rc = rt1w::params_check(p, nullptr); rc < 0) return rc;
     if (p->precision != RT1W_PRECISION_F64) return RT1W_ERR_UNSUPPORTED;
@@ -177,6 +243,7 @@ extern "C" int rt1w_lab_camera_rays_host(const rt1w_scene* s, const rt1w_render_
                 o[0] = path.ray.o.x; o[1] = path.ray.o.y; o[2] = path.ray.o.z;
                 o[3] = path.ray.d.x; o[4] = path.ray.d.y; o[5] = path.ray.d.z;
                 o[6] = path.ray.time; o[7] = 1.0; /* valid, as in rt1w_lab_dump_rays */
+                if (out_word) *out_word++ = rt_rng_word(path.rng); /* where the sample's stream stands behind Camera::get_ray */
             }
     return RT1W_OK;
 }

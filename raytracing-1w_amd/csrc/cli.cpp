@@ -8,7 +8,13 @@
  *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
  *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]]
  *        [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]]
- *        [--pick I J]
+ *        [--pick I J] [--panorama W H]
+ * --panorama W H renders an equirectangular 360 x 180 degree image of W x H pixels from the arm's look_from through rt1w_ray_color: the
+ * camera is a few lines of host code.  Pixel (i, j), j counting rows from the bottom, looks along longitude phi = 2 pi (i + 1/2) / W - pi
+ * + phi0 and latitude theta = pi (j + 1/2) / H - pi / 2: direction (cos theta sin phi, sin theta, -cos theta cos phi), time 0.  phi0 =
+ * atan2(dx, -dz) of d = look_at - look_from (0 if d is vertical) puts what the arm's own camera looks at into the middle column.  Ray r = j W + i
+ * draws from the streams of pixel seed r (first_stream 0), --spp samples each (default: the arm's), --depth and --seed as for a render;
+ * the means go through the quantiser and the PPM writer of every other mode.
  * --pick I J renders nothing: it prints the hit record (rt1w_hit) of the ray through the CENTRE of pixel (I, J), J counting the
  * reference's rows j (0 = bottom row, main.rs:957): origin = the camera's lens centre, direction = lower_left_corner + s horizontal +
  * t vertical - origin with s = (I + 1/2) / (width - 1), t = (J + 1/2) / (height - 1) (rt1w_context_get_camera; the s, t of
@@ -67,6 +73,7 @@ int main(int argc, char** argv) {
     bool specialised_tiles = false;  /* --adaptive with rounds through the tile entries: RT1W_TILES_SPECIALISED */
     std::string err_path;
     long pick_i = -1, pick_j = -1;   /* >= 0: --pick, the record under a pixel instead of a render */
+    long pano_w = 0, pano_h = 0;     /* > 0: --panorama, an equirectangular image through rt1w_ray_color */
     long frames = 0;                 /* > 0: an animation through rt1w_render_temporal */
     double orbit = 0.0;
     double temporal_variance = -1.0; /* >= 0: the frames through rt1w_render_temporal_var with this sigma_variance (0 = default) */
@@ -115,6 +122,7 @@ int main(int argc, char** argv) {
         else if (a == "--err-out") err_path = next("--err-out");
         else if (a == "--frames") frames = std::atol(next("--frames"));
         else if (a == "--pick") { pick_i = std::atol(next("--pick I")); pick_j = std::atol(next("--pick J")); }
+        else if (a == "--panorama") { pano_w = std::atol(next("--panorama W")); pano_h = std::atol(next("--panorama H")); }
         else if (a == "--temporal-variance") {
             temporal_variance = 0.0;
             if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) temporal_variance = std::atof(argv[++i]);
@@ -123,7 +131,7 @@ int main(int argc, char** argv) {
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--target-error") target_error = std::atof(next("--target-error"));
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]] [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]] [--pick I J]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]] [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]] [--pick I J] [--panorama W H]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -177,6 +185,44 @@ int main(int argc, char** argv) {
         else
             std::printf("hit\nt %.17g\np %.17g %.17g %.17g\nnormal %.17g %.17g %.17g\nu %.17g\nv %.17g\nfront_face %d\nmaterial %u\nnode %u\n", rec[1], rec[2],
                         rec[3], rec[4], rec[5], rec[6], rec[7], rec[8], rec[9], (int)rec[10], (unsigned)rec[11], node);
+        rt1w_context_destroy(ctx);
+        rt1w_scene_destroy(scene);
+        return 0;
+    }
+    if (pano_w != 0 || pano_h != 0) {
+        if (pano_w < 1 || pano_h < 1 || (unsigned long long)pano_w * (unsigned long long)pano_h > 0xFFFFFFFFull) { std::fprintf(stderr, "rt1w: --panorama W H: at least 1 x 1, at most 2^32 - 1 pixels\n"); return 2; }
+        if (reference_stream || f32 || denoise || adaptive >= 0 || frames > 0) { std::fprintf(stderr, "rt1w: --panorama goes with --scene, --spp, --depth, --seed and --out only\n"); return 2; }
+        double lf[3], la[3], up[3], vfov, aperture, focus;
+        if (rt1w_reference_camera(arm, lf, la, up, &vfov, &aperture, &focus) < 0) return fail("camera");
+        const size_t n = (size_t)pano_w * (size_t)pano_h;
+        const double pi = 3.14159265358979323846;
+        const double dx = la[0] - lf[0], dz = la[2] - lf[2];
+        const double phi0 = (dx == 0.0 && dz == 0.0) ? 0.0 : std::atan2(dx, -dz); /* the middle column looks towards look_at */
+        std::vector<double> rays(n * 7), means(n * 3);
+        for (long j = 0; j < pano_h; ++j)
+            for (long i = 0; i < pano_w; ++i) {
+                const double phi = 2.0 * pi * (((double)i + 0.5) / (double)pano_w) - pi + phi0, theta = pi * (((double)j + 0.5) / (double)pano_h) - 0.5 * pi;
+                double* r = rays.data() + ((size_t)j * pano_w + i) * 7;
+                r[0] = lf[0]; r[1] = lf[1]; r[2] = lf[2];
+                r[3] = std::cos(theta) * std::sin(phi); r[4] = std::sin(theta); r[5] = -(std::cos(theta) * std::cos(phi));
+                r[6] = 0.0;
+            }
+        rt1w_ray_color_params rp;
+        std::memset(&rp, 0, sizeof rp);
+        rp.n = n; rp.spp = (uint32_t)spp; rp.max_depth = (uint32_t)depth; rp.global_seed = (uint32_t)seed;
+        rt1w_stats rs;
+        std::fprintf(stderr, "rt1w: scene arm %d, panorama %ldx%ld, %ld spp, depth %ld\n", arm, pano_w, pano_h, spp, depth);
+        if (rt1w_ray_color(ctx, &rp, rays.data(), nullptr, means.data(), &rs) < 0) return fail("panorama");
+        const int64_t len = rt1w_format_ppm(means.data(), (uint32_t)pano_w, (uint32_t)pano_h, nullptr, 0);
+        if (len < 0) return fail("format");
+        std::vector<char> text((size_t)len + 1);
+        if (rt1w_format_ppm(means.data(), (uint32_t)pano_w, (uint32_t)pano_h, text.data(), (uint64_t)len + 1) < 0) return fail("format");
+        FILE* f = out_path.empty() ? stdout : std::fopen(out_path.c_str(), "w");
+        if (!f) { std::perror("rt1w: --out"); return 1; }
+        std::fwrite(text.data(), 1, (size_t)len, f);
+        if (f != stdout) std::fclose(f);
+        std::fprintf(stderr, "Done\nrt1w: %.1f ms kernels, %.1f Mpaths/s, %.2f segments/path, kernel variant V%u\n", rs.kernel_ms,
+                     (double)rs.paths / rs.kernel_ms / 1e3, (double)rs.segments / (double)rs.paths, rs.variant);
         rt1w_context_destroy(ctx);
         rt1w_scene_destroy(scene);
         return 0;

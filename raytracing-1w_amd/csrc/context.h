@@ -37,19 +37,29 @@ struct RtKernel {
     hipFunction_t jit = nullptr;  /* ... or the scene-specialised kernel (jit.cpp), from its module */
     bool pw = false,              /* takes the pair-walk view (rt_walk_pair.h) in second place */
          f32 = false,             /* takes the f32 scene's views (context_f32.hip) instead of the context's */
-         tiles = false;           /* tile-list form (context_tiles.hip): takes the tile list (RtTileArg) in last place */
+         tiles = false,           /* tile-list form (context_tiles.hip): takes the tile list (RtTileArg) in last place */
+         rays = false;            /* ray-list form (context_rays.hip): takes the ray list (RtRayArg) in last place */
     int grid = 0;
     /* the makers: RtKernel::of(block, bits, fn).with_pw() -- a call site names the arguments its kernel takes */
     static RtKernel of(int block, uint32_t bits, const void* fn = nullptr) { RtKernel k; k.block = block; k.bits = bits; k.fn = fn; return k; }
     RtKernel with_pw(bool on = true) const { RtKernel k = *this; k.pw = on; return k; }
     RtKernel with_f32(bool on = true) const { RtKernel k = *this; k.f32 = on; return k; }
     RtKernel with_tiles(bool on = true) const { RtKernel k = *this; k.tiles = on; return k; }
+    RtKernel with_rays(bool on = true) const { RtKernel k = *this; k.rays = on; return k; }
 };
 
 /* the tile list as the kernels of context_tiles.hip take it (rt_kernel_sorted.h: RtTileList; the same bytes, checked at first use) */
 struct RtTileArg {
     const uint32_t* rec = nullptr; /* device: [n][4] = rt1w_tile records */
     uint32_t side = 0, n = 0;
+};
+
+/* the ray list as the kernels of context_rays.hip take it (rt_ray_list.h: RtRayList; the same bytes, checked at first use) */
+struct RtRayArg {
+    const double* rays = nullptr;         /* device: [n][stride] */
+    const uint32_t* start_word = nullptr; /* device: [n], or null */
+    uint64_t n = 0, first_stream = 0;
+    uint32_t stride = 0, pad = 0;
 };
 
 /* The f64 render kernels by walk form and variant (context.hip: g_kernels).  Every walk form is followed by its build for
@@ -117,6 +127,9 @@ struct rt1w_context {
     RtKernel kt[RT_N_WALKS][RT_N_VARIANTS] = {};
     RtKernel pw_kt[2] = {};
     void* d_tiles = nullptr; size_t tiles_bytes = 0;
+    /* rt1w_ray_color: the ray-list forms of k64 and pw_k (context_rays.hip), resolved at their first use */
+    RtKernel kr[RT_N_WALKS][RT_N_VARIANTS] = {};
+    RtKernel pw_kr[2] = {};
     /* host copies of the flat arrays the two opt-in modes convert on first use (a scene may be destroyed before its contexts) */
     std::vector<RtNode> h_nodes, h_lights; std::vector<RtMaterial> h_materials; std::vector<RtTexture> h_textures; std::vector<RtPerlin> h_perlin;
     RtKernel k32[RT_N_VARIANTS][3] = {}; /* f32 kernels by variant and rt1w_internal_f32_kernel mode: plain, reordering, pair walk */
@@ -144,6 +157,9 @@ int render_common(rt1w_context* c, const rt1w_render_params* p, double* d_out, r
 /* the context's copy of a tile list (HOST memory in, device memory out: valid until the next upload), grown on demand */
 int tiles_upload(rt1w_context* c, const rt1w_tile* tiles, uint32_t n_tiles, const uint32_t** d_rec);
 int render_tiles_common(rt1w_context* c, const rt1w_render_params* p, uint32_t tile, const rt1w_tile* tiles, uint32_t n_tiles, double* d_out, rt1w_stats* stats);
+/* rt1w_ray_color_device without the entry's checks and clock (features.hip): the plan of a render of n x 1 pixels with RT1W_GENERIC, its
+ * kernel's ray-list form over the device buffers, launch on lane 0 (sample passes included), wait, stats */
+int ray_color_common(rt1w_context* c, const rt1w_render_params* frame, const RtRayArg& rays, double* d_out, rt1w_stats* stats);
 /* the host clock of an entry, for rt1w_stats.total_ms */
 struct RtTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -44,6 +44,11 @@ extern "C" const void* rt1w_internal_tile_kernel(int walk, int variant);
 extern "C" const void* rt1w_internal_tile_pw_kernel(int which);  /* 0 pair walk, 1 pair walk + reordering */
 extern "C" unsigned rt1w_internal_tile_sizeof(int what);         /* bytes of its 0 RtSceneView, 1 RtFrame, 2 RtPwView, 3 RtTileList */
 
+/* context_rays.hip: the ray-list forms of the f64 kernels (rt1w_ray_color), indexed like the tile-list forms */
+extern "C" const void* rt1w_internal_ray_kernel(int walk, int variant);
+extern "C" const void* rt1w_internal_ray_pw_kernel(int which);
+extern "C" unsigned rt1w_internal_ray_sizeof(int what);          /* bytes of its 0 RtSceneView, 1 RtFrame, 2 RtPwView, 3 RtRayList */
+
 #include "rt_kernels.h"
 #include "rt_walk_table.h"
 
@@ -267,7 +272,7 @@ void lane_destroy(RtLane& l) {
 #endif
 /* where a plan's kernel sits in the context: k64[i][v], pw_k[i], or neither; its tile-list form has the same index (tile_kernel_of) */
 struct RtKernelAt { enum Table { NOWHERE, K64, PW } table = NOWHERE; int i = 0, v = 0; };
-struct RtLaunch { RtFrame f; unsigned long long npix; unsigned long long partial_budget = RT_PARTIAL_BUDGET; int variant; RtKernel k; RtKernelAt at; RtTileArg tl; };
+struct RtLaunch { RtFrame f; unsigned long long npix; unsigned long long partial_budget = RT_PARTIAL_BUDGET; int variant; RtKernel k; RtKernelAt at; RtTileArg tl; RtRayArg rl; };
 
 /* the persistent grid of a kernel: as many workgroups as are resident at once, at least one per CU; 0, with the error set, if the
  * occupancy query failed */
@@ -426,11 +431,13 @@ int render_launch(rt1w_context* c, RtLane& l, const rt1w_render_params* p, const
     double* partial = l.d_partial;
     unsigned long long* counters = l.d_counters;
     RtTileArg tl = L.tl;
+    RtRayArg rl = L.rl;
     void* args[6];
     int n = 0;
     args[n++] = const_cast<void*>(view);
     if (k.pw) args[n++] = const_cast<void*>(pw);
     args[n++] = &PF; args[n++] = &partial; args[n++] = &counters;
+    if (k.rays) args[n++] = &rl;
     if (k.tiles) args[n++] = &tl; /* a pass's sample delta reaches every tile through PF.sample_offset, which the kernel adds to the tile's own */
     if (!hip_ok(k.jit ? hipModuleLaunchKernel(k.jit, (unsigned)k.grid, 1, 1, (unsigned)k.block, 1, 1, 0, l.stream, args, nullptr)
                       : hipLaunchKernel(k.fn, dim3(k.grid), dim3(k.block), args, 0, l.stream), "render kernel launch")) return RT1W_ERR_DEVICE;
@@ -589,9 +596,38 @@ int tile_kernel_of(rt1w_context* c, RtLaunch& L) {
     return RT1W_OK;
 }
 
+/* the ray-list form of the kernel a plan holds (from k64 / pw_k: the plan was made with RT1W_GENERIC), resolved at its first use */
+int ray_kernel_of(rt1w_context* c, RtLaunch& L) {
+    if (rt1w_internal_ray_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_ray_sizeof(1) != sizeof(RtFrame) ||
+        rt1w_internal_ray_sizeof(2) != sizeof(RtPwView) || rt1w_internal_ray_sizeof(3) != sizeof(RtRayArg)) {
+        rt1w::set_error("ray-list kernels built against another scene layout"); return RT1W_ERR_DEVICE;
+    }
+    const RtKernelAt& at = L.at;
+    RtKernel* const slot = at.table == RtKernelAt::PW ? &c->pw_kr[at.i] : at.table == RtKernelAt::K64 ? &c->kr[at.i][at.v] : nullptr;
+    RtKernel want = L.k.with_rays(); want.grid = 0;
+    want.fn = at.table == RtKernelAt::PW ? rt1w_internal_ray_pw_kernel(at.i) : at.table == RtKernelAt::K64 ? rt1w_internal_ray_kernel(at.i, at.v) : nullptr;
+    if (!slot || !want.fn) { rt1w::set_error("rt1w_ray_color: the kernel this scene renders with has no ray-list form"); return RT1W_ERR_DEVICE; }
+    const int rc = first_use(c, *slot, want);
+    if (rc < 0) return rc;
+    L.k = *slot;
+    return RT1W_OK;
+}
+
 } // namespace
 
 namespace rt1w {
+int ray_color_common(rt1w_context* c, const rt1w_render_params* q, const RtRayArg& rays, double* d_out, rt1w_stats* stats) {
+    RtLaunch L;
+    int rc = render_plan(c, q, L); /* q: n x 1 pixels, RT1W_GENERIC: a kernel of k64 / pw_k, never the scene-specialised one */
+    if (rc < 0) return rc;
+    if ((rc = ray_kernel_of(c, L)) < 0) return rc;
+    L.rl = rays;
+    RtLane& l = c->lane[0];
+    if ((rc = lane_reserve_partial(l, L)) < 0) return rc;
+    if ((rc = render_launch(c, l, q, L, d_out)) < 0) return rc;
+    return render_finish(l, L, stats);
+}
+
 int tiles_upload(rt1w_context* c, const rt1w_tile* tiles, uint32_t n_tiles, const uint32_t** d_rec) {
     static_assert(sizeof(rt1w_tile) == 16, "the kernels read a tile's record as four 32-bit words");
     const size_t bytes = (size_t)n_tiles * sizeof(rt1w_tile);
@@ -1008,6 +1044,7 @@ uint32_t rt1w_abi_sizeof(int what) {
         case 3: return (uint32_t)sizeof(rt1w_specialise_info);
         case 4: return (uint32_t)sizeof(rt1w_denoise_params);
         case 6: return (uint32_t)sizeof(rt1w_camera);
+        case 8: return (uint32_t)sizeof(rt1w_ray_color_params);
         default: return 0u;
     }
 }

@@ -1,4 +1,4 @@
-/* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_hit*, rt1w_denoise*,
+/* features.hip -- the entries of the feature buffers and the denoiser (include/rt1w.h: rt1w_render_aov*, rt1w_hit*, rt1w_ray_color*, rt1w_denoise*,
  * rt1w_render_denoised*, rt1w_batch_variance*, rt1w_accum_*, rt1w_guides_*, rt1w_render_adaptive*, rt1w_temporal_*, rt1w_render_temporal*) and a live context's camera (rt1w_context_set_camera).  Host code only, built without a device pass: the kernels
  * belong to aov.hip, hit.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip, temporal.hip and temporal_var.hip and are reached through rt_feature_launch.h, the context and its render
  * path belong to context.hip (context.h), so a change here rebuilds none of the code objects.
@@ -14,6 +14,7 @@
 #include "rt_feature_launch.h"
 #include "rt_aov_deep.h" /* rt_aov_deep_args_ok only */
 #include "rt_hit.h" /* RtHitParams, rt_hit_refusal only */
+#include "rt_ray_list.h" /* RtRayColorParams, rt_ray_color_refusal only */
 #include "rt_denoise_var.h" /* rt_dv_batches_ok, rt_dv_sigma, rt_dv_split only */
 #include "rt_adaptive_plan.h" /* the plan of rt1w_render_adaptive and rt1w_adaptive_select; rt_ad_*_ok of rt_adaptive.h; the tile lists' checks */
 #include "rt_guides.h" /* RT_GD_RECORD only */
@@ -203,6 +204,34 @@ int hit(rt1w_context* c, const rt1w_hit_params* p, const void* rays, void* out, 
         if (r < 0) return r;
         if (host && out_node && !hip_ok(hipMemcpy(out_node, d_node, node_bytes, hipMemcpyDeviceToHost), "node index copy")) return (int)RT1W_ERR_DEVICE;
         return (int)RT1W_OK;
+    });
+}
+
+/* ---- radiance queries (include/rt1w.h: rt1w_ray_color) ---- */
+static_assert(sizeof(rt1w_ray_color_params) == sizeof(RtRayColorParams) && sizeof(RtRayColorParams) == 56, "rt1w_ray_color_params is RtRayColorParams' layout");
+/* the two radiance entries.  The buffers are device memory, or (host) host memory, passed through the context's framebuffer.  The rays go
+ * through the render kernels' ray-list form (context.hip: ray_color_common) as a render of n x 1 pixels with RT1W_GENERIC */
+int ray_color(rt1w_context* c, const rt1w_ray_color_params* p, const void* rays, const void* start_word, void* out, bool host, rt1w_stats* stats) {
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (const char* why = rt_ray_color_refusal((const RtRayColorParams*)p, rays, start_word, out, RT1W_OUT_SUM, RT1W_GENERIC)) { set_error(why); return RT1W_ERR_INVALID; }
+    const uint32_t stride = p->stride ? p->stride : (uint32_t)RT_RAY_RECORD;
+    rt1w_render_params q;
+    memset(&q, 0, sizeof q);
+    q.width = q.tile_w = (uint32_t)p->n; q.height = q.tile_h = 1u;
+    q.spp = p->spp; q.sample_offset = p->sample_offset; q.max_depth = p->max_depth; q.global_seed = (uint32_t)p->global_seed;
+    q.chunk = p->chunk; q.partial_mib = p->partial_mib; q.precision = RT1W_PRECISION_F64;
+    q.flags = (p->flags & RT1W_OUT_SUM) | RT1W_GENERIC;
+    const uint64_t word_bytes = p->n * sizeof(uint32_t);
+    /* the start words are 4 bytes each: staged as room of whole doubles, copied in here in their own size */
+    Staged s[] = {{(const double*)rays, nullptr, (size_t)((p->n - 1u) * stride + RT_RAY_RECORD), FRAMEBUFFER, "ray copy", nullptr},
+                  {nullptr, (double*)out, (size_t)p->n * 3u, FRAMEBUFFER, nullptr, "radiance copy"},
+                  {nullptr, nullptr, host && start_word ? (size_t)((p->n + 1u) / 2u) : 0u, FRAMEBUFFER, nullptr, nullptr}};
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
+        RtRayArg rl;
+        rl.rays = s[0].d_in; rl.n = p->n; rl.first_stream = p->first_stream; rl.stride = stride;
+        rl.start_word = host ? (start_word ? (const uint32_t*)s[2].d_out : nullptr) : (const uint32_t*)start_word;
+        if (host && start_word && !hip_ok(hipMemcpy(s[2].d_out, start_word, word_bytes, hipMemcpyHostToDevice), "start word copy")) return (int)RT1W_ERR_DEVICE;
+        return ray_color_common(c, &q, rl, s[1].d_out, st);
     });
 }
 
@@ -1161,6 +1190,8 @@ int rt1w_render_aov_deep_device(rt1w_context* c, const rt1w_render_params* p, ui
 }
 int rt1w_hit(rt1w_context* c, const rt1w_hit_params* p, const double* rays, double* out, uint32_t* out_node, rt1w_stats* stats) { return hit(c, p, rays, out, out_node, true, stats); }
 int rt1w_hit_device(rt1w_context* c, const rt1w_hit_params* p, const void* d_rays, void* d_out, void* d_out_node, rt1w_stats* stats) { return hit(c, p, d_rays, d_out, d_out_node, false, stats); }
+int rt1w_ray_color(rt1w_context* c, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out, rt1w_stats* stats) { return ray_color(c, p, rays, start_word, out, true, stats); }
+int rt1w_ray_color_device(rt1w_context* c, const rt1w_ray_color_params* p, const void* d_rays, const void* d_start_word, void* d_out, rt1w_stats* stats) { return ray_color(c, p, d_rays, d_start_word, d_out, false, stats); }
 int rt1w_denoise(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, double* out, rt1w_stats* stats) { return denoise(c, p, frame, aov, out, true, stats); }
 int rt1w_denoise_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, void* d_out, rt1w_stats* stats) {
     return denoise(c, p, (const double*)d_frame, (const double*)d_aov, (double*)d_out, false, stats);

@@ -137,7 +137,7 @@ __device__ __forceinline__ void rt_render_plain_body(const RtSceneView& sc, cons
         rt_stamp_last[threadIdx.x >> 6] = __builtin_amdgcn_s_memtime();
     }
 #endif
-    const unsigned long long n_items = rt_item_count(f);
+    const unsigned long long n_items = RT_ITEM_COUNT();
     const unsigned long long npix = (unsigned long long)f.tile_w * f.tile_h;
     unsigned long long item = (unsigned long long)blockIdx.x * RT_BLOCK + threadIdx.x;
     bool fresh = true; /* `item` holds an id that was not decoded yet */
@@ -175,7 +175,7 @@ __device__ __forceinline__ void rt_render_plain_body(const RtSceneView& sc, cons
                 }
                 fresh = false;
                 if (item >= n_items) break;
-                rt_item_decode(f, item, px, py, chunk);
+                RT_ITEM_DECODE();
                 if (RT_ITEM_TAKEN()) {
                     s = chunk * f.chunk;
                     s_end = s + f.chunk < f.spp ? s + f.chunk : f.spp;
@@ -184,7 +184,7 @@ __device__ __forceinline__ void rt_render_plain_body(const RtSceneView& sc, cons
                 }
             }
             if (!have) break; /* no work left: this lane retires */
-            rt_path_begin(sc, f, RT_ITEM_BEGIN_ARGS, path);
+            RT_ITEM_BEGIN(path);
             RT_STAMP(1);
         }
 #if defined(RT_HAVE_PW)
@@ -485,7 +485,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
         wn.p = sc.nodes;
     }
     const uint32_t walk_root = HC > 0 ? 0u : sc.root; /* the root's walk id is 0 */
-    const unsigned long long n_items = rt_item_count(f);
+    const unsigned long long n_items = RT_ITEM_COUNT();
     const unsigned long long npix = (unsigned long long)f.tile_w * f.tile_h;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     unsigned long long item = (unsigned long long)blockIdx.x * RT_BLOCK + threadIdx.x;
@@ -532,7 +532,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
                 }
                 fresh = false;
                 if (item >= n_items) break;
-                rt_item_decode(f, item, px, py, chunk);
+                RT_ITEM_DECODE();
                 if (RT_ITEM_TAKEN()) {
                     s = chunk * f.chunk;
                     sum = rt_v3d(RT_R(0.0), RT_R(0.0), RT_R(0.0));
@@ -541,7 +541,7 @@ __device__ __forceinline__ void rt_render_ss_body(const RtSceneView& sc, const R
             }
             if (!have) retired = true;
 #if !RT_CAM_AT_USE
-            else rt_path_begin(sc, f, RT_ITEM_BEGIN_ARGS, path);
+            else RT_ITEM_BEGIN(path);
 #else
             else {
                 /* the camera block is read where it is used, by scalar loads from the kernel-argument segment: held across the loop its

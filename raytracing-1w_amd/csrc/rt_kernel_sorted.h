@@ -88,7 +88,7 @@ __device__ __forceinline__ uint32_t lane_prefix(unsigned long long mask) {
  * indices of the wave (one round, seldom two), each read wave-uniformly.  It happens where an item is decoded, once per item: the
  * lane then carries the pixel's IMAGE position in (px, py), the tile's index and its sample offset; the virtual pixel its chunk sum is
  * stored at follows from those (x0 and y0 are multiples of T).  A pixel beyond the frame's edge is not traced: its chunk sums are
- * written as +0.0 here.  Without RT_TILE_LIST the macros below are the statements the kernels always had. */
+ * written as +0.0 here.  Without RT_TILE_LIST and RT_RAY_LIST the macros below are the statements the kernels always had. */
 #if defined(RT_TILE_LIST)
 struct RtTileList {
     const uint32_t* rec; /* [n][4]: x0, y0, sample_offset (the tile's own: the frame's is added to it), 0 */
@@ -125,6 +125,43 @@ __device__ __forceinline__ bool rt_tile_item(const RtFrame& f, const RtTileList&
 #define RT_ITEM_BEGIN_ARGS px, py, tso + s
 #define RT_XCH_TAIL(flags) RT_PK2((flags) | (tk << 3), tso) /* tk < 2^29: the host's bound on the list */
 #define RT_XCH_UNTAIL(v) do { tk = (uint32_t)(v) >> 3; tso = (uint32_t)((v) >> 32); } while (0)
+#elif defined(RT_RAY_LIST)
+/* ---- the ray-list form (context_rays.hip defines RT_RAY_LIST; rt1w_ray_color) -------------------------------------------------------
+ * The frame a kernel of this form is launched with is n x 1 "pixels": pixel r is ray r of the caller's list (rt_ray_list.h), whose record
+ * takes the camera's place where a sample begins.  Work items are numbered item = chunk * roundup(n, 64) + r, so the 64 lanes of a wave
+ * start on 64 consecutive rays of one chunk -- what is coherent in the list is coherent in the wave; the 8 x 8 blocks of rt_item_decode
+ * mean nothing here.  The ray's index travels in px (py stays 0), through the exchanges too; the partial sums are [chunk][ray][3], which
+ * the resolve kernel sums as it sums pixels.  A ray that is not traced (rt_ray_traced) is settled where its item is decoded: the sum of
+ * its misses is stored and the lane fetches another item, as the tile-list form does with a pixel outside the frame. */
+#include "rt_ray_list.h"
+#if RT_WAVE_ROUNDS_ON & 2
+#error "the ray-list form has no camera: RT_WAVE_ROUNDS part 2 does not apply"
+#endif
+__device__ __forceinline__ void rt_ray_item_decode(const RtRayList& rl, unsigned long long item, uint32_t& px, uint32_t& py, uint32_t& chunk) {
+    const unsigned long long per_chunk = (rl.n + 63ull) & ~63ull;
+    chunk = (uint32_t)(item / per_chunk);
+    px = (uint32_t)(item % per_chunk); /* < 2^32: n is */
+    py = 0u;
+}
+__device__ __forceinline__ bool rt_ray_item(const RtSceneView& sc, const RtFrame& f, const RtRayList& rl, rt_f64* __restrict__ partial,
+                                            unsigned long long npix, uint32_t chunk, uint32_t px) {
+    if (!(px < rl.n)) return false; /* the padding of the last wave */
+    if (rt_ray_traced(rl.rays + (unsigned long long)px * rl.stride)) return true;
+    const uint32_t s0 = chunk * f.chunk;
+    const RtV3d sum = rt_ray_untraced_sum(sc, f.max_depth, s0 + f.chunk < f.spp ? f.chunk : f.spp - s0);
+    rt_f64* dst = partial + ((unsigned long long)chunk * npix + px) * 3ull;
+    dst[0] = sum.x; dst[1] = sum.y; dst[2] = sum.z;
+    return false;
+}
+#define RT_TILE_PARAM , const RtRayList& tl
+#define RT_TILE_STATE
+#define RT_ITEM_COUNT() ((unsigned long long)f.n_chunks * ((tl.n + 63ull) & ~63ull))
+#define RT_ITEM_DECODE() rt_ray_item_decode(tl, item, px, py, chunk)
+#define RT_ITEM_TAKEN() rt_ray_item(sc, f, tl, partial, npix, chunk, px)
+#define RT_ITEM_PIXEL() ((unsigned long long)px)
+#define RT_ITEM_BEGIN(path) rt_ray_begin(tl, f.global_seed, f.max_depth, px, f.sample_offset + s, path)
+#define RT_XCH_TAIL(flags) RT_PK2((flags), 0u)
+#define RT_XCH_UNTAIL(v) do { } while (0)
 #else
 #define RT_TILE_PARAM
 #define RT_TILE_STATE
@@ -133,6 +170,12 @@ __device__ __forceinline__ bool rt_tile_item(const RtFrame& f, const RtTileList&
 #define RT_ITEM_BEGIN_ARGS f.x0 + px, rt_frame_row(f, py), f.sample_offset + s
 #define RT_XCH_TAIL(flags) RT_PK2((flags), 0u)
 #define RT_XCH_UNTAIL(v) do { } while (0)
+#endif
+/* what the rectangle and the tile-list form share (the ray-list form has its own above): the 8 x 8 blocks of rt_core.h, the camera's begin */
+#if !defined(RT_RAY_LIST)
+#define RT_ITEM_COUNT() rt_item_count(f)
+#define RT_ITEM_DECODE() rt_item_decode(f, item, px, py, chunk)
+#define RT_ITEM_BEGIN(path) rt_path_begin(sc, f, RT_ITEM_BEGIN_ARGS, path)
 #endif
 
 /* ---- render kernel with workgroup-level reordering ------------------------------------------
@@ -201,7 +244,7 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
     stk.sp = 0;
     RtGlobalNodes ns{sc.nodes};
 
-    const unsigned long long n_items = rt_item_count(f);
+    const unsigned long long n_items = RT_ITEM_COUNT();
     const unsigned long long npix = (unsigned long long)f.tile_w * f.tile_h;
 #if RT_SORT_SCAN
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); /* (a scalar: it is only added to addresses) */
@@ -251,7 +294,7 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
                 }
                 fresh = false;
                 if (item >= n_items) break;
-                rt_item_decode(f, item, px, py, chunk);
+                RT_ITEM_DECODE();
                 if (RT_ITEM_TAKEN()) {
                     s = chunk * f.chunk;
                     sum = rt_v3d(RT_R(0.0), RT_R(0.0), RT_R(0.0));
@@ -260,7 +303,7 @@ __device__ __forceinline__ void rt_render_sorted_body(const RtSceneView& sc, con
             }
             if (!have) retired = true;
             else if (RT_WAVE_ROUNDS_ON & 2) begin = true;
-            else rt_path_begin(sc, f, RT_ITEM_BEGIN_ARGS, path);
+            else RT_ITEM_BEGIN(path);
         }
 #if RT_WAVE_ROUNDS_ON & 2
         /* every lane of the wave is here, so those that begin nothing take rounds of the lens sample (rt_core.h: rt_wave_rounds) */

@@ -2,7 +2,8 @@
  * kernels behind them (resolve, quantise).  Their bodies are rt_kernel_sorted.h / rt_kernel_plain.h / rt_walk_pair.h.  Kept apart from
  * context.hip so that the identity of the kernels' source text (bench.py: kernel_sources_id, what a stored PMC measurement is matched
  * against) does not move with host-side edits.  Included by context.hip and, with RT_TILE_LIST defined and inside a namespace of its
- * own, by context_tiles.hip: every render kernel then takes the tile list (rt_kernel_sorted.h) as its last argument. */
+ * own, by context_tiles.hip: every render kernel then takes the tile list (rt_kernel_sorted.h) as its last argument; and with RT_RAY_LIST,
+ * likewise, by context_rays.hip: the last argument is then the caller's ray list (rt_ray_list.h). */
 #ifndef RT_KERNELS_H
 #define RT_KERNELS_H
 
@@ -10,6 +11,9 @@
 
 #if defined(RT_TILE_LIST)
 #define RT_TILE_KPARAM , RtTileList tl
+#define RT_TILE_KARG , tl
+#elif defined(RT_RAY_LIST)
+#define RT_TILE_KPARAM , RtRayList tl
 #define RT_TILE_KARG , tl
 #else
 #define RT_TILE_KPARAM
@@ -53,7 +57,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_STACK_WAVES) void rt_render_kernel_ss_
     rt_render_ss_body<Cfg, RT_SS_HC_CAP, RT_SS_HC_PARTS, false, RT_SS_HC_RECORDS>(sc, f, partial, counters RT_TILE_KARG);
 }
 
-#if !defined(RT_TILE_LIST) /* the walk table's count: the default build's alone */
+#if !defined(RT_TILE_LIST) && !defined(RT_RAY_LIST) /* the walk table's count: the default build's alone */
 /* node visits of a small render, counted per node: what the context ranks the walk table by (context.hip) */
 struct RtCountingNodes {
     static constexpr bool virt = false;
@@ -102,7 +106,7 @@ __global__ __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES(Cfg)) void rt_render_k
     rt_render_sorted_body<Cfg>(sc, f, partial, counters RT_TILE_KARG);
 }
 
-#if !defined(RT_TILE_LIST) /* resolve and quantise serve both forms from context.hip */
+#if !defined(RT_TILE_LIST) && !defined(RT_RAY_LIST) /* resolve and quantise serve every form from context.hip */
 /* Sum the chunk partials of each pixel in chunk order; then Color::into_sampled
  * (color.rs:14-21) unless raw sums were asked for. */
 __global__ void rt_resolve_kernel(const double* __restrict__ partial, double* __restrict__ out,

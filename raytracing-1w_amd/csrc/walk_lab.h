@@ -48,6 +48,15 @@ int rt1w_lab_hit_host(const rt1w_scene* s, const rt1w_hit_params* p, const doubl
  * sample_offset + k of the pixel -- the ray rt1w_render and rt1w_render_aov trace first (main.rs:964-971, camera.rs:61-73).  No GPU;
  * refusals of rt1w_lab_aov_host */
 int rt1w_lab_camera_rays_host(const rt1w_scene* s, const rt1w_render_params* p, double* out);
+/* the same rays and, per ray, out_word[tile_h][tile_w][spp] (may be null) = the word its sample's stream stands at behind rt_path_begin
+ * (rt1w_num.h: rt_rng_pos as one number, 4 * block + word): what rt1w_ray_color takes as start_word to continue that sample */
+int rt1w_lab_camera_rays_pos_host(const rt1w_scene* s, const rt1w_render_params* p, double* out, uint32_t* out_word);
+/* CPU twin of rt1w_ray_color (aov_host.cpp: rt_ray_list.h and rt_core.h built for the host): the same out[n][3] for a committed scene, the
+ * scene's own variant, no GPU; per ray, per work item of `chunk` samples, per sample rt_rng_at and rt_path_step until the path ends, summed
+ * as the kernels sum.  *segments (may be null) = the rays traced (rt1w_stats.segments of the entries).  RT1W_OK, RT1W_ERR_INVALID with the
+ * entries' own text (rt_ray_color_refusal), RT1W_ERR_STATE if a traversal stack overflowed */
+int rt1w_lab_ray_color_host(const rt1w_scene* s, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out,
+                            uint64_t* segments);
 
 /* CPU twin of rt1w_denoise (denoise_host.cpp: rt_denoise.h built for the host): the same double[h][w][3] from host buffers, no GPU.
  * RT1W_OK, or RT1W_ERR_INVALID as the device entry (null pointers, zero sizes, iterations > 8, unknown flags, bad sigmas) */
