@@ -90,6 +90,10 @@ struct HitRecord {
     Float t, u, v;
     bool front_face;
     const Material* material;
+    /* TEST SUPPORT with no counterpart in the reference and no part in any arithmetic or comparison: where the record came from
+     * (ORC_TAG_*: the leaf's kind and the wrappers it came back through; `leaf`: the construction number of the leaf or of the AABox
+     * around it; for a ConstantMedium its number among the scene's media).  orc_hit hands them out so that a ray set can be counted from the oracle's output alone. */
+    uint32_t tag = 0, leaf = 0;
     static HitRecord make(V3 position, V3 outward_normal, Float t, Float u, Float v, const Ray& ray,
                           const Material* material) {
         HitRecord h;
@@ -100,6 +104,10 @@ struct HitRecord {
         return h;
     }
 };
+
+enum { ORC_LEAF_SPHERE = 1, ORC_LEAF_MOVING = 2, ORC_LEAF_XY = 3, ORC_LEAF_XZ = 4, ORC_LEAF_YZ = 5, ORC_LEAF_MEDIUM = 6, ORC_LEAF_MASK = 7,
+       ORC_TAG_BOX = 8, ORC_TAG_TRANSLATE = 16, ORC_TAG_ROTATE = 32, ORC_TAG_FLIP = 64 };
+static uint32_t g_next_leaf = 0, g_next_medium = 0; /* construction numbers of leaves and boxes, and of media; restarted per scene build (orc_scene_build, orcb_new) */
 
 /* aabb.rs:7-52 */
 struct AABB {
@@ -447,7 +455,7 @@ struct Isotropic : Material { /* constant_medium.rs:31-51 */
 
 /* ---- sphere.rs ---- */
 struct Sphere : Hittable {
-    V3 center; Float radius; MatPtr material;
+    V3 center; Float radius; MatPtr material; uint32_t id = g_next_leaf++;
     Sphere(V3 c, Float r, MatPtr m) : center(c), radius(r), material(m) {}
     bool hit(const Ray& ray, Float t_min, Float t_max, MyRng&, HitRecord& out) const override { /* sphere.rs:24-63 */
         V3 oc = ray.origin - center;
@@ -467,6 +475,7 @@ struct Sphere : Hittable {
         Float u, v;
         sphere_uv(outward_normal, u, v);
         out = HitRecord::make(position, outward_normal, root, u, v, ray, material.get());
+        out.tag = ORC_LEAF_SPHERE; out.leaf = id;
         return true;
     }
     bool bounding_box(Float, Float, AABB& out) const override { /* sphere.rs:65-70 */
@@ -492,7 +501,7 @@ struct Sphere : Hittable {
 
 /* ---- moving_sphere.rs ---- */
 struct MovingSphere : Hittable {
-    V3 center0, center1; Float time0, time1, radius; MatPtr material;
+    V3 center0, center1; Float time0, time1, radius; MatPtr material; uint32_t id = g_next_leaf++;
     MovingSphere(V3 c0, V3 c1, Float t0, Float t1, Float r, MatPtr m) : center0(c0), center1(c1), time0(t0), time1(t1), radius(r), material(m) {}
     V3 center(Float time) const { return center0 + ((time - time0) / (time1 - time0)) * (center1 - center0); } /* :23-26 */
     bool hit(const Ray& ray, Float t_min, Float t_max, MyRng&, HitRecord& out) const override { /* :31-70 */
@@ -513,6 +522,7 @@ struct MovingSphere : Hittable {
         Float u, v;
         sphere_uv(outward_normal, u, v);
         out = HitRecord::make(position, outward_normal, root, u, v, ray, material.get());
+        out.tag = ORC_LEAF_MOVING; out.leaf = id;
         return true;
     }
     bool bounding_box(Float t0, Float t1, AABB& out) const override { /* :72-84 */
@@ -526,7 +536,7 @@ struct MovingSphere : Hittable {
 
 /* ---- aarect.rs ---- */
 struct XYRect : Hittable {
-    Float x0, x1, y0, y1, k; MatPtr material;
+    Float x0, x1, y0, y1, k; MatPtr material; uint32_t id = g_next_leaf++;
     XYRect(Float a, Float b, Float c, Float d, Float kk, MatPtr m) : x0(a), x1(b), y0(c), y1(d), k(kk), material(m) {}
     bool hit(const Ray& ray, Float t_min, Float t_max, MyRng&, HitRecord& out) const override { /* aarect.rs:46-72 */
         Float t = (k - ray.origin.z) / ray.direction.z;
@@ -537,6 +547,7 @@ struct XYRect : Hittable {
         Float u = (x - x0) / (x1 - x0);
         Float v = (y - y0) / (y1 - y0);
         out = HitRecord::make(ray.at(t), rt_v3(0.0, 0.0, 1.0), t, u, v, ray, material.get());
+        out.tag = ORC_LEAF_XY; out.leaf = id;
         return true;
     }
     bool bounding_box(Float, Float, AABB& out) const override { /* :74-79 */
@@ -544,7 +555,7 @@ struct XYRect : Hittable {
     }
 };
 struct XZRect : Hittable {
-    Float x0, x1, z0, z1, k; MatPtr material;
+    Float x0, x1, z0, z1, k; MatPtr material; uint32_t id = g_next_leaf++;
     XZRect(Float a, Float b, Float c, Float d, Float kk, MatPtr m) : x0(a), x1(b), z0(c), z1(d), k(kk), material(m) {}
     bool hit(const Ray& ray, Float t_min, Float t_max, MyRng&, HitRecord& out) const override { /* aarect.rs:84-110 */
         Float t = (k - ray.origin.y) / ray.direction.y;
@@ -555,6 +566,7 @@ struct XZRect : Hittable {
         Float u = (x - x0) / (x1 - x0);
         Float v = (z - z0) / (z1 - z0);
         out = HitRecord::make(ray.at(t), rt_v3(0.0, 1.0, 0.0), t, u, v, ray, material.get());
+        out.tag = ORC_LEAF_XZ; out.leaf = id;
         return true;
     }
     bool bounding_box(Float, Float, AABB& out) const override { /* :112-117 */
@@ -577,7 +589,7 @@ struct XZRect : Hittable {
     }
 };
 struct YZRect : Hittable {
-    Float y0, y1, z0, z1, k; MatPtr material;
+    Float y0, y1, z0, z1, k; MatPtr material; uint32_t id = g_next_leaf++;
     YZRect(Float a, Float b, Float c, Float d, Float kk, MatPtr m) : y0(a), y1(b), z0(c), z1(d), k(kk), material(m) {}
     bool hit(const Ray& ray, Float t_min, Float t_max, MyRng&, HitRecord& out) const override { /* aarect.rs:152-178 */
         Float t = (k - ray.origin.x) / ray.direction.x;
@@ -588,6 +600,7 @@ struct YZRect : Hittable {
         Float u = (y - y0) / (y1 - y0);
         Float v = (z - z0) / (z1 - z0);
         out = HitRecord::make(ray.at(t), rt_v3(1.0, 0.0, 0.0), t, u, v, ray, material.get());
+        out.tag = ORC_LEAF_YZ; out.leaf = id;
         return true;
     }
     bool bounding_box(Float, Float, AABB& out) const override { /* :180-185 */
@@ -690,6 +703,7 @@ int BVHNode::g_bvh_axis_rule = 0;
 struct AABox : Hittable {
     V3 box_min, box_max;
     std::unique_ptr<BVHNode> sides;
+    uint32_t id = g_next_leaf++;
     AABox(V3 p0, V3 p1, MatPtr material, MyRng& rng) : box_min(p0), box_max(p1) { /* aabox.rs:22-84 */
         std::vector<HBox> s;
         s.emplace_back(new XYRect(p0.x, p1.x, p0.y, p1.y, p1.z, material));
@@ -700,7 +714,11 @@ struct AABox : Hittable {
         s.emplace_back(new YZRect(p0.y, p1.y, p0.z, p1.z, p0.x, material));
         sides = BVHNode::make(std::move(s), 0.0, 1.0, rng);
     }
-    bool hit(const Ray& ray, Float t_min, Float t_max, MyRng& rng, HitRecord& out) const override { return sides->hit(ray, t_min, t_max, rng, out); } /* :88-96 */
+    bool hit(const Ray& ray, Float t_min, Float t_max, MyRng& rng, HitRecord& out) const override { /* :88-96 */
+        if (!sides->hit(ray, t_min, t_max, rng, out)) return false;
+        out.tag |= ORC_TAG_BOX; out.leaf = id;
+        return true;
+    }
     bool bounding_box(Float, Float, AABB& out) const override { out.minimum = box_min; out.maximum = box_max; return true; } /* :98-103 */
 };
 
@@ -713,6 +731,7 @@ struct Translate : Hittable { /* hittable.rs:49-52,205-234 */
         HitRecord hr;
         if (!hittable->hit(moved, t_min, t_max, rng, hr)) return false;
         out = HitRecord::make(hr.position + offset, hr.normal, hr.t, hr.u, hr.v, moved, hr.material);
+        out.tag = hr.tag | ORC_TAG_TRANSLATE; out.leaf = hr.leaf;
         return true;
     }
     bool bounding_box(Float t0, Float t1, AABB& out) const override {
@@ -761,6 +780,7 @@ struct RotateY : Hittable { /* hittable.rs:54-59,157-203,236-284 */
         normal.x = cos_theta * hr.normal.x + sin_theta * hr.normal.z;
         normal.z = -sin_theta * hr.normal.x + cos_theta * hr.normal.z;
         out = HitRecord::make(p, normal, hr.t, hr.u, hr.v, rotated_r, hr.material);
+        out.tag = hr.tag | ORC_TAG_ROTATE; out.leaf = hr.leaf;
         return true;
     }
     bool bounding_box(Float, Float, AABB& out) const override { if (!has_aabb) return false; out = aabb; return true; }
@@ -771,6 +791,7 @@ struct FlipFace : Hittable { /* hittable.rs:61,286-297 */
     bool hit(const Ray& ray, Float t_min, Float t_max, MyRng& rng, HitRecord& out) const override {
         if (!inner->hit(ray, t_min, t_max, rng, out)) return false;
         out.front_face = !out.front_face;
+        out.tag |= ORC_TAG_FLIP;
         return true;
     }
     bool bounding_box(Float t0, Float t1, AABB& out) const override { return inner->bounding_box(t0, t1, out); }
@@ -811,7 +832,7 @@ struct HittableList : Hittable {
 
 /* ---- constant_medium.rs ---- */
 struct ConstantMedium : Hittable {
-    HBox boundary; MatPtr phase_function; Float neg_inv_density;
+    HBox boundary; MatPtr phase_function; Float neg_inv_density; uint32_t id = g_next_medium++;
     ConstantMedium(HBox b, Float d, TexPtr texture) : boundary(std::move(b)), phase_function(new Isotropic(texture)), neg_inv_density(-1.0 / d) {} /* :22-28 */
     bool bounding_box(Float t0, Float t1, AABB& out) const override { return boundary->bounding_box(t0, t1, out); }
     bool hit(const Ray& ray, Float t_min, Float t_max, MyRng& rng, HitRecord& out) const override { /* :58-113 */
@@ -829,6 +850,7 @@ struct ConstantMedium : Hittable {
         Float t = rec1.t + hit_distance / ray_length;
         out.t = t; out.position = ray.at(t); out.normal = rt_v3(1.0, 0.0, 0.0);
         out.u = 0.0; out.v = 0.0; out.front_face = true; out.material = phase_function.get();
+        out.tag = ORC_LEAF_MEDIUM; out.leaf = id;
         return true;
     }
 };
@@ -864,12 +886,23 @@ struct Camera {
     }
 };
 
+/* TEST SUPPORT: orc_ray_color_trace notes every segment's world.hit here; null otherwise.  Nothing below reads it back. */
+static thread_local std::vector<double>* g_trace = nullptr;
+static void trace_note(const Ray& ray, bool hit, const HitRecord& h) {
+    if (!g_trace) return;
+    double row[16];
+    for (int k = 0; k < 16; ++k) row[k] = 0;
+    if (hit) { row[0] = 1; row[1] = h.t; row[2] = h.position.x; row[3] = h.position.y; row[4] = h.position.z; row[5] = (double)h.tag; row[6] = (double)h.leaf; row[7] = h.front_face ? 1 : 0; }
+    row[8] = ray.origin.x; row[9] = ray.origin.y; row[10] = ray.origin.z; row[11] = ray.direction.x; row[12] = ray.direction.y; row[13] = ray.direction.z; row[14] = ray.time;
+    g_trace->insert(g_trace->end(), row, row + 16);
+}
 /* ---- main.rs:51-116 ---- */
 static V3 ray_color(const Ray& ray, V3 background, const Hittable& world, const Hittable& lights, size_t depth, MyRng& rng) {
     if (depth == 0) return rt_v3(0.0, 0.0, 0.0);
     g_segments++;
     HitRecord hit_record;
     if (world.hit(ray, 0.001, RT_INF, rng, hit_record)) {
+        trace_note(ray, true, hit_record);
         V3 emitted = hit_record.material->emitted(ray, hit_record, hit_record.u, hit_record.v, hit_record.position);
         Scatter sc;
         if (hit_record.material->scatter(ray, hit_record, rng, sc)) {
@@ -889,6 +922,7 @@ static V3 ray_color(const Ray& ray, V3 background, const Hittable& world, const 
         }
         return emitted;
     }
+    trace_note(ray, false, hit_record);
     return background;
 }
 /* ---- main.rs:118-190 ---- */
@@ -897,6 +931,7 @@ static V3 ray_color_without_light_objects(const Ray& ray, V3 background, const H
     g_segments++;
     HitRecord hit_record;
     if (world.hit(ray, 0.001, RT_INF, rng, hit_record)) {
+        trace_note(ray, true, hit_record);
         V3 emitted = hit_record.material->emitted(ray, hit_record, hit_record.u, hit_record.v, hit_record.position);
         Scatter sc;
         if (hit_record.material->scatter(ray, hit_record, rng, sc)) {
@@ -914,6 +949,7 @@ static V3 ray_color_without_light_objects(const Ray& ray, V3 background, const H
         }
         return emitted;
     }
+    trace_note(ray, false, hit_record);
     return background;
 }
 
@@ -1155,6 +1191,7 @@ orc_scene* orc_scene_build(int arm, uint64_t build_seed, double aspect_ratio, co
         bool needs_earth = (arm == 3) || (arm < 0 || arm > 6);
         if (needs_earth && !earth) return nullptr;
         orc_scene* o = new orc_scene();
+        g_next_leaf = 0; g_next_medium = 0;
         o->s = build_scene(arm, build_seed, aspect_ratio, a);
         if (defaults) {
             defaults[0] = o->s.image_width;
@@ -1341,6 +1378,157 @@ int orc_aov(const orc_scene* o, uint32_t width, uint32_t height, uint32_t x0, ui
     return 0;
 #endif
 }
+/* ---- the caller's own rays (include/rt1w.h: rt1w_hit, rt1w_ray_color), stated on the class surface above ----
+ * orc_hit: for ray r of rays[n][9] = origin, direction, time, t_min, t_max: world.hit(ray, t_min, t_max, rng) (hittable.rs:63-64) on the
+ * scene's Hittable tree with rng = orc_rng_pixel(first_stream + r, sample, global_seed) drawn from its first word.  out[n][12] in the
+ * layout of rt1w_hit: hit 1 / 0, t, p, normal, u, v, front_face, material (the same number as out_mat, as a double); a miss is zeros.
+ * u, v are the record's own, always.  out_mat[n]: the index of the hit material in the builder's material list (orcb_mat_* order), -1
+ * for a material the builder did not hand out (a ConstantMedium's own Isotropic; every material of orc_scene_build) and on a miss.
+ * out_aux (may be NULL) int32[n][4], zeros on a miss: HitRecord.tag, HitRecord.leaf (see there), the material's dynamic type (0 Lambertian,
+ * 1 Metal, 2 Dielectric, 3 DiffuseLight, 4 Isotropic, 5 `()`), 1 if an image texture (texture.rs:67-89, the only one that reads u, v)
+ * stands in the material's texture tree.  No special case for non-finite or degenerate rays: the literal code runs on what it is given.
+ * The reference-stream build returns -1: its stream has no (pixel, sample) streams to start from. */
+#if !ORC_STREAM_PER_PIXEL
+static int material_kind(const Material* m) {
+    if (dynamic_cast<const Lambertian*>(m)) return 0;
+    if (dynamic_cast<const Metal*>(m)) return 1;
+    if (dynamic_cast<const Dielectric*>(m)) return 2;
+    if (dynamic_cast<const DiffuseLight*>(m)) return 3;
+    if (dynamic_cast<const Isotropic*>(m)) return 4;
+    return 5;
+}
+static bool texture_reads_uv(const Texture* t) {
+    if (dynamic_cast<const ImageTexture*>(t)) return true;
+    if (const CheckerTexture* c = dynamic_cast<const CheckerTexture*>(t)) return texture_reads_uv(c->odd.get()) || texture_reads_uv(c->even.get());
+    return false;
+}
+static bool material_reads_uv(const Material* m) {
+    if (const Lambertian* l = dynamic_cast<const Lambertian*>(m)) return texture_reads_uv(l->albedo.get());
+    if (const DiffuseLight* d = dynamic_cast<const DiffuseLight*>(m)) return texture_reads_uv(d->emit.get());
+    if (const Isotropic* i = dynamic_cast<const Isotropic*>(m)) return texture_reads_uv(i->albedo.get());
+    return false;
+}
+#endif
+int orc_hit(const orc_scene* o, const double* rays, uint64_t n, uint64_t first_stream, uint32_t sample, uint32_t global_seed, double* out,
+            int32_t* out_mat, int32_t* out_aux) {
+#if ORC_STREAM_PER_PIXEL
+    (void)o; (void)rays; (void)n; (void)first_stream; (void)sample; (void)global_seed; (void)out; (void)out_mat; (void)out_aux;
+    return -1;
+#else
+    if (!o || !rays || !out || !out_mat) return -1;
+    const Scene& s = o->s;
+    for (uint64_t r = 0; r < n; ++r) {
+        const double* q = rays + r * 9;
+        Ray ray{rt_v3(q[0], q[1], q[2]), rt_v3(q[3], q[4], q[5]), q[6]};
+        MyRng rng = orc_rng_pixel(first_stream + r, sample, global_seed);
+        HitRecord rec;
+        double* d = out + r * 12;
+        for (int k = 0; k < 12; ++k) d[k] = 0.0;
+        out_mat[r] = -1;
+        if (out_aux) for (int k = 0; k < 4; ++k) out_aux[r * 4 + k] = 0;
+        if (!s.world->hit(ray, q[7], q[8], rng, rec)) continue;
+        d[0] = 1.0; d[1] = rec.t; d[2] = rec.position.x; d[3] = rec.position.y; d[4] = rec.position.z;
+        d[5] = rec.normal.x; d[6] = rec.normal.y; d[7] = rec.normal.z; d[8] = rec.u; d[9] = rec.v; d[10] = rec.front_face ? 1.0 : 0.0;
+        for (size_t m = 0; m < o->keep_mats.size(); ++m) if (o->keep_mats[m].get() == rec.material) { out_mat[r] = (int32_t)m; break; }
+        d[11] = (double)out_mat[r];
+        if (out_aux) {
+            out_aux[r * 4] = (int32_t)rec.tag; out_aux[r * 4 + 1] = (int32_t)rec.leaf;
+            out_aux[r * 4 + 2] = material_kind(rec.material); out_aux[r * 4 + 3] = material_reads_uv(rec.material) ? 1 : 0;
+        }
+    }
+    return 0;
+#endif
+}
+/* orc_ray_color: one sample per ray of rays[n][stride] = origin, direction, time, ..: ray_color / ray_color_without_light_objects as
+ * orc_render chooses between them (main.rs:972-989), with the stream orc_rng_pixel(first_stream + r, sample, global_seed) moved to word
+ * start_word[r] (NULL: 0) by drawing and discarding that many 32-bit words.  out[n][3]: the sample; out_segments[n] (may be NULL): the
+ * ray's segments as orc_render counts them.  trace (may be NULL, then cap = 0): for ray 0 only, 16 doubles per segment up to cap segments
+ * -- hit, t, p, tag, leaf, front_face, the segment's ray (origin, direction, time), 0; *n_trace = the segments noted.
+ * The reference-stream build returns -1. */
+int orc_ray_color_trace(const orc_scene* o, const double* rays, const uint32_t* start_word, uint64_t n, uint32_t stride, uint64_t first_stream,
+                        uint32_t sample, uint32_t global_seed, uint32_t max_depth, double* out, uint32_t* out_segments, double* trace, uint32_t cap,
+                        uint32_t* n_trace) {
+#if ORC_STREAM_PER_PIXEL
+    (void)o; (void)rays; (void)start_word; (void)n; (void)stride; (void)first_stream; (void)sample; (void)global_seed; (void)max_depth; (void)out;
+    (void)out_segments; (void)trace; (void)cap; (void)n_trace;
+    return -1;
+#else
+    if (!o || !rays || !out || stride < 7) return -1;
+    const Scene& s = o->s;
+    std::vector<double> noted;
+    for (uint64_t r = 0; r < n; ++r) {
+        const double* q = rays + r * stride;
+        Ray ray{rt_v3(q[0], q[1], q[2]), rt_v3(q[3], q[4], q[5]), q[6]};
+        MyRng rng = orc_rng_pixel(first_stream + r, sample, global_seed);
+        for (uint32_t w = 0; start_word && w < start_word[r]; ++w) (void)rt_next_u32(rng);
+        g_segments = 0;
+        g_trace = (trace && r == 0) ? &noted : nullptr;
+        V3 col = s.lights ? ray_color(ray, s.background, *s.world, *s.lights, max_depth, rng)
+                          : ray_color_without_light_objects(ray, s.background, *s.world, max_depth, rng);
+        g_trace = nullptr;
+        out[r * 3] = col.x; out[r * 3 + 1] = col.y; out[r * 3 + 2] = col.z;
+        if (out_segments) out_segments[r] = (uint32_t)g_segments;
+    }
+    if (trace) {
+        const size_t rows = std::min((size_t)cap, noted.size() / 16);
+        for (size_t k = 0; k < rows * 16; ++k) trace[k] = noted[k];
+        if (n_trace) *n_trace = (uint32_t)(noted.size() / 16);
+    }
+    return 0;
+#endif
+}
+int orc_ray_color(const orc_scene* o, const double* rays, const uint32_t* start_word, uint64_t n, uint32_t stride, uint64_t first_stream,
+                  uint32_t sample, uint32_t global_seed, uint32_t max_depth, double* out, uint32_t* out_segments) {
+    return orc_ray_color_trace(o, rays, start_word, n, stride, first_stream, sample, global_seed, max_depth, out, out_segments, nullptr, 0, nullptr);
+}
+/* what a scene holds, read off its object graph: out[0] Spheres with a Dielectric, out[1] ConstantMediums, out[2] AABoxes under a
+ * Translate or RotateY, out[3] Translates, out[4] RotateYs, out[5] FlipFaces, out[6] MovingSpheres (a medium's boundary counts for the
+ * medium only: it returns no record of its own); box[6]: the world's bounding box over [0, 1] */
+static void scene_census(const Hittable* h, bool wrapped, int32_t out[7]) {
+    if (const BVHNode* b = dynamic_cast<const BVHNode*>(h)) { scene_census(b->left.get(), wrapped, out); if (b->right) scene_census(b->right.get(), wrapped, out); }
+    else if (dynamic_cast<const AABox*>(h)) { if (wrapped) out[2]++; }
+    else if (const Translate* t = dynamic_cast<const Translate*>(h)) { out[3]++; scene_census(t->hittable.get(), true, out); }
+    else if (const RotateY* ry = dynamic_cast<const RotateY*>(h)) { out[4]++; scene_census(ry->hittable.get(), true, out); }
+    else if (const FlipFace* f = dynamic_cast<const FlipFace*>(h)) { out[5]++; scene_census(f->inner.get(), wrapped, out); }
+    else if (dynamic_cast<const ConstantMedium*>(h)) out[1]++;
+    else if (dynamic_cast<const MovingSphere*>(h)) out[6]++;
+    else if (const Sphere* sp = dynamic_cast<const Sphere*>(h)) { if (dynamic_cast<const Dielectric*>(sp->material.get())) out[0]++; }
+}
+int orc_scene_census(const orc_scene* o, int32_t out[7], double box[6]) {
+    if (!o || !out || !box) return -1;
+    for (int k = 0; k < 7; ++k) out[k] = 0;
+    scene_census(o->s.world.get(), false, out);
+    AABB b;
+    if (!o->s.world->bounding_box(0.0, 1.0, b)) return -1;
+    box[0] = b.minimum.x; box[1] = b.minimum.y; box[2] = b.minimum.z; box[3] = b.maximum.x; box[4] = b.maximum.y; box[5] = b.maximum.z;
+    return 0;
+}
+/* The slab planes of the scene, in the space of the ray that meets them: rows of 7 doubles -- 0, then the aabb of a BVHNode (minimum,
+ * maximum), for every BVHNode of the graph (those inside wrappers, boxes and media included); or 1 + the fixed axis (1 x, 2 y, 3 z) of
+ * an axis-aligned rect, its plane k in the first slot and zeros.  Returns the number of rows; writes at most cap of them. */
+static void scene_planes(const Hittable* h, std::vector<double>& rows) {
+    auto rect = [&](int axis, Float k) { const double r[7] = {(double)(1 + axis), (double)k, 0, 0, 0, 0, 0}; rows.insert(rows.end(), r, r + 7); };
+    if (const BVHNode* b = dynamic_cast<const BVHNode*>(h)) {
+        const double r[7] = {0, (double)b->aabb.minimum.x, (double)b->aabb.minimum.y, (double)b->aabb.minimum.z, (double)b->aabb.maximum.x, (double)b->aabb.maximum.y, (double)b->aabb.maximum.z};
+        rows.insert(rows.end(), r, r + 7);
+        scene_planes(b->left.get(), rows);
+        if (b->right) scene_planes(b->right.get(), rows);
+    } else if (const AABox* a = dynamic_cast<const AABox*>(h)) scene_planes(a->sides.get(), rows);
+    else if (const Translate* t = dynamic_cast<const Translate*>(h)) scene_planes(t->hittable.get(), rows);
+    else if (const RotateY* ry = dynamic_cast<const RotateY*>(h)) scene_planes(ry->hittable.get(), rows);
+    else if (const FlipFace* f = dynamic_cast<const FlipFace*>(h)) scene_planes(f->inner.get(), rows);
+    else if (const ConstantMedium* m = dynamic_cast<const ConstantMedium*>(h)) scene_planes(m->boundary.get(), rows);
+    else if (const XYRect* xy = dynamic_cast<const XYRect*>(h)) rect(3, xy->k);
+    else if (const XZRect* xz = dynamic_cast<const XZRect*>(h)) rect(2, xz->k);
+    else if (const YZRect* yz = dynamic_cast<const YZRect*>(h)) rect(1, yz->k);
+}
+uint64_t orc_scene_planes(const orc_scene* o, double* out, uint64_t cap) {
+    if (!o) return 0;
+    std::vector<double> rows;
+    scene_planes(o->s.world.get(), rows);
+    for (size_t k = 0; out && k < rows.size() && k < cap * 7; ++k) out[k] = rows[k];
+    return rows.size() / 7;
+}
 /* 1 = this library was built with -DORC_REFSTREAM (ChaCha12 per-pixel stream + libm) */
 int orc_is_refstream(void) { return ORC_STREAM_PER_PIXEL; }
 
@@ -1361,7 +1549,7 @@ struct orc_builder {
     V3 background;
     Camera camera;
 };
-orc_builder* orcb_new(uint64_t build_seed) { orc_builder* b = new orc_builder(); b->rng = orc_rng_build(build_seed); b->background = rt_v3(0, 0, 0); return b; }
+orc_builder* orcb_new(uint64_t build_seed) { orc_builder* b = new orc_builder(); g_next_leaf = 0; g_next_medium = 0; b->rng = orc_rng_build(build_seed); b->background = rt_v3(0, 0, 0); return b; }
 void orcb_free(orc_builder* b) { delete b; }
 double orcb_rng_f64(orc_builder* b) { return rt_gen_f64(b->rng); }
 double orcb_rng_range(orc_builder* b, double lo, double hi) { return rt_gen_range(b->rng, lo, hi); }

@@ -350,6 +350,7 @@ _LAB_SIGS = {
     "rt1w_lab_camera_rays_host": [_P, _PR, _P],
     "rt1w_lab_camera_rays_pos_host": [_P, _PR, _P, _P],
     "rt1w_lab_ray_color_host": [_P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(_N)],
+    "rt1w_lab_ray_color_counts_host": [_P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(_N), _P],
     "rt1w_lab_denoise_host": [_PD, _P, _P, _P],
     "rt1w_lab_batch_variance_host": [_U] * 5 + [_P] * 4,
     "rt1w_lab_denoise_var_host": [_PD, _P, _P, _P, _F, _P],
@@ -1430,12 +1431,15 @@ def camera_rays_pos_host(scene, width, height, spp, tile=None, sample_offset=0, 
 
 def ray_color_host(scene, rays, start_word=None, with_stats=False, **kw):
     """CPU twin of Context.ray_color (librt1w_lab.so: rt1w_lab_ray_color_host, rt_ray_list.h and rt_core.h built for the host): the
-    array the GPU must equal bit for bit; with_stats: (array, {"segments": rays traced}).  No GPU needed.  This twin says why it
-    refuses a call, as the entries do."""
+    array the GPU must equal bit for bit; with_stats: (array, {"segments": rays traced, "ray_segments": uint32 [n], the rays traced per
+    ray of the list (rt1w_lab_ray_color_counts_host)}).  No GPU needed.  This twin says why it refuses a call, as the entries do."""
     args, out = _ray_color_prep(rays, start_word, kw)
     seg = C.c_uint64()
-    _twin("rt1w_lab_ray_color_host", ((scene._h, *args), out), C.byref(seg), says_why=True)
-    return (out, {"segments": seg.value}) if with_stats else out
+    if not with_stats:
+        return _twin("rt1w_lab_ray_color_host", ((scene._h, *args), out), C.byref(seg), says_why=True)
+    per_ray = np.zeros(out.shape[0], dtype=np.uint32)
+    _twin("rt1w_lab_ray_color_counts_host", ((scene._h, *args), out), C.byref(seg), per_ray, says_why=True)
+    return out, {"segments": seg.value, "ray_segments": per_ray}
 
 
 def guides_merge_tiles_host(gacc, tile_sums, spp, tile, tiles):

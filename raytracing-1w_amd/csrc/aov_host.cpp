@@ -146,11 +146,13 @@ bool hit_rays(const RtSceneView& sc, const RtHitParams& hp, uint64_t k0, uint64_
 /* rays k0, k0 + step, .. of a radiance list, as the ray-list kernels run them (rt_kernel_sorted.h with RT_RAY_LIST): per ray, per work item
  * of f.chunk samples, per sample rt_ray_begin and rt_path_step until the path ends; the items' sums added in order (rt_resolve_kernel) */
 template <class Cfg>
-bool ray_color_rays(const RtSceneView& sc, const RtFrame& f, const RtRayList& rl, bool out_sum, uint64_t k0, uint64_t step, double* out, uint64_t* segments) {
+bool ray_color_rays(const RtSceneView& sc, const RtFrame& f, const RtRayList& rl, bool out_sum, uint64_t k0, uint64_t step, double* out, uint64_t* segments,
+                    uint32_t* ray_segments) {
     AovHostStack stk;
     RtGlobalNodes ns{sc.nodes};
     for (uint64_t r = k0; r < rl.n; r += step) {
         const bool traced = rt_ray_traced(rl.rays + r * (uint64_t)rl.stride);
+        const uint64_t before = *segments;
         RtV3 total = rt_v3(0.0, 0.0, 0.0);
         for (uint32_t chunk = 0; chunk < f.n_chunks; ++chunk) {
             const uint32_t s0 = chunk * f.chunk, s_end = s0 + f.chunk < f.spp ? s0 + f.chunk : f.spp;
@@ -171,13 +173,14 @@ bool ray_color_rays(const RtSceneView& sc, const RtFrame& f, const RtRayList& rl
         }
         if (!out_sum) total = rt_into_sampled(total, f.spp);
         out[r * 3u] = total.x; out[r * 3u + 1u] = total.y; out[r * 3u + 2u] = total.z;
+        if (ray_segments) ray_segments[r] = (uint32_t)(*segments - before);
     }
     return true;
 }
 } // namespace
 
-extern "C" int rt1w_lab_ray_color_host(const rt1w_scene* s, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out,
-                                       uint64_t* segments) {
+extern "C" int rt1w_lab_ray_color_counts_host(const rt1w_scene* s, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out,
+                                              uint64_t* segments, uint32_t* ray_segments) {
     static_assert(sizeof(rt1w_ray_color_params) == sizeof(RtRayColorParams), "rt1w_ray_color_params is RtRayColorParams' layout");
     if (!s || !s->committed) { rt1w_internal_set_error("null or uncommitted scene"); return RT1W_ERR_INVALID; }
     if (const char* why = rt_ray_color_refusal((const RtRayColorParams*)p, rays, start_word, out, RT1W_OUT_SUM, RT1W_GENERIC)) { /* the entries' own check */
@@ -198,11 +201,16 @@ extern "C" int rt1w_lab_ray_color_host(const rt1w_scene* s, const rt1w_ray_color
     rl.stride = p->stride ? p->stride : (uint32_t)RT_RAY_RECORD; rl.pad = 0u;
     uint64_t segs[MAX_THREADS] = {}; /* per thread */
     const bool ok = round_robin((uint32_t)p->n, [&](uint32_t t, uint32_t n_threads) { /* the list's rays */
-        return with_variant(v, [&](auto cfg) { return ray_color_rays<decltype(cfg)>(sc, f, rl, (p->flags & RT1W_OUT_SUM) != 0u, t, n_threads, out, &segs[t]); });
+        return with_variant(v, [&](auto cfg) { return ray_color_rays<decltype(cfg)>(sc, f, rl, (p->flags & RT1W_OUT_SUM) != 0u, t, n_threads, out, &segs[t], ray_segments); });
     });
     if (!ok) return RT1W_ERR_STATE;
     if (segments) { *segments = 0u; for (uint64_t k : segs) *segments += k; }
     return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_ray_color_host(const rt1w_scene* s, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out,
+                                       uint64_t* segments) {
+    return rt1w_lab_ray_color_counts_host(s, p, rays, start_word, out, segments, nullptr);
 }
 
 extern "C" int rt1w_lab_hit_host(const rt1w_scene* s, const rt1w_hit_params* p, const double* rays, double* out, uint32_t* out_node) {

@@ -57,6 +57,9 @@ int rt1w_lab_camera_rays_pos_host(const rt1w_scene* s, const rt1w_render_params*
  * entries' own text (rt_ray_color_refusal), RT1W_ERR_STATE if a traversal stack overflowed */
 int rt1w_lab_ray_color_host(const rt1w_scene* s, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out,
                             uint64_t* segments);
+/* the same call; ray_segments (may be null) uint32[n]: the rays traced for ray r, over all of its samples -- they add up to *segments */
+int rt1w_lab_ray_color_counts_host(const rt1w_scene* s, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out,
+                                   uint64_t* segments, uint32_t* ray_segments);
 
 /* CPU twin of rt1w_denoise (denoise_host.cpp: rt_denoise.h built for the host): the same double[h][w][3] from host buffers, no GPU.
  * RT1W_OK, or RT1W_ERR_INVALID as the device entry (null pointers, zero sizes, iterations > 8, unknown flags, bad sigmas) */

@@ -42,10 +42,16 @@ def _d3(v):
 
 
 class OracleBuilt(orc.OracleScene):
-    def __init__(self, handle):
+    """material_of: oracle material index (orcb_mat_* order) -> the product's material id; isotropic_of: the construction number of a
+    ConstantMedium in the oracle (HitRecord.leaf) -> the id its Isotropic must have in the product by include/rt1w.h's rule, the next
+    free id at the moment the medium was made."""
+
+    def __init__(self, handle, material_of=None, isotropic_of=None):
         self._h = handle
         self.defaults = None
         self.earth = None
+        self.material_of = dict(material_of or {})
+        self.isotropic_of = dict(isotropic_of or {})
 
 
 class Dual:
@@ -58,6 +64,13 @@ class Dual:
         self.best_axis = best_axis  # the product's default build (RT1W_BVH_BEST_AXIS); False: both sides draw the axes (RT1W_BVH_REFERENCE)
         A.orc_set_bvh_axis_rule(1 if best_axis else 0)
         self._img = []
+        self.material_of, self.isotropic_of = {}, {}
+        self._next_free = 0   # the product's next free material id: constructors and media take them in turn (include/rt1w.h)
+
+    def _mat(self, pair):
+        self.material_of[pair[1]] = pair[0]
+        self._next_free += 1
+        return pair
 
     def rng_f64(self):
         a, b = self.p.rng_f64(), A.orcb_rng_f64(self.o)
@@ -74,11 +87,11 @@ class Dual:
         h, w = rgb8.shape[:2]
         return (self.p.image_texture(rgb8), A.orcb_tex_image(self.o, rgb8.ctypes.data_as(_P), w, h))
 
-    def lambertian(self, t): return (self.p.lambertian(t[0]), A.orcb_mat_lambertian(self.o, t[1]))
-    def metal(self, c, fuzz): return (self.p.metal(c, fuzz), A.orcb_mat_metal(self.o, float(c[0]), float(c[1]), float(c[2]), fuzz))
-    def dielectric(self, ir): return (self.p.dielectric(ir), A.orcb_mat_dielectric(self.o, ir))
-    def diffuse_light(self, t): return (self.p.diffuse_light(t[0]), A.orcb_mat_diffuse_light(self.o, t[1]))
-    def null_material(self): return (self.p.null_material(), A.orcb_mat_null(self.o))
+    def lambertian(self, t): return self._mat((self.p.lambertian(t[0]), A.orcb_mat_lambertian(self.o, t[1])))
+    def metal(self, c, fuzz): return self._mat((self.p.metal(c, fuzz), A.orcb_mat_metal(self.o, float(c[0]), float(c[1]), float(c[2]), fuzz)))
+    def dielectric(self, ir): return self._mat((self.p.dielectric(ir), A.orcb_mat_dielectric(self.o, ir)))
+    def diffuse_light(self, t): return self._mat((self.p.diffuse_light(t[0]), A.orcb_mat_diffuse_light(self.o, t[1])))
+    def null_material(self): return self._mat((self.p.null_material(), A.orcb_mat_null(self.o)))
     def sphere(self, c, r, m): return (self.p.sphere(c, r, m[0]), A.orcb_sphere(self.o, float(c[0]), float(c[1]), float(c[2]), r, m[1]))
 
     def moving_sphere(self, c0, c1, t0, t1, r, m):
@@ -92,7 +105,11 @@ class Dual:
     def translate(self, h, off): return (self.p.translate(h[0], off), A.orcb_translate(self.o, h[1], float(off[0]), float(off[1]), float(off[2])))
     def rotate_y(self, h, deg): return (self.p.rotate_y(h[0], deg), A.orcb_rotate_y(self.o, h[1], deg))
     def flip_face(self, h): return (self.p.flip_face(h[0]), A.orcb_flip_face(self.o, h[1]))
-    def constant_medium(self, h, d, t): return (self.p.constant_medium(h[0], d, t[0]), A.orcb_constant_medium(self.o, h[1], d, t[1]))
+
+    def constant_medium(self, h, d, t):
+        self.isotropic_of[len(self.isotropic_of)] = self._next_free  # the oracle numbers its media in construction order
+        self._next_free += 1
+        return (self.p.constant_medium(h[0], d, t[0]), A.orcb_constant_medium(self.o, h[1], d, t[1]))
 
     def bvh(self, hs):
         arr = (C.c_int * len(hs))(*[h[1] for h in hs])
@@ -116,7 +133,7 @@ class Dual:
         h = A.orcb_finish(self.o)
         A.orc_set_bvh_axis_rule(0)
         self.o = None
-        return self.p, OracleBuilt(h)
+        return self.p, OracleBuilt(h, self.material_of, self.isotropic_of)
 
 
 def random_scene_pair(seed, n_objects=None, best_axis=True):

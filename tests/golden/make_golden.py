@@ -8,6 +8,7 @@
     configurations of every scene arm, incl. BASELINE config C1 (Cornell 200x200x64);
 (3) block means of the same oracle built with `type Float = f32` (oracle/oracle_f32.cpp) -- `make_golden.py f32` makes only these;
 (4) `make_golden.py census [frame ...]` only: the census of non-finite samples of the single-precision frames (f32_nonfinite_census.json).
+(5) `make_golden.py query` only: the census of the ray sets of the query tests (query_oracle_census.json), from the literal oracle alone.
 The reference (Rust) cannot be run here, so (2) are oracle outputs, not reference
 outputs; (1) is the reference's.
 """
@@ -204,9 +205,18 @@ def census(only=None):
     with open(path, 'w') as f:
         json.dump(out, f, indent=1)
 
+def query_census():
+    """(5) `make_golden.py query`: per scene and set of tests/query_rays.py what the literal oracle says of the rays -- hits, hits under a
+    wrapper, rays started inside glass / a medium / a wrapped box, window cuts, slab-plane rays, segments.  Asserts every set's conditions."""
+    import query_rays
+    with open(query_rays.CENSUS_PATH, 'w') as f:
+        json.dump(query_rays.census_document(), f, indent=1)
+
 def main():
     if sys.argv[1:] == ["f32"]:
         return f32_frames()
+    if sys.argv[1:] == ["query"]:
+        return query_census()
     if sys.argv[1:2] == ["census"]:
         return census(sys.argv[2:])
     f32_frames()

@@ -37,6 +37,16 @@ for _L in (A, REF):
     _L.orc_is_refstream.restype = C.c_int
     _L.orc_aov.restype = C.c_int
     _L.orc_aov.argtypes = [_P] + [C.c_uint32] * 10 + [C.c_double, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_uint64)]
+    _L.orc_hit.restype = C.c_int
+    _L.orc_hit.argtypes = [_P, _P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P]
+    _L.orc_ray_color.restype = C.c_int
+    _L.orc_ray_color.argtypes = [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]
+    _L.orc_ray_color_trace.restype = C.c_int
+    _L.orc_ray_color_trace.argtypes = _L.orc_ray_color.argtypes + [_P, C.c_uint32, C.POINTER(C.c_uint32)]
+    _L.orc_scene_census.restype = C.c_int
+    _L.orc_scene_census.argtypes = [_P, _P, _P]
+    _L.orc_scene_planes.restype = C.c_uint64
+    _L.orc_scene_planes.argtypes = [_P, _P, C.c_uint64]
 # the same restatement with `type Float = f32` (main.rs:1; oracle/oracle_f32.cpp): `double` parameters are `float` in this library
 F32 = C.CDLL(os.path.join(ORACLE_DIR, "liborc_f32.so"))
 F32.orc_scene_build.restype = _P
@@ -80,6 +90,12 @@ def rt():
 
 def default_aspect(arm):
     return 1.0 if (arm in (5, 6) or arm < 0 or arm > 6) else 16.0 / 9.0
+
+
+# oracle.cpp: HitRecord.tag and material_kind, as OracleScene.hit hands them out
+LEAF_SPHERE, LEAF_MOVING, LEAF_XY, LEAF_XZ, LEAF_YZ, LEAF_MEDIUM, LEAF_MASK = 1, 2, 3, 4, 5, 6, 7
+TAG_BOX, TAG_TRANSLATE, TAG_ROTATE, TAG_FLIP = 8, 16, 32, 64
+MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_LIGHT, MAT_ISOTROPIC, MAT_NULL = range(6)
 
 
 class OracleScene:
@@ -157,6 +173,63 @@ class OracleScene:
         if rc != 0:
             raise RuntimeError(f"orc_aov refused ({rc})")
         return out, {"segments": seg.value, "paths": tw * th * spp, "counts": [int(c) for c in counts]}
+
+    def hit(self, rays, first_stream=0, sample=0, global_seed=0):
+        """world.hit of the caller's rays [n, 9] = origin, direction, time, t_min, t_max on the literal tree (oracle.cpp: orc_hit), ray r
+        with the stream of (first_stream + r, sample, global_seed) from its first word.  Returns (records float64 [n, 12] in rt1w_hit's
+        layout with the record's own u, v always; material int32 [n]: the index in the builder's material list, -1 for a material the
+        builder did not hand out and on a miss; aux int32 [n, 4]: where the record came from (ORC_TAG_* bits, the construction number of
+        the leaf / box / medium), the material's type (MAT_*), 1 if its texture tree holds an image texture)."""
+        r = np.ascontiguousarray(rays, dtype=np.float64)
+        assert r.ndim == 2 and r.shape[1] == 9
+        out = np.empty((len(r), 12), dtype=np.float64)
+        mat = np.empty(len(r), dtype=np.int32)
+        aux = np.empty((len(r), 4), dtype=np.int32)
+        rc = self.lib.orc_hit(self._h, r.ctypes.data_as(_P), len(r), first_stream, sample, global_seed, out.ctypes.data_as(_P),
+                              mat.ctypes.data_as(_P), aux.ctypes.data_as(_P))
+        if rc != 0:
+            raise RuntimeError(f"orc_hit refused ({rc})")
+        return out, mat, aux
+
+    def ray_color(self, rays, start_word=None, first_stream=0, sample=0, global_seed=0, max_depth=50, trace=0):
+        """One sample of ray_color per ray of rays [n, stride >= 7] (oracle.cpp: orc_ray_color), the stream of (first_stream + r, sample,
+        global_seed) moved to word start_word[r] by drawing that many 32-bit words.  Returns (float64 [n, 3], segments uint32 [n]);
+        trace = k > 0: also float64 [segments of ray 0, up to k][16], the segments of ray 0 (hit, t, p, tag, leaf, front_face, the
+        segment's ray, 0)."""
+        r = np.ascontiguousarray(rays, dtype=np.float64)
+        assert r.ndim == 2 and r.shape[1] >= 7
+        sw = None if start_word is None else np.ascontiguousarray(start_word, dtype=np.uint32)
+        assert sw is None or sw.shape == (len(r),)
+        out = np.empty((len(r), 3), dtype=np.float64)
+        seg = np.empty(len(r), dtype=np.uint32)
+        args = [self._h, r.ctypes.data_as(_P), None if sw is None else sw.ctypes.data_as(_P), len(r), r.shape[1], first_stream, sample, global_seed,
+                max_depth, out.ctypes.data_as(_P), seg.ctypes.data_as(_P)]
+        if not trace:
+            rc = self.lib.orc_ray_color(*args)
+        else:
+            rows, n = np.zeros((trace, 16), dtype=np.float64), C.c_uint32()
+            rc = self.lib.orc_ray_color_trace(*args, rows.ctypes.data_as(_P), trace, C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"orc_ray_color refused ({rc})")
+        return (out, seg, rows[:min(trace, n.value)]) if trace else (out, seg)
+
+    def census(self):
+        """what the scene's object graph holds (oracle.cpp: orc_scene_census): how many glass spheres, media, boxes under a Translate /
+        RotateY, Translates, RotateYs, FlipFaces and moving spheres; and the world's bounding box over the shutter, (lo [3], hi [3])"""
+        n, box = np.zeros(7, dtype=np.int32), np.zeros(6, dtype=np.float64)
+        assert self.lib.orc_scene_census(self._h, n.ctypes.data_as(_P), box.ctypes.data_as(_P)) == 0
+        names = ("glass_spheres", "media", "wrapped_boxes", "translates", "rotates", "flips", "moving_spheres")
+        return {k: int(v) for k, v in zip(names, n)}, (box[:3].copy(), box[3:].copy())
+
+    def planes(self):
+        """the slab planes of the scene's own graph (oracle.cpp: orc_scene_planes): per axis x, y, z the set of coordinates that are a
+        face of some BVHNode's box or the plane of an axis-aligned rect"""
+        n = int(self.lib.orc_scene_planes(self._h, None, 0))
+        rows = np.zeros((max(n, 1), 7), dtype=np.float64)
+        self.lib.orc_scene_planes(self._h, rows.ctypes.data_as(_P), n)
+        rows = rows[:n]
+        box = rows[rows[:, 0] == 0.0]
+        return [set(box[:, 1 + a]) | set(box[:, 4 + a]) | set(rows[rows[:, 0] == 1.0 + a, 1]) for a in range(3)]
 
     def apply_topology(self, topo, merge_nested=True):
         """Rebuild every BVH of this oracle scene over its own leaves with the trees of `topo` (the product's opt-in SAH build,
