@@ -1123,7 +1123,9 @@ int rt1w_debug_aabb(rt1w_context* c, const double* in, int* out_literal, int* ou
 /* The shading-side leaf functions ON THE DEVICE for n inputs in[i] = {u, v, p.x, p.y, p.z}, out[i] = 3 doubles:
  * mode 0 `Texture::value(u, v, p)` of texture `tex` of the context's scene (src/texture.rs:40-89) -> rgb;
  * mode 1 `Perlin::noise(p)` and `Perlin::turb(p, 7)` of Perlin table `tex` (src/perlin.rs:46-86) -> out[0], out[1];
- * mode 2 `sphere_uv(p)` (src/math.rs:67-71) -> out[0] = u, out[1] = v.
+ * mode 2 `sphere_uv(p)` (src/math.rs:67-71) -> out[0] = u, out[1] = v; it reads no record of the scene and ignores `tex`.
+ * RT1W_ERR_INVALID, before anything is launched: a null pointer, an unknown mode, mode 0 with `tex` not a texture of the scene,
+ * mode 1 with `tex` not one of its Perlin tables (a scene has one per noise texture, in the order they were made).
  * Known-answer tests of what no artefact of the reference reaches (lattice points of the noise, checker parity, poles and
  * seam of sphere_uv). */
 int rt1w_debug_texture(rt1w_context* c, int mode, uint32_t tex, const double* in, double* out, uint64_t n);

@@ -241,10 +241,10 @@ struct Perlin { /* perlin.rs:8-106, POINT_COUNT = 256 */
         generate_perm(rng, perm_y);
         generate_perm(rng, perm_z);
     }
-    static int64_t as_isize(Float f) { /* saturating `as isize` */
+    static int64_t as_isize(Float f) { /* saturating `as isize`: at 2^63 and below -2^63 (-2^63 itself converts exactly), NaN -> 0 */
         if (f != f) return 0;
-        if (f >= 9.2e18) return INT64_MAX;
-        if (f <= -9.2e18) return INT64_MIN;
+        if (f >= 9223372036854775808.0) return INT64_MAX;
+        if (f < -9223372036854775808.0) return INT64_MIN;
         return (int64_t)f;
     }
     Float noise(V3 p) const { /* perlin.rs:46-72 */

@@ -100,6 +100,26 @@ uint64_t orcflat_f32_records(const void* nodes, uint32_t n_nodes, const void* li
     return bytes;
 }
 
+/* The shading-side leaf functions of the f32 core over the converted records, for the known-answer tests (tests/test_texture_kats.py):
+ * in[i] = {u, v, p.x, p.y, p.z}, each rounded to float once; out[i] = 3 results widened to double.  mode 0 rt_texture of texture `tex`,
+ * mode 1 rt_perlin_noise and rt_perlin_turb(.., 7) of Perlin table `tex`.  0, or -1: another mode, or `tex` beyond the records. */
+int orcflat_f32_texture(const void* nodes, uint32_t n_nodes, const void* lights, uint32_t n_lights, const void* materials, uint32_t n_materials,
+                        const void* textures, uint32_t n_textures, const void* perlin, uint32_t n_perlin, const void* images, const void* cam_bg,
+                        int mode, uint32_t tex, const double* in, double* out, uint64_t n) {
+    if (!in || !out || mode < 0 || mode > 1 || (mode == 0 && tex >= n_textures) || (mode == 1 && tex >= n_perlin)) return -1;
+    rt_f32_scene::Arrays a;
+    convert(nodes, n_nodes, lights, n_lights, materials, n_materials, textures, n_textures, perlin, n_perlin, images, cam_bg, a);
+    for (uint64_t i = 0; i < n; ++i) {
+        const float u = (float)in[i * 5], v = (float)in[i * 5 + 1];
+        const rtf32::RtV3 p = rtf32::rt_v3((float)in[i * 5 + 2], (float)in[i * 5 + 3], (float)in[i * 5 + 4]);
+        rtf32::RtV3 r = rtf32::rt_v3(0.0f, 0.0f, 0.0f);
+        if (mode == 0) r = rtf32::rt_texture<rtf32::RtCfgV1>(a.view, tex, u, v, p);
+        else { r.x = rtf32::rt_perlin_noise(a.view.perlin[tex], p); r.y = rtf32::rt_perlin_turb(a.view.perlin[tex], p, 7); }
+        out[i * 3] = (double)r.x; out[i * 3 + 1] = (double)r.y; out[i * 3 + 2] = (double)r.z;
+    }
+    return 0;
+}
+
 /* the five elementary functions as the f32 core calls them on the host: the 64-bit function of include/rt1w_num.h, rounded once.
  * fn 0 sin(x), 1 cos(x), 2 atan2(x, y), 3 acos(x), 4 ln(x) */
 void orcflat_f32_elementary(int fn, const float* x, const float* y, uint64_t n, float* out) {

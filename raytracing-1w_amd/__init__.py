@@ -347,6 +347,7 @@ _LAB_SIGS = {
     "rt1w_lab_aov_deep_host": [_P, _PR, _U, _F, _P, C.POINTER(_N), _P],
     "rt1w_lab_aov_tiles_host": [_P, _PR, _U, _P, _U, _P],
     "rt1w_lab_hit_host": [_P, C.POINTER(HitParams), _P, _P, _P],
+    "rt1w_lab_texture_host": [_P, _I, _U, _P, _P, _N],
     "rt1w_lab_camera_rays_host": [_P, _PR, _P],
     "rt1w_lab_camera_rays_pos_host": [_P, _PR, _P, _P],
     "rt1w_lab_ray_color_host": [_P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(_N)],
@@ -1410,6 +1411,14 @@ def hit_host(scene, rays, t_min=0.001, t_max=float("inf"), first_stream=0, sampl
     must equal bit for bit.  No GPU needed."""
     args, out = _hit_prep(rays, t_min, t_max, first_stream, sample, global_seed, variant)
     return _twin("rt1w_lab_hit_host", ((scene._h, *args), out))
+
+
+def texture_host(scene, mode, tex, uvp):
+    """CPU twin of Context.debug_texture (librt1w_lab.so: rt1w_lab_texture_host, the same rt_core.h functions built for the host) over a
+    committed scene: uvp[n, 5] = u, v, p.xyz -> out[n, 3], the array the GPU must equal bit for bit.  No GPU needed."""
+    a = np.ascontiguousarray(uvp, dtype=np.float64).reshape(-1, 5)
+    out = np.empty((a.shape[0], 3), dtype=np.float64)
+    return _twin("rt1w_lab_texture_host", ((scene._h, mode, tex, a, out, a.shape[0]), out), says_why=True)
 
 
 def camera_rays_host(scene, width, height, spp, tile=None, sample_offset=0, global_seed=0, strips=None):

@@ -229,6 +229,30 @@ extern "C" int rt1w_lab_hit_host(const rt1w_scene* s, const rt1w_hit_params* p, 
     return ok ? RT1W_OK : RT1W_ERR_STATE;
 }
 
+/* what rt_debug_texture_kernel (context.hip) does per input, over the scene's host arrays */
+extern "C" int rt1w_lab_texture_host(const rt1w_scene* s, int mode, uint32_t tex, const double* in, double* out, uint64_t n) {
+    if (!s || !s->committed) { rt1w_internal_set_error("null or uncommitted scene"); return RT1W_ERR_INVALID; }
+    if (!in || !out) { rt1w_internal_set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (n == 0) return RT1W_OK;
+    if (const char* why = rt1w::debug_texture_refusal(mode, tex, in, out, s->textures.size(), s->perlin.size())) { /* the probe's own check */
+        rt1w_internal_set_error(why); return RT1W_ERR_INVALID;
+    }
+    std::vector<RtNode> nodes;
+    RtSceneView sc;
+    int v;
+    if (!host_view(s, 0u, nodes, sc, v)) return RT1W_ERR_INVALID;
+    for (uint64_t i = 0; i < n; ++i) {
+        const double u = in[i * 5], vv = in[i * 5 + 1];
+        const RtV3 p = rt_v3(in[i * 5 + 2], in[i * 5 + 3], in[i * 5 + 4]);
+        RtV3 r = rt_v3(0.0, 0.0, 0.0);
+        if (mode == 0) r = rt_texture<RtCfgV1>(sc, tex, u, vv, p);
+        else if (mode == 1) { r.x = rt_perlin_noise(sc.perlin[tex], p); r.y = rt_perlin_turb(sc.perlin[tex], p, 7); }
+        else { double su, sv; rt_sphere_uv(p, su, sv); r.x = su; r.y = sv; }
+        out[i * 3] = r.x; out[i * 3 + 1] = r.y; out[i * 3 + 2] = r.z;
+    }
+    return RT1W_OK;
+}
+
 extern "C" int rt1w_lab_camera_rays_pos_host(const rt1w_scene* s, const rt1w_render_params* p, double* out, uint32_t* out_word);
 extern "C" int rt1w_lab_camera_rays_host(const rt1w_scene* s, const rt1w_render_params* p, double* out) { return rt1w_lab_camera_rays_pos_host(s, p, out, nullptr); }
 

@@ -1094,9 +1094,10 @@ int rt1w_debug_texture(rt1w_context* c, int mode, uint32_t tex, const double* in
     if (n == 0) return RT1W_OK;
     RtSceneView view;
     memcpy(&view, &c->view, sizeof view);
-    if (mode < 0 || mode > 2) { rt1w::set_error("unknown mode"); return RT1W_ERR_INVALID; }
-    if (mode == 0 && tex >= view.n_textures) { rt1w::set_error("bad texture id"); return RT1W_ERR_INVALID; }
-    if (mode == 1 && view.perlin == nullptr) { rt1w::set_error("the scene has no Perlin table"); return RT1W_ERR_INVALID; }
+    /* h_perlin is the scene's table list as uploaded: mode 1 indexes it, so `tex` is held to its count before anything is launched */
+    if (const char* why = rt1w::debug_texture_refusal(mode, tex, in, out, view.n_textures, view.perlin ? c->h_perlin.size() : 0u)) {
+        rt1w::set_error(why); return RT1W_ERR_INVALID;
+    }
     if (!hip_ok(hipSetDevice(c->device), "hipSetDevice")) return RT1W_ERR_DEVICE;
     double *din = nullptr, *dout = nullptr;
     int rc = RT1W_OK;

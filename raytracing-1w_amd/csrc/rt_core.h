@@ -1493,10 +1493,12 @@ RT_HD bool rt_closest_hit(const RtSceneView& sc, const NS& ns, const RtRay& ray,
 RT_HD double rt_perlin_noise(const RtPerlin& pl, RtV3 p) {
     double fx = rt_floor(p.x), fy = rt_floor(p.y), fz = rt_floor(p.z);
     double u = p.x - fx, v = p.y - fy, w = p.z - fz;
-    /* `as isize` saturates; & 255 afterwards */
-    int64_t i = (fx >= RT_R(9.2e18)) ? INT64_MAX : (fx <= -RT_R(9.2e18)) ? INT64_MIN : (fx != fx ? 0 : (int64_t)fx);
-    int64_t j = (fy >= RT_R(9.2e18)) ? INT64_MAX : (fy <= -RT_R(9.2e18)) ? INT64_MIN : (fy != fy ? 0 : (int64_t)fy);
-    int64_t k = (fz >= RT_R(9.2e18)) ? INT64_MAX : (fz <= -RT_R(9.2e18)) ? INT64_MIN : (fz != fz ? 0 : (int64_t)fz);
+    /* `as isize` saturates where Rust does (perlin.rs:51-53): at 2^63 and below -2^63 (-2^63 itself converts exactly), NaN -> 0; & 255
+     * afterwards.  Both constants are exact as floats too.  A floor in [9.2e18, 2^63) converts exactly: it is a multiple of 1024, so the
+     * corners read perm[0] and perm[1] (tests/test_texture_kats.py) */
+    int64_t i = (fx >= RT_R(9223372036854775808.0)) ? INT64_MAX : (fx < -RT_R(9223372036854775808.0)) ? INT64_MIN : (fx != fx ? 0 : (int64_t)fx);
+    int64_t j = (fy >= RT_R(9223372036854775808.0)) ? INT64_MAX : (fy < -RT_R(9223372036854775808.0)) ? INT64_MIN : (fy != fy ? 0 : (int64_t)fy);
+    int64_t k = (fz >= RT_R(9223372036854775808.0)) ? INT64_MAX : (fz < -RT_R(9223372036854775808.0)) ? INT64_MIN : (fz != fz ? 0 : (int64_t)fz);
     double uu = u * u * (RT_R(3.0) - RT_R(2.0) * u);
     double vv = v * v * (RT_R(3.0) - RT_R(2.0) * v);
     double ww = w * w * (RT_R(3.0) - RT_R(2.0) * w);

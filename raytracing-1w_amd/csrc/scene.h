@@ -64,6 +64,17 @@ inline int camera_make(const double look_from[3], const double look_at[3], const
     return RT1W_OK;
 }
 
+/* What rt1w_debug_texture and its CPU twin (rt1w_lab_texture_host) refuse, before anything is launched or read: the refusal's text,
+ * or null.  Mode 0 reads texture `tex`, mode 1 Perlin table `tex`, mode 2 (sphere_uv) no record at all: it ignores `tex` */
+inline const char* debug_texture_refusal(int mode, uint32_t tex, const double* in, const double* out, size_t n_textures, size_t n_perlin) {
+    if (!in || !out) return "null argument";
+    if (mode < 0 || mode > 2) return "unknown mode";
+    if (mode == 0 && tex >= n_textures) return "bad texture id";
+    if (mode == 1 && n_perlin == 0u) return "the scene has no Perlin table";
+    if (mode == 1 && tex >= n_perlin) return "bad Perlin table index";
+    return nullptr;
+}
+
 } // namespace rt1w
 
 struct rt1w_scene {

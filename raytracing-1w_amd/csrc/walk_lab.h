@@ -44,6 +44,11 @@ int rt1w_lab_aov_deep_host(const rt1w_scene* s, const rt1w_render_params* p, uin
  * scene, same variant choice (or p->flags' RT1W_FORCE_VARIANT), no GPU.  RT1W_OK, RT1W_ERR_INVALID as the device entry (null pointers,
  * n, global_seed, flags, overlapping buffers), RT1W_ERR_STATE if a traversal stack overflowed */
 int rt1w_lab_hit_host(const rt1w_scene* s, const rt1w_hit_params* p, const double* rays, double* out, uint32_t* out_node);
+/* CPU twin of rt1w_debug_texture (aov_host.cpp: rt_texture, rt_perlin_noise, rt_perlin_turb and rt_sphere_uv of rt_core.h built for the
+ * host, called as rt_debug_texture_kernel calls them): the same modes, in[n][5] = {u, v, p.x, p.y, p.z} and out[n][3], over a committed
+ * scene's own arrays, no GPU.  RT1W_OK, RT1W_ERR_INVALID with the probe's own text (null pointers, an unknown mode, mode 0 with tex
+ * beyond the textures, mode 1 with tex beyond the Perlin tables) */
+int rt1w_lab_texture_host(const rt1w_scene* s, int mode, uint32_t tex, const double* in, double* out, uint64_t n);
 /* the camera rays of a tile: out[tile_h][tile_w][spp][8] = {origin, direction, time, 1} of the ray rt_path_begin gives sample
  * sample_offset + k of the pixel -- the ray rt1w_render and rt1w_render_aov trace first (main.rs:964-971, camera.rs:61-73).  No GPU;
  * refusals of rt1w_lab_aov_host */

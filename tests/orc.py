@@ -283,6 +283,8 @@ def flat_f32_lib(name="liborc_flat_f32.so"):
     lib.orcflat_f32_records.argtypes = _F32_ARRAYS + [_P, C.c_int, _P, C.c_uint64]
     lib.orcflat_f32_sizeof.restype = C.c_uint32
     lib.orcflat_f32_elementary.argtypes = [C.c_int, _P, _P, C.c_uint64, _P]
+    lib.orcflat_f32_texture.restype = C.c_int
+    lib.orcflat_f32_texture.argtypes = _F32_ARRAYS + [_P, _P, C.c_int, C.c_uint32, _P, _P, C.c_uint64]
     return lib
 
 
@@ -335,6 +337,22 @@ def flat_f32_records(scene, what, lib=None):
     buf = np.zeros(max(int(n), 1), dtype=np.uint8)
     lib.orcflat_f32_records(*head, ptr[6], what, buf.ctypes.data_as(_P), int(n))
     return buf[:int(n)]
+
+
+def flat_f32_texture(scene, mode, tex, uvp, lib=None):
+    """The f32 twin of the shading-side leaf functions (orcflat_f32_texture): uvp[n, 5] = u, v, p.xyz, rounded to float32 once, ->
+    float64 [n, 3] of float32 values; mode 0 Texture::value of texture `tex`, 1 Perlin noise / turb of table `tex`, over the converted
+    records of a committed scene."""
+    global _F32
+    if lib is None:
+        lib = _F32 = _F32 or flat_f32_lib()
+    arrs, info, ptr, head = _f32_array_args(scene)
+    a = np.ascontiguousarray(uvp, dtype=np.float64).reshape(-1, 5)
+    out = np.empty((a.shape[0], 3), dtype=np.float64)
+    rc = lib.orcflat_f32_texture(*head, ptr[5], ptr[6], mode, tex, a.ctypes.data_as(_P), out.ctypes.data_as(_P), a.shape[0])
+    if rc != 0:
+        raise RuntimeError(f"orcflat_f32_texture refused ({rc})")
+    return out
 
 
 def declare_flat(lib):

@@ -1,5 +1,7 @@
 """Known answers, ON THE DEVICE, for the parts of the path that no artefact of the reference pins pixel for pixel (round-2 review:
-the Cornell PNG reaches neither ConstantMedium nor the Checker / Noise / Image textures nor sphere_uv's seam).  Closed forms:
+the Cornell PNG reaches neither ConstantMedium nor the Checker / Noise textures nor sphere_uv's seam).  These are properties, not
+values; the values of the noise, of sphere_uv and of the Image texture, which nothing here tests, are held to an independent statement
+of the reference in tests/test_texture_kats.py and tests/test_texture_kats_gpu.py.  Closed forms:
   * ConstantMedium's free flight is exponential: hit_distance = -(1/density) ln(xi) (constant_medium.rs:85-91) -- a
     Kolmogorov-Smirnov test over 10^6 rays traced by the product's walk through one big medium;
   * Perlin::noise vanishes at lattice points (perlin.rs:46-72: every weight vector has a zero component product there), is bounded
