@@ -478,6 +478,83 @@ int rt1w_ray_color(rt1w_context* c, const rt1w_ray_color_params* params, const d
 int rt1w_ray_color_device(rt1w_context* c, const rt1w_ray_color_params* params, const void* d_rays, const void* d_start_word /* may be NULL */,
                           void* d_out, rt1w_stats* stats);
 
+/* ---- path states: ray_color one level at a time ----
+ * What lies between one world.hit (rt1w_hit) and the whole recursion (rt1w_ray_color): a path as a VALUE, a self-contained 128-byte record
+ * that the library advances by a chosen number of levels of ray_color (main.rs:51-116; a scene without lights :118-190).  Between calls the
+ * caller may inspect, reorder, compact or split the list, or stop: an integrator of its own, per-bounce contributions, path vertices.
+ * Carried to its end a record holds the bits of rt1w_ray_color, and begun at the camera (rt1w_path_begin) the bits of rt1w_render.
+ *   bytes    field               meaning
+ *   0-55     double ray[7]       origin xyz, direction xyz, time (Ray, ray.rs:5): the NEXT ray to trace
+ *   56-79    double beta[3]      product of attenuation * scattering_pdf / pdf so far (main.rs:96-115)
+ *   80-103   double radiance[3]  sum of beta (.) terminal values so far
+ *   104-111  uint64_t stream     pixel seed of the Philox stream: j * width + i in a render, first_stream + r in the queries
+ *   112-115  uint32_t sample     the stream's sample index
+ *   116-119  uint32_t word       position in that stream, 4 * block + word in block (rt1w_ray_color's start_word)
+ *   120-123  uint32_t depth_left the `depth` argument of ray_color still to spend
+ *   124-127  uint32_t status     RT1W_PATH_ALIVE | RT1W_PATH_TRACED | event << 8; all other bits are ignored on input and written as 0
+ * RT1W_PATH_TRACED: a level of the entry produced this ray; a caller's fresh state leaves it clear.  The event of the last level taken
+ * (RT1W_PATH_EVENT(status)): 0 none yet, 1 miss (the background, main.rs:64-66), 2 depth exhausted (main.rs:59-61), 3 DiffuseLight
+ * (emitted, no scatter: material.rs:168-181, main.rs:110-112), 4 `()` (material.rs:68: absorbed), 5 Lambertian, 6 Metal, 7 Dielectric,
+ * 8 Isotropic -- the material of the leaf hit, whether or not it scattered --, 9 not traced (a caller's ray that is not finite).
+ * Everything a level needs travels in the record; only global_seed is per call.
+ *
+ * rt1w_path_step advances each of n states by up to `steps` levels while it is alive:
+ *   - RT1W_PATH_TRACED clear and one of the seven ray doubles an infinity or a NaN (the ONE DEVIATION rt1w_ray_color has): the level is a
+ *     miss that is not traced, radiance += beta (.) (depth_left == 0 ? 0 : background), the state is dead with event 9;
+ *   - else one level: the stream of (stream, sample, global_seed) placed at `word`; depth check and world.hit (main.rs:59-62), emitted,
+ *     scatter, the next ray (main.rs:63-115); `word` = where the stream stands afterwards, RT1W_PATH_TRACED set, the event written.  A ray
+ *     a level produced is traced as it is, finite or not, as the render kernels trace it;
+ *   - a dead state is copied unchanged, every bit of it.
+ * Split, order and company change no bit: 64 levels in one call, in 64 calls, with the list shuffled or compacted in between.
+ *   out_node  (may be NULL) uint32[n]: the hit leaf of the last level the state took, in rt1w_hit's convention; 0xFFFFFFFF for a miss, a
+ *             level without depth, a dead state or a ray that is not traced.
+ * `in` and `out` may be the same pointer (a state is read whole before it is written); any other overlap is refused.
+ * RT1W_ERR_INVALID: a null context, params, in or out; n = 0 or n > 2^32 - 1; steps = 0 or steps > 65536; global_seed >= 2^32; flags other
+ * than 0 or RT1W_FORCE_VARIANT(v) with a v that covers the scene; reserved != 0; overlapping buffers; in the device form a state pointer
+ * that is not 16-byte aligned (the host form copies and takes any alignment).  f64 and Philox only: the block has no precision member.
+ * stats: paths = n; segments = levels that traced a ray, counted as rt1w_ray_color counts them; kernel_ms, total_ms, grid, block, variant
+ * as rt1w_hit's.  One lane per state, 64 consecutive states per wave; the list is not reordered.  Bit-identical to the CPU build of the
+ * same code (librt1w_lab.so: rt1w_lab_path_step_host). */
+#define RT1W_PATH_ALIVE 1u
+#define RT1W_PATH_TRACED 2u
+#define RT1W_PATH_EVENT(status) (((status) >> 8) & 0xFFu)
+typedef struct rt1w_path_state {
+    double ray[7];
+    double beta[3];
+    double radiance[3];
+    uint64_t stream;
+    uint32_t sample;
+    uint32_t word;
+    uint32_t depth_left;
+    uint32_t status;
+} rt1w_path_state; /* 128 bytes; rt1w_abi_sizeof(11) */
+typedef struct rt1w_path_params {
+    uint64_t n;           /* states, 1 .. 2^32 - 1 */
+    uint64_t global_seed; /* as rt1w_render_params.global_seed; below 2^32 */
+    uint32_t steps;       /* levels per state at most, 1 .. 65536 */
+    uint32_t flags;       /* 0 or RT1W_FORCE_VARIANT(v) */
+    uint32_t reserved[2]; /* 0 */
+} rt1w_path_params; /* 32 bytes; rt1w_abi_sizeof(10) */
+/* host memory in and out (through the context's device buffers, grown on demand and freed with the context); ray_color, main.rs:51-116 */
+int rt1w_path_step(rt1w_context* c, const rt1w_path_params* params, const rt1w_path_state* in, rt1w_path_state* out,
+                   uint32_t* out_node /* may be NULL */, rt1w_stats* stats);
+/* same, on device memory of the context's GPU (e.g. torch tensors): d_in and d_out n states, 16-byte aligned, d_out_node uint32[n] or
+ * NULL; no host copy.  Synchronises the context's stream before returning.  ray_color, main.rs:51-116 */
+int rt1w_path_step_device(rt1w_context* c, const rt1w_path_params* params, const void* d_in, void* d_out, void* d_out_node /* may be NULL */,
+                          rt1w_stats* stats);
+/* Fresh states from the context's live camera (rt1w_context_set_camera included): for entry r of pixels = {i, j, sample}, Camera::get_ray
+ * (camera.rs:61-73) with the jitter of main.rs:964-971 for that sample of pixel (i, j) of a width x height frame -- the ray rt1w_render
+ * begins that sample with --, beta 1, radiance 0, stream = j * width + i, the sample, word = the stream's position behind get_ray,
+ * depth_left = max_depth, status RT1W_PATH_ALIVE.  begin -> step* -> radiance is that sample of rt1w_render, bit for bit.
+ * RT1W_ERR_INVALID: a null context, pixels or out; width or height below 2 (as a render); n = 0 or n > 2^32 - 1; global_seed >= 2^32; an
+ * entry with i >= width or j >= height (its state, and only its, is written as zeros); out overlapping pixels; in the device form an out
+ * that is not 16-byte aligned.  stats: paths = n, segments = 0.  Bit-identical to librt1w_lab.so's rt1w_lab_path_begin_host */
+int rt1w_path_begin(rt1w_context* c, uint32_t width, uint32_t height, uint64_t global_seed, uint32_t max_depth, const uint32_t* pixels /* [n][3] */,
+                    uint64_t n, rt1w_path_state* out, rt1w_stats* stats);
+/* same, on device memory: d_pixels uint32[n][3], d_out n states, 16-byte aligned.  camera.rs:61-73 */
+int rt1w_path_begin_device(rt1w_context* c, uint32_t width, uint32_t height, uint64_t global_seed, uint32_t max_depth, const void* d_pixels,
+                           uint64_t n, void* d_out, rt1w_stats* stats);
+
 /* ---- feature-guided denoiser: the consumer of the feature buffers above ----
  * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) over an image and its first-hit feature buffers.
  * Replaces nothing of the reference, which reaches a clean image by sample count alone (10 000 spp for final_scene, src/main.rs:939).
@@ -1104,7 +1181,8 @@ int64_t rt1w_format_ppm(const double* means, uint32_t width, uint32_t height, ch
 
 /* sizeof of the ABI structs as this library was compiled (bindings check their own layout against it):
  * 0 rt1w_render_params, 1 rt1w_stats, 2 rt1w_scene_info, 3 rt1w_specialise_info, 4 rt1w_denoise_params, 6 rt1w_camera,
- * 8 rt1w_ray_color_params; 0 for anything else (5 and 7 are not given out: they stay codes that answer 0) */
+ * 8 rt1w_ray_color_params, 10 rt1w_path_params, 11 rt1w_path_state; 0 for anything else (5, 7 and 9 are not given out: they stay codes
+ * that answer 0) */
 uint32_t rt1w_abi_sizeof(int what);
 
 /* ---- diagnostics ---- */

@@ -303,6 +303,23 @@ RAY_RECORD = 7  # rt1w_ray_color: origin xyz, direction xyz, time per ray; a rec
 _sig("rt1w_ray_color", C.c_int, _P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(Stats))
 _sig("rt1w_ray_color_device", C.c_int, _P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(Stats))
 
+
+class PathParams(C.Structure):
+    """rt1w_path_params: n states advanced by up to `steps` levels of ray_color each; the streams take `global_seed`."""
+    _fields_ = [("n", C.c_uint64), ("global_seed", C.c_uint64), ("steps", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+# rt1w_path_state, 128 bytes: the next ray, the path's throughput and radiance so far, its Philox stream and position, the depth left, status
+PATH_STATE = np.dtype([("ray", "<f8", (7,)), ("beta", "<f8", (3,)), ("radiance", "<f8", (3,)), ("stream", "<u8"), ("sample", "<u4"), ("word", "<u4"),
+                       ("depth_left", "<u4"), ("status", "<u4")])
+PATH_ALIVE, PATH_TRACED = 1, 2  # RT1W_PATH_ALIVE, RT1W_PATH_TRACED; the event of the last level: (status >> 8) & 0xFF, a key of PATH_EVENTS
+PATH_EVENTS = {0: "none", 1: "miss", 2: "depth", 3: "light", 4: "absorbed", 5: "lambertian", 6: "metal", 7: "dielectric", 8: "isotropic", 9: "untraced"}
+PATH_NO_NODE = 0xFFFFFFFF  # out_node of a miss, a level without depth, a dead state, a ray that is not traced
+_sig("rt1w_path_step", C.c_int, _P, C.POINTER(PathParams), _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_path_step_device", C.c_int, _P, C.POINTER(PathParams), _P, _P, _P, C.POINTER(Stats))
+_sig("rt1w_path_begin", C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _P, C.c_uint64, _P, C.POINTER(Stats))
+_sig("rt1w_path_begin_device", C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _P, C.c_uint64, _P, C.POINTER(Stats))
+
 _CAM_ARGS = [_D3, _D3, _D3] + [C.c_double] * 6
 _sig("rt1w_reference_camera", C.c_int, C.c_int, _D3, _D3, _D3, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("rt1w_context_set_camera", C.c_int, _P, *_CAM_ARGS)
@@ -337,6 +354,8 @@ if _lib.rt1w_abi_sizeof(6) != C.sizeof(Camera):
     raise ImportError("librt1w.so and this binding disagree on the layout of Camera: rebuild the library")
 if _lib.rt1w_abi_sizeof(8) != C.sizeof(RayColorParams) or C.sizeof(RayColorParams) != 56:
     raise ImportError("librt1w.so and this binding disagree on the layout of RayColorParams: rebuild the library")
+if _lib.rt1w_abi_sizeof(11) != PATH_STATE.itemsize or PATH_STATE.itemsize != 128 or _lib.rt1w_abi_sizeof(10) != C.sizeof(PathParams):
+    raise ImportError("librt1w.so and this binding disagree on the layout of PATH_STATE or PathParams: rebuild the library")
 
 
 # The functions of librt1w_lab.so this binding calls (csrc/walk_lab.h), name -> argtypes; every one returns int.  load_lab applies it.
@@ -352,6 +371,8 @@ _LAB_SIGS = {
     "rt1w_lab_camera_rays_pos_host": [_P, _PR, _P, _P],
     "rt1w_lab_ray_color_host": [_P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(_N)],
     "rt1w_lab_ray_color_counts_host": [_P, C.POINTER(RayColorParams), _P, _P, _P, C.POINTER(_N), _P],
+    "rt1w_lab_path_step_host": [_P, C.POINTER(PathParams), _P, _P, _P, C.POINTER(_N)],
+    "rt1w_lab_path_begin_host": [_P, _U, _U, _N, _U, _P, _N, _P],
     "rt1w_lab_denoise_host": [_PD, _P, _P, _P],
     "rt1w_lab_batch_variance_host": [_U] * 5 + [_P] * 4,
     "rt1w_lab_denoise_var_host": [_PD, _P, _P, _P, _F, _P],
@@ -550,6 +571,46 @@ def _ray_color_prep(rays, start_word, kw):
         raise ValueError("start_word must be [n]")
     out = np.empty((r.shape[0], 3), dtype=np.float64)
     return (_ray_color_params(r.shape[0], stride=r.shape[1], **kw), r, sw, out), out
+
+
+def _path_params(n, steps=1, global_seed=0, variant=None, flags=0):
+    return PathParams(n, global_seed, steps, flags | (0 if variant is None else (variant + 1) << 8), (C.c_uint32 * 2)(0, 0))
+
+
+def _path_states(states):
+    """states: a PATH_STATE array [n], or float64 [n, 16] holding the same 128 bytes per row"""
+    s = np.asarray(states)
+    if s.dtype != PATH_STATE:
+        if s.dtype != np.float64 or s.ndim != 2 or s.shape[1] != 16:
+            raise ValueError("states must be a PATH_STATE array [n] or float64 [n, 16]")
+        s = np.ascontiguousarray(s).view(PATH_STATE)
+    return np.ascontiguousarray(s).reshape(-1)
+
+
+def _path_step_prep(states, steps, global_seed, variant):
+    s = _path_states(states)
+    out = np.empty_like(s)
+    node = np.empty(s.shape[0], dtype=np.uint32)
+    return (_path_params(s.shape[0], steps, global_seed, variant), s, out, node), (out, node)
+
+
+def _path_begin_prep(width, height, pixels, global_seed, max_depth):
+    """pixels [n, 3] = i, j, sample"""
+    px = np.ascontiguousarray(pixels, dtype=np.uint32)
+    if px.ndim != 2 or px.shape[1] != 3:
+        raise ValueError("pixels must be [n, 3] (i, j, sample)")
+    out = np.empty(px.shape[0], dtype=PATH_STATE)
+    return (width, height, global_seed, max_depth, px, px.shape[0], out), out
+
+
+def _path_tensor(t, what):
+    """a torch tensor of path states on a GPU, [n, 16] float64 contiguous: (its address, n).  The entries run on the context's own
+    stream, so what torch has enqueued for the tensor's device -- the gather that compacted the list, say -- is waited for here"""
+    if t.dim() != 2 or t.shape[1] != 16 or str(t.dtype) != "torch.float64" or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError(f"{what} must be a contiguous float64 tensor [n, 16] on the GPU")
+    import torch
+    torch.cuda.current_stream(t.device).synchronize()
+    return t.data_ptr(), t.shape[0]
 
 
 def _denoise_prep(frame, aov, kw):
@@ -1059,6 +1120,44 @@ class Context:
         refusal).  Returns the stats dict."""
         return _call(_lib.rt1w_ray_color_device, self._h, _ray_color_params(n, stride=stride, **kw), d_rays, d_start_word, d_out)
 
+    def path_begin(self, width, height, pixels, global_seed=0, max_depth=50, device=False, out=None, with_stats=False):
+        """Fresh path states from the context's live camera (rt1w_path_begin): pixels [n, 3] = i, j, sample -> a PATH_STATE array [n]
+        holding the camera ray of that sample of pixel (i, j) of a width x height frame, beta 1, radiance 0, the stream and its position
+        behind Camera::get_ray, depth_left = max_depth, status PATH_ALIVE.  device=True: `pixels` is an int32 tensor [n, 3] on the
+        context's GPU, the states come back as a float64 tensor [n, 16] (`out`, or a new one) without a host copy."""
+        if not device:
+            return self._entry(_lib.rt1w_path_begin, _path_begin_prep(width, height, pixels, global_seed, max_depth), with_stats)
+        import torch
+        if pixels.dim() != 2 or pixels.shape[1] != 3 or pixels.element_size() != 4 or not pixels.is_contiguous() or not pixels.is_cuda:
+            raise ValueError("pixels must be a contiguous int32 tensor [n, 3] on the GPU")
+        if out is None:
+            out = torch.empty((pixels.shape[0], 16), dtype=torch.float64, device=pixels.device)
+        d_out, n = _path_tensor(out, "out")
+        if n != pixels.shape[0]:
+            raise ValueError("out must hold one state per pixel")
+        return _ret(out, self.path_begin_device(pixels.data_ptr(), d_out, n, width, height, global_seed, max_depth), with_stats)
+
+    def path_begin_device(self, d_pixels, d_out, n, width, height, global_seed=0, max_depth=50):
+        """rt1w_path_begin_device on raw device addresses: d_pixels n * 3 uint32, d_out n states (16-byte aligned).  Returns the stats."""
+        return _call(_lib.rt1w_path_begin_device, self._h, width, height, global_seed, max_depth, d_pixels, n, d_out)
+
+    def path_step(self, states, steps=1, global_seed=0, variant=None, device=False, nodes=None, with_stats=False):
+        """Path states advanced by up to `steps` levels of ray_color each (rt1w_path_step): states = a PATH_STATE array [n] (or float64
+        [n, 16]).  Returns (the advanced states, uint32 [n] = the hit leaf of each state's last level, PATH_NO_NODE for none); the input
+        is left as it was.  A dead state comes back unchanged.  device=True: `states` is a float64 tensor [n, 16] on the context's GPU
+        and is advanced IN PLACE, taken by pointer (`nodes`: an optional int32 tensor [n] for the leaves); returns the stats."""
+        if not device:
+            return self._entry(_lib.rt1w_path_step, _path_step_prep(states, steps, global_seed, variant), with_stats)
+        d_states, n = _path_tensor(states, "states")
+        if nodes is not None and (nodes.dim() != 1 or nodes.shape[0] != n or nodes.element_size() != 4 or not nodes.is_contiguous() or not nodes.is_cuda):
+            raise ValueError("nodes must be a contiguous int32 tensor [n] on the GPU")
+        return self.path_step_device(d_states, d_states, None if nodes is None else nodes.data_ptr(), n, steps, global_seed, variant)
+
+    def path_step_device(self, d_in, d_out, d_node, n, steps=1, global_seed=0, variant=None):
+        """rt1w_path_step_device on raw device addresses: d_in, d_out n states (16-byte aligned; the same address or apart), d_node None
+        or n uint32.  Returns the stats."""
+        return _call(_lib.rt1w_path_step_device, self._h, _path_params(n, steps, global_seed, variant), d_in, d_out, d_node)
+
     def hit_device(self, d_rays, d_out, d_node, n, first_stream=0, sample=0, global_seed=0, variant=None):
         """Same on device memory (int addresses, e.g. torch tensors' .data_ptr()): d_rays n * 9 float64 with the bounds in, d_out n * 12
         float64, d_node n uint32 or None; returns the stats dict."""
@@ -1449,6 +1548,22 @@ def ray_color_host(scene, rays, start_word=None, with_stats=False, **kw):
     per_ray = np.zeros(out.shape[0], dtype=np.uint32)
     _twin("rt1w_lab_ray_color_counts_host", ((scene._h, *args), out), C.byref(seg), per_ray, says_why=True)
     return out, {"segments": seg.value, "ray_segments": per_ray}
+
+
+def path_step_host(scene, states, steps=1, global_seed=0, variant=None, with_stats=False):
+    """CPU twin of Context.path_step (librt1w_lab.so: rt1w_lab_path_step_host, rt_path_state.h and rt_core.h built for the host): the
+    (states, nodes) the GPU must equal bit for bit; with_stats: + {"segments": levels that traced a ray}.  No GPU needed.  This twin says
+    why it refuses a call, as the entries do."""
+    args, out = _path_step_prep(states, steps, global_seed, variant)
+    seg = C.c_uint64()
+    _twin("rt1w_lab_path_step_host", ((scene._h, *args), out), C.byref(seg), says_why=True)
+    return out + ({"segments": seg.value},) if with_stats else out
+
+
+def path_begin_host(scene, width, height, pixels, global_seed=0, max_depth=50):
+    """CPU twin of Context.path_begin (librt1w_lab.so: rt1w_lab_path_begin_host) over the scene's own camera.  No GPU needed."""
+    args, out = _path_begin_prep(width, height, pixels, global_seed, max_depth)
+    return _twin("rt1w_lab_path_begin_host", ((scene._h, *args), out), says_why=True)
 
 
 def guides_merge_tiles_host(gacc, tile_sums, spp, tile, tiles):

@@ -1,4 +1,4 @@
-/* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip, aov_tiles.hip) and of the ray-query kernels (hit.hip) and the ray-list form of the render kernels (context_rays.hip): rt_aov.h, rt_aov_deep.h, rt_aov_tiles.h and rt_hit.h compiled for the host (g++, -ffp-contract=off
+/* aov_host.cpp -- the CPU twin of the AOV kernels (aov.hip, aov_tiles.hip) and of the ray-query kernels (hit.hip) and the ray-list form of the render kernels (context_rays.hip) and of the path-state kernels (path_step.hip): rt_aov.h, rt_aov_deep.h, rt_aov_tiles.h, rt_hit.h and rt_path_state.h compiled for the host (g++, -ffp-contract=off
  * like every build of the core) and run over a committed scene's flat arrays.  Diagnostics library only (librt1w_lab.so): the expected side of the GPU
  * tests' bit-equality checks and of the CPU tier's checks against the literal oracle.  librt1w.so keeps no CPU render path. */
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include "rt_aov_tiles.h"
 #include "rt_hit.h"
 #include "rt_ray_list.h"
+#include "rt_path_state.h"
 #include "walk_lab.h"
 
 namespace {
@@ -177,7 +178,66 @@ bool ray_color_rays(const RtSceneView& sc, const RtFrame& f, const RtRayList& rl
     }
     return true;
 }
+
+/* states k0, k0 + step, .. of a list by rt_state_advance, as the step kernel's lanes run them; a state is copied whole before it is
+ * written, so `in` may be `out` */
+template <class Cfg>
+bool path_states(const RtSceneView& sc, const RtPathParams& pp, uint64_t k0, uint64_t step, const RtPathState* in, RtPathState* out, uint32_t* out_node,
+                 uint64_t* segments) {
+    AovHostStack stk;
+    RtGlobalNodes ns{sc.nodes};
+    for (uint64_t r = k0; r < pp.n; r += step) {
+        RtPathState s;
+        memcpy(&s, (const char*)in + r * sizeof s, sizeof s); /* the caller's states may have any alignment */
+        uint32_t node;
+        *segments += rt_state_advance<Cfg>(sc, ns, (uint32_t)pp.global_seed, pp.steps, s, stk, node);
+        if (stk.overflow) return false;
+        memcpy((char*)out + r * sizeof s, &s, sizeof s);
+        if (out_node) out_node[r] = node;
+    }
+    return true;
+}
 } // namespace
+
+extern "C" int rt1w_lab_path_step_host(const rt1w_scene* s, const rt1w_path_params* p, const rt1w_path_state* in, rt1w_path_state* out, uint32_t* out_node,
+                                       uint64_t* segments) {
+    static_assert(sizeof(rt1w_path_params) == sizeof(RtPathParams) && sizeof(rt1w_path_state) == sizeof(RtPathState), "the path blocks are the kernels' layouts");
+    if (!s || !s->committed) { rt1w_internal_set_error("null or uncommitted scene"); return RT1W_ERR_INVALID; }
+    if (const char* why = rt_path_step_refusal((const RtPathParams*)p, in, out, out_node, false)) { /* the entries' own check */
+        rt1w_internal_set_error(why); return RT1W_ERR_INVALID;
+    }
+    RtPathParams pp;
+    memcpy(&pp, p, sizeof pp);
+    std::vector<RtNode> nodes;
+    RtSceneView sc;
+    int v;
+    if (!host_view(s, p->flags, nodes, sc, v)) { rt1w_internal_set_error("path_step: the forced variant does not cover the scene"); return RT1W_ERR_INVALID; }
+    uint64_t segs[MAX_THREADS] = {}; /* per thread */
+    const bool ok = round_robin((uint32_t)pp.n, [&](uint32_t t, uint32_t n_threads) { /* the list's states */
+        return with_variant(v, [&](auto cfg) {
+            return path_states<decltype(cfg)>(sc, pp, t, n_threads, (const RtPathState*)in, (RtPathState*)out, out_node, &segs[t]);
+        });
+    });
+    if (!ok) return RT1W_ERR_STATE;
+    if (segments) { *segments = 0u; for (uint64_t k : segs) *segments += k; }
+    return RT1W_OK;
+}
+
+extern "C" int rt1w_lab_path_begin_host(const rt1w_scene* s, uint32_t width, uint32_t height, uint64_t global_seed, uint32_t max_depth, const uint32_t* pixels,
+                                        uint64_t n, rt1w_path_state* out) {
+    if (!s || !s->committed) { rt1w_internal_set_error("null or uncommitted scene"); return RT1W_ERR_INVALID; }
+    if (const char* why = rt_path_begin_refusal(width, height, global_seed, pixels, n, out, false)) { rt1w_internal_set_error(why); return RT1W_ERR_INVALID; }
+    RtPathBeginParams bp;
+    bp.n = n; bp.width = width; bp.height = height; bp.global_seed = (uint32_t)global_seed; bp.max_depth = max_depth;
+    bool inside = true;
+    for (uint64_t r = 0; r < n; ++r) {
+        RtPathState st;
+        inside &= rt_state_begin(s->camera, bp, pixels + r * 3u, st);
+        memcpy((char*)out + r * sizeof st, &st, sizeof st);
+    }
+    if (!inside) { rt1w_internal_set_error("path_begin: a pixel of the list lies outside the frame (i >= width or j >= height)"); return RT1W_ERR_INVALID; }
+    return RT1W_OK;
+}
 
 extern "C" int rt1w_lab_ray_color_counts_host(const rt1w_scene* s, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out,
                                               uint64_t* segments, uint32_t* ray_segments) {

@@ -8,7 +8,11 @@
  *        [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]]
  *        [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]]
  *        [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]]
- *        [--pick I J] [--panorama W H]
+ *        [--pick I J] [--panorama W H] [--trace-path I J [S]]
+ * --trace-path I J [S] renders nothing: it follows sample S (default 0) of pixel (I, J), J counting the reference's rows j, one level of
+ * ray_color at a time (main.rs:51-116) -- rt1w_path_begin for the one state, then rt1w_path_step with n = 1, steps = 1 until the state is
+ * dead -- and prints per level the event, the hit leaf's node, the next ray, beta, radiance and the stream word.  The last radiance is
+ * that pixel sample of rt1w_render (spp 1, sample_offset S, RT1W_OUT_SUM).  --depth and --seed as for a render.
  * --panorama W H renders an equirectangular 360 x 180 degree image of W x H pixels from the arm's look_from through rt1w_ray_color: the
  * camera is a few lines of host code.  Pixel (i, j), j counting rows from the bottom, looks along longitude phi = 2 pi (i + 1/2) / W - pi
  * + phi0 and latitude theta = pi (j + 1/2) / H - pi / 2: direction (cos theta sin phi, sin theta, -cos theta cos phi), time 0.  phi0 =
@@ -74,6 +78,7 @@ int main(int argc, char** argv) {
     std::string err_path;
     long pick_i = -1, pick_j = -1;   /* >= 0: --pick, the record under a pixel instead of a render */
     long pano_w = 0, pano_h = 0;     /* > 0: --panorama, an equirectangular image through rt1w_ray_color */
+    long trace_i = -1, trace_j = -1, trace_s = 0; /* >= 0: --trace-path, one path level by level instead of a render */
     long frames = 0;                 /* > 0: an animation through rt1w_render_temporal */
     double orbit = 0.0;
     double temporal_variance = -1.0; /* >= 0: the frames through rt1w_render_temporal_var with this sigma_variance (0 = default) */
@@ -123,6 +128,10 @@ int main(int argc, char** argv) {
         else if (a == "--frames") frames = std::atol(next("--frames"));
         else if (a == "--pick") { pick_i = std::atol(next("--pick I")); pick_j = std::atol(next("--pick J")); }
         else if (a == "--panorama") { pano_w = std::atol(next("--panorama W")); pano_h = std::atol(next("--panorama H")); }
+        else if (a == "--trace-path") {
+            trace_i = std::atol(next("--trace-path I")); trace_j = std::atol(next("--trace-path J"));
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') trace_s = std::atol(argv[++i]);
+        }
         else if (a == "--temporal-variance") {
             temporal_variance = 0.0;
             if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) temporal_variance = std::atof(argv[++i]);
@@ -131,7 +140,7 @@ int main(int argc, char** argv) {
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--target-error") target_error = std::atof(next("--target-error"));
         else if (a == "--earth") { earth_path = next("--earth"); earth_w = (unsigned)std::atoi(next("--earth W")); earth_h = (unsigned)std::atoi(next("--earth H")); }
-        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]] [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]] [--pick I J] [--panorama W H]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: rt1w [--scene N] [--width W] [--height H] [--spp S] [--depth D] [--seed G] [--build-seed B] [--device I] [--earth file.rgb8 W H] [--out file.ppm] [--specialise | --generic] [--reference-stream] [--f32] [--near-far] [--sah] [--denoise [--denoise-iterations N] [--deep-guides [N]] [--variance [K]]] [--adaptive BUDGET [--max-spp N] [--target-error E] [--one-launch] [--filtered-error [--full-guides] | --cross-filter [--err-out FILE]] [--specialised-tiles]] [--frames N --orbit DEG [--denoise [--temporal-variance [SIGMA]]]] [--pick I J] [--panorama W H] [--trace-path I J [S]]\n"); return 2; }
     }
     std::vector<unsigned char> earth;
     if (!earth_path.empty()) {
@@ -185,6 +194,36 @@ int main(int argc, char** argv) {
         else
             std::printf("hit\nt %.17g\np %.17g %.17g %.17g\nnormal %.17g %.17g %.17g\nu %.17g\nv %.17g\nfront_face %d\nmaterial %u\nnode %u\n", rec[1], rec[2],
                         rec[3], rec[4], rec[5], rec[6], rec[7], rec[8], rec[9], (int)rec[10], (unsigned)rec[11], node);
+        rt1w_context_destroy(ctx);
+        rt1w_scene_destroy(scene);
+        return 0;
+    }
+    if (trace_i >= 0 || trace_j >= 0) {
+        if (trace_i < 0 || trace_j < 0 || trace_i >= width || trace_j >= height || trace_s > 0xFFFFFFFEl) { std::fprintf(stderr, "rt1w: --trace-path I J [S]: a pixel of the %ldx%ld frame\n", width, height); return 2; }
+        static const char* const events[] = {"none", "miss", "depth exhausted", "DiffuseLight", "() absorbed", "Lambertian", "Metal", "Dielectric", "Isotropic", "not traced"};
+        const uint32_t pixel[3] = {(uint32_t)trace_i, (uint32_t)trace_j, (uint32_t)trace_s};
+        rt1w_path_state st;
+        rt1w_stats ps;
+        if (rt1w_path_begin(ctx, (uint32_t)width, (uint32_t)height, (uint64_t)(uint32_t)seed, (uint32_t)depth, pixel, 1u, &st, &ps) < 0) return fail("trace-path");
+        rt1w_path_params pp;
+        std::memset(&pp, 0, sizeof pp);
+        pp.n = 1u; pp.global_seed = (uint32_t)seed; pp.steps = 1u;
+        const auto print_state = [&st]() {
+            std::printf("  ray %.17g %.17g %.17g  %.17g %.17g %.17g  time %.17g\n  beta %.17g %.17g %.17g\n  radiance %.17g %.17g %.17g\n  word %u  depth_left %u\n",
+                        st.ray[0], st.ray[1], st.ray[2], st.ray[3], st.ray[4], st.ray[5], st.ray[6], st.beta[0], st.beta[1], st.beta[2], st.radiance[0],
+                        st.radiance[1], st.radiance[2], st.word, st.depth_left);
+        };
+        std::printf("pixel %ld %ld sample %ld stream %llu\nlevel 0: camera\n", trace_i, trace_j, trace_s, (unsigned long long)st.stream);
+        print_state();
+        for (long level = 1; st.status & RT1W_PATH_ALIVE; ++level) {
+            uint32_t node;
+            if (rt1w_path_step(ctx, &pp, &st, &st, &node, &ps) < 0) return fail("trace-path");
+            const uint32_t ev = RT1W_PATH_EVENT(st.status);
+            std::printf("level %ld: %s", level, ev < 10u ? events[ev] : "?");
+            if (node != 0xFFFFFFFFu) std::printf(", node %u", node);
+            std::printf("%s\n", (st.status & RT1W_PATH_ALIVE) ? "" : ", the path ends");
+            print_state();
+        }
         rt1w_context_destroy(ctx);
         rt1w_scene_destroy(scene);
         return 0;

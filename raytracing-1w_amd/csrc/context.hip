@@ -1045,6 +1045,8 @@ uint32_t rt1w_abi_sizeof(int what) {
         case 4: return (uint32_t)sizeof(rt1w_denoise_params);
         case 6: return (uint32_t)sizeof(rt1w_camera);
         case 8: return (uint32_t)sizeof(rt1w_ray_color_params);
+        case 10: return (uint32_t)sizeof(rt1w_path_params);
+        case 11: return (uint32_t)sizeof(rt1w_path_state);
         default: return 0u;
     }
 }

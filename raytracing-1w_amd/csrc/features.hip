@@ -15,6 +15,7 @@
 #include "rt_aov_deep.h" /* rt_aov_deep_args_ok only */
 #include "rt_hit.h" /* RtHitParams, rt_hit_refusal only */
 #include "rt_ray_list.h" /* RtRayColorParams, rt_ray_color_refusal only */
+#include "rt_path_state.h" /* RtPathParams, RtPathState, rt_path_step_refusal, rt_path_begin_refusal only */
 #include "rt_denoise_var.h" /* rt_dv_batches_ok, rt_dv_sigma, rt_dv_split only */
 #include "rt_adaptive_plan.h" /* the plan of rt1w_render_adaptive and rt1w_adaptive_select; rt_ad_*_ok of rt_adaptive.h; the tile lists' checks */
 #include "rt_guides.h" /* RT_GD_RECORD only */
@@ -233,6 +234,83 @@ int ray_color(rt1w_context* c, const rt1w_ray_color_params* p, const void* rays,
         if (host && start_word && !hip_ok(hipMemcpy(s[2].d_out, start_word, word_bytes, hipMemcpyHostToDevice), "start word copy")) return (int)RT1W_ERR_DEVICE;
         return ray_color_common(c, &q, rl, s[1].d_out, st);
     });
+}
+
+/* ---- path states (include/rt1w.h: rt1w_path_step, rt1w_path_begin) ---- */
+static_assert(sizeof(rt1w_path_params) == sizeof(RtPathParams) && sizeof(RtPathParams) == 32, "rt1w_path_params is RtPathParams' layout");
+static_assert(sizeof(rt1w_path_state) == sizeof(RtPathState), "rt1w_path_state is RtPathState's layout");
+constexpr size_t PATH_STATE_DOUBLES = sizeof(RtPathState) / sizeof(double);
+/* One launch of path_step.hip through lane_run with the lane's second counter -- the one the render kernels count their segments in --
+ * zeroed in front of the lane's two events and read behind them (render_aov_common does the same for the deep kernel): *count = what
+ * the kernel added to it */
+template <class Enqueue>
+int path_counted_run(rt1w_context* c, uint64_t n, const char* what, rt1w_stats* st, unsigned long long* count, Enqueue enqueue) {
+    if (rt1w_internal_path_sizeof(0) != sizeof(RtSceneView) || rt1w_internal_path_sizeof(1) != sizeof(rt1w_path_params) ||
+        rt1w_internal_path_sizeof(2) != sizeof(rt1w_path_state)) {
+        set_error("path-state kernels built against another scene layout"); return RT1W_ERR_DEVICE;
+    }
+    RtLane& l = c->lane[0];
+    unsigned long long* d_count = l.d_counters + 1;
+    if (!hip_ok(hipMemsetAsync(d_count, 0, sizeof *d_count, l.stream), "path-state counter")) return RT1W_ERR_DEVICE;
+    const int r = lane_run(c, n, what, st, [&](hipStream_t stream, unsigned* launch) { return enqueue(d_count, stream, launch); });
+    if (r < 0) return r;
+    if (!(hip_ok(hipMemcpyAsync(l.h_counters + 1, d_count, sizeof *d_count, hipMemcpyDeviceToHost, l.stream), "path-state counter copy") &&
+          hip_ok(hipStreamSynchronize(l.stream), "path-state counter copy")))
+        return RT1W_ERR_DEVICE; /* on the lane's own stream: no other stream of the device is waited for */
+    *count = l.h_counters[1];
+    st->chunk = 1u; st->n_chunks = 1u;
+    return RT1W_OK;
+}
+/* the two step entries.  The buffers are device memory, or (host) host memory, passed through the context's framebuffer, where the states
+ * have one place: the kernel advances them where they lie */
+int path_step(rt1w_context* c, const rt1w_path_params* p, const void* in, void* out, void* out_node, bool host, rt1w_stats* stats) {
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (const char* why = rt_path_step_refusal((const RtPathParams*)p, in, out, out_node, !host)) { set_error(why); return RT1W_ERR_INVALID; }
+    int variant = c->variant;
+    const int rc = forced_variant(c, p->flags, true, &variant);
+    if (rc < 0) return rc;
+    const uint64_t node_bytes = p->n * sizeof(uint32_t);
+    /* host: the caller's states may have any alignment, they are copied as bytes; the node indices are 4 bytes each, staged as room of
+     * whole doubles and copied out here in their own size */
+    Staged s[] = {{(const double*)in, (double*)out, (size_t)p->n * PATH_STATE_DOUBLES, FRAMEBUFFER, "path state copy", "path state copy"},
+                  {nullptr, nullptr, host && out_node ? (size_t)((p->n + 1u) / 2u) : 0u, FRAMEBUFFER, nullptr, nullptr}};
+    return staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
+        uint32_t* d_node = host ? (out_node ? (uint32_t*)s[1].d_out : nullptr) : (uint32_t*)out_node;
+        unsigned long long segments = 0u;
+        const int r = path_counted_run(c, p->n, "path step", st, &segments, [&](unsigned long long* d_count, hipStream_t stream, unsigned* launch) {
+            return rt1w_internal_path_step_launch(&c->view, p, variant, s[0].d_in, s[0].d_out, d_node, d_count, stream, launch);
+        });
+        if (r < 0) return r;
+        st->segments = segments;
+        st->variant = (uint32_t)variant;
+        if (host && out_node && !hip_ok(hipMemcpy(out_node, d_node, node_bytes, hipMemcpyDeviceToHost), "node index copy")) return (int)RT1W_ERR_DEVICE;
+        return (int)RT1W_OK;
+    });
+}
+/* the two begin entries: the states first in the framebuffer (16-byte aligned there), the list behind them in its own size */
+int path_begin(rt1w_context* c, uint32_t width, uint32_t height, uint64_t global_seed, uint32_t max_depth, const void* pixels, uint64_t n, void* out,
+               bool host, rt1w_stats* stats) {
+    if (!c) { set_error("null argument"); return RT1W_ERR_INVALID; }
+    if (const char* why = rt_path_begin_refusal(width, height, global_seed, pixels, n, out, !host)) { set_error(why); return RT1W_ERR_INVALID; }
+    const uint64_t pixel_bytes = n * 3u * sizeof(uint32_t);
+    Staged s[] = {{nullptr, (double*)out, (size_t)n * PATH_STATE_DOUBLES, FRAMEBUFFER, nullptr, "path state copy"},
+                  {nullptr, nullptr, host ? (size_t)((n * 3u + 1u) / 2u) : 0u, FRAMEBUFFER, nullptr, nullptr}};
+    bool outside_frame = false;
+    const int rc = staged_entry(c, host, s, stats, [&](rt1w_stats* st) {
+        const uint32_t* d_pixels = host ? (const uint32_t*)s[1].d_out : (const uint32_t*)pixels;
+        if (host && !hip_ok(hipMemcpy(s[1].d_out, pixels, pixel_bytes, hipMemcpyHostToDevice), "pixel list copy")) return (int)RT1W_ERR_DEVICE;
+        unsigned long long outside = 0u;
+        const int r = path_counted_run(c, n, "path begin", st, &outside, [&](unsigned long long* d_count, hipStream_t stream, unsigned* launch) {
+            return rt1w_internal_path_begin_launch(&c->view, width, height, (uint32_t)global_seed, max_depth, d_pixels, n, s[0].d_out, d_count, stream, launch);
+        });
+        if (r < 0) return r;
+        outside_frame = outside != 0u;
+        st->variant = (uint32_t)c->variant;
+        return (int)RT1W_OK;
+    });
+    if (rc < 0) return rc;
+    if (outside_frame) { set_error("path_begin: a pixel of the list lies outside the frame (i >= width or j >= height)"); return RT1W_ERR_INVALID; }
+    return RT1W_OK;
 }
 
 /* ---- feature-guided denoiser (include/rt1w.h: rt1w_denoise) ---- */
@@ -1192,6 +1270,14 @@ int rt1w_hit(rt1w_context* c, const rt1w_hit_params* p, const double* rays, doub
 int rt1w_hit_device(rt1w_context* c, const rt1w_hit_params* p, const void* d_rays, void* d_out, void* d_out_node, rt1w_stats* stats) { return hit(c, p, d_rays, d_out, d_out_node, false, stats); }
 int rt1w_ray_color(rt1w_context* c, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out, rt1w_stats* stats) { return ray_color(c, p, rays, start_word, out, true, stats); }
 int rt1w_ray_color_device(rt1w_context* c, const rt1w_ray_color_params* p, const void* d_rays, const void* d_start_word, void* d_out, rt1w_stats* stats) { return ray_color(c, p, d_rays, d_start_word, d_out, false, stats); }
+int rt1w_path_step(rt1w_context* c, const rt1w_path_params* p, const rt1w_path_state* in, rt1w_path_state* out, uint32_t* out_node, rt1w_stats* stats) { return path_step(c, p, in, out, out_node, true, stats); }
+int rt1w_path_step_device(rt1w_context* c, const rt1w_path_params* p, const void* d_in, void* d_out, void* d_out_node, rt1w_stats* stats) { return path_step(c, p, d_in, d_out, d_out_node, false, stats); }
+int rt1w_path_begin(rt1w_context* c, uint32_t width, uint32_t height, uint64_t global_seed, uint32_t max_depth, const uint32_t* pixels, uint64_t n, rt1w_path_state* out, rt1w_stats* stats) {
+    return path_begin(c, width, height, global_seed, max_depth, pixels, n, out, true, stats);
+}
+int rt1w_path_begin_device(rt1w_context* c, uint32_t width, uint32_t height, uint64_t global_seed, uint32_t max_depth, const void* d_pixels, uint64_t n, void* d_out, rt1w_stats* stats) {
+    return path_begin(c, width, height, global_seed, max_depth, d_pixels, n, d_out, false, stats);
+}
 int rt1w_denoise(rt1w_context* c, const rt1w_denoise_params* p, const double* frame, const double* aov, double* out, rt1w_stats* stats) { return denoise(c, p, frame, aov, out, true, stats); }
 int rt1w_denoise_device(rt1w_context* c, const rt1w_denoise_params* p, const void* d_frame, const void* d_aov, void* d_out, rt1w_stats* stats) {
     return denoise(c, p, (const double*)d_frame, (const double*)d_aov, (double*)d_out, false, stats);

@@ -1,4 +1,4 @@
-/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip, temporal.hip, temporal_var.hip and hit.hip, declared once.
+/* rt_feature_launch.h -- what features.hip calls in the kernel units aov.hip, aov_tiles.hip, guides.hip, denoise.hip, denoise_var.hip, denoise_halves.hip, denoise_cross.hip, adaptive.hip, temporal.hip, temporal_var.hip, hit.hip and path_step.hip, declared once.
  * The functions are extern "C": nothing in their names says what they take, so caller and definition both include this header and the
  * compiler holds each definition to the declaration the caller sees.  Private (librt1w.map exports none of them).
  * Every kernel is reached through a typed *_launch: no kernel handle leaves its unit, and no argument array is built by hand.  The
@@ -91,6 +91,16 @@ unsigned rt1w_internal_temporal_var_sizeof(void);
 int rt1w_internal_hit_launch(const void* view, const void* params, int variant, const double* rays, double* out, uint32_t* out_node,
                              hipStream_t stream, unsigned launch[2]);
 unsigned rt1w_internal_hit_sizeof(int what);
+/* path_step.hip: the path states (rt1w_path_step, rt1w_path_begin).  The step kernel of `variant` over the params->n states of `in` into `out`
+ * (the same buffer or apart; out_node unless null), all device memory, the states 16-byte aligned; `view` and `params` by address: the bytes
+ * of an RtSceneView and an rt1w_path_params, rt1w_internal_path_sizeof(0) and (1) of them; *segments, zeroed by the caller, receives the
+ * levels that traced a ray.  The begin kernel over n entries {i, j, sample} with the camera of `view`; *outside, zeroed by the caller,
+ * receives the entries whose pixel is outside the frame.  rt1w_internal_path_sizeof(2): bytes of a state, (3): waves per SIMD of the build */
+int rt1w_internal_path_step_launch(const void* view, const void* params, int variant, const void* in, void* out, uint32_t* out_node,
+                                   unsigned long long* segments, hipStream_t stream, unsigned launch[2]);
+int rt1w_internal_path_begin_launch(const void* view, uint32_t width, uint32_t height, uint32_t global_seed, uint32_t max_depth, const uint32_t* pixels,
+                                    uint64_t n, void* out, unsigned long long* outside, hipStream_t stream, unsigned launch[2]);
+unsigned rt1w_internal_path_sizeof(int what);
 }
 
 #endif

@@ -66,6 +66,17 @@ int rt1w_lab_ray_color_host(const rt1w_scene* s, const rt1w_ray_color_params* p,
 int rt1w_lab_ray_color_counts_host(const rt1w_scene* s, const rt1w_ray_color_params* p, const double* rays, const uint32_t* start_word, double* out,
                                    uint64_t* segments, uint32_t* ray_segments);
 
+/* CPU twin of rt1w_path_step (aov_host.cpp: rt_path_state.h and rt_core.h built for the host): the same out[n] and out_node[n] (may be
+ * null) for a committed scene, same variant choice (or p->flags' RT1W_FORCE_VARIANT), no GPU; `in` may be `out`, and neither needs an
+ * alignment.  *segments (may be null) = the levels that traced a ray (rt1w_stats.segments of the entries).  RT1W_OK, RT1W_ERR_INVALID with
+ * the entries' own text (rt_path_step_refusal), RT1W_ERR_STATE if a traversal stack overflowed */
+int rt1w_lab_path_step_host(const rt1w_scene* s, const rt1w_path_params* p, const rt1w_path_state* in, rt1w_path_state* out, uint32_t* out_node,
+                            uint64_t* segments);
+/* CPU twin of rt1w_path_begin (aov_host.cpp: rt_state_begin of rt_path_state.h built for the host) over the scene's own camera, which
+ * rt1w_lab_scene_set_camera moves as rt1w_context_set_camera moves a context's; refusals and texts of the entries */
+int rt1w_lab_path_begin_host(const rt1w_scene* s, uint32_t width, uint32_t height, uint64_t global_seed, uint32_t max_depth, const uint32_t* pixels,
+                             uint64_t n, rt1w_path_state* out);
+
 /* CPU twin of rt1w_denoise (denoise_host.cpp: rt_denoise.h built for the host): the same double[h][w][3] from host buffers, no GPU.
  * RT1W_OK, or RT1W_ERR_INVALID as the device entry (null pointers, zero sizes, iterations > 8, unknown flags, bad sigmas) */
 int rt1w_lab_denoise_host(const rt1w_denoise_params* p, const double* frame, const double* aov, double* out);
